@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the Aliengo hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--task aliengo] [--mode train|env]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--task aliengo] [--mode train|env] [--full] [--dump-outputs DIR]
 
 One "step" = one LeggedRobot.step() over the whole batch of envs of a rank (4 physics sub-steps + post-physics +
 reset + observations), driven the way the reference's runner drives it (HIMR:105-157).  Prints ONE JSON line from rank 0.
 
 --mode train (default) is the reference's `Perf/total_fps` (HIMR:179): value = N * T * iterations / (collection + learn).  The timed
-region always consists of WHOLE PPO iterations -- max(5, ceil(K / T)) of them, T = num_steps_per_env = 100 -- each one = T x {policy
-inference + step + storage} + compute_returns + update(); `steps` echoes the request, `timed_env_steps` says what was timed.
+region always consists of WHOLE PPO iterations -- ceil(K / T) of them, T = num_steps_per_env = 100, so K steps exactly when K is a
+multiple of T -- each one = T x {policy inference + step + storage} + compute_returns + update(); `steps` echoes the request,
+`timed_env_steps` says what was timed and `ms_per_step` is the time of one timed env-step.
 --mode env times step() back-to-back with pre-generated actions (exactly K steps), no learner.
+
+A plain run sets up, warms up, times the steps and prints the headline.  Everything else the line can carry -- the CPU baseline
+(oracle/cpu_bench.py, unless --no-cpu-baseline), the per-kernel profile and roofline, the shader clock, the GEMM-rate and copy-rate
+probes, the TunableOp report and the per-rank diagnostics of an N > 1 run -- is measured only with --full.
+--dump-outputs DIR writes what the timed path computed in its last step (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB
+(a fixed, seeded sample of the env rows beyond that, the rows in env_rows.npy); the inputs are seeded, identical from run to run.
 
 Multi-GPU: one process per GPU, environments sharded with no data-path collective (weak scaling); in train mode the PPO
 gradients are all-reduced over RCCL.  `python bench.py --gpus N` (no torchrun) starts the N rank processes itself, before
@@ -277,6 +284,29 @@ def gemm_probe(torch, dev, seconds=0.02):
         return {"tflops": None, "error": f"{type(e).__name__}: {e}"}
 
 
+def dump_outputs(outputs, out_dir, n_envs, limit=64 << 20):
+    """outputs {name: tensor / array} -> out_dir/<name>.npy in float32 (float64 stays float64); past `limit` bytes in all, the arrays with
+    one row per env keep the same fixed, seeded sample of rows, listed in env_rows.npy"""
+    import numpy as np
+    arrs = {}
+    for k, v in outputs.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrs[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    per_env = [k for k, a in arrs.items() if a.ndim >= 1 and a.shape[0] == n_envs]
+    total = sum(a.nbytes for a in arrs.values())
+    if total > limit and per_env:
+        row_bytes = sum(arrs[k].nbytes // n_envs for k in per_env)
+        fixed = total - row_bytes * n_envs + 8 * n_envs          # (+ the row index itself, float64)
+        keep = int(max(1, min(n_envs, (limit - fixed) // (row_bytes + 8))))
+        rows = np.sort(np.random.RandomState(0).choice(n_envs, keep, replace=False))
+        for k in per_env:
+            arrs[k] = arrs[k][rows]
+        arrs["env_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -285,7 +315,11 @@ def parse_args():
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--task", default="aliengo")
     ap.add_argument("--mode", default="train", choices=["env", "train"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, kernel profile and roofline, clock and rate probes, per-rank diagnostics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--actions", default="normal", choices=["normal", "zeros"],
                     help="env mode action source (SURVEY.md 8d): N(0,1) = an untrained policy (init_noise_std 1), or zeros = standing robots")
     ap.add_argument("--mixed-robots", action="store_true",
@@ -330,7 +364,7 @@ def main():
 
     # CPU baseline first: a child process on the host cores, while this process has not initialised the GPU yet (rank 0 at N = 1 only)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.task)
         except Exception as e:  # the baseline is a reported extra, never the thing measured
@@ -408,7 +442,8 @@ def main():
             acts = [torch.zeros(N, 12, device=dev)] * 16
         for i in range(W):
             env.step_device(acts[i % 16])
-        env._L.lsim_set_profiling(env._h, K)
+        if args.full:
+            env._L.lsim_set_profiling(env._h, K)
         barrier()
         nf0 = int(env.nonfinite_envs)            # (a host read: outside the timed region)
         t0 = time.perf_counter()
@@ -418,13 +453,17 @@ def main():
         elapsed = time.perf_counter() - t0
         nonfinite = int(env.nonfinite_envs) - nf0
         timed_steps = K
-        ms_a = (ctypes.c_float * K)()
-        ms_b = (ctypes.c_float * K)()
-        n = ctypes.c_int(K)
-        env._L.lsim_read_profile(env._h, ms_a, ms_b, ctypes.byref(n))
-        ka = sum(ms_a[i] for i in range(n.value)) / max(n.value, 1)
-        kb = sum(ms_b[i] for i in range(n.value)) / max(n.value, 1)
-        extra = {"kernel_a_ms": ka, "kernel_b_ms": kb, "timed_env_steps": K, "nonfinite_envs": nonfinite}
+        from isaacgymloco_amd.learn.bench_train import env_outputs
+        outputs = env_outputs(env)
+        extra = {"timed_env_steps": K, "nonfinite_envs": nonfinite}
+        if args.full:
+            ms_a = (ctypes.c_float * K)()
+            ms_b = (ctypes.c_float * K)()
+            n = ctypes.c_int(K)
+            env._L.lsim_read_profile(env._h, ms_a, ms_b, ctypes.byref(n))
+            ka = sum(ms_a[i] for i in range(n.value)) / max(n.value, 1)
+            kb = sum(ms_b[i] for i in range(n.value)) / max(n.value, 1)
+            extra.update(kernel_a_ms=ka, kernel_b_ms=kb)
         actions_src = args.actions
         workload = (f"{args.task}: LeggedRobot.step() back-to-back, {'N(0,1)' if args.actions == 'normal' else 'zero'} actions, {N} envs/GPU "
                     "(no policy/learner in the loop)")
@@ -435,13 +474,14 @@ def main():
             pci = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
         except AttributeError:
             pci = "unknown"
-        clocks = ClockSampler(pci)
-        elapsed, extra, workload = run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=clocks)
-        extra["gemm_probe_after_timed_region"] = gemm_probe(torch, dev)
-        extra["gpu_max_hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "unset (runtime default 4)")
-        extra["host"] = host
-        extra["device"] = {"name": pr.name, "compute_units": pr.multi_processor_count, "pci": pci, "arch": getattr(pr, "gcnArchName", None)}
-        ka = extra["kernel_a_ms"]
+        clocks = ClockSampler(pci) if args.full else None
+        elapsed, extra, workload, outputs = run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=clocks, full=args.full)
+        if args.full:
+            extra["gemm_probe_after_timed_region"] = gemm_probe(torch, dev)
+            extra["gpu_max_hw_queues"] = os.environ.get("GPU_MAX_HW_QUEUES", "unset (runtime default 4)")
+            extra["host"] = host
+            extra["device"] = {"name": pr.name, "compute_units": pr.multi_processor_count, "pci": pci, "arch": getattr(pr, "gcnArchName", None)}
+            ka = extra["kernel_a_ms"]
         timed_steps = extra["timed_env_steps"]
         actions_src = "policy"
 
@@ -457,8 +497,23 @@ def main():
         # is then not a measurement of the workload (non-finite robots also run slower: until round 6 this was only noticed as a slow kernel A)
         raise SystemExit(f"bench.py: {extra['nonfinite_envs']} env-steps of the timed region had a non-finite robot state (solver blow-up): no line printed")
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(outputs, args.dump_outputs, N)
+
     if rank == 0:
         value = world * N * timed_steps / elapsed
+        out = {
+            "metric": "env-steps/sec (whole node)", "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": 1e3 * elapsed / timed_steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload, "task": base_task, "envs_per_gpu": N, "mode": mode, "parallelism": f"dp{world}",
+                       "mixed_robots": bool(args.mixed_robots and world > 1), "full": bool(args.full)},
+            "roofline": None,
+        }
+    if rank == 0 and not args.full:
+        out.update({k: v for k, v in extra.items() if k not in out})
+        os.write(result_fd, (json.dumps(out) + "\n").encode())
+    elif rank == 0:
         achieved = ALGO_BYTES_PER_ENV_STEP * N / (ka * 1e-3) / 1e9 if ka == ka and ka > 0 else None
         pmc = pmc_for(args.task, N, mode, actions_src, "tgs" if int(env.lcfg.solver_type) == 1 else "pgs")
         traffic = pmc["traffic_bytes_per_launch"] if pmc else None
@@ -468,14 +523,6 @@ def main():
             # The clock is the measured effective clock of the PMC pass (GRBM_GUI_ACTIVE / duration) when it was collected, else the 2.4 GHz maximum.
             clk = pmc.get("effective_clock_hz") or MAX_CLOCK_HZ
             valu_frac = pmc["valu_wave_insts_per_launch"] * VALU_CYCLES_PER_WAVE_INST / (N_SIMD * clk * ka * 1e-3)
-        out = {
-            "metric": "env-steps/sec (whole node)", "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": 1e3 * elapsed / timed_steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload, "task": base_task, "envs_per_gpu": N, "mode": mode, "parallelism": f"dp{world}",
-                       "mixed_robots": bool(args.mixed_robots and world > 1)},
-            "roofline": None,
-        }
         # Roofline of the dominant kernel (kernel A).  The task's schema offers hbm | mfma; kernel A is neither: it moves 6.9 KB per env-step
         # (3 % of HBM) and has no matrix work worth MFMA (tools/micro/delassus_mfma).  Its real limiter is VALU issue /
         # dependent-instruction latency, so when wave-instruction counts from a PMC pass of THIS workload are available the line says

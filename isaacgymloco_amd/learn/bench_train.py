@@ -2,11 +2,12 @@
 env-steps/s over collection (policy inference + LeggedRobot.step + storage) PLUS compute_returns + update().
 
 The unit of timing is one WHOLE PPO iteration (HIMR:105-157): T = num_steps_per_env rollout steps, then GAE, then
-HIMPPO.update().  `--steps K` asks for K env-steps; max(10, ceil(K / T)) iterations are timed -- never fewer than ten (1 s at the
-BASELINE size), so that one clock ramp or collector pause cannot move the line by several per cent -- and `--warmup W`
-likewise runs ceil(W / T) untimed iterations (at least three: the first update carries lazy library initialisation and creates the
-optimiser state).  `value` stays
-whole-region throughput (all timed env-steps / barrier-to-barrier time); the per-iteration minimum / median / maximum are reported beside it."""
+HIMPPO.update().  `--steps K` asks for K env-steps; ceil(K / T) iterations are timed, so K is exact whenever it is a multiple of T
+(pass K >= 1000, ten iterations or 1 s at the BASELINE size, when one clock ramp or collector pause must not move the line by several
+per cent: VERDICT r2, r4) -- and `--warmup W` runs ceil(W / T) untimed iterations (at least six: the first update carries lazy library
+initialisation and creates the optimiser state).  `value` stays
+whole-region throughput (all timed env-steps / barrier-to-barrier time); with `full` the per-iteration minimum / median / maximum, the
+kernel profile, the shader clock and the per-rank diagnostics are reported beside it."""
 import ctypes
 import os
 import time
@@ -17,7 +18,6 @@ from ..envs import config as C
 from .runner import HIMOnPolicyRunner
 
 
-MIN_TIMED_ITERATIONS = 10
 MIN_WARMUP_ITERATIONS = 6      # (round 6: on one fresh lease the first two timed iterations after three warm-ups still ran 9-14 % long; cause not isolated -- the box's host is shared)
 
 
@@ -32,7 +32,9 @@ def weights_digest(module):
     return [float(flat.sum()), float((flat * flat).sum())]
 
 
-def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
+def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None, full=True):
+    """-> (elapsed seconds, extra fields of the line, workload text, outputs of the last timed iteration).  full=False (a plain bench run)
+    times the same iterations and skips everything the headline does not need: kernel profile, shader clock, per-rank diagnostics."""
     task = args.task if args.task in C.TASKS else "aliengo"
     tc = train_cfg_dict(task)
     torch.manual_seed(1)   # identical initial policy on every rank (then broadcast anyway)
@@ -45,7 +47,7 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
         runner = HIMOnPolicyRunner(env, tc, log_dir=None, device=str(dev))
     use_graphs = os.environ.get("LSIM_NO_GRAPHS") != "1" and runner.enable_graphs()
     T = runner.num_steps_per_env
-    iters = max(MIN_TIMED_ITERATIONS, -(-args.steps // T))
+    iters = max(1, -(-args.steps // T))
     warm_iters = max(MIN_WARMUP_ITERATIONS, -(-args.warmup // T))
     env.episode_length_buf = torch.randint_like(env.episode_length_buf, high=int(env.max_episode_length))   # HIMR:90-91
     state = dict(obs=env.get_observations().clone(), critic=env.get_privileged_observations().clone())
@@ -54,6 +56,7 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
     spans = {"collection": [], "update": []}      # wall-clock intervals of the two halves of every iteration (the clock sampler splits its samples by them)
 
     enqueue = []       # host seconds the update took to ENQUEUE (HIMPPO.update: up to its first read-back), every iteration incl. warm-up
+    last = {}          # what the last iteration's update returned (the losses a caller of the loop receives)
 
     def one_iteration():
         """HIMR:105-157 without the logging: returns (collection seconds, learn seconds), each closed by a device sync"""
@@ -71,7 +74,7 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
             runner.alg.compute_returns(state["critic"])
         if use_graphs:
             runner.graphs.end_iteration()
-        runner.alg.update()
+        last["update"] = runner.alg.update()
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         enqueue.append(getattr(runner.alg, "update_enqueue_s", 0.0))
@@ -102,17 +105,18 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
     import gc
     gc.collect(); gc.freeze()
     n_prof = iters * T
-    env._L.lsim_set_profiling(env._h, n_prof)
+    if full:
+        env._L.lsim_set_profiling(env._h, n_prof)
     coll = learn = 0.0
     per_iter = []
-    multi_diag = alg.dist_ctx is not None and alg.dist_ctx.enabled        # N > 1 (or the forced 1-rank group): how long this rank stands in the collectives
+    multi_diag = full and alg.dist_ctx is not None and alg.dist_ctx.enabled        # N > 1 (or the forced 1-rank group): how long this rank stands in the collectives
     if multi_diag:
         alg.dist_ctx.timing = True
         alg.dist_ctx.take_blocked_seconds()
     blocked = 0.0
     barrier()
     nf0 = int(env.nonfinite_envs)                # (a host read: outside the timed region)
-    if clocks is not None:
+    if clocks is not None and full:
         clocks.start()
     t0 = time.perf_counter()
     for _ in range(iters):
@@ -125,6 +129,14 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
     barrier()
     elapsed = time.perf_counter() - t0
     nonfinite = int(env.nonfinite_envs) - nf0
+    outputs = last_outputs(env, runner, last.get("update"))
+    workload = (f"{task}: {type(runner).__name__} loop, {iters} whole PPO iteration(s) timed, each = {T} x (policy inference + LeggedRobot.step + "
+                f"storage) + GAE + {type(alg).__name__}.update ({alg.num_learning_epochs} epochs x {alg.num_mini_batches} minibatches), "
+                f"{env.num_envs} envs/GPU")
+    extra = {"timed_env_steps": iters * T, "nonfinite_envs": nonfinite, "ppo_updates_timed": iters, "warmup_iterations": warm_iters,
+             "ppo_iteration_wall_s": elapsed / iters, "collection_s_per_iteration": coll / iters, "learn_s_per_update": learn / iters}
+    if not full:
+        return elapsed, extra, workload, outputs
     sclk = clocks.stop(phases=spans) if clocks is not None else None
     ms_a, ms_b, n = (ctypes.c_float * n_prof)(), (ctypes.c_float * n_prof)(), ctypes.c_int(n_prof)
     env._L.lsim_read_profile(env._h, ms_a, ms_b, ctypes.byref(n))
@@ -153,8 +165,7 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
         digests, masses, per_rank, skew = [digest], [mass], [mine], [0.0] * len(walls_local)
     walls = sorted(c + l for c, l in per_iter)
     med = walls[len(walls) // 2] if len(walls) % 2 else 0.5 * (walls[len(walls) // 2 - 1] + walls[len(walls) // 2])
-    extra = {"kernel_a_ms": ka, "kernel_b_ms": kb, "timed_env_steps": iters * T, "nonfinite_envs": nonfinite, "ppo_updates_timed": iters, "warmup_iterations": warm_iters,
-             "ppo_iteration_wall_s": elapsed / iters, "collection_s_per_iteration": coll / iters, "learn_s_per_update": learn / iters,
+    extra.update({"kernel_a_ms": ka, "kernel_b_ms": kb,
              "collection_env_steps_per_s": world * env.num_envs * iters * T / max(coll, 1e-9),
              "collection_learn_s_by_iteration": per_iter[:32], "rollout_hip_graphs": bool(use_graphs), "weights_digest_by_rank": digests,
              "ranks_in_lockstep": all(x == digests[0] for x in digests), "robot_mass_kg_by_rank": [round(m, 3) for m in masses],
@@ -177,8 +188,24 @@ def run_train_bench(env, cfg, args, dev, rank, world, barrier, clocks=None):
              # which form the hidden layers' forward ran in (learn/fused_linear.py: linear_elu_forward): "aligned" = the library's MFMA kernel with bias + ELU in
              # the epilogue on the layers with 16-byte-aligned rows, BLAS + torch ELU on the rest; "0" = BLAS + ELU everywhere; "all"
              "linear_elu_forward": os.environ.get("LSIM_ELU_FORWARD", "aligned"),
-             "sclk_during_timed_region": sclk}
-    workload = (f"{task}: {type(runner).__name__} loop, {iters} whole PPO iteration(s) timed, each = {T} x (policy inference + LeggedRobot.step + "
-                f"storage) + GAE + {type(alg).__name__}.update ({alg.num_learning_epochs} epochs x {alg.num_mini_batches} minibatches), "
-                f"{env.num_envs} envs/GPU")
-    return elapsed, extra, workload
+             "sclk_during_timed_region": sclk})
+    return elapsed, extra, workload, outputs
+
+
+def env_outputs(env):
+    """what LeggedRobot.step_device hands its caller after the last step: observations, privileged observations, rewards, reset flags"""
+    return {"obs": env.obs_buf, "privileged_obs": env.privileged_obs_buf, "rew": env.rew_buf, "reset": env.reset_buf}
+
+
+def last_outputs(env, runner, update_ret):
+    """what the timed loop computed in its last iteration, as device / host values: the environment's outputs of the last step, the actions
+    of the last rollout step (fused rollout graphs only: the eager path keeps them in its storage), the update's returned losses and the
+    parameters of the policy after that update"""
+    out = env_outputs(env)
+    if getattr(runner.graphs, "actions", None) is not None:
+        out["actions"] = runner.graphs.actions
+    if update_ret is not None:
+        vals = update_ret if isinstance(update_ret, (tuple, list)) else (update_ret,)
+        out["update_losses"] = torch.tensor([float(v) for v in vals], dtype=torch.float64)
+    out["policy_params"] = torch.cat([p.detach().reshape(-1).float() for p in runner.alg.actor_critic.parameters()])
+    return out

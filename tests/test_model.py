@@ -1,7 +1,6 @@
 """Robot model table: derived constants (mass after Isaac Gym's fixed-joint collapse) and, when the reference
 checkout is present (build container only), a re-derivation from its URDF."""
 import os
-import xml.etree.ElementTree as ET
 
 import numpy as np
 import pytest
@@ -23,29 +22,22 @@ def test_masses_and_topology():
     assert m.num_collision_points == 64       # every URDF collision primitive incl. the rotor housings (robots/common.py rules)
 
 
-@pytest.mark.skipif(not os.path.exists(URDF), reason="reference checkout not present")
 def test_table_matches_reference_urdf():
-    root = ET.parse(URDF).getroot()
-    links = {l.get("name"): l for l in root.findall("link")}
-    joints = {j.get("name"): j for j in root.findall("joint")}
+    """the hand table against the values of the reference's aliengo.urdf (tests/golden/urdf_aliengo_values.json, tools/gen_golden_urdf.py)"""
+    import json
+    ref = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "urdf_aliengo_values.json")))
     bodies = aliengo.body_table()
     for leg in aliengo.LEGS:
-        hip = links[f"{leg}_hip"].find("inertial")
+        r = ref["legs"][leg]
         b = bodies[aliengo.BODY_NAMES.index(f"{leg}_hip")]
-        m_rotor = float(links[f"{leg}_thigh_rotor"].find("inertial").find("mass").get("value"))
-        assert abs(b["mass"] - (float(hip.find("mass").get("value")) + m_rotor)) < 1e-9
-        jo = [float(x) for x in joints[f"{leg}_hip_joint"].find("origin").get("xyz").split()]
-        np.testing.assert_allclose(b["joint_pos"], jo, atol=1e-12)
-        lim = joints[f"{leg}_calf_joint"].find("limit")
-        assert float(lim.get("lower")) == aliengo.LIMITS["calf"][0] and float(lim.get("effort")) == aliengo.LIMITS["calf"][3]
-        calf = links[f"{leg}_calf"].find("inertial")
+        assert abs(b["mass"] - (r["hip_mass"] + r["thigh_rotor_mass"])) < 1e-9
+        np.testing.assert_allclose(b["joint_pos"], r["hip_joint_origin"], atol=1e-12)
+        assert r["calf_limit_lower"] == aliengo.LIMITS["calf"][0] and r["calf_limit_effort"] == aliengo.LIMITS["calf"][3]
         c = bodies[aliengo.BODY_NAMES.index(f"{leg}_calf")]
-        np.testing.assert_allclose(c["com"], [float(x) for x in calf.find("origin").get("xyz").split()], atol=1e-12)
-        th = links[f"{leg}_thigh"].find("inertial").find("inertia")
+        np.testing.assert_allclose(c["com"], r["calf_com"], atol=1e-12)
         # thigh inertia products mirror with the leg side
-        assert np.sign(float(th.get("ixy"))) == np.sign(aliengo._mirror(aliengo.THIGH, 1.0, aliengo._SY[leg])["inertia"][1])
-    trunk = float(links["trunk"].find("inertial").find("mass").get("value"))
-    assert abs(bodies[0]["mass"] - (trunk + 0.001 + 4 * 0.146)) < 1e-9
+        assert np.sign(r["thigh_ixy"]) == np.sign(aliengo._mirror(aliengo.THIGH, 1.0, aliengo._SY[leg])["inertia"][1])
+    assert abs(bodies[0]["mass"] - (ref["trunk_mass"] + 0.001 + 4 * 0.146)) < 1e-9
 
 
 def test_stored_tables_build_and_aliengo_table_equals_hand_table():

@@ -23,7 +23,7 @@ except Exception as e:
     out["rocm_smi"] = f"{type(e).__name__}: {e}"
 sizes = {}
 for n in (3584, 3840, 4032, 4096, 4160, 8192):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "env", "--envs", str(n), "--steps", "300", "--warmup", "50", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "env", "--envs", str(n), "--steps", "300", "--warmup", "50", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600)
     try:
         j = json.loads(r.stdout.strip().splitlines()[-1])

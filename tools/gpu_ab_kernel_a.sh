@@ -7,7 +7,7 @@ for round in 1 2 3; do
     name=${v%%=*}; path=${v#*=}
     for task in aliengo aliengo_stairs; do
       if [ $name = product ]; then unset LSIM_LIB; else export LSIM_LIB=$PWD/$path; fi
-      timeout 300 python bench.py --mode env --task $task --steps 500 --warmup 50 --no-cpu-baseline < /dev/null > $O/env_${name}_${task}_$round.log 2>&1
+      timeout 300 python bench.py --full --mode env --task $task --steps 500 --warmup 50 --no-cpu-baseline < /dev/null > $O/env_${name}_${task}_$round.log 2>&1
       timeout 20 python -c "import json; d=json.loads(open('$O/env_${name}_${task}_$round.log').read().strip().splitlines()[-1]); print('$name $task round $round kernel_a %.4f ms  value %.2f M  nonfinite %s' % (d['kernel_a_ms'], d['value'] / 1e6, d.get('nonfinite_envs')))" < /dev/null
     done
   done

@@ -13,18 +13,18 @@ b() { name=$1; shift; "$@" < /dev/null > $O/$name.log 2>&1; tail -1 $O/$name.log
 rm -f $O/free_running_parity.jsonl
 LSIM_PARITY_REPORT=$O/free_running_parity.jsonl timeout 1500 python -m pytest tests -m gpu -q < /dev/null > $O/gpu_tests.log 2>&1; tail -2 $O/gpu_tests.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" < /dev/null > $O/smoke.log 2>&1; tail -1 $O/smoke.log
-b bench_default timeout 900 python bench.py
-b bench_driver_args timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
-b bench_env timeout 600 python bench.py --mode env --steps 500 --warmup 50 --no-cpu-baseline
-b bench_env_N262144 timeout 300 python bench.py --mode env --envs 262144 --steps 50 --warmup 10 --no-cpu-baseline
-b bench_env_zero_actions timeout 300 python bench.py --mode env --actions zeros --steps 500 --warmup 50 --no-cpu-baseline
-b bench_env_aliengo_stairs timeout 300 python bench.py --mode env --task aliengo_stairs --steps 500 --warmup 50 --no-cpu-baseline
-for t in aliengo_stairs aliengo_amp go1 go2; do b bench_$t timeout 400 python bench.py --task $t --no-cpu-baseline; done
-LSIM_AMP_FUSED_STEP=0 LSIM_AMP_FUSED_UPDATE=0 b bench_aliengo_amp_round5_path timeout 400 python bench.py --task aliengo_amp --no-cpu-baseline
-LSIM_DEBUG_SINGLE_DEVICE=1 b bench_2ranks_debug timeout 600 python bench.py --gpus 2 --no-cpu-baseline
-LSIM_DEBUG_SINGLE_DEVICE=1 b bench_2ranks_mixed_debug timeout 600 python bench.py --gpus 2 --mixed-robots --no-cpu-baseline
-LSIM_DEBUG_FORCE_COLLECTIVES=1 b bench_rccl_1rank timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --no-cpu-baseline
-b bench_plain_again timeout 600 python bench.py --no-cpu-baseline
+b bench_default timeout 900 python bench.py --full
+b bench_driver_args timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline
+b bench_env timeout 600 python bench.py --full --mode env --steps 500 --warmup 50 --no-cpu-baseline
+b bench_env_N262144 timeout 300 python bench.py --full --mode env --envs 262144 --steps 50 --warmup 10 --no-cpu-baseline
+b bench_env_zero_actions timeout 300 python bench.py --full --mode env --actions zeros --steps 500 --warmup 50 --no-cpu-baseline
+b bench_env_aliengo_stairs timeout 300 python bench.py --full --mode env --task aliengo_stairs --steps 500 --warmup 50 --no-cpu-baseline
+for t in aliengo_stairs aliengo_amp go1 go2; do b bench_$t timeout 400 python bench.py --full --task $t --no-cpu-baseline; done
+LSIM_AMP_FUSED_STEP=0 LSIM_AMP_FUSED_UPDATE=0 b bench_aliengo_amp_round5_path timeout 400 python bench.py --full --task aliengo_amp --no-cpu-baseline
+LSIM_DEBUG_SINGLE_DEVICE=1 b bench_2ranks_debug timeout 600 python bench.py --full --gpus 2 --no-cpu-baseline
+LSIM_DEBUG_SINGLE_DEVICE=1 b bench_2ranks_mixed_debug timeout 600 python bench.py --full --gpus 2 --mixed-robots --no-cpu-baseline
+LSIM_DEBUG_FORCE_COLLECTIVES=1 b bench_rccl_1rank timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --no-cpu-baseline
+b bench_plain_again timeout 600 python bench.py --full --no-cpu-baseline
 for i in 1 2 3; do timeout 120 python tools/policy_time.py < /dev/null 2>/dev/null; done > $O/policy_time.txt
 for n in 4096 8192; do timeout 120 python tools/amp_step_time.py $n < /dev/null 2>/dev/null; done > $O/amp_step_time.txt
 timeout 120 tools/micro/valu_peak < /dev/null > $O/valu_peak.json 2>/dev/null

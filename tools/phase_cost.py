@@ -37,7 +37,7 @@ def bench(lib):
     env = dict(os.environ)
     if lib:
         env["LSIM_LIB"] = lib
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "env", "--steps", "300", "--warmup", "50", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--mode", "env", "--steps", "300", "--warmup", "50", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True)
     return json.loads(r.stdout.strip().splitlines()[-1])["kernel_a_ms"]
 
