@@ -59,6 +59,7 @@ extern "C" {
 #define LSIM_MAX_CONTACTS 8
 #endif
 #define LSIM_MAX_POSITION_ITERATIONS 12   /* solver_type 1: sub-iterations per sim_dt (the reference sets 4, LRC:246) */
+#define LSIM_MAX_ROBOTS 4                 /* robot descriptions of one lsim_create_mixed instance */
 #define LSIM_SOLVER_PGS 0
 #define LSIM_SOLVER_TGS 1
 #define LSIM_TERRAIN_LEVELS_MAX 32
@@ -428,6 +429,20 @@ int lsim_query_arena(const lsim_config* cfg, size_t* bytes_out);
 int lsim_create(const lsim_config* cfg, const lsim_robot_model* model,
                 const int16_t* height_grid, const float* terrain_origins,
                 void* arena_dev, int device_id, lsim_handle* out);
+
+/* several quadrupeds in one instance: env e simulates robot env_robot[e] (host uint8 [num_envs], each < num_robots) for its whole life.
+ * cfgs[k] / models[k] describe robot k; cfgs[k] is a complete config for it (as for lsim_create), and the configs may differ ONLY in the
+ * robot-specific set:
+ *     action_scale, hip_reduction, p_gains, d_gains, torque_limits, default_dof_pos, base_init_state,
+ *     base_height_target, foot_height_target_base, foot_height_target_terrain
+ * (and the whole lsim_robot_model).  Everything else -- task, terrain, rewards, commands, domain randomisation, noise, solver -- is shared.
+ * LSIM_E_INVALID if two configs differ outside that set, num_robots is not in 1..LSIM_MAX_ROBOTS, an env_robot entry is out of range, or a
+ * robot is given no env.  The arena is sized by lsim_query_arena(&cfgs[0]).  Random draws are keyed by env as in lsim_create, so env e of
+ * a mixed instance evolves exactly as env e of the single-robot instance of its robot (same config, seed and terrain).  lsim_create is the
+ * num_robots = 1 case of this call. */
+int lsim_create_mixed(const lsim_config* cfgs, const lsim_robot_model* models, int32_t num_robots,
+                      const uint8_t* env_robot, const int16_t* height_grid, const float* terrain_origins,
+                      void* arena_dev, int device_id, lsim_handle* out);
 
 /* replaces gymtorch.wrap_tensor(acquire_*) (LR:930-944): device pointer + shape of one buffer. */
 int lsim_get_buffer(lsim_handle h, int buffer_id, void** dev_ptr, int64_t shape[4], int* ndim, int* dtype);

@@ -16,8 +16,9 @@
 #include "ls_shared.h"
 
 struct lsim_sim {
-    lsim_config cfg;
-    lsim_robot_model model;
+    lsim_config cfg;          // robot 0's config (every field outside the robot-specific set is the instance's)
+    int num_robots;
+    uint8_t* env_robot;       // device [num_envs] robot of each env, owned; null for a one-robot instance
     LsCtx host_ctx;
     LsCtx* dev_ctx;
     char* arena;
@@ -144,34 +145,81 @@ static std::vector<int32_t> ls_terrain_mesh_flags(const lsim_config& c, const in
     return out;
 }
 
-static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model, const int16_t* height_grid,
-                          const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out, lsim_sim** partial);
+// the robot-specific set (include/lsim.h, lsim_create_mixed): the fields two configs of one instance may differ in -- cleared in a copy
+static void ls_clear_robot_fields(lsim_config& c) {
+    c.action_scale = 0.0f; c.hip_reduction = 0.0f;
+    memset(c.p_gains, 0, sizeof(c.p_gains)); memset(c.d_gains, 0, sizeof(c.d_gains));
+    memset(c.torque_limits, 0, sizeof(c.torque_limits)); memset(c.default_dof_pos, 0, sizeof(c.default_dof_pos));
+    memset(c.base_init_state, 0, sizeof(c.base_init_state));
+    c.base_height_target = 0.0f; c.foot_height_target_base = 0.0f; c.foot_height_target_terrain = 0.0f;
+}
+static void ls_robot_entry(const lsim_config& c, const lsim_robot_model& m, LsRobot& r) {
+    r.model = m;
+    r.action_scale = c.action_scale; r.hip_reduction = c.hip_reduction;
+    memcpy(r.p_gains, c.p_gains, sizeof(r.p_gains)); memcpy(r.d_gains, c.d_gains, sizeof(r.d_gains));
+    memcpy(r.torque_limits, c.torque_limits, sizeof(r.torque_limits)); memcpy(r.default_dof_pos, c.default_dof_pos, sizeof(r.default_dof_pos));
+    memcpy(r.base_init_state, c.base_init_state, sizeof(r.base_init_state));
+    r.base_height_target = c.base_height_target; r.foot_height_target_base = c.foot_height_target_base; r.foot_height_target_terrain = c.foot_height_target_terrain;
+}
+static int ls_check_robots(const lsim_config* cfgs, const lsim_robot_model* models, int num_robots, const uint8_t* env_robot) {
+    if (num_robots < 1 || num_robots > LSIM_MAX_ROBOTS) return LSIM_E_INVALID;
+    if (num_robots > 1 && !env_robot) return LSIM_E_INVALID;
+    lsim_config c0 = cfgs[0];
+    ls_clear_robot_fields(c0);
+    for (int k = 0; k < num_robots; ++k) {
+        if (models[k].num_collision_points > LSIM_MAX_COLLISION_POINTS || models[k].num_collision_points < 0) return LSIM_E_INVALID;
+        lsim_config ck = cfgs[k];
+        ls_clear_robot_fields(ck);
+        if (memcmp(&ck, &c0, sizeof(lsim_config)) != 0) return LSIM_E_INVALID;
+    }
+    if (env_robot) {
+        int used[LSIM_MAX_ROBOTS] = {0};
+        for (int e = 0; e < cfgs[0].num_envs; ++e) {
+            if (env_robot[e] >= num_robots) return LSIM_E_INVALID;
+            used[env_robot[e]] = 1;
+        }
+        for (int k = 0; k < num_robots; ++k) if (!used[k]) return LSIM_E_INVALID;
+    }
+    return LSIM_OK;
+}
+
+static int ls_create_impl(const lsim_config* cfgs, const lsim_robot_model* models, int num_robots, const uint8_t* env_robot,
+                          const int16_t* height_grid, const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out, lsim_sim** partial);
+static void ls_free_partial(lsim_sim* s) {
+    if (s->owns_arena && s->arena) lsbk_free(s->arena);
+    if (s->dev_ctx) lsbk_free(s->dev_ctx);
+    if (s->env_robot) lsbk_free(s->env_robot);
+    free(s);
+}
 // include/lsim.h promises that no exception crosses the ABI: the set-up below fills std::vectors (the init-time draws, the terrain mesh words),
 // whose allocation failure is a C++ exception -- caught here, what had been allocated is released, LSIM_E_NOMEM returned
-extern "C" int LS_API(create)(const lsim_config* cfg, const lsim_robot_model* model, const int16_t* height_grid,
-                              const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out) {
+extern "C" int LS_API(create_mixed)(const lsim_config* cfgs, const lsim_robot_model* models, int32_t num_robots, const uint8_t* env_robot,
+                                    const int16_t* height_grid, const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out) {
     lsim_sim* partial = nullptr;
     try {
-        return ls_create_impl(cfg, model, height_grid, terrain_origins, arena_dev, device_id, out, &partial);
+        return ls_create_impl(cfgs, models, num_robots, env_robot, height_grid, terrain_origins, arena_dev, device_id, out, &partial);
     } catch (...) {
-        if (partial) {
-            if (partial->owns_arena && partial->arena) lsbk_free(partial->arena);
-            if (partial->dev_ctx) lsbk_free(partial->dev_ctx);
-            free(partial);
-        }
+        if (partial) ls_free_partial(partial);
         return LSIM_E_NOMEM;
     }
 }
-static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model, const int16_t* height_grid,
-                          const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out, lsim_sim** partial) {
-    if (!cfg || !model || !out) return LSIM_E_INVALID;
+// the one-robot case of lsim_create_mixed
+extern "C" int LS_API(create)(const lsim_config* cfg, const lsim_robot_model* model, const int16_t* height_grid,
+                              const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out) {
+    return LS_API(create_mixed)(cfg, model, 1, nullptr, height_grid, terrain_origins, arena_dev, device_id, out);
+}
+static int ls_create_impl(const lsim_config* cfgs, const lsim_robot_model* models, int num_robots, const uint8_t* env_robot,
+                          const int16_t* height_grid, const float* terrain_origins, void* arena_dev, int device_id, lsim_sim** out, lsim_sim** partial) {
+    if (!cfgs || !models || !out) return LSIM_E_INVALID;
+    const lsim_config* cfg = &cfgs[0];
     int rc = ls_check_cfg(cfg);
     if (rc != LSIM_OK) return rc;
     if (cfg->mesh_type != 0 && (!height_grid || !terrain_origins)) return LSIM_E_INVALID;
-    if (model->num_collision_points > LSIM_MAX_COLLISION_POINTS || model->num_collision_points < 0) return LSIM_E_INVALID;
+    rc = ls_check_robots(cfgs, models, num_robots, env_robot);
+    if (rc != LSIM_OK) return rc;
     lsim_sim* s = (lsim_sim*)calloc(1, sizeof(lsim_sim));
     if (!s) return LSIM_E_NOMEM;
-    s->cfg = *cfg; s->model = *model; s->device_id = device_id;
+    s->cfg = *cfg; s->num_robots = num_robots; s->device_id = device_id;
     const lsim_config& c = s->cfg;
     const int N = c.num_envs;
     if (lsbk_set_device(device_id) != 0) { free(s); return LSIM_E_HIP; }
@@ -183,6 +231,7 @@ static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model,
     }
     if (lsbk_memset(s->arena, 0, total) != 0) { if (s->owns_arena) lsbk_free(s->arena); free(s); return LSIM_E_HIP; }
     *partial = s;        // from here on an exception (std::bad_alloc of the vectors below) is cleaned up by the caller
+    auto robot_of = [&](int env) { return env_robot ? (int)env_robot[env] : 0; };
 
     // ---- init-time draws (LR:999-1032, LR:1172-1179, LR:506-513, LR:1232-1239), identical to the oracle's
     const uint32_t W = 0xFFFFFFFFu;
@@ -209,7 +258,7 @@ static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model,
             typ[e] = lsim_terrain_type_of_env(e, N, c.terrain_num_cols);     // LR:1234 (torch's floor division, see lsim_layout.h)
             for (int k = 0; k < 3; ++k) org[3 * e + k] = terrain_origins[(lvl[e] * c.terrain_num_cols + typ[e]) * 3 + k];
         }
-        for (int k = 0; k < 13; ++k) root[13 * e + k] = c.base_init_state[k];
+        for (int k = 0; k < 13; ++k) root[13 * e + k] = cfgs[robot_of(e)].base_init_state[k];       // the env's robot's (LR:1160-1161)
         for (int k = 0; k < 3; ++k) root[13 * e + k] += org[3 * e + k];
     }
     std::vector<float> stats(2 * LSIM_STATS_SIZE, 0.0f);
@@ -229,7 +278,13 @@ static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model,
     // ---- device context
     LsCtx& h = s->host_ctx;
     memset(&h, 0, sizeof(h));
-    h.cfg = c; h.model = s->model;
+    h.cfg = c;
+    for (int k = 0; k < num_robots; ++k) ls_robot_entry(cfgs[k], models[k], h.robots[k]);
+    if (env_robot) {
+        if (lsbk_malloc((void**)&s->env_robot, (size_t)N) != 0) bad = 1;
+        else bad |= lsbk_h2d(s->env_robot, env_robot, (size_t)N);
+        h.env_robot = s->env_robot;
+    }
     for (int id = 0; id < LSIM_NUM_BUFFERS; ++id) h.buf[id] = s->arena + s->offsets[id];
     h.accum = (float*)h.buf[LSIM_BUF_STATS];
     h.num_active = 0;
@@ -243,7 +298,7 @@ static int ls_create_impl(const lsim_config* cfg, const lsim_robot_model* model,
     }
     if (lsbk_malloc((void**)&s->dev_ctx, sizeof(LsCtx)) != 0) bad = 1;
     else bad |= lsbk_h2d(s->dev_ctx, &h, sizeof(LsCtx));
-    if (bad) { *partial = nullptr; if (s->owns_arena) lsbk_free(s->arena); if (s->dev_ctx) lsbk_free(s->dev_ctx); free(s); return LSIM_E_HIP; }
+    if (bad) { *partial = nullptr; ls_free_partial(s); return LSIM_E_HIP; }
     s->step_counter = 0;
     s->priority_max_envs = 32768;
     if (const char* e = getenv("LSIM_PRIORITY_MAX_ENVS")) s->priority_max_envs = atoi(e);
@@ -333,5 +388,6 @@ extern "C" void LS_API(destroy)(lsim_sim* s) {
     lsbk_prof_free(s);
     if (s->owns_arena && s->arena) lsbk_free(s->arena);
     if (s->dev_ctx) lsbk_free(s->dev_ctx);
+    if (s->env_robot) lsbk_free(s->env_robot);
     free(s);
 }

@@ -17,7 +17,7 @@
 #define LS_PHASE(call) do { for (int lane = 0; lane < 64; ++lane) { LaneRegs& rg = L[lane]; (void)rg; call; } } while (0)
 #define LS_COLLECTIVE(gpu_call, emu_call) do { emu_call; } while (0)
 #define LS_KINEMATICS() LS_PHASE(ph_kinematics(sh, lane))
-#define LS_TORQUES_KINEMATICS() LS_PHASE(ph_torques(cx, sh, lane, env, sub, a.flags); ph_kinematics(sh, lane))
+#define LS_TORQUES_KINEMATICS() LS_PHASE(ph_torques(cx, rb, sh, lane, env, sub, a.flags); ph_kinematics(sh, lane))
 #define LS_ATOMIC_ADD(ptr, v) (*(ptr) += (v))
 #define LS_ATOMIC_ADD_I64(ptr, v) (*(ptr) += (v))
 #define LS_ATOMIC_FETCH_ADD_I64(ptr, v) ls_emu_fetch_add((ptr), (v))
@@ -82,7 +82,7 @@ __device__ unsigned int g_ls_wave_cp[16 * 65536];              // per env: shade
 #define LS_PHASE(call) do { { const int lane = ls_opaque_lane(lane0); call; } LS_WAVE_SYNC(); LS_AGAIN(call); LS_MARK(); LS_TICK(__LINE__ - ls_line0); LS_SUBCP(); } while (0)
 #define LS_COLLECTIVE(gpu_call, emu_call) do { { const int lane = ls_opaque_lane(lane0); gpu_call; } LS_WAVE_SYNC(); LS_AGAIN(gpu_call); LS_MARK(); LS_TICK(__LINE__ - ls_line0); LS_SUBCP(); } while (0)
 #define LS_KINEMATICS() LS_COLLECTIVE(wc_kinematics(sh, lane), (void)0)
-#define LS_TORQUES_KINEMATICS() LS_COLLECTIVE(ph_torques(cx, sh, lane, env, sub, a.flags); wc_kinematics(sh, lane), (void)0)
+#define LS_TORQUES_KINEMATICS() LS_COLLECTIVE(ph_torques(cx, rb, sh, lane, env, sub, a.flags); wc_kinematics(sh, lane), (void)0)
 #define LS_ATOMIC_ADD(ptr, v) atomicAdd((ptr), (v))
 // 64-bit integer atomics on the fixed-point accumulators (device scope: they are performed at the memory side, coherent across the XCDs)
 #define LS_ATOMIC_ADD_I64(ptr, v) ((void)atomicAdd((unsigned long long*)(ptr), (unsigned long long)(v)))
@@ -104,11 +104,20 @@ LS_FN long long ls_to_fix(float v) { return (long long)llrintf(fminf(fmaxf(v, -1
 LS_FN float ls_from_fix(long long f) { return (float)((double)f * (1.0 / 4294967296.0)); }
 LS_FN long long* ls_fix_row(const LsCtx& cx, int row) { return (long long*)(cx.accum + row * LSIM_STATS_SIZE + LSIM_STATS_FIX); }
 
+// ---- the env's robot description (lsim_create_mixed): wave-uniform -- env comes from the block index -- so the entry's address stays in SGPRs
+//      and every read of the robot's constants is a scalar load, as the single table of a one-robot instance was.  Looked up once per wave,
+//      before the first store; a one-robot instance (no env_robot array) skips the load
+LS_FN const LsRobot& ls_env_robot(const LsCtx& cx, int env) {
+    int r = 0;
+    if (cx.env_robot) r = LS_UNIFORM((int)LS_G(const uint8_t, cx.env_robot)[env]);
+    return cx.robots[r];
+}
+
 // ---- load the robot's state into LDS, clip the actions (LR:129-130), draw the action delay (LR:134)
 // Load phases: every global load is issued first, unconditionally -- a lane with no use for a value reads element 0 of the same row, always
 // a valid address -- and the LDS writes follow.  `if (lane < n) sh.x[lane] = buf[...]` per quantity compiles to one branch per quantity with
 // the load AND its wait inside, i.e. a chain of ~20 serialised memory round trips (12 k of the 27 k ticks of a kernel-B wave).
-LS_FN void ph_load_a(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane, int env, const LsStepArgs& a) {
+LS_FN void ph_load_a(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, LaneRegs& rg, int lane, int env, const LsStepArgs& a) {
     const lsim_config& c = cx.cfg;
     const int l12 = lane < 12 ? lane : 0;
     const float v_root = LSB(cx, LSIM_BUF_ROOT_STATES, float)[13 * env + (lane < 13 ? lane : 0)];
@@ -149,8 +158,8 @@ LS_FN void ph_load_a(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane, in
     for (int k = 0; k < 3; ++k) v_cd3[k] = LSB(cx, LSIM_BUF_COM_DISPLACEMENT, float)[3 * env + k];
     float v_jc[7];
     {
-        const lsim_robot_model& m = cx.model;
-        v_jc[0] = c.default_dof_pos[l12]; v_jc[1] = c.p_gains[l12]; v_jc[2] = c.d_gains[l12]; v_jc[3] = c.torque_limits[l12];
+        const lsim_robot_model& m = rb.model;
+        v_jc[0] = rb.default_dof_pos[l12]; v_jc[1] = rb.p_gains[l12]; v_jc[2] = rb.d_gains[l12]; v_jc[3] = rb.torque_limits[l12];
         v_jc[4] = m.dof_pos_lower[l12]; v_jc[5] = m.dof_pos_upper[l12]; v_jc[6] = m.dof_vel_limit[l12];
     }
     // ---- LDS writes
@@ -161,7 +170,7 @@ LS_FN void ph_load_a(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane, in
     if (lane < LSIM_MAX_HEIGHT_PTS_X) sh.mpx[lane] = v_mp; else sh.mpy[lane - LSIM_MAX_HEIGHT_PTS_X] = v_mp;
     if (lane < 13 && !(to_origin && lane >= 7 && lane < 10)) sh.root[lane] = v_root;
     if (to_origin && lane == 14) {
-        const lsim_body& b0 = cx.model.bodies[0];
+        const lsim_body& b0 = rb.model.bodies[0];
         const V3 cl = v3(b0.com[0] + v_cd3[0], b0.com[1] + v_cd3[1], b0.com[2] + v_cd3[2]);            // ls_body_com_local(sh, 0)
         const V3 r = quat_apply(v_r10, cl);
         const V3 v = v3p(v_r10 + 4) - cross(v3p(v_r10 + 7), r);
@@ -197,7 +206,7 @@ LS_FN void ph_load_a(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane, in
         LSB(cx, LSIM_BUF_DELAY_STEPS, int32_t)[env] = delay;
     }
     if (lane >= 16 && lane < 16 + LS_NB) {
-        const lsim_body& b = cx.model.bodies[lane - 16];
+        const lsim_body& b = rb.model.bodies[lane - 16];
         LsBodyLds& o = sh.body[lane - 16];
         o.mass = b.mass;
         for (int k = 0; k < 3; ++k) { o.com[k] = b.com[k]; o.jpos[k] = b.joint_pos[k]; o.axis[k] = b.joint_axis[k]; }
@@ -217,14 +226,14 @@ LS_FN void ph_load_a(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane, in
 }
 
 // ---- LeggedRobot._compute_torques (LR:658-688) with the delayed action of sub-step `sub` (LR:138); lane = dof
-LS_FN void ph_torques(const LsCtx& cx, WaveShared& sh, int lane, int env, int sub, uint32_t flags) {
+LS_FN void ph_torques(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, int lane, int env, int sub, uint32_t flags) {
     if (lane >= 12) return;
     const lsim_config& c = cx.cfg;
     float act = sh.act[lane], last = sh.last_act[lane];
     float a = c.delay ? last + (act - last) * ((sub >= sh.delay) ? 1.0f : 0.0f) : act;
     a = sh.ms[lane] * a;
-    float as = a * c.action_scale;
-    if (lane % 3 == 0) as *= c.hip_reduction;
+    float as = a * rb.action_scale;
+    if (lane % 3 == 0) as *= rb.hip_reduction;
     float target = sh.jc_q0[lane] + as;
     float q = sh.q[lane], qd = sh.qd[lane], t;
     if (c.control_type == 0) t = sh.jc_kp[lane] * sh.kpf * (target - q) - sh.jc_kd[lane] * sh.kdf * qd;
@@ -272,14 +281,14 @@ __device__ __forceinline__ void wc_count_nonfinite(const LsCtx& cx, WaveShared& 
 // the rigid-body state rows into registers (LaneRegs::bs) while the kinematics arrays are still alive -- the height samples overlay them --
 // and stored by ph_store_body_states once everything the wave had requested from memory has been consumed: a load whose result is read
 // while stores are in flight waits for the stores too (vmcnt retires in order), and at 4096 robots in lockstep a store burst takes ~5 us
-LS_FN void ph_body_states_all(const LsCtx& cx, WaveShared& sh, LaneRegs& rg, int lane) {
+LS_FN void ph_body_states_all(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, LaneRegs& rg, int lane) {
     const bool at_com = cx.cfg.lin_vel_at_com != 0;
     ph_body_states(sh, lane, rg.bs, at_com);
     if (at_com && lane == 0)   // the root state tensor's linear velocity is row 0's: from here on (stores, post-physics, pushes) the centre of mass's
         for (int k = 0; k < 3; ++k) sh.root[7 + k] = rg.bs[7 + k];
     if (lane < LS_NB)       // the feet rows of the tensor for the reward terms, from registers
         for (int f = 0; f < 4; ++f)
-            if (cx.model.feet_bodies[f] == lane) {         // uniform f: scalar loads
+            if (rb.model.feet_bodies[f] == lane) {         // uniform f: scalar loads
                 for (int k = 0; k < 3; ++k) { sh.feet[f][k] = rg.bs[k]; sh.feet[f][3 + k] = rg.bs[7 + k]; }
             }
 }
@@ -289,7 +298,7 @@ LS_FN void ph_store_body_states(const LsCtx& cx, const LaneRegs& rg, int lane, i
     for (int k = 0; k < 13; ++k) o[k] = rg.bs[k];
 }
 // LSIM_STEP_SKIP_PHYSICS: take the simulator tensors as injected by the caller
-LS_FN void ph_load_injected(const LsCtx& cx, WaveShared& sh, int lane, int env) {
+LS_FN void ph_load_injected(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, int lane, int env) {
     if (lane < 12) {
         sh.dofs[2 * lane] = sh.q[lane]; sh.dofs[2 * lane + 1] = sh.qd[lane];
         LSB(cx, LSIM_BUF_TORQUES, float)[12 * env + lane] = sh.tau[lane];
@@ -297,7 +306,7 @@ LS_FN void ph_load_injected(const LsCtx& cx, WaveShared& sh, int lane, int env) 
     if (lane < 3 * LS_NB) sh.cf[lane / 3][lane % 3] = LSB(cx, LSIM_BUF_CONTACT_FORCES, float)[3 * LS_NB * env + lane];
     if (lane < 24) {
         int f = lane / 6, k = lane % 6;
-        LS_GLOBAL const float* bs = LSB(cx, LSIM_BUF_RIGID_BODY_STATES, float) + 13 * (LS_NB * env + ls_foot_body(cx, f));
+        LS_GLOBAL const float* bs = LSB(cx, LSIM_BUF_RIGID_BODY_STATES, float) + 13 * (LS_NB * env + ls_foot_body(rb, f));
         sh.feet[f][k] = k < 3 ? bs[k] : bs[7 + k - 3];
     }
 }
@@ -472,7 +481,7 @@ LS_FN void ph_b_reset_draws(const LsCtx& cx, WaveShared& sh, int lane, int env, 
     ls_u01x4(c.seed, c.rank, (uint32_t)env, stepw, tag, block, u);
     for (int k = 0; k < 4; ++k) dr[4 * lane + k] = u[k];
 }
-LS_FN void ph_b_reset_state(const LsCtx& cx, WaveShared& sh, int lane, int env, const LsStepArgs& a, const float* q0 /* default_dof_pos: LDS copy or the config's */,
+LS_FN void ph_b_reset_state(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, int lane, int env, const LsStepArgs& a, const float* q0 /* default_dof_pos: LDS copy or the config's */,
                             const float* dr /* ph_b_reset_draws */) {
     if (!LS_UNIFORM(sh.do_reset)) return;          // wave-uniform: a scalar branch, nothing of the body is issued for the other waves
     const lsim_config& c = cx.cfg;
@@ -492,7 +501,7 @@ LS_FN void ph_b_reset_state(const LsCtx& cx, WaveShared& sh, int lane, int env, 
         float u[12];
         for (int k = 0; k < 12; ++k) u[k] = dr[24 + k];
         float r[13];
-        for (int k = 0; k < 13; ++k) r[k] = c.base_init_state[k];
+        for (int k = 0; k < 13; ++k) r[k] = rb.base_init_state[k];
         for (int k = 0; k < 3; ++k) r[k] += org[k];
         if (c.mesh_type != 0) {
             if (c.has_base_init_pos_range) for (int k = 0; k < 3; ++k) r[k] += rand_range(u[k], c.base_init_pos_range[k][0], c.base_init_pos_range[k][1]);
@@ -687,6 +696,7 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
     const float dt = c.sim_dt;
     constexpr bool TGS = SOLVER == LSIM_SOLVER_TGS;
     const bool skip = (a.flags & LSIM_STEP_SKIP_PHYSICS) != 0;
+    const LsRobot& rb = ls_env_robot(cx, env);
     [[maybe_unused]] constexpr int ls_line0 = __LINE__;   // phase-site ids (LS_PHASE_TIMING builds) count lines from here
     LS_TICK_INIT();
 #if defined(LS_WAVE_TIMES)    // diagnostics build only (tools/wave_times.py): when each wave of the latest step started and ended
@@ -694,14 +704,14 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
     unsigned int ls_cp[16] = {};
     [[maybe_unused]] int ls_sub = -1, ls_k = 0;
 #endif
-    LS_PHASE(ph_load_a(cx, sh, rg, lane, env, a));
+    LS_PHASE(ph_load_a(cx, rb, sh, rg, lane, env, a));
     LS_CP(0);
     for (int sub = 0; sub < c.decimation; ++sub) {
 #if defined(LS_WAVE_TIMES) && LS_WAVE_TIMES == 2
         ls_sub = sub;
         if (sub == 1) { ls_cp[0] = (unsigned int)(clock64() - ls_wc0); ls_k = 1; }
 #endif
-        if (skip) { LS_PHASE(ph_torques(cx, sh, lane, env, sub, a.flags)); continue; }
+        if (skip) { LS_PHASE(ph_torques(cx, rb, sh, lane, env, sub, a.flags)); continue; }
         // phases that do not depend on each other share a barrier: (torques, kinematics), (free velocity, narrow phase),
         // (contact compaction, joint-limit rows), (apply impulses, contact forces)
         LS_TORQUES_KINEMATICS();
@@ -714,7 +724,7 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
         LS_PHASE(ph_free_leg(sh, lane));
         LS_PHASE(ph_free_base(sh, lane));
         bool walls = false;       // a point of this robot is in the wall path of the narrow phase (stair risers)
-        LS_PHASE(ph_free_finish(sh, lane, dt); ph_collide_prefetch(cx, rg, lane); walls |= ph_collide(cx, sh, rg, lane));
+        LS_PHASE(ph_free_finish(sh, lane, dt); ph_collide_prefetch(rb, rg, lane); walls |= ph_collide(cx, rb, sh, rg, lane));
         LS_COLLECTIVE(wc_compact_contacts(sh, rg, lane); wc_limits(cx, sh, lane, dt), wc_compact_contacts(sh, L); LS_PHASE(ph_limits(cx, sh, lane, dt)));
         // A launch of <= 4096 robots is ONE round of waves, over when its slowest wave is: the median wave needs 83 us, one with 8 contacts 97
         // (2.3 us per contact: rows, Delassus entries, relaxations), the kernel 117 (tools/wave_times.py).  The more contacts a robot has in
@@ -752,7 +762,7 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
         LS_COLLECTIVE(wc_kinematics(sh, lane); ph_late_load(cx, rg, lane, env, fuse); ph_heights_issue(cx, sh, rg, lane), (void)0);
 #endif
         LS_CP(5);
-        LS_PHASE(ph_body_states_all(cx, sh, rg, lane));
+        LS_PHASE(ph_body_states_all(cx, rb, sh, rg, lane));
         LS_PHASE(ph_heights_finish(cx, sh, rg, lane, env); ph_late_stage(sh, rg, lane, fuse));   // the loads' results, before the first store; Mbl .. vnew are dead from here on
         LS_CP(6);
         LS_COLLECTIVE(ph_store_body_states(cx, rg, lane, env); ph_store_sim_state(cx, sh, lane, env); wc_count_nonfinite(cx, sh, lane, a),
@@ -761,19 +771,19 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
     } else {
         LS_PHASE(ph_late_load(cx, rg, lane, env, fuse); ph_heights_issue(cx, sh, rg, lane));
         LS_PHASE(ph_heights_finish(cx, sh, rg, lane, env); ph_late_stage(sh, rg, lane, fuse));
-        LS_PHASE(ph_load_injected(cx, sh, lane, env));
+        LS_PHASE(ph_load_injected(cx, rb, sh, lane, env));
     }
     // ---- post_physics_step (LR:178-228)
-    LS_PHASE(ph_post_state(cx, sh, lane, env));
+    LS_PHASE(ph_post_state(cx, rb, sh, lane, env));
     LS_PHASE(ph_callback(cx, sh, lane, env, a, sh.ranges));
     LS_CP(8);
 #if defined(LS_EXP_TWICE) && LS_EXP_TWICE == 9003      // cost probe: counter-based draws, so a second pass writes the same values
     LS_PHASE(ph_callback(cx, sh, lane, env, a, sh.ranges));
 #endif
-    LS_PHASE(ph_termination(cx, sh, lane, env); ph_reward_parts(cx, sh, ls_part_items(sh), lane, env));
-    LS_PHASE(ph_reward_terms(cx, sh, rg, lane, env));
+    LS_PHASE(ph_termination(cx, rb, sh, lane, env); ph_reward_parts(cx, rb, sh, ls_part_items(sh), lane, env));
+    LS_PHASE(ph_reward_terms(cx, rb, sh, rg, lane, env));
 #if defined(LS_EXP_TWICE) && LS_EXP_TWICE == 9002      // cost probe (adds the step's rewards to the episode sums twice: statistics only)
-    LS_PHASE(ph_reward_terms(cx, sh, rg, lane, env));
+    LS_PHASE(ph_reward_terms(cx, rb, sh, rg, lane, env));
 #endif
     LS_PHASE(ph_reward_total(cx, sh, lane, env));
     LS_CP(9);
@@ -783,7 +793,7 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
     if (fuse) {     // LR:229-241 + LR:167-171 for this robot (kernel B's phases; its cross-env part is lsim_k_step_finish)
         LS_PHASE(ph_tail_setup(cx, sh, lane, a));
         LS_PHASE(ph_b_terrain_curriculum(cx, sh, lane, env, a); ph_b_reset_draws(cx, sh, lane, env, a, ls_reset_draws_a(sh)));
-        LS_PHASE(ph_b_reset_state(cx, sh, lane, env, a, sh.jc_q0, ls_reset_draws_a(sh)));
+        LS_PHASE(ph_b_reset_state(cx, rb, sh, lane, env, a, sh.jc_q0, ls_reset_draws_a(sh)));
         LS_CP(14);
         LS_PHASE(if (LS_UNIFORM(sh.do_reset) && c.measure_heights) ph_heights(cx, sh, lane, env, true, sh.mpx, sh.mpy));     // loads: ahead of reset_idx's stores and atomics
         LS_CP(15);
@@ -806,6 +816,7 @@ template <int SOLVER> LS_WAVE_FN void ls_wave_step_a(const LsCtx& cx, const LsSt
 
 LS_WAVE_FN void ls_wave_step_b(const LsCtx& cx, const LsStepArgs& a, const int env, WaveShared& sh, LS_LANES_PARAM) {
     const lsim_config& c = cx.cfg;
+    const LsRobot& rb = ls_env_robot(cx, env);
     [[maybe_unused]] constexpr int ls_line0 = __LINE__ - 96;   // kernel B's sites land above kernel A's (A uses 0..95)
 #if defined(LS_WAVE_TIMES)
     [[maybe_unused]] int ls_sub = -1, ls_k = 0; [[maybe_unused]] unsigned int ls_cp[16]; [[maybe_unused]] const unsigned long long ls_wc0 = 0;   // (LS_PHASE's checkpoint hook: kernel A only)
@@ -813,7 +824,7 @@ LS_WAVE_FN void ls_wave_step_b(const LsCtx& cx, const LsStepArgs& a, const int e
     LS_TICK_INIT();
     LS_PHASE(ph_load_b(cx, sh, lane, env, a));
     LS_PHASE(ph_b_housekeeping(cx, sh, lane, env, a); ph_b_terrain_curriculum(cx, sh, lane, env, a); ph_b_reset_draws(cx, sh, lane, env, a, ls_reset_draws_b(sh)));
-    LS_PHASE(ph_b_reset_state(cx, sh, lane, env, a, cx.cfg.default_dof_pos, ls_reset_draws_b(sh)));
+    LS_PHASE(ph_b_reset_state(cx, rb, sh, lane, env, a, rb.default_dof_pos, ls_reset_draws_b(sh)));
     LS_PHASE(ph_b_reset_store(cx, sh, lane, env, a, ls_reset_draws_b(sh)));
     LS_PHASE(ph_b_episode_stats(cx, sh, rg, lane, env, a));
     LS_PHASE(if (LS_UNIFORM(sh.do_reset) && c.measure_heights) ph_heights(cx, sh, lane, env, true, c.measured_points_x, c.measured_points_y));
@@ -822,7 +833,7 @@ LS_WAVE_FN void ls_wave_step_b(const LsCtx& cx, const LsStepArgs& a, const int e
         LS_PHASE(ph_b_stats_convert(cx, sh, lane, a));
         return;
     }
-    LS_PHASE(ph_build_obs(cx, sh, lane, env, (uint32_t)a.step_counter, LSIM_RNG_OBS_NOISE, sh.cur, cx.cfg.default_dof_pos));
+    LS_PHASE(ph_build_obs(cx, sh, lane, env, (uint32_t)a.step_counter, LSIM_RNG_OBS_NOISE, sh.cur, rb.default_dof_pos));
     LS_PHASE(ph_b_store(cx, sh, lane, env, a, &sh.u.I6[0][0]); ph_b_stats_publish(cx, sh, rg, lane, a));
     LS_PHASE(ph_b_stats_convert(cx, sh, lane, a));
     LS_TICK_FLUSH();

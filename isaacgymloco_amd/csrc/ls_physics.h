@@ -530,8 +530,8 @@ LS_FN void ls_terrain_contact(const LsCtx& cx, V3 cw, float radius, float& dist,
 
 // ---- the collision point's constants (lane = point): re-read from the cache-resident model every sub-step rather than held in registers through
 //      the solver (the register peak), but at the TOP of the sub-step, so that the load latency hides behind the dynamics phases
-LS_FN void ph_collide_prefetch(const LsCtx& cx, LaneRegs& r, int lane) {
-    const lsim_collision_point& cp = cx.model.points[lane < cx.model.num_collision_points ? lane : 0];
+LS_FN void ph_collide_prefetch(const LsRobot& rb, LaneRegs& r, int lane) {
+    const lsim_collision_point& cp = rb.model.points[lane < rb.model.num_collision_points ? lane : 0];
     r.cp_body = cp.body;
     r.cp_r = cp.radius;
     for (int k = 0; k < 3; ++k) r.cp_pos[k] = cp.pos[k];
@@ -588,9 +588,9 @@ __device__ __forceinline__ void wc_wall_contacts(const LsCtx& cx, WaveShared& sh
 }
 #endif
 // returns whether any point of the wave took the wall path (GPU: wave-uniform; lane emulator: this lane's point)
-LS_FN bool ph_collide(const LsCtx& cx, WaveShared& sh, LaneRegs& r, int lane) {
+LS_FN bool ph_collide(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, LaneRegs& r, int lane) {
     r.cp_active = 0;
-    const bool has = lane < cx.model.num_collision_points;
+    const bool has = lane < rb.model.num_collision_points;
     const int b = r.cp_body;
     const float cp_r = r.cp_r;
     V3 pw = mul(m3p(sh.R[b]), v3(r.cp_pos[0], r.cp_pos[1], r.cp_pos[2])) + v3p(sh.p[b]);

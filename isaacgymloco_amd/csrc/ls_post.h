@@ -13,8 +13,8 @@ LS_FN float ls_draw(const LsCtx& cx, int env, uint32_t stepw, uint32_t tag, uint
 
 // body index of foot f for a per-lane f: four uniform (scalar) loads and selects -- indexing the model table in global memory by a lane
 // value is a vector load, and behind the post-physics stack's stores it waits for all of them (vmcnt retires in order)
-LS_FN int ls_foot_body(const LsCtx& cx, int f) {
-    const int b0 = cx.model.feet_bodies[0], b1 = cx.model.feet_bodies[1], b2 = cx.model.feet_bodies[2], b3 = cx.model.feet_bodies[3];
+LS_FN int ls_foot_body(const LsRobot& rb, int f) {
+    const int b0 = rb.model.feet_bodies[0], b1 = rb.model.feet_bodies[1], b2 = rb.model.feet_bodies[2], b3 = rb.model.feet_bodies[3];
     return f == 0 ? b0 : (f == 1 ? b1 : (f == 2 ? b2 : b3));
 }
 
@@ -192,7 +192,7 @@ LS_FN void ls_resample_commands_u(const LsCtx& cx, int env, const float* u, cons
 }
 
 // ---- Q1: derived base state, contact filter, episode counter (LR:193-209)
-LS_FN void ph_post_state(const LsCtx& cx, WaveShared& sh, int lane, int env) {
+LS_FN void ph_post_state(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, int lane, int env) {
     if (lane == 0) {
         const int v = sh.pre_eplen + 1;
         LSB(cx, LSIM_BUF_EPISODE_LENGTH, int64_t)[env] = (int64_t)v;
@@ -209,7 +209,7 @@ LS_FN void ph_post_state(const LsCtx& cx, WaveShared& sh, int lane, int env) {
     } else if (lane < 8) {
         int f = lane - 4;
         const uint8_t lc = (uint8_t)((sh.pre_lc >> (8 * f)) & 0xffu);
-        uint8_t contact = sh.cf[ls_foot_body(cx, f)][2] > 1.0f;
+        uint8_t contact = sh.cf[ls_foot_body(rb, f)][2] > 1.0f;
         const uint8_t filt = contact | lc;
         sh.filt[f] = filt;
         LSB(cx, LSIM_BUF_CONTACT_FILT, uint8_t)[4 * env + f] = filt;
@@ -251,12 +251,12 @@ LS_FN void ph_callback(const LsCtx& cx, WaveShared& sh, int lane, int env, const
 }
 
 // ---- Q4: check_termination (LR:249-286), lane 0
-LS_FN void ph_termination(const LsCtx& cx, WaveShared& sh, int lane, int env) {
+LS_FN void ph_termination(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, int lane, int env) {
     if (lane != 0) return;
     const lsim_config& c = cx.cfg;
     int r = 0;
     for (int b = 0; b < LS_NB; ++b)
-        if ((cx.model.termination_body_mask >> b) & 1u) {
+        if ((rb.model.termination_body_mask >> b) & 1u) {
             V3 f = v3p(sh.cf[b]);
             if (sqrtf(dot(f, f)) > 1.0f) r = 1;
         }
@@ -292,18 +292,18 @@ LS_FN float ls_cmd_norm(const WaveShared& sh) { return sqrtf(sh.cmd[0] * sh.cmd[
 //      each (ph_reward_parts: lane = (term, part) pair from a host-built item table), then the term's lane adds them up IN THE ORDER of the
 //      reference's torch.sum and applies the term's factor (ph_reward_terms).  One lane per term alone ran all 21 term bodies one after the
 //      other -- 12-joint loops on a single lane each -- a tenth of kernel A's instructions.
-LS_FN float ls_foot_slide_part(const LsCtx& cx, const WaveShared& sh, const LsRewCtx& x, bool with_height, int f) {  // LR:1610-1619 / LR:1682-1698
+LS_FN float ls_foot_slide_part(const LsCtx& cx, const LsRobot& rb, const WaveShared& sh, const LsRewCtx& x, bool with_height, int f) {  // LR:1610-1619 / LR:1682-1698
     const float* bs = sh.feet[f];
     V3 vb = quat_rotate_inverse(sh.root + 3, v3(bs[3] - sh.root[7], bs[4] - sh.root[8], bs[5] - sh.root[9]));
     float lat = sqrtf(vb.x * vb.x + vb.y * vb.y);
     if (with_height) {
         V3 pb = quat_rotate_inverse(sh.root + 3, v3(bs[0] - sh.root[0], bs[1] - sh.root[1], bs[2] - sh.root[2]));
-        float he = pb.z - cx.cfg.foot_height_target_base;
+        float he = pb.z - rb.foot_height_target_base;
         return (he * he) * lat;
     }
     return (x.filt[f] ? 1.0f : 0.0f) * lat;
 }
-LS_FN float ls_foot_clearance_terrain_part(const LsCtx& cx, const WaveShared& sh, int shifts, int f) {  // LR:1717-1743 incl. quirk 3 (in-place += border)
+LS_FN float ls_foot_clearance_terrain_part(const LsCtx& cx, const LsRobot& rb, const WaveShared& sh, int shifts, int f) {  // LR:1717-1743 incl. quirk 3 (in-place += border)
     const lsim_config& c = cx.cfg;
     const float* bs = sh.feet[f];
     float fh;
@@ -320,14 +320,14 @@ LS_FN float ls_foot_clearance_terrain_part(const LsCtx& cx, const WaveShared& sh
         fh = pz - (float)h * c.vertical_scale;
     }
     float lat = sqrtf(bs[3] * bs[3] + bs[4] * bs[4]);
-    float d = fh - c.foot_height_target_terrain;
+    float d = fh - rb.foot_height_target_terrain;
     return lat * (d * d);
 }
-LS_FN float ls_stumble(const LsCtx& cx, const WaveShared& sh, int env, float ratio) {  // LR:1589-1608
+LS_FN float ls_stumble(const LsCtx& cx, const LsRobot& rb, const WaveShared& sh, int env, float ratio) {  // LR:1589-1608
     const lsim_config& c = cx.cfg;
     int any = 0;
     for (int f = 0; f < 4; ++f) {
-        const float* F = sh.cf[cx.model.feet_bodies[f]];
+        const float* F = sh.cf[rb.model.feet_bodies[f]];
         if (sqrtf(F[0] * F[0] + F[1] * F[1]) > ratio * fabsf(F[2])) any = 1;
     }
     float r = (any && sh.pre_level > 3) ? 1.0f : 0.0f;
@@ -344,7 +344,7 @@ LS_FN float ls_var12(const float* v) {
 }
 
 // part j of term id: one summand of the `_reward_<name>()` (LR:1444-1770)
-LS_FN float ls_reward_part(const LsCtx& cx, WaveShared& sh, const LsRewCtx& x, int id, int j, int env, int fct_shifts) {
+LS_FN float ls_reward_part(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, const LsRewCtx& x, int id, int j, int env, int fct_shifts) {
     const lsim_config& c = cx.cfg;
     const float dt = c.sim_dt * (float)c.decimation;
     switch (id) {
@@ -385,22 +385,22 @@ LS_FN float ls_reward_part(const LsCtx& cx, WaveShared& sh, const LsRewCtx& x, i
         case LSIM_R_FEET_AIR_TIME: {  // LR:1459-1470 (mutates last_contacts and feet_air_time)
             // quirk 2: the reference recomputes contact | last_contacts here AFTER post_physics_step already set last_contacts = contact
             // (LR:207-209), so the filter of this term is the raw contact flag and rewriting last_contacts changes nothing
-            const bool contact = sh.cf[ls_foot_body(cx, j)][2] > 1.0f;
+            const bool contact = sh.cf[ls_foot_body(rb, j)][2] > 1.0f;
             float a = sh.pre_air[j];
             const float first = (a > 0.0f && contact) ? 1.0f : 0.0f;
             a += dt;
             LSB(cx, LSIM_BUF_FEET_AIR_TIME, float)[4 * env + j] = a * (contact ? 0.0f : 1.0f);
             return (a - 0.5f) * first;
         }
-        case LSIM_R_FEET_CONTACT_FORCES: { V3 F = v3p(sh.cf[ls_foot_body(cx, j)]); return fmaxf(sqrtf(dot(F, F)) - c.max_contact_force, 0.0f); }
-        case LSIM_R_FEET_SLIDE: case LSIM_R_FEET_SLIDE_UP: return ls_foot_slide_part(cx, sh, x, false, j);
-        case LSIM_R_FOOT_CLEARANCE_BASE: case LSIM_R_FOOT_CLEARANCE_BASE_UP: return ls_foot_slide_part(cx, sh, x, true, j);
-        case LSIM_R_FOOT_CLEARANCE_TERRAIN: case LSIM_R_FOOT_CLEARANCE_TERRAIN_UP: return ls_foot_clearance_terrain_part(cx, sh, fct_shifts, j);
+        case LSIM_R_FEET_CONTACT_FORCES: { V3 F = v3p(sh.cf[ls_foot_body(rb, j)]); return fmaxf(sqrtf(dot(F, F)) - c.max_contact_force, 0.0f); }
+        case LSIM_R_FEET_SLIDE: case LSIM_R_FEET_SLIDE_UP: return ls_foot_slide_part(cx, rb, sh, x, false, j);
+        case LSIM_R_FOOT_CLEARANCE_BASE: case LSIM_R_FOOT_CLEARANCE_BASE_UP: return ls_foot_slide_part(cx, rb, sh, x, true, j);
+        case LSIM_R_FOOT_CLEARANCE_TERRAIN: case LSIM_R_FOOT_CLEARANCE_TERRAIN_UP: return ls_foot_clearance_terrain_part(cx, rb, sh, fct_shifts, j);
         default: return 0.0f;
     }
 }
 // a term with parts from its n parts p[0..n) (added in index order: the order of the reference's reductions)
-LS_FN float ls_reward_finish(const LsCtx& cx, const WaveShared& sh, int id, const float* p, int n) {
+LS_FN float ls_reward_finish(const LsCtx& cx, const LsRobot& rb, const WaveShared& sh, int id, const float* p, int n) {
     const lsim_config& c = cx.cfg;
     if (id == LSIM_R_TORQUES_DISTRIBUTION || id == LSIM_R_POWER_DISTRIBUTION) return ls_var12(p);
     float acc = 0.0f;
@@ -409,7 +409,7 @@ LS_FN float ls_reward_finish(const LsCtx& cx, const WaveShared& sh, int id, cons
         case LSIM_R_BASE_HEIGHT:
         case LSIM_R_BASE_HEIGHT_UP: {
             const float bh = c.mesh_type == 0 ? sh.root[2] : acc / 63.0f;
-            const float d = bh - c.base_height_target;
+            const float d = bh - rb.base_height_target;
             return id == LSIM_R_BASE_HEIGHT ? d * d : d * d * ls_up(sh);
         }
         case LSIM_R_STAND_STILL: return acc * ((ls_cmd_norm(sh) < 0.1f) ? 1.0f : 0.0f);
@@ -422,7 +422,7 @@ LS_FN float ls_reward_finish(const LsCtx& cx, const WaveShared& sh, int id, cons
     }
 }
 // a scalar `_reward_<name>()` (LR:1444-1770)
-LS_FN float ls_reward_scalar(const LsCtx& cx, WaveShared& sh, const LsRewCtx& x, int id, int env) {
+LS_FN float ls_reward_scalar(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, const LsRewCtx& x, int id, int env) {
     const lsim_config& c = cx.cfg;
     float acc = 0.0f;
     switch (id) {
@@ -447,11 +447,11 @@ LS_FN float ls_reward_scalar(const LsCtx& cx, WaveShared& sh, const LsRewCtx& x,
         case LSIM_R_COLLISION:
         case LSIM_R_COLLISION_UP:
             for (int b = 0; b < LS_NB; ++b)
-                if ((cx.model.penalised_body_mask >> b) & 1u) { V3 f = v3p(sh.cf[b]); acc += (sqrtf(dot(f, f)) > 0.1f) ? 1.0f : 0.0f; }
+                if ((rb.model.penalised_body_mask >> b) & 1u) { V3 f = v3p(sh.cf[b]); acc += (sqrtf(dot(f, f)) > 0.1f) ? 1.0f : 0.0f; }
             return id == LSIM_R_COLLISION ? acc : acc * ls_up(sh);
         case LSIM_R_TERMINATION: return (sh.reset && !sh.timeout) ? 1.0f : 0.0f;
-        case LSIM_R_FEET_STUMBLE: return ls_stumble(cx, sh, env, 5.0f);
-        case LSIM_R_FEET_STUMBLE_UP: return ls_stumble(cx, sh, env, 4.0f) * ls_up(sh);
+        case LSIM_R_FEET_STUMBLE: return ls_stumble(cx, rb, sh, env, 5.0f);
+        case LSIM_R_FEET_STUMBLE_UP: return ls_stumble(cx, rb, sh, env, 4.0f) * ls_up(sh);
         case LSIM_R_FEET_MIRROR:
         case LSIM_R_FEET_MIRROR_UP: {
             const float* d = x.dof;
@@ -483,7 +483,7 @@ LS_FN int ls_fct_shifts(const LsCtx& cx, int id) {
 }
 // ---- Q5a: the parts of the terms that have them.  Item = (term id << 10) | (term's index in the active list << 4) | part, built by the host
 //      (ls_api_impl.h) and staged in LDS by ph_load_a; same-term items are neighbours, so a pass of 64 lanes runs only a few term bodies.
-LS_FN void ph_reward_parts(const LsCtx& cx, WaveShared& sh, const uint16_t* items, int lane, int env) {
+LS_FN void ph_reward_parts(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, const uint16_t* items, int lane, int env) {
     const LsRewCtx x = ls_rew_ctx(sh);
     for (int it = 0; it < (LS_MAX_PART_ITEMS + 63) / 64; ++it) {
         const int k = lane + 64 * it;
@@ -491,22 +491,22 @@ LS_FN void ph_reward_parts(const LsCtx& cx, WaveShared& sh, const uint16_t* item
         if (k >= cx.num_part_items) continue;
         const int item = items[k];
         const int id = item >> 10, ai = (item >> 4) & 63, j = item & 15;
-        sh.u.r.rj[ai][j] = ls_reward_part(cx, sh, x, id, j, env, ls_fct_shifts(cx, id));
+        sh.u.r.rj[ai][j] = ls_reward_part(cx, rb, sh, x, id, j, env, ls_fct_shifts(cx, id));
     }
 }
 // ---- Q5b: compute_reward (LR:363-380).  Lane i owns active term i; lane 0 then accumulates in the reference's order.
-LS_FN void ph_reward_terms(const LsCtx& cx, WaveShared& sh, const LaneRegs& rg, int lane, int env) {
+LS_FN void ph_reward_terms(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, const LaneRegs& rg, int lane, int env) {
     if (lane >= cx.num_active) return;
     const int id = rg.term_id;                   // cx.active_terms[lane], fetched by ph_late_load
     const LsRewCtx x = ls_rew_ctx(sh);
     const int n = ls_reward_num_parts(id);
     float v;
-    if (n == 0) v = ls_reward_scalar(cx, sh, x, id, env);
+    if (n == 0) v = ls_reward_scalar(cx, rb, sh, x, id, env);
     else {
         float* p = sh.u.r.rj[lane];
         if (!((cx.parted_mask >> lane) & 1ull))      // more parts than the item table holds (every term switched on): this lane does its own
-            for (int j = 0; j < n; ++j) p[j] = ls_reward_part(cx, sh, x, id, j, env, ls_fct_shifts(cx, id));
-        v = ls_reward_finish(cx, sh, id, p, n);
+            for (int j = 0; j < n; ++j) p[j] = ls_reward_part(cx, rb, sh, x, id, j, env, ls_fct_shifts(cx, id));
+        v = ls_reward_finish(cx, rb, sh, id, p, n);
     }
     v *= rg.term_scale;                          // cx.cfg.reward_scales[id]
     sh.rewv[lane] = v;

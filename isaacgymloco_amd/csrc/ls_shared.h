@@ -47,10 +47,22 @@ LS_FN int ls_reward_num_parts(int id) {
     }
 }
 
+// the robot-specific values of one robot of an instance (include/lsim.h, "robot-specific set"): its model and the lsim_config fields that
+// may differ between the robots of a mixed instance.  The kernels read them through the env's entry of LsCtx::robots with a wave-uniform
+// index, never through LsCtx::cfg (whose copies of these fields are robot 0's)
+struct LsRobot {
+    lsim_robot_model model;
+    float action_scale, hip_reduction;
+    float p_gains[LSIM_NUM_DOF], d_gains[LSIM_NUM_DOF], torque_limits[LSIM_NUM_DOF], default_dof_pos[LSIM_NUM_DOF];
+    float base_init_state[13];
+    float base_height_target, foot_height_target_base, foot_height_target_terrain;
+};
+
 // constant per simulator instance; lives in device global memory, read through uniform (scalar) loads
 struct LsCtx {
     lsim_config cfg;
-    lsim_robot_model model;
+    LsRobot robots[LSIM_MAX_ROBOTS];
+    const uint8_t* env_robot;         // [num_envs] robot of each env (lsim_create_mixed); null: every env simulates robots[0]
     void* buf[LSIM_NUM_BUFFERS];
     float* accum;                     // [2][LSIM_STATS_SIZE] ping-pong per-step reductions (== buf[LSIM_BUF_STATS])
     int32_t active_terms[LSIM_NUM_REWARD_TERMS];

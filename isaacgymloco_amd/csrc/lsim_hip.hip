@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64) void lsim_k_debug_kin(const LsCtx* __restrict__
     if (lane < 13) sh.root[lane] = in[lane];
     if (lane < 12) { sh.q[lane] = in[13 + lane]; sh.qd[lane] = in[25 + lane]; }
     if (lane >= 16 && lane < 16 + LS_NB) {
-        const lsim_body& b = cx.model.bodies[lane - 16];
+        const lsim_body& b = cx.robots[0].model.bodies[lane - 16];
         LsBodyLds& o = sh.body[lane - 16];
         o.mass = b.mass;
         for (int k = 0; k < 3; ++k) { o.com[k] = b.com[k]; o.jpos[k] = b.joint_pos[k]; o.axis[k] = b.joint_axis[k]; }

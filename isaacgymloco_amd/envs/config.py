@@ -330,3 +330,108 @@ TASKS = {
     "aliengo_amp": (aliengo_amp_cfg, aliengo_amp_cfg_ppo),
     "aliengo_recover": (aliengo_recover_cfg, aliengo_recover_cfg_ppo),
 }
+
+
+# ----------------------------------------------------------------------------- several robots in one environment instance
+# The robot-specific set: the only config keys in which the robots of one mixed instance may differ (include/lsim.h, lsim_create_mixed,
+# lists the lsim_config fields they flatten into).  It is exactly what GO1_OVERRIDES / GO2_OVERRIDES change on the Aliengo task.
+MAX_ROBOTS = 4     # LSIM_MAX_ROBOTS
+ROBOT_SPECIFIC_KEYS = ("asset", "init_state", "control.stiffness", "control.damping", "control.action_scale", "control.hip_reduction",
+                       "rewards.base_height_target", "rewards.foot_height_target_base", "rewards.foot_height_target_terrain")
+
+
+def is_robot_specific(key):
+    """whether the dotted config key lies in the robot-specific set"""
+    return any(key == k or key.startswith(k + ".") for k in ROBOT_SPECIFIC_KEYS)
+
+
+def _flat(d, prefix=""):
+    out = {}
+    for k, v in d.items():
+        key = prefix + str(k)
+        if isinstance(v, dict) and v:
+            out.update(_flat(v, key + "."))
+        else:
+            out[key] = v
+    return out
+
+
+def _node_get(node, key):
+    for part in key.split("."):
+        if not hasattr(node, part):
+            return None
+        node = getattr(node, part)
+    return node
+
+
+def _node_set(node, key, value):
+    *parents, last = key.split(".")
+    for part in parents:
+        node = getattr(node, part)
+    setattr(node, last, copy.deepcopy(value))
+
+
+def uses_amp(train_cfg):
+    runner = getattr(train_cfg, "runner", None)
+    return getattr(train_cfg, "runner_class_name", "") == "HybridPolicyRunner" or bool(getattr(runner, "amp_motion_files", None))
+
+
+def mixed_cfg(task, robots):
+    """One environment instance that simulates several quadrupeds: mixed_cfg("aliengo", {"aliengo": 0.5, "go2": 0.5}).
+
+    `task` is the base task (everything outside the robot-specific set comes from it); `robots` maps single-robot task names of TASKS to
+    the fraction of envs that simulate that robot (LeggedRobot assigns them with assign_robots).  Returns (env_cfg, train_cfg): the base
+    task's configs, env_cfg with `robots` = [{"name", "fraction", "overrides"}] where overrides maps each robot-specific key to the robot's
+    value.  ValueError if a robot's task differs from the base task outside the robot-specific set (naming the key), if the fractions do not
+    sum to 1, or if the task trains with AMP (its mocap clips and discriminator are one robot's)."""
+    if task not in TASKS:
+        raise ValueError(f"unknown task {task!r}")
+    robots = dict(robots)
+    if not 1 <= len(robots) <= MAX_ROBOTS:
+        raise ValueError(f"a mixed instance holds 1..{MAX_ROBOTS} robots, got {len(robots)}")
+    for name, f in robots.items():
+        if name not in TASKS:
+            raise ValueError(f"unknown robot task {name!r}")
+        if not f > 0:
+            raise ValueError(f"robot {name!r}: fraction {f} must be positive")
+    if abs(sum(robots.values()) - 1.0) > 1e-6:
+        raise ValueError(f"robot fractions sum to {sum(robots.values())}, not 1")
+    env_cfg, train_cfg = TASKS[task][0](), TASKS[task][1]()
+    if uses_amp(train_cfg):
+        raise ValueError(f"task {task!r} uses AMP: its motion clips and discriminator are one robot's, mixed robots are not supported")
+    base = _flat(env_cfg.to_dict())
+    entries = []
+    for name, f in robots.items():
+        rcfg = TASKS[name][0]()
+        other = _flat(rcfg.to_dict())
+        for key in sorted(set(base) | set(other)):
+            if not is_robot_specific(key) and (key not in base or key not in other or base[key] != other[key]):
+                raise ValueError(f"robot {name!r} differs from task {task!r} outside the robot-specific set: {key}")
+        entries.append({"name": name, "fraction": float(f),
+                        "overrides": {k: copy.deepcopy(_node_get(rcfg, k)) for k in ROBOT_SPECIFIC_KEYS if _node_get(rcfg, k) is not None}})
+    env_cfg.robots = entries
+    return env_cfg, train_cfg
+
+
+def robot_cfg(env_cfg, k):
+    """the single-robot config of robot k of a mixed env_cfg: the shared config with that robot's robot-specific values"""
+    cfg = copy.deepcopy(env_cfg)
+    entry = cfg.robots[k]
+    del cfg.robots
+    for key, value in entry["overrides"].items():
+        _node_set(cfg, key, value)
+    return cfg
+
+
+def assign_robots(num_envs, fractions):
+    """robot of each env, interleaved: largest remainder over the prefix, so that after the first e envs robot k holds round(e * f_k) of
+    them give or take one.  Envs are cut into terrain columns and other index-based slices in contiguous blocks (lsim_terrain_type_of_env):
+    a block assignment would put each robot on its own terrain types.  Deterministic; returns a list of robot indices."""
+    count = [0] * len(fractions)
+    out = []
+    for e in range(num_envs):
+        # the robot furthest behind its share after this env (ties: the lower index)
+        k = max(range(len(fractions)), key=lambda i: ((e + 1) * fractions[i] - count[i], -i))
+        count[k] += 1
+        out.append(k)
+    return out

@@ -13,6 +13,7 @@ by the HIP kernels behind include/lsim.h (isaacgymloco_amd/csrc); this file only
 the current torch stream and assembles the reference's return tuple.  There is no CPU fallback.
 """
 import ctypes
+import hashlib
 import os
 
 import numpy as np
@@ -23,6 +24,7 @@ from ..robots import aliengo
 
 
 from ..robots.model import build_robot_model  # noqa: E402,F401  (lives in robots/model.py: importable without torch)
+from . import config as C
 from . import lsim_config as LC
 from .terrain import Terrain
 
@@ -66,8 +68,14 @@ class LeggedRobot:
         dev = torch.device(sim_device)
         self._dev_index = dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else 0)
         self.terrain = terrain if terrain is not None else Terrain(cfg.terrain, self.num_envs, seed=seed if terrain_seed is None else terrain_seed)
-        self.model = build_robot_model(cfg.asset)
-        self.lcfg = LC.make_lsim_config(cfg, num_envs=self.num_envs, terrain=self.terrain, model=self.model, seed=seed, rank=rank, using_amp=using_amp)
+        # several robots in one instance (config.mixed_cfg): one model and config per robot, robot k's config = the shared one with k's
+        # robot-specific values; self.model / self.lcfg are robot 0's
+        self.robots = getattr(cfg, "robots", None)
+        if self.robots is not None:
+            self._setup_robots(seed, rank)
+        else:
+            self.model = build_robot_model(cfg.asset)
+            self.lcfg = LC.make_lsim_config(cfg, num_envs=self.num_envs, terrain=self.terrain, model=self.model, seed=seed, rank=rank, using_amp=using_amp)
 
         nbytes = ctypes.c_size_t()
         lib.check(self._L.lsim_query_arena(ctypes.byref(self.lcfg), ctypes.byref(nbytes)), what="lsim_query_arena")
@@ -79,8 +87,15 @@ class LeggedRobot:
             grid_p, orig_p = self._grid.ctypes.data, self._orig.ctypes.data
         self._h = ctypes.c_void_p()
         self._sync()
-        lib.check(self._L.lsim_create(ctypes.byref(self.lcfg), ctypes.byref(self.model), grid_p, orig_p,
-                                      self._arena.data_ptr(), self._dev_index, ctypes.byref(self._h)), what="lsim_create")
+        if self.robots is None:
+            lib.check(self._L.lsim_create(ctypes.byref(self.lcfg), ctypes.byref(self.model), grid_p, orig_p,
+                                          self._arena.data_ptr(), self._dev_index, ctypes.byref(self._h)), what="lsim_create")
+        else:
+            R = len(self._robot_models)
+            cfgs = (abi.LsimConfig * R)(*self._robot_lcfgs)
+            models = (abi.LsimRobotModel * R)(*self._robot_models)
+            lib.check(self._L.lsim_create_mixed(cfgs, models, R, self._env_robot.ctypes.data, grid_p, orig_p,
+                                                self._arena.data_ptr(), self._dev_index, ctypes.byref(self._h)), what="lsim_create_mixed")
         self._sync()
         self._bind_buffers()
         self.extras = {}
@@ -91,6 +106,23 @@ class LeggedRobot:
         self.extras["nonfinite_envs"] = self.nonfinite_envs
         self.common_step_counter = 0
         self.init_done = True
+
+    def _setup_robots(self, seed, rank):
+        if self.using_amp and len(self.robots) > 1:
+            raise ValueError("AMP with more than one robot: the motion clips and the discriminator are one robot's")
+        cfgs = [C.robot_cfg(self.cfg, k) for k in range(len(self.robots))]
+        self._robot_models = [build_robot_model(c.asset) for c in cfgs]
+        self._robot_lcfgs = [LC.make_lsim_config(c, num_envs=self.num_envs, terrain=self.terrain, model=m, seed=seed, rank=rank, using_amp=self.using_amp)
+                             for c, m in zip(cfgs, self._robot_models)]
+        m0 = self._robot_models[0]
+        for r, m in zip(self.robots, self._robot_models):
+            for key in ("feet_bodies", "penalised_body_mask", "termination_body_mask"):
+                a, b = getattr(m0, key), getattr(m, key)
+                a, b = (list(a), list(b)) if key == "feet_bodies" else (int(a), int(b))
+                if a != b:
+                    raise ValueError(f"robot {r['name']!r}: {key} differs from robot {self.robots[0]['name']!r}'s ({b} vs {a}); the env's index tensors are shared")
+        self._env_robot = np.ascontiguousarray(C.assign_robots(self.num_envs, [r["fraction"] for r in self.robots]), dtype=np.uint8)
+        self.model, self.lcfg = m0, self._robot_lcfgs[0]
 
     # ------------------------------------------------------------------ the simulator behind this object
     def _load_library(self):
@@ -150,15 +182,27 @@ class LeggedRobot:
         self.feet_indices = torch.tensor(list(self.model.feet_bodies), dtype=torch.long, device=dev)
         self.penalised_contact_indices = torch.tensor([i for i in range(17) if (self.model.penalised_body_mask >> i) & 1], dtype=torch.long, device=dev)
         self.termination_contact_indices = torch.tensor([i for i in range(17) if (self.model.termination_body_mask >> i) & 1], dtype=torch.long, device=dev)
-        self.default_dof_pos = torch.tensor([self.lcfg.default_dof_pos[i] for i in range(12)], device=dev).unsqueeze(0)
-        self.p_gains = torch.tensor([self.lcfg.p_gains[i] for i in range(12)], device=dev)
-        self.d_gains = torch.tensor([self.lcfg.d_gains[i] for i in range(12)], device=dev)
-        self.torque_limits = torch.tensor([self.model.dof_effort_limit[i] for i in range(12)], device=dev)
-        self.dof_vel_limits = torch.tensor([self.model.dof_vel_limit[i] for i in range(12)], device=dev)
-        lim = torch.tensor([[self.model.dof_pos_lower[i], self.model.dof_pos_upper[i]] for i in range(12)], device=dev)
+        if self.robots is None:
+            q0, self.p_gains, self.d_gains, self.torque_limits, self.dof_vel_limits, self.dof_pos_limits = self._joint_constants(self.lcfg, self.model, dev)
+            self.default_dof_pos = q0.unsqueeze(0)
+        else:       # per env (N, 12) / (N, 12, 2): the rows of each env's robot
+            self.robot_ids = torch.as_tensor(self._env_robot, dtype=torch.long, device=dev)
+            self.robot_names = [r["name"] for r in self.robots]
+            per = [self._joint_constants(lc, m, dev) for lc, m in zip(self._robot_lcfgs, self._robot_models)]
+            (self.default_dof_pos, self.p_gains, self.d_gains, self.torque_limits, self.dof_vel_limits,
+             self.dof_pos_limits) = (torch.stack(t)[self.robot_ids] for t in zip(*per))
+
+    def _joint_constants(self, lcfg, model, dev):
+        """default pose, gains, torque / velocity limits (12,) and soft position limits (12, 2) of one robot"""
+        q0 = torch.tensor([lcfg.default_dof_pos[i] for i in range(12)], device=dev)
+        kp = torch.tensor([lcfg.p_gains[i] for i in range(12)], device=dev)
+        kd = torch.tensor([lcfg.d_gains[i] for i in range(12)], device=dev)
+        tau = torch.tensor([model.dof_effort_limit[i] for i in range(12)], device=dev)
+        vel = torch.tensor([model.dof_vel_limit[i] for i in range(12)], device=dev)
+        lim = torch.tensor([[model.dof_pos_lower[i], model.dof_pos_upper[i]] for i in range(12)], device=dev)
         m, r = (lim[:, 0] + lim[:, 1]) / 2, lim[:, 1] - lim[:, 0]          # soft limits, LR:574-578
         s = self.cfg.rewards.soft_dof_pos_limit
-        self.dof_pos_limits = torch.stack((m - 0.5 * r * s, m + 0.5 * r * s), dim=1)
+        return q0, kp, kd, tau, vel, torch.stack((m - 0.5 * r * s, m + 0.5 * r * s), dim=1)
 
     @property
     def episode_length_buf(self):
@@ -302,13 +346,19 @@ class LeggedRobot:
     def _conventions(self):
         from .. import abi
         c = self.lcfg
-        return {"abi_version": int(abi.ABI_VERSION), "lin_vel_at_com": int(c.lin_vel_at_com), "tgs_limit_passes": int(c.tgs_limit_passes),
+        conv = {"abi_version": int(abi.ABI_VERSION), "lin_vel_at_com": int(c.lin_vel_at_com), "tgs_limit_passes": int(c.tgs_limit_passes),
                 "solver_type": int(c.solver_type), "num_position_iterations": int(c.num_position_iterations)}
+        if self.robots is not None:     # the robot mix: names, fractions and which env simulates which robot
+            digest = hashlib.sha256(self._env_robot.tobytes()).hexdigest()[:16]
+            conv["robots"] = {"names": [r["name"] for r in self.robots], "fractions": [float(r["fraction"]) for r in self.robots], "assignment": digest}
+        return conv
 
     def load_state_dict(self, d):
         from .. import abi
         import warnings
         conv, live = d.get("conventions"), self._conventions()
+        if (conv or {}).get("robots") != live.get("robots"):
+            raise ValueError(f"simulator state was saved with another robot mix: robots {(conv or {}).get('robots')}, live {live.get('robots')}")
         if conv is None:
             warnings.warn("simulator state saved before round 6: it does not record the conventions it was trained under (centre-of-mass vs link-origin "
                           f"linear velocities, TGS limit passes); this simulator runs {live} -- LSIM_LIN_VEL=origin LSIM_TGS_LIMIT_PASSES=0 restore rounds 1-4")

@@ -34,6 +34,7 @@ def load_path(path):
     vp, i32, u32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_int64
     L.lsim_query_arena.argtypes = [ctypes.POINTER(abi.LsimConfig), ctypes.POINTER(ctypes.c_size_t)]
     L.lsim_create.argtypes = [ctypes.POINTER(abi.LsimConfig), ctypes.POINTER(abi.LsimRobotModel), vp, vp, vp, i32, ctypes.POINTER(vp)]
+    L.lsim_create_mixed.argtypes = [ctypes.POINTER(abi.LsimConfig), ctypes.POINTER(abi.LsimRobotModel), i32, vp, vp, vp, vp, i32, ctypes.POINTER(vp)]
     L.lsim_get_buffer.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.lsim_reset_all.argtypes = [vp, vp]
     L.lsim_reset_envs.argtypes = [vp, vp, vp]
