@@ -33,10 +33,11 @@
 extern "C" {
 #endif
 
-#define LSIM_ABI_VERSION 6   /* 2: LSIM_BUF_CONTACT_COUNT, fixed-point words in LSIM_BUF_STATS (round 2); 3: LSIM_BUF_SUBSTEP_TORQUES (round 3);
+#define LSIM_ABI_VERSION 7   /* 2: LSIM_BUF_CONTACT_COUNT, fixed-point words in LSIM_BUF_STATS (round 2); 3: LSIM_BUF_SUBSTEP_TORQUES (round 3);
                                  4: lsim_config.solver_type / num_position_iterations out of the reserved words (round 4);
                                  5: lsim_config.lin_vel_at_com (centre-of-mass linear velocities, the PhysX convention) and tgs_limit_passes, lsim_get / set_reset_calls (round 5);
-                                 6: LSIM_BUF_NONFINITE + LSIM_STATS_NONFINITE (robots whose simulated state is not finite), lsim_amp_step and the discriminator-update kernels (round 6) */
+                                 6: LSIM_BUF_NONFINITE + LSIM_STATS_NONFINITE (robots whose simulated state is not finite), lsim_amp_step and the discriminator-update kernels (round 6);
+                                 7: lsim_eval + lsim_eval_sizes / lsim_eval_clear / lsim_eval_accumulate (device-side policy evaluation: grouped metrics and state traces); no earlier struct or entry changed */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -799,6 +800,127 @@ int lsim_adam_clip_step_ex(int count, const int64_t* numel, float* const* params
  * ld_obs / ld_enc (floats).  No gradient flows through this (the estimator's outputs are detached there). */
 int lsim_actor_input(const float* obs, int64_t ld_obs, int num_one_step_obs, const float* enc_out, int64_t ld_enc, int latent,
                      int64_t batch, float* out, void* stream);
+
+/* ---- policy evaluation on the device: grouped metrics and state traces (no reference FFI; the reference evaluates in
+ * legged_gym/scripts/play.py:124-164 with .item() reads of one robot and the means of extras["episode"]).
+ * ONE launch per env-step, after lsim_step, on the caller's stream, no host synchronisation, capturable in a single-stream graph.
+ * The evaluator only READS the simulator's buffers; it works on raw device pointers (this struct, filled by the caller from
+ * lsim_get_buffer and its own per-env constants), not on the lsim_handle.
+ *
+ * Group of an env = ((robot * num_types) + terrain_type) * num_levels + terrain_level, where a factor whose LSIM_EVAL_BY_* bit is NOT set in
+ * `group_by` counts as 0 and its extent as 1 (num_groups = product of the kept extents).  robot = robot_ids[env] (0 when robot_ids == NULL);
+ * each factor is clamped into [0, extent).  The group is LATCHED when an episode starts: on a reset step terrain_levels already holds the NEXT
+ * episode's level.  After lsim_eval_clear the first lsim_eval_accumulate latches every env from the buffers as they are (group, start position),
+ * so an episode in progress at that moment is counted from there on; clear right after env.reset() for whole episodes.
+ *
+ * Every step, per env, in this order (g = the latched group):
+ *   return_so_far += fix(rew) (int64, exact), length_so_far += 1          -- rew / reset_buf / time_out_buf describe the step that just ended
+ *   reset_buf == 0 -> STEP SAMPLE added to group g (the state buffers hold the state after the step):
+ *       SAMPLES += 1
+ *       e2 = (cmd_x - base_lin_vel_x)^2 + (cmd_y - base_lin_vel_y)^2;  LIN_ERR += sqrt(e2);  LIN_ERR_SQ += e2
+ *       y = |cmd_yaw - base_ang_vel_z|;  YAW_ERR += y;  YAW_ERR_SQ += y * y
+ *       POWER += sum_j |tau_j * qd_j|;  TORQUE_SQ += sum_j tau_j^2;  ACTION_RATE += sum_j (a_j - a_last_j)^2        (sums in joint order 0..11, fp32)
+ *       FEET_CONTACT += number of nonzero contact_filt[env][0..3]
+ *       TORQUE_SAT += number of joints with |tau_j| >= 0.98f * torque_limit_j
+ *       PEAK_TORQUE_RATIO = max(PEAK_TORQUE_RATIO, fix(max_j |tau_j| / torque_limit_j))                                (integer atomicMax)
+ *     then last_position = root_states[env][0..1]
+ *   reset_buf != 0 -> EPISODE RECORD added to group g (the state buffers already hold the post-reset state and are NOT sampled):
+ *       EPISODES += 1;  TIME_OUTS += (time_out_buf != 0);  FALLS += (time_out_buf == 0)
+ *       RETURN += return_so_far (valid on the reset step too: it is the evaluator's own sum of rew);  LENGTH += length_so_far
+ *       DISTANCE += |last_position - start_position| (horizontal; last_position is the last PRE-reset position, so the distance is one
+ *                   step short of the episode's end by construction)
+ *     then return_so_far = length_so_far = 0, g = group from the buffers now, start_position = last_position = root_states[env][0..1]
+ * Accumulators: int64 words, value * 2^32 (fix(v) = llrint(clamp(v, -2^20, 2^20) * 2^32): every addend clamped as in LSIM_BUF_STATS), added with
+ * integer atomics, so equal inputs give bitwise equal tables whatever the order of waves; COUNT words are plain integers.  A non-finite addend
+ * (incl. a non-finite rew or peak candidate) is not added: it increments the group's NONFINITE word instead.  The host divides. */
+#define LSIM_EVAL_BY_ROBOT 1u
+#define LSIM_EVAL_BY_TYPE 2u
+#define LSIM_EVAL_BY_LEVEL 4u
+#define LSIM_EVAL_MAX_GROUPS 4096          /* LSIM_MAX_ROBOTS x LSIM_TERRAIN_TYPES_MAX x LSIM_TERRAIN_LEVELS_MAX */
+#define LSIM_EVAL_MAX_TRACE_ENVS 64
+#define LSIM_EVAL_SAT_PERMILLE 980         /* TORQUE_SAT threshold: |tau| >= 0.98 x limit */
+enum lsim_eval_word {                      /* columns of the table [num_groups, LSIM_EVAL_WORDS] int64; "count" = plain integer, "fix" = value * 2^32 */
+    LSIM_EVAL_W_SAMPLES = 0,               /* count */
+    LSIM_EVAL_W_LIN_ERR,                   /* fix */
+    LSIM_EVAL_W_LIN_ERR_SQ,                /* fix */
+    LSIM_EVAL_W_YAW_ERR,                   /* fix */
+    LSIM_EVAL_W_YAW_ERR_SQ,                /* fix */
+    LSIM_EVAL_W_POWER,                     /* fix */
+    LSIM_EVAL_W_TORQUE_SQ,                 /* fix */
+    LSIM_EVAL_W_ACTION_RATE,               /* fix */
+    LSIM_EVAL_W_FEET_CONTACT,              /* count */
+    LSIM_EVAL_W_TORQUE_SAT,                /* count */
+    LSIM_EVAL_W_PEAK_TORQUE_RATIO,         /* fix, maximum instead of sum */
+    LSIM_EVAL_W_EPISODES,                  /* count */
+    LSIM_EVAL_W_TIME_OUTS,                 /* count */
+    LSIM_EVAL_W_FALLS,                     /* count */
+    LSIM_EVAL_W_RETURN,                    /* fix */
+    LSIM_EVAL_W_LENGTH,                    /* count (env-steps) */
+    LSIM_EVAL_W_DISTANCE,                  /* fix */
+    LSIM_EVAL_W_NONFINITE,                 /* count */
+    LSIM_EVAL_WORDS
+};
+/* Trace ring: row (t mod trace_capacity) of trace [trace_capacity, num_trace_envs, LSIM_EVAL_TRACE_DIM] f32, t = the evaluator's device-side
+ * launch counter (starts at 0 after lsim_eval_clear; the first 8 bytes of `state`, int64).  Columns, for env trace_envs[k] -- the fields of the
+ * reference's Logger.log_states call (play.py:143-158) for ALL joints and feet, then root pose, reward and reset flag (on a reset step the
+ * state columns hold the post-reset state, as the buffers do): */
+#define LSIM_EVAL_TR_DOF_POS_TARGET 0      /* 12: actions * action_scale + default_dof_pos (fp32, product and sum rounded separately or fused) */
+#define LSIM_EVAL_TR_DOF_POS 12            /* 12 */
+#define LSIM_EVAL_TR_DOF_VEL 24            /* 12 */
+#define LSIM_EVAL_TR_TORQUES 36            /* 12 */
+#define LSIM_EVAL_TR_COMMANDS 48           /* 3: x, y, yaw */
+#define LSIM_EVAL_TR_BASE_LIN_VEL 51       /* 3 */
+#define LSIM_EVAL_TR_BASE_ANG_VEL 54       /* 3 */
+#define LSIM_EVAL_TR_CONTACT_FORCES_Z 57   /* 4: contact_forces[env][feet_bodies[i]][2] */
+#define LSIM_EVAL_TR_ROOT_POS 61           /* 3 */
+#define LSIM_EVAL_TR_ROOT_QUAT 64          /* 4: xyzw */
+#define LSIM_EVAL_TR_REW 68                /* 1 */
+#define LSIM_EVAL_TR_RESET 69              /* 1: 0.0 / 1.0 */
+#define LSIM_EVAL_TRACE_DIM 70
+typedef struct lsim_eval {
+    /* simulator buffers (lsim_get_buffer), read only */
+    const float* rew;                 /* [N] */
+    const uint8_t* reset_buf;         /* [N] */
+    const uint8_t* time_out_buf;      /* [N] */
+    const float* commands;            /* [N,4]     16-byte aligned */
+    const float* base_lin_vel;        /* [N,3] */
+    const float* base_ang_vel;        /* [N,3] */
+    const float* root_states;         /* [N,13] */
+    const float* dof_state;           /* [N,12,2]  16-byte aligned */
+    const float* torques;             /* [N,12]    16-byte aligned */
+    const float* actions;             /* [N,12]    16-byte aligned */
+    const float* last_actions;        /* [N,12]    16-byte aligned */
+    const uint8_t* contact_filt;      /* [N,4]     4-byte aligned */
+    const float* contact_forces;      /* [N,17,3] */
+    const int64_t* terrain_types;     /* [N] */
+    const int64_t* terrain_levels;    /* [N] */
+    /* per-env constants of the caller */
+    const uint8_t* robot_ids;         /* [N] or NULL (one robot) */
+    const float* torque_limits;       /* [N,12]    16-byte aligned */
+    const float* default_dof_pos;     /* [N,12]    16-byte aligned */
+    const float* action_scale;        /* [N,12]    16-byte aligned; per joint, hip reduction included */
+    /* evaluator-owned device memory, sizes from lsim_eval_sizes, zeroed by lsim_eval_clear */
+    void* state;                      /* 16-byte aligned */
+    int64_t* table;                   /* [num_groups, LSIM_EVAL_WORDS] */
+    float* trace;                     /* [trace_capacity, num_trace_envs, LSIM_EVAL_TRACE_DIM] or NULL when num_trace_envs == 0 */
+    int32_t num_envs, num_robots, num_types, num_levels;
+    uint32_t group_by;                /* LSIM_EVAL_BY_* bits */
+    int32_t num_groups;               /* must equal the product of the kept extents */
+    int32_t num_trace_envs, trace_capacity;
+    int32_t feet_bodies[LSIM_NUM_LEGS];                 /* rows of contact_forces */
+    int32_t trace_envs[LSIM_EVAL_MAX_TRACE_ENVS];       /* host-side list: checked (< num_envs) before any launch */
+} lsim_eval;
+/* bytes of state / table / trace.  LSIM_E_INVALID: num_envs < 1, num_groups < 1 or > LSIM_EVAL_MAX_GROUPS, num_trace_envs < 0 or
+ * > LSIM_EVAL_MAX_TRACE_ENVS, trace_capacity < 1, a NULL output pointer. */
+int lsim_eval_sizes(int64_t num_envs, int num_groups, int num_trace_envs, int trace_capacity, size_t* state_bytes, size_t* table_bytes,
+                    size_t* trace_bytes);
+/* zero state, table and trace (three memsets on the stream): no group latched, launch counter 0 */
+int lsim_eval_clear(const lsim_eval* e, void* stream);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch: e == NULL, a NULL or misaligned pointer (robot_ids may be
+ * NULL; trace may be NULL only when num_trace_envs == 0), num_envs < 1, num_robots outside 1..LSIM_MAX_ROBOTS, num_types outside
+ * 1..LSIM_TERRAIN_TYPES_MAX, num_levels outside 1..LSIM_TERRAIN_LEVELS_MAX, group_by with unknown bits, num_groups != product of the kept
+ * extents, num_trace_envs outside 0..LSIM_EVAL_MAX_TRACE_ENVS, trace_capacity < 1, a trace env or a feet body out of range. */
+int lsim_eval_accumulate(const lsim_eval* e, void* stream);
 
 #ifdef __cplusplus
 }

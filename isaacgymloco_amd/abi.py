@@ -102,6 +102,7 @@ LsimMlpLayer = STRUCTS["lsim_mlp_layer"]
 LsimHimPolicy = STRUCTS["lsim_him_policy"]
 LsimWgradPending = STRUCTS["lsim_wgrad_pending"]
 LsimAmpDisc = STRUCTS["lsim_amp_disc"]
+LsimEval = STRUCTS["lsim_eval"]
 
 REWARD_IDS = {k[len("LSIM_R_"):].lower(): v for k, v in ENUMS["lsim_reward_id"].items() if k.startswith("LSIM_R_")}
 NUM_REWARD_TERMS = ENUMS["lsim_reward_id"]["LSIM_NUM_REWARD_TERMS"]
@@ -118,6 +119,8 @@ STEP_NO_RESET = DEFINES["LSIM_STEP_NO_RESET"]
 STEP_RECORD_SUBSTEPS = DEFINES["LSIM_STEP_RECORD_SUBSTEPS"]
 STEP_TWO_KERNELS = DEFINES["LSIM_STEP_TWO_KERNELS"]
 STEP_FLAT_PRIORITY = DEFINES["LSIM_STEP_FLAT_PRIORITY"]
+EVAL_WORDS = {k[len("LSIM_EVAL_W_"):].lower(): v for k, v in ENUMS["lsim_eval_word"].items() if k.startswith("LSIM_EVAL_W_")}
+NUM_EVAL_WORDS = ENUMS["lsim_eval_word"]["LSIM_EVAL_WORDS"]
 STATS = {k[len("LSIM_STATS_"):].lower(): v for k, v in DEFINES.items() if k.startswith("LSIM_STATS_")}
 
 

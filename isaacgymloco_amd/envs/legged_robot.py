@@ -182,15 +182,20 @@ class LeggedRobot:
         self.feet_indices = torch.tensor(list(self.model.feet_bodies), dtype=torch.long, device=dev)
         self.penalised_contact_indices = torch.tensor([i for i in range(17) if (self.model.penalised_body_mask >> i) & 1], dtype=torch.long, device=dev)
         self.termination_contact_indices = torch.tensor([i for i in range(17) if (self.model.termination_body_mask >> i) & 1], dtype=torch.long, device=dev)
+        # target angle = action * action_scales + default_dof_pos: the per-joint scale the kernels apply (hip joints times hip_reduction), per env
+        scales = [torch.tensor([lc.action_scale * (lc.hip_reduction if j % 3 == 0 else 1.0) for j in range(12)], dtype=torch.float32, device=dev)
+                  for lc in (self._robot_lcfgs if self.robots is not None else [self.lcfg])]
         if self.robots is None:
             q0, self.p_gains, self.d_gains, self.torque_limits, self.dof_vel_limits, self.dof_pos_limits = self._joint_constants(self.lcfg, self.model, dev)
             self.default_dof_pos = q0.unsqueeze(0)
+            self.action_scales = scales[0].unsqueeze(0).expand(N, 12).contiguous()
         else:       # per env (N, 12) / (N, 12, 2): the rows of each env's robot
             self.robot_ids = torch.as_tensor(self._env_robot, dtype=torch.long, device=dev)
             self.robot_names = [r["name"] for r in self.robots]
             per = [self._joint_constants(lc, m, dev) for lc, m in zip(self._robot_lcfgs, self._robot_models)]
             (self.default_dof_pos, self.p_gains, self.d_gains, self.torque_limits, self.dof_vel_limits,
              self.dof_pos_limits) = (torch.stack(t)[self.robot_ids] for t in zip(*per))
+            self.action_scales = torch.stack(scales)[self.robot_ids].contiguous()
 
     def _joint_constants(self, lcfg, model, dev):
         """default pose, gains, torque / velocity limits (12,) and soft position limits (12, 2) of one robot"""

@@ -1,0 +1,371 @@
+"""Evaluate a trained policy on the device: metrics per robot x terrain type x terrain level, and state traces of chosen envs.
+
+    python -m isaacgymloco_amd.learn.evaluate --task aliengo [--robots aliengo=0.5,go2=0.5] --checkpoint model.pt --envs 4096 --steps 1000 \
+        --commands 1.0,0,0 --out eval.json [--trace-envs 0,1 --trace-out trace.npz]
+
+The evaluation half of the reference's legged_gym/scripts/play.py (fixed commands, randomisation off, deterministic actions; play.py:66-85 and
+play.py:124-133).  Every env-step costs ONE extra HIP launch, `lsim_eval_accumulate` (include/lsim.h states the semantics; csrc/ls_eval.h is the
+kernel): sums in 2^-32 fixed-point int64 words per group, bitwise reproducible, no host synchronisation.  The evaluator only reads the
+simulator's buffers.  The numbers are measurements of the policy on THIS simulator: its dynamics are not pinned against PhysX.
+"""
+import argparse
+import copy
+import ctypes
+import json
+import sys
+
+import numpy as np
+import torch
+
+from .. import abi, lib
+from ..envs import config as C
+
+GROUP_BITS = {"robot": abi.DEFINES["LSIM_EVAL_BY_ROBOT"], "type": abi.DEFINES["LSIM_EVAL_BY_TYPE"], "level": abi.DEFINES["LSIM_EVAL_BY_LEVEL"]}
+TRACE_DIM = abi.DEFINES["LSIM_EVAL_TRACE_DIM"]
+MAX_TRACE_ENVS = abi.DEFINES["LSIM_EVAL_MAX_TRACE_ENVS"]
+SAT_THRESHOLD = abi.DEFINES["LSIM_EVAL_SAT_PERMILLE"] / 1000.0
+FIX_ONE = 2.0 ** 32
+CLAMP = float(2 ** 20)
+W = abi.EVAL_WORDS
+# name -> (first column, width) of a trace row, in the order of the LSIM_EVAL_TR_* offsets
+_TR = sorted(((v, k[len("LSIM_EVAL_TR_"):].lower()) for k, v in abi.DEFINES.items() if k.startswith("LSIM_EVAL_TR_")))
+TRACE_COLUMNS = {name: (start, (_TR[i + 1][0] if i + 1 < len(_TR) else TRACE_DIM) - start) for i, (start, name) in enumerate(_TR)}
+
+
+def play_cfg(cfg, keep_terminations=True):
+    """A copy of an env config (single robot or mixed_cfg) with the evaluation overrides of the reference's play.py:66-85: observation noise,
+    friction / payload randomisation, pushes and the disturbance force off; terrain curriculum off (robots start on random levels up to
+    max_init_terrain_level = 5 and stay in their cell); heading command and command curriculum off; commands never resampled
+    (resampling_time 1e4).  num_envs and the terrain's size stay the caller's.  play.py also empties terminate_after_contacts_on;
+    falls are what an evaluation wants to count, so that is opt-in here: keep_terminations=False."""
+    cfg = copy.deepcopy(cfg)
+    cfg.terrain.curriculum = False
+    cfg.terrain.max_init_terrain_level = 5
+    cfg.noise.add_noise = False
+    cfg.domain_rand.randomize_friction = False
+    cfg.domain_rand.push_robots = False
+    cfg.domain_rand.disturbance = False
+    cfg.domain_rand.randomize_payload_mass = False
+    cfg.commands.heading_command = False
+    cfg.commands.curriculum = False
+    cfg.commands.resampling_time = 10000.0
+    if not keep_terminations:
+        cfg.asset.terminate_after_contacts_on = []
+        for r in getattr(cfg, "robots", None) or []:
+            if "asset" in r["overrides"]:
+                r["overrides"]["asset"].terminate_after_contacts_on = []
+    return cfg
+
+
+def group_mask(group_by):
+    mask = 0
+    for g in group_by:
+        if g not in GROUP_BITS:
+            raise ValueError(f"unknown group_by entry {g!r}: one of {sorted(GROUP_BITS)}")
+        mask |= GROUP_BITS[g]
+    return mask
+
+
+def group_shape(mask, num_robots, num_types, num_levels):
+    return (num_robots if mask & GROUP_BITS["robot"] else 1, num_types if mask & GROUP_BITS["type"] else 1, num_levels if mask & GROUP_BITS["level"] else 1)
+
+
+def group_index(mask, shape, robot, ttype, level):
+    """the table row of (robot, type, level): collapsed factors count as 0"""
+    r = robot if mask & GROUP_BITS["robot"] else 0
+    t = ttype if mask & GROUP_BITS["type"] else 0
+    l = level if mask & GROUP_BITS["level"] else 0
+    return (r * shape[1] + t) * shape[2] + l
+
+
+def group_key(mask, shape, index, robot_names):
+    """table row -> {"robot": name, "type": int, "level": int} with only the kept factors"""
+    l = index % shape[2]
+    t = (index // shape[2]) % shape[1]
+    r = index // (shape[1] * shape[2])
+    key = {}
+    if mask & GROUP_BITS["robot"]:
+        key["robot"] = robot_names[r]
+    if mask & GROUP_BITS["type"]:
+        key["type"] = int(t)
+    if mask & GROUP_BITS["level"]:
+        key["level"] = int(l)
+    return key
+
+
+def key_index(mask, shape, key, robot_names):
+    """inverse of group_key"""
+    return group_index(mask, shape, robot_names.index(key["robot"]) if "robot" in key else 0, key.get("type", 0), key.get("level", 0))
+
+
+def metrics_of_row(row):
+    """One table row (LSIM_EVAL_WORDS int64 words, or a sum of rows) -> float64 means / rates / RMS values with their counts.
+    Per-sample means divide by `samples` (env-steps that did not end an episode), per-episode means by `episodes`."""
+    row = [int(v) for v in row]
+    n, ep = row[W["samples"]], row[W["episodes"]]
+    per = lambda w, d: (row[W[w]] / FIX_ONE / d) if d else float("nan")
+    cnt = lambda w, d: (row[W[w]] / d) if d else float("nan")
+    return {
+        "samples": n, "episodes": ep, "time_outs": row[W["time_outs"]], "falls": row[W["falls"]], "nonfinite": row[W["nonfinite"]],
+        "lin_vel_error_mean": per("lin_err", n), "lin_vel_error_rms": per("lin_err_sq", n) ** 0.5 if n else float("nan"),
+        "yaw_rate_error_mean": per("yaw_err", n), "yaw_rate_error_rms": per("yaw_err_sq", n) ** 0.5 if n else float("nan"),
+        "mechanical_power_mean": per("power", n), "torque_rms": (per("torque_sq", n) / 12.0) ** 0.5 if n else float("nan"),
+        "action_rate_mean": per("action_rate", n), "feet_in_contact_mean": cnt("feet_contact", n),
+        "torque_saturation_rate": cnt("torque_sat", 12 * n), "peak_torque_ratio": row[W["peak_torque_ratio"]] / FIX_ONE,
+        "fall_rate": cnt("falls", ep), "time_out_rate": cnt("time_outs", ep),
+        "episode_return_mean": per("return", ep), "episode_length_mean": cnt("length", ep), "episode_distance_mean": per("distance", ep),
+    }
+
+
+def total_row(table):
+    """sum of the rows of an int64 table [groups, words]: integer sums, except the peak word (a maximum)"""
+    tot = table.sum(axis=0)
+    tot[W["peak_torque_ratio"]] = table[:, W["peak_torque_ratio"]].max()
+    return tot
+
+
+class Evaluator:
+    """Owns the evaluator's device state for one env: `.accumulate()` after every `env.step_device(...)`, `.result()` / `.trace()` at the end."""
+
+    def __init__(self, env, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=1024, api=None):
+        """`api`: an object with lsim_eval_sizes / _clear / _accumulate in place of the HIP library's (the test suite's CPU shim of the kernel source)"""
+        self.env = env
+        dev = env.buf["rew"].device
+        N = env.num_envs
+        self.mask = group_mask(group_by)
+        self.robot_names = list(getattr(env, "robot_names", None) or [getattr(env.cfg.asset, "name", "robot")])
+        has_grid = env.cfg.terrain.mesh_type in ("heightfield", "trimesh")
+        self.num_types = int(env.cfg.terrain.num_cols) if has_grid else 1
+        self.num_levels = int(env.cfg.terrain.num_rows) if has_grid else 1
+        self.shape = group_shape(self.mask, len(self.robot_names), self.num_types, self.num_levels)
+        self.num_groups = self.shape[0] * self.shape[1] * self.shape[2]
+        self.trace_envs = [int(i) for i in trace_envs]
+        if len(self.trace_envs) > MAX_TRACE_ENVS:
+            raise ValueError(f"at most {MAX_TRACE_ENVS} trace envs, got {len(self.trace_envs)}")
+        self.trace_capacity = int(trace_capacity)
+        self._L = api if api is not None else lib.load()
+        sb, tb, rb = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+        lib.check(self._L.lsim_eval_sizes(N, self.num_groups, len(self.trace_envs), self.trace_capacity, ctypes.byref(sb), ctypes.byref(tb), ctypes.byref(rb)),
+                  what="lsim_eval_sizes")
+        self.state = torch.zeros(sb.value // 8, dtype=torch.int64, device=dev)
+        self.table = torch.zeros(self.num_groups, abi.NUM_EVAL_WORDS, dtype=torch.int64, device=dev)
+        self.trace_buf = torch.zeros(self.trace_capacity, len(self.trace_envs), TRACE_DIM, dtype=torch.float32, device=dev)
+        per_env = lambda t: t.to(device=dev, dtype=torch.float32).expand(N, 12).contiguous()
+        self._const = {"torque_limits": per_env(env.torque_limits), "default_dof_pos": per_env(env.default_dof_pos), "action_scale": per_env(env.action_scales)}
+        if getattr(env, "robots", None) is not None:
+            self._const["robot_ids"] = env.robot_ids.to(torch.uint8).contiguous()
+        e = abi.LsimEval()
+        b = env.buf
+        for field, name in (("rew", "rew"), ("reset_buf", "reset"), ("time_out_buf", "time_out"), ("commands", "commands"), ("base_lin_vel", "base_lin_vel"),
+                            ("base_ang_vel", "base_ang_vel"), ("root_states", "root_states"), ("dof_state", "dof_state"), ("torques", "torques"),
+                            ("actions", "actions"), ("last_actions", "last_actions"), ("contact_filt", "contact_filt"), ("contact_forces", "contact_forces"),
+                            ("terrain_types", "terrain_types"), ("terrain_levels", "terrain_levels")):
+            setattr(e, field, b[name].data_ptr())
+        for field, t in self._const.items():
+            setattr(e, field, t.data_ptr())
+        e.state, e.table = self.state.data_ptr(), self.table.data_ptr()
+        e.trace = self.trace_buf.data_ptr() if self.trace_envs else None
+        e.num_envs, e.num_robots, e.num_types, e.num_levels = N, len(self.robot_names), self.num_types, self.num_levels
+        e.group_by, e.num_groups = self.mask, self.num_groups
+        e.num_trace_envs, e.trace_capacity = len(self.trace_envs), self.trace_capacity
+        for k, body in enumerate(env.model.feet_bodies):
+            e.feet_bodies[k] = int(body)
+        for k, i in enumerate(self.trace_envs):
+            e.trace_envs[k] = i
+        self._e = e
+        self.clear()
+
+    def _stream(self):
+        return self.env._stream()
+
+    def clear(self):
+        lib.check(self._L.lsim_eval_clear(ctypes.byref(self._e), self._stream()), what="lsim_eval_clear")
+
+    def accumulate(self):
+        lib.check(self._L.lsim_eval_accumulate(ctypes.byref(self._e), self._stream()), what="lsim_eval_accumulate")
+
+    @property
+    def steps(self):
+        """launches since clear() (reads the device-side counter: a host sync)"""
+        return int(self.state[0].item())
+
+    def result(self):
+        """plain dict (JSON-serialisable): `groups` = one entry per group that saw a sample or an episode, `total` = all groups together"""
+        table = self.table.cpu().numpy()
+        groups = []
+        for g in range(self.num_groups):
+            if table[g, W["samples"]] or table[g, W["episodes"]] or table[g, W["nonfinite"]]:
+                groups.append({"key": group_key(self.mask, self.shape, g, self.robot_names), **metrics_of_row(table[g])})
+        env = self.env
+        conv = dict(env._conventions()) if hasattr(env, "_conventions") else {"abi_version": int(abi.ABI_VERSION)}
+        conv.update({"addend_clamp": CLAMP, "fixed_point_scale": FIX_ONE, "torque_saturation_threshold": SAT_THRESHOLD,
+                     "robot_names": self.robot_names, "num_types": self.num_types, "num_levels": self.num_levels})
+        return {"group_by": [g for g in ("robot", "type", "level") if self.mask & GROUP_BITS[g]], "num_envs": int(env.num_envs), "steps": self.steps,
+                "dt": float(env.dt), "groups": groups, "total": metrics_of_row(total_row(table)),
+                "nonfinite": {"addends": int(table[:, W["nonfinite"]].sum()), "simulator_env_steps": int(env.nonfinite_envs.item())},
+                "conventions": conv}
+
+    def trace(self):
+        """dict of named numpy arrays [steps kept, trace envs, width], oldest step first, plus "envs" and "step" (launch index of each row)"""
+        t, cap = self.steps, self.trace_capacity
+        kept = min(t, cap)
+        rows = [(s % cap) for s in range(t - kept, t)]
+        data = self.trace_buf.cpu().numpy()[rows]
+        out = {name: data[:, :, start:start + width] for name, (start, width) in TRACE_COLUMNS.items()}
+        out["envs"] = np.asarray(self.trace_envs, dtype=np.int64)
+        out["step"] = np.arange(t - kept, t, dtype=np.int64)
+        return out
+
+
+def check_conventions(saved, live):
+    """refuse a checkpoint made under other simulator conventions or another robot mix, naming the first differing key"""
+    if saved is None:
+        return
+    for k in ("robots", "lin_vel_at_com", "tgs_limit_passes", "solver_type", "num_position_iterations"):
+        if saved.get(k) != live.get(k):
+            raise ValueError(f"checkpoint conventions differ from the env's in {k!r}: saved {saved.get(k)!r}, live {live.get(k)!r}")
+
+
+def _actor_critic(env, policy, device):
+    """HIMActorCritic from a module, a runner, or a checkpoint path written by runner.save"""
+    from .modules import HIMActorCritic
+    if isinstance(policy, HIMActorCritic):
+        return policy
+    if hasattr(policy, "alg"):                 # a runner
+        policy.get_inference_policy()          # flushes a deferred rollout store, eval mode
+        return policy.alg.actor_critic
+    if isinstance(policy, str):
+        d = torch.load(policy, map_location=device, weights_only=False)
+        check_conventions((d.get("env_state_dict") or {}).get("conventions"), env._conventions())
+        sd = d["model_state_dict"]
+        hidden = lambda prefix: [sd[k].shape[0] for k in sorted((k for k in sd if k.startswith(prefix) and k.endswith(".weight")), key=lambda k: int(k.split(".")[-2]))]
+        actor, critic, enc = hidden("actor."), hidden("critic."), hidden("estimator.encoder.")
+        num_critic_obs = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
+        ac = HIMActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, actor_hidden_dims=tuple(actor[:-1]),
+                            critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
+        if enc != [l.out_features for l in ac.estimator.encoder if isinstance(l, torch.nn.Linear)]:
+            raise ValueError(f"checkpoint estimator encoder widths {enc} differ from the default HIMEstimator's: pass the HIMActorCritic itself")
+        ac.load_state_dict(sd)
+        ac.eval()
+        return ac
+    raise TypeError(f"policy must be a HIMActorCritic, a runner or a checkpoint path, got {type(policy).__name__}")
+
+
+@torch.no_grad()
+def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None):
+    """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
+    action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
+    No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`)."""
+    from .fused_policy import PackedHimPolicy
+    dev = env.buf["rew"].device
+    ac = _actor_critic(env, policy, dev)
+    ac.eval()
+    ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
+    cmd = None
+    if commands is not None:
+        cmd = torch.as_tensor(commands, dtype=torch.float32, device=dev)
+        cmd = cmd.expand(env.num_envs, 3).contiguous() if cmd.dim() == 1 else cmd.contiguous()
+        if tuple(cmd.shape) != (env.num_envs, 3):
+            raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
+    use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
+    if use_fused and not PackedHimPolicy.supported(ac):
+        raise ValueError("fused=True but lsim_policy_forward does not support this policy's topology")
+    if hasattr(env, "_external_call"):
+        env._external_call()
+    if use_fused:
+        packed = PackedHimPolicy(ac)
+        mean = torch.empty(env.num_envs, env.num_actions, device=dev)
+        values = torch.empty(env.num_envs, 1, device=dev)
+    obs, priv = env.get_observations(), env.get_privileged_observations()
+    for _ in range(int(steps)):
+        if cmd is not None:
+            env.commands[:, :3] = cmd
+        if use_fused:
+            packed.forward(obs, priv, mean, values)
+            actions = mean
+        else:
+            actions = ac.act_inference(obs)
+        env.step_device(actions)
+        ev.accumulate()
+    return ev
+
+
+def format_table(result):
+    cols = ("samples", "episodes", "fall_rate", "lin_vel_error_rms", "yaw_rate_error_rms", "mechanical_power_mean", "torque_saturation_rate",
+            "episode_return_mean", "episode_length_mean", "episode_distance_mean")
+    lines = [" ".join([f"{'group':<28}"] + [f"{c[:14]:>14}" for c in cols])]
+    for g in result["groups"] + [{"key": {"all": ""}, **result["total"]}]:
+        name = " ".join(f"{k}={v}" if v != "" else k for k, v in g["key"].items()) or "all"
+        lines.append(" ".join([f"{name:<28}"] + [f"{g[c]:>14d}" if isinstance(g[c], int) else f"{g[c]:>14.4f}" for c in cols]))
+    return "\n".join(lines)
+
+
+def parse_args(argv=None):
+    """the command line; argument errors raise SystemExit through argparse"""
+    ap = argparse.ArgumentParser(prog="python -m isaacgymloco_amd.learn.evaluate", description=__doc__.split("\n")[0])
+    ap.add_argument("--task", required=True, choices=sorted(C.TASKS))
+    ap.add_argument("--robots", default=None, help="name=fraction,... (a mixed instance, config.mixed_cfg)")
+    ap.add_argument("--checkpoint", required=True, help="file written by runner.save")
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--commands", default="1.0,0,0", help="vx,vy,yaw written every step; 'env' keeps the env's own sampled commands")
+    ap.add_argument("--group-by", default="robot,type,level")
+    ap.add_argument("--no-terminations", action="store_true", help="empty terminate_after_contacts_on as the reference's play.py does")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--trace-envs", default="")
+    ap.add_argument("--trace-out", default=None)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    if a.envs < 1 or a.steps < 1:
+        ap.error("--envs and --steps must be positive")
+    if a.commands == "env":
+        a.commands = None
+    else:
+        try:
+            a.commands = tuple(float(v) for v in a.commands.split(","))
+        except ValueError:
+            ap.error(f"--commands: not numbers: {a.commands!r}")
+        if len(a.commands) != 3:
+            ap.error("--commands takes vx,vy,yaw")
+    a.group_by = tuple(g for g in a.group_by.split(",") if g)
+    try:
+        group_mask(a.group_by)
+    except ValueError as exc:
+        ap.error(str(exc))
+    try:
+        a.trace_envs = tuple(int(v) for v in a.trace_envs.split(",") if v)
+    except ValueError:
+        ap.error(f"--trace-envs: not integers: {a.trace_envs!r}")
+    if len(a.trace_envs) > MAX_TRACE_ENVS or any(not 0 <= i < a.envs for i in a.trace_envs):
+        ap.error(f"--trace-envs: at most {MAX_TRACE_ENVS} envs, each in [0, --envs)")
+    if bool(a.trace_envs) != bool(a.trace_out):
+        ap.error("--trace-envs and --trace-out go together")
+    if a.robots is not None:
+        try:
+            a.robots = {k: float(v) for k, v in (item.split("=") for item in a.robots.split(","))}
+        except ValueError:
+            ap.error(f"--robots: expected name=fraction,..., got {a.robots!r}")
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    from ..envs.legged_robot import LeggedRobot
+    cfg = C.mixed_cfg(a.task, a.robots)[0] if a.robots else C.TASKS[a.task][0]()
+    cfg = play_cfg(cfg, keep_terminations=not a.no_terminations)
+    cfg.env.num_envs = a.envs
+    env = LeggedRobot(cfg, sim_device=a.device, seed=a.seed)
+    env.reset()
+    ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs)
+    res = ev.result()
+    print(format_table(res))
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    if a.trace_out:
+        np.savez(a.trace_out, **ev.trace())
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -97,6 +97,10 @@ def load_path(path):
     L.lsim_amp_pair_rows.argtypes = [vp, i64, vp, i64, vp, vp, ctypes.c_double, ctypes.c_double, i64, i32, vp, i64, vp]
     L.lsim_amp_step_workspace.argtypes = [i64, ctypes.POINTER(ctypes.c_size_t)]
     L.lsim_amp_step.argtypes = [ctypes.POINTER(abi.LsimAmpDisc), vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, ctypes.c_size_t, vp]
+    sz = ctypes.POINTER(ctypes.c_size_t)
+    L.lsim_eval_sizes.argtypes = [i64, i32, i32, i32, sz, sz, sz]
+    L.lsim_eval_clear.argtypes = [ctypes.POINTER(abi.LsimEval), vp]
+    L.lsim_eval_accumulate.argtypes = [ctypes.POINTER(abi.LsimEval), vp]
     L.lsim_destroy.argtypes = [vp]
     L.lsim_destroy.restype = None
     return L
