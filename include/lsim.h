@@ -37,7 +37,9 @@ extern "C" {
                                  4: lsim_config.solver_type / num_position_iterations out of the reserved words (round 4);
                                  5: lsim_config.lin_vel_at_com (centre-of-mass linear velocities, the PhysX convention) and tgs_limit_passes, lsim_get / set_reset_calls (round 5);
                                  6: LSIM_BUF_NONFINITE + LSIM_STATS_NONFINITE (robots whose simulated state is not finite), lsim_amp_step and the discriminator-update kernels (round 6);
-                                 7: lsim_eval + lsim_eval_sizes / lsim_eval_clear / lsim_eval_accumulate (device-side policy evaluation: grouped metrics and state traces); no earlier struct or entry changed */
+                                 7: lsim_eval + lsim_eval_sizes / lsim_eval_clear / lsim_eval_accumulate (device-side policy evaluation: grouped metrics and state traces); no earlier struct or entry changed;
+                                    also under 7, as pure additions (no earlier struct or entry changed, so a caller built against the first
+                                    version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -921,6 +923,63 @@ int lsim_eval_clear(const lsim_eval* e, void* stream);
  * 1..LSIM_TERRAIN_TYPES_MAX, num_levels outside 1..LSIM_TERRAIN_LEVELS_MAX, group_by with unknown bits, num_groups != product of the kept
  * extents, num_trace_envs outside 0..LSIM_EVAL_MAX_TRACE_ENVS, trace_capacity < 1, a trace env or a feet body out of range. */
 int lsim_eval_accumulate(const lsim_eval* e, void* stream);
+
+/* ---- range sensors: rays against the terrain mesh (depth cameras, lidar; no reference FFI: the reference has no such sensor).
+ * ONE launch, on the caller's stream, no host synchronisation, capturable in a graph.  The launch only READS the simulator's buffers,
+ * through raw device pointers (this struct, filled by the caller from lsim_get_buffer and the terrain constants of its lsim_config).
+ * ONLY THE TERRAIN IS SEEN: not the robot's own bodies, not other robots.
+ *
+ * Geometry -- the mesh the contact code collides with (LSIM_BUF_TERRAIN_MESH, word[a][b] of grid vertex (a, b)):
+ *   vertex (a, b) = ( (a + dx) * horizontal_scale - border_size, (b + dy) * horizontal_scale - border_size, (int16)(word & 0xFFFF) * vertical_scale ),
+ *                   dx = ((word >> 16) & 3) - 1, dy = ((word >> 18) & 3) - 1
+ *   cell (i, j), 0 <= i <= grid_rows - 2, 0 <= j <= grid_cols - 2, has the two triangles (p00, p11, p01) and (p00, p10, p11), pab = vertex (i + a, j + b).
+ *   A triangle (a, b, c) with |(b - a) x (c - a)|^2 < 1e-16 does not exist.  mesh_type 1 (heightfield): the same words, dx = dy = 0 in all of them.
+ *   mesh_type 0 (plane), or mesh == NULL: the single unbounded plane z = 0.
+ *   Bits 20 and 24-31 of a word only speed the walk up and never change a result: bit 20 clear = no vertex of the 4 x 4 vertex block
+ *   (i-1..i+2, j-1..j+2) is displaced; bits 24-31 = dz: no vertex of that block is higher than (height + dz * 4) height steps, 255 = unknown.
+ * Ray r of env e:  o = p + R(q) * mount_pos[e],  d = R(q) * R(mount_quat[e]) * dirs[r],  (p, q) = root_states[e][0:3], [3:7] (quaternion xyzw, used as
+ *   given: the caller keeps it and dirs[r] of unit length; R(q) v = v + 2 w (u x v) + 2 u x (u x v), u = q.xyz, w = q.w).
+ * Result: the smallest t in [near, far] for which o + t d lies on a triangle, from EITHER side of it (the walls that displacement makes are seen
+ *   from both sides); `far` when there is none -- also when the ray never meets the grid's footprint [0, (rows-1) hs] x [0, (cols-1) hs] - border.
+ *   A ray (nearly) parallel to a triangle's plane, |n . d| < 1e-30 for the unnormalised n, does not hit that triangle.
+ *   Edges are inclusive.  With U, V, W the three edge functions of the triangle (U = -e2 . (s x d), V = e1 . (s x d), W = n . d - U - V for
+ *   e1 = b - a, e2 = c - a, s = o - a, n = e1 x e2, all three multiplied by sign(n . d)), the ray is inside when U >= -E2, V >= -E1 and
+ *   W >= -(E1 + E2 + E3), Ek = 2^-18 * max|component of ek| * max|component of s|, E3 = 2^-20 * max|component of e1| * max|component of e2| (the
+ *   rounding of n . d): Ek is 4-8 times the rounding error of the fp32 edge function (six products of three factors each), so two triangles
+ *   that share an edge cannot both reject a ray that passes between them.  It admits a
+ *   ray that passes OUTSIDE an edge by at most 2^-18 * sqrt(3) * |o - a| / sin(angle between ray and edge), 3.3e-5 m at 5 m: less than the position
+ *   uncertainty of a world coordinate 190 m from the origin that the tests allow for (6e-5 m), so a ray reported as a hit is a hit for a ray within that.
+ *   out[e][r] = t * scale[r] (scale == NULL: t); a miss is far * scale[r].  scale[r] = cos(angle of dirs[r] to the optical axis) turns range into
+ *   the z-depth a depth camera reports.
+ *   A non-finite component of o or d: out = far * scale[r], and the ray is counted in state[0] (int64, cumulative, the caller may zero it; it must
+ *   stay 0, as LSIM_BUF_NONFINITE).  No NaN is ever written (a non-finite scale is the caller's).
+ *   Envs: e = 0, env_stride, 2 env_stride, ...; the other rows of `out` are not touched.
+ * NOT SUPPORTED: an origin below the surface.  The mesh is a displaced height grid without overhangs; a ray that starts under it reports the first
+ *   face it meets from below, which means nothing. */
+#define LSIM_RAYCAST_MAX_RAYS 16384        /* rays per env: a 128 x 128 image; 64 x 48 = 3072, a 16 x 360 lidar = 5760 */
+#define LSIM_RAYCAST_STATE_WORDS 4         /* int64: [0] non-finite rays; [1] reserved; [2] cells walked, [3] triangles tested (only a build with LS_RAYCAST_COUNTERS writes [2], [3]) */
+typedef struct lsim_raycast {
+    const float* root_states;         /* [N,13] simulator buffer, read only */
+    const int32_t* mesh;              /* LSIM_BUF_TERRAIN_MESH [grid_rows,grid_cols], or NULL (plane) */
+    const float* mount;               /* [N,7] sensor pose in the base frame: position, quaternion xyzw */
+    const float* dirs;                /* [R,3] unit vectors in the sensor frame, shared by all envs */
+    const float* scale;               /* [R] or NULL */
+    float* out;                       /* [N,out_stride], 16-byte aligned; row e holds R values */
+    void* state;                      /* LSIM_RAYCAST_STATE_WORDS int64, 8-byte aligned, zeroed by the caller */
+    int32_t num_envs, num_rays;       /* N >= 1, R in 1..LSIM_RAYCAST_MAX_RAYS */
+    int32_t env_stride;               /* >= 1 */
+    int32_t out_stride;               /* floats between rows of out: >= R, a multiple of 4 (16-byte aligned rows) */
+    int32_t mesh_type, grid_rows, grid_cols;      /* lsim_config's; grid extents >= 2 unless plane */
+    float horizontal_scale, vertical_scale, border_size;
+    float near, far;                  /* 0 <= near < far, far finite */
+} lsim_raycast_t;    /* the struct tag and the entry point share the name; C and C++ code names the type lsim_raycast_t */
+/* bytes of `state`.  LSIM_E_INVALID: a NULL output pointer */
+int lsim_raycast_sizes(size_t* state_bytes);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch: rc == NULL; root_states, mount, dirs, out or state NULL;
+ * a pointer not aligned to its element (out: 16 bytes, state: 8); mesh NULL with mesh_type != 0; N < 1; R outside 1..LSIM_RAYCAST_MAX_RAYS;
+ * env_stride < 1; out_stride < R or not a multiple of 4; mesh_type outside 0..2; grid_rows or grid_cols < 2 for a mesh; horizontal_scale or
+ * vertical_scale not finite and > 0, border_size not finite (mesh only); near < 0, near >= far, far not finite. */
+int lsim_raycast(const lsim_raycast_t* rc, void* stream);
 
 #ifdef __cplusplus
 }

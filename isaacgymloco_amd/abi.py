@@ -103,6 +103,7 @@ LsimHimPolicy = STRUCTS["lsim_him_policy"]
 LsimWgradPending = STRUCTS["lsim_wgrad_pending"]
 LsimAmpDisc = STRUCTS["lsim_amp_disc"]
 LsimEval = STRUCTS["lsim_eval"]
+LsimRaycast = STRUCTS["lsim_raycast_t"]
 
 REWARD_IDS = {k[len("LSIM_R_"):].lower(): v for k, v in ENUMS["lsim_reward_id"].items() if k.startswith("LSIM_R_")}
 NUM_REWARD_TERMS = ENUMS["lsim_reward_id"]["LSIM_NUM_REWARD_TERMS"]

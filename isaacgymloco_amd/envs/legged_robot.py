@@ -38,6 +38,7 @@ class LeggedRobot:
     def __init__(self, cfg, sim_params=None, physics_engine=None, sim_device="cuda:0", headless=True,
                  *, seed=1, rank=0, using_amp=False, terrain=None, terrain_seed=None):
         self._L = self._load_library()
+        self.sensors = {}         # name -> envs.sensors.RaySensor (add_sensor); empty: nothing is created or launched
         self.cfg = cfg
         self.sim_params = sim_params
         self.physics_engine = physics_engine
@@ -296,6 +297,7 @@ class LeggedRobot:
         else:
             lib.check(self._L.lsim_reset_envs(self._h, mask.data_ptr(), self._stream()), self._h, "lsim_reset_envs")
             self._reset_mask_ref = mask   # keep alive until the kernels ran
+        self._update_sensors()
         self._refresh_extras(force_valid=True)
 
     def reset(self):
@@ -313,9 +315,23 @@ class LeggedRobot:
             actions = actions.to(device=self._arena.device, dtype=torch.float32).contiguous()
         with lib.roctx_range("lsim_step"):
             lib.check(self._L.lsim_step_ex(self._h, actions.data_ptr(), ctypes.c_uint32(flags | _EXTRA_STEP_FLAGS), self._stream()), self._h, "lsim_step")
+        self._update_sensors()
         self.common_step_counter += 1
         self._last_actions_ref = actions   # keep alive until the kernels ran
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf
+
+    def add_sensor(self, name, sensor):
+        """attach a range sensor (envs/sensors.py): from now on every step_device() / reset_idx() ends with the sensor's launch on the same
+        stream, after the post-step reset, so `env.sensors[name].out` belongs to the observations of the same step.  Added before a
+        step_device() is captured into a graph, the launch is captured with it (raw pointers only, no host sync)."""
+        if name in self.sensors:
+            raise ValueError(f"sensor {name!r} exists")
+        self.sensors[name] = sensor
+        return sensor
+
+    def _update_sensors(self):
+        for s in self.sensors.values():
+            s.update()
 
     def step(self, actions):
         """LeggedRobot.step (LR:122-176): same 7-tuple (8 with terminal AMP states when using_amp)."""

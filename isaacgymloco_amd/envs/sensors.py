@@ -1,0 +1,144 @@
+"""Range sensors on the terrain mesh (include/lsim.h, lsim_raycast): depth cameras and lidar.
+
+    cam = depth_camera(env, 64, 48, hfov_deg=87, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30, near=0.05, far=5.0)
+    env.add_sensor("depth", cam)            # from now on every env.step_device() ends with one more launch
+    img = env.sensors["depth"].image()      # [N, 48, 64] z-depth in metres, the live device tensor of the latest step
+
+A sensor is one HIP launch over all envs and rays, on the current stream, without host synchronisation; it reads the post-step, post-reset
+`root_states`, so it is consistent with the observations of the same step.  ONLY THE TERRAIN IS SEEN: not the robot's own bodies, not
+other robots.  There is no torch fall-back: without the library's lsim_raycast the constructor raises.
+
+Frames: the sensor frame is the base frame moved by the mount -- x forward, y left, z up, as the reference's base frame.  A camera looks along
+its +x; image rows run top to bottom, columns left to right (row-major, r = row * width + col).
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .. import abi, lib
+
+
+def quat_from_pitch(pitch_deg):
+    """xyzw of a rotation about the base y axis; positive pitch looks DOWN (x forward, z up: a positive rotation about y turns +x towards -z)"""
+    h = math.radians(pitch_deg) / 2.0
+    return (0.0, math.sin(h), 0.0, math.cos(h))
+
+
+def pinhole_dirs(width, height, hfov_deg):
+    """(dirs [H*W, 3] unit, scale [H*W] = cos to the optical axis) of a pinhole camera with square pixels looking along +x: pixel centres, the
+    horizontal field of view spanning the image's full width (edge to edge); the vertical one follows from the aspect ratio"""
+    tx = math.tan(math.radians(hfov_deg) / 2.0)
+    ys = (1.0 - (2.0 * np.arange(width) + 1.0) / width) * tx                      # left (+y) to right
+    zs = (1.0 - (2.0 * np.arange(height) + 1.0) / height) * tx * height / width   # top (+z) to bottom
+    v = np.stack((np.ones((height, width)), np.broadcast_to(ys[None, :], (height, width)), np.broadcast_to(zs[:, None], (height, width))), axis=-1)
+    n = np.linalg.norm(v, axis=-1, keepdims=True)
+    return (v / n).reshape(-1, 3).astype(np.float32), (1.0 / n).reshape(-1).astype(np.float32)
+
+
+def ring_dirs(channels, vfov_deg, points_per_rev):
+    """dirs [channels * points_per_rev, 3] of a spinning lidar: channel c at elevation vfov[0] + c * (vfov[1] - vfov[0]) / (channels - 1) (degrees, up
+    positive; one channel: the mean), azimuth k * 360 / points_per_rev counter-clockwise from +x; r = c * points_per_rev + k"""
+    lo, hi = (-vfov_deg / 2.0, vfov_deg / 2.0) if np.isscalar(vfov_deg) else vfov_deg
+    el = np.radians(np.linspace(lo, hi, channels) if channels > 1 else np.array([(lo + hi) / 2.0]))
+    az = 2.0 * np.pi * np.arange(points_per_rev) / points_per_rev
+    v = np.stack((np.cos(el)[:, None] * np.cos(az)[None, :], np.cos(el)[:, None] * np.sin(az)[None, :], np.broadcast_to(np.sin(el)[:, None], (channels, points_per_rev))), axis=-1)
+    return v.reshape(-1, 3).astype(np.float32)
+
+
+class RaySensor:
+    """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
+    dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
+    rendered (the other rows of the output keep their initial value, `far`).  `update()` launches once and returns the live [N, R] tensor."""
+
+    def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None):
+        self.env = env
+        self._api = api if api is not None else env._L
+        if not hasattr(self._api, "lsim_raycast"):
+            raise lib.LsimError("the loaded library has no lsim_raycast: rebuild it (there is no torch fall-back for the range sensors)")
+        dev = env.root_states.device
+        N = int(env.num_envs)
+        self.dirs = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device=dev).contiguous()
+        R = self.num_rays = int(self.dirs.shape[0])
+        self.near, self.far, self.env_stride = float(near), float(far), int(env_stride)
+        self.scale = None if scale is None else torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float32).reshape(R), device=dev).contiguous()
+        self.mount = torch.cat((self._per_env(mount_pos, 3, dev), self._per_env(mount_quat, 4, dev)), dim=1).contiguous()
+        stride = (R + 3) // 4 * 4
+        self._out = torch.full((N, stride), self.far, dtype=torch.float32, device=dev)
+        if self.scale is not None:
+            self._out[:, :R] *= self.scale
+        self.out = self._out[:, :R]
+        nbytes = ctypes.c_size_t()
+        lib.check(self._api.lsim_raycast_sizes(ctypes.byref(nbytes)), what="lsim_raycast_sizes")
+        self.state = torch.zeros(nbytes.value // 8, dtype=torch.int64, device=dev)
+        lc = env.lcfg
+        rc = abi.LsimRaycast()
+        rc.root_states, rc.mount, rc.dirs = env.root_states.data_ptr(), self.mount.data_ptr(), self.dirs.data_ptr()
+        rc.scale = None if self.scale is None else self.scale.data_ptr()
+        rc.out, rc.state = self._out.data_ptr(), self.state.data_ptr()
+        rc.mesh_type = int(lc.mesh_type)
+        if rc.mesh_type != 0:
+            rc.mesh = env.buf["terrain_mesh"].data_ptr()
+            rc.grid_rows, rc.grid_cols = int(lc.grid_rows), int(lc.grid_cols)
+        rc.horizontal_scale, rc.vertical_scale, rc.border_size = lc.horizontal_scale, lc.vertical_scale, lc.border_size
+        rc.num_envs, rc.num_rays, rc.env_stride, rc.out_stride = N, R, self.env_stride, stride
+        rc.near, rc.far = self.near, self.far
+        self._rc = rc
+
+    def _per_env(self, pose, width, dev):
+        N = int(self.env.num_envs)
+        if isinstance(pose, dict):
+            names = getattr(self.env, "robot_names", None)
+            if names is None:
+                raise ValueError("a {robot name: pose} mount needs a mixed-robot instance (config.mixed_cfg)")
+            missing = [n for n in names if n not in pose]
+            if missing:
+                raise ValueError(f"no mount for robots {missing}")
+            table = torch.tensor([list(pose[n]) for n in names], dtype=torch.float32, device=dev).reshape(len(names), width)
+            return table[self.env.robot_ids.to(dev)]
+        p = torch.as_tensor(pose, dtype=torch.float32, device=dev)
+        if p.shape == (width,):
+            return p.unsqueeze(0).expand(N, width)
+        if p.shape == (N, width):
+            return p
+        raise ValueError(f"mount: expected ({width},), ({N}, {width}) or a dict by robot name, got {tuple(p.shape)}")
+
+    def _stream(self, stream):
+        if stream is not None:
+            return stream
+        return self.env._stream() if self._out.is_cuda else None
+
+    def update(self, stream=None):
+        """one launch on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor"""
+        lib.check(self._api.lsim_raycast(ctypes.byref(self._rc), self._stream(stream)), what="lsim_raycast")
+        return self.out
+
+    @property
+    def nonfinite_rays(self):
+        """0-d device tensor: rays so far whose origin or direction was not finite (they report `far`); must stay 0"""
+        return self.state[0]
+
+
+class DepthCamera(RaySensor):
+    def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None):
+        dirs, scale = pinhole_dirs(width, height, hfov_deg)
+        self.width, self.height = int(width), int(height)
+        super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg), near, far, scale=scale, env_stride=env_stride, api=api)
+
+    def image(self):
+        """[N, H, W] view of the output: z-depth along the optical axis in metres, far * cos where nothing is hit"""
+        return self.out.unflatten(1, (self.height, self.width))
+
+
+def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` as RaySensor's"""
+    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api)
+
+
+def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None):
+    """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
+    `points_per_rev` azimuths each; reports range (scale=None)"""
+    s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api)
+    s.channels, s.points_per_rev = int(channels), int(points_per_rev)
+    return s

@@ -101,6 +101,8 @@ def load_path(path):
     L.lsim_eval_sizes.argtypes = [i64, i32, i32, i32, sz, sz, sz]
     L.lsim_eval_clear.argtypes = [ctypes.POINTER(abi.LsimEval), vp]
     L.lsim_eval_accumulate.argtypes = [ctypes.POINTER(abi.LsimEval), vp]
+    L.lsim_raycast_sizes.argtypes = [sz]
+    L.lsim_raycast.argtypes = [ctypes.POINTER(abi.LsimRaycast), vp]
     L.lsim_destroy.argtypes = [vp]
     L.lsim_destroy.restype = None
     return L

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""HIP-event time of the range-sensor launch (lsim_raycast) next to kernel A's.
+
+    python tools/raycast_time.py [--num-envs 4096] [--terrains flat,stairs] [--iters 100] [--warmup 10] [--out profiles/raycast_time.json]
+
+Per terrain (Aliengo, zero actions for 20 steps so that the robots stand where they were put): `camera_us` = one launch of a 64 x 48 depth
+camera (87 degrees, far 5 m, pitched down 30 degrees, 0.3 m ahead of the base), `lidar_us` = one launch of a 16 x 360 lidar (30 degrees
+vertical, far 10 m), each with rays/s; `kernel_a_us` = kernel A from the library's own events (lsim_read_profile) in the same process;
+`cells_per_ray` / `triangles_per_ray` = the walk's two debug counters, from one launch through a build of the library with
+-DLS_RAYCAST_COUNTERS (isaacgymloco_amd/csrc/liblsim_rccount.so, built here when stale; the product build has no counters).
+The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from isaacgymloco_amd import lib  # noqa: E402
+from isaacgymloco_amd.csrc import build as hip_build  # noqa: E402
+from isaacgymloco_amd.envs import config as C, sensors  # noqa: E402
+from isaacgymloco_amd.envs.legged_robot import LeggedRobot  # noqa: E402
+
+COUNT_LIB = os.path.join(os.path.dirname(hip_build.LIB), "liblsim_rccount.so")
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1000.0 / iters
+
+
+def counters(sensor, count_lib):
+    """(cells, triangles) per ray of one launch through the counters build, on the sensor's own struct"""
+    sensor.state.zero_()
+    lib.check(count_lib.lsim_raycast(ctypes.byref(sensor._rc), sensor.env._stream()), what="lsim_raycast (counters build)")
+    torch.cuda.synchronize()
+    st = sensor.state.cpu().tolist()
+    rays = sensor.num_rays * ((sensor.env.num_envs + sensor.env_stride - 1) // sensor.env_stride)
+    sensor.state.zero_()
+    return st[2] / rays, st[3] / rays, st[0]
+
+
+def measure(n, terrain, iters, warmup, count_lib):
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    L = env._L
+    L.lsim_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    L.lsim_read_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
+    steps = 20
+    L.lsim_set_profiling(env._h, steps)
+    for _ in range(steps):
+        env.step_device(zero)
+    torch.cuda.synchronize()
+    ms_a, ms_b, cnt = (ctypes.c_float * steps)(), (ctypes.c_float * steps)(), ctypes.c_int(steps)
+    L.lsim_read_profile(env._h, ms_a, ms_b, ctypes.byref(cnt))
+    L.lsim_set_profiling(env._h, 0)
+    out = {"num_envs": n, "terrain": terrain, "kernel_a_us": 1000.0 * sum(ms_a[:cnt.value]) / max(cnt.value, 1)}
+    cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0)
+    lid = sensors.lidar(env, 16, 30.0, 360, mount_pos=(0.0, 0.0, 0.15), near=0.05, far=10.0)
+    for name, s in (("camera", cam), ("lidar", lid)):
+        us = timed(s.update, iters, warmup)
+        rays = n * s.num_rays
+        out[name + "_us"] = us
+        out[name + "_rays"] = rays
+        out[name + "_rays_per_s"] = rays / (us * 1e-6)
+        out[name + "_over_kernel_a"] = us / out["kernel_a_us"]
+        out[name + "_hit_share"] = float((s.out < s.far * (s.scale if s.scale is not None else 1.0) * 0.999).float().mean().item())
+        if count_lib is not None:
+            cells, tris, bad = counters(s, count_lib)
+            out[name + "_cells_per_ray"], out[name + "_triangles_per_ray"] = cells, tris
+        out[name + "_nonfinite_rays"] = int(s.nonfinite_rays.item())
+    out["torch_us"] = None
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--terrains", default="flat,stairs")
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--no-counters", action="store_true")
+    ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    count_lib = None
+    if not a.no_counters:
+        if hip_build.variant_is_stale(COUNT_LIB):
+            hip_build.build_variant(COUNT_LIB, ["-DLS_RAYCAST_COUNTERS"])
+        if a.build_only:
+            print(COUNT_LIB)
+            return
+        count_lib = lib.load_path(COUNT_LIB)
+    res = {"tool": "raycast_time", "iters": a.iters, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
+           "camera": "64x48, hfov 87, pitch 30 down, far 5 m", "lidar": "16x360, vfov 30, far 10 m",
+           "cases": [measure(a.num_envs, t, a.iters, a.warmup, count_lib) for t in a.terrains.split(",")]}
+    line = json.dumps(res)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line)
+
+
+if __name__ == "__main__":
+    main()
