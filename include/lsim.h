@@ -39,7 +39,8 @@ extern "C" {
                                  6: LSIM_BUF_NONFINITE + LSIM_STATS_NONFINITE (robots whose simulated state is not finite), lsim_amp_step and the discriminator-update kernels (round 6);
                                  7: lsim_eval + lsim_eval_sizes / lsim_eval_clear / lsim_eval_accumulate (device-side policy evaluation: grouped metrics and state traces); no earlier struct or entry changed;
                                     also under 7, as pure additions (no earlier struct or entry changed, so a caller built against the first
-                                    version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh) */
+                                    version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh);
+                                    lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -927,7 +928,7 @@ int lsim_eval_accumulate(const lsim_eval* e, void* stream);
 /* ---- range sensors: rays against the terrain mesh (depth cameras, lidar; no reference FFI: the reference has no such sensor).
  * ONE launch, on the caller's stream, no host synchronisation, capturable in a graph.  The launch only READS the simulator's buffers,
  * through raw device pointers (this struct, filled by the caller from lsim_get_buffer and the terrain constants of its lsim_config).
- * ONLY THE TERRAIN IS SEEN: not the robot's own bodies, not other robots.
+ * lsim_raycast sees ONLY THE TERRAIN; lsim_raycast_bodies (below) adds the collision shapes of the env's OWN robot.  Other envs' robots are never seen.
  *
  * Geometry -- the mesh the contact code collides with (LSIM_BUF_TERRAIN_MESH, word[a][b] of grid vertex (a, b)):
  *   vertex (a, b) = ( (a + dx) * horizontal_scale - border_size, (b + dy) * horizontal_scale - border_size, (int16)(word & 0xFFFF) * vertical_scale ),
@@ -957,7 +958,7 @@ int lsim_eval_accumulate(const lsim_eval* e, void* stream);
  * NOT SUPPORTED: an origin below the surface.  The mesh is a displaced height grid without overhangs; a ray that starts under it reports the first
  *   face it meets from below, which means nothing. */
 #define LSIM_RAYCAST_MAX_RAYS 16384        /* rays per env: a 128 x 128 image; 64 x 48 = 3072, a 16 x 360 lidar = 5760 */
-#define LSIM_RAYCAST_STATE_WORDS 4         /* int64: [0] non-finite rays; [1] reserved; [2] cells walked, [3] triangles tested (only a build with LS_RAYCAST_COUNTERS writes [2], [3]) */
+#define LSIM_RAYCAST_STATE_WORDS 4         /* int64: [0] non-finite rays; [1] reserved; [2] cells walked, [3] triangles tested (only a build with LS_RAYCAST_COUNTERS writes [2], [3], and from lsim_raycast_bodies [1] = primitives that passed the bounding test) */
 typedef struct lsim_raycast {
     const float* root_states;         /* [N,13] simulator buffer, read only */
     const int32_t* mesh;              /* LSIM_BUF_TERRAIN_MESH [grid_rows,grid_cols], or NULL (plane) */
@@ -980,6 +981,84 @@ int lsim_raycast_sizes(size_t* state_bytes);
  * env_stride < 1; out_stride < R or not a multiple of 4; mesh_type outside 0..2; grid_rows or grid_cols < 2 for a mesh; horizontal_scale or
  * vertical_scale not finite and > 0, border_size not finite (mesh only); near < 0, near >= far, far not finite. */
 int lsim_raycast(const lsim_raycast_t* rc, void* stream);
+
+/* ---- range sensors that also see the robot: the terrain of lsim_raycast plus the articulated collision primitives of the env's OWN robot.
+ * ONE launch, same rules as lsim_raycast (caller's stream, no host synchronisation, capturable, read-only on the simulator's buffers).
+ * NOT SUPPORTED: the robots of other envs (they share terrain tiles without colliding; a sensor never sees them).
+ *
+ * Everything lsim_raycast_t says holds for `rc` (terrain geometry, near / far / scale, misses, the non-finite rule and state[0], env_stride), with
+ * these additions.
+ * Sensor frame.  flags == 0: as lsim_raycast, o = p + R(q) mount_pos[e], d = R(q) R(mount_quat[e]) dirs[r].  LSIM_RAYCAST_FRAME_YAW: the same two
+ *   formulas with q replaced by qy = (0, 0, q.z, q.w) / sqrt(q.z^2 + q.w^2) (the base's position and yaw only: a gimbal or chase camera; a base with
+ *   q.z = q.w = 0 makes the pose non-finite).  Body poses below ALWAYS use the full q.
+ * Robot.  k = env_robot[e] (NULL: 0) selects robots[k], 0 <= k < num_robots.  A robot is 17 bodies in the order and tree of lsim_robot_model
+ *   (body 0 the base; leg l = 0..3 has hip 1 + 4l, thigh 2 + 4l, calf 3 + 4l, foot 4 + 4l, each the child of the one before, the hip of body 0)
+ *   and num_prims primitives.  Forward kinematics, from root_states[e][0:7] and th_j = dof_state[e][j][0] ONLY (rigid_body_states is not read:
+ *   after the post-step reset root and joint state are the consistent pair), in coordinates RELATIVE TO THE BASE POSITION p:
+ *     body 0:  P_0 = 0, Q_0 = q.      body b > 0 with parent a:  P_b = P_a + R(Q_a) joint_pos_b,
+ *     Q_b = Q_a * (joint_axis_b sin(th/2), cos(th/2)), th = th_dof_b, or 0 when dof_b < 0 (the fixed feet);  (a * b: R(a * b) = R(a) R(b), xyzw).
+ *   Primitive i on body b:  centre C_i = P_b + R(Q_b) pos_i,  axes = the columns of R(Q_b * quat_i)  (pos, quat: the primitive's pose in the body frame).
+ * Primitives are convex solids, in their own frame (centre at 0):
+ *     LSIM_RAYCAST_PRIM_SPHERE    size[0] = r:               |x| <= r
+ *     LSIM_RAYCAST_PRIM_BOX       size = half extents:       |x_k| <= size[k]
+ *     LSIM_RAYCAST_PRIM_CAPSULE   size[0] = r, size[1] = h:  distance to the segment (0, 0, -h)..(0, 0, h) <= r
+ *     LSIM_RAYCAST_PRIM_CYLINDER  size[0] = r, size[1] = h:  x^2 + y^2 <= r^2 and |z| <= h        (flat caps)
+ * Body test, carried out in the base-relative coordinates: the ray is o' + t d with o' = o - p = R(q or qy) mount_pos[e] -- small, and exact to
+ *   rounding wherever the env stands, so the accuracy of a body hit does not depend on the env's distance from the world origin (the test
+ *   tolerances rest on this: a body hit is judged at the coordinate magnitude of this frame, under a metre).  The set of t with o' + t d inside
+ *   primitive i is an interval [t_in, t_out] (the whole line counts, t may be negative) or empty.  The primitive contributes t_in -- its FRONT
+ *   face -- if near <= t_in <= far, and nothing otherwise: a ray that starts inside a primitive, or enters it before `near`, passes out of it
+ *   freely (a camera may sit inside the trunk box).  Only primitives whose body b has bit b of body_mask set are seen.
+ * Result: t = min(terrain result of lsim_raycast, the contributed t_in of every seen primitive); out[e][r] = t * scale[r], far * scale[r] for a miss.
+ *   A non-finite component of o, d or of any of the twelve th_j of the env: out = far * scale[r], label 0, the ray is counted in state[0].
+ *   With num_prims == 0 for the env's robot, or body_mask == 0, and flags == 0, `out` is lsim_raycast's bit for bit.
+ * labels (may be NULL): labels[e][r] (uint8, label_stride bytes between rows) = 0: the result is `far` and no body gave it; 1: terrain, t < far;
+ *   2 + b: body b.  When a body's t_in equals the terrain's t the body wins; between bodies the primitive earlier in the table wins.  (Terrain met
+ *   exactly at t == far is the value of a miss and is labelled 0.) */
+#define LSIM_RAYCAST_MAX_PRIMS 48          /* primitives per robot (Aliengo: 29) */
+#define LSIM_RAYCAST_PRIM_SPHERE 0
+#define LSIM_RAYCAST_PRIM_BOX 1
+#define LSIM_RAYCAST_PRIM_CAPSULE 2
+#define LSIM_RAYCAST_PRIM_CYLINDER 3
+#define LSIM_RAYCAST_FRAME_YAW 1u          /* flags: the sensor frame follows the base's position and yaw only */
+typedef struct lsim_raycast_prim {
+    int32_t kind, body;               /* LSIM_RAYCAST_PRIM_*, 0..LSIM_NUM_BODIES-1 */
+    float pos[3];                     /* centre in the body frame */
+    float quat[4];                    /* orientation in the body frame, xyzw, unit */
+    float size[3];                    /* per kind, above; unused entries 0 */
+} lsim_raycast_prim;
+typedef struct lsim_raycast_body {    /* the four kinematic fields of lsim_body */
+    float joint_pos[3];
+    float joint_axis[3];
+    int32_t parent, dof;
+} lsim_raycast_body;
+typedef struct lsim_raycast_robot {
+    lsim_raycast_body bodies[LSIM_NUM_BODIES];
+    int32_t num_prims;                /* 0..LSIM_RAYCAST_MAX_PRIMS */
+    int32_t pad[3];
+    lsim_raycast_prim prims[LSIM_RAYCAST_MAX_PRIMS];
+} lsim_raycast_robot;
+typedef struct lsim_raycast_bodies {
+    lsim_raycast_t rc;                /* as for lsim_raycast */
+    const float* dof_state;           /* [N,12,2] simulator buffer, read only */
+    const uint8_t* env_robot;         /* [N] robot index per env, or NULL: robot 0 */
+    const lsim_raycast_robot* robots; /* [num_robots] DEVICE memory: what the launch reads */
+    const lsim_raycast_robot* robots_host;  /* the same bytes in HOST memory: what the argument check reads (a launch replayed from a graph checks nothing) */
+    uint8_t* labels;                  /* [N,label_stride] or NULL */
+    int32_t num_robots;               /* 1..LSIM_MAX_ROBOTS; 1 when env_robot == NULL */
+    int32_t label_stride;             /* bytes between rows of labels: >= R (ignored when labels == NULL) */
+    uint32_t body_mask;               /* bit b: body b is seen */
+    uint32_t flags;                   /* LSIM_RAYCAST_FRAME_YAW or 0 */
+} lsim_raycast_bodies_t;
+/* bytes of `state` (lsim_raycast's) and of one lsim_raycast_robot.  LSIM_E_INVALID: a NULL output pointer */
+int lsim_raycast_bodies_sizes(size_t* state_bytes, size_t* robot_bytes);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch: rb == NULL; anything lsim_raycast refuses in rb->rc;
+ * dof_state, robots or robots_host NULL or not 4-byte aligned; num_robots outside 1..LSIM_MAX_ROBOTS, or != 1 with env_robot == NULL (a table of
+ * several robots without the table of which env runs which); labels != NULL with label_stride < R; a flag bit other than LSIM_RAYCAST_FRAME_YAW;
+ * and in robots_host[0..num_robots): num_prims outside 0..LSIM_RAYCAST_MAX_PRIMS; a body whose parent / dof is not the tree's above (dof: -1 or
+ * 0..11) or whose joint_pos / joint_axis is not finite; a primitive with kind outside 0..3, body outside 0..16, a non-finite pos or quat, or a
+ * size entry it uses (sphere 1, box 3, capsule / cylinder 2) that is not finite and > 0. */
+int lsim_raycast_bodies(const lsim_raycast_bodies_t* rb, void* stream);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,9 @@ LsimWgradPending = STRUCTS["lsim_wgrad_pending"]
 LsimAmpDisc = STRUCTS["lsim_amp_disc"]
 LsimEval = STRUCTS["lsim_eval"]
 LsimRaycast = STRUCTS["lsim_raycast_t"]
+LsimRaycastBodies = STRUCTS["lsim_raycast_bodies_t"]
+LsimRaycastRobot = STRUCTS["lsim_raycast_robot"]
+LsimRaycastPrim = STRUCTS["lsim_raycast_prim"]
 
 REWARD_IDS = {k[len("LSIM_R_"):].lower(): v for k, v in ENUMS["lsim_reward_id"].items() if k.startswith("LSIM_R_")}
 NUM_REWARD_TERMS = ENUMS["lsim_reward_id"]["LSIM_NUM_REWARD_TERMS"]
@@ -115,6 +118,8 @@ RNG_TAGS = {k[len("LSIM_RNG_"):].lower(): v for k, v in ENUMS["lsim_rng_tag"].it
 DT_F32, DT_I64, DT_U8, DT_I32, DT_I16 = (DEFINES[k] for k in ("LSIM_DT_F32", "LSIM_DT_I64", "LSIM_DT_U8", "LSIM_DT_I32", "LSIM_DT_I16"))
 E_INVALID, E_NOMEM, E_HIP, E_UNSUPPORTED, E_ABI = (DEFINES[k] for k in ("LSIM_E_INVALID", "LSIM_E_NOMEM", "LSIM_E_HIP", "LSIM_E_UNSUPPORTED", "LSIM_E_ABI"))
 ABI_VERSION = DEFINES["LSIM_ABI_VERSION"]
+RAYCAST_PRIM_KINDS = {k[len("LSIM_RAYCAST_PRIM_"):].lower(): v for k, v in DEFINES.items() if k.startswith("LSIM_RAYCAST_PRIM_")}
+RAYCAST_FRAME_YAW = DEFINES["LSIM_RAYCAST_FRAME_YAW"]
 STEP_SKIP_PHYSICS = DEFINES["LSIM_STEP_SKIP_PHYSICS"]
 STEP_NO_RESET = DEFINES["LSIM_STEP_NO_RESET"]
 STEP_RECORD_SUBSTEPS = DEFINES["LSIM_STEP_RECORD_SUBSTEPS"]

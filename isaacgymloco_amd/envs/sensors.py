@@ -1,15 +1,22 @@
-"""Range sensors on the terrain mesh (include/lsim.h, lsim_raycast): depth cameras and lidar.
+"""Range sensors on the terrain mesh and the robot's own collision shapes (include/lsim.h, lsim_raycast / lsim_raycast_bodies): depth cameras and lidar.
 
-    cam = depth_camera(env, 64, 48, hfov_deg=87, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30, near=0.05, far=5.0)
+    cam = depth_camera(env, 64, 48, hfov_deg=87, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30, near=0.05, far=5.0, see_robot=True, labels=True)
     env.add_sensor("depth", cam)            # from now on every env.step_device() ends with one more launch
     img = env.sensors["depth"].image()      # [N, 48, 64] z-depth in metres, the live device tensor of the latest step
+    seg = env.sensors["depth"].label_image()    # [N, 48, 64] uint8: 0 nothing, 1 terrain, 2 + b body b (env.sensors["depth"].body_names[b])
 
 A sensor is one HIP launch over all envs and rays, on the current stream, without host synchronisation; it reads the post-step, post-reset
-`root_states`, so it is consistent with the observations of the same step.  ONLY THE TERRAIN IS SEEN: not the robot's own bodies, not
-other robots.  There is no torch fall-back: without the library's lsim_raycast the constructor raises.
+`root_states` (and `dof_state`), so it is consistent with the observations of the same step.  What is seen: by default (`see_robot=False`) the
+terrain only, through lsim_raycast exactly as before.  `see_robot=True` adds the URDF collision primitives of the env's OWN robot (trunk box,
+hip and rotor cylinders -- capsules under asset.replace_cylinder_with_capsule --, thigh and calf boxes, foot spheres), posed by forward kinematics
+inside the launch (lsim_raycast_bodies); `ignore_bodies` hides bodies by name or index.  A ray that starts inside a shape passes out of it
+freely, so a camera mounted inside the trunk box still sees the legs and the ground.  The robots of OTHER envs are never seen.  There is no torch
+fall-back: without the library's entry point the constructor raises.
 
-Frames: the sensor frame is the base frame moved by the mount -- x forward, y left, z up, as the reference's base frame.  A camera looks along
-its +x; image rows run top to bottom, columns left to right (row-major, r = row * width + col).
+Frames: the sensor frame is the base frame moved by the mount -- x forward, y left, z up, as the reference's base frame; `frame="yaw"` keeps the
+base's position and yaw but not its roll and pitch (a gimbal, or with a mount behind and above the robot a chase camera: a third-person depth
+frame of the env's robot on its terrain, tools/sensor_frames.py).  A camera looks along its +x; image rows run top to bottom, columns left to
+right (row-major, r = row * width + col).
 """
 import ctypes
 import math
@@ -18,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import abi, lib
+from . import config
 
 
 def quat_from_pitch(pitch_deg):
@@ -50,13 +58,24 @@ def ring_dirs(channels, vfov_deg, points_per_rev):
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
-    rendered (the other rows of the output keep their initial value, `far`).  `update()` launches once and returns the live [N, R] tensor."""
+    rendered (the other rows of the output keep their initial value, `far`).  `update()` launches once and returns the live [N, R] tensor.
+    `see_robot=True`: the env's own robot is seen too (lsim_raycast_bodies), except the bodies of `ignore_bodies` (names or indices);
+    `labels=True` (needs see_robot): `labels()` is the live uint8 [N, R] tensor of what each ray met; `frame`: "base" or "yaw" (module docstring).
+    With the defaults nothing of this is allocated and the launch is lsim_raycast."""
 
-    def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None):
+    def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base"):
         self.env = env
         self._api = api if api is not None else env._L
-        if not hasattr(self._api, "lsim_raycast"):
-            raise lib.LsimError("the loaded library has no lsim_raycast: rebuild it (there is no torch fall-back for the range sensors)")
+        if frame not in ("base", "yaw"):
+            raise ValueError(f"frame: expected 'base' or 'yaw', got {frame!r}")
+        self.see_robot, self.frame = bool(see_robot), frame
+        self._bodies = self.see_robot or frame == "yaw"       # the yaw frame is the new entry point's, with or without bodies
+        if (labels or len(tuple(ignore_bodies))) and not self.see_robot:
+            raise ValueError("labels / ignore_bodies need see_robot=True")
+        need = "lsim_raycast_bodies" if self._bodies else "lsim_raycast"
+        if not hasattr(self._api, need):
+            raise lib.LsimError(f"the loaded library has no {need}: rebuild it (there is no torch fall-back for the range sensors)")
         dev = env.root_states.device
         N = int(env.num_envs)
         self.dirs = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device=dev).contiguous()
@@ -69,8 +88,13 @@ class RaySensor:
         if self.scale is not None:
             self._out[:, :R] *= self.scale
         self.out = self._out[:, :R]
-        nbytes = ctypes.c_size_t()
-        lib.check(self._api.lsim_raycast_sizes(ctypes.byref(nbytes)), what="lsim_raycast_sizes")
+        nbytes, rbytes = ctypes.c_size_t(), ctypes.c_size_t()
+        if self._bodies:
+            lib.check(self._api.lsim_raycast_bodies_sizes(ctypes.byref(nbytes), ctypes.byref(rbytes)), what="lsim_raycast_bodies_sizes")
+            if rbytes.value != ctypes.sizeof(abi.LsimRaycastRobot):
+                raise lib.LsimError("lsim_raycast_robot: the library's layout differs from include/lsim.h; rebuild")
+        else:
+            lib.check(self._api.lsim_raycast_sizes(ctypes.byref(nbytes)), what="lsim_raycast_sizes")
         self.state = torch.zeros(nbytes.value // 8, dtype=torch.int64, device=dev)
         lc = env.lcfg
         rc = abi.LsimRaycast()
@@ -85,6 +109,57 @@ class RaySensor:
         rc.num_envs, rc.num_rays, rc.env_stride, rc.out_stride = N, R, self.env_stride, stride
         rc.near, rc.far = self.near, self.far
         self._rc = rc
+        self._labels = None
+        if self._bodies:
+            self._setup_bodies(rc, ignore_bodies, labels, dev)
+
+    def _setup_bodies(self, rc, ignore_bodies, labels, dev):
+        """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
+        from ..robots.model import build_sensor_table
+        env = self.env
+        tables = getattr(env, "sensor_tables", None)          # (tables, body names) given by the env (the test doubles), else from its config
+        if tables is None:
+            robots = getattr(env, "robots", None)
+            assets = [env.cfg.asset] if robots is None else [config.robot_cfg(env.cfg, k).asset for k in range(len(robots))]
+            built = [build_sensor_table(a) for a in assets]
+            tables = ([t for t, _ in built], built[0][1])
+        tabs, self.body_names = list(tables[0]), list(tables[1])
+        if not self.see_robot:
+            tabs = [abi.LsimRaycastRobot.from_buffer_copy(t) for t in tabs]
+            for t in tabs:
+                t.num_prims = 0
+        self._robots_host = (abi.LsimRaycastRobot * len(tabs))(*tabs)
+        raw = np.frombuffer(self._robots_host, dtype=np.uint8).copy()
+        self._robots_dev = torch.from_numpy(raw).to(dev)
+        mask = (1 << abi.DEFINES["LSIM_NUM_BODIES"]) - 1
+        for b in ignore_bodies:
+            if isinstance(b, str):
+                hit = [i for i, n in enumerate(self.body_names) if n == b] or [i for i, n in enumerate(self.body_names) if b in n]
+                if not hit:
+                    raise ValueError(f"ignore_bodies: no body named {b!r} (bodies: {self.body_names})")
+            else:
+                hit = [int(b)]
+                if not 0 <= hit[0] < abi.DEFINES["LSIM_NUM_BODIES"]:
+                    raise ValueError(f"ignore_bodies: body index {b} out of range")
+            for i in hit:
+                mask &= ~(1 << i)
+        self.body_mask = mask
+        rb = abi.LsimRaycastBodies()
+        rb.rc = rc
+        rb.dof_state = env.dof_state.data_ptr()
+        rb.robots = self._robots_dev.data_ptr()
+        rb.robots_host = ctypes.addressof(self._robots_host)
+        rb.num_robots = len(tabs)
+        if len(tabs) > 1:
+            self._env_robot = env.robot_ids.to(device=dev, dtype=torch.uint8).contiguous()
+            rb.env_robot = self._env_robot.data_ptr()
+        rb.body_mask = mask
+        rb.flags = abi.RAYCAST_FRAME_YAW if self.frame == "yaw" else 0
+        if labels:
+            R = self.num_rays
+            self._labels = torch.zeros((int(env.num_envs), (R + 3) // 4 * 4), dtype=torch.uint8, device=dev)
+            rb.labels, rb.label_stride = self._labels.data_ptr(), self._labels.shape[1]
+        self._rb = rb
 
     def _per_env(self, pose, width, dev):
         N = int(self.env.num_envs)
@@ -111,8 +186,17 @@ class RaySensor:
 
     def update(self, stream=None):
         """one launch on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor"""
-        lib.check(self._api.lsim_raycast(ctypes.byref(self._rc), self._stream(stream)), what="lsim_raycast")
+        if self._bodies:
+            lib.check(self._api.lsim_raycast_bodies(ctypes.byref(self._rb), self._stream(stream)), what="lsim_raycast_bodies")
+        else:
+            lib.check(self._api.lsim_raycast(ctypes.byref(self._rc), self._stream(stream)), what="lsim_raycast")
         return self.out
+
+    def labels(self):
+        """live uint8 [N, R] tensor of the latest launch (labels=True): 0 nothing within [near, far], 1 terrain, 2 + b body b (`body_names[b]`)"""
+        if self._labels is None:
+            raise ValueError("the sensor was created without labels=True")
+        return self._labels[:, :self.num_rays]
 
     @property
     def nonfinite_rays(self):
@@ -121,24 +205,32 @@ class RaySensor:
 
 
 class DepthCamera(RaySensor):
-    def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None):
+    def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None, **bodies):
         dirs, scale = pinhole_dirs(width, height, hfov_deg)
         self.width, self.height = int(width), int(height)
-        super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg), near, far, scale=scale, env_stride=env_stride, api=api)
+        super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg), near, far, scale=scale, env_stride=env_stride, api=api, **bodies)
 
     def image(self):
         """[N, H, W] view of the output: z-depth along the optical axis in metres, far * cos where nothing is hit"""
         return self.out.unflatten(1, (self.height, self.width))
 
+    def label_image(self):
+        """[N, H, W] view of labels()"""
+        return self.labels().unflatten(1, (self.height, self.width))
 
-def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None):
-    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` as RaySensor's"""
-    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api)
+
+def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base"):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last four keywords as RaySensor's"""
+    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api,
+                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame)
 
 
-def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None):
+def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
+          see_robot=False, ignore_bodies=(), labels=False, frame="base"):
     """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
-    `points_per_rev` azimuths each; reports range (scale=None)"""
-    s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api)
+    `points_per_rev` azimuths each; reports range (scale=None); the last four keywords as RaySensor's"""
+    s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
+                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame)
     s.channels, s.points_per_rev = int(channels), int(points_per_rev)
     return s

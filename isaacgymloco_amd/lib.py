@@ -103,6 +103,9 @@ def load_path(path):
     L.lsim_eval_accumulate.argtypes = [ctypes.POINTER(abi.LsimEval), vp]
     L.lsim_raycast_sizes.argtypes = [sz]
     L.lsim_raycast.argtypes = [ctypes.POINTER(abi.LsimRaycast), vp]
+    if hasattr(L, "lsim_raycast_bodies"):      # a library older than the entry point still loads; envs/sensors.py raises when see_robot needs it
+        L.lsim_raycast_bodies_sizes.argtypes = [sz, sz]
+        L.lsim_raycast_bodies.argtypes = [ctypes.POINTER(abi.LsimRaycastBodies), vp]
     L.lsim_destroy.argtypes = [vp]
     L.lsim_destroy.restype = None
     return L

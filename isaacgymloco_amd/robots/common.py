@@ -115,3 +115,55 @@ def collision_points(bodies, foot_name="foot", max_points=None):
         if len(pts) <= max_points:
             return pts
     return pts[:max_points]
+
+
+def quat_from_matrix(R):
+    """xyzw of a rotation matrix (w >= 0)"""
+    R = np.asarray(R, dtype=np.float64)
+    K = np.array([[R[0, 0] - R[1, 1] - R[2, 2], R[1, 0] + R[0, 1], R[2, 0] + R[0, 2], R[2, 1] - R[1, 2]],
+                  [R[1, 0] + R[0, 1], R[1, 1] - R[0, 0] - R[2, 2], R[2, 1] + R[1, 2], R[0, 2] - R[2, 0]],
+                  [R[2, 0] + R[0, 2], R[2, 1] + R[1, 2], R[2, 2] - R[0, 0] - R[1, 1], R[1, 0] - R[0, 1]],
+                  [R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1], R[0, 0] + R[1, 1] + R[2, 2]]]) / 3.0
+    w, v = np.linalg.eigh(K)
+    q = v[:, np.argmax(w)]
+    return q if q[3] >= 0 else -q
+
+
+def sensor_table(bodies, capsule=True):
+    """lsim_raycast_robot (include/lsim.h) of a robot for the body-aware range sensors (envs/sensors.py, see_robot=True): the 17 bodies'
+    kinematic fields and EVERY URDF collision primitive of `bodies[i]["prims"]` as it is -- spheres and boxes unchanged; a cylinder as a capsule
+    of the same radius and segment length when `capsule` (asset.replace_cylinder_with_capsule, AGC:131: what the reference's simulator
+    collides with, the rule collision_points above follows), as a flat-capped cylinder otherwise.  Nothing is dropped or merged: a sensor sees
+    the shapes, not the contact model's sample points."""
+    kinds = abi.RAYCAST_PRIM_KINDS
+    t = abi.LsimRaycastRobot()
+    if len(bodies) != abi.DEFINES["LSIM_NUM_BODIES"]:
+        raise ValueError(f"expected {abi.DEFINES['LSIM_NUM_BODIES']} bodies, got {len(bodies)}")
+    n = 0
+    for i, b in enumerate(bodies):
+        tb = t.bodies[i]
+        for k in range(3):
+            tb.joint_pos[k] = float(b["joint_pos"][k])
+            tb.joint_axis[k] = float(b["axis"][k])
+        tb.parent, tb.dof = int(b["parent"]), int(b["dof"])
+        for kind, dims, pos, R in b.get("prims", ()):
+            if n >= abi.DEFINES["LSIM_RAYCAST_MAX_PRIMS"]:
+                raise ValueError(f"more than LSIM_RAYCAST_MAX_PRIMS = {abi.DEFINES['LSIM_RAYCAST_MAX_PRIMS']} collision primitives")
+            p = t.prims[n]
+            p.body = i
+            if kind == "sphere":
+                p.kind, size = kinds["sphere"], (float(dims[0]), 0.0, 0.0)
+            elif kind == "box":
+                p.kind, size = kinds["box"], tuple(0.5 * float(d) for d in dims)
+            elif kind == "cylinder":
+                p.kind, size = kinds["capsule" if capsule else "cylinder"], (float(dims[0]), 0.5 * float(dims[1]), 0.0)
+            else:
+                raise ValueError(f"collision primitive {kind!r} is not one of sphere, box, cylinder")
+            q = quat_from_matrix(R)
+            for k in range(3):
+                p.pos[k], p.size[k] = float(pos[k]), size[k]
+            for k in range(4):
+                p.quat[k] = float(q[k])
+            n += 1
+    t.num_prims = n
+    return t

@@ -8,6 +8,9 @@ camera (87 degrees, far 5 m, pitched down 30 degrees, 0.3 m ahead of the base), 
 vertical, far 10 m), each with rays/s; `kernel_a_us` = kernel A from the library's own events (lsim_read_profile) in the same process;
 `cells_per_ray` / `triangles_per_ray` = the walk's two debug counters, from one launch through a build of the library with
 -DLS_RAYCAST_COUNTERS (isaacgymloco_amd/csrc/liblsim_rccount.so, built here when stale; the product build has no counters).
+`--bodies`: each sensor is also timed with see_robot=True (lsim_raycast_bodies, all bodies seen) in the same process, next to lsim_raycast and
+kernel A: `<sensor>_bodies_us`, its ratio to the terrain-only launch, the share of rays that end on a body, and from the counters build the
+primitives that passed the bounding test per ray and the cells walked per ray (the walk stops at the body hit).
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -52,7 +55,18 @@ def counters(sensor, count_lib):
     return st[2] / rays, st[3] / rays, st[0]
 
 
-def measure(n, terrain, iters, warmup, count_lib):
+def counters_bodies(sensor, count_lib):
+    """(primitives past the bounding test, cells, triangles) per ray of one lsim_raycast_bodies launch through the counters build"""
+    sensor.state.zero_()
+    lib.check(count_lib.lsim_raycast_bodies(ctypes.byref(sensor._rb), sensor.env._stream()), what="lsim_raycast_bodies (counters build)")
+    torch.cuda.synchronize()
+    st = sensor.state.cpu().tolist()
+    rays = sensor.num_rays * sensor.env.num_envs
+    sensor.state.zero_()
+    return st[1] / rays, st[2] / rays, st[3] / rays
+
+
+def measure(n, terrain, iters, warmup, count_lib, bodies=False):
     cfg = C.aliengo_cfg()
     cfg.env.num_envs = n
     cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
@@ -85,6 +99,20 @@ def measure(n, terrain, iters, warmup, count_lib):
             cells, tris, bad = counters(s, count_lib)
             out[name + "_cells_per_ray"], out[name + "_triangles_per_ray"] = cells, tris
         out[name + "_nonfinite_rays"] = int(s.nonfinite_rays.item())
+    if bodies:
+        camb = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True)
+        lidb = sensors.lidar(env, 16, 30.0, 360, mount_pos=(0.0, 0.0, 0.15), near=0.05, far=10.0, see_robot=True, labels=True)
+        for name, s in (("camera", camb), ("lidar", lidb)):
+            us = timed(s.update, iters, warmup)
+            out[name + "_bodies_us"] = us
+            out[name + "_bodies_over_terrain_only"] = us / out[name + "_us"]
+            out[name + "_bodies_over_kernel_a"] = us / out["kernel_a_us"]
+            out[name + "_body_share"] = float((s.labels() >= 2).float().mean().item())
+            out[name + "_primitives"] = int(s._robots_host[0].num_prims)
+            if count_lib is not None:
+                prims, cells, tris = counters_bodies(s, count_lib)
+                out[name + "_bodies_prims_tested_per_ray"], out[name + "_bodies_cells_per_ray"], out[name + "_bodies_triangles_per_ray"] = prims, cells, tris
+            out[name + "_bodies_nonfinite_rays"] = int(s.nonfinite_rays.item())
     out["torch_us"] = None
     return out
 
@@ -96,6 +124,7 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-counters", action="store_true")
+    ap.add_argument("--bodies", action="store_true", help="also time lsim_raycast_bodies (see_robot=True) on every workload")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -109,7 +138,7 @@ def main():
         count_lib = lib.load_path(COUNT_LIB)
     res = {"tool": "raycast_time", "iters": a.iters, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
            "camera": "64x48, hfov 87, pitch 30 down, far 5 m", "lidar": "16x360, vfov 30, far 10 m",
-           "cases": [measure(a.num_envs, t, a.iters, a.warmup, count_lib) for t in a.terrains.split(",")]}
+           "cases": [measure(a.num_envs, t, a.iters, a.warmup, count_lib, a.bodies) for t in a.terrains.split(",")]}
     line = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:

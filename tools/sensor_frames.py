@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Third-person depth and label frames of robots on their terrain, without a viewer: a frame="yaw" chase camera (envs/sensors.py, see_robot=True).
+
+    python tools/sensor_frames.py --out frames/ [--task aliengo] [--num-envs 64] [--envs 0,1,2] [--steps 50] [--every 10]
+                                  [--checkpoint model.pt] [--width 160] [--height 120] [--terrain stairs]
+
+Steps the env under a checkpoint's actor (learn/evaluate.py's loader) or zero actions; every `--every` steps writes, for each chosen env,
+`depth_e<env>_s<step>.npy` (float32 [H, W] z-depth in metres), `labels_e<env>_s<step>.npy` (uint8: 0 nothing, 1 terrain, 2 + b body b) and the
+same two as 8-bit PGM (depth: near = white, far = black; labels: spread over the grey range).  A PGM is a text header plus raw bytes."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+
+def write_pgm(path, img8):
+    """binary PGM (P5) of a uint8 [H, W] array"""
+    img8 = np.ascontiguousarray(img8, dtype=np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (img8.shape[1], img8.shape[0]))
+        f.write(img8.tobytes())
+
+
+def depth_to_gray(depth, near, far):
+    d = np.clip((np.asarray(depth, np.float64) - near) / (far - near), 0.0, 1.0)
+    return np.round(255.0 * (1.0 - d)).astype(np.uint8)
+
+
+def labels_to_gray(labels):
+    lab = np.asarray(labels, np.int64)
+    return np.where(lab == 0, 0, np.where(lab == 1, 60, 80 + (lab - 2) * 10)).astype(np.uint8)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--task", default="aliengo")
+    ap.add_argument("--num-envs", type=int, default=64)
+    ap.add_argument("--envs", default="0")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--every", type=int, default=10)
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--terrain", choices=("flat", "stairs"), default="stairs")
+    ap.add_argument("--width", type=int, default=160)
+    ap.add_argument("--height", type=int, default=120)
+    ap.add_argument("--hfov", type=float, default=60.0)
+    ap.add_argument("--mount", default="-1.2,0.0,0.7", help="camera position in the yaw frame of the base (behind and above)")
+    ap.add_argument("--pitch", type=float, default=28.0)
+    ap.add_argument("--far", type=float, default=5.0)
+    a = ap.parse_args()
+    import torch
+    from isaacgymloco_amd.envs import config as C, sensors
+    from isaacgymloco_amd.envs.legged_robot import LeggedRobot
+    cfg = C.aliengo_cfg() if a.task == "aliengo" else C.robot_cfg(C.mixed_cfg("aliengo", {"aliengo": 0.5, a.task: 0.5})[0], 1)
+    cfg.env.num_envs = a.num_envs
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if a.terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    cam = env.add_sensor("chase", sensors.depth_camera(env, a.width, a.height, a.hfov, mount_pos=tuple(float(v) for v in a.mount.split(",")),
+                                                       pitch_deg=a.pitch, near=0.05, far=a.far, see_robot=True, labels=True, frame="yaw"))
+    env.reset()
+    policy = None
+    if a.checkpoint:
+        from isaacgymloco_amd.learn import evaluate
+        policy = evaluate._actor_critic(env, a.checkpoint, "cuda:0").act_inference
+    ids = [int(v) for v in a.envs.split(",")]
+    os.makedirs(a.out, exist_ok=True)
+    zero = torch.zeros(a.num_envs, 12, device="cuda:0")
+    for step in range(1, a.steps + 1):
+        with torch.no_grad():
+            actions = zero if policy is None else policy(env.get_observations())
+        env.step_device(actions)
+        if step % a.every == 0 or step == a.steps:
+            depth, labels = cam.image().cpu().numpy(), cam.label_image().cpu().numpy()
+            for e in ids:
+                stem = f"e{e}_s{step:04d}"
+                np.save(os.path.join(a.out, f"depth_{stem}.npy"), depth[e])
+                np.save(os.path.join(a.out, f"labels_{stem}.npy"), labels[e])
+                write_pgm(os.path.join(a.out, f"depth_{stem}.pgm"), depth_to_gray(depth[e], cam.near, cam.far))
+                write_pgm(os.path.join(a.out, f"labels_{stem}.pgm"), labels_to_gray(labels[e]))
+    print(f"{len(ids)} env(s), frames under {a.out}; non-finite rays: {int(cam.nonfinite_rays)}")
+
+
+if __name__ == "__main__":
+    main()
