@@ -1,9 +1,10 @@
 """ctypes mirror of include/lsim.h, generated at import time by parsing the header.
 
 The header is the single source of truth for the C-ABI (struct layouts, enums,
-#defines); parsing it here means a field added to `lsim_config` can never silently
-disagree with the Python side.  `lsim_sizeof_config()` / `lsim_sizeof_model()` are
-checked against these mirrors when a library is loaded (see `check_abi`).
+#defines and function prototypes); parsing it here means a field added to `lsim_config`
+or a parameter added to an entry point can never silently disagree with the Python side.
+`lsim_sizeof_config()` / `lsim_sizeof_model()` are checked against these mirrors when a
+library is loaded (see `check_abi`); `bind` types a library's functions from `PROTOTYPES`.
 """
 import ctypes
 import os
@@ -136,19 +137,68 @@ def structs_for(overrides):
         return _parse(f.read(), overrides)[2]
 
 
+_SCALARS = {**_CTYPES, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "lsim_handle": ctypes.c_void_p}
+_RESTYPES = {"int": ctypes.c_int, "void": None, "const char*": ctypes.c_char_p}
+
+
+def _param_type(param, structs, decl):
+    """a scalar by its fixed-width type, lsim_handle as void*, a pointer to a header struct as POINTER(mirror), any other pointer or array as void*"""
+    m = re.match(r"(\w+)\s*((?:\*\s*)*)(\w+)?\s*((?:\[[^\]]*\])*)$", re.sub(r"\bconst\b", "", param).strip())
+    if m:
+        base, stars, dims = m.group(1), m.group(2).count("*"), m.group(4)
+        if not stars and not dims and base in _SCALARS:
+            return _SCALARS[base]
+        if stars == 1 and not dims and base in structs:      # byref(struct) and arrays of the struct
+            return ctypes.POINTER(structs[base])
+        if (stars or dims) and (base == "void" or base in _SCALARS):
+            return ctypes.c_void_p
+    raise ValueError(f"include/lsim.h: cannot bind parameter '{param.strip()}' of '{decl}'")
+
+
+def parse_prototypes(text, structs):
+    """{name: (restype, argtypes)} of every function `text` declares; a declaration the rules above cannot type raises, naming it"""
+    text = re.sub(r"^\s*#.*$", "", _strip_comments(text), flags=re.M)
+    protos = {}
+    for m in re.finditer(r"([\w \t*]+?)\b(lsim_\w+)\s*\(([^()]*)\)\s*;", text):
+        decl = " ".join(m.group(0).split())
+        ret = re.sub(r"\s*\*", "*", " ".join(m.group(1).split()))
+        if ret not in _RESTYPES or m.group(2) in protos:
+            raise ValueError(f"include/lsim.h: cannot bind '{decl}' (return type or a second declaration)")
+        params = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+        protos[m.group(2)] = (_RESTYPES[ret], [_param_type(p, structs, decl) for p in params])
+    skipped = set(re.findall(r"\b(lsim_\w+)\s*\(", text)) - set(protos)
+    if skipped:
+        raise ValueError(f"include/lsim.h: declarations not understood: {sorted(skipped)}")
+    return protos
+
+
+with open(HEADER_PATH) as _f:
+    PROTOTYPES = parse_prototypes(_f.read(), STRUCTS)
+
+
 def declared_functions():
-    """Names of every function the header declares (used by the 'exports every symbol' test)."""
-    with open(HEADER_PATH) as f:
-        text = _strip_comments(f.read())
-    return sorted(set(re.findall(r"\b(lsim_\w+)\s*\(", text)) - {"lsim_sim"})
+    """Names of every function the header declares."""
+    return sorted(PROTOTYPES)
+
+
+def bind(L, prefix="lsim", names=None):
+    """set restype / argtypes of `prefix`_<name> on the library `L` from the header, for every declared function or for `names` (header
+    names, lsim_<name>); raises, listing them, if `L` lacks any of those symbols"""
+    names = sorted(PROTOTYPES) if names is None else list(names)
+    symbol = {n: prefix + n[len("lsim"):] for n in names}
+    missing = [s for s in symbol.values() if not hasattr(L, s)]
+    if missing:
+        raise RuntimeError(f"{getattr(L, '_name', L)} does not export {missing}")
+    for n, s in symbol.items():
+        fn = getattr(L, s)
+        fn.restype, fn.argtypes = PROTOTYPES[n]
+    return L
 
 
 def check_abi(lib, prefix="lsim", structs=None):
     """Raise if the loaded library was built against a different struct layout."""
     structs = structs or STRUCTS
     for what, struct in (("config", structs["lsim_config"]), ("model", structs["lsim_robot_model"])):
-        fn = getattr(lib, f"{prefix}_sizeof_{what}")
-        fn.restype = ctypes.c_int
-        got = fn()
+        got = getattr(lib, f"{prefix}_sizeof_{what}")()
         if got != ctypes.sizeof(struct):
             raise RuntimeError(f"ABI mismatch: {prefix}_sizeof_{what}() = {got}, python mirror = {ctypes.sizeof(struct)}; rebuild the library")

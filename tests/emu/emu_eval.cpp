@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE -- CPU shim of the evaluator launch (isaacgymloco_amd/csrc/ls_eval.h): the same per-env / per-block functions the HIP kernel
-// lsim_k_eval calls, in the same order, with the lanes of a block looped and plain memory in place of LDS and atomics.  `order` (may be NULL) is
-// a permutation of the envs: the order in which the "lanes" run, to show that the table does not depend on it.
+// lsim_k_eval calls, in the same order, with the lanes of a block looped and plain memory in place of LDS and atomics.  The entry points carry
+// the signatures of include/lsim.h (the stream is ignored); the test-only emu_eval_accumulate_ordered runs the same loops with `order` (may be
+// NULL), a permutation of the envs: the order in which the "lanes" run, to show that the table does not depend on it.
 #define LS_EMU 1
 #include <string.h>
 #include <vector>
@@ -11,7 +12,7 @@ extern "C" int emu_eval_sizes(int64_t num_envs, int num_groups, int num_trace_en
     return ls_eval_sizes(num_envs, num_groups, num_trace_envs, trace_capacity, state_bytes, table_bytes, trace_bytes);
 }
 
-extern "C" int emu_eval_clear(const lsim_eval* e) {
+extern "C" int emu_eval_clear(const lsim_eval* e, void* /*stream*/) {
     const int rc = ls_eval_validate(e);
     if (rc != LSIM_OK) return rc;
     size_t sb, tb, rb;
@@ -22,7 +23,7 @@ extern "C" int emu_eval_clear(const lsim_eval* e) {
     return LSIM_OK;
 }
 
-extern "C" int emu_eval_accumulate(const lsim_eval* ep, const int32_t* order) {
+extern "C" int emu_eval_accumulate_ordered(const lsim_eval* ep, const int32_t* order) {
     const int rc = ls_eval_validate(ep);
     if (rc != LSIM_OK) return rc;
     const lsim_eval& e = *ep;
@@ -50,3 +51,5 @@ extern "C" int emu_eval_accumulate(const lsim_eval* ep, const int32_t* order) {
     *st.counter = t + 1;
     return LSIM_OK;
 }
+
+extern "C" int emu_eval_accumulate(const lsim_eval* e, void* /*stream*/) { return emu_eval_accumulate_ordered(e, nullptr); }

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE -- CPU shim of the range-sensor launch (isaacgymloco_amd/csrc/ls_raycast.h): the same per-ray function the HIP kernel
 // lsim_k_raycast calls, over the same (block, lane) -> (env, ray) map, with the lanes looped.  Compile with -DLS_RAYCAST_COUNTERS to have the
-// cells-walked / triangles-tested counters in state[2], state[3].
+// cells-walked / triangles-tested counters in state[2], state[3].  The entry points carry the signatures of include/lsim.h (the stream is ignored).
 #define LS_EMU 1
 #include "../../isaacgymloco_amd/csrc/ls_raycast.h"
 
@@ -10,7 +10,7 @@ extern "C" int emu_raycast_sizes(size_t* state_bytes) {
     return LSIM_OK;
 }
 
-extern "C" int emu_raycast(const lsim_raycast_t* rcp) {
+extern "C" int emu_raycast(const lsim_raycast_t* rcp, void* /*stream*/) {
     const int rv = ls_rc_validate(rcp);
     if (rv != LSIM_OK) return rv;
     const lsim_raycast_t& rc = *rcp;

@@ -1,7 +1,8 @@
 // TEST INFRASTRUCTURE -- CPU shim of the body-aware range-sensor launch (isaacgymloco_amd/csrc/ls_raycast_bodies.h): the same per-block and
 // per-ray functions the HIP kernel lsim_k_raycast_bodies calls, over the same (block, lane) -> (env, ray) map, the lanes looped and each
-// __syncthreads() a loop boundary.  `bodies_out` (may be NULL) receives the block's 17 body poses (8 floats each: base-relative position,
-// quaternion) of every env it renders, so that the forward kinematics can be tested on its own.  Compile with -DLS_RAYCAST_COUNTERS for the counters.
+// __syncthreads() a loop boundary.  The entry points carry the signatures of include/lsim.h (the stream is ignored); the test-only
+// emu_raycast_bodies_poses runs the same loops and also writes the block's 17 body poses (8 floats each: base-relative position, quaternion)
+// of every env it renders to `bodies_out`, so that the forward kinematics can be tested on its own.  Compile with -DLS_RAYCAST_COUNTERS for the counters.
 #define LS_EMU 1
 #include "../../isaacgymloco_amd/csrc/ls_raycast_bodies.h"
 #include <string.h>
@@ -13,7 +14,7 @@ extern "C" int emu_raycast_bodies_sizes(size_t* state_bytes, size_t* robot_bytes
     return LSIM_OK;
 }
 
-extern "C" int emu_raycast_bodies(const lsim_raycast_bodies_t* rbp, float* bodies_out) {
+extern "C" int emu_raycast_bodies_poses(const lsim_raycast_bodies_t* rbp, float* bodies_out) {
     const int rv = ls_rcb_validate(rbp);
     if (rv != LSIM_OK) return rv;
     const lsim_raycast_bodies_t& rb = *rbp;
@@ -35,3 +36,5 @@ extern "C" int emu_raycast_bodies(const lsim_raycast_bodies_t* rbp, float* bodie
     }
     return LSIM_OK;
 }
+
+extern "C" int emu_raycast_bodies(const lsim_raycast_bodies_t* rb, void* /*stream*/) { return emu_raycast_bodies_poses(rb, nullptr); }

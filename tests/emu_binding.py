@@ -1,4 +1,6 @@
-"""TEST INFRASTRUCTURE -- builds and binds tests/emu (CPU lane emulator of the HIP kernel sources)."""
+"""TEST INFRASTRUCTURE -- builds and binds the CPU shims of tests/emu (the kernel sources compiled by g++ under LS_EMU): the lane emulator of
+kernels A / B (emu_lsim.cpp) and the shims of the single launches (emu_eval.cpp, emu_raycast.cpp, emu_raycast_bodies.cpp).  A shim exports
+emu_<name> with the signature include/lsim.h declares for lsim_<name>, so abi.bind types it from the header."""
 import ctypes
 import os
 import subprocess
@@ -7,28 +9,64 @@ import numpy as np
 
 from helpers import ROOT, abi
 
-SRC = os.path.join(ROOT, "tests", "emu", "emu_lsim.cpp")
-OUT = os.path.join(ROOT, "tests", "_build", "liblsim_emu.so")
+CSRC = os.path.join(ROOT, "isaacgymloco_amd", "csrc")
 _NP = {abi.DT_F32: np.float32, abi.DT_I64: np.int64, abi.DT_U8: np.uint8, abi.DT_I32: np.int32, abi.DT_I16: np.int16}
-_lib = None
+_shims = {}
 
 
-def build():
-    csrc = os.path.join(ROOT, "isaacgymloco_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")] + \
-           [os.path.join(ROOT, "include", f) for f in ("lsim.h", "lsim_layout.h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", OUT, SRC])
-    return OUT
+def build_shim(src, out, deps, defines=()):
+    """g++ `src` into the shared library `out` unless it is newer than `src`, `deps` and include/lsim.h"""
+    deps = [src, os.path.join(ROOT, "include", "lsim.h")] + list(deps)
+    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas"] +
+                              ["-D" + d for d in defines] + ["-o", out, src])
+    return out
+
+
+def load_shim(what, headers, counters=False):
+    """tests/emu/emu_<what>.cpp (depends on csrc/`headers`) built and bound, cached: every emu_<name> it exports for a declared lsim_<name>
+    is typed from the header.  `counters`: the -DLS_RAYCAST_COUNTERS variant, a library of its own"""
+    if (what, counters) not in _shims:
+        out = os.path.join(ROOT, "tests", "_build", f"lib{what}_emu{'_counters' if counters else ''}.so")
+        L = ctypes.CDLL(build_shim(os.path.join(ROOT, "tests", "emu", f"emu_{what}.cpp"), out, [os.path.join(CSRC, h) for h in headers],
+                                   ("LS_RAYCAST_COUNTERS",) if counters else ()))
+        _shims[what, counters] = abi.bind(L, "emu", [n for n in abi.PROTOTYPES if hasattr(L, "emu" + n[len("lsim"):])])
+        if hasattr(L, "emu_sizeof_config"):
+            abi.check_abi(L, prefix="emu")
+    return _shims[what, counters]
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = ctypes.CDLL(build())
-        abi.check_abi(_lib, prefix="emu")
-    return _lib
+    return load_shim("lsim", [f for f in os.listdir(CSRC) if f.endswith(".h")] + ["../../include/lsim_layout.h"])
+
+
+def aligned(shape, dtype, align=64):
+    """zeroed numpy array whose data pointer is `align`-byte aligned"""
+    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+    raw = np.zeros(n + align, np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off:off + n].view(dtype).reshape(shape)
+
+
+class EmuApi:
+    """lsim_<name> for every declared entry point that one of the shim libraries `libs` exports as emu_<name>, with the library's
+    signatures (streams ignored): what LeggedRobot, learn.evaluate.Evaluator(api=...) and envs.sensors.RaySensor(api=...) call.
+    `.calls[name]` counts the calls of each name in `count`"""
+
+    def __init__(self, *libs, count=()):
+        self.calls = {name: 0 for name in count}
+        for L in libs:
+            for name in abi.PROTOTYPES:
+                fn = getattr(L, "emu" + name[len("lsim"):], None)
+                if fn is not None:
+                    setattr(self, name, self._counted(name, fn) if name in self.calls else fn)
+
+    def _counted(self, name, fn):
+        def call(*a):
+            self.calls[name] += 1
+            return fn(*a)
+        return call
 
 
 class EmuSim:

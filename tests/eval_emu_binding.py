@@ -1,16 +1,12 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_eval.cpp (the CPU shim of the evaluator launch, isaacgymloco_amd/csrc/ls_eval.h compiled
 by g++ under LS_EMU) and helps to fill an lsim_eval from numpy arrays."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from helpers import ROOT, abi
-
-SRC = os.path.join(ROOT, "tests", "emu", "emu_eval.cpp")
-OUT = os.path.join(ROOT, "tests", "_build", "libeval_emu.so")
-_lib = None
+import emu_binding
+from emu_binding import aligned
+from helpers import abi
 
 # lsim_eval field -> (dtype, per-env shape) of the simulator buffers and per-env constants
 FIELDS = {"rew": (np.float32, ()), "reset_buf": (np.uint8, ()), "time_out_buf": (np.uint8, ()), "commands": (np.float32, (4,)),
@@ -20,44 +16,15 @@ FIELDS = {"rew": (np.float32, ()), "reset_buf": (np.uint8, ()), "time_out_buf": 
           "robot_ids": (np.uint8, ()), "torque_limits": (np.float32, (12,)), "default_dof_pos": (np.float32, (12,)), "action_scale": (np.float32, (12,))}
 
 
-def build():
-    deps = [SRC, os.path.join(ROOT, "isaacgymloco_amd", "csrc", "ls_eval.h"), os.path.join(ROOT, "include", "lsim.h")]
-    if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
-        os.makedirs(os.path.dirname(OUT), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", OUT, SRC])
-    return OUT
-
-
 def lib():
-    global _lib
-    if _lib is None:
-        _lib = ctypes.CDLL(build())
-        sz = ctypes.POINTER(ctypes.c_size_t)
-        _lib.emu_eval_sizes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, sz, sz, sz]
-        _lib.emu_eval_clear.argtypes = [ctypes.POINTER(abi.LsimEval)]
-        _lib.emu_eval_accumulate.argtypes = [ctypes.POINTER(abi.LsimEval), ctypes.c_void_p]
-    return _lib
+    L = emu_binding.load_shim("eval", ["ls_eval.h"])
+    L.emu_eval_accumulate_ordered.argtypes = [ctypes.POINTER(abi.LsimEval), ctypes.c_void_p]       # test-only: the env order permutation
+    return L
 
 
-def aligned(shape, dtype, align=64):
-    """zeroed numpy array whose data pointer is `align`-byte aligned"""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    raw = np.zeros(n + align, np.uint8)
-    off = (-raw.ctypes.data) % align
-    return raw[off:off + n].view(dtype).reshape(shape)
-
-
-class EmuApi:
-    """lsim_eval_sizes / _clear / _accumulate with the library's signatures (stream ignored), for learn.evaluate.Evaluator(api=...)"""
-
-    def lsim_eval_sizes(self, *a):
-        return lib().emu_eval_sizes(*a)
-
-    def lsim_eval_clear(self, e, stream):
-        return lib().emu_eval_clear(e)
-
-    def lsim_eval_accumulate(self, e, stream):
-        return lib().emu_eval_accumulate(e, None)
+def EmuApi():
+    """lsim_eval_sizes / _clear / _accumulate of the shim, for learn.evaluate.Evaluator(api=...)"""
+    return emu_binding.EmuApi(lib())
 
 
 class EmuEval:
@@ -88,29 +55,15 @@ class EmuEval:
         for k, i in enumerate(trace_envs):
             e.trace_envs[k] = i
         self.e = e
-        assert L.emu_eval_clear(ctypes.byref(e)) == 0
+        assert L.emu_eval_clear(ctypes.byref(e), None) == 0
 
     def accumulate(self, order=None):
         o = None if order is None else np.ascontiguousarray(order, np.int32)
-        rc = lib().emu_eval_accumulate(ctypes.byref(self.e), None if o is None else o.ctypes.data)
+        rc = lib().emu_eval_accumulate_ordered(ctypes.byref(self.e), None if o is None else o.ctypes.data)
         assert rc == 0, rc
 
 
 def emu_mixed_env(cfg, seed=3):
-    """the product's LeggedRobot surface over the lane emulator of kernels A / B (tests/emu_env.py), with the mixed-robot constructor bound"""
-    import emu_binding
-    from emu_env import EmuLeggedRobot, _EmuApi
-
-    class Api(_EmuApi):
-        def __init__(self):
-            super().__init__()
-            vp = ctypes.c_void_p
-            fn = emu_binding.lib().emu_create_mixed
-            fn.argtypes = [ctypes.POINTER(abi.LsimConfig), ctypes.POINTER(abi.LsimRobotModel), ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, ctypes.POINTER(vp)]
-            self.lsim_create_mixed = fn
-
-    class Env(EmuLeggedRobot):
-        def _load_library(self):
-            return Api()
-
-    return Env(cfg, seed=seed)
+    """the product's LeggedRobot surface over the lane emulator of kernels A / B (tests/emu_env.py)"""
+    from emu_env import EmuLeggedRobot
+    return EmuLeggedRobot(cfg, seed=seed)

@@ -1,54 +1,23 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_raycast_bodies.cpp (the CPU shim of the body-aware range-sensor launch,
 isaacgymloco_amd/csrc/ls_raycast_bodies.h compiled by g++ under LS_EMU) and fills an lsim_raycast_bodies from numpy arrays."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
+import emu_binding
 import raycast_emu_binding as EMU
-from helpers import ROOT, abi
-
-SRC = os.path.join(ROOT, "tests", "emu", "emu_raycast_bodies.cpp")
-_libs = {}
-
-
-def build(counters=False):
-    out = os.path.join(ROOT, "tests", "_build", "libraycast_bodies_emu_counters.so" if counters else "libraycast_bodies_emu.so")
-    deps = [SRC, os.path.join(ROOT, "include", "lsim.h")] + [os.path.join(ROOT, "isaacgymloco_amd", "csrc", f) for f in ("ls_raycast.h", "ls_raycast_bodies.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas"] +
-                              (["-DLS_RAYCAST_COUNTERS"] if counters else []) + ["-o", out, SRC])
-    return out
+from helpers import abi
 
 
 def lib(counters=False):
-    if counters not in _libs:
-        L = ctypes.CDLL(build(counters))
-        sz = ctypes.POINTER(ctypes.c_size_t)
-        L.emu_raycast_bodies_sizes.argtypes = [sz, sz]
-        L.emu_raycast_bodies.argtypes = [ctypes.POINTER(abi.LsimRaycastBodies), ctypes.c_void_p]
-        _libs[counters] = L
-    return _libs[counters]
+    L = emu_binding.load_shim("raycast_bodies", ["ls_raycast.h", "ls_raycast_bodies.h"], counters)
+    L.emu_raycast_bodies_poses.argtypes = [ctypes.POINTER(abi.LsimRaycastBodies), ctypes.c_void_p]       # test-only: the body pose output
+    return L
 
 
-class EmuApi(EMU.EmuApi):
-    """the four range-sensor entry points with the library's signatures (stream ignored), for envs.sensors.RaySensor(api=...); counts the calls"""
-
-    def __init__(self):
-        self.calls = {"lsim_raycast": 0, "lsim_raycast_bodies": 0}
-
-    def lsim_raycast(self, rc, stream):
-        self.calls["lsim_raycast"] += 1
-        return super().lsim_raycast(rc, stream)
-
-    def lsim_raycast_bodies_sizes(self, sb, rb):
-        return lib().emu_raycast_bodies_sizes(sb, rb)
-
-    def lsim_raycast_bodies(self, rb, stream):
-        self.calls["lsim_raycast_bodies"] += 1
-        return lib().emu_raycast_bodies(rb, None)
+def EmuApi():
+    """the four range-sensor entry points of the two shims, for envs.sensors.RaySensor(api=...); counts the launches"""
+    return emu_binding.EmuApi(EMU.lib(), lib(), count=("lsim_raycast", "lsim_raycast_bodies"))
 
 
 def fill(scene, tables, env_robot, root_states, dof_pos, mount, dirs, near, far, scale=None, env_stride=1, body_mask=0x1FFFF, flags=0, labels=True,
@@ -78,7 +47,7 @@ def cast(scene, tables, env_robot, root_states, dof_pos, mount, dirs, near, far,
     """run the emulated launch: (out [N, R], labels [N, R], state [4], body poses [N, 17, 8])"""
     rb, a = fill(scene, tables, env_robot, root_states, dof_pos, mount, dirs, near, far, **kw)
     bodies = np.full((root_states.shape[0], 17, 8), np.nan, np.float32)
-    rv = lib(counters).emu_raycast_bodies(ctypes.byref(rb), bodies.ctypes.data)
+    rv = lib(counters).emu_raycast_bodies_poses(ctypes.byref(rb), bodies.ctypes.data)
     assert rv == 0, rv
     R = dirs.shape[0]
     return a["out"][:, :R].copy(), a["labels"][:, :R].copy(), a["state"].copy(), bodies

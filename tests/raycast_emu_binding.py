@@ -1,52 +1,21 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_raycast.cpp (the CPU shim of the range-sensor launch, isaacgymloco_amd/csrc/ls_raycast.h
 compiled by g++ under LS_EMU) and fills an lsim_raycast from numpy arrays."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 
-from helpers import ROOT, abi
-
-SRC = os.path.join(ROOT, "tests", "emu", "emu_raycast.cpp")
-_libs = {}
-
-
-def build(counters=False):
-    out = os.path.join(ROOT, "tests", "_build", "libraycast_emu_counters.so" if counters else "libraycast_emu.so")
-    deps = [SRC, os.path.join(ROOT, "isaacgymloco_amd", "csrc", "ls_raycast.h"), os.path.join(ROOT, "include", "lsim.h")]
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas"] +
-                              (["-DLS_RAYCAST_COUNTERS"] if counters else []) + ["-o", out, SRC])
-    return out
+import emu_binding
+from emu_binding import aligned
+from helpers import abi
 
 
 def lib(counters=False):
-    if counters not in _libs:
-        L = ctypes.CDLL(build(counters))
-        L.emu_raycast_sizes.argtypes = [ctypes.POINTER(ctypes.c_size_t)]
-        L.emu_raycast.argtypes = [ctypes.POINTER(abi.LsimRaycast)]
-        _libs[counters] = L
-    return _libs[counters]
+    return emu_binding.load_shim("raycast", ["ls_raycast.h"], counters)
 
 
-def aligned(shape, dtype, align=64):
-    """zeroed numpy array whose data pointer is `align`-byte aligned"""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    raw = np.zeros(n + align, np.uint8)
-    off = (-raw.ctypes.data) % align
-    return raw[off:off + n].view(dtype).reshape(shape)
-
-
-class EmuApi:
-    """lsim_raycast_sizes / lsim_raycast with the library's signatures (stream ignored), for envs.sensors.RaySensor(api=...)"""
-
-    def lsim_raycast_sizes(self, sb):
-        return lib().emu_raycast_sizes(sb)
-
-    def lsim_raycast(self, rc, stream):
-        return lib().emu_raycast(rc)
+def EmuApi():
+    """lsim_raycast_sizes / lsim_raycast of the shim, for envs.sensors.RaySensor(api=...)"""
+    return emu_binding.EmuApi(lib())
 
 
 def fill(scene, root_states, mount, dirs, near, far, scale=None, env_stride=1, out_fill=np.nan):
@@ -80,6 +49,6 @@ def fill(scene, root_states, mount, dirs, near, far, scale=None, env_stride=1, o
 def cast(scene, root_states, mount, dirs, near, far, scale=None, env_stride=1, counters=False):
     """run the emulated launch: (out [N,R], state [4])"""
     rc, a = fill(scene, root_states, mount, dirs, near, far, scale, env_stride)
-    rv = lib(counters).emu_raycast(ctypes.byref(rc))
+    rv = lib(counters).emu_raycast(ctypes.byref(rc), None)
     assert rv == 0, rv
     return a["out"][:, :dirs.shape[0]].copy(), a["state"].copy()

@@ -22,11 +22,77 @@ def test_library_exports_every_declared_symbol():
     for fn in abi.declared_functions():
         assert hasattr(L, fn), f"liblsim.so does not export {fn}"
     abi.check_abi(L, "lsim")
-    L.lsim_reward_name.restype = ctypes.c_char_p
-    L.lsim_buffer_name.restype = ctypes.c_char_p
+    abi.bind(L, names=("lsim_reward_name", "lsim_buffer_name"))
     assert [L.lsim_reward_name(i).decode() for i in range(abi.NUM_REWARD_TERMS)] == abi.REWARD_NAMES
     names = sorted(abi.BUFFER_IDS, key=abi.BUFFER_IDS.get)
     assert [L.lsim_buffer_name(i).decode() for i in range(abi.NUM_BUFFERS)] == names
+
+
+def test_every_declared_function_has_a_prototype_of_the_headers_arity():
+    import re
+    text = re.sub(r"^\s*#.*$", "", abi._strip_comments(open(abi.HEADER_PATH).read()), flags=re.M)
+    assert len(abi.declared_functions()) >= 72 and set(abi.declared_functions()) == set(abi.PROTOTYPES)
+    for name in abi.declared_functions():
+        params, = re.findall(r"\b%s\s*\(([^()]*)\)\s*;" % name, text)
+        want = 0 if params.strip() in ("", "void") else params.count(",") + 1
+        assert len(abi.PROTOTYPES[name][1]) == want, name
+
+
+def test_prototypes_follow_the_mapping_rules():
+    """one literal signature per rule: scalars by width, lsim_handle and plain pointers as void*, struct pointers typed, the three return types"""
+    c = ctypes
+    vp, i64, P = c.c_void_p, c.c_int64, abi.PROTOTYPES
+    assert P["lsim_step_ex"] == (c.c_int, [vp, vp, c.c_uint32, vp])
+    assert P["lsim_amp_pair_rows"] == (c.c_int, [vp, i64, vp, i64, vp, vp, c.c_double, c.c_double, i64, c.c_int, vp, i64, vp])
+    assert P["lsim_linear_wgrad_workspace"] == (c.c_int, [c.c_long, c.c_int, c.c_int, vp, vp])
+    assert P["lsim_raycast_bodies"] == (c.c_int, [c.POINTER(abi.LsimRaycastBodies), vp])
+    assert P["lsim_create_mixed"] == (c.c_int, [c.POINTER(abi.LsimConfig), c.POINTER(abi.LsimRobotModel), c.c_int32, vp, vp, vp, vp, c.c_int, vp])
+    assert P["lsim_get_buffer"] == (c.c_int, [vp, c.c_int, vp, vp, vp, vp])                       # void**, int64_t [4]
+    assert P["lsim_adam_clip_step"][1][:4] == [c.c_int, vp, vp, vp] and P["lsim_adam_clip_step"][1][-2] is c.c_size_t      # float* const*
+    assert P["lsim_rollout_gae"][1][2:4] == [c.c_float, c.c_float]
+    assert P["lsim_destroy"] == (None, [vp])
+    assert P["lsim_last_error"] == (c.c_char_p, [vp])
+    assert P["lsim_reward_name"] == (c.c_char_p, [c.c_int])
+    assert P["lsim_sizeof_config"] == (c.c_int, [])
+
+
+def test_loaded_library_has_every_prototype_set():
+    from isaacgymloco_amd import lib
+    L = lib.load()
+    for name in abi.declared_functions():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and (fn.restype, list(fn.argtypes)) == abi.PROTOTYPES[name], name
+
+
+def test_bind_names_the_missing_symbols():
+    class Partial:
+        def lsim_step(self):
+            pass
+    with pytest.raises(RuntimeError, match=r"lsim_destroy.*lsim_raycast_bodies|lsim_raycast_bodies.*lsim_destroy"):
+        abi.bind(Partial(), names=("lsim_step", "lsim_raycast_bodies", "lsim_destroy"))
+    with pytest.raises(RuntimeError, match="emu_raycast"):
+        abi.bind(Partial(), prefix="emu", names=("lsim_raycast",))
+
+
+def test_library_without_a_declared_symbol_is_refused_at_load(tmp_path):
+    import subprocess
+    from isaacgymloco_amd import lib
+    src, out = os.path.join(tmp_path, "old.c"), os.path.join(tmp_path, "libold.so")
+    with open(src, "w") as f:
+        f.write("int lsim_sizeof_config(void) { return %d; }\nint lsim_sizeof_model(void) { return %d; }\nint lsim_abi_version(void) { return %d; }\n"
+                % (ctypes.sizeof(abi.LsimConfig), ctypes.sizeof(abi.LsimRobotModel), abi.ABI_VERSION))
+    subprocess.check_call(["gcc", "-shared", "-fPIC", "-o", out, src])
+    with pytest.raises(lib.LsimError, match="lsim_raycast_bodies"):
+        lib.load_path(out)
+
+
+@pytest.mark.parametrize("decl", ["int lsim_new(unsigned int flags);", "int lsim_new(lsim_config cfg);", "int lsim_new(struct foo* p);",
+                                  "float lsim_new(int a);", "int lsim_new(int (*callback)(int));"])
+def test_unknown_type_spelling_in_a_declaration_raises(decl):
+    assert abi.parse_prototypes("int lsim_ok(const lsim_config* cfg, size_t* n);", abi.STRUCTS) == \
+        {"lsim_ok": (ctypes.c_int, [ctypes.POINTER(abi.LsimConfig), ctypes.c_void_p])}
+    with pytest.raises(ValueError, match="lsim_new"):
+        abi.parse_prototypes("int lsim_ok(void);\n" + decl, abi.STRUCTS)
 
 
 def test_integration_document_names_every_entry_point():

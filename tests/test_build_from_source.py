@@ -19,7 +19,6 @@ def test_from_source_compile_exports_the_abi(tmp_path):
     missing = [f for f in abi.declared_functions() if not hasattr(L, f)]
     assert not missing, missing
     abi.check_abi(L, prefix="lsim")
-    L.lsim_abi_version.restype = ctypes.c_int
     assert L.lsim_abi_version() == abi.ABI_VERSION
 
 

@@ -7,26 +7,12 @@ import pytest
 import torch
 
 import emu_binding
-from emu_env import EmuLeggedRobot, _EmuApi
+from emu_env import EmuLeggedRobot as EmuMixedRobot
 from helpers import C, LC, T, abi
 from isaacgymloco_amd.robots.model import build_robot_model
 from mixed_robots_common import MIXES, mixed_and_single_cfgs, run_lockstep, assert_rows_equal
 
 E_INVALID = abi.DEFINES["LSIM_E_INVALID"]
-
-
-class _EmuMixedApi(_EmuApi):
-    def __init__(self):
-        super().__init__()
-        vp = ctypes.c_void_p
-        fn = emu_binding.lib().emu_create_mixed
-        fn.argtypes = [ctypes.POINTER(abi.LsimConfig), ctypes.POINTER(abi.LsimRobotModel), ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, ctypes.POINTER(vp)]
-        self.lsim_create_mixed = fn
-
-
-class EmuMixedRobot(EmuLeggedRobot):
-    def _load_library(self):
-        return _EmuMixedApi()
 
 
 def _make(cfg, seed):
@@ -112,7 +98,7 @@ def _two_robot_args(n=8, mutate=None, env_robot=None, num_robots=2):
 
 
 def _create_mixed(cfgs, mods, num_robots, er, grid, orig):
-    L = _EmuMixedApi()
+    L = emu_binding.EmuApi(emu_binding.lib())
     h = ctypes.c_void_p()
     rc = L.lsim_create_mixed(cfgs, mods, num_robots, er.ctypes.data, grid.ctypes.data, orig.ctypes.data, None, 0, ctypes.byref(h))
     if rc == 0:

@@ -135,10 +135,10 @@ def test_every_invalid_argument_is_refused():
     def rv(edit):
         rc, keep = EMU.fill(sc, rs, mt, dirs, S.NEAR, S.FAR, scale=scale)
         edit(rc)
-        return L.emu_raycast(ctypes.byref(rc))
+        return L.emu_raycast(ctypes.byref(rc), None)
 
     assert rv(lambda rc: None) == 0
-    assert L.emu_raycast(None) == abi.E_INVALID
+    assert L.emu_raycast(None, None) == abi.E_INVALID
     assert L.emu_raycast_sizes(None) == abi.E_INVALID
     nbytes = ctypes.c_size_t()
     assert L.emu_raycast_sizes(ctypes.byref(nbytes)) == 0 and nbytes.value == 8 * abi.DEFINES["LSIM_RAYCAST_STATE_WORDS"]
@@ -165,7 +165,7 @@ def test_every_invalid_argument_is_refused():
     assert abi.DEFINES["LSIM_RAYCAST_MAX_RAYS"] >= 64 * 48
     # a plane needs no mesh and no grid
     rc, keep = EMU.fill(REF.plane_scene(), rs, mt, dirs, S.NEAR, S.FAR)
-    assert L.emu_raycast(ctypes.byref(rc)) == 0
+    assert L.emu_raycast(ctypes.byref(rc), None) == 0
 
 
 # ---- envs/sensors.py

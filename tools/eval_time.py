@@ -74,8 +74,6 @@ def measure(n, terrain, iters, warmup):
     L = env._L
     out = {"num_envs": n, "terrain": terrain, "groups": ev.num_groups}
     out["step_us"] = timed(step, iters, warmup)
-    L.lsim_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.lsim_read_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
     L.lsim_set_profiling(env._h, iters)
     timed(step_eval, iters, 0)
     ms_a, ms_b, cnt = (ctypes.c_float * iters)(), (ctypes.c_float * iters)(), ctypes.c_int(iters)

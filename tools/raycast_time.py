@@ -74,8 +74,6 @@ def measure(n, terrain, iters, warmup, count_lib, bodies=False):
     env.reset()
     zero = torch.zeros(n, 12, device="cuda:0")
     L = env._L
-    L.lsim_set_profiling.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    L.lsim_read_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
     steps = 20
     L.lsim_set_profiling(env._h, steps)
     for _ in range(steps):
