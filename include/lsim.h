@@ -40,7 +40,8 @@ extern "C" {
                                  7: lsim_eval + lsim_eval_sizes / lsim_eval_clear / lsim_eval_accumulate (device-side policy evaluation: grouped metrics and state traces); no earlier struct or entry changed;
                                     also under 7, as pure additions (no earlier struct or entry changed, so a caller built against the first
                                     version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh);
-                                    lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot) */
+                                    lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot);
+                                    lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -155,8 +156,10 @@ enum lsim_rng_tag {
                                   15 payload, 16..18 com, 19 friction bucket id, 20 terrain level;
                                   step word = 0xFFFFFFFF                                    */
     LSIM_RNG_INIT_BUCKET = 13, /* LR:511            env word = bucket index, idx 0         */
-    LSIM_RNG_POLICY = 14       /* HIMP:94 (actor_critic.act sample), lsim_rollout_act: step word = draw counter,
+    LSIM_RNG_POLICY = 14,      /* HIMP:94 (actor_critic.act sample), lsim_rollout_act: step word = draw counter,
                                   block p gives the two Box-Muller pairs of actions 2p, 2p+1       */
+    LSIM_RNG_SENSOR = 15       /* lsim_sensor_capture (no reference site): step word = (uint32) tick, the fourth counter word =
+                                  (stream_id << 16) | ray -- one whole block per ray, all four words used      */
 };
 
 /* ---- robot model: the URDF after Isaac Gym's fixed-joint collapse ----
@@ -1059,6 +1062,61 @@ int lsim_raycast_bodies_sizes(size_t* state_bytes, size_t* robot_bytes);
  * 0..11) or whose joint_pos / joint_axis is not finite; a primitive with kind outside 0..3, body outside 0..16, a non-finite pos or quat, or a
  * size entry it uses (sphere 1, box 3, capsule / cylinder 2) that is not finite and > 0. */
 int lsim_raycast_bodies(const lsim_raycast_bodies_t* rb, void* stream);
+
+/* ---- sensor model: a range sensor as a real instrument -- an update period, latency, a short history of frames, noise, dropout, clipping.
+ * ONE launch, same rules as lsim_raycast_bodies (caller's stream, no host synchronisation, read-only on the simulator's buffers).  The launch
+ * renders only the envs that are DUE, runs each of their rays through the model and maintains hist, a per-env ring of the last K captures.
+ *
+ * Rays.  `rb` is read exactly as lsim_raycast_bodies reads it, and `raw`, the value of ray r of env e, is the value lsim_raycast_bodies writes
+ *   to out[e][r], bit for bit, with its label.  TERRAIN-ONLY FORM: rb.robots == NULL with rb.num_robots == 0 and rb.flags == 0 -- then dof_state,
+ *   env_robot, robots_host and body_mask are not read, raw is the value lsim_raycast(&rb.rc) writes, bit for bit, and a label (labels may still
+ *   be given) is 1 for t < far and 0 otherwise.
+ * Which envs.  Env e is visited when e % rb.rc.env_stride == 0, as before.  For a visited env
+ *     fill = (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0          (the env was reset since its last step: LSIM_BUF_EPISODE_LENGTH)
+ *     due  = fill || ( !(flags & LSIM_SENSOR_RESETS_ONLY) && (tick + (stagger ? e : 0)) % period == 0 )
+ *   For an env that is NOT due NOTHING is written: not its row of rb.rc.out, not its labels, not its rows of hist.  (state[0] counts only rays
+ *   of due envs.)  stagger spreads the captures over the period, 1 env in `period` per launch; without it all envs capture on the same ticks.
+ * Per ray r of a due env, all arithmetic in fp32 (a compiler may contract a product and a sum into one fused operation):
+ *     rb.rc.out[e][r] = raw, the label as before: `out` stays the CLEAN value (a privileged target);
+ *     hit = (t < far) for the unscaled t of the ray: a miss, and a non-finite ray (counted in state[0], as before), carries no noise and is never dropped;
+ *     x0..x3 = Philox4x32-10, key (seed, rank), counter (e, (uint32_t)tick, LSIM_RNG_SENSOR, (stream_id << 16) | r);   u_k = (x_k >> 8) * 2^-24;
+ *     g = 2 * ((u0 + u1 + u2) - 1.5f), summed left to right: a bounded three-uniform stand-in for a unit normal -- mean 0, variance exactly 1,
+ *         |g| <= 3, no transcendental function, so the same bits on every host;
+ *     v = hit ? raw + (sigma0 + sigma2 * raw * raw) * g : raw          (noise that grows with the square of the depth, as a stereo camera's)
+ *     if (hit && u3 < p_drop) v = drop_value                            (a hole)
+ *     v = min(max(v, clip_lo), clip_hi);      y = (v - offset) * gain
+ *   and the history, K = latency + frames slots per env, oldest first:
+ *     fill:       hist[e][k][r] = y for every k < K                    (an episode never starts with frames of the previous one)
+ *     otherwise:  hist[e][k][r] = hist[e][k + 1][r] for k = 0 .. K - 2 in this order, then hist[e][K - 1][r] = y.
+ *   hist[e][0 .. frames) is what a policy reads: `frames` consecutive captures, oldest first, the newest of them (slot frames - 1) `latency`
+ *   captures old; slots frames .. K - 1 are the captures still on their way.  Age is counted in captures of the env, not in ticks.
+ * tick is passed BY VALUE, as the simulator's step word is: a launch replayed from a captured graph repeats its due set and its draws.  A caller
+ *   that captures the launch captures one graph per tick of a period, or launches the sensor outside the graph. */
+#define LSIM_SENSOR_MAX_HISTORY 8
+#define LSIM_SENSOR_FILL_ALL 1u            /* flags: every visited env is due and its whole history is filled */
+#define LSIM_SENSOR_RESETS_ONLY 2u         /* flags: only envs with episode_length == 0 are due (a by-hand reset between two steps) */
+typedef struct lsim_sensor_model {
+    lsim_raycast_bodies_t rb;         /* as for lsim_raycast_bodies; rb.robots == NULL with num_robots == 0 and rb.flags == 0: terrain only */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    float* hist;                      /* [N, K, hist_stride], K = latency + frames, 16-byte aligned */
+    int64_t tick;                     /* >= 0: the caller's step counter, by value */
+    uint32_t seed, rank, stream_id;   /* Philox key; stream_id < 65536 separates the sensors of one env */
+    int32_t period, stagger;          /* period >= 1; stagger 0 / 1 */
+    int32_t latency, frames;          /* latency >= 0, frames >= 1, latency + frames <= LSIM_SENSOR_MAX_HISTORY */
+    int32_t hist_stride;              /* floats between slots of hist: >= R, a multiple of 4 */
+    float sigma0, sigma2;             /* finite, >= 0 */
+    float p_drop, drop_value;         /* 0 <= p_drop <= 1; drop_value finite */
+    float clip_lo, clip_hi;           /* finite, clip_lo <= clip_hi */
+    float offset, gain;               /* finite */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+} lsim_sensor_model_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch: sm == NULL; anything lsim_raycast_bodies refuses in sm->rb
+ * (terrain-only form: anything lsim_raycast refuses in sm->rb.rc, labels != NULL with label_stride < R; robots == NULL with num_robots != 0 or
+ * rb.flags != 0 is not that form and is refused); episode_length NULL or not 8-byte aligned; hist NULL or not 16-byte aligned; tick < 0;
+ * stream_id >= 65536; period < 1; stagger outside 0..1; latency < 0; frames < 1; latency + frames > LSIM_SENSOR_MAX_HISTORY; hist_stride < R or
+ * not a multiple of 4; sigma0, sigma2 not finite or < 0; p_drop outside [0, 1]; drop_value, clip_lo, clip_hi, offset or gain not finite;
+ * clip_lo > clip_hi; a flag bit other than the two above; both of them set. */
+int lsim_sensor_capture(const lsim_sensor_model_t* sm, void* stream);
 
 #ifdef __cplusplus
 }

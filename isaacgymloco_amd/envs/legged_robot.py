@@ -297,7 +297,7 @@ class LeggedRobot:
         else:
             lib.check(self._L.lsim_reset_envs(self._h, mask.data_ptr(), self._stream()), self._h, "lsim_reset_envs")
             self._reset_mask_ref = mask   # keep alive until the kernels ran
-        self._update_sensors()
+        self._update_sensors(abi.DEFINES["LSIM_SENSOR_RESETS_ONLY"])      # a modelled sensor captures only the envs just reset: the others are not due twice
         self._refresh_extras(force_valid=True)
 
     def reset(self):
@@ -323,15 +323,25 @@ class LeggedRobot:
     def add_sensor(self, name, sensor):
         """attach a range sensor (envs/sensors.py): from now on every step_device() / reset_idx() ends with the sensor's launch on the same
         stream, after the post-step reset, so `env.sensors[name].out` belongs to the observations of the same step.  Added before a
-        step_device() is captured into a graph, the launch is captured with it (raw pointers only, no host sync)."""
+        step_device() is captured into a graph, the launch is captured with it (raw pointers only, no host sync).
+        A sensor with a model (sensors.SensorModel) gets its index in `env.sensors` as stream_id and has every env's frame history filled once
+        here.  Its tick is `common_step_counter` BEFORE step_device() increments it: the first step after construction is tick 0, and a
+        reset_idx() by hand shares the tick of the step that follows it.  The tick goes into the launch by value, so a captured step_device()
+        replays one tick's due set and noise draws: launch a modelled sensor outside the graph, or capture one graph per tick of a period."""
         if name in self.sensors:
             raise ValueError(f"sensor {name!r} exists")
         self.sensors[name] = sensor
+        if getattr(sensor, "model", None) is not None:
+            sensor.stream_id = len(self.sensors) - 1
+            sensor.refresh(tick=self.common_step_counter)
         return sensor
 
-    def _update_sensors(self):
+    def _update_sensors(self, model_flags=0):
         for s in self.sensors.values():
-            s.update()
+            if getattr(s, "model", None) is None:
+                s.update()
+            else:
+                s.update(tick=self.common_step_counter, flags=model_flags)
 
     def step(self, actions):
         """LeggedRobot.step (LR:122-176): same 7-tuple (8 with terminal AMP states when using_amp)."""

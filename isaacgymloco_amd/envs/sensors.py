@@ -17,6 +17,15 @@ Frames: the sensor frame is the base frame moved by the mount -- x forward, y le
 base's position and yaw but not its roll and pitch (a gimbal, or with a mount behind and above the robot a chase camera: a third-person depth
 frame of the env's robot on its terrain, tools/sensor_frames.py).  A camera looks along its +x; image rows run top to bottom, columns left to
 right (row-major, r = row * width + col).
+
+Sensor model (`model=SensorModel(...)`, lsim_sensor_capture): the same launch renders only the envs that are due on the current tick (a
+10-30 Hz camera under a 50 Hz policy: `period`, spread over the period by `stagger`), and turns each clean depth into what an instrument
+reports -- depth-dependent noise, dropped pixels, clipping, normalisation -- kept as the env's last `frames` captures, `latency` captures
+late, refilled inside the launch when the env resets:
+
+    cam = depth_camera(env, 64, 48, 87, ..., model=SensorModel(period=5, stagger=True, latency=1, frames=2, noise=(0.01, 0.002), dropout=0.02, normalise=True))
+    env.add_sensor("depth", cam)            # fills every env's history once, then one launch per step_device()
+    obs = env.sensors["depth"].frame_images()    # [N, 2, 48, 64], oldest first, live; cam.image() stays the clean depth of the env's latest capture
 """
 import ctypes
 import math
@@ -55,17 +64,52 @@ def ring_dirs(channels, vfov_deg, points_per_rev):
     return v.reshape(-1, 3).astype(np.float32)
 
 
+class SensorModel:
+    """What lsim_sensor_capture adds to a ray cast (include/lsim.h states every formula).  `period`: an env captures on every period-th
+    tick; `stagger`: env e captures when (tick + e) % period == 0 instead of tick % period == 0, so that every launch renders 1 env in
+    `period`; `frames`: the captures a policy reads, oldest first; `latency`: how many captures old the newest of them is; `noise` =
+    (sigma0, sigma2): standard deviation sigma0 + sigma2 * depth^2 on a hit; `dropout`: probability that a hit reads `drop_value`; `clip` =
+    (lo, hi), None: the sensor's (near, far); `normalise`: (v - (lo + hi) / 2) / (hi - lo), in [-0.5, 0.5], instead of v.
+    An env that was reset (episode_length 0) captures at once and all its frames are that capture."""
+
+    def __init__(self, period=1, stagger=False, latency=0, frames=1, noise=(0.0, 0.0), dropout=0.0, drop_value=0.0, clip=None, normalise=False):
+        self.period, self.stagger, self.latency, self.frames = int(period), bool(stagger), int(latency), int(frames)
+        self.noise = (float(noise[0]), float(noise[1]))
+        self.dropout, self.drop_value = float(dropout), float(drop_value)
+        self.clip = None if clip is None else (float(clip[0]), float(clip[1]))
+        self.normalise = bool(normalise)
+        kmax = abi.DEFINES["LSIM_SENSOR_MAX_HISTORY"]
+        if self.period < 1 or self.latency < 0 or self.frames < 1 or self.latency + self.frames > kmax:
+            raise ValueError(f"SensorModel: period >= 1, latency >= 0, frames >= 1 and latency + frames <= {kmax}")
+        if min(self.noise) < 0.0 or not 0.0 <= self.dropout <= 1.0 or (self.clip is not None and not self.clip[0] <= self.clip[1]):
+            raise ValueError("SensorModel: noise >= 0, 0 <= dropout <= 1, clip[0] <= clip[1]")
+
+    def offset_gain(self, near, far):
+        """((lo, hi), offset, gain) for a sensor with this [near, far]"""
+        lo, hi = (near, far) if self.clip is None else self.clip
+        if not self.normalise:
+            return (lo, hi), 0.0, 1.0
+        if not hi > lo:
+            raise ValueError("SensorModel: normalise needs clip[0] < clip[1]")
+        return (lo, hi), (lo + hi) / 2.0, 1.0 / (hi - lo)
+
+
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
     rendered (the other rows of the output keep their initial value, `far`).  `update()` launches once and returns the live [N, R] tensor.
     `see_robot=True`: the env's own robot is seen too (lsim_raycast_bodies), except the bodies of `ignore_bodies` (names or indices);
     `labels=True` (needs see_robot): `labels()` is the live uint8 [N, R] tensor of what each ray met; `frame`: "base" or "yaw" (module docstring).
-    With the defaults nothing of this is allocated and the launch is lsim_raycast."""
+    With the defaults nothing of this is allocated and the launch is lsim_raycast.
+    `model` (a SensorModel): the launch is lsim_sensor_capture -- `update(tick=...)` renders the envs due on that tick, `frames()` is the live
+    [N, frames, R] history, `out` the clean value of each env's latest capture, `refresh()` fills every env's history from the present state,
+    `tick` the tick of the last launch and `stream_id` (set by env.add_sensor) what separates the noise of the sensors of one env.
+    With `model=None` nothing of this is allocated and the launch is the one above."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base"):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
         self.env = env
+        self.model = model
         self._api = api if api is not None else env._L
         if frame not in ("base", "yaw"):
             raise ValueError(f"frame: expected 'base' or 'yaw', got {frame!r}")
@@ -76,6 +120,8 @@ class RaySensor:
         need = "lsim_raycast_bodies" if self._bodies else "lsim_raycast"
         if not hasattr(self._api, need):
             raise lib.LsimError(f"the loaded library has no {need}: rebuild it (there is no torch fall-back for the range sensors)")
+        if model is not None and not hasattr(self._api, "lsim_sensor_capture"):
+            raise lib.LsimError("the loaded library has no lsim_sensor_capture: rebuild it (there is no torch fall-back for the sensor model)")
         dev = env.root_states.device
         N = int(env.num_envs)
         self.dirs = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device=dev).contiguous()
@@ -112,6 +158,38 @@ class RaySensor:
         self._labels = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
+        if model is not None:
+            self._setup_model(model, dev)
+
+    def _setup_model(self, model, dev):
+        """the lsim_sensor_model struct around the sensor's lsim_raycast_bodies (or, terrain only, around its lsim_raycast) and the history"""
+        env, N = self.env, int(self.env.num_envs)
+        sm = abi.LsimSensorModel()
+        if self._bodies:
+            sm.rb = self._rb
+        else:
+            sm.rb.rc = self._rc               # robots NULL, num_robots 0, flags 0: the terrain-only form
+        self._episode_length = env.episode_length_buf
+        sm.episode_length = self._episode_length.data_ptr()
+        K, stride = model.latency + model.frames, self._out.shape[1]
+        self._hist = torch.zeros((N, K, stride), dtype=torch.float32, device=dev)
+        sm.hist, sm.hist_stride = self._hist.data_ptr(), stride
+        sm.seed, sm.rank, sm.stream_id = int(env.lcfg.seed), int(env.lcfg.rank), 0
+        sm.period, sm.stagger, sm.latency, sm.frames = model.period, int(model.stagger), model.latency, model.frames
+        sm.sigma0, sm.sigma2 = model.noise
+        sm.p_drop, sm.drop_value = model.dropout, model.drop_value
+        (sm.clip_lo, sm.clip_hi), sm.offset, sm.gain = model.offset_gain(self.near, self.far)
+        self._sm = sm
+        self.tick = -1
+
+    @property
+    def stream_id(self):
+        return int(self._sm.stream_id) if self.model is not None else 0
+
+    @stream_id.setter
+    def stream_id(self, value):
+        if self.model is not None:
+            self._sm.stream_id = int(value)
 
     def _setup_bodies(self, rc, ignore_bodies, labels, dev):
         """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
@@ -184,13 +262,31 @@ class RaySensor:
             return stream
         return self.env._stream() if self._out.is_cuda else None
 
-    def update(self, stream=None):
-        """one launch on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor"""
+    def update(self, stream=None, tick=None, flags=0):
+        """one launch on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor.  With a model: the
+        envs due on `tick` (default: the env's common_step_counter), `flags` = 0 or one of LSIM_SENSOR_FILL_ALL / LSIM_SENSOR_RESETS_ONLY"""
+        if self.model is not None:
+            self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
+            self._sm.tick, self._sm.flags = self.tick, int(flags)
+            lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
+            return self.out
         if self._bodies:
             lib.check(self._api.lsim_raycast_bodies(ctypes.byref(self._rb), self._stream(stream)), what="lsim_raycast_bodies")
         else:
             lib.check(self._api.lsim_raycast(ctypes.byref(self._rc), self._stream(stream)), what="lsim_raycast")
         return self.out
+
+    def refresh(self, stream=None, tick=None):
+        """capture every env now and fill its whole history with that capture (a model only)"""
+        if self.model is None:
+            raise ValueError("the sensor was created without a model")
+        return self.update(stream, tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+
+    def frames(self):
+        """live [N, frames, R] view of the history: what the model reports, oldest first; the last one is `latency` captures old"""
+        if self.model is None:
+            raise ValueError("the sensor was created without a model")
+        return self._hist[:, :self.model.frames, :self.num_rays]
 
     def labels(self):
         """live uint8 [N, R] tensor of the latest launch (labels=True): 0 nothing within [near, far], 1 terrain, 2 + b body b (`body_names[b]`)"""
@@ -218,19 +314,23 @@ class DepthCamera(RaySensor):
         """[N, H, W] view of labels()"""
         return self.labels().unflatten(1, (self.height, self.width))
 
+    def frame_images(self):
+        """[N, frames, H, W] view of frames()"""
+        return self.frames().unflatten(2, (self.height, self.width))
+
 
 def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base"):
-    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last four keywords as RaySensor's"""
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last five keywords as RaySensor's"""
     return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api,
-                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame)
+                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model)
 
 
 def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
-          see_robot=False, ignore_bodies=(), labels=False, frame="base"):
+          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
     """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
-    `points_per_rev` azimuths each; reports range (scale=None); the last four keywords as RaySensor's"""
+    `points_per_rev` azimuths each; reports range (scale=None); the last five keywords as RaySensor's"""
     s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
-                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame)
+                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model)
     s.channels, s.points_per_rev = int(channels), int(points_per_rev)
     return s

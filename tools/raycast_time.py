@@ -11,6 +11,10 @@ vertical, far 10 m), each with rays/s; `kernel_a_us` = kernel A from the library
 `--bodies`: each sensor is also timed with see_robot=True (lsim_raycast_bodies, all bodies seen) in the same process, next to lsim_raycast and
 kernel A: `<sensor>_bodies_us`, its ratio to the terrain-only launch, the share of rays that end on a body, and from the counters build the
 primitives that passed the bounding test per ray and the cells walked per ray (the walk stops at the body hit).
+`--model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02` (implies --bodies): each see_robot sensor is also timed through
+lsim_sensor_capture with that sensors.SensorModel, the tick advancing by one per launch so that a staggered period is averaged over whole
+periods (`<sensor>_model_us`), and with SensorModel() -- period 1, everything else off: what the epilogue and the history traffic add to
+lsim_raycast_bodies (`<sensor>_model_period1_us`); both with their ratio to `<sensor>_bodies_us` of the same process.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -66,7 +70,33 @@ def counters_bodies(sensor, count_lib):
     return st[1] / rays, st[2] / rays, st[3] / rays
 
 
-def measure(n, terrain, iters, warmup, count_lib, bodies=False):
+def parse_model(text):
+    """sensors.SensorModel from key=value pairs: period, stagger, latency, frames, noise=sigma0:sigma2, dropout, drop_value, clip=lo:hi, normalise"""
+    kw = {}
+    for item in text.split(","):
+        k, v = item.split("=")
+        if k in ("noise", "clip"):
+            kw[k] = tuple(float(x) for x in v.split(":"))
+        elif k in ("dropout", "drop_value"):
+            kw[k] = float(v)
+        elif k in ("stagger", "normalise"):
+            kw[k] = bool(int(v))
+        else:
+            kw[k] = int(v)
+    return sensors.SensorModel(**kw)
+
+
+def timed_ticks(sensor, iters, warmup):
+    """`timed` over launches whose tick advances by one each"""
+    tick = [0]
+
+    def fn():
+        sensor.update(tick=tick[0])
+        tick[0] += 1
+    return timed(fn, iters, warmup)
+
+
+def measure(n, terrain, iters, warmup, count_lib, bodies=False, model=None):
     cfg = C.aliengo_cfg()
     cfg.env.num_envs = n
     cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
@@ -111,6 +141,20 @@ def measure(n, terrain, iters, warmup, count_lib, bodies=False):
                 prims, cells, tris = counters_bodies(s, count_lib)
                 out[name + "_bodies_prims_tested_per_ray"], out[name + "_bodies_cells_per_ray"], out[name + "_bodies_triangles_per_ray"] = prims, cells, tris
             out[name + "_bodies_nonfinite_rays"] = int(s.nonfinite_rays.item())
+    if model is not None:
+        for name, make in (("camera", lambda m: sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0,
+                                                                       see_robot=True, labels=True, model=m)),
+                           ("lidar", lambda m: sensors.lidar(env, 16, 30.0, 360, mount_pos=(0.0, 0.0, 0.15), near=0.05, far=10.0, see_robot=True, labels=True, model=m))):
+            for key, m in (("_model", model), ("_model_period1", sensors.SensorModel())):
+                s = make(m)
+                s.refresh(tick=0)
+                whole = max(m.period, iters // m.period * m.period)          # whole periods: every env captures equally often
+                us = timed_ticks(s, whole, warmup)
+                out[name + key + "_us"] = us
+                out[name + key + "_over_bodies"] = us / out[name + "_bodies_us"]
+                out[name + key + "_over_kernel_a"] = us / out["kernel_a_us"]
+                out[name + key + "_nonfinite_rays"] = int(s.nonfinite_rays.item())
+        out["resetting_envs"] = int((env.episode_length_buf == 0).sum().item())      # envs with episode_length 0 are due on every tick: must be 0 here
     out["torch_us"] = None
     return out
 
@@ -123,6 +167,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--no-counters", action="store_true")
     ap.add_argument("--bodies", action="store_true", help="also time lsim_raycast_bodies (see_robot=True) on every workload")
+    ap.add_argument("--model", default=None, help="also time lsim_sensor_capture with this sensor model, e.g. period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -134,9 +179,10 @@ def main():
             print(COUNT_LIB)
             return
         count_lib = lib.load_path(COUNT_LIB)
+    model = parse_model(a.model) if a.model else None
     res = {"tool": "raycast_time", "iters": a.iters, "warmup": a.warmup, "device": torch.cuda.get_device_name(0),
-           "camera": "64x48, hfov 87, pitch 30 down, far 5 m", "lidar": "16x360, vfov 30, far 10 m",
-           "cases": [measure(a.num_envs, t, a.iters, a.warmup, count_lib, a.bodies) for t in a.terrains.split(",")]}
+           "camera": "64x48, hfov 87, pitch 30 down, far 5 m", "lidar": "16x360, vfov 30, far 10 m", "model": a.model,
+           "cases": [measure(a.num_envs, t, a.iters, a.warmup, count_lib, a.bodies or model is not None, model) for t in a.terrains.split(",")]}
     line = json.dumps(res)
     if a.out:
         with open(a.out, "w") as f:
