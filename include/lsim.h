@@ -205,9 +205,9 @@ typedef struct lsim_config {
     uint32_t rank;            /* second Philox key word: one stream per data-parallel rank */
 
     /* control (LRC:117-127, AGC:94-100) */
-    float sim_dt;             /* 0.005, LRC:239 */
+    float sim_dt;             /* 0.005, LRC:239; > 0 (a divisor in the 'V' law), else LSIM_E_INVALID */
     int32_t decimation;       /* 4 */
-    int32_t control_type;     /* 0 'P', 1 'V', 2 'T' (LR:676-687) */
+    int32_t control_type;     /* 0 'P', 1 'V', 2 'T' (LR:676-687); anything else: LSIM_E_INVALID (the reference raises, LR:687) */
     float action_scale;
     float hip_reduction;
     float p_gains[LSIM_NUM_DOF];
@@ -226,8 +226,8 @@ typedef struct lsim_config {
     int32_t randomize_restitution; float restitution_range[2];
     int32_t randomize_payload_mass; float payload_mass_range[2];
     int32_t randomize_com_displacement; float com_displacement_range[2];
-    int32_t push_robots; int32_t push_interval; float max_push_vel_xy;        /* LR:627, LR:1263 */
-    int32_t disturbance; int32_t disturbance_interval; float disturbance_range[2]; /* LR:631 */
+    int32_t push_robots; int32_t push_interval; float max_push_vel_xy;        /* LR:627, LR:1263; interval > 0 when push_robots, else LSIM_E_INVALID */
+    int32_t disturbance; int32_t disturbance_interval; float disturbance_range[2]; /* LR:631; interval > 0 when disturbance, else LSIM_E_INVALID */
 
     /* reset (LR:690-820) */
     int32_t has_dof_init_pos_ratio; float dof_init_pos_ratio_range[2];
@@ -245,7 +245,8 @@ typedef struct lsim_config {
     float max_forward_curriculum, max_backward_curriculum, max_lat_curriculum;
 
     /* terrain (AGC:67-91) */
-    int32_t mesh_type;              /* 0 plane, 1 heightfield, 2 trimesh */
+    int32_t mesh_type;              /* 0 plane, 1 heightfield, 2 trimesh; anything else: LSIM_E_INVALID.  Plane: LSIM_BUF_ENV_ORIGINS starts at zero,
+                                       the grid of robots (LR:1243-1250) is left to the host (the product binding keeps every robot at the origin) */
     float horizontal_scale, vertical_scale, border_size;
     int32_t grid_rows, grid_cols;   /* tot_rows, tot_cols, TER:59-60 */
     int32_t terrain_num_rows, terrain_num_cols;  /* levels, types */
@@ -359,7 +360,7 @@ enum lsim_buffer_id {
     LSIM_BUF_TERM_PRIV_OBS,      /* f32 [N,238]   rows valid where reset_buf (LR:227) */
     LSIM_BUF_TERM_AMP_OBS,       /* f32 [N,30]    rows valid where reset_buf (LR:228) */
     LSIM_BUF_AMP_OBS,            /* f32 [N,30]    get_amp_observations() of the post-step state (LR:406-416) */
-    LSIM_BUF_DELAY_STEPS,        /* i32 [N]       last drawn action delay (LR:134) */
+    LSIM_BUF_DELAY_STEPS,        /* i32 [N]       action delay applied in the last step: the draw of LR:134, 0 with lsim_config.delay off (LR:135) */
     LSIM_BUF_CONTACT_COUNT,      /* i32 [N,2]     diagnostic: collision points within contact_offset of the terrain BEFORE the cap of
                                                   LSIM_MAX_CONTACTS -- [0] maximum over the sub-steps of this step, [1] last sub-step */
     LSIM_BUF_SUBSTEP_TORQUES,    /* f32 [N,decimation,12] diagnostic, written only under LSIM_STEP_RECORD_SUBSTEPS: the torques of EVERY sub-step

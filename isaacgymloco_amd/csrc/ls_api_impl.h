@@ -47,6 +47,9 @@ static int ls_check_cfg(const lsim_config* c) {
     if (c->solver_type == LSIM_SOLVER_TGS && (c->num_position_iterations < 1 || c->num_position_iterations > LSIM_MAX_POSITION_ITERATIONS)) return LSIM_E_INVALID;
     // (a direct C-ABI caller with a large value would get an unbounded per-sub-step loop in the limit pass)
     if (c->tgs_limit_passes < 0 || c->tgs_limit_passes > LSIM_MAX_POSITION_ITERATIONS || (c->lin_vel_at_com != 0 && c->lin_vel_at_com != 1)) return LSIM_E_INVALID;
+    // an unknown controller is an error (LR:687), not torque control; the intervals and sim_dt are divisors inside the kernel (negated comparison: NaN fails too)
+    if (c->control_type < 0 || c->control_type > 2 || c->mesh_type < 0 || c->mesh_type > 2 || !(c->sim_dt > 0.0f)) return LSIM_E_INVALID;
+    if ((c->push_robots && c->push_interval <= 0) || (c->disturbance && c->disturbance_interval <= 0)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
 

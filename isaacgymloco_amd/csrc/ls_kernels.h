@@ -201,6 +201,7 @@ LS_FN void ph_load_a(const LsCtx& cx, const LsRobot& rb, WaveShared& sh, LaneReg
     }
     if (lane == 15) {
         int delay = (int)(ls_draw(cx, env, (uint32_t)a.step_counter, LSIM_RNG_DELAY, 0) * (float)c.decimation);   // LR:134
+        if (!c.delay) delay = 0;                                                                                 // LR:135: drawn, not applied
         sh.delay = delay;
         sh.nact = 0; sh.nact_max = 0;
         LSB(cx, LSIM_BUF_DELAY_STEPS, int32_t)[env] = delay;

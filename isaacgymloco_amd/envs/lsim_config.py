@@ -41,6 +41,8 @@ def make_lsim_config(cfg, num_envs=None, terrain=None, model=None, seed=1, rank=
     dt = cfg.control.decimation * sim_dt                                 # LR:1253
     c.sim_dt = sim_dt
     c.decimation = int(cfg.control.decimation)
+    if cfg.control.control_type not in CONTROL_TYPES:                    # LR:687 raises on the first step; here at construction
+        raise ValueError(f"cfg.control.control_type must be one of {sorted(CONTROL_TYPES)}, got {cfg.control.control_type!r}")
     c.control_type = CONTROL_TYPES[cfg.control.control_type]
     c.action_scale = cfg.control.action_scale
     c.hip_reduction = cfg.control.hip_reduction

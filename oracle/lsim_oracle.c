@@ -744,6 +744,9 @@ static int check_cfg(const lsim_config* c) {
     if (c->solver_type != LSIM_SOLVER_PGS && c->solver_type != LSIM_SOLVER_TGS) return LSIM_E_INVALID;
     if (c->solver_type == LSIM_SOLVER_TGS && (c->num_position_iterations < 1 || c->num_position_iterations > LSIM_MAX_POSITION_ITERATIONS)) return LSIM_E_INVALID;
     if (c->tgs_limit_passes < 0 || c->tgs_limit_passes > LSIM_MAX_POSITION_ITERATIONS || (c->lin_vel_at_com != 0 && c->lin_vel_at_com != 1)) return LSIM_E_INVALID;
+    /* an unknown controller is an error (LR:687), not torque control; the intervals and sim_dt are divisors of the step (negated comparison: NaN fails too) */
+    if (c->control_type < 0 || c->control_type > 2 || c->mesh_type < 0 || c->mesh_type > 2 || !(c->sim_dt > 0.0f)) return LSIM_E_INVALID;
+    if ((c->push_robots && c->push_interval <= 0) || (c->disturbance && c->disturbance_interval <= 0)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
 
@@ -879,6 +882,7 @@ int orc_step_ex(orc_sim* s, const float* actions, uint32_t flags) {
         const float* last = ORC_F(s, LSIM_BUF_LAST_ACTIONS) + N_DOF * e;
         for (int j = 0; j < N_DOF; ++j) act[j] = clipf(actions[N_DOF * e + j], -c->clip_actions, c->clip_actions); /* LR:129-130 */
         int delay = (int)(u01(s, e, stepw, LSIM_RNG_DELAY, 0) * (float)c->decimation); /* LR:134 */
+        if (!c->delay) delay = 0;                                                      /* LR:135: drawn, not applied */
         ORC_I32(s, LSIM_BUF_DELAY_STEPS)[e] = delay;
         ORC_I32(s, LSIM_BUF_CONTACT_COUNT)[2 * e] = 0; ORC_I32(s, LSIM_BUF_CONTACT_COUNT)[2 * e + 1] = 0;
         const int at_com = c->lin_vel_at_com && !(flags & LSIM_STEP_SKIP_PHYSICS);

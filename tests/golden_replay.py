@@ -24,12 +24,73 @@ def _all_terms(cfg):
     cfg.rewards.only_positive_rewards = True
 
 
+def _stairs(cfg):    # only generators that exist in-tree (TER:229-294): stairs up / down
+    cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5, 0.0, 0.0, 0.0, 0.0]
+
+
+# ---- config branches no shipped task takes (tools/gen_golden.py runs the reference's own step() under the same tweak functions).
+# control_type V / T (LR:680-685).  Gains chosen so that the clip of LR:688 is exercised but does not hide the law; the conditions are
+# asserted on the reference's own outputs (tests/test_golden_branch_coverage.py).  Torque limits 44 / 44 / 55 N m.
+#   V: tau = kp (a_scaled - qd) - kd (qd - last_qd) / 0.005.  With the stock gains (kp 40, kd 2: 400 N m per rad/s of change over a step)
+#      every entry sits on a limit, and so do 8 in 10 at any kp >= 4, where a velocity loop on the light links is unstable at dt = 5 ms
+#      and the injected joint speeds stay pinned at the URDF speed limit (last_qd == qd: the kd term is dead).  kp 1, kd 0.02 (4 N m per rad/s of change),
+#      action_scale 10 (targets ~ N(0, 10) rad/s): about 8 entries in 10 inside the limits, the rest on them
+#   T: tau = a_scaled, actions ~ N(0, 1): action_scale 25 puts a few entries in 100 beyond 44 N m
+def _ctrl_v(cfg):
+    _flat(cfg)
+    cfg.control.control_type = "V"
+    cfg.control.stiffness = {"joint": 1.0}
+    cfg.control.damping = {"joint": 0.02}
+    cfg.control.action_scale = 10.0
+
+
+def _ctrl_t(cfg):
+    _flat(cfg)
+    cfg.control.control_type = "T"
+    cfg.control.action_scale = 25.0
+
+
+def _dr_off(cfg):
+    _flat(cfg)
+    for k in ("delay", "push_robots", "disturbance", "randomize_kp", "randomize_kd", "randomize_motor_strength", "randomize_friction", "randomize_dof_vel"):
+        setattr(cfg.domain_rand, k, False)
+    cfg.domain_rand.randomize_restitution = True
+    cfg.noise.add_noise = False
+    cfg.env.send_timeouts = False
+
+
+def _curricula_off(cfg):
+    _flat(cfg)
+    cfg.commands.heading_command = False
+    cfg.commands.curriculum = False
+    cfg.terrain.curriculum = False
+
+
+def _plane_allterms(cfg):
+    _all_terms(cfg)
+    cfg.terrain.mesh_type = "plane"
+
+
+def _plane_allterms_inside(cfg):
+    _plane_allterms(cfg)
+    cfg.termination.out_of_border = False
+
+
 TWEAKS = {
     "aliengo_flat": ("aliengo", _flat),
-    "aliengo_stairs": ("aliengo_stairs", lambda cfg: setattr(cfg.terrain, "terrain_proportions", [0.0, 0.0, 0.0, 0.0, 0.5, 0.5, 0.0, 0.0, 0.0, 0.0])),
+    "aliengo_stairs": ("aliengo_stairs", _stairs),
     "aliengo_allterms": ("aliengo", _all_terms),
     "aliengo_amp": ("aliengo_amp", _flat),
     "aliengo_reset_subset": ("aliengo", _flat),      # + the reference's reset_idx(env_ids) called by hand after the last step (fin_* keys)
+    "aliengo_ctrl_v": ("aliengo", _ctrl_v),
+    "aliengo_ctrl_t": ("aliengo", _ctrl_t),
+    "aliengo_dr_off": ("aliengo", _dr_off),
+    "aliengo_curricula_off": ("aliengo", _curricula_off),
+    # "aliengo_plane_allterms" (_plane_allterms) is not here: the reference's own step() raises under it -- check_termination (LR:276) calls
+    # self.terrain.in_terrain_range with the Aliengo task's termination.out_of_border = True, and create_sim (LR:470-471) builds self.terrain
+    # for heightfield / trimesh only: AttributeError: 'LeggedRobot' object has no attribute 'terrain'.  The plane branches of the step
+    # (LR:1331, 1370, 1719, 1746) are captured with that one termination switched off instead:
+    "aliengo_plane_allterms_inside": ("aliengo", _plane_allterms_inside),
 }
 SCENARIOS = sorted(TWEAKS)
 
@@ -74,6 +135,9 @@ class FixtureTerrain:
     """Terrain stand-in carrying the fixture's own grid (robust to later generator changes)."""
 
     def __init__(self, fx):
+        if "height_grid" not in fx.files:      # mesh_type plane: no grid (TER:52-53)
+            self.heightsamples = self.env_origins = None
+            return
         self.heightsamples = fx["height_grid"]
         self.env_origins = fx["terrain_origins"]
         self.tot_rows, self.tot_cols = self.heightsamples.shape
@@ -103,6 +167,8 @@ def replay(fx, backend, get, put, extra_flags=0):
     if big:   # the init-time draws that place the robots (LR:1221-1244) at BASELINE size, before anything has stepped
         for k in ("terrain_levels", "terrain_types", "env_origins"):
             np.testing.assert_array_equal(get(k), fx["init_" + k], err_msg=f"init {k} at N = {N}")
+    if "init_env_origins" in fx.files:   # mesh_type plane: the grid of robots (LR:1241-1250) is the host's to set (include/lsim.h)
+        put("env_origins", fx["init_env_origins"])
     backend.reset_all()
     T = len(fx["in_counter_before"])
     for t in range(T):
@@ -169,6 +235,8 @@ def compare_step(t, ref, get_full, stats_row, dt=0.02):
     # E2, the action-delay model (LR:133-138) on EVERY sub-step: the drawn delay, the torques _compute_torques returned for each of the four
     # delayed actions (only the last sub-step's action equals `actions` whatever the delay), and the delayed actions rebuilt from the
     # backend's own buffers
+    if "restitution" in ref:     # fixtures captured since the randomize_restitution branch is pinned
+        np.testing.assert_allclose(get("restitution", "restitution"), ref["restitution"], rtol=2e-5, atol=1e-6, err_msg=f"step {t}: restitution")
     delay = get("delay_steps")
     np.testing.assert_array_equal(delay, ref["delay_steps"], err_msg=f"step {t}: delay_steps")
     np.testing.assert_allclose(get("substep_torques", "substep_torques"), ref["substep_torques"], rtol=2e-5, atol=2e-4, err_msg=f"step {t}: per-sub-step torques")
@@ -177,6 +245,9 @@ def compare_step(t, ref, get_full, stats_row, dt=0.02):
         act, last, delay = act[sel], last[sel], delay[sel]
     sub = np.arange(ref["delayed_actions"].shape[1])
     rebuilt = last[:, None, :] + (act - last)[:, None, :] * (sub[None, :, None] >= delay[:, None, None]).astype(np.float32)
+    if not ref.get("delay_on", 1):   # LR:133 / LR:135: with domain_rand.delay off every sub-step takes `actions` itself, not last + (actions - last) * 1
+        assert not delay.any()
+        rebuilt = np.repeat(act[:, None, :], len(sub), axis=1)
     np.testing.assert_allclose(rebuilt, ref["delayed_actions"], rtol=0, atol=1e-6, err_msg=f"step {t}: delayed_actions")
     mask = ref["term_mask"].astype(bool)
     np.testing.assert_array_equal(get("reset").astype(bool), mask, err_msg=f"step {t}: termination ids")

@@ -44,6 +44,7 @@ from legged_gym.envs.aliengo import aliengo_config, aliengo_stairs_config, alien
 from isaacgym import gymapi  # noqa: E402  (stub)
 
 import philox_np  # noqa: E402
+import golden_replay as GR  # noqa: E402  (the scenario list and its tweak functions: one definition for the generator and the tests)
 from helpers import make_oracle  # noqa: E402
 from isaacgymloco_amd import abi  # noqa: E402
 from isaacgymloco_amd.envs import config as C  # noqa: E402
@@ -176,14 +177,22 @@ def install_rng_patches():
     wrap(LeggedRobot, "_update_terrain_curriculum",
          before=lambda self, env_ids: setattr(CTX, "plan", [(TAG["reset_level"], 0, np_ids(env_ids))]))
 
-    def before_reset_dofs(self, env_ids):
+    def before_reset_dofs(self, env_ids):      # LR:698-711: the stream index of a draw is fixed (positions 0-11, velocities 12-23), the draw optional
         ids = np_ids(env_ids)
-        CTX.plan = [(TAG["reset_dof"], 0, ids), (TAG["reset_dof"], 12, ids)]
+        plan = []
+        if getattr(self.cfg.domain_rand, "dof_init_pos_ratio_range", None) is not None:
+            plan.append((TAG["reset_dof"], 0, ids))
+        if getattr(self.cfg.domain_rand, "randomize_dof_vel", False):
+            plan.append((TAG["reset_dof"], 12, ids))
+        CTX.plan = plan
     wrap(LeggedRobot, "_reset_dofs", before=before_reset_dofs)
 
-    def before_reset_root(self, env_ids):
+    def before_reset_root(self, env_ids):      # LR:726-813: position 0-2 (custom origins only), rotation 3-5, velocity 6-11
         ids = np_ids(env_ids)
-        CTX.plan = [(TAG["reset_root"], k, ids) for k in range(12)]
+        dr = self.cfg.domain_rand
+        assert hasattr(dr, "base_init_pos_range") and hasattr(dr, "base_init_rot_range") and isinstance(getattr(dr, "base_init_vel_range", None), dict), \
+            "draw plan written for the per-axis ranges every Aliengo task sets"
+        CTX.plan = [(TAG["reset_root"], k, ids) for k in range(0 if self.custom_origins else 3, 12)]
     wrap(LeggedRobot, "_reset_root_states", before=before_reset_root)
 
     def before_shape_props(self, env_ids):
@@ -268,16 +277,18 @@ def build_reference_env(ref_cfg, terrain, model, N):
     env.history_length = int(env.num_obs / env.num_one_step_obs)
     # create_sim / _create_envs products (LR:463-482, LR:1107-1219) supplied as data
     env.up_axis_idx = 2
-    rt = object.__new__(RefTerrain)  # the reference's Terrain class, filled with our grid (its generators need isaacgym)
-    rt.cfg = ref_cfg.terrain
-    rt.env_length, rt.env_width = ref_cfg.terrain.terrain_length, ref_cfg.terrain.terrain_width
-    rt.xSize = ref_cfg.terrain.terrain_length * ref_cfg.terrain.num_rows
-    rt.ySize = ref_cfg.terrain.terrain_width * ref_cfg.terrain.num_cols
-    rt.heightsamples = terrain.heightsamples
-    rt.env_origins = terrain.env_origins
-    rt.tot_rows, rt.tot_cols = terrain.tot_rows, terrain.tot_cols
-    env.terrain = rt
-    env.height_samples = torch.tensor(terrain.heightsamples).view(terrain.tot_rows, terrain.tot_cols)
+    meshed = ref_cfg.terrain.mesh_type in ("heightfield", "trimesh")
+    if meshed:   # LR:470-471: create_sim builds self.terrain for these two only -- on a plane the attribute does not exist
+        rt = object.__new__(RefTerrain)  # the reference's Terrain class, filled with our grid (its generators need isaacgym)
+        rt.cfg = ref_cfg.terrain
+        rt.env_length, rt.env_width = ref_cfg.terrain.terrain_length, ref_cfg.terrain.terrain_width
+        rt.xSize = ref_cfg.terrain.terrain_length * ref_cfg.terrain.num_rows
+        rt.ySize = ref_cfg.terrain.terrain_width * ref_cfg.terrain.num_cols
+        rt.heightsamples = terrain.heightsamples
+        rt.env_origins = terrain.env_origins
+        rt.tot_rows, rt.tot_cols = terrain.tot_rows, terrain.tot_cols
+        env.terrain = rt
+        env.height_samples = torch.tensor(terrain.heightsamples).view(terrain.tot_rows, terrain.tot_cols)
     env.num_dof = env.num_dofs = 12
     env.num_bodies = 17
     env.dof_names = list(aliengo.DOF_NAMES)
@@ -304,9 +315,10 @@ def build_reference_env(ref_cfg, terrain, model, N):
     env.dof_pos_limits = lim
     base_init = ref_cfg.init_state.pos + ref_cfg.init_state.rot + ref_cfg.init_state.lin_vel + ref_cfg.init_state.ang_vel
     env.base_init_state = torch.tensor(base_init, dtype=torch.float)
-    env.custom_origins = True
-    env.max_terrain_level = ref_cfg.terrain.num_rows
-    env.terrain_origins = torch.from_numpy(terrain.env_origins).to(torch.float)
+    if meshed:
+        env.custom_origins = True
+        env.max_terrain_level = ref_cfg.terrain.num_rows
+        env.terrain_origins = torch.from_numpy(terrain.env_origins).to(torch.float)
     env.default_rigid_body_mass = torch.tensor([b.mass for b in model.bodies])
     tensors = dict(root=torch.zeros(N, 13), dof=torch.zeros(N * 12, 2), contact=torch.zeros(N * 17, 3), body=torch.zeros(N * 17, 13))
     tensors["root"][:, 6] = 1.0
@@ -315,6 +327,8 @@ def build_reference_env(ref_cfg, terrain, model, N):
     env.terrain_levels = torch.zeros(N, dtype=torch.long)
     env.terrain_types = torch.zeros(N, dtype=torch.long)
     env.env_origins = torch.zeros(N, 3)
+    if not meshed:
+        env._get_env_origins()       # the reference's own grid of robots (LR:1241-1250); sets custom_origins = False
     env._init_buffers()              # the reference's own buffer set-up (LR:913-1032)
     env._prepare_reward_function()   # LR:1035-1059
     env.init_done = True
@@ -333,9 +347,11 @@ def sync_initial_state(env, tensors, orc):
     env.com_displacement = t(b["com_displacement"])
     env.friction_coeffs = t(b["friction"]).unsqueeze(1)
     env.restitution_coeffs = t(b["restitution"]).unsqueeze(1)
-    env.terrain_levels = t(b["terrain_levels"])
-    env.terrain_types = t(b["terrain_types"])
-    env.env_origins = t(b["env_origins"])
+    if env.custom_origins:
+        env.terrain_levels = t(b["terrain_levels"])
+        env.terrain_types = t(b["terrain_types"])
+        env.env_origins = t(b["env_origins"])
+    # (plane: env.env_origins is the reference's own grid of robots, LR:1241-1250, which run_scenario hands to the build -- include/lsim.h leaves it to the host)
     tensors["root"][:] = t(b["root_states"])
     tensors["dof"][:] = t(b["dof_state"]).view(-1, 2)
 
@@ -351,7 +367,7 @@ OUT_KEYS = ["obs", "priv_obs", "rew", "reset", "time_out", "extras_time_outs", "
             "commands", "torques", "base_lin_vel", "base_ang_vel", "projected_gravity", "feet_air_time", "last_contacts",
             "contact_filt", "measured_heights", "root_states", "dof_state", "terrain_levels", "env_origins", "episode_length",
             "kp_factors", "kd_factors", "friction", "last_actions", "last_last_actions", "last_dof_vel", "episode_sums",
-            "command_ranges", "ep_stats", "level_mean", "delayed_actions", "delay_steps", "substep_torques"]
+            "command_ranges", "ep_stats", "level_mean", "delayed_actions", "delay_steps", "delay_on", "substep_torques", "restitution"]
 
 
 def capture(env, tensors, N):
@@ -381,12 +397,14 @@ def capture(env, tensors, N):
         dof_state=tensors["dof"].numpy().reshape(N, 12, 2).copy(), terrain_levels=env.terrain_levels.numpy().copy(),
         env_origins=env.env_origins.numpy().copy(), episode_length=env.episode_length_buf.numpy().copy(),
         kp_factors=env.Kp_factors.numpy()[:, 0].copy(), kd_factors=env.Kd_factors.numpy()[:, 0].copy(),
-        friction=env.friction_coeffs.numpy()[:, 0].copy(), last_actions=env.last_actions.numpy().copy(),
+        friction=env.friction_coeffs.numpy()[:, 0].copy(), restitution=env.restitution_coeffs.numpy()[:, 0].copy(), last_actions=env.last_actions.numpy().copy(),
         last_last_actions=env.last_last_actions.numpy().copy(), last_dof_vel=env.last_dof_vel.numpy().copy(),
         episode_sums=es, ep_stats=ep, level_mean=level_mean, amp_obs=env.get_amp_observations().numpy().copy(),
         command_ranges=np.array([cr["lin_vel_x"], cr["lin_vel_y"], cr["ang_vel_yaw"], cr["heading"]], dtype=np.float64),
         delayed_actions=env.delayed_actions.numpy().copy(),                                   # (N, 4, 12), LR:133-138
-        delay_steps=CTX.last_delay.numpy().reshape(N).astype(np.int32),                        # the draw of LR:134
+        # the delay LR:135-138 applied: the draw of LR:134 (a local the reference drops), which is made but not used when domain_rand.delay is off
+        delay_steps=(CTX.last_delay.numpy().reshape(N).astype(np.int32) if env.cfg.domain_rand.delay else np.zeros(N, np.int32)),
+        delay_on=np.uint8(bool(env.cfg.domain_rand.delay)),
         substep_torques=torch.stack(CTX.sub_torques[-env.cfg.control.decimation:], dim=1).numpy().copy(),   # (N, 4, 12), LR:146 per sub-step
     )
 
@@ -406,6 +424,10 @@ def run_scenario(name, task, ref_cfg_cls, N, segments, seed=1, tweak=None, using
         tweak(ref_cfg)
     CTX = None
     env, tensors = build_reference_env(ref_cfg, terrain, model, N)
+    if not env.custom_origins:
+        for sim in (gen, orc):
+            sim.buf["env_origins"][:] = env.env_origins.numpy()
+            sim.buf["root_states"][:, :3] += env.env_origins.numpy()
     sync_initial_state(env, tensors, orc)
     CTX = RngCtx(seed, 0, N)
     rs = np.random.RandomState(1234)
@@ -475,9 +497,12 @@ def run_scenario(name, task, ref_cfg_cls, N, segments, seed=1, tweak=None, using
             gen.buf["episode_length"][:] = env.episode_length_buf.numpy()
             gen.buf["terrain_levels"][:] = env.terrain_levels.numpy()
             gen.buf["env_origins"][:] = env.env_origins.numpy()
-    pack = {"num_envs": np.int64(N), "seed": np.int64(seed), "task": np.array(task),
-            "height_grid": terrain.heightsamples, "terrain_origins": terrain.env_origins.astype(np.float32),
-            "segments": np.array(segments, dtype=np.int64)}
+    pack = {"num_envs": np.int64(N), "seed": np.int64(seed), "task": np.array(task), "segments": np.array(segments, dtype=np.int64),
+            "torque_limits": env.torque_limits.numpy().copy()}
+    if terrain.heightsamples is not None:
+        pack["height_grid"], pack["terrain_origins"] = terrain.heightsamples, terrain.env_origins.astype(np.float32)
+    else:                                     # mesh_type plane: no grid; the robots stand on the reference's own grid of origins (LR:1241-1250)
+        pack["init_env_origins"] = orc.buf["env_origins"].copy()
     if final_reset_ids is not None:
         ids = np.asarray(final_reset_ids, dtype=np.int64)
         # the command curriculum averages over the reset SET (LR:307-308, LR:875): only the chosen envs carry a tracking sum above the bar
@@ -608,36 +633,54 @@ def run_scenario_big(name, task, ref_cfg_cls, N=4096, seed=1, tweak=None, using_
           f"size={os.path.getsize(path) / 1e6:.2f} MB")
 
 
+REF_CFGS = {"aliengo": aliengo_config.AlienGoRoughCfg, "aliengo_stairs": aliengo_stairs_config.AlienGoStairsCfg,
+            "aliengo_amp": aliengo_amp_config.AlienGoRoughCfg}
+# N = 16 scenarios: segments of (start_counter, num_steps); name, task and tweak come from golden_replay.TWEAKS
+SEGMENTS = {
+    "aliengo_flat": [(0, 6), (795, 10), (996, 8)],
+    "aliengo_stairs": [(0, 6), (795, 8), (996, 8)],
+    "aliengo_allterms": [(0, 4), (795, 8)],
+    "aliengo_amp": [(0, 4), (795, 8)],
+    "aliengo_reset_subset": [(0, 3), (997, 3)],
+    # the config branches no shipped task takes.  Counters crossed: 800 (disturbance % 8, push % 800), 1000 (% 8, command curriculum with the
+    # reset forced on it); every later segment spreads the episode lengths over 0 .. 1002 (command resampling at % 500, time-outs past 1000)
+    "aliengo_ctrl_v": [(0, 4), (795, 8)],
+    "aliengo_ctrl_t": [(0, 4), (795, 8)],
+    "aliengo_dr_off": [(0, 4), (795, 8), (996, 8)],
+    "aliengo_curricula_off": [(0, 4), (996, 8)],
+    "aliengo_plane_allterms": [(0, 4), (795, 8)],
+    "aliengo_plane_allterms_inside": [(0, 4), (795, 8)],
+}
+BRANCH_SCENARIOS = ["aliengo_ctrl_v", "aliengo_ctrl_t", "aliengo_dr_off", "aliengo_curricula_off", "aliengo_plane_allterms_inside"]
+
+
+def run_named(name, **kw):
+    task, tweak = GR.TWEAKS[name]
+    run_scenario(name, task, REF_CFGS[task], 16, SEGMENTS[name], tweak=tweak, using_amp=(task == "aliengo_amp"), **kw)
+
+
 def main():
     install_rng_patches()
-
-    def flat_only(cfg):
-        cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0]
+    flat_only, stairs_only, all_terms = GR._flat, GR._stairs, GR._all_terms
 
     if sys.argv[1:] == ["reset_subset"]:     # only the by-hand reset_idx(env_ids) fixture
-        run_scenario("aliengo_reset_subset", "aliengo", aliengo_config.AlienGoRoughCfg, 16, [(0, 3), (997, 3)], tweak=flat_only,
-                     final_reset_ids=[1, 3, 4, 9, 15])
+        run_named("aliengo_reset_subset", final_reset_ids=[1, 3, 4, 9, 15])
+        return
+    if sys.argv[1:] == ["branches"]:         # only the config-branch fixtures
+        for name in BRANCH_SCENARIOS:
+            run_named(name)
+        return
+    if sys.argv[1:] == ["plane_allterms"]:   # the variant the reference's own step() raises under (golden_replay.TWEAKS): shows the error, writes nothing
+        run_scenario("aliengo_plane_allterms", "aliengo", REF_CFGS["aliengo"], 16, SEGMENTS["aliengo_plane_allterms"], tweak=GR._plane_allterms)
         return
 
-    def stairs_only(cfg):   # only generators that exist in-tree (TER:229-294): stairs up/down
-        cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5, 0.0, 0.0, 0.0, 0.0]
-
-    run_scenario("aliengo_flat", "aliengo", aliengo_config.AlienGoRoughCfg, 16, [(0, 6), (795, 10), (996, 8)], tweak=flat_only)
-    run_scenario("aliengo_stairs", "aliengo_stairs", aliengo_stairs_config.AlienGoStairsCfg, 16, [(0, 6), (795, 8), (996, 8)], tweak=stairs_only)
-
-    def all_terms(cfg):     # every _reward_* function of LR:1444-1770 active (the 30 terms no shipped config enables)
-        flat_only(cfg)
-        for k, nm in enumerate(abi.REWARD_NAMES):
-            setattr(cfg.rewards.scales, nm, (0.5 + 0.01 * k) * (-1.0 if k % 3 else 1.0))
-        cfg.rewards.only_positive_rewards = True
-    run_scenario("aliengo_allterms", "aliengo", aliengo_config.AlienGoRoughCfg, 16, [(0, 4), (795, 8)], tweak=all_terms)
-    run_scenario("aliengo_amp", "aliengo_amp", aliengo_amp_config.AlienGoRoughCfg, 16, [(0, 4), (795, 8)], tweak=flat_only, using_amp=True)
+    for name in ("aliengo_flat", "aliengo_stairs", "aliengo_allterms", "aliengo_amp"):
+        run_named(name)
+    for name in BRANCH_SCENARIOS:
+        run_named(name)
 
     # BASELINE size (cfg 2-4): the same three tasks at N = 4096.  `aliengo` runs with every reward term on so that the stumble slices are live.
-    def all_terms_10(cfg):   # 10-entry proportions of in-tree generators only (flat, stairs, pit, gap): the stairs-up / pit / gap slices of LR:1597-1607 are non-empty
-        all_terms(cfg)
-        cfg.terrain.terrain_proportions = [0.5, 0.0, 0.0, 0.0, 0.2, 0.1, 0.0, 0.0, 0.1, 0.1]
-    run_scenario_big("aliengo", "aliengo", aliengo_config.AlienGoRoughCfg, tweak=all_terms_10)
+    run_scenario_big("aliengo", "aliengo", aliengo_config.AlienGoRoughCfg, tweak=GR._all_terms_10)
     run_scenario_big("aliengo_stairs", "aliengo_stairs", aliengo_stairs_config.AlienGoStairsCfg, tweak=stairs_only)
     run_scenario_big("aliengo_amp", "aliengo_amp", aliengo_amp_config.AlienGoRoughCfg, tweak=flat_only, using_amp=True)
 
