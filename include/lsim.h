@@ -41,7 +41,8 @@ extern "C" {
                                     also under 7, as pure additions (no earlier struct or entry changed, so a caller built against the first
                                     version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh);
                                     lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot);
-                                    lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise) */
+                                    lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise);
+                                    lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1118,6 +1119,67 @@ typedef struct lsim_sensor_model {
  * not a multiple of 4; sigma0, sigma2 not finite or < 0; p_drop outside [0, 1]; drop_value, clip_lo, clip_hi, offset or gain not finite;
  * clip_lo > clip_hi; a flag bit other than the two above; both of them set. */
 int lsim_sensor_capture(const lsim_sensor_model_t* sm, void* stream);
+
+/* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (training runs the same
+ * parameters through torch; isaacgymloco_amd/learn/depth_encoder.py).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no
+ * host synchronisation, raw pointers only, so it can be captured in a graph.  It reads `hist` (and episode_length for the due rule), the
+ * parameters where the caller keeps them, and writes `latent`; nothing else.
+ *
+ * Input.  hist, hist_stride are those of the sensor's lsim_sensor_model_t, hist_slots its K = latency + frames.  The image of env e has `frames`
+ *   channels, channel f = slot f (oldest first), pixel (y, x) = ray r = y * width + x:
+ *     x[f][y][x] = hist[(e * hist_slots + f) * hist_stride + y * width + x],   f < frames, y < height, x < width.
+ * Network.  Two square-kernel convolutions without padding or dilation, then a linear layer; ELU(v) = v > 0 ? v : expm1(v)  (alpha = 1):
+ *     h1 = (height - k1) / s1 + 1,  w1 = (width - k1) / s1 + 1,  h2 = (h1 - k2) / s2 + 1,  w2 = (w1 - k2) / s2 + 1      (integer division)
+ *     a1[c][y][x] = ELU( b1[c] + sum_{f < frames, i < k1, j < k1} w1[c][f][i][j] * x[f][y * s1 + i][x * s1 + j] ),      c < c1, y < h1, x < w1
+ *     a2[c][y][x] = ELU( b2[c] + sum_{d < c1, i < k2, j < k2}     w2[c][d][i][j] * a1[d][y * s2 + i][x * s2 + j] ),     c < c2, y < h2, x < w2
+ *     z[o]        = b3[o] + sum_{c < c2, y < h2, x < w2} w3[o][(c * h2 + y) * w2 + x] * a2[c][y][x],                    o < latent_dim
+ *     latent[e * latent_stride + o] = final_act ? ELU(z[o]) : z[o]
+ *   The parameters are in torch's own contiguous layout -- w1 [c1][frames][k1][k1], w2 [c2][c1][k2][k2] (Conv2d.weight), w3 [latent_dim][c2*h2*w2]
+ *   (Linear.weight on torch.flatten of NCHW: (c, y, x)) -- and are read at every launch, so an optimiser step is seen by the next one.
+ *   Every sum is fp32, in any order, and a product and a sum may be fused.  A non-finite value of hist propagates as it does through torch.
+ * Which envs.  Env e is visited when e % env_stride == 0 and is due by the rule of lsim_sensor_capture, with the same episode_length, tick,
+ *   period, stagger and flags:  fill = (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0;
+ *     due = fill || ( !(flags & LSIM_SENSOR_RESETS_ONLY) && (tick + (stagger ? e : 0)) % period == 0 ).
+ *   For an env that is not visited or not due NOTHING is written: its latent row keeps the encoding of its last capture.  Launched after the
+ *   sensor's capture of the same tick, the due envs are exactly those whose history has just changed.  tick is passed by value (see above).
+ * Limits: the kernel keeps the image, a1 and a2 of one env in the workgroup's LDS; lsim_depth_encode_sizes states the bytes. */
+#define LSIM_DEPTH_ENC_MAX_CHANNELS 64     /* c1, c2 */
+#define LSIM_DEPTH_ENC_MAX_KERNEL 8        /* k1, k2 */
+#define LSIM_DEPTH_ENC_MAX_STRIDE 4        /* s1, s2 */
+#define LSIM_DEPTH_ENC_MAX_LATENT 256      /* latent_dim */
+#define LSIM_DEPTH_ENC_MAX_LDS_BYTES 163840 /* 4 * (max(frames*height*width, c2*h2*w2) + c1*h1*w1 + frames*k1*k1 + c1*k2*k2), the first two terms each
+                                              rounded up to a multiple of 4: the image and a2 share one region, a1 has its own, then one tap table per convolution */
+typedef struct lsim_depth_encoder {
+    const float* hist;                /* [N, hist_slots, hist_stride]: lsim_sensor_model_t.hist, read only, 16-byte aligned */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    const float* w1;                  /* [c1][frames][k1][k1], 4-byte aligned like every parameter */
+    const float* b1;                  /* [c1] */
+    const float* w2;                  /* [c2][c1][k2][k2] */
+    const float* b2;                  /* [c2] */
+    const float* w3;                  /* [latent_dim][c2 * h2 * w2] */
+    const float* b3;                  /* [latent_dim] */
+    float* latent;                    /* [N, latent_stride], 16-byte aligned: row e, latent_dim floats */
+    int64_t tick;                     /* >= 0, by value: the tick of the sensor's capture */
+    int32_t hist_stride, hist_slots;  /* floats between slots (>= height * width, a multiple of 4); K: frames <= hist_slots <= LSIM_SENSOR_MAX_HISTORY */
+    int32_t num_envs, env_stride;     /* >= 1 */
+    int32_t height, width, frames;    /* >= 1 */
+    int32_t c1, k1, s1;               /* 1..MAX_CHANNELS, 1..MAX_KERNEL (<= height, width), 1..MAX_STRIDE */
+    int32_t c2, k2, s2;               /* likewise, k2 <= h1, w1 */
+    int32_t latent_dim, final_act;    /* 1..MAX_LATENT; 0 / 1 */
+    int32_t latent_stride;            /* floats between rows of latent: >= latent_dim, a multiple of 4 */
+    int32_t period, stagger;          /* as lsim_sensor_model_t's */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+} lsim_depth_encoder_t;
+/* bytes of dynamic LDS the configuration needs (only the extents are read: no pointer, no tick).  LSIM_E_INVALID: de or lds_bytes NULL, an extent
+ * out of range as listed below, or more than LSIM_DEPTH_ENC_MAX_LDS_BYTES */
+int lsim_depth_encode_sizes(const lsim_depth_encoder_t* de, size_t* lds_bytes);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch (nothing is written): de == NULL; hist or latent NULL or
+ * not 16-byte aligned; episode_length NULL or not 8-byte aligned; a parameter NULL or not 4-byte aligned; num_envs, env_stride, height, width
+ * or frames < 1; frames > hist_slots; hist_slots > LSIM_SENSOR_MAX_HISTORY; height * width > hist_stride; hist_stride not a multiple of 4;
+ * c1, c2 outside 1..64; k1, k2 outside 1..8; s1, s2 outside 1..4; k1 > height or width; k2 > h1 or w1; latent_dim outside 1..256; final_act
+ * outside 0..1; latent_stride < latent_dim or not a multiple of 4; the LDS bytes above the limit; tick < 0; period < 1; stagger outside 0..1;
+ * a flag bit other than the sensor model's two; both of them set. */
+int lsim_depth_encode(const lsim_depth_encoder_t* de, void* stream);
 
 #ifdef __cplusplus
 }

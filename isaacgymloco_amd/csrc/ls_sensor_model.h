@@ -18,12 +18,16 @@
 #include "ls_math.h"
 
 // is env due on this tick, and is its whole history filled?  tick_mod = tick % period (formed on the host: no 64-bit division on the device)
-LS_RC_FN bool ls_sm_due(const lsim_sensor_model_t& sm, int env, uint32_t tick_mod, bool& fill) {
-    fill = (sm.flags & LSIM_SENSOR_FILL_ALL) != 0u || sm.episode_length[env] == 0;
+// The rule itself, on the fields it reads: lsim_k_sensor_capture and lsim_k_depth_encode (ls_depth_encoder.h) both decide with this function.
+LS_RC_FN bool ls_sensor_due(uint32_t flags, const int64_t* episode_length, int period, int stagger, int env, uint32_t tick_mod, bool& fill) {
+    fill = (flags & LSIM_SENSOR_FILL_ALL) != 0u || episode_length[env] == 0;
     if (fill) return true;
-    if (sm.flags & LSIM_SENSOR_RESETS_ONLY) return false;
-    const uint32_t p = (uint32_t)sm.period;
-    return (tick_mod + (sm.stagger ? (uint32_t)env % p : 0u)) % p == 0u;      // both terms < p <= 2^31: no wrap
+    if (flags & LSIM_SENSOR_RESETS_ONLY) return false;
+    const uint32_t p = (uint32_t)period;
+    return (tick_mod + (stagger ? (uint32_t)env % p : 0u)) % p == 0u;      // both terms < p <= 2^31: no wrap
+}
+LS_RC_FN bool ls_sm_due(const lsim_sensor_model_t& sm, int env, uint32_t tick_mod, bool& fill) {
+    return ls_sensor_due(sm.flags, sm.episode_length, sm.period, sm.stagger, env, tick_mod, fill);
 }
 
 // ls_rc_ray without its store: the value lsim_raycast writes for ray r of env; hit = (t < far), label 1 / 0

@@ -26,6 +26,10 @@ late, refilled inside the launch when the env resets:
     cam = depth_camera(env, 64, 48, 87, ..., model=SensorModel(period=5, stagger=True, latency=1, frames=2, noise=(0.01, 0.002), dropout=0.02, normalise=True))
     env.add_sensor("depth", cam)            # fills every env's history once, then one launch per step_device()
     obs = env.sensors["depth"].frame_images()    # [N, 2, 48, 64], oldest first, live; cam.image() stays the clean depth of the env's latest capture
+
+Encoder (`cam.attach_encoder(learn.depth_encoder.DepthEncoder(48, 64, frames=2).to(device))`, lsim_depth_encode): every capture is followed,
+on the same stream and with the same tick and flags, by one more launch that turns the frames of the envs just captured into a latent row;
+`cam.latent()` is the live [N, latent_dim] tensor.  Without an attached encoder nothing of this is created or launched.
 """
 import ctypes
 import math
@@ -103,7 +107,8 @@ class RaySensor:
     With the defaults nothing of this is allocated and the launch is lsim_raycast.
     `model` (a SensorModel): the launch is lsim_sensor_capture -- `update(tick=...)` renders the envs due on that tick, `frames()` is the live
     [N, frames, R] history, `out` the clean value of each env's latest capture, `refresh()` fills every env's history from the present state,
-    `tick` the tick of the last launch and `stream_id` (set by env.add_sensor) what separates the noise of the sensors of one env.
+    `tick` the tick of the last launch and `stream_id` (set by env.add_sensor) what separates the noise of the sensors of one env;
+    `attach_encoder(enc)` adds the encoder's launch behind every capture and `latent()` is its live [N, latent_dim] output.
     With `model=None` nothing of this is allocated and the launch is the one above."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
@@ -156,6 +161,7 @@ class RaySensor:
         rc.near, rc.far = self.near, self.far
         self._rc = rc
         self._labels = None
+        self._encoder = self._latent = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
@@ -269,6 +275,8 @@ class RaySensor:
             self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
             self._sm.tick, self._sm.flags = self.tick, int(flags)
             lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
+            if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
+                self._encoder.encode_device(self, self.tick, int(flags), stream)
             return self.out
         if self._bodies:
             lib.check(self._api.lsim_raycast_bodies(ctypes.byref(self._rb), self._stream(stream)), what="lsim_raycast_bodies")
@@ -287,6 +295,30 @@ class RaySensor:
         if self.model is None:
             raise ValueError("the sensor was created without a model")
         return self._hist[:, :self.model.frames, :self.num_rays]
+
+    def attach_encoder(self, enc):
+        """from now on every update() / refresh() is followed by `enc`'s launch (learn.depth_encoder.DepthEncoder.encode_device) on the same
+        stream with the same tick and flags; encodes every env once now, from the present history, when the sensor has captured before"""
+        if self.model is None:
+            raise ValueError("attach_encoder: the sensor was created without a model, so it has no frame history to encode")
+        self._encoder = enc
+        if self.tick >= 0:
+            enc.encode_device(self, self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+        return enc
+
+    def _latent_buffer(self, latent_dim):
+        """the [N, stride] buffer an encoder's launch writes; created on first use"""
+        stride = (int(latent_dim) + 3) // 4 * 4
+        if self._latent is None or self._latent.shape[1] != stride:
+            self._latent = torch.zeros((int(self.env.num_envs), stride), dtype=torch.float32, device=self._out.device)
+        self._latent_dim = int(latent_dim)
+        return self._latent
+
+    def latent(self):
+        """live [N, latent_dim] tensor: row e is the encoding of env e's frames at its last capture (attach_encoder)"""
+        if self._latent is None:
+            raise ValueError("the sensor has no encoder (attach_encoder)")
+        return self._latent[:, :self._latent_dim]
 
     def labels(self):
         """live uint8 [N, R] tensor of the latest launch (labels=True): 0 nothing within [near, far], 1 terrain, 2 + b body b (`body_names[b]`)"""
