@@ -27,7 +27,6 @@ struct lsim_sim {
     int device_id;
     int64_t step_counter;
     uint32_t reset_calls;   // lsim_reset_envs calls so far (salt of their random draws)
-    int priority_max_envs;  // contact-count wave priorities up to this many robots (LSIM_PRIORITY_MAX_ENVS overrides: a measurement hook)
     int init_done;
     int stats_row;
     void* prof;        // backend-owned profiling state (HIP events), may be null
@@ -303,8 +302,6 @@ static int ls_create_impl(const lsim_config* cfgs, const lsim_robot_model* model
     else bad |= lsbk_h2d(s->dev_ctx, &h, sizeof(LsCtx));
     if (bad) { *partial = nullptr; ls_free_partial(s); return LSIM_E_HIP; }
     s->step_counter = 0;
-    s->priority_max_envs = 32768;
-    if (const char* e = getenv("LSIM_PRIORITY_MAX_ENVS")) s->priority_max_envs = atoi(e);
     s->init_done = 1;   // construction completes before the runner's first reset (LR:116, HIMR:84)
     *partial = nullptr;
     *out = s;
@@ -333,7 +330,7 @@ extern "C" int LS_API(step_ex)(lsim_sim* s, const float* actions_dev, uint32_t f
     // contact-count wave priorities pay while a launch is a few rounds of waves (4096 resident at a time): +6.5 % at N = 4096, +3.7 % at 8192,
     // +2.1 % at 12 288, +1.2 % at 16 384, nothing at 32 768; with many rounds in flight the slowest wave of a round hides behind the next
     // and the priorities only perturb the arbiter (-0.4 % at N = 65 536 / 262 144)
-    if (s->cfg.num_envs > s->priority_max_envs) a.flags |= LSIM_STEP_FLAT_PRIORITY;
+    if (s->cfg.num_envs > 32768) a.flags |= LSIM_STEP_FLAT_PRIORITY;
     lsbk_prof_mark(s, 0, stream);
     if (lsbk_launch_a(s, a, stream) != 0) LS_FAIL(s, LSIM_E_HIP, "kernel A launch failed");
     lsbk_prof_mark(s, 1, stream);
@@ -341,11 +338,7 @@ extern "C" int LS_API(step_ex)(lsim_sim* s, const float* actions_dev, uint32_t f
     // the error is reported, and the handle's state matches what the device will have done)
     s->step_counter = step;
     s->stats_row = a.row_out;
-#if defined(LS_EXP_NO_FINISH)      // timing probe only (wrong statistics): what the finish launch costs on the rollout's critical path
-    if (a.fuse_tail) { }
-#else
     if (a.fuse_tail) { if (lsbk_launch_finish(s, a, stream) != 0) LS_FAIL(s, LSIM_E_HIP, "finish kernel launch failed"); }
-#endif
     else if (lsbk_launch_b(s, a, stream) != 0) LS_FAIL(s, LSIM_E_HIP, "kernel B launch failed");
     lsbk_prof_mark(s, 2, stream);
     return LSIM_OK;

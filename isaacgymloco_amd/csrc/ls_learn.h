@@ -111,9 +111,8 @@ __global__ __launch_bounds__(64 * LS_WGRAD_WAVES_PER_BLOCK) void lsim_k_linear_w
 // (65 us).  Every output is still added up in the same order: (s0 + s1) + (s2 + s3) over the partials w = s, s + 16, ..., then the 16 slices.
 #define LS_LEARN_HD static __host__ __device__ __forceinline__
 LS_LEARN_HD int ls_reduce_vec4(const float* part, int count) { return (count % 4 == 0) && ((((uintptr_t)part) & 15) == 0); }
-#ifndef LS_REDUCE_QUADS
 #define LS_REDUCE_QUADS 1          // output quads per thread of the vector form.  Measured in round 5 (train line, three interleaved runs): 1 -> update
-#endif                             // 70.3-70.9 ms, 2 -> 71.9-74.5, 4 -> 73.5-75.0: the summing launch wants more blocks, not more loads per thread
+                                   // 70.3-70.9 ms, 2 -> 71.9-74.5, 4 -> 73.5-75.0: the summing launch wants more blocks, not more loads per thread
 LS_LEARN_HD int ls_reduce_blocks(const float* part, int count) { return ls_reduce_vec4(part, count) ? (count + 64 * LS_REDUCE_QUADS - 1) / (64 * LS_REDUCE_QUADS) : (count + 15) / 16; }
 __device__ __forceinline__ void ls_wgrad_reduce_body(const float* __restrict__ part, int num_waves, int count, float* __restrict__ out,
                                                      const float* __restrict__ part2, int count2, float* __restrict__ out2, int block) {
@@ -323,9 +322,6 @@ __device__ __forceinline__ void ls_wgrad_ld(const float* __restrict__ r, const i
     else if (VEC == 1) { const float2 ta = *(const float2*)(r + o[0]), tb = *(const float2*)(r + o[2]); v[0] = ta.x; v[1] = ta.y; v[2] = tb.x; v[3] = tb.y; }
     else { v[0] = r[o[0]]; v[1] = r[o[1]]; v[2] = r[o[2]]; v[3] = r[o[3]]; }
 }
-#ifndef LS_WG_KNOCK
-#define LS_WG_KNOCK 0        /* diagnostic builds only (wrong results): 1 = no operand loads in the steady-state loop, 2 = no MFMAs (one FMA per accumulator instead) */
-#endif
 template <int KG> struct LsWgradStage { float a[4], z[4], x[KG][4]; };
 
 template <int VX, int VG, int KG, bool FZ, bool LIVE1 /* the second 64-column k group exists (compile-time: no branch between MFMAs) */,
@@ -371,13 +367,12 @@ __device__ __forceinline__ long ls_wgrad_tile_loop3(const float* __restrict__ x,
 #define LS_GRP(ST, J) do {                                                                                                   \
         dbacc[J] += ST.a[J];                                                                                                 \
         __builtin_amdgcn_s_setprio(1);          /* the wave entering an MFMA group wins arbitration over the one issuing loads: +5 % */  \
-        if (LS_WG_KNOCK != 2) {                                                                                              \
         _Pragma("unroll") for (int kt = 0; kt < 4; ++kt)                                                                     \
             acc[J][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ST.a[J], ST.x[0][kt], acc[J][kt], 0, 0, 0);                    \
         if (live_k1) {                                                                                                       \
             _Pragma("unroll") for (int kt = 4; kt < 4 * KG; ++kt)                                                            \
                 acc[J][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ST.a[J], ST.x[KG - 1][kt & 3], acc[J][kt], 0, 0, 0);       \
-        } } else { _Pragma("unroll") for (int kt = 0; kt < 4 * KG; ++kt) acc[J][kt][0] += ST.a[J] * ST.x[(kt >> 2) ? KG - 1 : 0][kt & 3]; }  \
+        }                                                                                                                    \
         __builtin_amdgcn_s_setprio(0); } while (0)
 #define LS_STEP(CS, CROW, LS, LROW) do { const long lr_ = (LROW);                                                            \
         if (FZ) {     /* g_z * elu'(z) for the whole step up front: spread between the MFMA groups it costs 10 % (measured) */   \
@@ -385,13 +380,13 @@ __device__ __forceinline__ long ls_wgrad_tile_loop3(const float* __restrict__ x,
             if (WGY) *(float4*)(gy + (CROW) * (long)n_out + n_base + 4 * col) = make_float4(CS.a[0], CS.a[1], CS.a[2], CS.a[3]);  \
         }                                                                                                                    \
         LS_SB(); LS_GRP(CS, 0); LS_SB();                                                                                     \
-        if (LS_WG_KNOCK != 1) ls_wgrad_ld<VG>(g + lr_ * ldg, og, LS.a); LS_SB();                                             \
+        ls_wgrad_ld<VG>(g + lr_ * ldg, og, LS.a); LS_SB();                                                                   \
         LS_GRP(CS, 1); LS_SB();                                                                                              \
-        if (LS_WG_KNOCK != 1) { if (FZ) ls_wgrad_ld<VG>(z + lr_ * ldz, og, LS.z); else ls_wgrad_ld<VX>(x + lr_ * ldx, ox0, LS.x[0]); }   \
+        if (FZ) ls_wgrad_ld<VG>(z + lr_ * ldz, og, LS.z); else ls_wgrad_ld<VX>(x + lr_ * ldx, ox0, LS.x[0]);                 \
         LS_SB(); LS_GRP(CS, 2); LS_SB();                                                                                     \
-        if (LS_WG_KNOCK != 1) { if (FZ) ls_wgrad_ld<VX>(x + lr_ * ldx, ox0, LS.x[0]); else if (live_k1) ls_wgrad_ld<VX>(x + lr_ * ldx, ox1, LS.x[KG - 1]); }  \
+        if (FZ) ls_wgrad_ld<VX>(x + lr_ * ldx, ox0, LS.x[0]); else if (live_k1) ls_wgrad_ld<VX>(x + lr_ * ldx, ox1, LS.x[KG - 1]);  \
         LS_SB(); LS_GRP(CS, 3); LS_SB();                                                                                     \
-        if (LS_WG_KNOCK != 1) { if (FZ && live_k1) ls_wgrad_ld<VX>(x + lr_ * ldx, ox1, LS.x[KG - 1]); }                      \
+        if (FZ && live_k1) ls_wgrad_ld<VX>(x + lr_ * ldx, ox1, LS.x[KG - 1]);                                                \
         LS_SB(); } while (0)
     long b = b0;
     LS_LD(s0, b + sub);
@@ -527,9 +522,6 @@ void lsim_k_linear_wgrad_tiled(const float* __restrict__ x, long ldx, const floa
 // The next step's global loads are issued before the MFMAs; two blocks per CU (61 KB of LDS each) overlap one's load / split with the other's MFMAs.
 typedef __bf16 ls_bf8 __attribute__((ext_vector_type(8)));
 #define LS_SP_STRIDE 40
-#ifndef LS_SP_KNOCKOUT
-#define LS_SP_KNOCKOUT 0      // diagnostic builds (tools/wgrad_split_probe.py): 1 no MFMA phase, 2 no global loads in the loop, 3 no split / LDS writes
-#endif
 template <bool FZ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void lsim_k_linear_wgrad_split(const float* __restrict__ x, long ldx, const float* __restrict__ g, long ldg, const float* __restrict__ z, long ldz,
@@ -586,7 +578,6 @@ void lsim_k_linear_wgrad_split(const float* __restrict__ x, long ldx, const floa
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (LS_SP_KNOCKOUT == 3 && rb > s0) break;
             ls_bf8 p0, p1, p2;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -601,8 +592,7 @@ void lsim_k_linear_wgrad_split(const float* __restrict__ x, long ldx, const floa
             *(ls_bf8*)&planes[half][0][o] = p0; *(ls_bf8*)&planes[half][1][o] = p1; *(ls_bf8*)&planes[half][2][o] = p2;
         }
         __syncthreads();
-        if (LS_SP_KNOCKOUT != 2 && rb + 32 < s1) LS_SP_LOAD(rb + 32);
-        if (LS_SP_KNOCKOUT == 1) { __syncthreads(); continue; }
+        if (rb + 32 < s1) LS_SP_LOAD(rb + 32);
         ls_bf8 fa[4][3];
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -1069,9 +1059,7 @@ extern "C" int lsim_sinkhorn(const float* scores, int64_t lds, int64_t batch, in
 // registers: 48 + 49 us per call at the minibatch of 102 400.  With the quad a wave reads and writes 16 CONSECUTIVE rows (2 KB
 // contiguous per instruction group), row reductions are two quad_perm DPP steps, and 4x the waves hide the latency.
 #define LS_EST_ROWS 64                      // sample rows per block of 256 threads
-#if !defined(LS_EST_WAVES_PER_EU)
 #define LS_EST_WAVES_PER_EU 4
-#endif
 template <int CTRL> __device__ __forceinline__ float ls_est_dpp(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
 }

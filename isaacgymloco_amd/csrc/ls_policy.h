@@ -385,8 +385,7 @@ static int ls_policy_launch(const lsim_him_policy* p, const float* obs, const fl
         p->critic[1].n_pad > LS_POL_MAX_IN || p->critic[3].n_pad > LS_POL_MAX_IN) bad = 1;
     if (bad) return LSIM_E_UNSUPPORTED;
     // 32 environments per block once that still fills the chip's 256 CUs with one block each; 16 per block (two blocks per CU) below that
-    static const bool force16 = getenv("LSIM_POLICY_ROWS16") != nullptr;      // A/B switch (tools/policy_time.py), read once
-    const bool wide = num_envs >= 2048 && !force16;
+    const bool wide = num_envs >= 2048;
     const int rows = wide ? 32 : 16;
     const size_t lds = (size_t)rows * (LS_POL_STRIDE_IN + LS_POL_STRIDE_A + LS_POL_STRIDE_B) * sizeof(float);
     static size_t configured[4][64] = {{0}};     // per kernel and device: the attribute belongs to the device's copy of the kernel

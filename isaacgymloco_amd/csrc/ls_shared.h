@@ -18,9 +18,7 @@
 // (0.1101 -> 0.1097 ms) and got NaNs in the GPU suite: the two padding floats of a row were never written, and they lie inside Y rows that the solver reads as
 // "holds no row yet" slots (times a zero impulse) -- uninitialised LDS is not finite.  Round 6: ph_body_inertia zeroes them with the row (two LDS stores per
 // body lane and sub-step); interleaved A/B on one lease: flat 0.1103 -> 0.1097 ms, stairs 0.1209 -> 0.1197 (tools/gpu_ab_kernel_a.sh), GPU suite green.
-#ifndef LS_I6_STRIDE
 #define LS_I6_STRIDE 38
-#endif
 #define LS_NV 18
 #define LS_MAXC LSIM_MAX_CONTACTS
 #define LS_MAXR (3 * LSIM_MAX_CONTACTS + LSIM_NUM_DOF)  // 60 <= 64 lanes

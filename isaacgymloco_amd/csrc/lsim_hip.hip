@@ -37,12 +37,11 @@ static void lsbk_prof_free(lsim_sim* s);
 __device__ __forceinline__ int ls_env_of_block(int b, int num_envs) {
     const int l = b >> 3;
     return ((((l >> 5) << 3) + (b & 7)) << 5) + (l & 31);
-    (void)num_envs;
 }
 
 // Kernel A is bound by per-wave latency (dependent VALU chains, LDS round trips at ~19 phase boundaries per sub-step):
 // 4 waves per SIMD (<= 128 VGPRs, no scratch) beat 1-2 waves with more registers by 1.35x at N = 4096, where 4 waves/SIMD is also exactly
-// the whole batch resident at once (4096 waves / 1024 SIMDs; the 9.6 KB LDS struct allows 16 blocks per CU).
+// the whole batch resident at once (4096 waves / 1024 SIMDs; the 10 240 B LDS struct allows 16 blocks per CU).
 // One kernel per solver (lsim_config.solver_type: the host picks at launch), so that neither carries the other's code: lsim_k_step_a_tgs is
 // what every reference config runs (LRC:245), lsim_k_step_a_pgs the build's earlier velocity-level solver.
 #define LS_KERNEL_A(name, SOLVER) \
@@ -222,9 +221,6 @@ extern "C" int lsim_debug_read_phase_ticks(unsigned long long* ticks, unsigned l
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ls_phase_calls), z, sizeof(z));
     return 0;
 }
-#endif
-
-#if defined(LS_PHASE_TIMING)
 // the per-site ticks again by kind of wave ([3][129]: few contacts / many contacts / resetting; last column = waves), read and cleared
 extern "C" int lsim_debug_read_phase_ticks_by(unsigned long long* out) {
     if (hipDeviceSynchronize() != hipSuccess) return 1;

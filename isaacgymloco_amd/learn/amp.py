@@ -449,8 +449,7 @@ def _trunk_fused(trunk, x):
     """the discriminator trunk (Linear, ReLU, Linear, ReLU, ...) through _LinearReluFn; None when the layout / device does not qualify"""
     # only for the update's tall minibatches: at the rollout's 4096 rows the TunableOp-selected plain GEMM + relu is faster than the
     # default-heuristic epilogue GEMM (collection 0.034 -> 0.037 s per iteration when it was used there too)
-    if (not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and len(trunk) % 2 == 0) or x.shape[0] < 16384
-            or os.environ.get("LSIM_AMP_RELU_EPILOGUE") == "0"):
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and len(trunk) % 2 == 0) or x.shape[0] < 16384:
         return None
     mods = list(trunk)
     for i in range(0, len(mods), 2):

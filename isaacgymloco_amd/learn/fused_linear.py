@@ -267,9 +267,10 @@ def _eligible_fused_elu(batch, k_in, n_out):
 
 
 def _fused_forward_wanted(x, k_in):
-    """Default: the library kernel for the hidden layers whose rows are 16-byte aligned -- k_in % 4 == 0 (64 -> 512, 512 -> 256, 256 -> 128, 128 -> 64) or,
-    since round 6, rows an aligned pitch apart (the shuffled 238- / 270-wide observation fields, learn/storage.py: the weights are then zero-padded to the
-    pitch's width, see linear_elu_forward).  Unaligned rows stay on BLAS + torch ELU: their 8- and 4-byte loads double and quadruple the kernel's fetch
+    """Default: the library kernel for the hidden layers whose rows are 16-byte aligned -- k_in % 4 == 0 (64 -> 512, 512 -> 256, 256 -> 128, 128 -> 64) or
+    rows an aligned pitch apart (the shuffled 238- / 270-wide observation fields when LSIM_PAD_SHUFFLED=1 lays them out padded, learn/storage.py -- off by
+    default, so by default those two layers are unaligned; the weights are then zero-padded to the pitch's width, see linear_elu_forward).
+    Unaligned rows stay on BLAS + torch ELU: their 8- and 4-byte loads double and quadruple the kernel's fetch
     instructions, and the fetch is what bounds it (238 -> 512 took 415 us against ~325 for BLAS + ELU in round 5's loop).
     LSIM_ELU_FORWARD=0 / all: A/B switches"""
     mode = os.environ.get("LSIM_ELU_FORWARD", "aligned")

@@ -78,8 +78,9 @@ def tunableop_status(device, table_path=None):
 
 
 def _two_streams_allowed(critic, rows, multi_rank=False, single_device_ranks=False):
-    """May the critic chain of the update run on a side stream, concurrently with the actor / estimator chain?  (LSIM_UPDATE_STREAMS = 0 / 1
-    forces it off / on.)  Two library GEMMs in flight at once are only safe when neither is a kernel whose workgroups wait for each other
+    """May the critic chain of the update run on a side stream, concurrently with the actor / estimator chain?  The automatic
+    rule below is the only rule: no switch forces the answer either way (a forced "on" with an unqualified GEMM table is the configuration
+    that hung the device).  Two library GEMMs in flight at once are only safe when neither is a kernel whose workgroups wait for each other
     (hipBLASLt's default heuristics pick such stream-K style kernels for some of these shapes: with TunableOp off, two concurrent GEMM streams
     hung the device at N = 4096, round 3).  So the automatic answer is yes only when TunableOp is enabled in look-up mode AND it has LOADED an
     explicit (non-"Default") solution for every BLAS GEMM of the critic chain at this minibatch size: forward (tn_), input gradients (nn_)
@@ -91,9 +92,6 @@ def _two_streams_allowed(critic, rows, multi_rank=False, single_device_ranks=Fal
     wait cycle with them, and a 1-rank RCCL group with every collective issued runs both streams (tests/test_bench_cli.py).  What does hang is
     the DEBUG mode with several rank processes on ONE GPU (LSIM_DEBUG_SINGLE_DEVICE, gloo): four GEMM streams of two processes time-sliced on
     one device -- `single_device_ranks` keeps the side stream off there."""
-    mode = os.environ.get("LSIM_UPDATE_STREAMS", "auto")
-    if mode in ("0", "1"):
-        return mode == "1"
     if multi_rank and (single_device_ranks or os.environ.get("LSIM_DEBUG_SINGLE_DEVICE") == "1"):
         return False
     tun = getattr(torch.cuda, "tunable", None)
@@ -343,7 +341,7 @@ class HIMPPO:
         stream never overlaps a collective: the one all-reduce of a minibatch is issued after both streams have joined behind the backward
         pass, and the next minibatch's critic forward is ordered behind the optimiser step that waited for it."""
         memo = self.__dict__.setdefault("_two_stream_decision", {})
-        key = (rows, bool(multi_rank), os.environ.get("LSIM_UPDATE_STREAMS", "auto"))
+        key = (rows, bool(multi_rank))
         if key not in memo:
             ok = _two_streams_allowed(critic, rows, multi_rank)
             if multi_rank:
@@ -558,15 +556,14 @@ class HIMPPO:
                 value = ac.evaluate(critic_obs)
         ac.estimator.prime(obs)        # one encoder forward serves the policy features and the estimator loss below
         early_est = None
-        if two_streams and os.environ.get("LSIM_EARLY_EST_LOSS", "1") != "0":
+        if two_streams:
             # The estimator's loss head -- target encoder, prototype scores, three Sinkhorn rounds, log-softmax, losses and their gradients:
             # ~15 launches that each leave most of the device idle -- depends on the encoder output alone.  Formed HERE, while the critic's
             # GEMMs run on the side stream, it fills what they leave; behind the join it ran by itself (0.27 ms per minibatch).  Same values.
             early_est = ac.estimator.losses(obs, next_critic_obs)
         # the reference calls act() here (HIMP:141) and throws the sample away; torch.normal(mean, std) validates std >= 0 with a
         # host read-back, i.e. one pipeline drain per minibatch on the GPU: only the distribution is needed
-        std_direct = obs.is_cuda and obs.dtype == torch.float32 and ac.std.dim() == 1 and ac.std.numel() <= 60 and \
-            os.environ.get("LSIM_PPO_STD_DIRECT", "1") != "0"
+        std_direct = obs.is_cuda and obs.dtype == torch.float32 and ac.std.dim() == 1 and ac.std.numel() <= 60
         if std_direct:
             # the policy's std is one value per action (HAC:93): the loss kernel takes it as it is (lsim_ppo_loss_std) instead of the
             # broadcast mean * 0 + std the distribution object forms (HAC:147) -- no [B, A] sigma, no backward of the broadcast, no column sum

@@ -154,12 +154,13 @@ class HIMRolloutStorage:
     def _shuffle(self, fields, perm):
         """every field gathered through the permutation.  On the GPU the destinations are PERSISTENT buffers (allocated at the first call):
         minibatch i of every update lives at the same addresses and the update stops allocating 0.4 GB per call.
-        Round 6: the rows of 2-D fields whose width is not a multiple of four floats (the 270-wide observation history, the 238-wide privileged
-        observations) are laid out 16-byte aligned -- row pitch rounded up to 4 floats, the padding zero and never written -- and handed out as
+        Opt-in, LSIM_PAD_SHUFFLED=1 (off by default: measured no gain on the update): the rows of 2-D fields whose width is
+        not a multiple of four floats (the 270-wide observation history, the 238-wide privileged observations) are laid out 16-byte aligned --
+        row pitch rounded up to 4 floats, the padding zero and never written -- and handed out as
         [B, width] VIEWS of the padded buffer: the first layers of the networks then read aligned rows and join the library's fused Linear + ELU
         forward (fused_linear.linear_elu_forward with a zero-padded weight copy) and the 16-byte form of the weight-gradient kernel.  (Round 5
         measured padded rows with the BLAS forward kept: -1 %, the BLAS kernels are TunableOp-selected per leading dimension.)
-        LSIM_PAD_SHUFFLED=0: contiguous rows (A/B switch)."""
+        Default: contiguous rows."""
         if not fields[0].is_cuda:
             return tuple(_gather_rows(f, perm) for f in fields)
         import os

@@ -27,13 +27,13 @@ def rpy_matrix(rpy):
 
 
 
-def _limb_box_points(dims, pos, R, skip_far_end, n=3, span=None, wide=False):
+def _limb_box_points(dims, pos, R, skip_far_end, n=3, span=None):
     """spheres along the long axis of a limb's box; the end away from the joint is left to the child link when skip_far_end.
     span = (t0, t1): n spheres evenly from t0 to t1 of the length instead (the calf rule below)"""
     lengths = dims
     a = int(np.argmax(lengths))
     others = [lengths[k] for k in range(3) if k != a]
-    r = 0.5 * (max(others) if wide else min(others))      # wide: the larger half-width of the cross-section (the calf rule)
+    r = 0.5 * min(others)
     axis = R[:, a]
     L = lengths[a]
     ends = [pos - 0.5 * L * axis, pos + 0.5 * L * axis]

@@ -15,4 +15,4 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record()
 for _ in range(200): pk.forward(obs, priv, mean, val)
 e1.record(); torch.cuda.synchronize()
-print(os.environ.get("LSIM_POLICY_ROWS16", "rows32"), "policy forward us:", e0.elapsed_time(e1) / 200 * 1e3)
+print("policy forward us:", e0.elapsed_time(e1) / 200 * 1e3)
