@@ -342,22 +342,11 @@ def _cols_ws(batch, n, device):
 def _relu_wgrad(x, g, a, weight, bias):
     """(dW, db) of relu(x W^T + b) from the gradient g of its OUTPUT a: the mask is applied to g as the MFMA operand is formed (lsim_linear_relu_wgrad);
     the masked gradient is never written.  Falls back to the torch statements for shapes the library leaves to BLAS."""
-    import ctypes
-    from .. import lib
     from . import fused_linear as FL
-    L = lib.load()
-    batch, k_in = x.shape
-    n_out = weight.shape[0]
-    need, parts = ctypes.c_size_t(), ctypes.c_int()
-    if FL._eligible_fused_elu(batch, k_in, n_out) and L.lsim_linear_wgrad_workspace(batch, k_in, n_out, ctypes.byref(need), ctypes.byref(parts)) == 0:
-        # plain output tensors, summed at once: the discriminator's parameters receive a second contribution from the gradient penalty in the same
-        # backward pass, so their gradient-arena slices (whose deferred sums assume a single contribution, fused_linear._wgrad_call) are not used here
-        ws = FL._workspace("wgrad_relu", x.device, need.value, floor=1 << 20)
-        dw, db = torch.empty(n_out, k_in, device=x.device), torch.empty(n_out, device=x.device)
-        lib.check(L.lsim_linear_relu_wgrad(x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0), a.data_ptr(), a.stride(0), batch, k_in, n_out, dw.data_ptr(),
-                                           db.data_ptr(), None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream),
-                  what="lsim_linear_relu_wgrad")
-        return dw, db
+    if FL._eligible_fused_elu(x.shape[0], x.shape[1], weight.shape[0]):
+        # arena=False -- plain output tensors, summed at once: the discriminator's parameters receive a second contribution from the gradient penalty in
+        # the same backward pass, so their gradient-arena slices (whose deferred sums assume a single contribution, fused_linear._wgrad_call) are not used here
+        return FL._wgrad_launch("relu", x, g, a, None, None, arena=False, ws_kind="wgrad_relu")[:2]
     gy = torch.ops.aten.threshold_backward(g, a, 0.0)
     return gy.t() @ x, gy.sum(dim=0)
 

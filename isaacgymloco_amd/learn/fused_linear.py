@@ -218,29 +218,45 @@ def _eligible(batch, k_in, n_out):
     return ok
 
 
-def linear_wgrad(x, g, want_bias=True, weight_ptr=None, bias_ptr=None):
-    """(g^T x, g.sum(0)) for 2-D fp32 CUDA tensors through lsim_linear_wgrad; weight_ptr / bias_ptr: data_ptr() of the parameters the results
-    are gradients of (GradArena: they are written into the parameters' gradient slices)"""
+def _wgrad_launch(kind, x, g, act_out, weight_ptr, bias_ptr, want_bias=True, want_grad_pre=False, arena=True, ws_kind="wgrad"):
+    """the one weight-gradient launch -> (dw, db or None, grad_pre or None) of act(x W^T + b) from the gradient g of its output.  `kind`: the
+    activation, "none" / "elu" / "relu"; for the last two `act_out` is the saved activation output, whose derivative is applied to g as the MFMA
+    operand is formed (grad_pre = g * act'(act_out) is written out when `want_grad_pre`).  x, g, act_out: 2-D fp32 CUDA, unit column stride.
+    weight_ptr / bias_ptr: data_ptr() of the parameters the results are gradients of.  `arena`: the results may go to those parameters'
+    GradArena slices and, inside a deferred block, wait for the block's one summing launch; else plain tensors, summed at once."""
     from .. import lib
     L = lib.load()
-    if x.stride(1) != 1:
-        x = x.contiguous()
-    if g.stride(1) != 1:
-        g = g.contiguous()
     batch, k_in = x.shape
     n_out = g.shape[1]
     need, waves = ctypes.c_size_t(), ctypes.c_int()
     lib.check(L.lsim_linear_wgrad_workspace(batch, k_in, n_out, ctypes.byref(need), ctypes.byref(waves)), what="lsim_linear_wgrad_workspace")
+    if not arena:
+        weight_ptr = bias_ptr = None
     # inside a deferred block every layer keeps its partial results until the block's one summing launch: a buffer per parameter
-    ws = _workspace("wgrad" if _pending is None else ("wgrad", weight_ptr), x.device, need.value, floor=1 << 20 if _pending is None else 0)
+    per_param = arena and _pending is not None
+    ws = _workspace((ws_kind, weight_ptr) if per_param else ws_kind, x.device, need.value, floor=0 if per_param else 1 << 20)
     hit = [True]
     dw = _grad_out(weight_ptr, (n_out, k_in), x.device, hit)
     db = _grad_out(bias_ptr, (n_out,), x.device, hit) if want_bias else None
-    lib.check(_wgrad_call(L, "lsim_linear_wgrad", "lsim_linear_wgrad_deferred",
-                          (x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0), batch, k_in, n_out, dw.data_ptr(),
-                           db.data_ptr() if want_bias else None, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream),
-                          weight_ptr, ws, (x, g), hit[0] or _defer_without_arena), what="lsim_linear_wgrad")
-    return dw, db
+    grad_pre = torch.empty(batch, n_out, device=x.device, dtype=torch.float32) if want_grad_pre else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    act = () if kind == "none" else (act_out.data_ptr(), act_out.stride(0))
+    args = ((x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0)) + act + (batch, k_in, n_out, dw.data_ptr(), ptr(db))
+            + (() if kind == "none" else (ptr(grad_pre),)) + (ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream))
+    fn = "lsim_linear_wgrad" if kind == "none" else f"lsim_linear_{kind}_wgrad"
+    lib.check(_wgrad_call(L, fn, fn + "_deferred", args, weight_ptr, ws, (x, g) if kind == "none" else (x, g, act_out),
+                          arena and (hit[0] or _defer_without_arena)), what=fn)
+    return dw, db, grad_pre
+
+
+def linear_wgrad(x, g, want_bias=True, weight_ptr=None, bias_ptr=None):
+    """(g^T x, g.sum(0)) for 2-D fp32 CUDA tensors through lsim_linear_wgrad; weight_ptr / bias_ptr: data_ptr() of the parameters the results
+    are gradients of (GradArena: they are written into the parameters' gradient slices)"""
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    if g.stride(1) != 1:
+        g = g.contiguous()
+    return _wgrad_launch("none", x, g, None, weight_ptr, bias_ptr, want_bias)[:2]
 
 
 class _SkinnyLinearFn(torch.autograd.Function):
@@ -332,28 +348,12 @@ class _LinearEluFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import lib
         x, weight, z = ctx.saved_tensors
-        L = lib.load()
         if x.stride(1) != 1:
             x = x.contiguous()
-        g = g.contiguous()
-        batch, k_in = x.shape
-        n_out = weight.shape[0]
-        need, parts = ctypes.c_size_t(), ctypes.c_int()
-        lib.check(L.lsim_linear_wgrad_workspace(batch, k_in, n_out, ctypes.byref(need), ctypes.byref(parts)), what="lsim_linear_wgrad_workspace")
-        wptr = weight.data_ptr()
-        ws = _workspace("wgrad" if _pending is None else ("wgrad", wptr), x.device, need.value, floor=1 << 20 if _pending is None else 0)
-        hit = [True]
-        dw = _grad_out(wptr, (n_out, k_in), x.device, hit)
-        db = _grad_out(ctx.bias_ptr, (n_out,), x.device, hit) if ctx.has_bias else None
         # the gradient of the pre-activation is written out only where an input gradient follows (not for a network's first layer: 210 MB per call)
-        g_pre = torch.empty(batch, n_out, device=x.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        lib.check(_wgrad_call(L, "lsim_linear_elu_wgrad", "lsim_linear_elu_wgrad_deferred",
-                              (x.data_ptr(), x.stride(0), g.data_ptr(), g.stride(0), z.data_ptr(), z.stride(0), batch, k_in, n_out,
-                               dw.data_ptr(), db.data_ptr() if db is not None else None, g_pre.data_ptr() if g_pre is not None else None,
-                               ws.data_ptr(), ws.numel(), torch.cuda.current_stream(x.device).cuda_stream),
-                              wptr, ws, (x, g, z), hit[0]), what="lsim_linear_elu_wgrad")
+        dw, db, g_pre = _wgrad_launch("elu", x, g.contiguous(), z, weight.data_ptr(), ctx.bias_ptr, want_bias=ctx.has_bias,
+                                      want_grad_pre=ctx.needs_input_grad[0])
         gx = g_pre @ weight if g_pre is not None else None
         return gx, dw, db
 

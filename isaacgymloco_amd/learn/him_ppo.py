@@ -21,6 +21,7 @@ import time
 import torch
 import torch.nn as nn
 
+from . import fused_linear as FL
 from .storage import HIMRolloutStorage
 
 
@@ -102,7 +103,6 @@ def _two_streams_allowed(critic, rows, multi_rank=False, single_device_ranks=Fal
     if key not in _two_stream_memo:
         ok = False
         try:
-            from .fused_linear import _eligible
             table = _loaded_tunableop_solutions(next(critic.parameters()).device)
             need = []
             for i, (k, n) in enumerate(dims):
@@ -110,7 +110,7 @@ def _two_streams_allowed(critic, rows, multi_rank=False, single_device_ranks=Fal
                     need.append(f"tn_{n}_{rows}_{k}")                  # forward  y = x W^T (+ bias); a single output column is a GEMV
                 if i > 0:
                     need.append(f"nn_{k}_{rows}_{n}")                  # input gradient  g W
-                if not _eligible(rows, k, n):
+                if not FL._eligible(rows, k, n):
                     need.append(f"nt_{k}_{n}_{rows}")                  # weight gradient  g^T x through BLAS
             ok = bool(table) and all(table.get(sig, "Default") != "Default" for sig in need)
         except Exception:
@@ -155,7 +155,6 @@ class DistCtx:
         the bucket is a PERSISTENT flat buffer that the gradients already live in -- the weight-gradient kernels wrote them there -- so there
         is no concatenation and nothing to re-view afterwards; the few gradients that autograd's own kernels produced are copied into their
         slices by one multi-tensor launch (Bucket.adopt).  Device work only."""
-        from . import fused_linear as FL
         if n_extra is None:
             n_extra = extra.numel() if extra is not None else 0
             extra_at = 0
@@ -281,6 +280,22 @@ class DistCtx:
             self.dist.broadcast(t.data, src=0)
 
 
+class _Minibatch:
+    """what one minibatch of update() carries from its forward to its optimiser steps: _mb_forward fills the first row of slots, _mb_backward the
+    second (the single-rank order: est / swap only); `aux` is the hooks' (HybridPPO: the sampled AMP pairs, then the discriminator's statistics)"""
+    __slots__ = ("obs", "next_critic_obs", "old_mu", "old_sigma", "loss", "mu", "sigma", "kl_mean", "surrogate_loss", "value_loss", "early_est", "aux",
+                 "est", "swap", "est_params", "ppo_params", "kl", "dist", "bucket")
+
+    def step_joint(self, alg, ac, more_params=()):
+        """the optimiser half of one minibatch in the data-parallel order: both backwards, ONE all-reduce of every gradient + the KL estimate,
+        then the same two optimiser steps as the single-rank order (lr rule -> estimator step -> PPO step, HIMP:144-184).  Also the order of
+        the single-rank two-stream path (no collectives).  Three pieces: device work up to the gradients, the collective, device work of
+        the two optimiser steps."""
+        alg._mb_backward(ac, self, more_params)
+        alg._mb_reduce(self)
+        alg._mb_optim(ac, self)
+
+
 class HIMPPO:
     def __init__(self, actor_critic, num_learning_epochs=1, num_mini_batches=1, clip_param=0.2, gamma=0.998, lam=0.95,
                  value_loss_coef=1.0, entropy_coef=0.0, learning_rate=1e-3, max_grad_norm=1.0, use_clipped_value_loss=True,
@@ -326,7 +341,6 @@ class HIMPPO:
     def _grad_arena(self, more_params=()):
         """persistent gradient buckets on the GPU (fused_linear.GradArena), created at the first update: the estimator's parameters + one slot
         for the KL estimate, and everything else the PPO optimiser steps (+ `more_params`: HybridPPO's discriminator)"""
-        from . import fused_linear as FL
         ac = self.actor_critic
         if getattr(self, "_arena", None) is None:
             if not next(ac.parameters()).is_cuda or os.environ.get("LSIM_GRAD_ARENA", "1") == "0":
@@ -357,10 +371,8 @@ class HIMPPO:
     def _clip_and_step(self, optimizer, params, max_grad_norm):
         """clip_grad_norm_ + optimizer.step() (HIMP:183-184); on the device-lr fast path one C-ABI call of two launches"""
         params = list(params)
-        if self._lr_t is not None:
-            from .fused_linear import adam_clip_step_hip
-            if adam_clip_step_hip(optimizer, max_grad_norm, clip_params=params):
-                return
+        if self._lr_t is not None and FL.adam_clip_step_hip(optimizer, max_grad_norm, clip_params=params):
+            return
         nn.utils.clip_grad_norm_(params, max_grad_norm)
         optimizer.step()
 
@@ -442,9 +454,8 @@ class HIMPPO:
         """(total loss, surrogate, value loss, KL mean or None) of HIMP:136-176.  On the GPU one HIP kernel (lsim_ppo_loss: forward, backward
         and the KL estimate of the adaptive-lr rule in a single pass); elsewhere the reference's torch statement."""
         if mu.is_cuda and mu.dtype == torch.float32:
-            from .fused_linear import ppo_loss_hip
-            loss, st = ppo_loss_hip(mu, sigma, value, actions, old_logp, advantages, returns, target_values, old_mu, old_sigma, self.clip_param,
-                                    self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, out=self._stats_slot())
+            loss, st = FL.ppo_loss_hip(mu, sigma, value, actions, old_logp, advantages, returns, target_values, old_mu, old_sigma, self.clip_param,
+                                       self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss, out=self._stats_slot())
             return loss, st[0], st[1], st[3]
         logp = ac.get_actions_log_prob(actions)
         entropy = ac.entropy
@@ -466,67 +477,56 @@ class HIMPPO:
         b = self._arena.buckets.get("all")
         return b.extra_view if b is not None and b.extra == 5 else None
 
-    def _step_minibatch_data_parallel(self, ac, obs, next_critic_obs, loss, mu, sigma, old_mu, old_sigma, kl_mean, adaptive, more_params=(),
-                                      est_losses=None):
-        """the optimiser half of one minibatch in the data-parallel order: both backwards, ONE all-reduce of every gradient + the KL estimate,
-        then the same two optimiser steps as the single-rank order (lr rule -> estimator step -> PPO step, HIMP:144-184).  Also the order of
-        the single-rank two-stream path (no collectives).  Returns the estimator's (estimation, swap) losses.  Three pieces: device work
-        up to the gradients, the collective, device work of the two optimiser steps."""
-        st = self._mb_backward(ac, obs, next_critic_obs, loss, mu, sigma, old_mu, old_sigma, kl_mean, adaptive, more_params, est_losses)
-        self._mb_reduce(st)
-        self._mb_optim(ac, st)
-        return st["est"], st["swap"]
+    @property
+    def _adaptive(self):
+        return self.desired_kl is not None and self.schedule == "adaptive"
 
-    def _mb_backward(self, ac, obs, next_critic_obs, loss, mu, sigma, old_mu, old_sigma, kl_mean, adaptive, more_params=(), est_losses=None):
+    def _mb_backward(self, ac, mb, more_params=()):
         """piece 1: both backward passes; every gradient and the KL estimate end up in the arena bucket (GPU) / a flat tensor (CPU)"""
-        from . import fused_linear as FL
         ctx, est_mod = self.dist_ctx, ac.estimator
         if ctx is not None and not ctx.enabled:
             ctx = None                                               # single rank: same order, no collectives (the two-stream path of update())
         est_params = list(est_mod.parameters())
         self.optimizer.zero_grad()                                   # every parameter of the optimiser, the estimator's included
         FL.grad_cycle()
-        # est_losses: the estimator's losses when update() already formed them (before the critic's stream was joined)
-        est, swap, total = est_losses if est_losses is not None else est_mod.losses(obs, next_critic_obs)
+        # early_est: the estimator's losses when _mb_forward already formed them (before the critic's stream was joined)
+        est, swap, total = mb.early_est if mb.early_est is not None else est_mod.losses(mb.obs, mb.next_critic_obs)
         est_mod._primed = None
         with FL.deferred_wgrad_reduce():                             # one summing launch for the partial results of all ~15 layers
-            FL.backward_losses(total, loss)                          # estimator; actor / critic / std gradients
+            FL.backward_losses(total, mb.loss)                       # estimator; actor / critic / std gradients
         extra = None
-        if adaptive:
-            extra = kl_mean if kl_mean is not None else self._local_kl(mu, sigma, old_mu, old_sigma)
+        if self._adaptive:
+            extra = mb.kl_mean if mb.kl_mean is not None else self._local_kl(mb.mu, mb.sigma, mb.old_mu, mb.old_sigma)
         # `more_params`: parameters outside the actor-critic that the same optimiser steps (HybridPPO: the discriminator) -- reduced in the same
         # bucket, not clipped (HYBP:270 clips the actor-critic only)
         est_live = [p for p in est_params if p.grad is not None]
         est_ids = {id(p) for p in est_params}
         ppo_params = [p for p in ac.parameters() if p.grad is not None and id(p) not in est_ids]
         more = [p for p in more_params if p.grad is not None]
-        st = dict(est=est.detach(), swap=swap.detach(), est_params=est_params, ppo_params=ppo_params, adaptive=adaptive, kl=extra,
-                  dist=(mu, sigma, old_mu, old_sigma) if self._lr_t is None else None, bucket=None)
+        mb.est, mb.swap, mb.est_params, mb.ppo_params, mb.kl, mb.bucket = est.detach(), swap.detach(), est_params, ppo_params, extra, None
+        mb.dist = (mb.mu, mb.sigma, mb.old_mu, mb.old_sigma) if self._lr_t is None else (None,) * 4
         if ctx is not None:
             slot = self._stats_slot()
             in_place = slot is not None and extra is not None and extra.data_ptr() == slot[3:4].data_ptr()     # the loss kernel already wrote it there
-            st["bucket"] = ctx.prepare_bucket(est_live + ppo_params + more, extra=None if in_place else extra, key="all",
-                                              n_extra=5 if (extra is not None and extra.is_cuda) else None, extra_at=3)
+            mb.bucket = ctx.prepare_bucket(est_live + ppo_params + more, extra=None if in_place else extra, key="all",
+                                           n_extra=5 if (extra is not None and extra.is_cuda) else None, extra_at=3)
         elif self._grad_arena() is not None:                         # single rank: the same bucket, so that the optimisers' pointer tables repeat
             self._arena.bucket("all", est_live + ppo_params + more, 0).adopt()
-        return st
 
-    def _mb_reduce(self, st):
+    def _mb_reduce(self, mb):
         """piece 2: the minibatch's ONE collective (clip AFTER the all-reduce, HIMP:183)"""
-        if st["bucket"] is None:
+        if mb.bucket is None:
             return
         ctx = self.dist_ctx
-        got = ctx.finish_bucket(ctx.start_reduce(st["bucket"]))
-        if st["kl"] is not None:
-            st["kl"] = got[3:4] if got.numel() == 5 else got
+        got = ctx.finish_bucket(ctx.start_reduce(mb.bucket))
+        if mb.kl is not None:
+            mb.kl = got[3:4] if got.numel() == 5 else got
 
-    def _mb_optim(self, ac, st):
+    def _mb_optim(self, ac, mb):
         """piece 3: learning-rate rule, the estimator's clipped step, the PPO group's clipped step"""
-        from . import fused_linear as FL
         est_mod = ac.estimator
-        if st["adaptive"]:
-            mu, sigma, old_mu, old_sigma = st["dist"] if st["dist"] is not None else (None,) * 4
-            self._adapt_lr(mu, sigma, old_mu, old_sigma, st["kl"].reshape(()), already_global=True)
+        if self._adaptive:
+            self._adapt_lr(*mb.dist, mb.kl.reshape(()), already_global=True)
         if self._lr_t is None:                                       # host learning rate: the estimator steps with the PPO rate (HIMP:158)
             est_mod.learning_rate = self.learning_rate
             for g in est_mod.optimizer.param_groups:
@@ -535,14 +535,32 @@ class HIMPPO:
         if est_mod.fused_step:
             stepped = FL.adam_clip_step_hip(est_mod.optimizer, est_mod.max_grad_norm)
         if not stepped:
-            nn.utils.clip_grad_norm_(st["est_params"], est_mod.max_grad_norm)
+            nn.utils.clip_grad_norm_(mb.est_params, est_mod.max_grad_norm)
             est_mod.optimizer.step()
-        for p in st["est_params"]:                                   # the PPO optimiser also holds these parameters: as in the reference
+        for p in mb.est_params:                                      # the PPO optimiser also holds these parameters: as in the reference
             p.grad = None                                            # (zero_grad before the PPO backward) it must not step them
-        self._clip_and_step(self.optimizer, st["ppo_params"], self.max_grad_norm)
+        self._clip_and_step(self.optimizer, mb.ppo_params, self.max_grad_norm)
+
+    def _mb_step_single_rank(self, ac, mb, bucket_params, clip_params):
+        """the optimiser half of one minibatch in the reference's own order (HIMP:144-184).  `bucket_params`: what the PPO optimiser steps --
+        its gradients share the arena bucket "ppo"; `clip_params`: what the gradient norm is clipped over."""
+        if self._adaptive:
+            self._adapt_lr(mb.mu, mb.sigma, mb.old_mu, mb.old_sigma, mb.kl_mean)
+        mb.est, mb.swap = ac.estimator.update(mb.obs, mb.next_critic_obs, lr=None if self._lr_t is not None else self.learning_rate)
+        self._extra_losses(mb)                                       # behind the estimator's step in this order, see update()
+        self.optimizer.zero_grad()
+        FL.grad_cycle()
+        with FL.deferred_wgrad_reduce():
+            FL.backward_losses(mb.loss)
+        if FL._arena is not None:
+            FL._arena.bucket("ppo", [p for p in bucket_params if p.grad is not None]).adopt()
+        self._clip_and_step(self.optimizer, clip_params, self.max_grad_norm)
+
+    _std_direct = True             # _mb_forward may hand the loss kernel the policy's per-action std itself (lsim_ppo_loss_std) ...
+    _two_stream_forward = True     # ... and run the critic chain on a side stream where _two_streams() allows it (both off in HybridPPO)
 
     def _mb_forward(self, ac, batch, two_streams):
-        """forward of one minibatch up to the two losses (HIMP:136-176 and the estimator's loss head) -> dict"""
+        """forward of one minibatch up to the two losses (HIMP:136-176 and the estimator's loss head) -> _Minibatch"""
         (obs, critic_obs, actions, next_critic_obs, target_values, advantages, returns, old_logp, old_mu, old_sigma) = batch
         if two_streams:
             # The critic chain (forward here, backward inside loss.backward(): autograd runs a node on the stream of its forward) goes to a
@@ -555,15 +573,16 @@ class HIMPPO:
             with torch.cuda.stream(side):
                 value = ac.evaluate(critic_obs)
         ac.estimator.prime(obs)        # one encoder forward serves the policy features and the estimator loss below
-        early_est = None
+        mb = _Minibatch()
+        mb.obs, mb.next_critic_obs, mb.old_mu, mb.old_sigma, mb.early_est = obs, next_critic_obs, old_mu, old_sigma, None
         if two_streams:
             # The estimator's loss head -- target encoder, prototype scores, three Sinkhorn rounds, log-softmax, losses and their gradients:
             # ~15 launches that each leave most of the device idle -- depends on the encoder output alone.  Formed HERE, while the critic's
             # GEMMs run on the side stream, it fills what they leave; behind the join it ran by itself (0.27 ms per minibatch).  Same values.
-            early_est = ac.estimator.losses(obs, next_critic_obs)
+            mb.early_est = ac.estimator.losses(obs, next_critic_obs)
         # the reference calls act() here (HIMP:141) and throws the sample away; torch.normal(mean, std) validates std >= 0 with a
         # host read-back, i.e. one pipeline drain per minibatch on the GPU: only the distribution is needed
-        std_direct = obs.is_cuda and obs.dtype == torch.float32 and ac.std.dim() == 1 and ac.std.numel() <= 60
+        std_direct = self._std_direct and obs.is_cuda and obs.dtype == torch.float32 and ac.std.dim() == 1 and ac.std.numel() <= 60
         if std_direct:
             # the policy's std is one value per action (HAC:93): the loss kernel takes it as it is (lsim_ppo_loss_std) instead of the
             # broadcast mean * 0 + std the distribution object forms (HAC:147) -- no [B, A] sigma, no backward of the broadcast, no column sum
@@ -577,48 +596,61 @@ class HIMPPO:
             value.record_stream(cur)
         else:
             value = ac.evaluate(critic_obs)
-        mu, sigma = (mu_direct, ac.std) if std_direct else (ac.action_mean, ac.action_std)
-        loss, surrogate_loss, value_loss, kl_mean = self._ppo_loss(ac, mu, sigma, value, actions, old_logp, advantages, returns, target_values,
-                                                                   old_mu, old_sigma)
-        return dict(obs=obs, next_critic_obs=next_critic_obs, loss=loss, mu=mu, sigma=sigma, old_mu=old_mu, old_sigma=old_sigma, kl_mean=kl_mean,
-                    surrogate_loss=surrogate_loss, value_loss=value_loss, early_est=early_est)
+        mb.mu, mb.sigma = (mu_direct, ac.std) if std_direct else (ac.action_mean, ac.action_std)
+        mb.loss, mb.surrogate_loss, mb.value_loss, mb.kl_mean = self._ppo_loss(ac, mb.mu, mb.sigma, value, actions, old_logp, advantages, returns,
+                                                                               target_values, old_mu, old_sigma)
+        return mb
+
+    # ---- the hooks of update(): what a learner with more losses in the same optimiser overrides (HybridPPO) ----
+    _n_stats = 4                   # width of _stats_row
+
+    def _sample_stream(self):
+        """(storage minibatch, whatever else _extra_losses needs for it) per minibatch of the update"""
+        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+            yield batch, None
+
+    def _extra_losses(self, mb):
+        """add the learner's further losses to mb.loss -> the parameters outside the actor-critic they reach (the same optimiser steps them)"""
+        return ()
+
+    def _after_step(self, ac, mb):
+        """behind the optimiser steps of a minibatch"""
+
+    def _stats_row(self, mb):
+        return mb.value_loss.detach(), mb.surrogate_loss.detach(), mb.est, mb.swap
+
+    def _result(self, means, mb):
+        # the reference returns the LAST minibatch's estimator losses in slots 3 and 4 (HIMP:198)
+        return means[0], means[1], float(mb.est), float(mb.swap)
 
     def update(self):
+        """the one minibatch loop of both learners.  Two orders of the optimiser half: the reference's own (_mb_step_single_rank) and the joint
+        one of the data-parallel and two-stream paths (_Minibatch.step_joint).  _extra_losses is enqueued where HybridPPO's discriminator
+        forward has always been: behind the estimator's step in the first, before both backward passes in the second."""
         ac = self.actor_critic
         t_enqueue = time.perf_counter()
         self._grad_arena()
-        sums = torch.zeros(4, device=self.device)
-        last_est = last_swap = None
-        adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-        for batch in self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
+        sums = torch.zeros(self._n_stats, device=self.device)
+        dist_on = self.dist_ctx is not None and self.dist_ctx.enabled
+        for batch, aux in self._sample_stream():
             obs = batch[0]
-            multi_rank = self.dist_ctx is not None and self.dist_ctx.enabled and self.dist_ctx.world > 1
-            two_streams = obs.is_cuda and self._lr_t is not None and self._two_streams(ac.critic, obs.shape[0], multi_rank)
-            f = self._mb_forward(ac, batch, two_streams)
-            if (self.dist_ctx is not None and self.dist_ctx.enabled) or two_streams:
-                est, swap = self._step_minibatch_data_parallel(ac, obs, f["next_critic_obs"], f["loss"], f["mu"], f["sigma"], f["old_mu"], f["old_sigma"],
-                                                               f["kl_mean"], adaptive, est_losses=f["early_est"])
+            two_streams = (self._two_stream_forward and obs.is_cuda and self._lr_t is not None
+                           and self._two_streams(ac.critic, obs.shape[0], dist_on and self.dist_ctx.world > 1))
+            mb = self._mb_forward(ac, batch, two_streams)
+            mb.aux = aux
+            if dist_on or two_streams:
+                mb.step_joint(self, ac, self._extra_losses(mb))
             else:
-                if adaptive:
-                    self._adapt_lr(f["mu"], f["sigma"], f["old_mu"], f["old_sigma"], f["kl_mean"])
-                est, swap = ac.estimator.update(obs, f["next_critic_obs"], lr=None if self._lr_t is not None else self.learning_rate)
-                self.optimizer.zero_grad()
-                from . import fused_linear as FL
-                FL.grad_cycle()
-                with FL.deferred_wgrad_reduce():
-                    FL.backward_losses(f["loss"])
-                if FL._arena is not None:
-                    FL._arena.bucket("ppo", [p for p in ac.parameters() if p.grad is not None]).adopt()
-                self._clip_and_step(self.optimizer, ac.parameters(), self.max_grad_norm)
-            sums += torch.stack((f["value_loss"].detach(), f["surrogate_loss"].detach(), est, swap))
-            last_est, last_swap = est, swap
+                # the bucket holds everything the optimiser steps (HybridPPO: the discriminator too); the clip is over the actor-critic only (HYBP:270)
+                self._mb_step_single_rank(ac, mb, [p for g in self.optimizer.param_groups for p in g["params"]], ac.parameters())
+            self._after_step(ac, mb)
+            sums += torch.stack(self._stats_row(mb))
         n = self.num_learning_epochs * self.num_mini_batches
         # host time to ENQUEUE the update (no read-back before this point): against the update's wall time it says whether the device or the
         # host's launch rate bounds it (bench line: update_host_enqueue_s)
         self.update_enqueue_s = time.perf_counter() - t_enqueue
         if self._lr_t is not None:
             self.learning_rate = float(self._lr_t)       # one read-back per update (logging, checkpoints)
-        sums = (sums / n).tolist()
+        means = (sums / n).tolist()
         self.storage.clear()
-        # the reference returns the LAST minibatch's estimator losses in slots 3 and 4 (HIMP:198)
-        return sums[0], sums[1], float(last_est), float(last_swap)
+        return self._result(means, mb)

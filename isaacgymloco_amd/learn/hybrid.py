@@ -8,7 +8,6 @@ transition pairs go to a 1 M-entry replay buffer (HYBP:144-145).  The update add
 HYBP:252-273), clamps std >= min_std (HYBP:276-277) and feeds the running normaliser with the *normalised* policy /
 expert states exactly like the reference does (HYBP:236-241, HYBP:279-281).
 """
-import time
 import torch
 import torch.nn as nn
 
@@ -46,66 +45,43 @@ class HybridPPO(HIMPPO):
         self.amp_transition.clear()
         super().process_env_step(rewards, dones, infos, next_critic_obs)
 
-    def update(self):
-        ac, disc, dev = self.actor_critic, self.discriminator, self.device
-        n_updates = self.num_learning_epochs * self.num_mini_batches
-        mb = self.storage.num_envs * self.storage.num_transitions_per_env // self.num_mini_batches
-        sums = torch.zeros(6, device=dev)
-        est = swap = None
-        t_enqueue = time.perf_counter()
-        self._grad_arena()
-        gens = zip(self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs),
-                   self.amp_storage.feed_forward_generator(n_updates, mb), self.amp_data.feed_forward_generator(n_updates, mb))
-        for sample, (pol_s, pol_ns), (exp_s_raw, exp_ns_raw) in gens:
-            obs, critic_obs, actions, next_critic_obs, target_values, advantages, returns, old_logp, old_mu, old_sigma = sample
-            ac.estimator.prime(obs)        # one encoder forward serves the policy features and the estimator loss below
-            # the reference calls act() here (HIMP:141) and throws the sample away; torch.normal(mean, std) validates std >= 0 with a
-            # host read-back, i.e. one pipeline drain per minibatch on the GPU: only the distribution is needed
-            if obs.is_cuda:
-                ac.update_distribution(obs)
-            else:
-                ac.act(obs)
-            value = ac.evaluate(critic_obs)
-            mu, sigma = ac.action_mean, ac.action_std
-            ppo_loss, surrogate_loss, value_loss, kl_mean = self._ppo_loss(ac, mu, sigma, value, actions, old_logp, advantages, returns, target_values,
-                                                                           old_mu, old_sigma)
-            adaptive = self.desired_kl is not None and self.schedule == "adaptive"
-            dist_on = self.dist_ctx is not None and self.dist_ctx.enabled
-            if not dist_on:
-                if adaptive:
-                    self._adapt_lr(mu, sigma, old_mu, old_sigma, kl_mean)
-                est, swap = ac.estimator.update(obs, next_critic_obs, lr=None if self._lr_t is not None else self.learning_rate)
-            # normalise + concatenate the sampled pairs (HYBP:247-251, DISC:57): three launches on the GPU (AMPDiscriminator.pair_inputs)
-            expert_in, policy_in, expert_raw, exp_s, pol_s = disc.pair_inputs(exp_s_raw, exp_ns_raw, pol_s, pol_ns, self.amp_normalizer)
-            # (exp_s, pol_s: the NORMALISED states -- what the reference feeds its normaliser at the end of the minibatch, HYBP:279-281)
-            amp_loss, policy_d_mean, expert_d_mean = disc.lsgan_loss(expert_in, policy_in)   # HYBP:252-261
-            grad_pen = disc.compute_grad_pen(exp_s_raw, exp_ns_raw, lambda_=10, pair=expert_raw)     # on the un-normalised expert pair (HYBP:262-263)
-            loss = ppo_loss + amp_loss + grad_pen
-            if dist_on:      # two collectives per minibatch, the estimator's in flight during this backward (him_ppo.py)
-                est, swap = self._step_minibatch_data_parallel(ac, obs, next_critic_obs, loss, mu, sigma, old_mu, old_sigma, kl_mean, adaptive,
-                                                               more_params=list(disc.parameters()))
-            else:
-                self.optimizer.zero_grad()
-                from . import fused_linear as FL
-                FL.grad_cycle()
-                with FL.deferred_wgrad_reduce():
-                    loss.backward()
-                if FL._arena is not None:
-                    FL._arena.bucket("ppo", [p for g in self.optimizer.param_groups for p in g["params"] if p.grad is not None]).adopt()
-                self._clip_and_step(self.optimizer, ac.parameters(), self.max_grad_norm)     # HYBP:270-273: clipping over the actor-critic only
-            if self.min_std is not None:
-                ac.std.data = ac.std.data.clamp(min=self.min_std)
-            if self.amp_normalizer is not None:
-                self.amp_normalizer.update(pol_s)
-                self.amp_normalizer.update(exp_s)
-            sums += torch.stack((value_loss.detach(), surrogate_loss.detach(), amp_loss.detach(), grad_pen.detach(),
-                                 policy_d_mean, expert_d_mean))
-        self.update_enqueue_s = time.perf_counter() - t_enqueue      # (him_ppo.HIMPPO.update: host time to enqueue, no read-back before here)
-        if self._lr_t is not None:
-            self.learning_rate = float(self._lr_t)
-        s = (sums / n_updates).tolist()
-        self.storage.clear()
-        return s[0], s[1], float(est), float(swap), s[2], s[3], s[4], s[5]
+    # The AMP update has only ever run -- and been measured with -- the plain forward: the distribution object's [B, A] sigma, one stream.
+    # Enabling either switch is a separate, measured change, not a side effect of sharing HIMPPO's loop.
+    _std_direct = False
+    _two_stream_forward = False
+    _n_stats = 6
+
+    def _sample_stream(self):
+        n_updates, rows = self.num_learning_epochs * self.num_mini_batches, self.storage.num_envs * self.storage.num_transitions_per_env // self.num_mini_batches
+        for sample, policy_pair, expert_pair in zip(self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs),
+                                                    self.amp_storage.feed_forward_generator(n_updates, rows),
+                                                    self.amp_data.feed_forward_generator(n_updates, rows)):
+            yield sample, (policy_pair, expert_pair)
+
+    def _extra_losses(self, mb):
+        disc = self.discriminator
+        (pol_s, pol_ns), (exp_s_raw, exp_ns_raw) = mb.aux
+        # normalise + concatenate the sampled pairs (HYBP:247-251, DISC:57): three launches on the GPU (AMPDiscriminator.pair_inputs)
+        expert_in, policy_in, expert_raw, exp_s, pol_s = disc.pair_inputs(exp_s_raw, exp_ns_raw, pol_s, pol_ns, self.amp_normalizer)
+        # (exp_s, pol_s: the NORMALISED states -- what the reference feeds its normaliser at the end of the minibatch, HYBP:279-281)
+        amp_loss, policy_d_mean, expert_d_mean = disc.lsgan_loss(expert_in, policy_in)   # HYBP:252-261
+        grad_pen = disc.compute_grad_pen(exp_s_raw, exp_ns_raw, lambda_=10, pair=expert_raw)     # on the un-normalised expert pair (HYBP:262-263)
+        mb.loss = mb.loss + amp_loss + grad_pen
+        mb.aux = (pol_s, exp_s, amp_loss.detach(), grad_pen.detach(), policy_d_mean, expert_d_mean)
+        return disc.parameters()
+
+    def _after_step(self, ac, mb):
+        if self.min_std is not None:
+            ac.std.data = ac.std.data.clamp(min=self.min_std)
+        if self.amp_normalizer is not None:
+            self.amp_normalizer.update(mb.aux[0])
+            self.amp_normalizer.update(mb.aux[1])
+
+    def _stats_row(self, mb):
+        return (mb.value_loss.detach(), mb.surrogate_loss.detach()) + mb.aux[2:]
+
+    def _result(self, means, mb):
+        return means[0], means[1], float(mb.est), float(mb.swap), means[2], means[3], means[4], means[5]
 
 
 class HybridPolicyRunner(HIMOnPolicyRunner):
