@@ -42,7 +42,8 @@ extern "C" {
                                     version-7 header runs unchanged): lsim_raycast + lsim_raycast_sizes (range sensors: rays against the terrain mesh);
                                     lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot);
                                     lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise);
-                                    lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only) */
+                                    lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only);
+                                    lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1120,8 +1121,8 @@ typedef struct lsim_sensor_model {
  * clip_lo > clip_hi; a flag bit other than the two above; both of them set. */
 int lsim_sensor_capture(const lsim_sensor_model_t* sm, void* stream);
 
-/* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (training runs the same
- * parameters through torch; isaacgymloco_amd/learn/depth_encoder.py).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no
+/* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
+ * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no
  * host synchronisation, raw pointers only, so it can be captured in a graph.  It reads `hist` (and episode_length for the due rule), the
  * parameters where the caller keeps them, and writes `latent`; nothing else.
  *
@@ -1180,6 +1181,74 @@ int lsim_depth_encode_sizes(const lsim_depth_encoder_t* de, size_t* lds_bytes);
  * outside 0..1; latent_stride < latent_dim or not a multiple of 4; the LDS bytes above the limit; tick < 0; period < 1; stagger outside 0..1;
  * a flag bit other than the sensor model's two; both of them set. */
 int lsim_depth_encode(const lsim_depth_encoder_t* de, void* stream);
+
+/* ---- depth encoder, BACKWARD: the gradients of the six parameters from the gradient of `latent`, for a batch of images.  Same rules as every
+ * launch here: the caller's stream, no host synchronisation, raw pointers only, capturable in a graph.  THREE launches per call, whatever the
+ * extents and the data.  It reads the frames, the parameters, `g` and `latent`, and writes the six gradient buffers and the workspace; nothing else.
+ *
+ * Input.  The frames are addressed as lsim_depth_encode's hist -- x[b][f][y][x] = hist[(b * hist_slots + f) * hist_stride + y * width + x] -- so a
+ *   sensor's history and a contiguous [B, frames, H * W] batch (hist_slots = frames, hist_stride = H * W when that is a multiple of 4) both fit.
+ *   `latent` [B, latent_stride] is lsim_depth_encode's output for the same rows and parameters; g [B, g_stride] is the gradient of the loss with
+ *   respect to it.  a1, a2 are the forward's activations (recomputed; never stored in memory).  ELU'(a) = a > 0 ? 1 : a + 1 in terms of the
+ *   OUTPUT a of ELU (it equals exp(pre): continuous and 1-Lipschitz in a).
+ * Gradients.
+ *     dz[b][o]   = final_act ? g[b][o] * ELU'(latent[b][o]) : g[b][o]
+ *     gb3[o]     = sum_b dz[b][o]
+ *     gw3[o][j]  = sum_b dz[b][o] * a2[b][j]                                   j = (c * h2 + y) * w2 + x
+ *     da2[b][j]  = sum_o w3[o][j] * dz[b][o]
+ *     d2         = da2 * ELU'(a2)
+ *     gb2[c]     = sum_{b,y,x} d2[b][c][y][x]
+ *     gw2[c][d][i][j] = sum_{b,y,x} d2[b][c][y][x] * a1[b][d][y*s2+i][x*s2+j]
+ *     da1[b][d][Y][X] = sum_{c,i,j,y,x : y*s2+i = Y, x*s2+j = X} w2[c][d][i][j] * d2[b][c][y][x]
+ *     d1         = da1 * ELU'(a1)
+ *     gb1[c]     = sum_{b,y,x} d1[b][c][y][x]
+ *     gw1[c][f][i][j] = sum_{b,y,x} d1[b][c][y][x] * x[b][f][y*s1+i][x*s1+j]
+ *   Every sum is fp32 and a product and a sum may be fused; the ORDER of every sum is a function of the extents, `batch` and the number of
+ *   workgroups (below) only, so two calls with the same inputs write the same bits.  There is no gradient with respect to the frames.
+ *   The six outputs have the parameters' own contiguous layouts and are WRITTEN, not accumulated into.  A non-finite input: unspecified result.
+ * Workgroups.  W = min(batch, the kernel's own choice -- a function of the extents, at most 256 --, and grid_limit when that is > 0) workgroups
+ *   share the samples: workgroup k takes batch / W consecutive samples, the first batch % W workgroups one more, and keeps one partial sum of
+ *   gw1 | gb1 | gw2 | gb2 in the workspace; the partial sums are added in the order of k.
+ * Workspace.  lsim_depth_encode_backward_sizes states the bytes: 4 * batch * (c2*h2*w2 + latent_dim) -- a2 and dz of every row, for gw3 and gb3 --
+ *   plus the partial sums of the largest W the extents and grid_limit allow, which does not grow with batch.  No buffer of the size of a1 exists. */
+typedef struct lsim_depth_encoder_bwd {
+    const float* hist;                /* [B, hist_slots, hist_stride], read only, 16-byte aligned */
+    const float* w1;                  /* the parameters, as in lsim_depth_encoder_t, 4-byte aligned */
+    const float* b1;
+    const float* w2;
+    const float* b2;
+    const float* w3;
+    const float* b3;
+    const float* g;                   /* [B, g_stride]: d loss / d latent, 4-byte aligned */
+    const float* latent;              /* [B, latent_stride]: the forward's output of the same rows, 4-byte aligned */
+    float* gw1;                       /* [c1][frames][k1][k1], 4-byte aligned like every gradient */
+    float* gb1;                       /* [c1] */
+    float* gw2;                       /* [c2][c1][k2][k2] */
+    float* gb2;                       /* [c2] */
+    float* gw3;                       /* [latent_dim][c2 * h2 * w2] */
+    float* gb3;                       /* [latent_dim] */
+    void* workspace;                  /* 16-byte aligned, workspace_bytes >= what lsim_depth_encode_backward_sizes reports */
+    uint64_t workspace_bytes;
+    int32_t hist_stride, hist_slots;  /* as in lsim_depth_encoder_t */
+    int32_t batch;                    /* B >= 1 */
+    int32_t height, width, frames;
+    int32_t c1, k1, s1;
+    int32_t c2, k2, s2;
+    int32_t latent_dim, final_act;
+    int32_t g_stride, latent_stride;  /* floats between rows: >= latent_dim */
+    int32_t grid_limit;               /* 0: the kernel's own choice; n >= 1: at most n workgroups share the samples */
+} lsim_depth_encoder_bwd_t;
+/* bytes of dynamic LDS of the per-sample launch and of the workspace (only batch, the extents and grid_limit are read).  LSIM_E_INVALID: a NULL
+ * argument, batch < 1, grid_limit < 0, an extent out of range as for lsim_depth_encode_sizes, or more LDS than LSIM_DEPTH_ENC_MAX_LDS_BYTES:
+ *   4 * (frames*height*width + c1*h1*w1 + c2*h2*w2 + latent_dim, each rounded up to a multiple of 4, + frames*k1*k1 + c1*k2*k2 + h1*w1 + h2*w2)
+ *   plus a few hundred bytes for the launch's own arguments */
+int lsim_depth_encode_backward_sizes(const lsim_depth_encoder_bwd_t* db, size_t* lds_bytes, size_t* workspace_bytes);
+/* the launches described above.  LSIM_E_INVALID, checked on the host before anything is launched or written: db == NULL; hist NULL or not
+ * 16-byte aligned; a parameter, a gradient, g or latent NULL or not 4-byte aligned; workspace NULL or not 16-byte aligned; workspace_bytes below
+ * what _sizes reports; batch < 1; grid_limit < 0; height, width or frames < 1; frames > hist_slots; hist_slots > LSIM_SENSOR_MAX_HISTORY;
+ * height * width > hist_stride; hist_stride not a multiple of 4; c1, c2 outside 1..64; k1, k2 outside 1..8; s1, s2 outside 1..4; k1 > height or
+ * width; k2 > h1 or w1; latent_dim outside 1..256; final_act outside 0..1; g_stride or latent_stride < latent_dim; the LDS bytes above the limit. */
+int lsim_depth_encode_backward(const lsim_depth_encoder_bwd_t* db, void* stream);
 
 #ifdef __cplusplus
 }

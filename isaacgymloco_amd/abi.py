@@ -110,6 +110,7 @@ LsimRaycastRobot = STRUCTS["lsim_raycast_robot"]
 LsimRaycastPrim = STRUCTS["lsim_raycast_prim"]
 LsimSensorModel = STRUCTS["lsim_sensor_model_t"]
 LsimDepthEncoder = STRUCTS["lsim_depth_encoder_t"]
+LsimDepthEncoderBwd = STRUCTS["lsim_depth_encoder_bwd_t"]
 
 REWARD_IDS = {k[len("LSIM_R_"):].lower(): v for k, v in ENUMS["lsim_reward_id"].items() if k.startswith("LSIM_R_")}
 NUM_REWARD_TERMS = ENUMS["lsim_reward_id"]["LSIM_NUM_REWARD_TERMS"]

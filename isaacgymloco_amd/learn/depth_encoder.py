@@ -5,14 +5,18 @@
     cam.attach_encoder(enc)                 # from now on every capture is followed by ONE more launch on the same stream
     z = cam.latent()                        # [N, 64], live: row e is the encoding of env e's last capture
 
-Two paths over ONE set of parameters (nn.Conv2d, nn.Conv2d, nn.Linear; include/lsim.h, lsim_depth_encode, states the formulas):
-  * `forward(frames)` is plain torch -- autograd, the PPO update, the CPU;
+Three paths over ONE set of parameters (nn.Conv2d, nn.Conv2d, nn.Linear; include/lsim.h, lsim_depth_encode, states the formulas):
+  * `forward(frames)` is plain torch -- autograd through six library launches, the CPU;
   * `encode_device(sensor, tick)` is the fused HIP launch of the rollout: forward only, one workgroup per env that is DUE on `tick` (the
     sensor model's rule, so with a staggered period P it encodes 1 env in P), activations in LDS, the parameters read where torch keeps
-    them -- no packing step, so an optimiser step is seen by the next launch.  There is no torch fall-back: a library without the entry
-    point raises.
-Not here: a backward kernel, the latent as an input of HIMActorCritic / the runner / the rollout storage, a
-device-side tick."""
+    them -- no packing step, so an optimiser step is seen by the next launch;
+  * `forward_device(frames)` is the training path on the device: the same fused launch over a batch of frames with autograd attached, whose
+    backward is lsim_depth_encode_backward -- the conv activations are recomputed per sample in LDS, so nothing of their size is saved or
+    written.  The gradients go where learn/fused_linear.py puts its own: into a GradArena's slices when one is set.
+There is no torch fall-back behind the two device paths: a library without the entry points raises.
+Not here: the latent as an input of HIMActorCritic / the runner / the rollout storage, a gradient with respect to
+the frames, a device-side tick."""
+import contextlib
 import ctypes
 
 import torch
@@ -20,6 +24,63 @@ from torch import nn
 from torch.nn import functional as F
 
 from .. import abi, lib
+from . import fused_linear
+
+_PARAM_NAMES = ("w1", "b1", "w2", "b2", "w3", "b3")
+_live_rows = {}
+
+
+def _all_live(device, batch):
+    """[batch] int64 zeros: the episode_length of lsim_depth_encode for rows that are all encoded (FILL_ALL)"""
+    t = _live_rows.get(device)
+    if t is None or t.numel() < batch:
+        t = _live_rows[device] = torch.zeros(batch, dtype=torch.int64, device=device)
+    return t
+
+
+class _DepthEncodeFn(torch.autograd.Function):
+    """latent = lsim_depth_encode over a batch of frames (hist_slots = frames, FILL_ALL); backward = lsim_depth_encode_backward"""
+
+    @staticmethod
+    def forward(ctx, enc, api, hist, hist_stride, *params):
+        B, L = hist.shape[0], enc.latent_dim
+        latent = torch.empty(B, (L + 3) // 4 * 4, device=hist.device, dtype=torch.float32)
+        de = abi.LsimDepthEncoder.from_buffer_copy(enc._extents)
+        de.hist, de.hist_stride, de.hist_slots = hist.data_ptr(), hist_stride, enc.frames
+        de.episode_length, de.num_envs, de.env_stride = _all_live(hist.device, B).data_ptr(), B, 1
+        de.w1, de.b1, de.w2, de.b2, de.w3, de.b3 = (p.data_ptr() for p in params)
+        de.final_act = int(enc.final_act)
+        de.latent, de.latent_stride = latent.data_ptr(), latent.shape[1]
+        de.tick, de.period, de.stagger, de.flags = 0, 1, 0, abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+        lib.check(api.lsim_depth_encode(ctypes.byref(de), torch.cuda.current_stream(hist.device).cuda_stream), what="lsim_depth_encode")
+        out = latent[:, :L]
+        ctx.enc, ctx.api, ctx.hist_stride = enc, api, hist_stride
+        ctx.save_for_backward(hist, out, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        hist, latent, *params = ctx.saved_tensors
+        enc, api = ctx.enc, ctx.api
+        if g.dtype != torch.float32 or g.stride(1) != 1:
+            g = g.float().contiguous()
+        db = abi.LsimDepthEncoderBwd()
+        for k in ("height", "width", "frames", "c1", "k1", "s1", "c2", "k2", "s2", "latent_dim"):
+            setattr(db, k, getattr(enc._extents, k))
+        db.hist, db.hist_stride, db.hist_slots, db.batch = hist.data_ptr(), ctx.hist_stride, enc.frames, hist.shape[0]
+        db.final_act, db.grid_limit = int(enc.final_act), 0
+        db.g, db.g_stride, db.latent, db.latent_stride = g.data_ptr(), g.stride(0), latent.data_ptr(), latent.stride(0)
+        lds, need = ctypes.c_size_t(), ctypes.c_size_t()
+        lib.check(api.lsim_depth_encode_backward_sizes(ctypes.byref(db), ctypes.byref(lds), ctypes.byref(need)), what="lsim_depth_encode_backward_sizes")
+        ws = fused_linear._workspace("depth_encoder_backward", hist.device, need.value)
+        db.workspace, db.workspace_bytes = ws.data_ptr(), ws.numel()
+        grads = []
+        for name, p in zip(_PARAM_NAMES, params):
+            setattr(db, name, p.data_ptr())
+            grads.append(fused_linear._grad_out(p.data_ptr(), tuple(p.shape), hist.device))
+            setattr(db, "g" + name, grads[-1].data_ptr())
+        lib.check(api.lsim_depth_encode_backward(ctypes.byref(db), torch.cuda.current_stream(hist.device).cuda_stream), what="lsim_depth_encode_backward")
+        return (None, None, None, None) + tuple(gr if need_ else None for gr, need_ in zip(grads, ctx.needs_input_grad[4:]))
 
 
 class DepthEncoder(nn.Module):
@@ -90,3 +151,34 @@ class DepthEncoder(nn.Module):
         de.tick, de.period, de.stagger, de.flags = int(tick), model.period, int(model.stagger), int(flags)
         lib.check(entry(ctypes.byref(de), sensor._stream(stream)), what="lsim_depth_encode")
         return latent[:, :self.latent_dim]
+
+    def forward_device(self, frames, stream=None, api=None):
+        """[B, frames, height, width] fp32 on the parameters' device -> [B, latent_dim] WITH autograd to the six parameters: ONE launch of
+        lsim_depth_encode over the batch now, the launches of lsim_depth_encode_backward when the result is back-propagated (on `stream`, a
+        torch.cuda.Stream; default: the current one).  Contiguous frames whose height * width is a multiple of 4 are read in place, others
+        through a padded copy.  The frames are sensor data: there is no gradient with respect to them, and frames that ask for one raise."""
+        api = api if api is not None else lib.load()
+        for name in ("lsim_depth_encode", "lsim_depth_encode_backward_sizes", "lsim_depth_encode_backward"):
+            if getattr(api, name, None) is None:
+                raise lib.LsimError(f"the loaded library has no {name}: rebuild it (there is no torch fall-back for the depth encoder)")
+        if frames.requires_grad:
+            raise ValueError("forward_device: frames.requires_grad is set, but the depth encoder has no gradient with respect to its frames")
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (self.frames, self.height, self.width) or frames.shape[0] < 1:
+            raise ValueError(f"forward_device: frames must be [B >= 1, {self.frames}, {self.height}, {self.width}], got {tuple(frames.shape)}")
+        params = self.device_params()
+        dev = params[0].device
+        if frames.dtype != torch.float32 or frames.device != dev:
+            raise ValueError(f"forward_device: frames must be fp32 on {dev} (are {frames.dtype}, {frames.device})")
+        for name, p in zip(_PARAM_NAMES, params):
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+                raise ValueError(f"forward_device: parameter {name} must be fp32, contiguous and on {dev} (is {p.dtype}, "
+                                 f"{'contiguous' if p.is_contiguous() else 'strided'}, {p.device})")
+        R = self.height * self.width
+        with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+            if frames.is_contiguous() and R % 4 == 0 and frames.data_ptr() % 16 == 0:
+                hist, stride = frames, R
+            else:
+                stride = (R + 3) // 4 * 4
+                hist = torch.zeros(frames.shape[0], self.frames, stride, device=dev, dtype=torch.float32)
+                hist[:, :, :R] = frames.reshape(frames.shape[0], self.frames, R)
+            return _DepthEncodeFn.apply(self, api, hist, stride, *params)
