@@ -596,6 +596,29 @@ int lsim_policy_act_post_at(const lsim_him_policy* p, const lsim_rollout_storage
                             int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
                             const float* prev_term_priv_obs, float gamma, void* stream);
 
+/* The two launches above with ONE MORE SEGMENT of the actor input (a vision policy's depth latent, learn/vision.py).  The actor's first layer
+ * then reads, in this column order,
+ *   [ one-step observation (num_one_step_obs) | velocity estimate (3) | normalised latent (encoder[2].n_out - 3) | rows[env, 0 .. dim) ]
+ * i.e. the extra columns come LAST: a policy whose first actor layer holds zeros there computes what the plain launch computes, bit for bit.
+ * Rows past num_envs and the columns up to k_pad read zero.  Nothing else of the launch differs (same blocks, sampling, stores).
+ * `store`: NULL, or a dense [num_steps, num_envs, dim] tensor whose row step_idx receives the rows the actor read (lsim_policy_act_post_at_ext
+ * only; lsim_policy_forward_ext ignores it).
+ * Checked on the host before anything is launched or written: LSIM_E_INVALID for a NULL struct or rows, dim < 1 or ld < dim;
+ * LSIM_E_UNSUPPORTED unless actor[0].k_in == num_one_step_obs + encoder[2].n_out + dim and actor[0].k_pad <= 272; and whatever
+ * lsim_policy_forward / lsim_policy_act_post_at refuse.  (Those go on refusing a policy whose first actor layer is wider than theirs.) */
+typedef struct lsim_policy_extra {
+    const float* rows;   /* [num_envs, ld] fp32: row e is appended to env e's actor input */
+    int32_t dim, ld;     /* 1 <= dim <= ld */
+    float* store;        /* NULL, or dense [T, N, dim]: row step_idx receives the rows (act entry only) */
+} lsim_policy_extra;
+int lsim_policy_forward_ext(const lsim_him_policy* p, const lsim_policy_extra* extra, const float* obs, const float* priv_obs, int64_t num_envs,
+                            float* mean_out, float* values_out, void* stream);
+int lsim_policy_act_post_at_ext(const lsim_him_policy* p, const lsim_policy_extra* extra, const lsim_rollout_storage* st, int64_t step_idx,
+                                int64_t draw_counter, const float* obs, const float* priv_obs, const float* std, uint32_t seed, uint32_t rank,
+                                float* mean_out, float* values_out, float* actions_out,
+                                int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
+                                const float* prev_term_priv_obs, float gamma, void* stream);
+
 /* ---- the AMP rollout step in one launch (SURVEY.md 8f rank 4 "discriminator reward fused after the step"): what HybridPolicyRunner does between
  * env.step() and process_env_step() (rsl_rl/runners/hybrid_runner.py:183-200) --
  *   next' = where(dones, terminal_amp_states, next_amp_obs)                                  HYBR:191-192

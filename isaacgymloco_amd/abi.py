@@ -101,6 +101,7 @@ LsimCollisionPoint = STRUCTS["lsim_collision_point"]
 LsimRolloutStorage = STRUCTS["lsim_rollout_storage"]
 LsimMlpLayer = STRUCTS["lsim_mlp_layer"]
 LsimHimPolicy = STRUCTS["lsim_him_policy"]
+LsimPolicyExtra = STRUCTS["lsim_policy_extra"]
 LsimWgradPending = STRUCTS["lsim_wgrad_pending"]
 LsimAmpDisc = STRUCTS["lsim_amp_disc"]
 LsimEval = STRUCTS["lsim_eval"]

@@ -189,9 +189,19 @@ struct LsPolActArgs {
     const float* prev_rewards; const float* prev_term_priv;
     float gamma;
 };
-template <int ROWS, int WAVES, bool ACT>
+// EXT: a further segment of the actor input (lsim_policy_extra, include/lsim.h): `dim` floats of the caller's row of each env behind the
+// normalised latent, [obs_now | vel | z | extra]; in the ACT form the rows also go to ext_store[step].  The arguments ride behind the ACT
+// ones in a derived struct, so the kernels without the segment keep their argument list
+struct LsPolExtArgs : LsPolActArgs {
+    const float* ext_rows;
+    float* ext_store;
+    int ext_dim, ext_ld;
+};
+template <bool EXT> struct LsPolArgsOf { typedef LsPolActArgs type; };
+template <> struct LsPolArgsOf<true> { typedef LsPolExtArgs type; };
+template <int ROWS, int WAVES, bool ACT, bool EXT = false>
 __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4))) void lsim_k_policy_forward(lsim_him_policy p, const float* __restrict__ obs, const float* __restrict__ priv,
-                                                             long num_envs, float* __restrict__ mean_out, float* __restrict__ values_out, LsPolActArgs act) {
+                                                             long num_envs, float* __restrict__ mean_out, float* __restrict__ values_out, typename LsPolArgsOf<EXT>::type act) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long r0 = (long)blockIdx.x * ROWS;
     // blockIdx.y = 0: estimator encoder + actor on the observation history; 1: critic on the privileged observation.  The two halves are
@@ -308,6 +318,10 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
                 for (int k = 0; k < nl; ++k) { const float z = ls_pol_lds[o_a + r * s_a + ls_pol_col(r, 3 + k)]; ss += z * z; }
                 v = ls_pol_lds[o_a + r * s_a + ls_pol_col(r, 3 + (c - n1 - 3))] / fmaxf(sqrtf(ss), 1e-12f);      // F.normalize(p=2, eps=1e-12)
             }
+            if constexpr (EXT) {        // the caller's row behind the latent; rows past num_envs and the padding columns stay zero
+                const int j = c - (n1 + 3 + nl);
+                if (j >= 0 && j < act.ext_dim && r0 + r < num_envs) v = act.ext_rows[(r0 + r) * act.ext_ld + j];
+            }
             ls_pol_lds[o_b + r * s_b + ls_pol_col(r, c)] = v;
         }
         __syncthreads();
@@ -352,6 +366,16 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(4, 4
             act.st.actions_log_prob[(size_t)act.step * act.st.num_envs + r0 + tid] = (t4[0] + t4[2]) + (t4[1] + t4[3]);
         }
     }
+    if constexpr (ACT && EXT) {     // the rows the actor read, re-read from the caller's buffer (buffer B holds a later layer by now): behind
+        if (act.ext_store) {        // every barrier of the block, like store_rows
+            const int dim = act.ext_dim;
+            for (int e = tid; e < ROWS * dim; e += 64 * WAVES) {
+                const int r = e / dim, j = e - r * dim;
+                const long env = r0 + r;
+                if (env < num_envs) act.ext_store[((size_t)act.step * act.st.num_envs + env) * dim + j] = act.ext_rows[env * act.ext_ld + j];
+            }
+        }
+    }
     store_rows();
 }
 
@@ -363,18 +387,20 @@ static int ls_pol_check_layer(const lsim_mlp_layer* L, int k_in_expected) {
     return 0;
 }
 
+// ext: nullptr (the plain entries), or the further actor-input segment, already checked by ls_pol_check_extra
 static int ls_policy_launch(const lsim_him_policy* p, const float* obs, const float* priv_obs, int64_t num_envs, float* mean_out,
-                            float* values_out, const LsPolActArgs* act_args, void* stream) {
+                            float* values_out, const LsPolActArgs* act_args, void* stream, const lsim_policy_extra* ext = nullptr) {
     if (!p || !obs || !priv_obs || !mean_out || !values_out || num_envs <= 0) return LSIM_E_INVALID;
     const bool act = act_args != nullptr;
-    LsPolActArgs aa;
+    LsPolExtArgs aa;
     memset(&aa, 0, sizeof(aa));
-    if (act) aa = *act_args;
+    if (act) static_cast<LsPolActArgs&>(aa) = *act_args;
+    if (ext) { aa.ext_rows = ext->rows; aa.ext_store = act ? ext->store : nullptr; aa.ext_dim = ext->dim; aa.ext_ld = ext->ld; }
     if (p->num_obs > LS_POL_MAX_IN || p->num_priv_obs > LS_POL_MAX_IN || p->num_actions <= 0 || p->num_actions > 16) return LSIM_E_UNSUPPORTED;
     int bad = 0, k = p->num_obs;
     for (int l = 0; l < 3; ++l) { bad |= ls_pol_check_layer(&p->encoder[l], k); k = p->encoder[l].n_out; }
     if (p->encoder[2].n_out < 4 || p->encoder[0].k_pad > LS_POL_MAX_IN) bad = 1;
-    k = p->num_one_step_obs + p->encoder[2].n_out;
+    k = p->num_one_step_obs + p->encoder[2].n_out + (ext ? ext->dim : 0);
     for (int l = 0; l < 4; ++l) { bad |= ls_pol_check_layer(&p->actor[l], k); k = p->actor[l].n_out; }
     if (p->actor[3].n_out != p->num_actions || p->actor[0].k_pad > LS_POL_MAX_IN) bad = 1;
     k = p->num_priv_obs;
@@ -388,22 +414,26 @@ static int ls_policy_launch(const lsim_him_policy* p, const float* obs, const fl
     const bool wide = num_envs >= 2048;
     const int rows = wide ? 32 : 16;
     const size_t lds = (size_t)rows * (LS_POL_STRIDE_IN + LS_POL_STRIDE_A + LS_POL_STRIDE_B) * sizeof(float);
-    static size_t configured[4][64] = {{0}};     // per kernel and device: the attribute belongs to the device's copy of the kernel
+    static size_t configured[8][64] = {{0}};     // per kernel and device: the attribute belongs to the device's copy of the kernel
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
     const void* fn = wide ? (act ? (const void*)lsim_k_policy_forward<32, 16, true> : (const void*)lsim_k_policy_forward<32, 16, false>)
                           : (act ? (const void*)lsim_k_policy_forward<16, 8, true> : (const void*)lsim_k_policy_forward<16, 8, false>);
-    const int slot = 2 * (int)wide + (int)act;
+    if (ext) fn = wide ? (act ? (const void*)lsim_k_policy_forward<32, 16, true, true> : (const void*)lsim_k_policy_forward<32, 16, false, true>)
+                       : (act ? (const void*)lsim_k_policy_forward<16, 8, true, true> : (const void*)lsim_k_policy_forward<16, 8, false, true>);
+    const int slot = 4 * (int)(ext != nullptr) + 2 * (int)wide + (int)act;
     if (lds > configured[slot][dev]) {
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
         configured[slot][dev] = lds;
     }
     const int blocks = (int)((num_envs + rows - 1) / rows);
-#define LS_POL_LAUNCH(R, W, A) hipLaunchKernelGGL((lsim_k_policy_forward<R, W, A>), dim3(blocks, 2), dim3(64 * W), lds, (hipStream_t)stream, *p, obs, priv_obs, \
-                                                 (long)num_envs, mean_out, values_out, aa)
+#define LS_POL_LAUNCH_ARGS(R, W, A, E, ARGS) hipLaunchKernelGGL((lsim_k_policy_forward<R, W, A, E>), dim3(blocks, 2), dim3(64 * W), lds, (hipStream_t)stream, *p, obs, priv_obs, \
+                                                               (long)num_envs, mean_out, values_out, ARGS)
+#define LS_POL_LAUNCH(R, W, A) do { if (ext) LS_POL_LAUNCH_ARGS(R, W, A, true, aa); else LS_POL_LAUNCH_ARGS(R, W, A, false, static_cast<const LsPolActArgs&>(aa)); } while (0)
     if (wide) { if (act) LS_POL_LAUNCH(32, 16, true); else LS_POL_LAUNCH(32, 16, false); }
     else { if (act) LS_POL_LAUNCH(16, 8, true); else LS_POL_LAUNCH(16, 8, false); }
 #undef LS_POL_LAUNCH
+#undef LS_POL_LAUNCH_ARGS
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
 
@@ -427,11 +457,12 @@ extern "C" int lsim_policy_act_at(const lsim_him_policy* p, const lsim_rollout_s
     return ls_policy_launch(p, obs, priv_obs, st->num_envs, mean_out, values_out, &a, stream);
 }
 
-extern "C" int lsim_policy_act_post_at(const lsim_him_policy* p, const lsim_rollout_storage* st, int64_t step_idx, int64_t draw_counter,
-                                       const float* obs, const float* priv_obs, const float* std, uint32_t seed, uint32_t rank,
-                                       float* mean_out, float* values_out, float* actions_out,
-                                       int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
-                                       const float* prev_term_priv_obs, float gamma, void* stream) {
+// lsim_policy_act_post_at and its form with a further actor-input segment (ext != nullptr, already checked)
+static int ls_policy_act_post(const lsim_him_policy* p, const lsim_policy_extra* ext, const lsim_rollout_storage* st, int64_t step_idx, int64_t draw_counter,
+                              const float* obs, const float* priv_obs, const float* std, uint32_t seed, uint32_t rank,
+                              float* mean_out, float* values_out, float* actions_out,
+                              int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
+                              const float* prev_term_priv_obs, float gamma, void* stream) {
     if (!p || !st || !std || !actions_out) return LSIM_E_INVALID;
     int rc = ls_rollout_check(st);
     if (rc != LSIM_OK) return rc;
@@ -443,5 +474,38 @@ extern "C" int lsim_policy_act_post_at(const lsim_him_policy* p, const lsim_roll
     a.st = *st; a.step = step_idx; a.draw = draw_counter; a.std = std; a.seed = seed; a.rank = rank; a.actions_out = actions_out;
     a.prev_step = prev_step < 0 ? -1 : prev_step; a.prev_dones = prev_dones; a.prev_time_outs = prev_time_outs; a.prev_rewards = prev_rewards;
     a.prev_term_priv = prev_term_priv_obs; a.gamma = gamma;
-    return ls_policy_launch(p, obs, priv_obs, st->num_envs, mean_out, values_out, &a, stream);
+    return ls_policy_launch(p, obs, priv_obs, st->num_envs, mean_out, values_out, &a, stream, ext);
+}
+
+extern "C" int lsim_policy_act_post_at(const lsim_him_policy* p, const lsim_rollout_storage* st, int64_t step_idx, int64_t draw_counter,
+                                       const float* obs, const float* priv_obs, const float* std, uint32_t seed, uint32_t rank,
+                                       float* mean_out, float* values_out, float* actions_out,
+                                       int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
+                                       const float* prev_term_priv_obs, float gamma, void* stream) {
+    return ls_policy_act_post(p, nullptr, st, step_idx, draw_counter, obs, priv_obs, std, seed, rank, mean_out, values_out, actions_out,
+                              prev_step, prev_dones, prev_time_outs, prev_rewards, prev_term_priv_obs, gamma, stream);
+}
+
+// ---- the same launches with a further actor-input segment (include/lsim.h, lsim_policy_extra)
+static int ls_pol_check_extra(const lsim_policy_extra* x) {
+    if (!x || !x->rows || x->dim < 1 || x->ld < x->dim) return LSIM_E_INVALID;
+    return LSIM_OK;
+}
+
+extern "C" int lsim_policy_forward_ext(const lsim_him_policy* p, const lsim_policy_extra* extra, const float* obs, const float* priv_obs, int64_t num_envs,
+                                       float* mean_out, float* values_out, void* stream) {
+    int rc = ls_pol_check_extra(extra);
+    if (rc != LSIM_OK) return rc;
+    return ls_policy_launch(p, obs, priv_obs, num_envs, mean_out, values_out, nullptr, stream, extra);
+}
+
+extern "C" int lsim_policy_act_post_at_ext(const lsim_him_policy* p, const lsim_policy_extra* extra, const lsim_rollout_storage* st, int64_t step_idx,
+                                           int64_t draw_counter, const float* obs, const float* priv_obs, const float* std, uint32_t seed, uint32_t rank,
+                                           float* mean_out, float* values_out, float* actions_out,
+                                           int64_t prev_step, const uint8_t* prev_dones, const uint8_t* prev_time_outs, const float* prev_rewards,
+                                           const float* prev_term_priv_obs, float gamma, void* stream) {
+    int rc = ls_pol_check_extra(extra);
+    if (rc != LSIM_OK) return rc;
+    return ls_policy_act_post(p, extra, st, step_idx, draw_counter, obs, priv_obs, std, seed, rank, mean_out, values_out, actions_out,
+                              prev_step, prev_dones, prev_time_outs, prev_rewards, prev_term_priv_obs, gamma, stream);
 }

@@ -14,8 +14,8 @@ Three paths over ONE set of parameters (nn.Conv2d, nn.Conv2d, nn.Linear; include
     backward is lsim_depth_encode_backward -- the conv activations are recomputed per sample in LDS, so nothing of their size is saved or
     written.  The gradients go where learn/fused_linear.py puts its own: into a GradArena's slices when one is set.
 There is no torch fall-back behind the two device paths: a library without the entry points raises.
-Not here: the latent as an input of HIMActorCritic / the runner / the rollout storage, a gradient with respect to
-the frames, a device-side tick."""
+The latent as an input of the actor, the rollout storage and the runner is learn/vision.py.  Not here: a gradient
+with respect to the frames, a device-side tick."""
 import contextlib
 import ctypes
 

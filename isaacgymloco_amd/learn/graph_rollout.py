@@ -44,8 +44,7 @@ class GraphedRollout:
         self._seed, self._rank = int(self.env.lcfg.seed), int(self.env.lcfg.rank)
         self.graph_a = None
         # preferred: the library's fused policy kernel (11 Linear + 8 ELU + glue in one launch); otherwise capture torch's forward
-        from .fused_policy import PackedHimPolicy
-        self.packed = PackedHimPolicy(self.alg.actor_critic) if PackedHimPolicy.supported(self.alg.actor_critic) else None
+        self.packed = self._make_packed()
         self.by_value = self.packed is not None         # captured graphs need device-side counters; the direct launches do not
         if self.packed is None:
             self._capture()
@@ -55,6 +54,11 @@ class GraphedRollout:
         # rollout, env.reset()) or reads the storage in the middle of a rollout flushes it first
         self.env.before_external_step = self.flush
         self.storage.pending_store = lambda: self._pending_post is not None
+
+    def _make_packed(self):
+        """the packed weights of the fused policy launch, or None when it does not take the topology (subclasses: their own launch)"""
+        from .fused_policy import PackedHimPolicy
+        return PackedHimPolicy(self.alg.actor_critic) if PackedHimPolicy.supported(self.alg.actor_critic) else None
 
     # ---- HIMP:90-103 written against static tensors; the elementwise tail is one HIP kernel --------------------------
     def _act(self):

@@ -136,7 +136,7 @@ class HIMRolloutStorage:
         else:
             critic = next_critic = obs
         fields = (obs, critic, self.actions.flatten(0, 1), next_critic, self.values.flatten(0, 1), self.advantages.flatten(0, 1),
-                  self.returns.flatten(0, 1), self.actions_log_prob.flatten(0, 1), self.mu.flatten(0, 1), self.sigma.flatten(0, 1))
+                  self.returns.flatten(0, 1), self.actions_log_prob.flatten(0, 1), self.mu.flatten(0, 1), self.sigma.flatten(0, 1)) + self._extra_fields()
         # The reference draws ONE permutation and reuses it for every epoch (HST:140, HST:159-164), so minibatch i holds the same
         # rows in all epochs: gather the whole batch through the permutation once and hand out contiguous slices, instead of
         # re-gathering ~800 floats per sample for each of the epochs x minibatches (same values, 1/num_epochs of the gather traffic).
@@ -146,6 +146,10 @@ class HIMRolloutStorage:
                 if self._shuffle_generation != gen_id:
                     raise RuntimeError("a second mini_batch_generator of this storage re-shuffled the buffers this one hands out (one live generator per storage)")
                 yield tuple(f[i * mb:(i + 1) * mb] for f in shuffled)
+
+    def _extra_fields(self):
+        """further [T * N, .] fields a subclass's minibatches carry behind the ten above, gathered through the same permutation"""
+        return ()
 
     def release_shuffle_buffers(self):
         """free the persistent shuffle destinations (~0.4 GB at 4096 x 100): after the last update of a run, before an evaluation-only phase"""

@@ -1,0 +1,355 @@
+"""Vision policy: the depth encoder's latent row (learn/depth_encoder.py) as one more input segment of the HIM actor, from the rollout to
+the PPO update.
+
+    cam = env.add_sensor("depth", depth_camera(env, 64, 48, 87.0, model=SensorModel(period=5, stagger=True, latency=1, frames=2, normalise=True)))
+    runner = VisionOnPolicyRunner(env, train_cfg, sensor="depth", device=dev)
+    runner.enable_graphs()
+    runner.learn(n)
+
+Three decisions bound the memory and the code:
+  1. The actor reads the latent DETACHED, as it reads the estimator's output (HAC:136-141): the rollout stores, per transition, the row the
+     actor saw ([T, N, L] floats; the frames would be [T, N, frames, H, W]) and the update feeds that row back.  No PPO gradient reaches
+     the encoder.
+  2. The encoder is trained by an auxiliary regression of its own: frames -> latent -> linear head -> the height scan the critic already
+     receives as privileged information, on a few snapshots of one rollout, with its own Adam.  Encoder, head and that optimiser belong to
+     VisionPPO, not to the actor-critic: HIMPPO.optimizer, the GradArena buckets and the fused clip + Adam step see the parameters they
+     see for a HIM policy, the first actor layer merely being wider.
+  3. The depth columns come LAST in the actor input, [obs_now (n1) | vel (3) | z (nl) | depth (L)]: a HIM policy warm-starts a vision policy
+     by copying actor.0.weight into the first n1 + 3 + nl columns and zeroing the rest (load_him_state_dict), and is then arithmetically
+     the HIM policy.
+On the device the rollout step is the fused launch with the extra segment (include/lsim.h, lsim_policy_act_post_at_ext); topologies that
+launch does not take use the eager rollout.  One rank only."""
+import contextlib
+import copy
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import abi, lib
+from .fused_policy import PackedHimPolicy
+from .graph_rollout import GraphedRollout
+from .him_ppo import HIMPPO
+from .modules import HIMActorCritic, get_activation, mlp
+from .runner import _ALGOS, _POLICIES, HIMOnPolicyRunner
+from .storage import HIMRolloutStorage, Transition
+
+
+def height_scan_block(cfg=None):
+    """(offset, width) of the height scan inside a privileged observation row, from the layout the env assembles (csrc/ls_post.h,
+    ph_build_obs: the LSIM_NUM_HEIGHT_PTS samples are the row's last entries).  `cfg`: the env's config; one without measure_heights
+    has zeros there, which is no regression target, and raises."""
+    if cfg is not None and not bool(getattr(getattr(cfg, "terrain", None), "measure_heights", False)):
+        raise ValueError("the vision policy's encoder regresses the height scan of the privileged observation: the config needs terrain.measure_heights")
+    width = abi.DEFINES["LSIM_NUM_HEIGHT_PTS"]
+    return abi.DEFINES["LSIM_NUM_PRIV_OBS"] - width, width
+
+
+class VisionActorCritic(HIMActorCritic):
+    """HIMActorCritic whose actor reads `depth_latent_dim` more columns: actor = mlp([n1 + 3 + 16 + L, ...]); critic and estimator unchanged.
+    The latent is an explicit argument wherever the actor is evaluated (act, act_inference, update_distribution, _actor_input), or bound for
+    the extent of a `with bound_latent(rows):` block (HIMPPO._mb_forward calls _actor_input(obs)).  A missing latent raises."""
+
+    def __init__(self, num_actor_obs, num_critic_obs, num_one_step_obs, num_actions, depth_latent_dim=64, actor_hidden_dims=(512, 256, 128),
+                 activation="elu", **kwargs):
+        super().__init__(num_actor_obs, num_critic_obs, num_one_step_obs, num_actions, actor_hidden_dims=actor_hidden_dims, activation=activation, **kwargs)
+        self.depth_latent_dim = int(depth_latent_dim)
+        if self.depth_latent_dim < 1:
+            raise ValueError("VisionActorCritic: depth_latent_dim >= 1")
+        self.num_him_actor_inputs = self.actor[0].in_features
+        self.actor = mlp([self.num_him_actor_inputs + self.depth_latent_dim, *actor_hidden_dims, num_actions], get_activation(activation))
+        self._bound_latent = None
+
+    @contextlib.contextmanager
+    def bound_latent(self, rows):
+        """inside the block the actor reads `rows` [B, L] wherever no latent is passed (one minibatch of the update)"""
+        prev, self._bound_latent = self._bound_latent, rows
+        try:
+            yield self
+        finally:
+            self._bound_latent = prev
+
+    def _latent_rows(self, depth_latent, batch):
+        rows = depth_latent if depth_latent is not None else self._bound_latent
+        if rows is None:
+            raise ValueError("VisionActorCritic: no depth latent (pass depth_latent=..., or evaluate inside `with bound_latent(rows):`)")
+        if rows.dim() != 2 or rows.shape[0] != batch or rows.shape[1] != self.depth_latent_dim:
+            raise ValueError(f"VisionActorCritic: the depth latent must be [{batch}, {self.depth_latent_dim}], got {tuple(rows.shape)}")
+        return rows.detach()
+
+    def _actor_input(self, obs_history, depth_latent=None):
+        rows = self._latent_rows(depth_latent, obs_history.shape[0])
+        return torch.cat((super()._actor_input(obs_history), rows), dim=-1)
+
+    def update_distribution(self, obs_history, depth_latent=None):
+        with self.bound_latent(self._latent_rows(depth_latent, obs_history.shape[0])):
+            super().update_distribution(obs_history)
+
+    def act(self, obs_history=None, depth_latent=None, **kwargs):
+        self.update_distribution(obs_history, depth_latent)
+        return self.distribution.sample()
+
+    def act_inference(self, obs_history, depth_latent=None, observations=None):
+        return self.actor(self._actor_input(obs_history, depth_latent))
+
+    @torch.no_grad()
+    def load_him_state_dict(self, sd):
+        """warm start from a HIMActorCritic's state dict: actor.0.weight goes into the first n1 + 3 + nl columns, the depth columns are zero --
+        the policy then computes the HIM policy's means whatever the latent holds"""
+        sd = dict(sd)
+        w = sd["actor.0.weight"]
+        k = self.num_him_actor_inputs
+        if tuple(w.shape) != (self.actor[0].out_features, k):
+            raise ValueError(f"load_him_state_dict: actor.0.weight must be {(self.actor[0].out_features, k)}, got {tuple(w.shape)}")
+        wide = torch.zeros_like(self.actor[0].weight)
+        wide[:, :k] = w
+        sd["actor.0.weight"] = wide
+        return self.load_state_dict(sd)
+
+
+class VisionTransition:
+    __slots__ = Transition.__slots__ + ("depth_latent",)
+    __init__ = Transition.__init__
+    clear = Transition.clear
+
+
+class VisionRolloutStorage(HIMRolloutStorage):
+    """HIMRolloutStorage + depth_latent [T, N, L]: the row the actor saw at each transition; the minibatch generator yields it as an
+    eleventh field, gathered through the same permutation (and, on the GPU, into a persistent shuffle buffer like the other ten)"""
+    Transition = VisionTransition
+
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, depth_latent_dim, device="cpu"):
+        super().__init__(num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device)
+        self.depth_latent = torch.zeros(num_transitions_per_env, num_envs, int(depth_latent_dim), device=device)
+
+    def add_transitions(self, t):
+        if self.step >= self.num_transitions_per_env:
+            raise AssertionError("Rollout buffer overflow")
+        if t.depth_latent is None:
+            raise ValueError("VisionRolloutStorage: the transition carries no depth latent")
+        self.depth_latent[self.step].copy_(t.depth_latent)
+        super().add_transitions(t)
+
+    def _extra_fields(self):
+        return (self.depth_latent.flatten(0, 1),)
+
+
+class VisionPPO(HIMPPO):
+    """HIMPPO over a VisionActorCritic.  act() records `latent_source()` (the runner passes sensor.latent) with the transition, the update binds
+    each minibatch's stored rows to the actor, and behind it the encoder takes its own steps: `aux_snapshots` rollout steps, spread evenly
+    over the T steps, each keep a copy of (frames_source(), height scan of the same step's critic observation); one pass over them, one
+    minibatch per snapshot, of  z = encoder(frames), loss = mse(head(z), target), Adam(aux_learning_rate) over encoder and head.
+    update() returns HIMPPO's values plus the mean auxiliary loss."""
+
+    def __init__(self, actor_critic, encoder=None, latent_source=None, frames_source=None, height_scan=None, aux_snapshots=4, aux_learning_rate=1e-3,
+                 dist_ctx=None, **kwargs):
+        if dist_ctx is not None and getattr(dist_ctx, "world", 1) > 1:
+            raise NotImplementedError("VisionPPO: one rank only (the encoder's gradients are not reduced over ranks)")
+        super().__init__(actor_critic, dist_ctx=dist_ctx, **kwargs)
+        self.transition = VisionRolloutStorage.Transition()
+        self.aux_snapshots, self.aux_learning_rate = int(aux_snapshots), float(aux_learning_rate)
+        self.encoder = self.depth_head = self.aux_optimizer = None
+        self.latent_source = self.frames_source = self.height_scan = None
+        self._snap, self._snap_filled = [], []
+        self.last_aux_loss = float("nan")
+        if encoder is not None:
+            self.attach(encoder, latent_source, frames_source, height_scan)
+
+    def attach(self, encoder, latent_source, frames_source, height_scan=None):
+        """`encoder`: the DepthEncoder whose latent `latent_source()` returns ([N, L], live); `frames_source()`: the [N, frames, H, W] it
+        encodes; `height_scan`: (offset, width) of the regression target inside a critic observation row (default: the env's layout)"""
+        L = self.actor_critic.depth_latent_dim
+        if encoder.latent_dim != L:
+            raise ValueError(f"VisionPPO: the encoder's latent has {encoder.latent_dim} columns, the actor reads {L}")
+        self.height_scan = tuple(int(v) for v in (height_scan if height_scan is not None else height_scan_block()))
+        self.encoder = encoder.to(self.device)
+        self.depth_head = nn.Linear(L, self.height_scan[1]).to(self.device)
+        self.aux_optimizer = torch.optim.Adam(list(self.encoder.parameters()) + list(self.depth_head.parameters()), lr=self.aux_learning_rate)
+        self.latent_source, self.frames_source = latent_source, frames_source
+        self._snap, self._snap_filled = [], []
+
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        self.storage = VisionRolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape,
+                                            self.actor_critic.depth_latent_dim, self.device)
+
+    def _latent_now(self):
+        if self.latent_source is None:
+            raise RuntimeError("VisionPPO: no latent source (attach(encoder, latent_source, frames_source))")
+        return self.latent_source()
+
+    def act(self, obs, critic_obs):
+        rows = self._latent_now().detach().clone()          # a live sensor buffer: the transition keeps what the actor saw
+        self.snapshot_if_due(self.storage.step, critic_obs)
+        with self.actor_critic.bound_latent(rows):
+            actions = super().act(obs, critic_obs)
+        self.transition.depth_latent = rows
+        return actions
+
+    # ---- the encoder's own training data: a few (frames, target) pairs per rollout
+    def snapshot_steps(self):
+        T = self.storage.num_transitions_per_env
+        k = max(0, min(self.aux_snapshots, T))
+        return sorted({(2 * i + 1) * T // (2 * k) for i in range(k)})
+
+    def snapshot_if_due(self, step, critic_obs):
+        """called once per rollout step, before the env steps: on the steps of snapshot_steps() copy the frames and the height scan"""
+        steps = self.snapshot_steps()
+        if step not in steps:
+            return
+        if self.frames_source is None:
+            raise RuntimeError("VisionPPO: no frames source (attach(encoder, latent_source, frames_source))")
+        frames = self.frames_source()
+        off, width = self.height_scan
+        if critic_obs.shape[1] < off + width:
+            raise ValueError(f"VisionPPO: the critic observation has {critic_obs.shape[1]} columns, the height scan is [{off}, {off + width})")
+        if len(self._snap) != len(steps) or self._snap[0][0].shape != frames.shape or self._snap[0][0].device != frames.device:
+            with torch.inference_mode(False):      # the rollout runs under inference_mode; these are inputs of a backward pass later
+                self._snap = [(torch.zeros(tuple(frames.shape), device=frames.device), torch.zeros(frames.shape[0], width, device=frames.device))
+                              for _ in steps]
+            self._snap_filled = [False] * len(steps)
+        slot = steps.index(step)
+        self._snap[slot][0].copy_(frames)
+        self._snap[slot][1].copy_(critic_obs[:, off:off + width])
+        self._snap_filled[slot] = True
+
+    def _mb_forward(self, ac, batch, two_streams):
+        with ac.bound_latent(batch[10]):
+            return super()._mb_forward(ac, batch[:10], two_streams)
+
+    def encoder_step(self):
+        """one pass over this rollout's snapshots -> mean loss (a 0-d tensor), or None without a snapshot"""
+        if self.encoder is None:
+            raise RuntimeError("VisionPPO: no encoder (attach(encoder, latent_source, frames_source))")
+        on_device = next(self.encoder.parameters()).is_cuda
+        total, n = None, 0
+        for (frames, target), filled in zip(self._snap, self._snap_filled):
+            if not filled:
+                continue
+            z = self.encoder.forward_device(frames) if on_device else self.encoder(frames)
+            loss = F.mse_loss(self.depth_head(z), target)
+            self.aux_optimizer.zero_grad()
+            loss.backward()
+            self.aux_optimizer.step()
+            total = loss.detach() if total is None else total + loss.detach()
+            n += 1
+        self._snap_filled = [False] * len(self._snap)
+        return None if n == 0 else total / n
+
+    def update(self):
+        out = super().update()
+        aux = self.encoder_step()
+        self.last_aux_loss = float("nan") if aux is None else float(aux)
+        return tuple(out) + (self.last_aux_loss,)
+
+
+class PackedVisionPolicy(PackedHimPolicy):
+    """PackedHimPolicy (which packs whatever actor[0] is) launched through the entry points with the extra actor-input segment"""
+
+    @staticmethod
+    def supported(ac):
+        wide_enough = (ac.actor[0].in_features + 15) // 16 * 16 <= 272
+        return isinstance(ac, VisionActorCritic) and wide_enough and PackedHimPolicy.supported(ac)
+
+    def _extra(self, rows, store=None):
+        L = self.ac.depth_latent_dim
+        if not (rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.shape[1] == L and rows.stride(1) == 1):
+            raise ValueError(f"PackedVisionPolicy: the latent rows must be fp32 [N, {L}] on the device with unit column stride")
+        x = abi.LsimPolicyExtra()
+        x.rows, x.dim, x.ld = rows.data_ptr(), L, rows.stride(0)
+        if store is not None:
+            if not (store.is_cuda and store.dtype == torch.float32 and store.is_contiguous() and store.dim() == 3 and store.shape[2] == L):
+                raise ValueError(f"PackedVisionPolicy: the latent store must be a contiguous fp32 [T, N, {L}] device tensor")
+            x.store = store.data_ptr()
+        return x
+
+    def forward(self, obs, priv_obs, mean_out, values_out, rows=None):
+        if rows is None:
+            raise ValueError("PackedVisionPolicy.forward: no depth latent rows")
+        if rows.shape[0] != obs.shape[0]:
+            raise ValueError("PackedVisionPolicy.forward: one latent row per env")
+        x = self._extra(rows)
+        lib.check(self._L.lsim_policy_forward_ext(ctypes.byref(self._P), ctypes.byref(x), obs.data_ptr(), priv_obs.data_ptr(), obs.shape[0], mean_out.data_ptr(),
+                                                  values_out.data_ptr(), torch.cuda.current_stream(self.dev).cuda_stream), what="lsim_policy_forward_ext")
+
+    def forward_act(self, storage_struct, step, draw, obs, priv_obs, std, seed, rank, mean_out, values_out, actions_out, prev=None, rows=None, store=None):
+        """lsim_policy_act_post_at_ext; prev as PackedHimPolicy.forward_act's (None: no post-step store), `store` [T, N, L] or None"""
+        if rows is None:
+            raise ValueError("PackedVisionPolicy.forward_act: no depth latent rows")
+        if rows.shape[0] != storage_struct.num_envs or (store is not None and (store.shape[0] != storage_struct.num_steps or store.shape[1] != storage_struct.num_envs)):
+            raise ValueError("PackedVisionPolicy.forward_act: the latent rows / store do not match the storage's [T, N]")
+        x = self._extra(rows, store)
+        pstep, dones, touts, rewards, term, gamma = prev if prev is not None else (-1, None, None, None, None, 0.0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        lib.check(self._L.lsim_policy_act_post_at_ext(ctypes.byref(self._P), ctypes.byref(x), ctypes.byref(storage_struct), int(step), int(draw), obs.data_ptr(),
+                                                      priv_obs.data_ptr(), std.data_ptr(), seed, rank, mean_out.data_ptr(), values_out.data_ptr(),
+                                                      actions_out.data_ptr(), int(pstep), ptr(dones), ptr(touts), ptr(rewards), ptr(term), float(gamma),
+                                                      torch.cuda.current_stream(self.dev).cuda_stream), what="lsim_policy_act_post_at_ext")
+
+
+class VisionRollout(GraphedRollout):
+    """GraphedRollout whose policy launch also reads the sensor's live latent rows and stores them in storage.depth_latent[step]; the
+    previous step's deferred post-step store rides along as in the parent.  Only the fused launch: no captured-graph form."""
+
+    def __init__(self, runner, sensor):
+        self.sensor = sensor
+        super().__init__(runner)
+
+    def _make_packed(self):
+        ac = self.alg.actor_critic
+        if not PackedVisionPolicy.supported(ac):
+            raise lib.LsimError("VisionRollout: the fused policy launch does not take this topology (use the eager rollout)")
+        return PackedVisionPolicy(ac)
+
+    def _act(self):
+        env, ac = self.env, self.alg.actor_critic
+        self.alg.snapshot_if_due(self.storage.step, env.privileged_obs_buf)
+        prev, self._pending_post = self._pending_post, None
+        self.packed.forward_act(self._S, self.storage.step, self._draw_host, env.obs_buf, env.privileged_obs_buf, ac.std, self._seed, self._rank,
+                                self.mean, self.values, self.actions, prev=prev, rows=self.sensor.latent(), store=self.storage.depth_latent)
+
+
+class VisionOnPolicyRunner(HIMOnPolicyRunner):
+    """HIMOnPolicyRunner for a vision policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs a
+    SensorModel (the frame history).  `encoder`: a DepthEncoder for its frames; default DepthEncoder(height, width, frames).  The runner
+    attaches the encoder to the sensor.  train_cfg is HIMOnPolicyRunner's; policy["depth_latent_dim"] is set from the encoder and
+    algorithm["aux_snapshots"] / ["aux_learning_rate"] are optional."""
+
+    def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None):
+        cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
+        if getattr(cam, "model", None) is None:
+            raise ValueError("VisionOnPolicyRunner: the sensor has no SensorModel, so no frame history to encode")
+        scan = height_scan_block(env.cfg)
+        if encoder is None:
+            if not (hasattr(cam, "height") and hasattr(cam, "width")):
+                raise ValueError("VisionOnPolicyRunner: the sensor is no camera (no height / width): pass an encoder for its frames")
+            from .depth_encoder import DepthEncoder
+            encoder = DepthEncoder(cam.height, cam.width, cam.model.frames)
+        encoder = encoder.to(device)
+        _POLICIES["VisionActorCritic"], _ALGOS["VisionPPO"] = VisionActorCritic, VisionPPO
+        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
+        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "VisionPPO"
+        cfg["policy"]["depth_latent_dim"] = encoder.latent_dim
+        self.sensor = cam
+        super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
+        cam.attach_encoder(encoder)         # behind the parent's env.reset(): the sensor has captured, so every env is encoded now
+        frames = cam.frame_images if hasattr(cam, "frame_images") else (lambda: cam.frames().unflatten(2, (encoder.height, encoder.width)))
+        self.alg.attach(encoder, cam.latent, frames, scan)
+
+    def _make_fused_rollout(self):
+        return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
+
+    def _extra_checkpoint_state(self):
+        out = super()._extra_checkpoint_state()
+        alg = self.alg
+        out.update(depth_encoder_state_dict=alg.encoder.state_dict(), depth_head_state_dict=alg.depth_head.state_dict(),
+                   depth_optimizer_state_dict=alg.aux_optimizer.state_dict())
+        return out
+
+    def _load_extra_checkpoint_state(self, d):
+        super()._load_extra_checkpoint_state(d)
+        alg = self.alg
+        if "depth_encoder_state_dict" in d:
+            alg.encoder.load_state_dict(d["depth_encoder_state_dict"])
+            alg.depth_head.load_state_dict(d["depth_head_state_dict"])
+            alg.aux_optimizer.load_state_dict(d["depth_optimizer_state_dict"])

@@ -1,0 +1,81 @@
+"""Collection and update time per iteration of VisionOnPolicyRunner next to HIMOnPolicyRunner on the same env configuration, both with the
+depth camera attached (the HIM runner merely does not read it), and the encoder's own step separately.
+
+    python tools/vision_train_time.py [--envs 4096] [--iters 6] [--warmup 2] [--out profiles/vision_train_time.json]
+
+Wall clock around device synchronisations, as the runners' own last_perf; the encoder step with HIP events inside VisionPPO.update()."""
+import argparse, json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+DEV = "cuda:0"
+
+
+def make(kind, a):
+    from isaacgymloco_amd.envs import config as C, sensors
+    from isaacgymloco_amd.envs.legged_robot import LeggedRobot
+    from isaacgymloco_amd.learn.bench_train import train_cfg_dict
+    from isaacgymloco_amd.learn.runner import HIMOnPolicyRunner
+    from isaacgymloco_amd.learn.vision import VisionOnPolicyRunner
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = a.envs
+    env = LeggedRobot(cfg, sim_device=DEV, seed=1)
+    cam = env.add_sensor("depth", sensors.depth_camera(env, a.width, a.height, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0,
+                                                       model=sensors.SensorModel(period=5, stagger=True, latency=1, frames=2, normalise=True)))
+    tc = train_cfg_dict("aliengo")
+    torch.manual_seed(0)
+    if kind == "vision":
+        run = VisionOnPolicyRunner(env, tc, sensor="depth", device=DEV)
+    else:
+        from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
+        cam.attach_encoder(DepthEncoder(a.height, a.width, 2).to(DEV))      # the same launches per step; nobody reads the latent
+        run = HIMOnPolicyRunner(env, tc, log_dir=None, device=DEV)
+    assert run.enable_graphs()
+    return run
+
+
+def measure(kind, a):
+    run = make(kind, a)
+    enc_ms = []
+    if kind == "vision":
+        alg, step = run.alg, run.alg.encoder_step
+
+        def timed_step():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = step(); e1.record()
+            enc_ms.append((e0, e1))
+            return out
+        alg.encoder_step = timed_step
+    rows = []
+    for it in range(a.warmup + a.iters):
+        run.learn(1)
+        if it >= a.warmup:
+            rows.append((run.last_perf["collection_time"], run.last_perf["learn_time"]))
+    torch.cuda.synchronize()
+    med = lambda v: sorted(v)[len(v) // 2]
+    out = {"collection_s": med([r[0] for r in rows]), "update_s": med([r[1] for r in rows]), "iterations": len(rows),
+           "collection_s_all": [r[0] for r in rows], "update_s_all": [r[1] for r in rows]}
+    if enc_ms:
+        out["encoder_step_s"] = med([e0.elapsed_time(e1) * 1e-3 for e0, e1 in enc_ms[a.warmup:]])
+        out["aux_loss"] = run.alg.last_aux_loss
+    del run
+    torch.cuda.empty_cache()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--width", type=int, default=64)
+    ap.add_argument("--height", type=int, default=48)
+    ap.add_argument("--iters", type=int, default=6)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vision_train_time.json"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("vision_train_time.py needs a GPU: there is no CPU form of this measurement")
+    res = {"what": "seconds per PPO iteration (100 steps), median; update_s of the vision runner includes encoder_step_s", "num_envs": a.envs,
+           "camera": [a.width, a.height], "device": torch.cuda.get_device_name(0), "him": measure("him", a), "vision": measure("vision", a)}
+    print(json.dumps(res))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    json.dump(res, open(a.out, "w"), indent=1)
