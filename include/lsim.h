@@ -43,7 +43,8 @@ extern "C" {
                                     lsim_raycast_bodies + lsim_raycast_bodies_sizes (the same sensors also see the env's own robot);
                                     lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise);
                                     lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only);
-                                    lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters) */
+                                    lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters);
+                                    lsim_eval_columns + lsim_eval_columns_sizes / _clear / _accumulate (caller-supplied columns into the evaluator's groups) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -953,6 +954,40 @@ int lsim_eval_clear(const lsim_eval* e, void* stream);
  * 1..LSIM_TERRAIN_TYPES_MAX, num_levels outside 1..LSIM_TERRAIN_LEVELS_MAX, group_by with unknown bits, num_groups != product of the kept
  * extents, num_trace_envs outside 0..LSIM_EVAL_MAX_TRACE_ENVS, trace_capacity < 1, a trace env or a feet body out of range. */
 int lsim_eval_accumulate(const lsim_eval* e, void* stream);
+
+/* ---- caller-supplied per-env columns into the evaluator's groups: what lsim_eval's fixed metric set does not hold (a vision policy's
+ * depth influence, its encoder's scan error, ...), accumulated under the same guarantees -- 2^-32 fixed-point int64 words, integer atomics
+ * only, bitwise reproducible, ONE launch, no host synchronisation, no floating-point atomic anywhere.
+ *
+ * One lsim_eval_columns_accumulate launch, per env e:
+ *   e contributes only if reset_buf[e] == 0, its latched group g1 = group1[e] of `state` (group + 1; 0: none latched yet) is non-zero and
+ *   g1 - 1 < num_groups; otherwise nothing is written for it.  A contributing env adds to row g1 - 1 of `table`:
+ *     word 0 += 1
+ *     for column k, v = values[e * ld + k]:   v finite     -> sum_k += fix(v), sq_k += fix(v * v)     (the product is ONE fp32 multiply; fix is
+ *                                                             lsim_eval's, clamp to +-2^20 included, so an overflowing square adds the clamp)
+ *                                             v not finite -> nonfinite_k += 1 and nothing else
+ *   Row layout: [samples | sum_0, sq_0, nonfinite_0 | sum_1, sq_1, nonfinite_1 | ...], 1 + LSIM_EVAL_COL_WORDS * num_cols words.
+ * Ordering: the launch goes AFTER lsim_eval_accumulate of the same env-step, on the same stream (that launch latches the groups).  Launched once
+ * per lsim_eval_accumulate from the first one on, word 0 equals the main table's SAMPLES word group by group.  The launch reads `state` and
+ * never writes it; the evaluator's launch counter stays lsim_eval_accumulate's.  Before the first lsim_eval_accumulate no group is latched and
+ * the launch adds nothing. */
+#define LSIM_EVAL_MAX_COLUMNS 6
+#define LSIM_EVAL_COL_WORDS 3     /* per column: sum, sum of squares, non-finite count */
+typedef struct lsim_eval_columns {
+    const void* state;            /* the lsim_eval.state whose latched groups are used; READ ONLY here; 16-byte aligned */
+    const uint8_t* reset_buf;     /* [N], the one the evaluator reads */
+    const float* values;          /* [N, ld] fp32, 4-byte aligned */
+    int64_t* table;               /* [num_groups, 1 + 3 * num_cols] int64, 8-byte aligned */
+    int64_t num_envs;             /* the evaluator's */
+    int32_t num_groups, num_cols, ld;   /* 1 <= num_cols <= LSIM_EVAL_MAX_COLUMNS, ld >= num_cols */
+} lsim_eval_columns;
+/* bytes of the table.  LSIM_E_INVALID: num_groups outside 1..LSIM_EVAL_MAX_GROUPS, num_cols outside 1..LSIM_EVAL_MAX_COLUMNS, a NULL output pointer. */
+int lsim_eval_columns_sizes(int num_groups, int num_cols, size_t* table_bytes);
+/* zero the table (one memset on the stream); the argument checks of lsim_eval_columns_accumulate */
+int lsim_eval_columns_clear(const lsim_eval_columns* c, void* stream);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch: c == NULL, a NULL or misaligned pointer, num_envs outside
+ * what lsim_eval_sizes accepts, num_groups outside 1..LSIM_EVAL_MAX_GROUPS, num_cols outside 1..LSIM_EVAL_MAX_COLUMNS, ld < num_cols. */
+int lsim_eval_columns_accumulate(const lsim_eval_columns* c, void* stream);
 
 /* ---- range sensors: rays against the terrain mesh (depth cameras, lidar; no reference FFI: the reference has no such sensor).
  * ONE launch, on the caller's stream, no host synchronisation, capturable in a graph.  The launch only READS the simulator's buffers,

@@ -105,6 +105,7 @@ LsimPolicyExtra = STRUCTS["lsim_policy_extra"]
 LsimWgradPending = STRUCTS["lsim_wgrad_pending"]
 LsimAmpDisc = STRUCTS["lsim_amp_disc"]
 LsimEval = STRUCTS["lsim_eval"]
+LsimEvalColumns = STRUCTS["lsim_eval_columns"]
 LsimRaycast = STRUCTS["lsim_raycast_t"]
 LsimRaycastBodies = STRUCTS["lsim_raycast_bodies_t"]
 LsimRaycastRobot = STRUCTS["lsim_raycast_robot"]

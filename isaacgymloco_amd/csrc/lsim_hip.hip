@@ -22,6 +22,7 @@ static void lsbk_prof_free(lsim_sim* s);
 #include "ls_api_impl.h"
 #include "ls_kernels.h"
 #include "ls_eval.h"      // policy evaluation (lsim_eval_*): reads the simulator's buffers through raw pointers, touches neither LsCtx nor kernels A / B
+#include "ls_eval_columns.h"      // caller-supplied columns into the evaluator's groups (lsim_eval_columns_*): reads the evaluator's state, writes its own table
 #include "ls_raycast.h"   // range sensors (lsim_raycast): rays against LSIM_BUF_TERRAIN_MESH through raw pointers, likewise apart from kernels A / B
 #include "ls_raycast_bodies.h"   // the same sensors seeing the env's own robot (lsim_raycast_bodies): a launch of its own, shares the terrain walk
 #include "ls_sensor_model.h"     // the sensor model (lsim_sensor_capture): the same casts for the envs that are due, then noise / dropout / clip and the frame history

@@ -119,6 +119,7 @@ class RaySensor:
         if frame not in ("base", "yaw"):
             raise ValueError(f"frame: expected 'base' or 'yaw', got {frame!r}")
         self.see_robot, self.frame = bool(see_robot), frame
+        self.body_mask, self.body_names = None, []
         self._bodies = self.see_robot or frame == "yaw"       # the yaw frame is the new entry point's, with or without bodies
         if (labels or len(tuple(ignore_bodies))) and not self.see_robot:
             raise ValueError("labels / ignore_bodies need see_robot=True")
@@ -326,6 +327,37 @@ class RaySensor:
             raise ValueError("the sensor was created without labels=True")
         return self._labels[:, :self.num_rays]
 
+    def spec(self):
+        """What rebuilds this sensor on another env (from_spec), as a dict of plain Python values and lists -- a checkpoint's record of the
+        instrument a policy was trained with: kind ("camera" with width / height, "lidar" with channels / points_per_rev, else "rays"),
+        dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
+        without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None."""
+        out = {"kind": "rays"}
+        if hasattr(self, "width") and hasattr(self, "height"):
+            out.update(kind="camera", width=int(self.width), height=int(self.height))
+        elif hasattr(self, "channels") and hasattr(self, "points_per_rev"):
+            out.update(kind="lidar", channels=int(self.channels), points_per_rev=int(self.points_per_rev))
+        out["dirs"] = self.dirs.cpu().tolist()
+        out["scale"] = None if self.scale is None else self.scale.cpu().tolist()
+        out.update(near=self.near, far=self.far, env_stride=self.env_stride, see_robot=self.see_robot, labels=self._labels is not None, frame=self.frame)
+        mask = self.body_mask if self.see_robot else None
+        out["ignore_bodies"] = [] if mask is None else [n for i, n in enumerate(self.body_names) if not mask >> i & 1]
+        m = self.model
+        out["model"] = None if m is None else {"period": m.period, "stagger": m.stagger, "latency": m.latency, "frames": m.frames, "noise": list(m.noise),
+                                               "dropout": m.dropout, "drop_value": m.drop_value, "clip": None if m.clip is None else list(m.clip),
+                                               "normalise": m.normalise}
+        mount = self.mount.cpu()
+        pose = lambda row: {"pos": row[:3].tolist(), "quat": row[3:].tolist()}
+        names, ids = getattr(self.env, "robot_names", None), getattr(self.env, "robot_ids", None)
+        rows = [] if names is None or ids is None else [mount[ids.cpu() == k] for k in range(len(names))]
+        if bool((mount == mount[:1]).all()):
+            out["mount"] = pose(mount[0])
+        elif rows and all(bool((r == r[:1]).all()) for r in rows):
+            out["mount"] = {n: pose(r[0]) for n, r in zip(names, rows) if len(r)}
+        else:
+            out["mount"] = None
+        return out
+
     @property
     def nonfinite_rays(self):
         """0-d device tensor: rays so far whose origin or direction was not finite (they report `far`); must stay 0"""
@@ -366,3 +398,33 @@ def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mo
                   see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model)
     s.channels, s.points_per_rev = int(channels), int(points_per_rev)
     return s
+
+
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None):
+    """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
+    RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
+    per-robot mount that lacks one of the env's robots (RaySensor's own check)."""
+    mount = spec.get("mount")
+    if mount is not None and "pos" not in mount:
+        pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
+    elif mount is not None:
+        pos, quat = mount["pos"], mount["quat"]
+    else:
+        pos = quat = None
+    pos = mount_pos if mount_pos is not None else pos
+    quat = mount_quat if mount_quat is not None else quat
+    if pos is None or quat is None:
+        raise ValueError("from_spec: the recorded sensor's mount differed from env to env (spec['mount'] is None): pass mount_pos and mount_quat")
+    m = spec.get("model")
+    model = None if m is None else SensorModel(**m)
+    kind = spec.get("kind", "rays")
+    cls = DepthCamera if kind == "camera" else RaySensor
+    sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
+    if kind == "camera":
+        sensor.width, sensor.height = int(spec["width"]), int(spec["height"])
+    RaySensor.__init__(sensor, env, np.asarray(spec["dirs"], dtype=np.float32), pos, quat, spec["near"], spec["far"],
+                       scale=None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32), env_stride=spec["env_stride"], api=api,
+                       see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"], frame=spec["frame"], model=model)
+    if kind == "lidar":
+        sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
+    return sensor

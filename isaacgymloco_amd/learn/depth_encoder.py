@@ -105,6 +105,12 @@ class DepthEncoder(nn.Module):
         self.conv2 = nn.Conv2d(de.c1, de.c2, de.k2, de.s2)
         self.fc = nn.Linear(de.c2 * self.h2 * self.w2, self.latent_dim)
 
+    def config(self):
+        """the constructor's keywords as plain Python values: DepthEncoder(**enc.config()) has this encoder's shapes (a checkpoint's record)"""
+        de = self._extents
+        return {"height": self.height, "width": self.width, "frames": self.frames, "c1": int(de.c1), "k1": int(de.k1), "s1": int(de.s1),
+                "c2": int(de.c2), "k2": int(de.k2), "s2": int(de.s2), "latent_dim": self.latent_dim, "final_act": self.final_act}
+
     def forward(self, frames):
         x = F.elu(self.conv1(frames))
         x = F.elu(self.conv2(x))

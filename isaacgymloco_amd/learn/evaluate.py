@@ -1,7 +1,7 @@
 """Evaluate a trained policy on the device: metrics per robot x terrain type x terrain level, and state traces of chosen envs.
 
     python -m isaacgymloco_amd.learn.evaluate --task aliengo [--robots aliengo=0.5,go2=0.5] --checkpoint model.pt --envs 4096 --steps 1000 \
-        --commands 1.0,0,0 --out eval.json [--trace-envs 0,1 --trace-out trace.npz]
+        --commands 1.0,0,0 --out eval.json [--trace-envs 0,1 --trace-out trace.npz] [--blind] [--vision-metrics depth_influence,scan_error]
 
 The evaluation half of the reference's legged_gym/scripts/play.py (fixed commands, randomisation off, deterministic actions; play.py:66-85 and
 play.py:124-133).  Every env-step costs ONE extra HIP launch, `lsim_eval_accumulate` (include/lsim.h states the semantics; csrc/ls_eval.h is the
@@ -27,6 +27,8 @@ SAT_THRESHOLD = abi.DEFINES["LSIM_EVAL_SAT_PERMILLE"] / 1000.0
 FIX_ONE = 2.0 ** 32
 CLAMP = float(2 ** 20)
 W = abi.EVAL_WORDS
+MAX_COLUMNS = abi.DEFINES["LSIM_EVAL_MAX_COLUMNS"]
+COL_WORDS = abi.DEFINES["LSIM_EVAL_COL_WORDS"]
 # name -> (first column, width) of a trace row, in the order of the LSIM_EVAL_TR_* offsets
 _TR = sorted(((v, k[len("LSIM_EVAL_TR_"):].lower()) for k, v in abi.DEFINES.items() if k.startswith("LSIM_EVAL_TR_")))
 TRACE_COLUMNS = {name: (start, (_TR[i + 1][0] if i + 1 < len(_TR) else TRACE_DIM) - start) for i, (start, name) in enumerate(_TR)}
@@ -117,6 +119,17 @@ def metrics_of_row(row):
     }
 
 
+def columns_of_row(row, names):
+    """One row of the columns table ([samples | sum, sum of squares, non-finite count per column], or a sum of rows) -> {name: mean, rms, nonfinite}"""
+    row = [int(v) for v in row]
+    n = row[0]
+    out = {}
+    for k, name in enumerate(names):
+        s, q, bad = row[1 + COL_WORDS * k:1 + COL_WORDS * (k + 1)]
+        out[name] = {"mean": s / FIX_ONE / n if n else float("nan"), "rms": (q / FIX_ONE / n) ** 0.5 if n else float("nan"), "nonfinite": bad}
+    return out
+
+
 def total_row(table):
     """sum of the rows of an int64 table [groups, words]: integer sums, except the peak word (a maximum)"""
     tot = table.sum(axis=0)
@@ -173,13 +186,45 @@ class Evaluator:
         for k, i in enumerate(self.trace_envs):
             e.trace_envs[k] = i
         self._e = e
+        self.column_names, self.columns, self.col_table, self._c = (), None, None, None
         self.clear()
+
+    def add_columns(self, names):
+        """Up to LSIM_EVAL_MAX_COLUMNS named per-env values of the caller's, accumulated per group next to the evaluator's own metrics
+        (include/lsim.h, lsim_eval_columns): `.columns` is the [N, len(names)] fp32 device tensor to write before each
+        `.accumulate_columns()`, which goes after `.accumulate()` of the same env-step.  Once per evaluator."""
+        names = tuple(str(n) for n in names)
+        if self._c is not None:
+            raise ValueError("add_columns: the evaluator already has columns")
+        if not 1 <= len(names) <= MAX_COLUMNS or len(set(names)) != len(names):
+            raise ValueError(f"add_columns: 1 to {MAX_COLUMNS} unique names, got {list(names)}")
+        for fn in ("lsim_eval_columns_sizes", "lsim_eval_columns_clear", "lsim_eval_columns_accumulate"):
+            if not hasattr(self._L, fn):
+                raise lib.LsimError(f"the loaded library has no {fn}: rebuild it (there is no torch fall-back for the evaluator's columns)")
+        dev, N = self.table.device, int(self.env.num_envs)
+        tb = ctypes.c_size_t()
+        lib.check(self._L.lsim_eval_columns_sizes(self.num_groups, len(names), ctypes.byref(tb)), what="lsim_eval_columns_sizes")
+        self.columns = torch.zeros(N, len(names), dtype=torch.float32, device=dev)
+        self.col_table = torch.zeros(self.num_groups, tb.value // 8 // self.num_groups, dtype=torch.int64, device=dev)
+        c = abi.LsimEvalColumns()
+        c.state, c.reset_buf, c.values, c.table = self.state.data_ptr(), self._e.reset_buf, self.columns.data_ptr(), self.col_table.data_ptr()
+        c.num_envs, c.num_groups, c.num_cols, c.ld = N, self.num_groups, len(names), self.columns.stride(0)
+        self._c, self.column_names = c, names
+        lib.check(self._L.lsim_eval_columns_clear(ctypes.byref(c), self._stream()), what="lsim_eval_columns_clear")
+        return self.columns
+
+    def accumulate_columns(self):
+        if self._c is None:
+            raise ValueError("accumulate_columns: the evaluator has no columns (add_columns)")
+        lib.check(self._L.lsim_eval_columns_accumulate(ctypes.byref(self._c), self._stream()), what="lsim_eval_columns_accumulate")
 
     def _stream(self):
         return self.env._stream()
 
     def clear(self):
         lib.check(self._L.lsim_eval_clear(ctypes.byref(self._e), self._stream()), what="lsim_eval_clear")
+        if self._c is not None:
+            lib.check(self._L.lsim_eval_columns_clear(ctypes.byref(self._c), self._stream()), what="lsim_eval_columns_clear")
 
     def accumulate(self):
         lib.check(self._L.lsim_eval_accumulate(ctypes.byref(self._e), self._stream()), what="lsim_eval_accumulate")
@@ -200,8 +245,15 @@ class Evaluator:
         conv = dict(env._conventions()) if hasattr(env, "_conventions") else {"abi_version": int(abi.ABI_VERSION)}
         conv.update({"addend_clamp": CLAMP, "fixed_point_scale": FIX_ONE, "torque_saturation_threshold": SAT_THRESHOLD,
                      "robot_names": self.robot_names, "num_types": self.num_types, "num_levels": self.num_levels})
+        total = metrics_of_row(total_row(table))
+        if self._c is not None:             # word 0 of a columns row is the main row's `samples`, so the same groups are listed
+            ctable = self.col_table.cpu().numpy()
+            for grp in groups:
+                grp["columns"] = columns_of_row(ctable[key_index(self.mask, self.shape, grp["key"], self.robot_names)], self.column_names)
+            total["columns"] = columns_of_row(ctable.sum(axis=0), self.column_names)
+            conv["columns"] = list(self.column_names)
         return {"group_by": [g for g in ("robot", "type", "level") if self.mask & GROUP_BITS[g]], "num_envs": int(env.num_envs), "steps": self.steps,
-                "dt": float(env.dt), "groups": groups, "total": metrics_of_row(total_row(table)),
+                "dt": float(env.dt), "groups": groups, "total": total,
                 "nonfinite": {"addends": int(table[:, W["nonfinite"]].sum()), "simulator_env_steps": int(env.nonfinite_envs.item())},
                 "conventions": conv}
 
@@ -226,13 +278,18 @@ def check_conventions(saved, live):
             raise ValueError(f"checkpoint conventions differ from the env's in {k!r}: saved {saved.get(k)!r}, live {live.get(k)!r}")
 
 
-def _actor_critic(env, policy, device):
-    """HIMActorCritic from a module, a runner, or a checkpoint path written by runner.save"""
+def _actor_critic(env, policy, device, vision=None):
+    """HIMActorCritic (or VisionActorCritic) from a module, a runner, or a checkpoint path written by runner.save.  `vision`: a dict that
+    receives what a vision policy brings along -- "sensor", "encoder", "depth_head" from a VisionOnPolicyRunner; from a checkpoint its
+    "checkpoint" (the loaded dict), for _vision_parts to build encoder and head from"""
     from .modules import HIMActorCritic
-    if isinstance(policy, HIMActorCritic):
+    vision = vision if vision is not None else {}
+    if isinstance(policy, HIMActorCritic):     # VisionActorCritic is one
         return policy
     if hasattr(policy, "alg"):                 # a runner
         policy.get_inference_policy()          # flushes a deferred rollout store, eval mode
+        if getattr(policy.alg, "encoder", None) is not None:
+            vision.update(sensor=getattr(policy, "sensor", None), encoder=policy.alg.encoder, depth_head=policy.alg.depth_head)
         return policy.alg.actor_critic
     if isinstance(policy, str):
         d = torch.load(policy, map_location=device, weights_only=False)
@@ -245,21 +302,129 @@ def _actor_critic(env, policy, device):
                             critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
         if enc != [l.out_features for l in ac.estimator.encoder if isinstance(l, torch.nn.Linear)]:
             raise ValueError(f"checkpoint estimator encoder widths {enc} differ from the default HIMEstimator's: pass the HIMActorCritic itself")
+        extra = sd["actor.0.weight"].shape[1] - ac.actor[0].in_features
+        if extra > 0 and "depth_encoder_state_dict" in d:       # a vision policy: the depth columns come last (learn/vision.py)
+            from .vision import VisionActorCritic
+            ac = VisionActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, depth_latent_dim=extra,
+                                   actor_hidden_dims=tuple(actor[:-1]), critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
+            vision["checkpoint"] = d
         ac.load_state_dict(sd)
         ac.eval()
         return ac
     raise TypeError(f"policy must be a HIMActorCritic, a runner or a checkpoint path, got {type(policy).__name__}")
 
 
+def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
+    """(sensor, encoder, depth head or None) of a vision policy: the caller's keywords first, then what the runner or the checkpoint
+    brought (`found`, from _actor_critic).  The encoder ends up attached to the sensor (every capture is followed by its launch)."""
+    from .depth_encoder import DepthEncoder
+    cam = sensor if sensor is not None else found.get("sensor")
+    if cam is None:
+        cam = getattr(env, "sensors", {}).get("depth")
+    if cam is None or getattr(cam, "model", None) is None:
+        raise ValueError("evaluate: a vision policy needs a sensor with a SensorModel (sensor=..., or env.add_sensor('depth', ...))")
+    enc = encoder if encoder is not None else found.get("encoder")
+    head = depth_head if depth_head is not None else found.get("depth_head")
+    d = found.get("checkpoint")
+    if d is not None:
+        if enc is None:
+            record = (d.get("vision") or {}).get("encoder")
+            if record is None:
+                raise ValueError("evaluate: the checkpoint has no 'vision' record (vision['encoder'], the depth encoder's hyperparameters): "
+                                 "pass encoder=DepthEncoder(...) with the shapes it was trained with")
+            enc = DepthEncoder(**record)
+        enc.load_state_dict(d["depth_encoder_state_dict"])
+        if head is None and "depth_head_state_dict" in d:
+            w = d["depth_head_state_dict"]["weight"]
+            head = torch.nn.Linear(w.shape[1], w.shape[0])
+            head.load_state_dict(d["depth_head_state_dict"])
+    if enc is None:
+        raise ValueError("evaluate: a VisionActorCritic needs its depth encoder (encoder=...): nobody else can hand it a latent")
+    if enc.latent_dim != ac.depth_latent_dim:
+        raise ValueError(f"evaluate: the encoder's latent has {enc.latent_dim} columns, the actor reads {ac.depth_latent_dim}")
+    enc = enc.to(device).eval()
+    head = head.to(device).eval() if head is not None else None
+    if getattr(cam, "_encoder", None) is not enc:
+        cam.attach_encoder(enc)
+    return cam, enc, head
+
+
+def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics):
+    """evaluate()'s loop for a VisionActorCritic: the actor also reads the sensor's live latent rows (zeros when `blind`), and the evaluator
+    accumulates the `metrics` as columns (module docstring of learn/vision.py)"""
+    from .vision import PackedVisionPolicy, height_scan_block
+    dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
+    metrics = list(metrics)
+    for m in metrics:
+        if m not in ("depth_influence", "scan_error"):
+            raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error'")
+    scan = None
+    if "scan_error" in metrics:         # needs the auxiliary head and a privileged observation that holds the scan: else dropped, not zero
+        try:
+            scan = height_scan_block(env.cfg) if head is not None else None
+        except ValueError:
+            scan = None
+        if scan is None:
+            metrics.remove("scan_error")
+    if metrics and ev.column_names != tuple(metrics):
+        ev.add_columns(metrics)
+    use_fused = PackedVisionPolicy.supported(ac) if fused is None else bool(fused)
+    if use_fused and not PackedVisionPolicy.supported(ac):
+        raise ValueError("fused=True but lsim_policy_forward_ext does not support this policy's topology")
+    if hasattr(env, "_external_call"):
+        env._external_call()
+    zeros = torch.zeros(N, L, device=dev)
+    if use_fused:
+        packed = PackedVisionPolicy(ac)
+        mean, mean0 = torch.empty(N, env.num_actions, device=dev), torch.empty(N, env.num_actions, device=dev)
+        values = torch.empty(N, 1, device=dev)
+    influence = "depth_influence" in metrics
+    obs, priv = env.get_observations(), env.get_privileged_observations()
+    for _ in range(int(steps)):
+        if cmd is not None:
+            env.commands[:, :3] = cmd
+        live = cam.latent()
+        rows = zeros if blind else live
+        if use_fused:
+            packed.forward(obs, priv, mean, values, rows=rows)
+            actions = mean
+            if influence and not blind:
+                packed.forward(obs, priv, mean0, values, rows=zeros)
+        else:
+            actions = ac.act_inference(obs, depth_latent=rows)
+            if influence and not blind:
+                mean0 = ac.act_inference(obs, depth_latent=zeros)
+        for k, m in enumerate(metrics):     # from the observation the action came from; the step's reset flags decide what counts
+            if m == "depth_influence":
+                ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
+            else:
+                ev.columns[:, k] = (head(live) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
+        env.step_device(actions)
+        ev.accumulate()
+        if metrics:
+            ev.accumulate_columns()
+    return ev
+
+
 @torch.no_grad()
-def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None):
+def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
+             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=("depth_influence", "scan_error")):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
-    No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`)."""
+    No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
+    A vision policy (a VisionActorCritic, a VisionOnPolicyRunner, or a checkpoint of one) also reads the latent of `sensor` (default: the
+    runner's, else env.sensors["depth"]) through `encoder` (default: the runner's, else rebuilt from the checkpoint's `vision` record);
+    `blind=True` feeds zeros instead.  `vision_metrics` become columns of the result: "depth_influence" = the L2 distance of the action
+    mean from the mean with a zero latent (one more policy forward per step), "scan_error" = the mean square error of `depth_head` (the
+    encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
-    ac = _actor_critic(env, policy, dev)
+    found = {}
+    ac = _actor_critic(env, policy, dev, found)
     ac.eval()
+    is_vision = hasattr(ac, "depth_latent_dim")
+    if is_vision:
+        cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -267,6 +432,8 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         cmd = cmd.expand(env.num_envs, 3).contiguous() if cmd.dim() == 1 else cmd.contiguous()
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
+    if is_vision:
+        return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()))
     use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
     if use_fused and not PackedHimPolicy.supported(ac):
         raise ValueError("fused=True but lsim_policy_forward does not support this policy's topology")
@@ -293,10 +460,12 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
 def format_table(result):
     cols = ("samples", "episodes", "fall_rate", "lin_vel_error_rms", "yaw_rate_error_rms", "mechanical_power_mean", "torque_saturation_rate",
             "episode_return_mean", "episode_length_mean", "episode_distance_mean")
-    lines = [" ".join([f"{'group':<28}"] + [f"{c[:14]:>14}" for c in cols])]
+    extra = tuple(result["total"].get("columns", ()))          # the caller's columns (Evaluator.add_columns): their means, after the fixed ones
+    lines = [" ".join([f"{'group':<28}"] + [f"{c[:14]:>14}" for c in cols + extra])]
     for g in result["groups"] + [{"key": {"all": ""}, **result["total"]}]:
         name = " ".join(f"{k}={v}" if v != "" else k for k, v in g["key"].items()) or "all"
-        lines.append(" ".join([f"{name:<28}"] + [f"{g[c]:>14d}" if isinstance(g[c], int) else f"{g[c]:>14.4f}" for c in cols]))
+        lines.append(" ".join([f"{name:<28}"] + [f"{g[c]:>14d}" if isinstance(g[c], int) else f"{g[c]:>14.4f}" for c in cols] +
+                              [f"{g['columns'][c]['mean']:>14.6f}" for c in extra]))
     return "\n".join(lines)
 
 
@@ -314,6 +483,8 @@ def parse_args(argv=None):
     ap.add_argument("--out", required=True)
     ap.add_argument("--trace-envs", default="")
     ap.add_argument("--trace-out", default=None)
+    ap.add_argument("--blind", action="store_true", help="a vision policy acts on a zero latent instead of its camera's")
+    ap.add_argument("--vision-metrics", default="depth_influence,scan_error", help="columns a vision policy adds to the result; empty: none")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -329,6 +500,9 @@ def parse_args(argv=None):
         if len(a.commands) != 3:
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
+    a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
+    if any(m not in ("depth_influence", "scan_error") for m in a.vision_metrics):
+        ap.error(f"--vision-metrics: 'depth_influence' and / or 'scan_error', got {a.vision_metrics}")
     try:
         group_mask(a.group_by)
     except ValueError as exc:
@@ -357,7 +531,12 @@ def main(argv=None):
     cfg.env.num_envs = a.envs
     env = LeggedRobot(cfg, sim_device=a.device, seed=a.seed)
     env.reset()
-    ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs)
+    record = torch.load(a.checkpoint, map_location="cpu", weights_only=False).get("vision") or {}
+    if record.get("sensor") is not None:       # a vision policy's checkpoint names the camera it was trained with
+        from ..envs.sensors import from_spec
+        env.add_sensor("depth", from_spec(env, record["sensor"]))
+    ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
+                  vision_metrics=a.vision_metrics)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

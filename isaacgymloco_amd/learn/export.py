@@ -3,6 +3,9 @@
 
 The exported TorchScript module maps an observation history [B, 270] to action means [B, 12]:
     encoder(obs)[:, :19] -> (velocity[3], L2-normalised latent[16]);  actor(cat(obs[:, :45], velocity, latent)).
+A vision policy (learn/vision.py) exports as PolicyExporterVision: the same two networks with the wider first actor layer, plain copies of
+the depth encoder's three layers and the sensor model's clip / normalisation constants, so that the robot's program needs nothing but the file:
+    preprocess(depth in metres) -> frames;  encode(frames) -> latent, at camera rate;  act(obs_history, latent) -> action means, at control rate.
 The build's networks are `HimMLP` / `SkinnyLinear` modules (nn.Sequential / nn.Linear subclasses whose forward dispatches to the HIP
 weight-gradient kernels under autograd), which TorchScript cannot script; the exporter therefore re-materialises the two networks as plain
 `nn.Sequential(nn.Linear, nn.ELU, ...)` with the SAME weights -- exactly the module tree the reference scripts, so a file written here loads
@@ -56,8 +59,82 @@ class PolicyExporterHIM(nn.Module):
         return path
 
 
-def export_policy_as_jit(actor_critic, path):
-    """HLP:201-212.  `path` is a directory; returns the file written (policy.pt for HIM policies, policy_1.pt for a bare actor)."""
+class PolicyExporterVision(nn.Module):
+    """A VisionActorCritic with its DepthEncoder and the constants of the sensor it was trained with.  `sensor`: a RaySensor with a
+    SensorModel (envs/sensors.py) or its spec() (a checkpoint's vision["sensor"]).  Attributes clip_lo, clip_hi, offset, gain (lsim_sensor_capture's
+    clip and normalisation), period, latency, frames (how the robot must pace and delay its captures), height, width."""
+
+    def __init__(self, actor_critic, encoder, sensor):
+        super().__init__()
+        from ..envs.sensors import SensorModel
+        spec = sensor if isinstance(sensor, dict) else sensor.spec()
+        m = spec.get("model")
+        if m is None:
+            raise ValueError("PolicyExporterVision: the sensor has no SensorModel, so no frame history the encoder could have read")
+        model = SensorModel(**m)
+        if encoder.frames != model.frames or encoder.latent_dim != actor_critic.depth_latent_dim:
+            raise ValueError(f"PolicyExporterVision: the encoder reads {encoder.frames} frames and writes {encoder.latent_dim} columns; the sensor "
+                             f"keeps {model.frames}, the actor reads {actor_critic.depth_latent_dim}")
+        self.actor = plain_sequential(actor_critic.actor)
+        self.estimator = plain_sequential(actor_critic.estimator.encoder)
+        self.num_one_step_obs = int(actor_critic.num_one_step_obs)
+        self.num_enc_out = int(actor_critic.estimator.num_latent) + 3
+        self.conv1, self.conv2, self.fc = copy.deepcopy(encoder.conv1).cpu(), copy.deepcopy(encoder.conv2).cpu(), copy.deepcopy(encoder.fc).cpu()
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self.final_act = bool(encoder.final_act)
+        (lo, hi), offset, gain = model.offset_gain(float(spec["near"]), float(spec["far"]))
+        # the launch's own fp32 constants (lsim_sensor_model_t holds floats), so that preprocess is its arithmetic bit for bit
+        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+        self.clip_lo, self.clip_hi, self.offset, self.gain = f32(lo), f32(hi), f32(offset), f32(gain)
+        self.period, self.latency, self.frames = model.period, model.latency, model.frames
+        self.height, self.width = int(encoder.height), int(encoder.width)
+        self.latent_dim = int(encoder.latent_dim)
+
+    @torch.jit.export
+    def preprocess(self, depth_m: torch.Tensor) -> torch.Tensor:
+        """[B, H, W] depth in metres -> one frame as the policy was trained on it: the clip and normalise lines of lsim_sensor_capture, in
+        their order, without noise and holes"""
+        lo = torch.full_like(depth_m, self.clip_lo)
+        hi = torch.full_like(depth_m, self.clip_hi)
+        return (torch.minimum(torch.maximum(depth_m, lo), hi) - self.offset) * self.gain
+
+    @torch.jit.export
+    def encode(self, frames: torch.Tensor) -> torch.Tensor:
+        """[B, frames, H, W], oldest first -> latent [B, L]"""
+        x = F.elu(self.conv1(frames))
+        x = F.elu(self.conv2(x))
+        z = self.fc(torch.flatten(x, 1))
+        if self.final_act:
+            z = F.elu(z)
+        return z
+
+    @torch.jit.export
+    def act(self, obs_history: torch.Tensor, latent: torch.Tensor) -> torch.Tensor:
+        """PolicyExporterHIM.forward's estimator path, the depth columns last"""
+        parts = self.estimator(obs_history)[:, 0:self.num_enc_out]
+        vel, z = parts[..., :3], parts[..., 3:]
+        z = F.normalize(z, dim=-1, p=2.0)
+        return self.actor(torch.cat((obs_history[:, 0:self.num_one_step_obs], vel, z, latent), dim=1))
+
+    def forward(self, obs_history: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
+        return self.act(obs_history, self.encode(frames))
+
+    def export(self, path):
+        os.makedirs(path, exist_ok=True)
+        path = os.path.join(path, "policy.pt")
+        self.to("cpu")
+        torch.jit.script(self).save(path)
+        return path
+
+
+def export_policy_as_jit(actor_critic, path, encoder=None, sensor=None):
+    """HLP:201-212.  `path` is a directory; returns the file written (policy.pt for HIM and vision policies, policy_1.pt for a bare actor).
+    A vision policy needs its `encoder` and `sensor` (or the sensor's spec()): without them the module could not run, and this raises."""
+    if hasattr(actor_critic, "depth_latent_dim"):
+        if encoder is None or sensor is None:
+            raise ValueError("export_policy_as_jit: a vision policy exports with its depth encoder and sensor (encoder=..., sensor=...)")
+        return PolicyExporterVision(actor_critic, encoder, sensor).export(path)
     if hasattr(actor_critic, "estimator"):
         return PolicyExporterHIM(actor_critic).export(path)
     os.makedirs(path, exist_ok=True)

@@ -344,7 +344,16 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
         alg = self.alg
         out.update(depth_encoder_state_dict=alg.encoder.state_dict(), depth_head_state_dict=alg.depth_head.state_dict(),
                    depth_optimizer_state_dict=alg.aux_optimizer.state_dict())
+        cam = getattr(self, "sensor", None)           # what the policy was trained with: learn/evaluate.py and the exporter rebuild the pipeline from it
+        out["vision"] = {"encoder": alg.encoder.config(), "sensor": cam.spec() if hasattr(cam, "spec") else None,
+                         "latent_dim": int(alg.actor_critic.depth_latent_dim)}
         return out
+
+    def export(self, path):
+        """learn/export.py: export_policy_as_jit of this runner's actor-critic, encoder and sensor; `path` is a directory"""
+        from .export import export_policy_as_jit
+        self.get_inference_policy()
+        return export_policy_as_jit(self.alg.actor_critic, path, encoder=self.alg.encoder, sensor=self.sensor)
 
     def _load_extra_checkpoint_state(self, d):
         super()._load_extra_checkpoint_state(d)
