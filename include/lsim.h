@@ -44,7 +44,8 @@ extern "C" {
                                     lsim_sensor_capture + LSIM_RNG_SENSOR (the sensor model: update period, latency, frame history, noise);
                                     lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only);
                                     lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters);
-                                    lsim_eval_columns + lsim_eval_columns_sizes / _clear / _accumulate (caller-supplied columns into the evaluator's groups) */
+                                    lsim_eval_columns + lsim_eval_columns_sizes / _clear / _accumulate (caller-supplied columns into the evaluator's groups);
+                                    lsim_depth_memory_step + lsim_depth_memory_sizes, lsim_gru_sequence_forward / _backward (a GRU cell over the depth latent) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1307,6 +1308,99 @@ int lsim_depth_encode_backward_sizes(const lsim_depth_encoder_bwd_t* db, size_t*
  * height * width > hist_stride; hist_stride not a multiple of 4; c1, c2 outside 1..64; k1, k2 outside 1..8; s1, s2 outside 1..4; k1 > height or
  * width; k2 > h1 or w1; latent_dim outside 1..256; final_act outside 0..1; g_stride or latent_stride < latent_dim; the LDS bytes above the limit. */
 int lsim_depth_encode_backward(const lsim_depth_encoder_bwd_t* db, void* stream);
+
+/* ---- depth memory: ONE GRU cell (torch's nn.GRUCell, gate order r, z, n) behind the depth encoder, so that what the camera saw a second ago is
+ * still there when the hind feet reach it.  Three launches share the cell: lsim_depth_memory_step advances every env's hidden state by one
+ * control step during the rollout; lsim_gru_sequence_forward / _backward run the recurrence over a stored rollout chunk and back (truncated
+ * back-propagation through time; isaacgymloco_amd/learn/depth_memory.py joins them under autograd).  Same rules as every launch here: the
+ * caller's stream, no host synchronisation, raw pointers only, capturable in a graph, ONE launch per call.
+ *
+ * The cell.  The parameters stay in torch's own contiguous layout and are read where torch keeps them at every launch, so an optimiser step is
+ *   seen by the next one:  weight_ih [3H][I], weight_hh [3H][H], bias_ih [3H], bias_hh [3H];  rows 0..H-1 are gate r, H..2H-1 gate z (called u
+ *   below: z is the latent), 2H..3H-1 gate n.
+ *     x    = [ z_e (L columns of the encoder's latent row) | p_e (P columns of the env's one-step observation; P may be 0) ],   I = L + P
+ *     gi   = W_ih x + b_ih                       gh = W_hh h_prev + b_hh
+ *     r    = sigmoid(gi_r + gh_r)                u  = sigmoid(gi_z + gh_z)             n = tanh(gi_n + r * gh_n)
+ *     h'   = (1 - u) * n + u * h_prev            sigmoid(v) = 1 / (1 + exp(-v))
+ *   Note r * (W_hn h + b_hn), not W_hn (r * h).  Every sum is fp32, in any order, and a product and a sum may be fused.
+ * Limits.  hidden is a multiple of 16, at most LSIM_GRU_MAX_HIDDEN; I <= LSIM_GRU_MAX_INPUT.  The two sequence kernels keep W_hh resident in the
+ *   workgroup's LDS, so lsim_depth_memory_sizes -- and with it all three launches -- ACCEPTS hidden in {16, 32, 48, 64, 80, 96} and REFUSES 112
+ *   and 128 (their plan is above LSIM_GRU_MAX_LDS_BYTES).
+ *
+ * lsim_depth_memory_step.  A workgroup owns 16 consecutive envs.  For env e
+ *     fresh = (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0      (the rule of lsim_sensor_capture for a reset: no tick argument)
+ *     h_prev = fresh ? 0 : h[e]
+ *   flags 0: every env steps; LSIM_SENSOR_FILL_ALL: every env steps from h_prev = 0; LSIM_SENSOR_RESETS_ONLY: only fresh envs are stepped and
+ *   written, the others keep h and their row bit for bit (a by-hand reset between two steps).  For a stepped env h[e] = h' in place and, when
+ *   rows != NULL, rows[e] = [ z_e | h'_e ] (L + H columns: what the actor reads).  Nothing else is written. */
+#define LSIM_GRU_MAX_HIDDEN 128
+#define LSIM_GRU_MAX_INPUT 512
+#define LSIM_GRU_MAX_LDS_BYTES 163840
+typedef struct lsim_depth_memory {
+    const float* z;                   /* [N, z_ld]: the encoder's latent rows, L columns read, 4-byte aligned like every float pointer here */
+    const float* p;                   /* [N, p_ld]: the one-step observation, P columns read; NULL with proprio_dim == 0 */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    const float* weight_ih;           /* [3H][I] */
+    const float* weight_hh;           /* [3H][H] */
+    const float* bias_ih;             /* [3H] */
+    const float* bias_hh;             /* [3H] */
+    float* h;                         /* [N, h_ld]: the hidden state, H columns, updated in place */
+    float* rows;                      /* [N, rows_ld]: [z | h'], L + H columns; NULL: not written */
+    int32_t num_envs;                 /* >= 1 */
+    int32_t latent_dim, proprio_dim;  /* L >= 1, P >= 0, L + P <= LSIM_GRU_MAX_INPUT */
+    int32_t hidden;                   /* H */
+    int32_t z_ld, p_ld, h_ld, rows_ld;/* floats between rows: >= L, >= P, >= H, >= L + H (p_ld / rows_ld are not read without p / rows) */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+} lsim_depth_memory_t;
+/* bytes of dynamic LDS of the three launches for a cell of `hidden` units and `input_dim` = L + P inputs (any of the three outputs may be NULL):
+ *   step      4 * 16 * ((I rounded up to 16) + 2 + H + 2)                       the tile's x and h
+ *   forward   4 * (3H + 32) * (H + 2)                                            W_hh and two copies of the tile's h
+ *   backward  4 * (H + 32) * (3H + 2)                                            W_hh transposed and two copies of the tile's gate gradients
+ * LSIM_E_INVALID: hidden < 16, not a multiple of 16 or > LSIM_GRU_MAX_HIDDEN; input_dim outside 1..LSIM_GRU_MAX_INPUT; any of the three above
+ * LSIM_GRU_MAX_LDS_BYTES (hidden 112 and 128). */
+int lsim_depth_memory_sizes(int32_t hidden, int32_t input_dim, size_t* lds_step, size_t* lds_forward, size_t* lds_backward);
+/* the rollout launch described above.  LSIM_E_INVALID, checked on the host before any HIP call (nothing is written): dm == NULL; z, h, a
+ * parameter NULL or not 4-byte aligned; episode_length NULL or not 8-byte aligned; proprio_dim > 0 with p NULL or not 4-byte aligned; rows not
+ * 4-byte aligned; num_envs < 1; latent_dim < 1; proprio_dim < 0; hidden or latent_dim + proprio_dim refused by lsim_depth_memory_sizes;
+ * z_ld < L; p_ld < P with P > 0; h_ld < H; rows_ld < L + H with rows; a flag bit other than the sensor model's two; both of them set. */
+int lsim_depth_memory_step(const lsim_depth_memory_t* dm, void* stream);
+
+/* lsim_gru_sequence_forward / _backward: the same recurrence over T stored steps of n envs, contiguous [T, n, .] arrays.  A workgroup owns 16
+ * consecutive envs for all T steps, so the time of a call is T times the latency of one step, whatever n up to one workgroup per CU.
+ * Forward.  gi [T, n, 3H] is the input projection W_ih x + b_ih of every step, formed by the caller with one GEMM over all T * n rows (the
+ *   serial kernel never reads W_ih).  reset [T, n]: nonzero means h_prev = 0 at that step.  For t = 0 .. T-1
+ *     h_prev = reset[t] ? 0 : (t == 0 ? h0 : hs[t-1]);      hs[t] = h' of the cell above with gi = gi[t]
+ *   and, when save != NULL, save[t] = [ r | u | n | gh_n ] (4H columns; gh_n = W_hn h_prev + b_hn): what the backward needs, stored rather than
+ *   recomputed, because recomputing gh in the backward would double the matrix work of its serial chain.
+ * Backward.  dhs [T, n, H] is d loss / d hs[t] from whatever reads the states.  With dh the total gradient at step t (dh = dhs[T-1] at t = T-1),
+ *   for t = T-1 .. 0, h_prev as in the forward:
+ *     dn~ = dh * (1 - u) * (1 - n*n)        du~ = dh * (h_prev - n) * u * (1 - u)        dr~ = dn~ * gh_n * r * (1 - r)
+ *     dgi[t]  = [ dr~ | du~ | dn~ ]         dghn[t] = dn~ * r
+ *     dh(t-1) = ( dh * u + [ dr~ | du~ | dn~ * r ] . W_hh ) * (reset[t] ? 0 : 1)  +  dhs[t-1]           (the last term for t >= 1)
+ *   and dh0 (when not NULL) = the bracket times the reset factor at t = 0.  dgi and dghn are WRITTEN, not accumulated.  The parameter gradients
+ *   are then GEMMs and column sums over the T * n rows that the caller issues: dW_ih = dgi^T x, dW_hh = [dgi_r | dgi_u | dghn]^T h_prev,
+ *   db_ih = sum dgi, db_hh = sum [dgi_r | dgi_u | dghn].  There is no gradient with respect to x.
+ *   The order of every sum is a function of the extents only: two calls with the same inputs write the same bits. */
+typedef struct lsim_gru_sequence {
+    const float* gi;                  /* [T, n, 3H], 16-byte aligned like every [T, n, .] and [n, .] array here; forward only */
+    const float* h0;                  /* [n, H] */
+    const uint8_t* reset;             /* [T, n] */
+    const float* weight_hh;           /* [3H][H], 4-byte aligned */
+    const float* bias_hh;             /* [3H], 4-byte aligned; forward only */
+    float* hs;                        /* [T, n, H]: written by the forward, read by the backward */
+    float* save;                      /* [T, n, 4H]: written by the forward (NULL: not kept), read by the backward */
+    const float* dhs;                 /* [T, n, H]; backward only, like the next three */
+    float* dgi;                       /* [T, n, 3H] */
+    float* dghn;                      /* [T, n, H] */
+    float* dh0;                       /* [n, H], or NULL */
+    int32_t steps, num_envs, hidden;  /* T >= 1, n >= 1, H as above */
+} lsim_gru_sequence_t;
+/* LSIM_E_INVALID, checked on the host before any HIP call: gs == NULL; gi, h0 or hs NULL or not 16-byte aligned; save not 16-byte aligned;
+ * reset NULL; weight_hh or bias_hh NULL or not 4-byte aligned; steps < 1; num_envs < 1; hidden refused by lsim_depth_memory_sizes */
+int lsim_gru_sequence_forward(const lsim_gru_sequence_t* gs, void* stream);
+/* LSIM_E_INVALID likewise: gs == NULL; h0, hs, save, dhs, dgi or dghn NULL or not 16-byte aligned; dh0 not 16-byte aligned; reset NULL;
+ * weight_hh NULL or not 4-byte aligned; steps < 1; num_envs < 1; hidden refused by lsim_depth_memory_sizes */
+int lsim_gru_sequence_backward(const lsim_gru_sequence_t* gs, void* stream);
 
 #ifdef __cplusplus
 }

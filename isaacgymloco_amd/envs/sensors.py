@@ -162,7 +162,7 @@ class RaySensor:
         rc.near, rc.far = self.near, self.far
         self._rc = rc
         self._labels = None
-        self._encoder = self._latent = None
+        self._encoder = self._latent = self._memory = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
@@ -278,6 +278,8 @@ class RaySensor:
             lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
             if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
                 self._encoder.encode_device(self, self.tick, int(flags), stream)
+                if self._memory is not None:    # every env, every update: z is held between captures, the memory still ticks
+                    self._memory.step_device(self, int(flags), stream)
             return self.out
         if self._bodies:
             lib.check(self._api.lsim_raycast_bodies(ctypes.byref(self._rb), self._stream(stream)), what="lsim_raycast_bodies")
@@ -306,6 +308,22 @@ class RaySensor:
         if self.tick >= 0:
             enc.encode_device(self, self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
         return enc
+
+    def attach_memory(self, mem):
+        """from now on the encoder's launch of every update() / refresh() is followed by `mem`'s (learn.depth_memory.DepthMemory.step_device)
+        on the same stream with the same flags; steps every env once now from h = 0 (LSIM_SENSOR_FILL_ALL).  Needs an attached encoder."""
+        if self._encoder is None:
+            raise ValueError("attach_memory: the sensor has no encoder (attach_encoder first): the memory reads its latent rows")
+        self._latent_buffer(self._encoder.latent_dim)
+        self._memory = mem
+        mem.step_device(self, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+        return mem
+
+    def memory_rows(self):
+        """live [N, L + H] tensor: row e = [latent of env e | its memory's hidden state] (attach_memory)"""
+        if self._memory is None:
+            raise ValueError("the sensor has no memory (attach_memory)")
+        return self._memory.rows()
 
     def _latent_buffer(self, latent_dim):
         """the [N, stride] buffer an encoder's launch writes; created on first use"""

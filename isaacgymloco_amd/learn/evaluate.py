@@ -290,6 +290,8 @@ def _actor_critic(env, policy, device, vision=None):
         policy.get_inference_policy()          # flushes a deferred rollout store, eval mode
         if getattr(policy.alg, "encoder", None) is not None:
             vision.update(sensor=getattr(policy, "sensor", None), encoder=policy.alg.encoder, depth_head=policy.alg.depth_head)
+            if getattr(policy.alg, "memory", None) is not None:
+                vision.update(memory=policy.alg.memory, memory_head=policy.alg.memory_head)
         return policy.alg.actor_critic
     if isinstance(policy, str):
         d = torch.load(policy, map_location=device, weights_only=False)
@@ -340,32 +342,55 @@ def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
             head.load_state_dict(d["depth_head_state_dict"])
     if enc is None:
         raise ValueError("evaluate: a VisionActorCritic needs its depth encoder (encoder=...): nobody else can hand it a latent")
-    if enc.latent_dim != ac.depth_latent_dim:
-        raise ValueError(f"evaluate: the encoder's latent has {enc.latent_dim} columns, the actor reads {ac.depth_latent_dim}")
+    mem, mem_head = found.get("memory"), found.get("memory_head")
+    record = ((d.get("vision") or {}).get("memory")) if d is not None else None
+    if mem is None and record is not None:      # a checkpoint of a policy trained with a depth memory: rebuilt from its record
+        from .depth_memory import DepthMemory
+        mem = DepthMemory(**record)
+        mem.load_state_dict(d["depth_memory_state_dict"])
+        if "depth_memory_head_state_dict" in d:
+            w = d["depth_memory_head_state_dict"]["weight"]
+            mem_head = torch.nn.Linear(w.shape[1], w.shape[0])
+            mem_head.load_state_dict(d["depth_memory_head_state_dict"])
+    if enc.latent_dim + (mem.hidden if mem is not None else 0) != ac.depth_latent_dim:
+        raise ValueError(f"evaluate: the encoder's latent has {enc.latent_dim} columns" + (f" and the memory {mem.hidden}" if mem is not None else "") +
+                         f", the actor reads {ac.depth_latent_dim}")
     enc = enc.to(device).eval()
     head = head.to(device).eval() if head is not None else None
     if getattr(cam, "_encoder", None) is not enc:
         cam.attach_encoder(enc)
+    if mem is not None:
+        mem = mem.to(device).eval()
+        if getattr(cam, "_memory", None) is not mem:
+            cam.attach_memory(mem)
+        found["memory"], found["memory_head"] = mem, (mem_head.to(device).eval() if mem_head is not None else None)
     return cam, enc, head
 
 
-def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics):
+VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
+
+
+def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, memory=None, memory_head=None):
     """evaluate()'s loop for a VisionActorCritic: the actor also reads the sensor's live latent rows (zeros when `blind`), and the evaluator
     accumulates the `metrics` as columns (module docstring of learn/vision.py)"""
     from .vision import PackedVisionPolicy, height_scan_block
     dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
     metrics = list(metrics)
     for m in metrics:
-        if m not in ("depth_influence", "scan_error"):
-            raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error'")
+        if m not in VISION_METRICS:
+            raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error')")
     scan = None
-    if "scan_error" in metrics:         # needs the auxiliary head and a privileged observation that holds the scan: else dropped, not zero
-        try:
-            scan = height_scan_block(env.cfg) if head is not None else None
-        except ValueError:
-            scan = None
-        if scan is None:
-            metrics.remove("scan_error")
+    Lz = L - (memory.hidden if memory is not None else 0)       # the encoder's columns of the actor's depth segment
+    for m, h_ in (("scan_error", head), ("memory_scan_error", memory_head if memory is not None else None)):
+        if m in metrics:                # needs its head and a privileged observation that holds the scan: else dropped, not zero
+            try:
+                found_scan = height_scan_block(env.cfg) if h_ is not None else None
+            except ValueError:
+                found_scan = None
+            if found_scan is None:
+                metrics.remove(m)
+            else:
+                scan = found_scan
     if metrics and ev.column_names != tuple(metrics):
         ev.add_columns(metrics)
     use_fused = PackedVisionPolicy.supported(ac) if fused is None else bool(fused)
@@ -383,7 +408,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics):
     for _ in range(int(steps)):
         if cmd is not None:
             env.commands[:, :3] = cmd
-        live = cam.latent()
+        live = cam.latent() if memory is None else cam.memory_rows()       # with a memory: [z | h], zeros of the same width when blind
         rows = zeros if blind else live
         if use_fused:
             packed.forward(obs, priv, mean, values, rows=rows)
@@ -397,8 +422,10 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics):
         for k, m in enumerate(metrics):     # from the observation the action came from; the step's reset flags decide what counts
             if m == "depth_influence":
                 ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
+            elif m == "scan_error":
+                ev.columns[:, k] = (head(live[:, :Lz]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
             else:
-                ev.columns[:, k] = (head(live) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
+                ev.columns[:, k] = (memory_head(live[:, Lz:]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
         env.step_device(actions)
         ev.accumulate()
         if metrics:
@@ -408,7 +435,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics):
 
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
-             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=("depth_influence", "scan_error")):
+             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -416,7 +443,9 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     runner's, else env.sensors["depth"]) through `encoder` (default: the runner's, else rebuilt from the checkpoint's `vision` record);
     `blind=True` feeds zeros instead.  `vision_metrics` become columns of the result: "depth_influence" = the L2 distance of the action
     mean from the mean with a zero latent (one more policy forward per step), "scan_error" = the mean square error of `depth_head` (the
-    encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped."""
+    encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped.
+    A policy trained with a depth memory (the runner's alg.memory, or the checkpoint's vision["memory"] record) gets the memory rebuilt and
+    attached behind the encoder and reads cam.memory_rows(), [z | h]; "memory_scan_error" is the memory head's error on h."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
@@ -433,7 +462,8 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
     if is_vision:
-        return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()))
+        return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
+                                memory=found.get("memory"), memory_head=found.get("memory_head"))
     use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
     if use_fused and not PackedHimPolicy.supported(ac):
         raise ValueError("fused=True but lsim_policy_forward does not support this policy's topology")
@@ -501,8 +531,8 @@ def parse_args(argv=None):
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
     a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
-    if any(m not in ("depth_influence", "scan_error") for m in a.vision_metrics):
-        ap.error(f"--vision-metrics: 'depth_influence' and / or 'scan_error', got {a.vision_metrics}")
+    if any(m not in VISION_METRICS for m in a.vision_metrics):
+        ap.error(f"--vision-metrics: 'depth_influence', 'scan_error' and / or 'memory_scan_error', got {a.vision_metrics}")
     try:
         group_mask(a.group_by)
     except ValueError as exc:

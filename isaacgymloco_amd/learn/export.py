@@ -13,6 +13,7 @@ wherever the reference's file does (torch.jit.load, C++ libtorch on the robot) a
 """
 import copy
 import os
+from typing import Tuple
 
 import torch
 import torch.nn as nn
@@ -72,7 +73,7 @@ class PolicyExporterVision(nn.Module):
         if m is None:
             raise ValueError("PolicyExporterVision: the sensor has no SensorModel, so no frame history the encoder could have read")
         model = SensorModel(**m)
-        if encoder.frames != model.frames or encoder.latent_dim != actor_critic.depth_latent_dim:
+        if encoder.frames != model.frames or encoder.latent_dim + self._memory_columns() != actor_critic.depth_latent_dim:
             raise ValueError(f"PolicyExporterVision: the encoder reads {encoder.frames} frames and writes {encoder.latent_dim} columns; the sensor "
                              f"keeps {model.frames}, the actor reads {actor_critic.depth_latent_dim}")
         self.actor = plain_sequential(actor_critic.actor)
@@ -90,6 +91,11 @@ class PolicyExporterVision(nn.Module):
         self.period, self.latency, self.frames = model.period, model.latency, model.frames
         self.height, self.width = int(encoder.height), int(encoder.width)
         self.latent_dim = int(encoder.latent_dim)
+
+    @torch.jit.ignore
+    def _memory_columns(self):
+        """columns of the actor's depth segment that are not the encoder's: none here"""
+        return 0
 
     @torch.jit.export
     def preprocess(self, depth_m: torch.Tensor) -> torch.Tensor:
@@ -128,12 +134,47 @@ class PolicyExporterVision(nn.Module):
         return path
 
 
-def export_policy_as_jit(actor_critic, path, encoder=None, sensor=None):
+class PolicyExporterVisionMemory(PolicyExporterVision):
+    """PolicyExporterVision for a policy trained with a depth memory (learn/depth_memory.py): the actor reads rows = cat(latent, h).  The
+    robot keeps h between control steps, zero at the start of an episode: `remember` runs at CONTROL rate with the latest latent (held
+    between captures) and the current observation history, whose first proprio_dim columns are the cell's second input.  Attribute `hidden`."""
+
+    def __init__(self, actor_critic, encoder, sensor, memory):
+        self.hidden = int(memory.hidden)
+        super().__init__(actor_critic, encoder, sensor)
+        if memory.latent_dim != encoder.latent_dim or memory.proprio_dim > actor_critic.num_one_step_obs:
+            raise ValueError(f"PolicyExporterVisionMemory: the memory reads {memory.latent_dim} latent and {memory.proprio_dim} observation columns; the "
+                             f"encoder writes {encoder.latent_dim}, a one-step observation has {actor_critic.num_one_step_obs}")
+        self.cell = copy.deepcopy(memory.cell).cpu()
+        for p in self.cell.parameters():
+            p.requires_grad_(False)
+        self.proprio_dim = int(memory.proprio_dim)
+
+    @torch.jit.ignore
+    def _memory_columns(self):
+        return self.hidden
+
+    @torch.jit.export
+    def remember(self, latent: torch.Tensor, obs_history: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+        """latent [B, L], obs_history [B, num_obs], h [B, hidden] (zeros after a reset) -> h' [B, hidden]"""
+        return self.cell(torch.cat((latent, obs_history[:, 0:self.proprio_dim]), dim=1), h)
+
+    def forward(self, obs_history: torch.Tensor, frames: torch.Tensor, h: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(actions, h'): encode, remember, act on rows = cat(latent, h')"""
+        latent = self.encode(frames)
+        h2 = self.remember(latent, obs_history, h)
+        return self.act(obs_history, torch.cat((latent, h2), dim=1)), h2
+
+
+def export_policy_as_jit(actor_critic, path, encoder=None, sensor=None, memory=None):
     """HLP:201-212.  `path` is a directory; returns the file written (policy.pt for HIM and vision policies, policy_1.pt for a bare actor).
-    A vision policy needs its `encoder` and `sensor` (or the sensor's spec()): without them the module could not run, and this raises."""
+    A vision policy needs its `encoder` and `sensor` (or the sensor's spec()): without them the module could not run, and this raises;
+    one trained with a depth memory also its `memory` (the exported module then has remember() and forward(obs_history, frames, h))."""
     if hasattr(actor_critic, "depth_latent_dim"):
         if encoder is None or sensor is None:
             raise ValueError("export_policy_as_jit: a vision policy exports with its depth encoder and sensor (encoder=..., sensor=...)")
+        if memory is not None:
+            return PolicyExporterVisionMemory(actor_critic, encoder, sensor, memory).export(path)
         return PolicyExporterVision(actor_critic, encoder, sensor).export(path)
     if hasattr(actor_critic, "estimator"):
         return PolicyExporterHIM(actor_critic).export(path)

@@ -108,6 +108,21 @@ class VisionActorCritic(HIMActorCritic):
         return self.load_state_dict(sd)
 
 
+    @torch.no_grad()
+    def load_vision_state_dict(self, sd):
+        """warm start from a narrower VisionActorCritic's state dict (a vision policy without the depth memory): actor.0.weight goes into
+        the first columns, the new ones -- the memory's hidden state -- are zero, so the policy computes that policy's means bit for bit"""
+        sd = dict(sd)
+        w = sd["actor.0.weight"]
+        rows, wide_k = self.actor[0].weight.shape
+        if w.dim() != 2 or w.shape[0] != rows or not self.num_him_actor_inputs < w.shape[1] <= wide_k:
+            raise ValueError(f"load_vision_state_dict: actor.0.weight must be [{rows}, k] with {self.num_him_actor_inputs} < k <= {wide_k}, got {tuple(w.shape)}")
+        wide = torch.zeros_like(self.actor[0].weight)
+        wide[:, :w.shape[1]] = w
+        sd["actor.0.weight"] = wide
+        return self.load_state_dict(sd)
+
+
 class VisionTransition:
     __slots__ = Transition.__slots__ + ("depth_latent",)
     __init__ = Transition.__init__
@@ -143,7 +158,7 @@ class VisionPPO(HIMPPO):
     update() returns HIMPPO's values plus the mean auxiliary loss."""
 
     def __init__(self, actor_critic, encoder=None, latent_source=None, frames_source=None, height_scan=None, aux_snapshots=4, aux_learning_rate=1e-3,
-                 dist_ctx=None, **kwargs):
+                 memory_env_minibatches=4, memory_learning_rate=1e-3, dist_ctx=None, **kwargs):
         if dist_ctx is not None and getattr(dist_ctx, "world", 1) > 1:
             raise NotImplementedError("VisionPPO: one rank only (the encoder's gradients are not reduced over ranks)")
         super().__init__(actor_critic, dist_ctx=dist_ctx, **kwargs)
@@ -153,21 +168,31 @@ class VisionPPO(HIMPPO):
         self.latent_source = self.frames_source = self.height_scan = None
         self._snap, self._snap_filled = [], []
         self.last_aux_loss = float("nan")
+        self.memory = self.memory_head = self.memory_optimizer = None
+        self.memory_env_minibatches, self.memory_learning_rate = int(memory_env_minibatches), float(memory_learning_rate)
+        self.memory_api = None                      # tests: the CPU shim behind DepthMemory.sequence_device
+        self.last_memory_loss = float("nan")
         if encoder is not None:
             self.attach(encoder, latent_source, frames_source, height_scan)
 
-    def attach(self, encoder, latent_source, frames_source, height_scan=None):
+    def attach(self, encoder, latent_source, frames_source, height_scan=None, memory=None):
         """`encoder`: the DepthEncoder whose latent `latent_source()` returns ([N, L], live); `frames_source()`: the [N, frames, H, W] it
-        encodes; `height_scan`: (offset, width) of the regression target inside a critic observation row (default: the env's layout)"""
-        L = self.actor_critic.depth_latent_dim
-        if encoder.latent_dim != L:
-            raise ValueError(f"VisionPPO: the encoder's latent has {encoder.latent_dim} columns, the actor reads {L}")
+        encodes; `height_scan`: (offset, width) of the regression target inside a critic observation row (default: the env's layout);
+        `memory`: a DepthMemory -- `latent_source()` then returns [z | h] ([N, L + H]) and memory_step() trains the cell"""
+        L = self.actor_critic.depth_latent_dim - (memory.hidden if memory is not None else 0)
+        if encoder.latent_dim != L or (memory is not None and memory.latent_dim != L):
+            raise ValueError(f"VisionPPO: the encoder's latent has {encoder.latent_dim} columns, the actor reads {self.actor_critic.depth_latent_dim}"
+                             + (f" of which the memory's hidden state is {memory.hidden} and its input {memory.latent_dim}" if memory is not None else ""))
         self.height_scan = tuple(int(v) for v in (height_scan if height_scan is not None else height_scan_block()))
         self.encoder = encoder.to(self.device)
         self.depth_head = nn.Linear(L, self.height_scan[1]).to(self.device)
         self.aux_optimizer = torch.optim.Adam(list(self.encoder.parameters()) + list(self.depth_head.parameters()), lr=self.aux_learning_rate)
         self.latent_source, self.frames_source = latent_source, frames_source
         self._snap, self._snap_filled = [], []
+        if memory is not None:
+            self.memory = memory.to(self.device)
+            self.memory_head = nn.Linear(memory.hidden, self.height_scan[1]).to(self.device)
+            self.memory_optimizer = torch.optim.Adam(list(self.memory.parameters()) + list(self.memory_head.parameters()), lr=self.memory_learning_rate)
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = VisionRolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape,
@@ -236,11 +261,52 @@ class VisionPPO(HIMPPO):
         self._snap_filled = [False] * len(self._snap)
         return None if n == 0 else total / n
 
+    def memory_data(self):
+        """the BPTT data set a finished rollout IS, from the storage alone: steps 1 .. T-1 with x_t = [z_t | obs_t[:P]] (what the launch
+        behind env step t-1 read), reset_t = dones[t-1] (the env was fresh then), h0 = the h columns of step 0's stored row, and the height
+        scan of privileged_observations[t] as the target -> (x [T-1, N, I], h0 [N, H], reset [T-1, N] uint8, target [T-1, N, scan])"""
+        mem, st = self.memory, self.storage
+        L, P = mem.latent_dim, mem.proprio_dim
+        off, width = self.height_scan
+        rows = st.depth_latent
+        x = torch.cat((rows[1:, :, :L], st.observations[1:, :, :P]), dim=-1)
+        return x, rows[0][:, L:], st.dones[:-1, :, 0], st.privileged_observations[1:, :, off:off + width]
+
+    def memory_step(self):
+        """one pass over this rollout for the memory: memory_env_minibatches contiguous env slices, each ONE sequence pass over all T - 1
+        steps (DepthMemory.sequence_device on the device), loss = mse(memory_head(hs), height scan), one Adam step over memory and head.
+        The stored h0 (and, for later slices, every stored row) was produced by the weights of the rollout, not by the ones an earlier
+        slice has just updated: the usual truncated-BPTT approximation.  No gradient reaches the encoder (the stored z is data) or the
+        actor-critic.  -> mean loss (a 0-d tensor), or None for a rollout of fewer than 2 steps"""
+        if self.memory is None:
+            raise RuntimeError("VisionPPO: no memory (attach(..., memory=DepthMemory(...)))")
+        if self.storage.num_transitions_per_env < 2:
+            return None
+        x, h0, reset, target = self.memory_data()
+        N = x.shape[1]
+        k = max(1, min(self.memory_env_minibatches, N))
+        on_device = next(self.memory.parameters()).is_cuda or self.memory_api is not None
+        total = None
+        for i in range(k):
+            a, b = i * N // k, (i + 1) * N // k
+            xs, hs0, rs = x[:, a:b].contiguous(), h0[a:b].contiguous(), reset[:, a:b].contiguous()
+            hs = self.memory.sequence_device(xs, hs0, rs, api=self.memory_api) if on_device else self.memory.sequence(xs, hs0, rs)
+            loss = F.mse_loss(self.memory_head(hs), target[:, a:b])
+            self.memory_optimizer.zero_grad()
+            loss.backward()
+            self.memory_optimizer.step()
+            total = loss.detach() if total is None else total + loss.detach()
+        return total / k
+
     def update(self):
         out = super().update()
         aux = self.encoder_step()
         self.last_aux_loss = float("nan") if aux is None else float(aux)
-        return tuple(out) + (self.last_aux_loss,)
+        if self.memory is None:
+            return tuple(out) + (self.last_aux_loss,)
+        loss = self.memory_step()
+        self.last_memory_loss = float("nan") if loss is None else float(loss)
+        return tuple(out) + (self.last_aux_loss, self.last_memory_loss)
 
 
 class PackedVisionPolicy(PackedHimPolicy):
@@ -306,16 +372,19 @@ class VisionRollout(GraphedRollout):
         self.alg.snapshot_if_due(self.storage.step, env.privileged_obs_buf)
         prev, self._pending_post = self._pending_post, None
         self.packed.forward_act(self._S, self.storage.step, self._draw_host, env.obs_buf, env.privileged_obs_buf, ac.std, self._seed, self._rank,
-                                self.mean, self.values, self.actions, prev=prev, rows=self.sensor.latent(), store=self.storage.depth_latent)
+                                self.mean, self.values, self.actions, prev=prev, rows=self.alg._latent_now(), store=self.storage.depth_latent)
 
 
 class VisionOnPolicyRunner(HIMOnPolicyRunner):
     """HIMOnPolicyRunner for a vision policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs a
     SensorModel (the frame history).  `encoder`: a DepthEncoder for its frames; default DepthEncoder(height, width, frames).  The runner
     attaches the encoder to the sensor.  train_cfg is HIMOnPolicyRunner's; policy["depth_latent_dim"] is set from the encoder and
-    algorithm["aux_snapshots"] / ["aux_learning_rate"] are optional."""
+    algorithm["aux_snapshots"] / ["aux_learning_rate"] are optional.  `memory`: True builds DepthMemory(L, env.num_one_step_obs, 64), an
+    instance is taken as is; the actor then reads [z | h] (policy["depth_latent_dim"] = L + H, the stored row likewise) and VisionPPO trains
+    the cell behind the encoder's step (algorithm["memory_env_minibatches"] / ["memory_learning_rate"] are optional).  Without it nothing
+    is allocated, launched, stored or saved that was not before."""
 
-    def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None):
+    def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None, memory=None):
         cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
         if getattr(cam, "model", None) is None:
             raise ValueError("VisionOnPolicyRunner: the sensor has no SensorModel, so no frame history to encode")
@@ -330,11 +399,29 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
         cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
         cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "VisionPPO"
         cfg["policy"]["depth_latent_dim"] = encoder.latent_dim
-        self.sensor = cam
+        if memory is not None and memory is not False:
+            from .depth_memory import DepthMemory
+            memory = DepthMemory(encoder.latent_dim, env.num_one_step_obs, 64) if memory is True else memory
+            if memory.latent_dim != encoder.latent_dim or memory.proprio_dim > env.num_one_step_obs:
+                raise ValueError(f"VisionOnPolicyRunner: the memory reads {memory.latent_dim} latent and {memory.proprio_dim} observation columns, "
+                                 f"the encoder writes {encoder.latent_dim} and a one-step observation has {env.num_one_step_obs}")
+            memory = memory.to(device)
+            cfg["policy"]["depth_latent_dim"] = encoder.latent_dim + memory.hidden
+            first = env.num_one_step_obs + 3 + 16 + encoder.latent_dim + memory.hidden
+            if first > 272:         # LS_POL_MAX_IN (csrc/ls_policy.h): the fused policy launch's widest input row
+                raise ValueError(f"VisionOnPolicyRunner: the first actor layer would read {first} columns ({env.num_one_step_obs} + 3 + 16 + latent "
+                                 f"{encoder.latent_dim} + hidden {memory.hidden}), the fused policy launch takes at most 272")
+        else:
+            memory = None
+        self.sensor, self.memory = cam, memory
         super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
         cam.attach_encoder(encoder)         # behind the parent's env.reset(): the sensor has captured, so every env is encoded now
         frames = cam.frame_images if hasattr(cam, "frame_images") else (lambda: cam.frames().unflatten(2, (encoder.height, encoder.width)))
-        self.alg.attach(encoder, cam.latent, frames, scan)
+        if memory is None:
+            self.alg.attach(encoder, cam.latent, frames, scan)
+        else:
+            cam.attach_memory(memory)       # every env steps once from h = 0
+            self.alg.attach(encoder, cam.memory_rows, frames, scan, memory=memory)
 
     def _make_fused_rollout(self):
         return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
@@ -347,13 +434,17 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
         cam = getattr(self, "sensor", None)           # what the policy was trained with: learn/evaluate.py and the exporter rebuild the pipeline from it
         out["vision"] = {"encoder": alg.encoder.config(), "sensor": cam.spec() if hasattr(cam, "spec") else None,
                          "latent_dim": int(alg.actor_critic.depth_latent_dim)}
+        if alg.memory is not None:
+            out.update(depth_memory_state_dict=alg.memory.state_dict(), depth_memory_head_state_dict=alg.memory_head.state_dict(),
+                       depth_memory_optimizer_state_dict=alg.memory_optimizer.state_dict())
+            out["vision"]["memory"] = alg.memory.config()
         return out
 
     def export(self, path):
         """learn/export.py: export_policy_as_jit of this runner's actor-critic, encoder and sensor; `path` is a directory"""
         from .export import export_policy_as_jit
         self.get_inference_policy()
-        return export_policy_as_jit(self.alg.actor_critic, path, encoder=self.alg.encoder, sensor=self.sensor)
+        return export_policy_as_jit(self.alg.actor_critic, path, encoder=self.alg.encoder, sensor=self.sensor, memory=self.alg.memory)
 
     def _load_extra_checkpoint_state(self, d):
         super()._load_extra_checkpoint_state(d)
@@ -362,3 +453,7 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
             alg.encoder.load_state_dict(d["depth_encoder_state_dict"])
             alg.depth_head.load_state_dict(d["depth_head_state_dict"])
             alg.aux_optimizer.load_state_dict(d["depth_optimizer_state_dict"])
+        if alg.memory is not None and "depth_memory_state_dict" in d:
+            alg.memory.load_state_dict(d["depth_memory_state_dict"])
+            alg.memory_head.load_state_dict(d["depth_memory_head_state_dict"])
+            alg.memory_optimizer.load_state_dict(d["depth_memory_optimizer_state_dict"])

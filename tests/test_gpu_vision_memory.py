@@ -1,0 +1,186 @@
+"""GPU: the depth memory in the vision pipeline -- 64 Aliengo envs on stairs with a period-4 staggered camera: the rollout stores the rows the
+actor saw ([z | h]), h follows the torch twin step by step, training, checkpoint, evaluate() and the exported module run end to end, and a
+runner without a memory launches nothing new."""
+import numpy as np
+import pytest
+import torch
+
+import depth_memory_reference as R
+from helpers import abi
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+N, L, H, T = 64, 10, 32, 12
+ENC = dict(c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=L)
+
+
+def _env(seed):
+    from isaacgymloco_amd.envs import config as C
+    from isaacgymloco_amd.envs.legged_robot import LeggedRobot
+    from isaacgymloco_amd.learn.evaluate import play_cfg
+    cfg = play_cfg(C.aliengo_cfg())
+    cfg.env.num_envs = N
+    cfg.env.episode_length_s = 0.3                  # 15 steps: time-outs inside a rollout of 12 steps for the envs started late below
+    cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device=DEV, seed=seed)
+    env.reset()
+    return env
+
+
+def _camera(env):
+    from isaacgymloco_amd.envs import sensors
+    return sensors.depth_camera(env, 16, 12, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0,
+                                model=sensors.SensorModel(period=4, stagger=True, latency=1, frames=2, normalise=True))
+
+
+def _runner(env, memory, seed=5):
+    from isaacgymloco_amd.learn.bench_train import train_cfg_dict
+    from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
+    from isaacgymloco_amd.learn.vision import VisionOnPolicyRunner
+    tc = train_cfg_dict("aliengo")
+    tc["runner"]["num_steps_per_env"] = T
+    torch.manual_seed(seed)
+    return VisionOnPolicyRunner(env, tc, sensor="depth", encoder=DepthEncoder(12, 16, 2, **ENC), device=DEV, memory=memory)
+
+
+@pytest.fixture(scope="module")
+def trained(tmp_path_factory):
+    """a VisionOnPolicyRunner with DepthMemory(L, num_one_step_obs, 32): one recorded rollout + update, then learn(2), save, load, learn(1)"""
+    from isaacgymloco_amd.learn.depth_memory import DepthMemory
+    env = _env(5)
+    cam = env.add_sensor("depth", _camera(env))
+    run = _runner(env, DepthMemory(L, env.num_one_step_obs, H))
+    k = torch.arange(N, device=DEV) % 16            # behind the runner's own reset: some envs time out on the way
+    env.episode_length_buf.copy_(torch.where((k >= 3) & (k <= 6), int(env.max_episode_length) - 2 - k, torch.zeros_like(k)).to(env.episode_length_buf.dtype))
+    mem = run.alg.memory
+    assert mem is run.memory and cam._memory is mem and run.alg.actor_critic.depth_latent_dim == L + H
+    # ---- one rollout, recorded: what the sensor showed before every env step
+    seen = []
+    step = env.step_device
+
+    def recording(a, flags=0):
+        torch.cuda.synchronize()
+        seen.append((cam.memory_rows().clone(), cam.latent().clone(), env.obs_buf[:, :mem.proprio_dim].clone()))
+        out = step(a, flags)
+        return out
+    env.step_device = recording
+    run.learn(1)
+    env.step_device = step
+    torch.cuda.synchronize()
+    return run, cam, mem, seen
+
+
+def test_rollout_stores_the_rows_the_actor_saw_and_h_follows_the_twin(trained):
+    run, cam, mem, seen = trained
+    st = run.alg.storage
+    assert len(seen) == T and st.depth_latent.shape == (T, N, L + H)
+    dones = st.dones[:, :, 0].cpu().numpy() != 0
+    assert dones.any() and not dones.all(axis=0).any(), "time-outs inside the rollout, and envs without one"
+    for t in range(T):
+        assert torch.equal(st.depth_latent[t], seen[t][0]), f"step {t}: the stored row is cam.memory_rows() as it was before the step"
+        assert torch.equal(seen[t][0][:, :L], seen[t][1])
+    # the weights moved in learn(1)'s update, so the twin steps with the rollout's weights: recover them from a second, untouched rollout
+    run2_rows = []
+    step = run.env.step_device
+
+    def recording(a, flags=0):
+        torch.cuda.synchronize()
+        run2_rows.append((cam.memory_rows().clone(), run.env.obs_buf[:, :mem.proprio_dim].clone()))
+        return step(a, flags)
+    prm = tuple(p.detach().cpu().numpy().copy() for p in mem.device_params())
+    run.env.step_device = recording
+    run.get_inference_policy()           # flushes the rollout's deferred store
+    k = torch.arange(N, device=DEV) % 16
+    run.env.episode_length_buf.copy_(torch.where((k >= 3) & (k <= 6), int(run.env.max_episode_length) - 2 - k, run.env.episode_length_buf).to(run.env.episode_length_buf.dtype))
+    with torch.inference_mode():
+        for _ in range(T):
+            run.env.step_device(torch.zeros(N, 12, device=DEV))
+            run2_rows[-1] = run2_rows[-1] + (run.env.reset_buf.clone(),)
+    run.env.step_device = step
+    torch.cuda.synchronize()
+    worst, resets = 0.0, 0
+    for t in range(1, T):
+        rows, p = (v.cpu().numpy() for v in run2_rows[t][:2])
+        prev, fresh = run2_rows[t - 1][0].cpu().numpy()[:, L:], run2_rows[t - 1][2].cpu().numpy() != 0
+        want, bound = R.step(rows[:, :L], p, prev, fresh, prm)
+        worst = max(worst, float((np.abs(rows[:, L:] - want) / bound).max()))
+        if fresh.any():
+            zero, zb = R.step(rows[fresh, :L], p[fresh], np.zeros((int(fresh.sum()), H)), np.ones(int(fresh.sum()), bool), prm)
+            assert (np.abs(rows[fresh, L:] - zero) <= zb).all(), "a reset env's h is GRU(x, 0)"
+            resets += int(fresh.sum())
+    print(f"h against the fp64 twin over {T - 1} steps: worst |difference| / bound {worst:.2e}, {resets} resets")
+    assert worst <= 1.0 and resets > 0
+
+
+def test_learn_save_load_learn_evaluate_and_export(trained, tmp_path):
+    from isaacgymloco_amd.envs import sensors
+    from isaacgymloco_amd.learn.depth_memory import DepthMemory
+    from isaacgymloco_amd.learn.evaluate import evaluate
+    run, cam, mem, _ = trained
+    run.learn(2)
+    assert len(run.last_update) == 6 and all(np.isfinite(v) for v in run.last_update[4:]) and run.alg.last_memory_loss == run.last_update[5]
+    path = str(tmp_path / "model.pt")
+    run.save(path)
+    d = torch.load(path, map_location="cpu", weights_only=False)
+    assert d["vision"]["memory"] == {"latent_dim": L, "proprio_dim": run.env.num_one_step_obs, "hidden": H}
+    env2 = _env(7)
+    env2.add_sensor("depth", _camera(env2))
+    run2 = _runner(env2, DepthMemory(L, env2.num_one_step_obs, H), seed=9)
+    run2.load(path)
+    for a, b in zip(run.alg.memory.parameters(), run2.alg.memory.parameters()):
+        assert torch.equal(a, b)
+    run2.learn(1)
+    assert np.isfinite(run2.last_update[5])
+    # evaluate() on the checkpoint: fused and eager agree on the sample words, the memory head's column is there
+    res = {}
+    for fused in (True, False):
+        env = _env(9)
+        env.add_sensor("depth", sensors.from_spec(env, d["vision"]["sensor"]))
+        ev = evaluate(env, path, 20, commands=(0.8, 0.0, 0.0), fused=fused)
+        assert env.sensors["depth"]._memory is not None and env.sensors["depth"].memory_rows().shape == (N, L + H)
+        res[fused] = ev.result()
+        cols = res[fused]["total"]["columns"]
+        assert res[fused]["conventions"]["columns"] == ["depth_influence", "scan_error", "memory_scan_error"]
+        assert np.isfinite(cols["memory_scan_error"]["mean"]) and cols["memory_scan_error"]["mean"] > 0 and cols["memory_scan_error"]["nonfinite"] == 0
+    assert res[True]["total"]["samples"] == res[False]["total"]["samples"] and res[True]["total"]["episodes"] == res[False]["total"]["episodes"]
+    env = _env(9)
+    env.add_sensor("depth", sensors.from_spec(env, d["vision"]["sensor"]))
+    blind = evaluate(env, path, 5, commands=(0.8, 0.0, 0.0), blind=True).result()
+    assert blind["total"]["columns"]["depth_influence"]["mean"] == 0.0
+    # the exported module's remember on the CPU tracks state() over 5 steps
+    mod = torch.jit.load(run.export(str(tmp_path / "exported")))
+    assert mod.hidden == H
+    env, prm = run.env, tuple(p.detach().cpu().numpy() for p in mem.device_params())
+    g = torch.Generator().manual_seed(1)
+    torch.cuda.synchronize()
+    h = mem.state().cpu().clone()
+    for _ in range(5):
+        env.step_device((torch.randn(N, 12, generator=g) * 0.5).to(DEV))
+        torch.cuda.synchronize()
+        fresh = env.reset_buf.cpu() != 0
+        z, obs = cam.latent().cpu(), env.obs_buf.cpu()
+        with torch.no_grad():
+            got = mod.remember(z, obs, h * (~fresh).unsqueeze(-1))
+        want, bound = R.step(z.numpy(), obs[:, :mem.proprio_dim].numpy(), h.numpy(), fresh.numpy(), prm)
+        dev = mem.state().cpu()
+        assert (np.abs(got.numpy() - want) <= bound).all() and (np.abs(dev.numpy() - want) <= bound).all()
+        h = dev.clone()
+
+
+def test_a_runner_without_memory_launches_no_memory_kernel():
+    from isaacgymloco_amd import lib
+    env = _env(5)
+    cam = env.add_sensor("depth", _camera(env))
+    calls = []
+    real = cam._api
+    proxy = type("Api", (), {"__getattr__": lambda self, name: (calls.append(name), getattr(real, name))[1]})()
+    cam._api = proxy
+    run = _runner(env, None)
+    assert run.memory is None and run.alg.memory is None and cam._memory is None
+    run.learn(1)
+    assert "lsim_depth_encode" in calls and not any("memory" in c or "gru" in c for c in calls)
+    assert len(run.last_update) == 5 and run.alg.storage.depth_latent.shape == (T, N, L)
+    with pytest.raises(ValueError, match="no memory"):
+        cam.memory_rows()
+    assert cam.latent().shape == (N, L) and run.alg.actor_critic.depth_latent_dim == L
+    assert lib.load() is real or real is not None

@@ -1,0 +1,305 @@
+"""CPU: the depth memory above the kernels -- learn/depth_memory.py's torch paths and its device path through the CPU shim, the sensor hook on
+the emulated env, VisionPPO.memory_step on a stored rollout, the warm start, the checkpoint and the exporter."""
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import depth_memory_emu_binding as MB
+import depth_memory_reference as R
+from isaacgymloco_amd.learn import vision as V
+from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
+from isaacgymloco_amd.learn.depth_memory import DepthMemory
+
+O, P, N1, A = 270, 238, 45, 12
+K_HIM = N1 + 3 + 16
+
+
+def _memory_of(shape, prm):
+    mem = DepthMemory(shape["L"], shape["P"], shape["H"])
+    with torch.no_grad():
+        for p, v in zip(mem.device_params(), prm):
+            p.copy_(torch.from_numpy(np.asarray(v)))
+    return mem
+
+
+def test_constructor_config_and_refusals():
+    mem = DepthMemory(10, 7, 32)
+    assert mem.config() == {"latent_dim": 10, "proprio_dim": 7, "hidden": 32} and DepthMemory(**mem.config()).cell.weight_ih.shape == (96, 17)
+    assert [tuple(p.shape) for p in mem.device_params()] == [(96, 17), (96, 32), (96,), (96,)]
+    assert mem.lds_bytes(MB.EmuApi()) == (4 * 16 * (32 + 2 + 32 + 2), 4 * (96 + 32) * 34, 4 * (32 + 32) * 98)
+    for bad in (dict(latent_dim=0, proprio_dim=0), dict(latent_dim=4, proprio_dim=-1), dict(latent_dim=500, proprio_dim=13),
+                dict(latent_dim=4, proprio_dim=0, hidden=24), dict(latent_dim=4, proprio_dim=0, hidden=144), dict(latent_dim=4, proprio_dim=0, hidden=0)):
+        with pytest.raises(ValueError):
+            DepthMemory(**bad)
+    with pytest.raises(ValueError, match="not been stepped"):
+        mem.rows()
+    x = torch.zeros(3, 2, 17)
+    with pytest.raises(ValueError, match="requires_grad"):
+        mem.sequence_device(x.clone().requires_grad_(), torch.zeros(2, 32), torch.zeros(3, 2), api=MB.EmuApi())
+    with pytest.raises(ValueError, match="h0 must be"):
+        mem.sequence_device(x, torch.zeros(2, 16), torch.zeros(3, 2), api=MB.EmuApi())
+    with pytest.raises(Exception, match="no lsim_gru_sequence_forward"):
+        mem.sequence_device(x, torch.zeros(2, 32), torch.zeros(3, 2), api=types.SimpleNamespace())
+
+
+def test_sequence_is_T_calls_of_forward():
+    s, c = MB.SHAPES["B"], MB.sequence_case("B")
+    mem = _memory_of(s, c["prm"])
+    x, h0, reset = torch.from_numpy(c["x"]), torch.from_numpy(c["h0"]), torch.from_numpy(c["reset"])
+    with torch.no_grad():
+        hs = mem.sequence(x, h0, reset)
+        h = h0
+        for t in range(s["T"]):
+            h = mem(x[t, :, :s["L"]], x[t, :, s["L"]:], h, reset[t] != 0)
+            assert torch.equal(h, hs[t])
+    gi, e_gi, s_gi = R.project(c["x"], c["prm"])
+    want = R.sequence(gi, c["h0"], c["reset"], c["prm"], e_gi, s_gi)
+    assert (np.abs(hs.numpy() - want["hs"]) <= want["e_hs"]).all()
+
+
+@pytest.mark.parametrize("name", ["A", "B", "D"])
+def test_sequence_device_through_the_shim_has_the_gradients_of_autograd(name):
+    """hs within the bound; dW_ih, dW_hh, db_ih, db_hh and dh0 within 4 x the distance of autograd through the torch fp32 loop from the fp64 reference"""
+    s, c = MB.SHAPES[name], MB.sequence_case(name)
+    mem = _memory_of(s, c["prm"])
+    x, reset, dhs = torch.from_numpy(c["x"]), torch.from_numpy(c["reset"]), torch.from_numpy(c["dhs"])
+    gi, e_gi, s_gi = R.project(c["x"], c["prm"])
+    fwd = R.sequence(gi, c["h0"], c["reset"], c["prm"], e_gi, s_gi)
+    bwd = R.backward(c["dhs"], fwd, c["h0"], c["reset"], c["prm"])
+    want = list(R.param_grads(c["x"], fwd, bwd, c["h0"], c["reset"])) + [bwd["dh0"]]
+    grads = {}
+    for which in ("sequence", "sequence_device"):
+        mem.zero_grad()
+        h0 = torch.from_numpy(c["h0"]).clone().requires_grad_()
+        hs = mem.sequence_device(x, h0, reset, api=MB.EmuApi()) if which == "sequence_device" else mem.sequence(x, h0, reset)
+        assert (np.abs(hs.detach().numpy() - fwd["hs"]) <= fwd["e_hs"]).all(), which
+        (hs * dhs).sum().backward()
+        grads[which] = [p.grad.numpy().astype(np.float64) for p in mem.device_params()] + [h0.grad.numpy().astype(np.float64)]
+    for k, (w, twin, got) in enumerate(zip(want, grads["sequence"], grads["sequence_device"])):
+        dist = np.abs(twin - w).max()
+        assert 0 < dist < 1e-3 * max(np.abs(w).max(), 1.0)
+        assert np.abs(got - w).max() <= 4 * dist, (k, np.abs(got - w).max(), dist)
+
+
+def _alg(L, Pm, H, N, T, seed=0, api=None):
+    torch.manual_seed(seed)
+    ac = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L + H)
+    enc = DepthEncoder(12, 16, 2, c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=L)
+    mem = DepthMemory(L, Pm, H)
+    frames = torch.randn(N, 2, 12, 16)
+    alg = V.VisionPPO(ac, aux_snapshots=1, device="cpu")
+    alg.attach(enc, lambda: torch.zeros(N, L + H), lambda: frames, memory=mem)
+    alg.memory_api = api
+    alg.init_storage(N, T, [O], [P], [A])
+    return alg, ac, enc, mem
+
+
+@pytest.mark.parametrize("path", ["torch", "shim"])
+def test_memory_step_learns_what_it_saw_three_steps_earlier(path):
+    """T = 8, N = 16: the target at step t is a fixed function of the input of step t - 3, which only a cell that remembers can regress;
+    30 memory_step updates (4 env slices each) end below the first loss.  Recorded: 0.2958 -> 0.2483, ratio 0.839, the same on either path"""
+    L, Pm, H, N, T = 6, 4, 16, 16, 8
+    alg, ac, enc, mem = _alg(L, Pm, H, N, T, seed=3, api=MB.EmuApi() if path == "shim" else None)
+    st = alg.storage
+    g = torch.Generator().manual_seed(5)
+    st.depth_latent[:, :, :L] = torch.randn(T, N, L, generator=g)
+    st.depth_latent[:, :, L:] = 0.0
+    st.observations[:, :, :Pm] = torch.randn(T, N, Pm, generator=g)
+    st.dones.zero_()
+    mix = torch.randn(L + Pm, 187, generator=g) / (L + Pm) ** 0.5
+    xin = torch.cat((st.depth_latent[:, :, :L], st.observations[:, :, :Pm]), dim=-1)
+    off = P - 187
+    st.privileged_observations.zero_()
+    st.privileged_observations[3:, :, off:] = torch.tanh(xin[:-3] @ mix)
+    losses = [float(alg.memory_step()) for _ in range(30)]
+    print(f"memory-step losses ({path}): first {losses[0]:.4f}, last {losses[-1]:.4f}, ratio {losses[-1] / losses[0]:.3f}")
+    assert losses[-1] < losses[0], losses
+    assert all(p.grad is not None for p in mem.parameters()) and all(p.grad is not None for p in alg.memory_head.parameters())
+    assert all(p.grad is None for p in enc.parameters()) and all(p.grad is None for p in ac.parameters()) and all(p.grad is None for p in alg.depth_head.parameters())
+    assert not {id(p) for p in mem.parameters()} & {id(p) for g_ in alg.optimizer.param_groups for p in g_["params"]}
+    # update() appends the memory loss behind the auxiliary loss; a rollout of one step has no sequence
+    alg1, *_ = _alg(L, Pm, H, 4, 1)
+    assert alg1.memory_step() is None
+
+
+def test_memory_data_slices_and_alignment_of_a_stored_rollout_on_the_emulated_env():
+    """the sensor hook on the emulated env, recorded the way the rollout records it: every stored h row is one cell step from the row stored
+    before it with x_t = [z_t | obs_t[:P]] and reset_t = dones[t-1] -- what memory_data() hands to the sequence pass"""
+    import eval_emu_binding
+    from helpers import C
+    from isaacgymloco_amd.envs import sensors
+    cfg = C.mixed_cfg("aliengo", {"aliengo": 0.5, "go2": 0.5})[0]
+    cfg.env.num_envs = 4
+    cfg.terrain.num_rows, cfg.terrain.num_cols = 2, 2
+    cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = eval_emu_binding.emu_mixed_env(cfg)
+    env.reset()
+    api = MB.EmuApi(count=("lsim_depth_encode", "lsim_depth_memory_step"))
+    torch.manual_seed(2)
+    L, Pm, H, T = 6, 9, 16, 6
+    enc = DepthEncoder(4, 6, 2, c1=3, k1=2, s1=1, c2=5, k2=2, s2=1, latent_dim=L)
+    mem = DepthMemory(L, Pm, H)
+    m = sensors.SensorModel(period=2, stagger=True, latency=1, frames=2, clip=(0.1, 3.0), normalise=True)
+    kw = dict(mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, api=api, see_robot=True)
+    bare = sensors.depth_camera(env, 6, 4, 87.0, model=m, **kw)
+    with pytest.raises(ValueError, match="no encoder"):
+        bare.attach_memory(mem)
+    with pytest.raises(ValueError, match="no memory"):
+        bare.memory_rows()
+    cam = env.add_sensor("depth", sensors.depth_camera(env, 6, 4, 87.0, model=m, **kw))
+    cam.attach_encoder(enc)
+    assert api.calls["lsim_depth_memory_step"] == 0 and cam._memory is None          # without attach_memory nothing is allocated or launched
+    env.step_device(torch.zeros(4, 12))
+    assert api.calls["lsim_depth_memory_step"] == 0 and mem._h is None
+    assert cam.attach_memory(mem) is mem and api.calls["lsim_depth_memory_step"] == 1
+    prm = tuple(p.detach().numpy() for p in mem.device_params())
+    want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), np.zeros((4, H)), np.ones(4, bool), prm)
+    assert (np.abs(mem.state().numpy() - want) <= bound).all(), "attach_memory steps every env from h = 0"
+    assert cam.memory_rows().shape == (4, L + H) and torch.equal(cam.memory_rows()[:, :L], cam.latent()) and torch.equal(cam.memory_rows()[:, L:], mem.state())
+    env.episode_length_buf[1] = int(env.max_episode_length) - 3          # env 1 times out inside the rollout
+    alg, *_ = _alg(L, Pm, H, 4, T)
+    alg.memory = mem
+    st = V.VisionRolloutStorage(4, T, [env.num_obs], [env.num_privileged_obs], [12], L + H, "cpu")
+    alg.storage = st
+    alg.height_scan = V.height_scan_block()
+    g = torch.Generator().manual_seed(4)
+    for t in range(T):
+        st.depth_latent[t].copy_(cam.memory_rows())
+        st.observations[t].copy_(env.obs_buf)
+        st.privileged_observations[t].copy_(env.privileged_obs_buf)
+        calls = dict(api.calls)
+        env.step_device(torch.randn(4, 12, generator=g) * 0.3)
+        assert api.calls["lsim_depth_memory_step"] == calls["lsim_depth_memory_step"] + 1 == api.calls["lsim_depth_encode"] - calls["lsim_depth_encode"] + calls["lsim_depth_memory_step"]
+        st.dones[t, :, 0] = env.reset_buf.to(torch.uint8)
+    assert st.dones[:, 1].any() and not st.dones[:, 0].any()
+    x, h0, reset, target = alg.memory_data()
+    assert x.shape == (T - 1, 4, L + Pm) and h0.shape == (4, H) and reset.shape == (T - 1, 4) and target.shape == (T - 1, 4, 187)
+    assert torch.equal(h0, st.depth_latent[0][:, L:]) and torch.equal(reset, st.dones[:-1, :, 0])
+    for t in range(1, T):
+        xt = x[t - 1].numpy()
+        want, bound = R.step(xt[:, :L], xt[:, L:], st.depth_latent[t - 1][:, L:].numpy(), reset[t - 1].numpy() != 0, prm)
+        got = st.depth_latent[t][:, L:].numpy()
+        assert (np.abs(got - want) <= bound).all(), t
+        wrong, _ = R.step(xt[:, :L], xt[:, L:], st.depth_latent[t - 1][:, L:].numpy(), np.zeros(4, bool), prm)
+        if reset[t - 1].any():
+            assert (np.abs(got - wrong) > bound)[reset[t - 1].numpy() != 0].any(), "a reset env's h is GRU(x, 0), not GRU(x, h)"
+    # a reset by hand reaches the memory with the sensor's flags: only env 2 is stepped, from h = 0
+    before = mem.state().clone()
+    env.reset_idx([2])
+    after = mem.state()
+    assert torch.equal(after[[0, 1, 3]], before[[0, 1, 3]]) and not torch.equal(after[2], before[2])
+    want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), before.numpy(), np.array([False, False, True, False]), prm)
+    assert (np.abs(after.numpy()[2] - want[2]) <= bound[2]).all()
+    with pytest.raises(ValueError, match="fp32"):
+        DepthMemory(L, Pm, H).double().step_device(cam)
+    with pytest.raises(ValueError, match="latent columns"):
+        DepthMemory(L + 1, Pm, H).step_device(cam)
+
+
+def test_warm_started_twin_is_the_memoryless_vision_policy():
+    torch.manual_seed(1)
+    L, H = 10, 16
+    small = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L)
+    with torch.no_grad():
+        for p in small.parameters():
+            p.add_(0.05 * torch.randn_like(p))
+    wide = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L + H)
+    wide.load_vision_state_dict(small.state_dict())
+    assert torch.equal(wide.actor[0].weight[:, :K_HIM + L], small.actor[0].weight) and not wide.actor[0].weight[:, K_HIM + L:].any()
+    obs, priv, lat = torch.randn(9, O), torch.randn(9, P), torch.randn(9, L)
+    with torch.no_grad():
+        want = small.act_inference(obs, lat)
+        for h in (torch.randn(9, H), 1e4 * torch.randn(9, H), torch.zeros(9, H)):
+            assert torch.equal(wide.act_inference(obs, torch.cat((lat, h), dim=1)), want)
+        assert torch.equal(wide.evaluate(priv), small.evaluate(priv))
+    with pytest.raises(ValueError, match="actor.0.weight"):
+        small.load_vision_state_dict(wide.state_dict())
+
+
+def _hand_built_runner(seed, with_memory):
+    torch.manual_seed(seed)
+    L, H = 10, 16
+    ac = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L + (H if with_memory else 0))
+    frames = torch.randn(8, 2, 12, 16)
+    alg = V.VisionPPO(ac, aux_snapshots=1, device="cpu")
+    enc = DepthEncoder(12, 16, 2, c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=L)
+    alg.attach(enc, lambda: None, lambda: frames, memory=DepthMemory(L, 5, H) if with_memory else None)
+    alg.init_storage(8, 4, [O], [P], [A])
+    run = V.VisionOnPolicyRunner.__new__(V.VisionOnPolicyRunner)
+    run.alg, run.env, run.device, run.graphs = alg, types.SimpleNamespace(), "cpu", None
+    run.dist_ctx = types.SimpleNamespace(enabled=False)
+    run.current_learning_iteration = 7
+    return run, alg
+
+
+def test_checkpoint_round_trips_memory_head_and_moments_and_is_unchanged_without(tmp_path):
+    run, alg = _hand_built_runner(10, True)
+    st = alg.storage
+    st.depth_latent.normal_(), st.observations.normal_(), st.privileged_observations.normal_()
+    for _ in range(2):
+        alg.memory_step()
+    path = os.path.join(str(tmp_path), "model.pt")
+    run.save(path)
+    d = torch.load(path, map_location="cpu", weights_only=False)
+    assert d["vision"]["memory"] == {"latent_dim": 10, "proprio_dim": 5, "hidden": 16} and d["vision"]["latent_dim"] == 26
+    assert set(d["depth_memory_state_dict"]) == {"cell.weight_ih", "cell.weight_hh", "cell.bias_ih", "cell.bias_hh"}
+    run2, alg2 = _hand_built_runner(11, True)
+    assert not torch.equal(alg2.memory.cell.weight_hh, alg.memory.cell.weight_hh)
+    run2.load(path)
+    for a, b in ((alg.memory, alg2.memory), (alg.memory_head, alg2.memory_head)):
+        sa, sb = a.state_dict(), b.state_dict()
+        assert set(sa) == set(sb) and all(torch.equal(sa[k], sb[k]) for k in sa)
+    oa, ob = alg.memory_optimizer.state_dict(), alg2.memory_optimizer.state_dict()
+    assert len(oa["state"]) == 6 and set(oa["state"]) == set(ob["state"])
+    for k in oa["state"]:
+        for name in ("exp_avg", "exp_avg_sq", "step"):
+            assert torch.equal(torch.as_tensor(oa["state"][k][name]), torch.as_tensor(ob["state"][k][name]))
+    alg2.storage = alg.storage
+    assert float(alg.memory_step()) == float(alg2.memory_step())          # both continue identically
+    # without a memory: today's keys, today's record
+    plain, _ = _hand_built_runner(12, False)
+    p2 = os.path.join(str(tmp_path), "plain.pt")
+    plain.save(p2)
+    d0 = torch.load(p2, map_location="cpu", weights_only=False)
+    assert set(d) - set(d0) == {"depth_memory_state_dict", "depth_memory_head_state_dict", "depth_memory_optimizer_state_dict"}
+    assert set(d0["vision"]) == {"encoder", "sensor", "latent_dim"} and d0["vision"]["latent_dim"] == 10
+    out = plain.alg
+    assert out.memory is None and out.memory_head is None and out.memory_optimizer is None
+
+
+def test_exporter_remembers_like_the_module_and_is_unchanged_without(tmp_path):
+    from isaacgymloco_amd.envs.sensors import SensorModel
+    from isaacgymloco_amd.learn.export import PolicyExporterVision, PolicyExporterVisionMemory, export_policy_as_jit
+    torch.manual_seed(6)
+    L, Pm, H = 10, 7, 16
+    ac = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L + H)
+    enc = DepthEncoder(12, 16, 2, c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=L)
+    mem = DepthMemory(L, Pm, H)
+    spec = {"near": 0.05, "far": 5.0, "model": {"period": 5, "stagger": True, "latency": 1, "frames": 2, "noise": [0.0, 0.0], "dropout": 0.0,
+                                                 "drop_value": 0.0, "clip": None, "normalise": True}}
+    SensorModel(**spec["model"])
+    path = export_policy_as_jit(ac, str(tmp_path), encoder=enc, sensor=spec, memory=mem)
+    mod = torch.jit.load(path)
+    assert mod.hidden == H
+    obs, frames, h = torch.randn(5, O), torch.rand(5, 2, 12, 16), 0.3 * torch.randn(5, H)
+    with torch.no_grad():
+        z = enc(frames)
+        assert torch.equal(mod.encode(frames), z)
+        h2 = mod.remember(z, obs, h)
+        assert torch.equal(h2, mem(z, obs[:, :Pm], h))
+        assert torch.equal(mod.remember(z, obs, torch.zeros(5, H)), mem(z, obs[:, :Pm], h, torch.ones(5, dtype=torch.bool)))
+        actions, h3 = mod(obs, frames, h)
+        assert torch.equal(h3, h2) and torch.equal(actions, mod.act(obs, torch.cat((z, h2), dim=1)))
+        assert torch.equal(actions, ac.act_inference(obs, torch.cat((z, h2), dim=1)))
+    with pytest.raises(ValueError, match="encoder reads"):
+        PolicyExporterVision(ac, enc, spec)                                          # the actor reads L + H columns: the memory is part of it
+    with pytest.raises(ValueError, match="memory reads"):
+        PolicyExporterVisionMemory(ac, enc, spec, DepthMemory(L, 46, H))
+    small = V.VisionActorCritic(O, P, N1, A, depth_latent_dim=L)
+    plain = torch.jit.load(export_policy_as_jit(small, os.path.join(str(tmp_path), "plain"), encoder=enc, sensor=spec))
+    assert not hasattr(plain, "remember") and not hasattr(plain, "hidden")
+    with torch.no_grad():
+        assert torch.equal(plain(obs, frames), small.act_inference(obs, enc(frames)))

@@ -1,7 +1,7 @@
 """Collection and update time per iteration of VisionOnPolicyRunner next to HIMOnPolicyRunner on the same env configuration, both with the
 depth camera attached (the HIM runner merely does not read it), and the encoder's own step separately.
 
-    python tools/vision_train_time.py [--envs 4096] [--iters 6] [--warmup 2] [--out profiles/vision_train_time.json]
+    python tools/vision_train_time.py [--envs 4096] [--iters 6] [--warmup 2] [--memory] [--out profiles/vision_train_time.json]
 
 Wall clock around device synchronisations, as the runners' own last_perf; the encoder step with HIP events inside VisionPPO.update()."""
 import argparse, json, os, sys
@@ -24,8 +24,8 @@ def make(kind, a):
                                                        model=sensors.SensorModel(period=5, stagger=True, latency=1, frames=2, normalise=True)))
     tc = train_cfg_dict("aliengo")
     torch.manual_seed(0)
-    if kind == "vision":
-        run = VisionOnPolicyRunner(env, tc, sensor="depth", device=DEV)
+    if kind in ("vision", "memory"):
+        run = VisionOnPolicyRunner(env, tc, sensor="depth", device=DEV, memory=True if kind == "memory" else None)
     else:
         from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
         cam.attach_encoder(DepthEncoder(a.height, a.width, 2).to(DEV))      # the same launches per step; nobody reads the latent
@@ -36,8 +36,17 @@ def make(kind, a):
 
 def measure(kind, a):
     run = make(kind, a)
-    enc_ms = []
-    if kind == "vision":
+    enc_ms, mem_ms = [], []
+    if kind == "memory":
+        mstep = run.alg.memory_step
+
+        def timed_memory_step():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); out = mstep(); e1.record()
+            mem_ms.append((e0, e1))
+            return out
+        run.alg.memory_step = timed_memory_step
+    if kind in ("vision", "memory"):
         alg, step = run.alg, run.alg.encoder_step
 
         def timed_step():
@@ -58,6 +67,9 @@ def measure(kind, a):
     if enc_ms:
         out["encoder_step_s"] = med([e0.elapsed_time(e1) * 1e-3 for e0, e1 in enc_ms[a.warmup:]])
         out["aux_loss"] = run.alg.last_aux_loss
+    if mem_ms:
+        out["memory_step_s"] = med([e0.elapsed_time(e1) * 1e-3 for e0, e1 in mem_ms[a.warmup:]])
+        out["memory_loss"] = run.alg.last_memory_loss
     del run
     torch.cuda.empty_cache()
     return out
@@ -71,11 +83,14 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vision_train_time.json"))
+    ap.add_argument("--memory", action="store_true", help="also the vision runner with a depth memory (memory=True): collection, update and memory-step time")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("vision_train_time.py needs a GPU: there is no CPU form of this measurement")
     res = {"what": "seconds per PPO iteration (100 steps), median; update_s of the vision runner includes encoder_step_s", "num_envs": a.envs,
            "camera": [a.width, a.height], "device": torch.cuda.get_device_name(0), "him": measure("him", a), "vision": measure("vision", a)}
+    if a.memory:
+        res["memory"] = measure("memory", a)          # update_s includes encoder_step_s and memory_step_s
     print(json.dumps(res))
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     json.dump(res, open(a.out, "w"), indent=1)
