@@ -243,13 +243,8 @@ extern "C" int lsim_amp_step(const lsim_amp_disc* d, const float* amp_obs, const
     a.part = (float*)((char*)workspace + ((groups * sizeof(unsigned int) + 255) / 256) * 256);
     const size_t lds = (size_t)LS_AMP_LDS_FLOATS * sizeof(float);
     static size_t configured[2][64] = {{0}};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
     const void* fn = ns == 2 ? (const void*)lsim_k_amp_step<2> : (const void*)lsim_k_amp_step<1>;
-    if (lds > configured[ns - 1][dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
-        configured[ns - 1][dev] = lds;
-    }
+    if (ls_allow_dynamic_lds(fn, lds, configured[ns - 1]) != LSIM_OK) return LSIM_E_HIP;
     if (ns == 2) hipLaunchKernelGGL(lsim_k_amp_step<2>, dim3((unsigned)groups, 2), dim3(64 * LS_AMP_WAVES), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(lsim_k_amp_step<1>, dim3((unsigned)groups, 1), dim3(64 * LS_AMP_WAVES), lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;

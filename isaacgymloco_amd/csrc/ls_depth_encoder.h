@@ -243,15 +243,8 @@ extern "C" int lsim_depth_encode(const lsim_depth_encoder_t* de, void* stream) {
     const int rv = ls_de_validate(de, p);
     if (rv != LSIM_OK) return rv;
     const size_t lds = (size_t)p.words * 4u;
-    if (lds > 64u * 1024u) {                    // above 64 KB the device's copy of the kernel needs the attribute, once per device and size
-        static size_t configured[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
-        if (lds > configured[dev]) {
-            if (hipFuncSetAttribute((const void*)lsim_k_depth_encode, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
-            configured[dev] = lds;
-        }
-    }
+    static size_t configured[64] = {0};
+    if (ls_allow_dynamic_lds((const void*)lsim_k_depth_encode, lds, configured) != LSIM_OK) return LSIM_E_HIP;
     hipLaunchKernelGGL(lsim_k_depth_encode, dim3((unsigned)ls_de_env_slots(*de)), dim3(LS_DE_BLOCK), lds, (hipStream_t)stream, *de, p, ls_de_tick_mod(*de));
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }

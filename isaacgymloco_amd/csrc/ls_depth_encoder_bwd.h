@@ -402,15 +402,8 @@ extern "C" int lsim_depth_encode_backward(const lsim_depth_encoder_bwd_t* db, vo
     const int rv = ls_deb_validate(db, de, p, q);
     if (rv != LSIM_OK) return rv;
     const size_t lds = (size_t)q.words * 4u;
-    if (lds > 64u * 1024u) {                    // as in lsim_depth_encode: once per device and size
-        static size_t configured[64] = {0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
-        if (lds > configured[dev]) {
-            if (hipFuncSetAttribute((const void*)lsim_k_depth_encode_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
-            configured[dev] = lds;
-        }
-    }
+    static size_t configured[64] = {0};
+    if (ls_allow_dynamic_lds((const void*)lsim_k_depth_encode_bwd, lds, configured) != LSIM_OK) return LSIM_E_HIP;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(lsim_k_depth_encode_bwd, dim3((unsigned)q.G), dim3(LS_DE_BLOCK), lds, st, *db, p, q);
     const int jtiles = (p.K3 + 1 + 15) >> 4, otiles = (db->latent_dim + 15) >> 4;

@@ -320,18 +320,6 @@ __global__ __launch_bounds__(LS_GRU_BLOCK) void lsim_k_gru_sequence_backward(con
     }
 }
 
-// above 64 KB the device's copy of a kernel needs the attribute, once per device and size (as lsim_depth_encode)
-static int ls_gru_allow_lds(const void* kernel, size_t lds, size_t* configured) {
-    if (lds <= 64u * 1024u) return LSIM_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
-    if (lds > configured[dev]) {
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
-        configured[dev] = lds;
-    }
-    return LSIM_OK;
-}
-
 extern "C" int lsim_depth_memory_sizes(int32_t hidden, int32_t input_dim, size_t* lds_step, size_t* lds_forward, size_t* lds_backward) {
     return ls_gru_sizes(hidden, input_dim, lds_step, lds_forward, lds_backward);
 }
@@ -342,7 +330,7 @@ extern "C" int lsim_depth_memory_step(const lsim_depth_memory_t* dm, void* strea
     if (rv != LSIM_OK) return rv;
     static size_t configured[64] = {0};
     const size_t lds = (size_t)p.step_words * 4u;
-    if (ls_gru_allow_lds((const void*)lsim_k_depth_memory_step, lds, configured) != LSIM_OK) return LSIM_E_HIP;
+    if (ls_allow_dynamic_lds((const void*)lsim_k_depth_memory_step, lds, configured) != LSIM_OK) return LSIM_E_HIP;
     hipLaunchKernelGGL(lsim_k_depth_memory_step, dim3((unsigned)ls_gru_tiles(dm->num_envs)), dim3(LS_GRU_BLOCK), lds, (hipStream_t)stream, *dm, p);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
@@ -353,7 +341,7 @@ extern "C" int lsim_gru_sequence_forward(const lsim_gru_sequence_t* gs, void* st
     if (rv != LSIM_OK) return rv;
     static size_t configured[64] = {0};
     const size_t lds = (size_t)p.fwd_words * 4u;
-    if (ls_gru_allow_lds((const void*)lsim_k_gru_sequence_forward, lds, configured) != LSIM_OK) return LSIM_E_HIP;
+    if (ls_allow_dynamic_lds((const void*)lsim_k_gru_sequence_forward, lds, configured) != LSIM_OK) return LSIM_E_HIP;
     hipLaunchKernelGGL(lsim_k_gru_sequence_forward, dim3((unsigned)ls_gru_tiles(gs->num_envs)), dim3(LS_GRU_BLOCK), lds, (hipStream_t)stream, *gs, p);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
@@ -364,7 +352,7 @@ extern "C" int lsim_gru_sequence_backward(const lsim_gru_sequence_t* gs, void* s
     if (rv != LSIM_OK) return rv;
     static size_t configured[64] = {0};
     const size_t lds = (size_t)p.bwd_words * 4u;
-    if (ls_gru_allow_lds((const void*)lsim_k_gru_sequence_backward, lds, configured) != LSIM_OK) return LSIM_E_HIP;
+    if (ls_allow_dynamic_lds((const void*)lsim_k_gru_sequence_backward, lds, configured) != LSIM_OK) return LSIM_E_HIP;
     hipLaunchKernelGGL(lsim_k_gru_sequence_backward, dim3((unsigned)ls_gru_tiles(gs->num_envs)), dim3(LS_GRU_BLOCK), lds, (hipStream_t)stream, *gs, p);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }

@@ -279,3 +279,20 @@ LS_FN float ls_u01(uint32_t seed, uint32_t rank, uint32_t env, uint32_t step, ui
 }
 // isaacgym.torch_utils.torch_rand_float: span formed on the host in double, then fp32 (upper-lower)*u + lower
 LS_FN float rand_range(float u, float lo, float hi) { return (hi - lo) * u + lo; }
+
+// ---- host side of a launch with dynamic LDS ----
+// Above 64 KB of dynamic LDS the device's copy of a kernel needs hipFuncAttributeMaxDynamicSharedMemorySize, once per device and size;
+// at or below 64 KB the attribute is not needed and nothing is called.  `configured`: the kernel's own row of 64 sizes, one per device.
+#if defined(__HIPCC__) && !defined(LS_EMU)
+#include "../../include/lsim.h"
+static inline int ls_allow_dynamic_lds(const void* kernel, size_t lds, size_t* configured) {
+    if (lds <= 64u * 1024u) return LSIM_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
+    if (lds > configured[dev]) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
+        configured[dev] = lds;
+    }
+    return LSIM_OK;
+}
+#endif

@@ -415,17 +415,12 @@ static int ls_policy_launch(const lsim_him_policy* p, const float* obs, const fl
     const int rows = wide ? 32 : 16;
     const size_t lds = (size_t)rows * (LS_POL_STRIDE_IN + LS_POL_STRIDE_A + LS_POL_STRIDE_B) * sizeof(float);
     static size_t configured[8][64] = {{0}};     // per kernel and device: the attribute belongs to the device's copy of the kernel
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LSIM_E_HIP;
     const void* fn = wide ? (act ? (const void*)lsim_k_policy_forward<32, 16, true> : (const void*)lsim_k_policy_forward<32, 16, false>)
                           : (act ? (const void*)lsim_k_policy_forward<16, 8, true> : (const void*)lsim_k_policy_forward<16, 8, false>);
     if (ext) fn = wide ? (act ? (const void*)lsim_k_policy_forward<32, 16, true, true> : (const void*)lsim_k_policy_forward<32, 16, false, true>)
                        : (act ? (const void*)lsim_k_policy_forward<16, 8, true, true> : (const void*)lsim_k_policy_forward<16, 8, false, true>);
     const int slot = 4 * (int)(ext != nullptr) + 2 * (int)wide + (int)act;
-    if (lds > configured[slot][dev]) {
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return LSIM_E_HIP;
-        configured[slot][dev] = lds;
-    }
+    if (ls_allow_dynamic_lds(fn, lds, configured[slot]) != LSIM_OK) return LSIM_E_HIP;
     const int blocks = (int)((num_envs + rows - 1) / rows);
 #define LS_POL_LAUNCH_ARGS(R, W, A, E, ARGS) hipLaunchKernelGGL((lsim_k_policy_forward<R, W, A, E>), dim3(blocks, 2), dim3(64 * W), lds, (hipStream_t)stream, *p, obs, priv_obs, \
                                                                (long)num_envs, mean_out, values_out, ARGS)

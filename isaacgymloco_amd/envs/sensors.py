@@ -162,7 +162,7 @@ class RaySensor:
         rc.near, rc.far = self.near, self.far
         self._rc = rc
         self._labels = None
-        self._encoder = self._latent = self._memory = None
+        self._encoder = self._latent = self._memory = self._memory_h = self._memory_rows = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
@@ -311,10 +311,14 @@ class RaySensor:
 
     def attach_memory(self, mem):
         """from now on the encoder's launch of every update() / refresh() is followed by `mem`'s (learn.depth_memory.DepthMemory.step_device)
-        on the same stream with the same flags; steps every env once now from h = 0 (LSIM_SENSOR_FILL_ALL).  Needs an attached encoder."""
+        on the same stream with the same flags; steps every env once now from h = 0 (LSIM_SENSOR_FILL_ALL).  Needs an attached encoder.
+        The hidden state h [N, H] and the rows [N, L + H] are this sensor's, like its latent: one `mem` may serve several sensors."""
         if self._encoder is None:
             raise ValueError("attach_memory: the sensor has no encoder (attach_encoder first): the memory reads its latent rows")
         self._latent_buffer(self._encoder.latent_dim)
+        N, widths = int(self.env.num_envs), (mem.hidden, mem.latent_dim + mem.hidden)
+        if self._memory_h is None or (self._memory_h.shape[1], self._memory_rows.shape[1]) != widths:
+            self._memory_h, self._memory_rows = (torch.zeros((N, w), dtype=torch.float32, device=self._out.device) for w in widths)
         self._memory = mem
         mem.step_device(self, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
         return mem
@@ -323,7 +327,13 @@ class RaySensor:
         """live [N, L + H] tensor: row e = [latent of env e | its memory's hidden state] (attach_memory)"""
         if self._memory is None:
             raise ValueError("the sensor has no memory (attach_memory)")
-        return self._memory.rows()
+        return self._memory_rows
+
+    def memory_state(self):
+        """live [N, H] tensor: the hidden state of every env's memory (attach_memory)"""
+        if self._memory is None:
+            raise ValueError("the sensor has no memory (attach_memory)")
+        return self._memory_h
 
     def _latent_buffer(self, latent_dim):
         """the [N, stride] buffer an encoder's launch writes; created on first use"""

@@ -38,6 +38,33 @@ def _all_live(device, batch):
     return t
 
 
+def check_params(what, names, params, dev):
+    """the launches read the parameters' own storage: each must be fp32, contiguous and on `dev`"""
+    for name, p in zip(names, params):
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+            raise ValueError(f"{what}: parameter {name} must be fp32, contiguous and on {dev} (is {p.dtype}, "
+                             f"{'contiguous' if p.is_contiguous() else 'strided'}, {p.device})")
+
+
+def _launch_struct(enc, hist_ptr, hist_stride, hist_slots, episode_length, num_envs, env_stride, latent, params, tick, period, stagger, flags):
+    """the lsim_depth_encoder_t of ONE launch: `enc`'s extents, the frame history, the envs, the latent buffer and the parameters"""
+    de = abi.LsimDepthEncoder.from_buffer_copy(enc._extents)
+    de.hist, de.hist_stride, de.hist_slots = hist_ptr, hist_stride, hist_slots
+    de.episode_length, de.num_envs, de.env_stride = episode_length, num_envs, env_stride
+    de.w1, de.b1, de.w2, de.b2, de.w3, de.b3 = (p.data_ptr() for p in params)
+    de.final_act = int(enc.final_act)
+    de.latent, de.latent_stride = latent.data_ptr(), latent.shape[1]
+    de.tick, de.period, de.stagger, de.flags = int(tick), int(period), int(stagger), int(flags)
+    return de
+
+
+def _copy_extents(enc, dst):
+    """the ten extents of `enc` into another struct that names them alike (lsim_depth_encoder_bwd_t)"""
+    for k in ("height", "width", "frames", "c1", "k1", "s1", "c2", "k2", "s2", "latent_dim"):
+        setattr(dst, k, getattr(enc._extents, k))
+    return dst
+
+
 class _DepthEncodeFn(torch.autograd.Function):
     """latent = lsim_depth_encode over a batch of frames (hist_slots = frames, FILL_ALL); backward = lsim_depth_encode_backward"""
 
@@ -45,13 +72,8 @@ class _DepthEncodeFn(torch.autograd.Function):
     def forward(ctx, enc, api, hist, hist_stride, *params):
         B, L = hist.shape[0], enc.latent_dim
         latent = torch.empty(B, (L + 3) // 4 * 4, device=hist.device, dtype=torch.float32)
-        de = abi.LsimDepthEncoder.from_buffer_copy(enc._extents)
-        de.hist, de.hist_stride, de.hist_slots = hist.data_ptr(), hist_stride, enc.frames
-        de.episode_length, de.num_envs, de.env_stride = _all_live(hist.device, B).data_ptr(), B, 1
-        de.w1, de.b1, de.w2, de.b2, de.w3, de.b3 = (p.data_ptr() for p in params)
-        de.final_act = int(enc.final_act)
-        de.latent, de.latent_stride = latent.data_ptr(), latent.shape[1]
-        de.tick, de.period, de.stagger, de.flags = 0, 1, 0, abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+        de = _launch_struct(enc, hist.data_ptr(), hist_stride, enc.frames, _all_live(hist.device, B).data_ptr(), B, 1, latent, params,
+                            0, 1, 0, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
         lib.check(api.lsim_depth_encode(ctypes.byref(de), torch.cuda.current_stream(hist.device).cuda_stream), what="lsim_depth_encode")
         out = latent[:, :L]
         ctx.enc, ctx.api, ctx.hist_stride = enc, api, hist_stride
@@ -64,9 +86,7 @@ class _DepthEncodeFn(torch.autograd.Function):
         enc, api = ctx.enc, ctx.api
         if g.dtype != torch.float32 or g.stride(1) != 1:
             g = g.float().contiguous()
-        db = abi.LsimDepthEncoderBwd()
-        for k in ("height", "width", "frames", "c1", "k1", "s1", "c2", "k2", "s2", "latent_dim"):
-            setattr(db, k, getattr(enc._extents, k))
+        db = _copy_extents(enc, abi.LsimDepthEncoderBwd())
         db.hist, db.hist_stride, db.hist_slots, db.batch = hist.data_ptr(), ctx.hist_stride, enc.frames, hist.shape[0]
         db.final_act, db.grid_limit = int(enc.final_act), 0
         db.g, db.g_stride, db.latent, db.latent_stride = g.data_ptr(), g.stride(0), latent.data_ptr(), latent.stride(0)
@@ -142,19 +162,11 @@ class DepthEncoder(nn.Module):
         if entry is None:
             raise lib.LsimError("the loaded library has no lsim_depth_encode: rebuild it (there is no torch fall-back for the depth encoder)")
         hist = sensor._hist
-        for name, p in zip(("w1", "b1", "w2", "b2", "w3", "b3"), self.device_params()):
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != hist.device:
-                raise ValueError(f"encode_device: parameter {name} must be fp32, contiguous and on {hist.device} (is {p.dtype}, "
-                                 f"{'contiguous' if p.is_contiguous() else 'strided'}, {p.device})")
+        params = self.device_params()
+        check_params("encode_device", _PARAM_NAMES, params, hist.device)
         latent = sensor._latent_buffer(self.latent_dim)
-        de = abi.LsimDepthEncoder.from_buffer_copy(self._extents)
-        sm = sensor._sm
-        de.hist, de.hist_stride, de.hist_slots = hist.data_ptr(), hist.shape[2], hist.shape[1]
-        de.episode_length, de.num_envs, de.env_stride = sm.episode_length, hist.shape[0], sensor.env_stride
-        de.w1, de.b1, de.w2, de.b2, de.w3, de.b3 = (p.data_ptr() for p in self.device_params())
-        de.final_act = int(self.final_act)
-        de.latent, de.latent_stride = latent.data_ptr(), latent.shape[1]
-        de.tick, de.period, de.stagger, de.flags = int(tick), model.period, int(model.stagger), int(flags)
+        de = _launch_struct(self, hist.data_ptr(), hist.shape[2], hist.shape[1], sensor._sm.episode_length, hist.shape[0], sensor.env_stride,
+                            latent, params, tick, model.period, model.stagger, flags)
         lib.check(entry(ctypes.byref(de), sensor._stream(stream)), what="lsim_depth_encode")
         return latent[:, :self.latent_dim]
 
@@ -175,10 +187,7 @@ class DepthEncoder(nn.Module):
         dev = params[0].device
         if frames.dtype != torch.float32 or frames.device != dev:
             raise ValueError(f"forward_device: frames must be fp32 on {dev} (are {frames.dtype}, {frames.device})")
-        for name, p in zip(_PARAM_NAMES, params):
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise ValueError(f"forward_device: parameter {name} must be fp32, contiguous and on {dev} (is {p.dtype}, "
-                                 f"{'contiguous' if p.is_contiguous() else 'strided'}, {p.device})")
+        check_params("forward_device", _PARAM_NAMES, params, dev)
         R = self.height * self.width
         with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
             if frames.is_contiguous() and R % 4 == 0 and frames.data_ptr() % 16 == 0:

@@ -4,7 +4,10 @@ rsl_rl/modules/actor_critic_recurrent.py: a recurrent cell whose hidden state is
 
     mem = DepthMemory(enc.latent_dim, env.num_one_step_obs, hidden=64).to(env.device)
     cam.attach_memory(mem)                  # behind the encoder's launch of every update(): ONE more launch on the same stream
-    rows = cam.memory_rows()                # [N, L + H], live: row e = [z_e | h_e]
+    rows = cam.memory_rows()                # [N, L + H], live: row e = [z_e | h_e]; cam.memory_state() is h [N, H]
+
+The module is the cell's weights and the launches over them.  Everything per env -- h and the rows -- belongs to the sensor it is attached
+to (envs/sensors.py), next to the latent, so one DepthMemory serves any number of sensors and envs (a training env and an evaluation env).
 
 Four paths over ONE nn.GRUCell (gate order r, z, n; include/lsim.h, lsim_depth_memory_step, states the formulas):
   * `forward(z, p, h, fresh)` is one step in plain torch; `sequence(x, h0, reset)` the loop over it -- the CPU path and the twin in tests;
@@ -20,7 +23,9 @@ import torch
 from torch import nn
 
 from .. import abi, lib
+from .depth_encoder import check_params
 
+_PARAM_NAMES = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
 _ENTRIES = ("lsim_depth_memory_step", "lsim_gru_sequence_forward", "lsim_gru_sequence_backward", "lsim_depth_memory_sizes")
 
 
@@ -94,7 +99,6 @@ class DepthMemory(nn.Module):
         if self.hidden < 16 or self.hidden % 16 or self.hidden > d["LSIM_GRU_MAX_HIDDEN"]:
             raise ValueError(f"DepthMemory: hidden must be a multiple of 16 in 16 .. {d['LSIM_GRU_MAX_HIDDEN']}, got {self.hidden}")
         self.cell = nn.GRUCell(self.latent_dim + self.proprio_dim, self.hidden)
-        self._h = self._rows = None
 
     @property
     def input_dim(self):
@@ -134,12 +138,6 @@ class DepthMemory(nn.Module):
         return torch.stack(out)
 
     # ---- the library
-    def _check_params(self, dev, what):
-        for name, p in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), self.device_params()):
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise ValueError(f"{what}: parameter {name} must be fp32, contiguous and on {dev} (is {p.dtype}, "
-                                 f"{'contiguous' if p.is_contiguous() else 'strided'}, {p.device})")
-
     def sequence_device(self, x, h0, reset, api=None):
         """`sequence` through lsim_gru_sequence_forward, with autograd to the four parameters (and h0) through lsim_gru_sequence_backward;
         x must not ask for a gradient.  `api`: the library (default) or the CPU shim of the tests, which takes host tensors"""
@@ -153,29 +151,27 @@ class DepthMemory(nn.Module):
         T, n = x.shape[:2]
         if tuple(h0.shape) != (n, self.hidden) or tuple(reset.shape) != (T, n):
             raise ValueError(f"sequence_device: h0 must be [{n}, {self.hidden}] and reset [{T}, {n}], got {tuple(h0.shape)} and {tuple(reset.shape)}")
-        self._check_params(x.device, "sequence_device")
+        check_params("sequence_device", _PARAM_NAMES, self.device_params(), x.device)
         if x.dtype != torch.float32 or h0.dtype != torch.float32 or h0.device != x.device or reset.device != x.device:
             raise ValueError("sequence_device: x and h0 must be fp32, and x, h0 and reset on the parameters' device")
         reset = (reset != 0).to(torch.uint8).contiguous()
         return _GruSequenceFn.apply(api, x.contiguous(), h0.contiguous(), reset, *self.device_params())
 
-    def _live_buffers(self, num_envs, dev):
-        if self._h is None or self._h.shape[0] != num_envs or self._h.device != dev:
-            self._h = torch.zeros(num_envs, self.hidden, dtype=torch.float32, device=dev)
-            self._rows = torch.zeros(num_envs, self.latent_dim + self.hidden, dtype=torch.float32, device=dev)
-        return self._h, self._rows
-
     def step_device(self, sensor, flags=0, stream=None):
         """ONE launch of lsim_depth_memory_step on `stream` (default: the sensor's): z = the sensor's live latent rows, p = the first
-        proprio_dim columns of the env's obs_buf, freshness from the env's episode_length.  Returns the live rows [N, L + H]."""
+        proprio_dim columns of the env's obs_buf, freshness from the env's episode_length, h and the rows [N, L + H] the sensor's own
+        (RaySensor.attach_memory).  Returns the live rows."""
         entry = _entry(sensor._api, "lsim_depth_memory_step")
         if getattr(sensor, "_latent", None) is None:
             raise ValueError("step_device: the sensor has no encoder (attach_encoder), so no latent rows")
         z = sensor.latent()
         if z.shape[1] != self.latent_dim:
             raise ValueError(f"step_device: the memory reads {self.latent_dim} latent columns, the sensor's encoder writes {z.shape[1]}")
-        self._check_params(z.device, "step_device")
-        h, rows = self._live_buffers(z.shape[0], z.device)
+        check_params("step_device", _PARAM_NAMES, self.device_params(), z.device)
+        h, rows = getattr(sensor, "_memory_h", None), getattr(sensor, "_memory_rows", None)
+        if h is None or h.shape[1] != self.hidden or rows.shape[1] != self.latent_dim + self.hidden:
+            raise ValueError(f"step_device: the sensor holds no memory buffers of this cell's widths ({self.latent_dim} latent columns, "
+                             f"{self.hidden} hidden): attach the memory to it (RaySensor.attach_memory)")
         dm = abi.STRUCTS["lsim_depth_memory_t"]()
         dm.z, dm.z_ld = z.data_ptr(), z.stride(0)
         if self.proprio_dim:
@@ -189,15 +185,3 @@ class DepthMemory(nn.Module):
         dm.num_envs, dm.latent_dim, dm.proprio_dim, dm.hidden, dm.flags = z.shape[0], self.latent_dim, self.proprio_dim, self.hidden, int(flags)
         lib.check(entry(ctypes.byref(dm), sensor._stream(stream)), what="lsim_depth_memory_step")
         return rows
-
-    def state(self):
-        """live [N, H]: the hidden state of every env (after the first step_device)"""
-        if self._h is None:
-            raise ValueError("the memory has not been stepped on a sensor (RaySensor.attach_memory)")
-        return self._h
-
-    def rows(self):
-        """live [N, L + H]: row e = [z_e | h_e], what the actor reads"""
-        if self._rows is None:
-            raise ValueError("the memory has not been stepped on a sensor (RaySensor.attach_memory)")
-        return self._rows

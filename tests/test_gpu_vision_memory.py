@@ -14,12 +14,12 @@ N, L, H, T = 64, 10, 32, 12
 ENC = dict(c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=L)
 
 
-def _env(seed):
+def _env(seed, num_envs=N):
     from isaacgymloco_amd.envs import config as C
     from isaacgymloco_amd.envs.legged_robot import LeggedRobot
     from isaacgymloco_amd.learn.evaluate import play_cfg
     cfg = play_cfg(C.aliengo_cfg())
-    cfg.env.num_envs = N
+    cfg.env.num_envs = num_envs
     cfg.env.episode_length_s = 0.3                  # 15 steps: time-outs inside a rollout of 12 steps for the envs started late below
     cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
     env = LeggedRobot(cfg, sim_device=DEV, seed=seed)
@@ -147,13 +147,13 @@ def test_learn_save_load_learn_evaluate_and_export(trained, tmp_path):
     env.add_sensor("depth", sensors.from_spec(env, d["vision"]["sensor"]))
     blind = evaluate(env, path, 5, commands=(0.8, 0.0, 0.0), blind=True).result()
     assert blind["total"]["columns"]["depth_influence"]["mean"] == 0.0
-    # the exported module's remember on the CPU tracks state() over 5 steps
+    # the exported module's remember on the CPU tracks the sensor's memory_state() over 5 steps
     mod = torch.jit.load(run.export(str(tmp_path / "exported")))
     assert mod.hidden == H
     env, prm = run.env, tuple(p.detach().cpu().numpy() for p in mem.device_params())
     g = torch.Generator().manual_seed(1)
     torch.cuda.synchronize()
-    h = mem.state().cpu().clone()
+    h = cam.memory_state().cpu().clone()
     for _ in range(5):
         env.step_device((torch.randn(N, 12, generator=g) * 0.5).to(DEV))
         torch.cuda.synchronize()
@@ -162,9 +162,27 @@ def test_learn_save_load_learn_evaluate_and_export(trained, tmp_path):
         with torch.no_grad():
             got = mod.remember(z, obs, h * (~fresh).unsqueeze(-1))
         want, bound = R.step(z.numpy(), obs[:, :mem.proprio_dim].numpy(), h.numpy(), fresh.numpy(), prm)
-        dev = mem.state().cpu()
+        dev = cam.memory_state().cpu()
         assert (np.abs(got.numpy() - want) <= bound).all() and (np.abs(dev.numpy() - want) <= bound).all()
         h = dev.clone()
+
+
+def test_evaluate_on_a_second_env_leaves_the_training_sensors_rows_alone(trained):
+    """evaluate(env2, runner, sensor=cam2) attaches the runner's encoder and memory to a camera of 48 envs: h and the rows are that sensor's
+    own, so the rows the training policy is bound to keep their storage, shape and bits, and training goes on"""
+    from isaacgymloco_amd.learn.evaluate import evaluate
+    run, cam, mem, _ = trained
+    torch.cuda.synchronize()
+    ptr, bits = cam.memory_rows().data_ptr(), cam.memory_rows().clone()
+    env2 = _env(11, 48)
+    cam2 = env2.add_sensor("depth", _camera(env2))
+    evaluate(env2, run, 5, commands=(0.8, 0.0, 0.0), sensor=cam2)
+    torch.cuda.synchronize()
+    assert cam2._memory is mem and cam._memory is mem
+    assert cam.memory_rows().data_ptr() == ptr and cam.memory_rows().shape == (N, L + H) and torch.equal(cam.memory_rows(), bits)
+    assert cam2.memory_rows().shape == (48, L + H)
+    run.learn(1)
+    assert len(run.last_update) == 6 and all(np.isfinite(float(v)) for v in run.last_update)
 
 
 def test_a_runner_without_memory_launches_no_memory_kernel():

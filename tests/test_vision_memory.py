@@ -34,8 +34,7 @@ def test_constructor_config_and_refusals():
                 dict(latent_dim=4, proprio_dim=0, hidden=24), dict(latent_dim=4, proprio_dim=0, hidden=144), dict(latent_dim=4, proprio_dim=0, hidden=0)):
         with pytest.raises(ValueError):
             DepthMemory(**bad)
-    with pytest.raises(ValueError, match="not been stepped"):
-        mem.rows()
+    assert not hasattr(mem, "rows") and not hasattr(mem, "state")          # per-env buffers are the sensor's: its "no memory" refusal is checked below
     x = torch.zeros(3, 2, 17)
     with pytest.raises(ValueError, match="requires_grad"):
         mem.sequence_device(x.clone().requires_grad_(), torch.zeros(2, 32), torch.zeros(3, 2), api=MB.EmuApi())
@@ -149,16 +148,18 @@ def test_memory_data_slices_and_alignment_of_a_stored_rollout_on_the_emulated_en
         bare.attach_memory(mem)
     with pytest.raises(ValueError, match="no memory"):
         bare.memory_rows()
+    with pytest.raises(ValueError, match="no memory"):
+        bare.memory_state()
     cam = env.add_sensor("depth", sensors.depth_camera(env, 6, 4, 87.0, model=m, **kw))
     cam.attach_encoder(enc)
     assert api.calls["lsim_depth_memory_step"] == 0 and cam._memory is None          # without attach_memory nothing is allocated or launched
     env.step_device(torch.zeros(4, 12))
-    assert api.calls["lsim_depth_memory_step"] == 0 and mem._h is None
+    assert api.calls["lsim_depth_memory_step"] == 0 and cam._memory_h is None and cam._memory_rows is None
     assert cam.attach_memory(mem) is mem and api.calls["lsim_depth_memory_step"] == 1
     prm = tuple(p.detach().numpy() for p in mem.device_params())
     want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), np.zeros((4, H)), np.ones(4, bool), prm)
-    assert (np.abs(mem.state().numpy() - want) <= bound).all(), "attach_memory steps every env from h = 0"
-    assert cam.memory_rows().shape == (4, L + H) and torch.equal(cam.memory_rows()[:, :L], cam.latent()) and torch.equal(cam.memory_rows()[:, L:], mem.state())
+    assert (np.abs(cam.memory_state().numpy() - want) <= bound).all(), "attach_memory steps every env from h = 0"
+    assert cam.memory_rows().shape == (4, L + H) and torch.equal(cam.memory_rows()[:, :L], cam.latent()) and torch.equal(cam.memory_rows()[:, L:], cam.memory_state())
     env.episode_length_buf[1] = int(env.max_episode_length) - 3          # env 1 times out inside the rollout
     alg, *_ = _alg(L, Pm, H, 4, T)
     alg.memory = mem
@@ -187,9 +188,9 @@ def test_memory_data_slices_and_alignment_of_a_stored_rollout_on_the_emulated_en
         if reset[t - 1].any():
             assert (np.abs(got - wrong) > bound)[reset[t - 1].numpy() != 0].any(), "a reset env's h is GRU(x, 0), not GRU(x, h)"
     # a reset by hand reaches the memory with the sensor's flags: only env 2 is stepped, from h = 0
-    before = mem.state().clone()
+    before = cam.memory_state().clone()
     env.reset_idx([2])
-    after = mem.state()
+    after = cam.memory_state()
     assert torch.equal(after[[0, 1, 3]], before[[0, 1, 3]]) and not torch.equal(after[2], before[2])
     want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), before.numpy(), np.array([False, False, True, False]), prm)
     assert (np.abs(after.numpy()[2] - want[2]) <= bound[2]).all()
@@ -197,6 +198,67 @@ def test_memory_data_slices_and_alignment_of_a_stored_rollout_on_the_emulated_en
         DepthMemory(L, Pm, H).double().step_device(cam)
     with pytest.raises(ValueError, match="latent columns"):
         DepthMemory(L + 1, Pm, H).step_device(cam)
+
+
+@pytest.mark.parametrize("n2", [6, 4])
+def test_one_memory_on_two_sensors_keeps_one_hidden_state_per_sensor(n2):
+    """one DepthEncoder and one DepthMemory attached to the cameras of two emulated envs (4 and `n2` envs), as evaluate() does with a runner's
+    modules on a second env: h and the rows are each sensor's own, so the first sensor's rows keep their storage, shape and bits while the
+    second env steps, and each sensor's h follows the reference from its own latent, observation columns and reset_buf"""
+    import copy
+    import eval_emu_binding
+    from helpers import C
+    from isaacgymloco_amd.envs import sensors
+    L, Pm, H = 6, 9, 16
+    torch.manual_seed(2)
+    enc = DepthEncoder(4, 6, 2, c1=3, k1=2, s1=1, c2=5, k2=2, s2=1, latent_dim=L)
+    mem = DepthMemory(L, Pm, H)
+    prm = tuple(p.detach().numpy() for p in mem.device_params())
+    m = sensors.SensorModel(period=2, stagger=True, latency=1, frames=2, clip=(0.1, 3.0), normalise=True)
+
+    def rig(n):
+        cfg = C.mixed_cfg("aliengo", {"aliengo": 0.5, "go2": 0.5})[0]
+        cfg.env.num_envs = n
+        cfg.terrain.num_rows, cfg.terrain.num_cols = 2, 2
+        cfg.terrain.terrain_proportions = [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+        env = eval_emu_binding.emu_mixed_env(cfg)
+        env.reset()
+        cam = env.add_sensor("depth", sensors.depth_camera(env, 6, 4, 87.0, model=m, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, api=MB.EmuApi(),
+                                                           see_robot=True))
+        cam.attach_encoder(enc)
+        env.step_device(torch.zeros(n, 12))
+        return env, cam
+
+    def attach_and_step(env, cam, seed, steps=3):
+        """attach `mem`, step with the env's own random actions; every h is one reference step from the sensor's h before it"""
+        n = env.num_envs
+        assert cam.attach_memory(mem) is mem
+        want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), np.zeros((n, H)), np.ones(n, bool), prm)
+        assert (np.abs(cam.memory_state().numpy() - want) <= bound).all()
+        g = torch.Generator().manual_seed(seed)
+        for t in range(steps):
+            before = cam.memory_state().numpy().copy()
+            env.step_device(torch.randn(n, 12, generator=g) * 0.3)
+            want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), before, env.reset_buf.numpy() != 0, prm)
+            assert (np.abs(cam.memory_state().numpy() - want) <= bound).all(), (n, t)
+            assert torch.equal(cam.memory_rows()[:, :L], cam.latent()) and torch.equal(cam.memory_rows()[:, L:], cam.memory_state())
+
+    (env1, cam1), (env2, cam2) = rig(4), rig(n2)
+    with pytest.raises(ValueError, match="no memory buffers"):
+        mem.step_device(cam1)                                   # nothing to step on before attach_memory
+    attach_and_step(env1, cam1, seed=4)
+    with pytest.raises(ValueError, match="no memory buffers"):
+        DepthMemory(L, Pm, 2 * H).step_device(cam1)             # a cell of another width than the sensor's buffers
+    ptr, bits = cam1.memory_rows().data_ptr(), cam1.memory_rows().clone()
+    attach_and_step(env2, cam2, seed=7)
+    assert cam1.memory_rows().data_ptr() == ptr and cam1.memory_rows().shape == (4, L + H) and torch.equal(cam1.memory_rows(), bits)
+    assert cam2.memory_rows().shape == (n2, L + H) and cam2.memory_state().shape == (n2, H)
+    assert cam2.memory_rows().data_ptr() != ptr and cam2.memory_state().data_ptr() != cam1.memory_state().data_ptr()
+    # the module is weights only: nothing of [N, .] in its checkpoint or in a copy of it
+    assert set(mem.state_dict()) == {"cell.weight_ih", "cell.weight_hh", "cell.bias_ih", "cell.bias_hh"}
+    twin = copy.deepcopy(mem)
+    assert not [k for k, v in vars(twin).items() if torch.is_tensor(v)] and not list(twin.buffers())
+    assert {tuple(p.shape) for p in twin.parameters()} == {(3 * H, L + Pm), (3 * H, H), (3 * H,)}
 
 
 def test_warm_started_twin_is_the_memoryless_vision_policy():

@@ -76,7 +76,7 @@ def step_time(n, samples):
         L.lsim_set_profiling(env._h, 0)
         return 1000.0 * sorted(ms_a[:cnt.value])[cnt.value // 2]
     a_before = kernel_a()                               # without the memory attached
-    mem.step_device(cam, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+    cam.attach_memory(mem)                              # h and the rows are the sensor's; steps every env once from h = 0
     t = alternate({"step": lambda: mem.step_device(cam), "encode_staggered": lambda: cam._encoder.encode_device(cam, 1)}, samples, iters)
     a_after = kernel_a()
     return {"num_envs": n, "cell": {"latent_dim": 64, "proprio_dim": env.num_one_step_obs, "hidden": 64}, "lds_bytes": list(mem.lds_bytes(L)),

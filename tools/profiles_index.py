@@ -69,6 +69,16 @@ RULES = [   # (regex on the name without its round prefix, what it is, section)
 ]
 STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs, mode, actions, solver) before quoting `roofline.traffic` / `valu_issue_frac`; rewritten by every round's script", "6, 8"),
               "ref_cpu_partial.json": ("the reference's own torch post-physics stack and learner timed in the build container (no physics): SURVEY 8d legs B / C", "8"),
+              "depth_chain_refactor_ab.json": ("parent commit against the commit that moved the memory's per-env buffers to the sensor, alternating runs in one session: `tools/depth_memory_time.py` and `tools/vision_train_time.py --memory` medians with the parent's run-to-run spread", "7.12"),
+              "depth_encoder_time.json": ('`tools/depth_encoder_time.py`, N = 4096, 64 × 48 camera, 2 frames, the default network: `lsim_depth_encode` with every env due and at period 5 staggered, the torch forward on the same device, `lsim_sensor_capture` and kernel A in one process', "7.8"),
+              "depth_memory_time.json": ('`tools/depth_memory_time.py`, N = 4096, L = 64, P = 45, H = 64: `lsim_depth_memory_step` next to kernel A and the staggered encoder launch; `sequence_device` forward + backward, the two serial kernels alone and the `nn.GRUCell` loop at T = 99, n = 1024 / 4096, alternating samples in one process', "7.12"),
+              "eval_time.json": ('`tools/eval_time.py`, N = 4096, 400 groups: `lsim_eval_accumulate` next to the env step, kernel A and the torch statements it replaces, HIP events', "7.5"),
+              "policy_ext_time.json": ('`tools/policy_time.py --ext`, N = 4096, L = 64: `lsim_policy_forward_ext` / `lsim_policy_act_post_at_ext` against the plain launches in one process, alternating', "7.10"),
+              "raycast_bodies_time.json": ("`tools/raycast_time.py --bodies`, N = 4096: `lsim_raycast`, `lsim_raycast_bodies` (all bodies seen) and kernel A in one process, with the counters build's primitives tested and cells walked per ray", "7.6"),
+              "raycast_time.json": ('`tools/raycast_time.py`, N = 4096: `lsim_raycast` for the 64 × 48 camera and the 16 × 360 lidar next to kernel A, rays per second', "7.6"),
+              "sensor_model_time.json": ('`tools/raycast_time.py --model`, N = 4096: `lsim_sensor_capture` (full launch and period 5 staggered) next to the plain ray casts and kernel A', "7.7"),
+              "vision_train_time.json": ('`tools/vision_train_time.py`, N = 4096, 64 × 48 × 2 camera at period 5: collection / update per iteration of `VisionOnPolicyRunner` next to `HIMOnPolicyRunner`, the encoder step separately', "7.10"),
+              "vision_train_time_memory.json": ('`tools/vision_train_time.py --memory`, N = 4096, 64 × 48 × 2 camera at period 5: collection / update per iteration of the HIM runner, the vision runner and the vision runner with a depth memory (encoder step and memory step separately)', "7.12"),
               "INDEX.md": ("this file", "")}
 
 
