@@ -45,7 +45,8 @@ extern "C" {
                                     lsim_depth_encode + lsim_depth_encode_sizes (a small CNN over a sensor's frame history, forward only);
                                     lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters);
                                     lsim_eval_columns + lsim_eval_columns_sizes / _clear / _accumulate (caller-supplied columns into the evaluator's groups);
-                                    lsim_depth_memory_step + lsim_depth_memory_sizes, lsim_gru_sequence_forward / _backward (a GRU cell over the depth latent) */
+                                    lsim_depth_memory_step + lsim_depth_memory_sizes, lsim_gru_sequence_forward / _backward (a GRU cell over the depth latent);
+                                    lsim_sensor_mount_jitter + LSIM_RNG_SENSOR_MOUNT (a sensor's mount pose redrawn per episode, on the device) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -162,8 +163,10 @@ enum lsim_rng_tag {
     LSIM_RNG_INIT_BUCKET = 13, /* LR:511            env word = bucket index, idx 0         */
     LSIM_RNG_POLICY = 14,      /* HIMP:94 (actor_critic.act sample), lsim_rollout_act: step word = draw counter,
                                   block p gives the two Box-Muller pairs of actions 2p, 2p+1       */
-    LSIM_RNG_SENSOR = 15       /* lsim_sensor_capture (no reference site): step word = (uint32) tick, the fourth counter word =
+    LSIM_RNG_SENSOR = 15,      /* lsim_sensor_capture (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | ray -- one whole block per ray, all four words used      */
+    LSIM_RNG_SENSOR_MOUNT = 16 /* lsim_sensor_mount_jitter (no reference site): step word = (uint32) tick, the fourth counter word =
+                                  (stream_id << 16) | b, b = 0, 1 -- block 0: position x y z and rotation x, block 1: rotation y z, two words unused */
 };
 
 /* ---- robot model: the URDF after Isaac Gym's fixed-joint collapse ----
@@ -1179,6 +1182,45 @@ typedef struct lsim_sensor_model {
  * not a multiple of 4; sigma0, sigma2 not finite or < 0; p_drop outside [0, 1]; drop_value, clip_lo, clip_hi, offset or gain not finite;
  * clip_lo > clip_hi; a flag bit other than the two above; both of them set. */
 int lsim_sensor_capture(const lsim_sensor_model_t* sm, void* stream);
+
+/* ---- sensor mount jitter: where the instrument sits, redrawn for every env that starts an episode.  ONE launch, the rules of
+ * lsim_sensor_capture (caller's stream, no host synchronisation, raw pointers only).  It reads `nominal` and episode_length and writes rows of
+ * `mount` -- the array a sensor's lsim_raycast_t.mount points at, so a capture enqueued BEHIND it on the same stream renders a reset env, whole
+ * history included, from its new pose.  No capture kernel changes: they read the mount through the pointer they already have.
+ *
+ * Which envs.  Env e is visited when e % env_stride == 0.  A visited env is FRESH when
+ *     (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0                  (lsim_sensor_capture's `fill`; the tick plays no part in it)
+ *   LSIM_SENSOR_RESETS_ONLY is accepted and changes nothing here.  For an env that is not visited or not fresh NOTHING is written.
+ * Draws.  Two Philox4x32-10 blocks, key (seed, rank), counters (e, (uint32_t)tick, LSIM_RNG_SENSOR_MOUNT, (stream_id << 16) | b), b = 0, 1:
+ *     x0..x3 = block 0, x4..x7 = block 1;   u_k = (x_k >> 8) * 2^-24,   s_k = 2 u_k - 1   for k = 0..5 (exact in fp32); x6, x7 are not used.
+ *   The draw depends on (e, tick, stream_id) and the key only: a second launch on the same tick writes the same bits (reset_idx() by hand, then
+ *   the step that shares its tick).
+ * Per fresh env, all arithmetic in fp32 (a compiler may contract a product and a sum into one fused operation), n = nominal[e], m = mount[e]:
+ *     m[k] = n[k] + s_k * pos_range[k],  k = 0..2                              (metres along the base x, y, z)
+ *     a_k = s_{3+k} * rot_range[k];   h_k = 0.5 * a_k;   c = 1 / sqrt(1 + (h_0^2 + h_1^2 + h_2^2))     (square root and division correctly rounded)
+ *     d = (h_0 c, h_1 c, h_2 c, c)  xyzw: the Cayley map of a -- no transcendental function, so the same on every host.  Its rotation angle is
+ *         2 atan(|a| / 2): |a| to third order, 0.25 % short at 10 degrees, and never more than 2 atan(|rot_range| / 2);
+ *     m[3..6] = d (x) n[3..6],  the Hamilton product, R(m) = R(d) R(n):
+ *         m3 = d.w n.x + n.w d.x + (d.y n.z - d.z n.y),   m4 = d.w n.y + n.w d.y + (d.z n.x - d.x n.z),
+ *         m5 = d.w n.z + n.w d.z + (d.x n.y - d.y n.x),   m6 = d.w n.w - (d.x n.x + d.y n.y + d.z n.z)
+ *   The error turns about the BASE axes (rot_range[1] is the pitch error of a forward camera) and is not renormalised: |m_quat| = |n_quat| up
+ *   to rounding.  All-zero ranges give d = (0, 0, 0, 1) and m = n exactly (a component -0 may come out as +0).
+ * tick is passed by value as lsim_sensor_capture's is, and replays from a captured graph in the same way. */
+typedef struct lsim_sensor_mount_jitter {
+    const float* nominal;             /* [N, 7] position + quaternion xyzw, as lsim_raycast_t.mount; read only, 4-byte aligned */
+    float* mount;                     /* [N, 7] what the sensor's lsim_raycast_t.mount points at; 4-byte aligned; must not be `nominal` */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    int64_t tick;                     /* >= 0, by value: the tick of the capture that follows */
+    uint32_t seed, rank, stream_id;   /* as lsim_sensor_model_t's; stream_id < 65536 */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    float pos_range[3];               /* metres, half-widths along the base x, y, z: finite, >= 0 */
+    float rot_range[3];               /* radians, half-widths about the base x, y, z: finite, >= 0 */
+} lsim_sensor_mount_jitter_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: mj == NULL; nominal or mount NULL or not
+ * 4-byte aligned; episode_length NULL or not 8-byte aligned; mount == nominal; num_envs < 1; env_stride < 1; tick < 0; stream_id >= 65536; a
+ * pos_range or rot_range entry that is negative or not finite; a flag bit other than the sensor model's two; both of them set. */
+int lsim_sensor_mount_jitter(const lsim_sensor_mount_jitter_t* mj, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

@@ -30,6 +30,13 @@ late, refilled inside the launch when the env resets:
 Encoder (`cam.attach_encoder(learn.depth_encoder.DepthEncoder(48, 64, frames=2).to(device))`, lsim_depth_encode): every capture is followed,
 on the same stream and with the same tick and flags, by one more launch that turns the frames of the envs just captured into a latent row;
 `cam.latent()` is the live [N, latent_dim] tensor.  Without an attached encoder nothing of this is created or launched.
+
+Mount jitter (`mount_jitter=MountJitter(pos=0.01, rot_deg=(1, 5, 1))`, lsim_sensor_mount_jitter; needs a model): a real camera is mounted with
+millimetres and degrees of error, so every env draws its own mount pose when it starts an episode -- uniform offsets of up to `pos` metres
+along and up to `rot_deg` degrees about the base x, y, z, around the nominal mount.  One small launch ahead of every capture rewrites the
+rows of `cam.mount` of the envs just reset, on the device (nobody on the host learns who reset), so a reset env's frame history is
+refilled from its new pose within the same step; `cam.mount_nominal` keeps the nominal poses.  spec() records the jitter and from_spec()
+rebuilds it.  Without `mount_jitter` nothing of this is created or launched.
 """
 import ctypes
 import math
@@ -98,6 +105,35 @@ class SensorModel:
         return (lo, hi), (lo + hi) / 2.0, 1.0 / (hi - lo)
 
 
+class MountJitter:
+    """Per-episode error of a sensor's mount pose (lsim_sensor_mount_jitter; include/lsim.h states every formula): when an env starts an
+    episode its mount is the nominal one moved by uniform offsets in [-pos[k], pos[k]] metres along the base x, y, z and turned by about
+    [-rot_deg[k], rot_deg[k]] degrees about the base x, y, z (rot_deg[1] is the pitch error of a forward camera).  A scalar is the same
+    half-width on all three axes."""
+
+    def __init__(self, pos=(0.0, 0.0, 0.0), rot_deg=(0.0, 0.0, 0.0)):
+        self.pos, self.rot_deg = self._three(pos, "pos"), self._three(rot_deg, "rot_deg")
+
+    @staticmethod
+    def _three(v, name):
+        v = (float(v),) * 3 if np.isscalar(v) else tuple(float(x) for x in v)
+        if len(v) != 3 or any(not math.isfinite(x) or x < 0.0 for x in v):
+            raise ValueError(f"MountJitter: {name} takes one or three finite half-widths >= 0, got {v}")
+        return v
+
+    def record(self):
+        """the plain dict spec() stores and MountJitter(**record) reads"""
+        return {"pos": list(self.pos), "rot_deg": list(self.rot_deg)}
+
+    def __eq__(self, other):
+        return isinstance(other, MountJitter) and (self.pos, self.rot_deg) == (other.pos, other.rot_deg)
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"MountJitter(pos={self.pos}, rot_deg={self.rot_deg})"
+
+
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
@@ -109,10 +145,13 @@ class RaySensor:
     [N, frames, R] history, `out` the clean value of each env's latest capture, `refresh()` fills every env's history from the present state,
     `tick` the tick of the last launch and `stream_id` (set by env.add_sensor) what separates the noise of the sensors of one env;
     `attach_encoder(enc)` adds the encoder's launch behind every capture and `latent()` is its live [N, latent_dim] output.
-    With `model=None` nothing of this is allocated and the launch is the one above."""
+    With `model=None` nothing of this is allocated and the launch is the one above.
+    `mount_jitter` (a MountJitter; needs a model): `mount_nominal` keeps the [N, 7] poses given here, `mount` becomes a buffer of its own
+    that lsim_sensor_mount_jitter rewrites, ahead of every capture and with its stream, tick and flags, for the envs that start an episode.
+    With `mount_jitter=None` `mount` is `mount_nominal` and no such launch is made."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
         self.env = env
         self.model = model
         self._api = api if api is not None else env._L
@@ -134,7 +173,8 @@ class RaySensor:
         R = self.num_rays = int(self.dirs.shape[0])
         self.near, self.far, self.env_stride = float(near), float(far), int(env_stride)
         self.scale = None if scale is None else torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float32).reshape(R), device=dev).contiguous()
-        self.mount = torch.cat((self._per_env(mount_pos, 3, dev), self._per_env(mount_quat, 4, dev)), dim=1).contiguous()
+        self.mount = self.mount_nominal = torch.cat((self._per_env(mount_pos, 3, dev), self._per_env(mount_quat, 4, dev)), dim=1).contiguous()
+        self.mount_jitter = self._mj = None
         stride = (R + 3) // 4 * 4
         self._out = torch.full((N, stride), self.far, dtype=torch.float32, device=dev)
         if self.scale is not None:
@@ -167,6 +207,40 @@ class RaySensor:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
             self._setup_model(model, dev)
+        if mount_jitter is not None:
+            self.set_mount_jitter(mount_jitter)
+
+    def set_mount_jitter(self, jitter):
+        """`jitter` (a MountJitter) from now on, or None: back to the nominal mount and no launch.  The new poses are drawn by the next
+        refresh() (every env) or, env by env, as episodes start"""
+        if jitter is None:
+            self.mount_jitter = self._mj = None
+            self._point_mount(self.mount_nominal)
+            return
+        if not isinstance(jitter, MountJitter):
+            raise TypeError(f"mount_jitter: expected a MountJitter or None, got {type(jitter).__name__}")
+        if self.model is None:
+            raise ValueError("mount_jitter needs a model (SensorModel): the tick and the episode lengths that say who starts an episode are the model's")
+        if not hasattr(self._api, "lsim_sensor_mount_jitter"):
+            raise lib.LsimError("the loaded library has no lsim_sensor_mount_jitter: rebuild it (there is no torch fall-back for the mount jitter)")
+        if self.mount is self.mount_nominal:
+            self._point_mount(self.mount_nominal.clone())
+        mj = abi.LsimSensorMountJitter()
+        mj.nominal, mj.mount, mj.episode_length = self.mount_nominal.data_ptr(), self.mount.data_ptr(), self._sm.episode_length
+        mj.seed, mj.rank, mj.stream_id = self._sm.seed, self._sm.rank, self._sm.stream_id
+        mj.num_envs, mj.env_stride = int(self.env.num_envs), self.env_stride
+        for k in range(3):
+            mj.pos_range[k], mj.rot_range[k] = jitter.pos[k], math.radians(jitter.rot_deg[k])
+        self.mount_jitter, self._mj = jitter, mj
+
+    def _point_mount(self, mount):
+        """`mount` is what every launch of this sensor reads from now on (the structs hold copies of one another)"""
+        self.mount = mount
+        self._rc.mount = mount.data_ptr()
+        if self._bodies:
+            self._rb.rc.mount = mount.data_ptr()
+        if self.model is not None:
+            self._sm.rb.rc.mount = mount.data_ptr()
 
     def _setup_model(self, model, dev):
         """the lsim_sensor_model struct around the sensor's lsim_raycast_bodies (or, terrain only, around its lsim_raycast) and the history"""
@@ -197,6 +271,8 @@ class RaySensor:
     def stream_id(self, value):
         if self.model is not None:
             self._sm.stream_id = int(value)
+            if self._mj is not None:
+                self._mj.stream_id = int(value)
 
     def _setup_bodies(self, rc, ignore_bodies, labels, dev):
         """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
@@ -275,6 +351,9 @@ class RaySensor:
         if self.model is not None:
             self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
             self._sm.tick, self._sm.flags = self.tick, int(flags)
+            if self._mj is not None:            # first: the envs that start an episode are rendered, history and all, from their new pose
+                self._mj.tick, self._mj.flags = self.tick, int(flags)
+                lib.check(self._api.lsim_sensor_mount_jitter(ctypes.byref(self._mj), self._stream(stream)), what="lsim_sensor_mount_jitter")
             lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
             if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
                 self._encoder.encode_device(self, self.tick, int(flags), stream)
@@ -359,7 +438,9 @@ class RaySensor:
         """What rebuilds this sensor on another env (from_spec), as a dict of plain Python values and lists -- a checkpoint's record of the
         instrument a policy was trained with: kind ("camera" with width / height, "lidar" with channels / points_per_rev, else "rays"),
         dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
-        without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None."""
+        without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
+        With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
+        one there is no such key."""
         out = {"kind": "rays"}
         if hasattr(self, "width") and hasattr(self, "height"):
             out.update(kind="camera", width=int(self.width), height=int(self.height))
@@ -374,7 +455,7 @@ class RaySensor:
         out["model"] = None if m is None else {"period": m.period, "stagger": m.stagger, "latency": m.latency, "frames": m.frames, "noise": list(m.noise),
                                                "dropout": m.dropout, "drop_value": m.drop_value, "clip": None if m.clip is None else list(m.clip),
                                                "normalise": m.normalise}
-        mount = self.mount.cpu()
+        mount = self.mount_nominal.cpu()
         pose = lambda row: {"pos": row[:3].tolist(), "quat": row[3:].tolist()}
         names, ids = getattr(self.env, "robot_names", None), getattr(self.env, "robot_ids", None)
         rows = [] if names is None or ids is None else [mount[ids.cpu() == k] for k in range(len(names))]
@@ -384,6 +465,8 @@ class RaySensor:
             out["mount"] = {n: pose(r[0]) for n, r in zip(names, rows) if len(r)}
         else:
             out["mount"] = None
+        if self.mount_jitter is not None:
+            out["mount_jitter"] = self.mount_jitter.record()
         return out
 
     @property
@@ -412,26 +495,27 @@ class DepthCamera(RaySensor):
 
 
 def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
-    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last five keywords as RaySensor's"""
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last six keywords as RaySensor's"""
     return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api,
-                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model)
+                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter)
 
 
 def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
-          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None):
+          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
     """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
-    `points_per_rev` azimuths each; reports range (scale=None); the last five keywords as RaySensor's"""
+    `points_per_rev` azimuths each; reports range (scale=None); the last six keywords as RaySensor's"""
     s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
-                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model)
+                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter)
     s.channels, s.points_per_rev = int(channels), int(points_per_rev)
     return s
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
-    per-robot mount that lacks one of the env's robots (RaySensor's own check)."""
+    per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
+    (none when the record has none); None or a MountJitter takes its place."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -445,6 +529,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None):
         raise ValueError("from_spec: the recorded sensor's mount differed from env to env (spec['mount'] is None): pass mount_pos and mount_quat")
     m = spec.get("model")
     model = None if m is None else SensorModel(**m)
+    if isinstance(mount_jitter, str):
+        if mount_jitter != "spec":
+            raise ValueError(f"from_spec: mount_jitter is 'spec', None or a MountJitter, got {mount_jitter!r}")
+        j = spec.get("mount_jitter")
+        mount_jitter = None if j is None else MountJitter(**j)
     kind = spec.get("kind", "rays")
     cls = DepthCamera if kind == "camera" else RaySensor
     sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
@@ -452,7 +541,8 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None):
         sensor.width, sensor.height = int(spec["width"]), int(spec["height"])
     RaySensor.__init__(sensor, env, np.asarray(spec["dirs"], dtype=np.float32), pos, quat, spec["near"], spec["far"],
                        scale=None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32), env_stride=spec["env_stride"], api=api,
-                       see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"], frame=spec["frame"], model=model)
+                       see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"], frame=spec["frame"], model=model,
+                       mount_jitter=mount_jitter)
     if kind == "lidar":
         sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
     return sensor

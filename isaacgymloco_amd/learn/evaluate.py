@@ -187,6 +187,7 @@ class Evaluator:
             e.trace_envs[k] = i
         self._e = e
         self.column_names, self.columns, self.col_table, self._c = (), None, None, None
+        self.extra_conventions = {}       # what evaluate() adds to result()["conventions"] (a vision policy's camera_jitter)
         self.clear()
 
     def add_columns(self, names):
@@ -252,6 +253,7 @@ class Evaluator:
                 grp["columns"] = columns_of_row(ctable[key_index(self.mask, self.shape, grp["key"], self.robot_names)], self.column_names)
             total["columns"] = columns_of_row(ctable.sum(axis=0), self.column_names)
             conv["columns"] = list(self.column_names)
+        conv.update(self.extra_conventions)
         return {"group_by": [g for g in ("robot", "type", "level") if self.mask & GROUP_BITS[g]], "num_envs": int(env.num_envs), "steps": self.steps,
                 "dt": float(env.dt), "groups": groups, "total": total,
                 "nonfinite": {"addends": int(table[:, W["nonfinite"]].sum()), "simulator_env_steps": int(env.nonfinite_envs.item())},
@@ -367,6 +369,53 @@ def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
     return cam, enc, head
 
 
+def _camera_jitter(cam, found, camera_jitter):
+    """evaluate()'s `camera_jitter` applied to the camera: "trained" -- what the checkpoint's vision["sensor"] record says (a runner or a
+    module brings no record: the camera it is given carries what it was trained with, and stays as it is); None -- the nominal mount; a
+    MountJitter -- that one.  A camera whose jitter changes has every env's mount redrawn and history refilled once (refresh()).
+    Returns the entry of the result's conventions."""
+    from ..envs.sensors import MountJitter
+    current = getattr(cam, "mount_jitter", None)
+    if isinstance(camera_jitter, str):
+        if camera_jitter != "trained":
+            raise ValueError(f"evaluate: camera_jitter is 'trained', None or a MountJitter, got {camera_jitter!r}")
+        d = found.get("checkpoint")
+        record = ((d.get("vision") or {}).get("sensor")) if d is not None else None
+        want = current if record is None else (MountJitter(**record["mount_jitter"]) if record.get("mount_jitter") else None)
+        choice = "trained"
+    elif camera_jitter is None:
+        want, choice = None, "off"
+    elif isinstance(camera_jitter, MountJitter):
+        want, choice = camera_jitter, "override"
+    else:
+        raise TypeError(f"evaluate: camera_jitter is 'trained', None or a MountJitter, got {type(camera_jitter).__name__}")
+    if want != current:
+        cam.set_mount_jitter(want)
+        if cam.tick >= 0:
+            cam.refresh()
+    return {"choice": choice, "pos": None if want is None else list(want.pos), "rot_deg": None if want is None else list(want.rot_deg)}
+
+
+def parse_camera_jitter(text):
+    """the command line's --camera-jitter: "trained", "off" (None), or "pos=P,rot_deg=R" with P and R one number or three joined by "/"
+    (either key may be left out: 0)"""
+    from ..envs.sensors import MountJitter
+    if text == "trained":
+        return "trained"
+    if text == "off":
+        return None
+    kw = {}
+    for item in text.split(","):
+        k, sep, v = item.partition("=")
+        if not sep or k not in ("pos", "rot_deg") or k in kw:
+            raise ValueError(f"expected trained, off or pos=..,rot_deg=.., got {text!r}")
+        vals = [float(x) for x in v.split("/")]
+        if len(vals) not in (1, 3):
+            raise ValueError(f"{k}: one number or three joined by '/', got {v!r}")
+        kw[k] = vals[0] if len(vals) == 1 else vals
+    return MountJitter(**kw)
+
+
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 
 
@@ -435,7 +484,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
 
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
-             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS):
+             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained"):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -445,7 +494,11 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     mean from the mean with a zero latent (one more policy forward per step), "scan_error" = the mean square error of `depth_head` (the
     encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped.
     A policy trained with a depth memory (the runner's alg.memory, or the checkpoint's vision["memory"] record) gets the memory rebuilt and
-    attached behind the encoder and reads cam.memory_rows(), [z | h]; "memory_scan_error" is the memory head's error on h."""
+    attached behind the encoder and reads cam.memory_rows(), [z | h]; "memory_scan_error" is the memory head's error on h.
+    `camera_jitter` (a vision policy only): the per-episode mount error of the camera (envs.sensors.MountJitter) -- "trained": what the
+    checkpoint's record of the sensor says (a runner's camera stays as it is); None: the nominal mount; a MountJitter: that one, to
+    measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's
+    conventions["camera_jitter"]."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
@@ -454,6 +507,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     is_vision = hasattr(ac, "depth_latent_dim")
     if is_vision:
         cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
+        jitter_entry = _camera_jitter(cam, found, camera_jitter)       # after the encoder and the memory are attached: a refresh() runs them too
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -462,6 +516,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
     if is_vision:
+        ev.extra_conventions["camera_jitter"] = jitter_entry
         return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
                                 memory=found.get("memory"), memory_head=found.get("memory_head"))
     use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
@@ -515,9 +570,15 @@ def parse_args(argv=None):
     ap.add_argument("--trace-out", default=None)
     ap.add_argument("--blind", action="store_true", help="a vision policy acts on a zero latent instead of its camera's")
     ap.add_argument("--vision-metrics", default="depth_influence,scan_error", help="columns a vision policy adds to the result; empty: none")
+    ap.add_argument("--camera-jitter", default="trained", help="a vision policy's per-episode camera mount error: 'trained' (the checkpoint's record), "
+                    "'off' (the nominal mount) or pos=METRES,rot_deg=DEGREES (one number, or x/y/z)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    try:
+        a.camera_jitter = parse_camera_jitter(a.camera_jitter)
+    except ValueError as exc:
+        ap.error(f"--camera-jitter: {exc}")
     if a.envs < 1 or a.steps < 1:
         ap.error("--envs and --steps must be positive")
     if a.commands == "env":
@@ -566,7 +627,7 @@ def main(argv=None):
         from ..envs.sensors import from_spec
         env.add_sensor("depth", from_spec(env, record["sensor"]))
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
-                  vision_metrics=a.vision_metrics)
+                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

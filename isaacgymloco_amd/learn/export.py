@@ -6,6 +6,8 @@ The exported TorchScript module maps an observation history [B, 270] to action m
 A vision policy (learn/vision.py) exports as PolicyExporterVision: the same two networks with the wider first actor layer, plain copies of
 the depth encoder's three layers and the sensor model's clip / normalisation constants, so that the robot's program needs nothing but the file:
     preprocess(depth in metres) -> frames;  encode(frames) -> latent, at camera rate;  act(obs_history, latent) -> action means, at control rate.
+The exported module takes frames and knows no mount: a sensor's per-episode mount jitter (envs/sensors.py MountJitter, a record's
+"mount_jitter") is a property of the simulated instrument that trained the policy, and leaves the exported file what it was.
 The build's networks are `HimMLP` / `SkinnyLinear` modules (nn.Sequential / nn.Linear subclasses whose forward dispatches to the HIP
 weight-gradient kernels under autograd), which TorchScript cannot script; the exporter therefore re-materialises the two networks as plain
 `nn.Sequential(nn.Linear, nn.ELU, ...)` with the SAME weights -- exactly the module tree the reference scripts, so a file written here loads

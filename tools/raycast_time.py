@@ -15,6 +15,12 @@ primitives that passed the bounding test per ray and the cells walked per ray (t
 lsim_sensor_capture with that sensors.SensorModel, the tick advancing by one per launch so that a staggered period is averaged over whole
 periods (`<sensor>_model_us`), and with SensorModel() -- period 1, everything else off: what the epilogue and the history traffic add to
 lsim_raycast_bodies (`<sensor>_model_period1_us`); both with their ratio to `<sensor>_bodies_us` of the same process.
+`--mount-jitter POS,ROT_DEG` (metres, degrees; needs --model; a measurement of its own: the camera only, no lidar, no counters): per terrain,
+in one process, `jitter_all_fresh_us` / `jitter_none_fresh_us` = lsim_sensor_mount_jitter alone with LSIM_SENSOR_FILL_ALL and with no env at
+episode_length 0; `camera_model_us` = lsim_sensor_capture exactly as --model times it, on the nominal mount, and `camera_model_jittered_us` =
+the same launch on a sensor whose mounts were drawn once for every env (the jitter launch itself kept out of the timed loop), the two
+alternating `--repeats` times, each with its median and its range over the repeats (the run-to-run spread of this process);
+`camera_model_update_with_jitter_us` = update() as a jittered sensor runs it in a step: the jitter launch (nobody fresh) and the capture.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -27,7 +33,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from isaacgymloco_amd import lib  # noqa: E402
+from isaacgymloco_amd import abi, lib  # noqa: E402
 from isaacgymloco_amd.csrc import build as hip_build  # noqa: E402
 from isaacgymloco_amd.envs import config as C, sensors  # noqa: E402
 from isaacgymloco_amd.envs.legged_robot import LeggedRobot  # noqa: E402
@@ -94,6 +100,47 @@ def timed_ticks(sensor, iters, warmup):
         sensor.update(tick=tick[0])
         tick[0] += 1
     return timed(fn, iters, warmup)
+
+
+def measure_mount_jitter(n, terrain, iters, warmup, model, jitter, repeats):
+    """the --mount-jitter measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    torch.cuda.synchronize()
+    make = lambda **kw: sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True,
+                                             model=model, **kw)
+    nominal, jittered = make(), make(mount_jitter=jitter)
+    nominal.refresh(tick=0)
+    jittered.refresh(tick=0)                    # draws every env's mount once
+    out = {"num_envs": n, "terrain": terrain, "resetting_envs": int((env.episode_length_buf == 0).sum().item()),
+           "mount_offset_max_m": float((jittered.mount[:, :3] - jittered.mount_nominal[:, :3]).abs().max().item())}
+    mj, L = jittered._mj, env._L
+
+    def launch(flags):
+        mj.tick, mj.flags = 0, flags
+        lib.check(L.lsim_sensor_mount_jitter(ctypes.byref(mj), env._stream()), what="lsim_sensor_mount_jitter")
+    fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+    whole = max(model.period, iters // model.period * model.period)
+    rows = {"jitter_all_fresh_us": [], "jitter_none_fresh_us": [], "camera_model_us": [], "camera_model_jittered_us": [], "camera_model_update_with_jitter_us": []}
+    for _ in range(repeats):
+        rows["jitter_all_fresh_us"].append(timed(lambda: launch(fill_all), iters, warmup))
+        rows["jitter_none_fresh_us"].append(timed(lambda: launch(0), iters, warmup))
+        rows["camera_model_us"].append(timed_ticks(nominal, whole, warmup))
+        jittered._mj = None                     # the capture alone, reading the mounts drawn above
+        rows["camera_model_jittered_us"].append(timed_ticks(jittered, whole, warmup))
+        jittered._mj = mj
+        rows["camera_model_update_with_jitter_us"].append(timed_ticks(jittered, whole, warmup))
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    out["jittered_over_nominal"] = out["camera_model_jittered_us"] / out["camera_model_us"]
+    out["nonfinite_rays"] = int(nominal.nonfinite_rays.item()) + int(jittered.nonfinite_rays.item())
+    return out
 
 
 def measure(n, terrain, iters, warmup, count_lib, bodies=False, model=None):
@@ -168,9 +215,25 @@ def main():
     ap.add_argument("--no-counters", action="store_true")
     ap.add_argument("--bodies", action="store_true", help="also time lsim_raycast_bodies (see_robot=True) on every workload")
     ap.add_argument("--model", default=None, help="also time lsim_sensor_capture with this sensor model, e.g. period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02")
+    ap.add_argument("--mount-jitter", default=None, help="POS,ROT_DEG: time lsim_sensor_mount_jitter and lsim_sensor_capture on jittered against nominal mounts (needs --model)")
+    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.mount_jitter:
+        if not a.model:
+            ap.error("--mount-jitter needs --model")
+        pos, rot = (float(v) for v in a.mount_jitter.split(","))
+        model, jitter = parse_model(a.model), sensors.MountJitter(pos=pos, rot_deg=rot)
+        res = {"tool": "raycast_time --mount-jitter", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot", "model": a.model, "mount_jitter": jitter.record(),
+               "cases": [measure_mount_jitter(a.num_envs, t, a.iters, a.warmup, model, jitter, a.repeats) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     count_lib = None
     if not a.no_counters:
         if hip_build.variant_is_stale(COUNT_LIB):
