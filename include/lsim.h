@@ -46,7 +46,9 @@ extern "C" {
                                     lsim_depth_encode_backward + lsim_depth_encode_backward_sizes (the gradients of that CNN's parameters);
                                     lsim_eval_columns + lsim_eval_columns_sizes / _clear / _accumulate (caller-supplied columns into the evaluator's groups);
                                     lsim_depth_memory_step + lsim_depth_memory_sizes, lsim_gru_sequence_forward / _backward (a GRU cell over the depth latent);
-                                    lsim_sensor_mount_jitter + LSIM_RNG_SENSOR_MOUNT (a sensor's mount pose redrawn per episode, on the device) */
+                                    lsim_sensor_mount_jitter + LSIM_RNG_SENSOR_MOUNT (a sensor's mount pose redrawn per episode, on the device);
+                                    lsim_sensor_instrument + lsim_sensor_capture_inst + LSIM_RNG_SENSOR_INSTRUMENT (a sensor's latency, noise level,
+                                    depth-scale error and field of view redrawn per episode, and the capture that reads them) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -165,8 +167,10 @@ enum lsim_rng_tag {
                                   block p gives the two Box-Muller pairs of actions 2p, 2p+1       */
     LSIM_RNG_SENSOR = 15,      /* lsim_sensor_capture (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | ray -- one whole block per ray, all four words used      */
-    LSIM_RNG_SENSOR_MOUNT = 16 /* lsim_sensor_mount_jitter (no reference site): step word = (uint32) tick, the fourth counter word =
+    LSIM_RNG_SENSOR_MOUNT = 16, /* lsim_sensor_mount_jitter (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: position x y z and rotation x, block 1: rotation y z, two words unused */
+    LSIM_RNG_SENSOR_INSTRUMENT = 17 /* lsim_sensor_instrument (no reference site): step word = (uint32) tick, the fourth counter word =
+                                  (stream_id << 16) | b, b = 0, 1 -- block 0: latency, noise gain, depth scale, depth quad, block 1: tan scale, three words unused */
 };
 
 /* ---- robot model: the URDF after Isaac Gym's fixed-joint collapse ----
@@ -1221,6 +1225,76 @@ typedef struct lsim_sensor_mount_jitter {
  * 4-byte aligned; episode_length NULL or not 8-byte aligned; mount == nominal; num_envs < 1; env_stride < 1; tick < 0; stream_id >= 65536; a
  * pos_range or rot_range entry that is negative or not finite; a flag bit other than the sensor model's two; both of them set. */
 int lsim_sensor_mount_jitter(const lsim_sensor_mount_jitter_t* mj, void* stream);
+
+/* ---- sensor instrument error: the instrument's own constants -- latency, noise level, depth-scale error, field of view -- redrawn for every
+ * env that starts an episode, and the capture that reads them.  TWO entries, each ONE launch under the rules of lsim_sensor_capture (caller's
+ * stream, no host synchronisation, raw pointers only): lsim_sensor_instrument writes rows of `inst`, and lsim_sensor_capture_inst, enqueued
+ * BEHIND it on the same stream, is lsim_sensor_capture with the row of each env in place of the shared constants.  lsim_sensor_capture itself,
+ * its kernel and lsim_sensor_model_t do not change: the rows come through the new entry's own argument.
+ *
+ * The row.  inst[e] is 8 floats, rows 32 bytes apart:   { lat, noise_gain, depth_scale, depth_quad, tan_scale, 0, 0, 0 }
+ *   lat: the env's latency in captures, an integer held in a float; noise_gain: a factor on the model's noise; depth_scale (no unit) and
+ *   depth_quad (1/m): the relative depth error depth_scale + depth_quad * d of a hit at reported depth d (a focal / baseline miscalibration
+ *   gives an error proportional to d, a disparity offset one proportional to d^2); tan_scale: the factor on the tangent of every ray's angle
+ *   to the optical axis (the sensor frame's +x), 1 / (relative focal-length error).  The three zeros are reserved and written as zeros.
+ *   The NEUTRAL row { sm.latency, 1, 0, 0, 1, 0, 0, 0 } makes lsim_sensor_capture_inst write the bits lsim_sensor_capture writes.
+ *
+ * lsim_sensor_instrument.
+ * Which envs.  Env e is visited when e % env_stride == 0.  A visited env is FRESH when
+ *     (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0                  (lsim_sensor_capture's `fill`; the tick plays no part in it)
+ *   LSIM_SENSOR_RESETS_ONLY is accepted and changes nothing here.  For an env that is not visited or not fresh NOTHING is written.
+ * Draws.  Two Philox4x32-10 blocks, key (seed, rank), counters (e, (uint32_t)tick, LSIM_RNG_SENSOR_INSTRUMENT, (stream_id << 16) | b), b = 0, 1:
+ *     x0..x3 = block 0, x4..x7 = block 1;   u_k = (x_k >> 8) * 2^-24  for k = 0..4 (exact in fp32); x5, x6, x7 are not used.
+ *   The draw depends on (e, tick, stream_id) and the key only: a second launch on the same tick writes the same bits.
+ * Per fresh env, all arithmetic in fp32 (a compiler may contract a product and a sum into one fused operation):
+ *     span = lat_hi - lat_lo;   j = min(span, (int) floor(u_0 * (float)(span + 1)));   lat = (float)(lat_hi - j)
+ *         (uniform on the integers lat_lo .. lat_hi: u_0 (span + 1) < span + 1 before rounding, and the min takes a product rounded up to span + 1)
+ *     noise_gain  = gain_lo + u_1 * (gain_hi - gain_lo)
+ *     depth_scale = (2 u_2 - 1) * scale_range                                   (2 u - 1 is exact)
+ *     depth_quad  = (2 u_3 - 1) * quad_range
+ *     tan_scale   = 1 + (2 u_4 - 1) * fov_range
+ *   Zero ranges (lat_lo = lat_hi, gain_lo = gain_hi = 1, the other three 0) give the row { lat_hi, 1, 0, 0, 1, 0, 0, 0 } exactly (a 0 may
+ *   carry either sign).  The row is written as two 16-byte stores.
+ * tick is passed by value as lsim_sensor_capture's is, and replays from a captured graph in the same way. */
+typedef struct lsim_sensor_instrument {
+    float* inst;                      /* [N, 8] the rows, 32-byte aligned */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    int64_t tick;                     /* >= 0, by value: the tick of the capture that follows */
+    uint32_t seed, rank, stream_id;   /* as lsim_sensor_model_t's; stream_id < 65536 */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    int32_t lat_lo, lat_hi;           /* captures: 0 <= lat_lo <= lat_hi < LSIM_SENSOR_MAX_HISTORY */
+    float gain_lo, gain_hi;           /* finite, 0 <= gain_lo <= gain_hi */
+    float scale_range, quad_range;    /* half-widths of depth_scale (no unit) and depth_quad (1/m): finite, >= 0 */
+    float fov_range;                  /* half-width of tan_scale about 1: finite, 0 <= fov_range < 1 */
+} lsim_sensor_instrument_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: si == NULL; inst NULL or not 32-byte
+ * aligned; episode_length NULL or not 8-byte aligned; num_envs < 1; env_stride < 1; tick < 0; stream_id >= 65536; lat_lo < 0; lat_lo > lat_hi;
+ * lat_hi >= LSIM_SENSOR_MAX_HISTORY; gain_lo, gain_hi, scale_range, quad_range or fov_range negative or not finite; gain_lo > gain_hi;
+ * fov_range >= 1; a flag bit other than the sensor model's two; both of them set. */
+int lsim_sensor_instrument(const lsim_sensor_instrument_t* si, void* stream);
+
+/* lsim_sensor_capture with per-env instrument rows: everything said of lsim_sensor_capture holds -- which envs are due, the rays, `raw`, the
+ * clean `out` and the labels, the Philox block per ray at LSIM_RNG_SENSOR, dropout, clip, offset and gain, the layout of hist with its
+ * K = sm->latency + sm->frames slots -- except for the three things below.  `inst` is the [N, 8] array above (here 16-byte alignment
+ * suffices); a due env reads its own row { lat, noise_gain, depth_scale, depth_quad, tan_scale, .. } and an env that is not due reads none.
+ * Field of view.  s = dirs[r], in the sensor frame, sc = scale ? scale[r] : 1.  If tan_scale != 1.0f and s.x > 0, with T = tan_scale:
+ *     y' = s.y * T;   z' = s.z * T;   n = sqrt(s.x * s.x + y' * y' + z' * z')   (fp32 sum, left to right, possibly fused; the root correctly rounded)
+ *     q = 1 / n   (correctly rounded);      s' = (s.x * q, y' * q, z' * q);      sc' = sc * q      (q itself when scale is NULL)
+ *   and the ray is cast along s' and reported with sc' wherever lsim_sensor_capture uses s and sc: every tangent to the +x axis is multiplied
+ *   by T, and for a z-depth camera (scale = the cosine to the axis) sc' is the new cosine.  Otherwise (tan_scale == 1.0f, or a ray with
+ *   s.x <= 0, which has no finite tangent) s and sc are used untouched.  `out` and the labels are the clean values of the rays actually cast.
+ * Calibration and noise, on a hit only, in place of lsim_sensor_capture's line for v (g, u3 as there):
+ *     m = raw * (1 + (depth_scale + depth_quad * raw))                      (no operation of this line is fused with another: m is a rounded product)
+ *     v = m + (noise_gain * (sigma0 + sigma2 * raw * raw)) * g
+ *   then dropout, clip, offset and gain as there.  A miss and a non-finite ray report raw, as there.
+ * Latency.  L = min(max((int) lat, 0), sm->latency);   Ke = L + sm->frames  (<= K):
+ *     fill:       hist[e][k][r] = y for every k < K                              (as there)
+ *     otherwise:  hist[e][k][r] = hist[e][k + 1][r] for k = 0 .. Ke - 2 in this order, then hist[e][k][r] = y for k = Ke - 1 .. K - 1.
+ *   Slots 0 .. frames - 1, what a policy reads, are then L captures old; slots Ke .. K - 1 only ever hold the newest capture.  L = sm->latency
+ *   is lsim_sensor_capture's shift.
+ * LSIM_E_INVALID, checked on the host before any launch: everything lsim_sensor_capture refuses; inst NULL or not 16-byte aligned. */
+int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

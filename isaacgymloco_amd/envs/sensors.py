@@ -37,6 +37,13 @@ along and up to `rot_deg` degrees about the base x, y, z, around the nominal mou
 rows of `cam.mount` of the envs just reset, on the device (nobody on the host learns who reset), so a reset env's frame history is
 refilled from its new pose within the same step; `cam.mount_nominal` keeps the nominal poses.  spec() records the jitter and from_spec()
 rebuilds it.  Without `mount_jitter` nothing of this is created or launched.
+
+Instrument error (`instrument=InstrumentError(latency=(0, 2), noise_gain=(0.5, 2), depth_scale=0.02, depth_quad=0.005, fov=0.02)`,
+lsim_sensor_instrument + lsim_sensor_capture_inst; needs a model): a real unit is not its data sheet, so every env that starts an episode also
+draws the instrument's own constants -- how many captures late it is, a factor on the noise, a relative depth error that grows with depth, and
+a field of view a little wider or narrower.  One small launch ahead of every capture rewrites the rows of `cam.instrument_rows()` of the envs
+just reset, on the device, and the capture is lsim_sensor_capture_inst, which reads them.  spec() records the ranges and from_spec()
+rebuilds them.  Without `instrument` nothing of this is created or launched and the capture is lsim_sensor_capture.
 """
 import ctypes
 import math
@@ -134,6 +141,42 @@ class MountJitter:
         return f"MountJitter(pos={self.pos}, rot_deg={self.rot_deg})"
 
 
+class InstrumentError:
+    """Per-episode error of a sensor's own constants (lsim_sensor_instrument; include/lsim.h states every formula): when an env starts an
+    episode it draws `latency` = (lo, hi): its latency in captures, uniform on the integers lo .. hi (None: the model's, for every env;
+    hi <= the model's latency, which sizes the history); `noise_gain` = (lo, hi): a uniform factor on the model's noise; `depth_scale` and
+    `depth_quad` (1 / m): half-widths of the relative depth error depth_scale + depth_quad * d of a hit at depth d; `fov`: half-width of the
+    relative error of the tangent of every ray's angle to the optical axis (0.02: the image is up to 2 % wider or narrower), which needs
+    rays that all look forward (a camera, not a lidar)."""
+
+    def __init__(self, latency=None, noise_gain=(1.0, 1.0), depth_scale=0.0, depth_quad=0.0, fov=0.0):
+        self.latency = None if latency is None else (int(latency[0]), int(latency[1]))
+        if self.latency is not None and (len(latency) != 2 or self.latency != tuple(latency) or not 0 <= self.latency[0] <= self.latency[1] < abi.DEFINES["LSIM_SENSOR_MAX_HISTORY"]):
+            raise ValueError(f"InstrumentError: latency is None or integers 0 <= lo <= hi < {abi.DEFINES['LSIM_SENSOR_MAX_HISTORY']}, got {latency}")
+        self.noise_gain = (float(noise_gain[0]), float(noise_gain[1]))
+        self.depth_scale, self.depth_quad, self.fov = float(depth_scale), float(depth_quad), float(fov)
+        values = self.noise_gain + (self.depth_scale, self.depth_quad, self.fov)
+        if len(noise_gain) != 2 or any(not math.isfinite(x) or x < 0.0 for x in values) or self.noise_gain[0] > self.noise_gain[1] or self.fov >= 1.0:
+            raise ValueError(f"InstrumentError: finite 0 <= noise_gain[0] <= noise_gain[1], depth_scale >= 0, depth_quad >= 0 and 0 <= fov < 1, got {values}")
+
+    def record(self):
+        """the plain dict spec() stores and InstrumentError(**record) reads"""
+        return {"latency": None if self.latency is None else list(self.latency), "noise_gain": list(self.noise_gain),
+                "depth_scale": self.depth_scale, "depth_quad": self.depth_quad, "fov": self.fov}
+
+    def _key(self):
+        return (self.latency, self.noise_gain, self.depth_scale, self.depth_quad, self.fov)
+
+    def __eq__(self, other):
+        return isinstance(other, InstrumentError) and self._key() == other._key()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"InstrumentError(latency={self.latency}, noise_gain={self.noise_gain}, depth_scale={self.depth_scale}, "
+                f"depth_quad={self.depth_quad}, fov={self.fov})")
+
+
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
@@ -148,10 +191,13 @@ class RaySensor:
     With `model=None` nothing of this is allocated and the launch is the one above.
     `mount_jitter` (a MountJitter; needs a model): `mount_nominal` keeps the [N, 7] poses given here, `mount` becomes a buffer of its own
     that lsim_sensor_mount_jitter rewrites, ahead of every capture and with its stream, tick and flags, for the envs that start an episode.
-    With `mount_jitter=None` `mount` is `mount_nominal` and no such launch is made."""
+    With `mount_jitter=None` `mount` is `mount_nominal` and no such launch is made.
+    `instrument` (an InstrumentError; needs a model): `instrument_rows()` is the live [N, 8] tensor of each env's own latency, noise gain,
+    depth-scale error and field-of-view factor, which lsim_sensor_instrument rewrites ahead of every capture for the envs that start an
+    episode, and the capture is lsim_sensor_capture_inst.  With `instrument=None` there is no such tensor and no such launch."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
         self.env = env
         self.model = model
         self._api = api if api is not None else env._L
@@ -175,6 +221,7 @@ class RaySensor:
         self.scale = None if scale is None else torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float32).reshape(R), device=dev).contiguous()
         self.mount = self.mount_nominal = torch.cat((self._per_env(mount_pos, 3, dev), self._per_env(mount_quat, 4, dev)), dim=1).contiguous()
         self.mount_jitter = self._mj = None
+        self.instrument = self._si = self._inst = None
         stride = (R + 3) // 4 * 4
         self._out = torch.full((N, stride), self.far, dtype=torch.float32, device=dev)
         if self.scale is not None:
@@ -209,6 +256,45 @@ class RaySensor:
             self._setup_model(model, dev)
         if mount_jitter is not None:
             self.set_mount_jitter(mount_jitter)
+        if instrument is not None:
+            self.set_instrument(instrument)
+
+    def set_instrument(self, instrument):
+        """`instrument` (an InstrumentError) from now on, or None: back to lsim_sensor_capture, no launch and no rows.  Until the next
+        refresh() (every env) or, env by env, until episodes start, the rows are the neutral ones: the model's own constants"""
+        if instrument is None:
+            self.instrument = self._si = self._inst = None
+            return
+        if not isinstance(instrument, InstrumentError):
+            raise TypeError(f"instrument: expected an InstrumentError or None, got {type(instrument).__name__}")
+        if self.model is None:
+            raise ValueError("instrument needs a model (SensorModel): the latency, the noise and the history it varies are the model's")
+        lat = (self.model.latency, self.model.latency) if instrument.latency is None else instrument.latency
+        if lat[1] > self.model.latency:
+            raise ValueError(f"instrument: latency {instrument.latency} exceeds the model's latency {self.model.latency}, which sizes the history")
+        if instrument.fov > 0.0 and bool((self.dirs[:, 0] <= 0.0).any()):
+            raise ValueError("instrument: fov > 0 needs rays that all look forward (dirs[:, 0] > 0): a ray at or behind the image plane has no tangent to scale")
+        for need in ("lsim_sensor_instrument", "lsim_sensor_capture_inst"):
+            if not hasattr(self._api, need):
+                raise lib.LsimError(f"the loaded library has no {need}: rebuild it (there is no torch fall-back for the instrument error)")
+        N = int(self.env.num_envs)
+        if self._inst is None:
+            self._inst = torch.zeros((N, 8), dtype=torch.float32, device=self._out.device)
+            self._inst[:, 0], self._inst[:, 1], self._inst[:, 4] = float(self.model.latency), 1.0, 1.0
+        si = abi.LsimSensorInstrument()
+        si.inst, si.episode_length = self._inst.data_ptr(), self._sm.episode_length
+        si.seed, si.rank, si.stream_id = self._sm.seed, self._sm.rank, self._sm.stream_id
+        si.num_envs, si.env_stride = N, self.env_stride
+        si.lat_lo, si.lat_hi = lat
+        si.gain_lo, si.gain_hi = instrument.noise_gain
+        si.scale_range, si.quad_range, si.fov_range = instrument.depth_scale, instrument.depth_quad, instrument.fov
+        self.instrument, self._si = instrument, si
+
+    def instrument_rows(self):
+        """live [N, 8] tensor: row e = {latency, noise gain, depth_scale, depth_quad, tan_scale, 0, 0, 0} of env e (instrument=...)"""
+        if self._inst is None:
+            raise ValueError("the sensor has no instrument error (instrument=InstrumentError(...))")
+        return self._inst
 
     def set_mount_jitter(self, jitter):
         """`jitter` (a MountJitter) from now on, or None: back to the nominal mount and no launch.  The new poses are drawn by the next
@@ -273,6 +359,8 @@ class RaySensor:
             self._sm.stream_id = int(value)
             if self._mj is not None:
                 self._mj.stream_id = int(value)
+            if self._si is not None:
+                self._si.stream_id = int(value)
 
     def _setup_bodies(self, rc, ignore_bodies, labels, dev):
         """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
@@ -354,7 +442,12 @@ class RaySensor:
             if self._mj is not None:            # first: the envs that start an episode are rendered, history and all, from their new pose
                 self._mj.tick, self._mj.flags = self.tick, int(flags)
                 lib.check(self._api.lsim_sensor_mount_jitter(ctypes.byref(self._mj), self._stream(stream)), what="lsim_sensor_mount_jitter")
-            lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
+            if self._si is not None:            # then the instrument of those envs, and the capture that reads the rows
+                self._si.tick, self._si.flags = self.tick, int(flags)
+                lib.check(self._api.lsim_sensor_instrument(ctypes.byref(self._si), self._stream(stream)), what="lsim_sensor_instrument")
+                lib.check(self._api.lsim_sensor_capture_inst(ctypes.byref(self._sm), self._inst.data_ptr(), self._stream(stream)), what="lsim_sensor_capture_inst")
+            else:
+                lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
             if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
                 self._encoder.encode_device(self, self.tick, int(flags), stream)
                 if self._memory is not None:    # every env, every update: z is held between captures, the memory still ticks
@@ -440,7 +533,7 @@ class RaySensor:
         dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
-        one there is no such key."""
+        one there is no such key.  Likewise "instrument" holds an InstrumentError's record, and is absent without one."""
         out = {"kind": "rays"}
         if hasattr(self, "width") and hasattr(self, "height"):
             out.update(kind="camera", width=int(self.width), height=int(self.height))
@@ -467,6 +560,8 @@ class RaySensor:
             out["mount"] = None
         if self.mount_jitter is not None:
             out["mount_jitter"] = self.mount_jitter.record()
+        if self.instrument is not None:
+            out["instrument"] = self.instrument.record()
         return out
 
     @property
@@ -495,27 +590,29 @@ class DepthCamera(RaySensor):
 
 
 def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
-    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last six keywords as RaySensor's"""
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last seven keywords as RaySensor's"""
     return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api,
-                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter)
+                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter,
+                       instrument=instrument)
 
 
 def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
-          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None):
+          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
     """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
-    `points_per_rev` azimuths each; reports range (scale=None); the last six keywords as RaySensor's"""
+    `points_per_rev` azimuths each; reports range (scale=None); the last seven keywords as RaySensor's"""
     s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
-                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter)
+                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter,
+                  instrument=instrument)
     s.channels, s.points_per_rev = int(channels), int(points_per_rev)
     return s
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec"):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
-    (none when the record has none); None or a MountJitter takes its place."""
+    (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -534,6 +631,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
             raise ValueError(f"from_spec: mount_jitter is 'spec', None or a MountJitter, got {mount_jitter!r}")
         j = spec.get("mount_jitter")
         mount_jitter = None if j is None else MountJitter(**j)
+    if isinstance(instrument, str):
+        if instrument != "spec":
+            raise ValueError(f"from_spec: instrument is 'spec', None or an InstrumentError, got {instrument!r}")
+        i = spec.get("instrument")
+        instrument = None if i is None else InstrumentError(**i)
     kind = spec.get("kind", "rays")
     cls = DepthCamera if kind == "camera" else RaySensor
     sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
@@ -542,7 +644,7 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     RaySensor.__init__(sensor, env, np.asarray(spec["dirs"], dtype=np.float32), pos, quat, spec["near"], spec["far"],
                        scale=None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32), env_stride=spec["env_stride"], api=api,
                        see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"], frame=spec["frame"], model=model,
-                       mount_jitter=mount_jitter)
+                       mount_jitter=mount_jitter, instrument=instrument)
     if kind == "lidar":
         sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
     return sensor

@@ -187,7 +187,7 @@ class Evaluator:
             e.trace_envs[k] = i
         self._e = e
         self.column_names, self.columns, self.col_table, self._c = (), None, None, None
-        self.extra_conventions = {}       # what evaluate() adds to result()["conventions"] (a vision policy's camera_jitter)
+        self.extra_conventions = {}       # what evaluate() adds to result()["conventions"] (a vision policy's camera_jitter, camera_instrument)
         self.clear()
 
     def add_columns(self, names):
@@ -416,6 +416,57 @@ def parse_camera_jitter(text):
     return MountJitter(**kw)
 
 
+def _camera_instrument(cam, found, camera_instrument):
+    """evaluate()'s `camera_instrument` applied to the camera, as _camera_jitter applies the mount jitter: "trained" -- what the checkpoint's
+    vision["sensor"] record says (a runner's camera stays as it is); None -- the model's own constants for every env; an InstrumentError --
+    that one.  A camera whose instrument changes has every env's row redrawn and history refilled once (refresh()).
+    Returns the entry of the result's conventions."""
+    from ..envs.sensors import InstrumentError
+    current = getattr(cam, "instrument", None)
+    if isinstance(camera_instrument, str):
+        if camera_instrument != "trained":
+            raise ValueError(f"evaluate: camera_instrument is 'trained', None or an InstrumentError, got {camera_instrument!r}")
+        d = found.get("checkpoint")
+        record = ((d.get("vision") or {}).get("sensor")) if d is not None else None
+        want = current if record is None else (InstrumentError(**record["instrument"]) if record.get("instrument") else None)
+        choice = "trained"
+    elif camera_instrument is None:
+        want, choice = None, "off"
+    elif isinstance(camera_instrument, InstrumentError):
+        want, choice = camera_instrument, "override"
+    else:
+        raise TypeError(f"evaluate: camera_instrument is 'trained', None or an InstrumentError, got {type(camera_instrument).__name__}")
+    if want != current:
+        cam.set_instrument(want)
+        if cam.tick >= 0:
+            cam.refresh()
+    blank = {"latency": None, "noise_gain": None, "depth_scale": None, "depth_quad": None, "fov": None}
+    return dict(blank if want is None else want.record(), choice=choice)
+
+
+def parse_camera_instrument(text):
+    """the command line's --camera-instrument: "trained", "off" (None), or "latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F"
+    (any key may be left out: the model's latency, gain 1, 0)"""
+    from ..envs.sensors import InstrumentError
+    if text == "trained":
+        return "trained"
+    if text == "off":
+        return None
+    kw = {}
+    for item in text.split(","):
+        k, sep, v = item.partition("=")
+        if not sep or k not in ("latency", "noise_gain", "depth_scale", "depth_quad", "fov") or k in kw:
+            raise ValueError(f"expected trained, off or latency=LO:HI,noise_gain=LO:HI,depth_scale=..,depth_quad=..,fov=.., got {text!r}")
+        if k in ("latency", "noise_gain"):
+            vals = [(int if k == "latency" else float)(x) for x in v.split(":")]
+            if len(vals) != 2:
+                raise ValueError(f"{k}: two numbers joined by ':', got {v!r}")
+            kw[k] = tuple(vals)
+        else:
+            kw[k] = float(v)
+    return InstrumentError(**kw)
+
+
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 
 
@@ -484,7 +535,8 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
 
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
-             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained"):
+             sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained",
+             camera_instrument="trained"):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -498,7 +550,9 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     `camera_jitter` (a vision policy only): the per-episode mount error of the camera (envs.sensors.MountJitter) -- "trained": what the
     checkpoint's record of the sensor says (a runner's camera stays as it is); None: the nominal mount; a MountJitter: that one, to
     measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's
-    conventions["camera_jitter"]."""
+    conventions["camera_jitter"].
+    `camera_instrument` (a vision policy only): the same choice for the per-episode error of the camera's own constants
+    (envs.sensors.InstrumentError: latency, noise gain, depth-scale error, field of view), written to conventions["camera_instrument"]."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
@@ -508,6 +562,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     if is_vision:
         cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
         jitter_entry = _camera_jitter(cam, found, camera_jitter)       # after the encoder and the memory are attached: a refresh() runs them too
+        instrument_entry = _camera_instrument(cam, found, camera_instrument)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -517,6 +572,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
     if is_vision:
         ev.extra_conventions["camera_jitter"] = jitter_entry
+        ev.extra_conventions["camera_instrument"] = instrument_entry
         return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
                                 memory=found.get("memory"), memory_head=found.get("memory_head"))
     use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
@@ -572,9 +628,15 @@ def parse_args(argv=None):
     ap.add_argument("--vision-metrics", default="depth_influence,scan_error", help="columns a vision policy adds to the result; empty: none")
     ap.add_argument("--camera-jitter", default="trained", help="a vision policy's per-episode camera mount error: 'trained' (the checkpoint's record), "
                     "'off' (the nominal mount) or pos=METRES,rot_deg=DEGREES (one number, or x/y/z)")
+    ap.add_argument("--camera-instrument", default="trained", help="a vision policy's per-episode error of the camera's own constants: 'trained' (the "
+                    "checkpoint's record), 'off' or latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F (any subset)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    try:
+        a.camera_instrument = parse_camera_instrument(a.camera_instrument)
+    except ValueError as exc:
+        ap.error(f"--camera-instrument: {exc}")
     try:
         a.camera_jitter = parse_camera_jitter(a.camera_jitter)
     except ValueError as exc:
@@ -627,7 +689,7 @@ def main(argv=None):
         from ..envs.sensors import from_spec
         env.add_sensor("depth", from_spec(env, record["sensor"]))
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
-                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter)
+                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

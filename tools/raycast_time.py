@@ -21,6 +21,12 @@ episode_length 0; `camera_model_us` = lsim_sensor_capture exactly as --model tim
 the same launch on a sensor whose mounts were drawn once for every env (the jitter launch itself kept out of the timed loop), the two
 alternating `--repeats` times, each with its median and its range over the repeats (the run-to-run spread of this process);
 `camera_model_update_with_jitter_us` = update() as a jittered sensor runs it in a step: the jitter launch (nobody fresh) and the capture.
+`--instrument latency=0:2,noise_gain=0.5:2,depth_scale=0.02,depth_quad=0.005,fov=0.02` (the text of evaluate's --camera-instrument; needs
+--model; a measurement of its own, no counters): per terrain and for the camera and the lidar (the lidar without the field-of-view term,
+which it cannot take), in one process and alternating `--repeats` times, each with its median and range: `<sensor>_capture_us` =
+lsim_sensor_capture as --model times it; `<sensor>_inst_neutral_us` = lsim_sensor_capture_inst on the neutral rows; `<sensor>_inst_drawn_us` =
+the same on rows drawn once for every env (the draw launch kept out of the timed loop); `draw_all_fresh_us` / `draw_none_fresh_us` =
+lsim_sensor_instrument alone with LSIM_SENSOR_FILL_ALL and with no env at episode_length 0.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -143,6 +149,69 @@ def measure_mount_jitter(n, terrain, iters, warmup, model, jitter, repeats):
     return out
 
 
+def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
+    """the --instrument measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    torch.cuda.synchronize()
+    no_fov = sensors.InstrumentError(**dict(instrument.record(), fov=0.0))
+    makers = {"camera": (lambda **kw: sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True,
+                                                           labels=True, model=model, **kw), instrument),
+              "lidar": (lambda **kw: sensors.lidar(env, 16, 30.0, 360, mount_pos=(0.0, 0.0, 0.15), near=0.05, far=10.0, see_robot=True, labels=True,
+                                                   model=model, **kw), no_fov)}
+    out = {"num_envs": n, "terrain": terrain, "resetting_envs": int((env.episode_length_buf == 0).sum().item())}
+    L, fill_all = env._L, abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+    whole = max(model.period, iters // model.period * model.period)
+    rows, nonfinite = {}, 0
+    sensors_ = {}
+    for name, (make, inst) in makers.items():
+        plain, neutral, drawn = make(), make(instrument=inst), make(instrument=inst)
+        for s_ in (plain, neutral, drawn):
+            s_.refresh(tick=0)                  # `drawn`: draws every env's row once
+        neutral._inst.zero_()                   # back to the neutral rows {latency, 1, 0, 0, 1, 0, 0, 0}
+        neutral._inst[:, 0], neutral._inst[:, 1], neutral._inst[:, 4] = float(model.latency), 1.0, 1.0
+        sensors_[name] = (plain, neutral, drawn, drawn._si)
+        for k in ("capture", "inst_neutral", "inst_drawn"):
+            rows[f"{name}_{k}_us"] = []
+    rows["draw_all_fresh_us"], rows["draw_none_fresh_us"] = [], []
+    si = sensors_["camera"][3]
+
+    def draw(flags):
+        si.tick, si.flags = 0, flags
+        lib.check(L.lsim_sensor_instrument(ctypes.byref(si), env._stream()), what="lsim_sensor_instrument")
+
+    def capture_only(sensor):
+        """update() without the draw launch: lsim_sensor_capture_inst on the rows as they are"""
+        tick = [0]
+
+        def fn():
+            sensor._sm.tick, sensor._sm.flags = tick[0], 0
+            lib.check(L.lsim_sensor_capture_inst(ctypes.byref(sensor._sm), sensor._inst.data_ptr(), env._stream()), what="lsim_sensor_capture_inst")
+            tick[0] += 1
+        return timed(fn, whole, warmup)
+    for _ in range(repeats):                    # the draw at tick 0 rewrites the rows refresh(tick=0) drew: the same bits
+        for name, (plain, neutral, drawn, _) in sensors_.items():
+            rows[f"{name}_capture_us"].append(timed_ticks(plain, whole, warmup))
+            rows[f"{name}_inst_neutral_us"].append(capture_only(neutral))
+            rows[f"{name}_inst_drawn_us"].append(capture_only(drawn))
+        rows["draw_all_fresh_us"].append(timed(lambda: draw(fill_all), iters, warmup))
+        rows["draw_none_fresh_us"].append(timed(lambda: draw(0), iters, warmup))
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    for name, (plain, neutral, drawn, _) in sensors_.items():
+        out[f"{name}_neutral_over_capture"] = out[f"{name}_inst_neutral_us"] / out[f"{name}_capture_us"]
+        out[f"{name}_drawn_over_capture"] = out[f"{name}_inst_drawn_us"] / out[f"{name}_capture_us"]
+        nonfinite += sum(int(s_.nonfinite_rays.item()) for s_ in (plain, neutral, drawn))
+    out["nonfinite_rays"] = nonfinite
+    return out
+
+
 def measure(n, terrain, iters, warmup, count_lib, bodies=False, model=None):
     cfg = C.aliengo_cfg()
     cfg.env.num_envs = n
@@ -216,7 +285,9 @@ def main():
     ap.add_argument("--bodies", action="store_true", help="also time lsim_raycast_bodies (see_robot=True) on every workload")
     ap.add_argument("--model", default=None, help="also time lsim_sensor_capture with this sensor model, e.g. period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02")
     ap.add_argument("--mount-jitter", default=None, help="POS,ROT_DEG: time lsim_sensor_mount_jitter and lsim_sensor_capture on jittered against nominal mounts (needs --model)")
-    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter: alternating repetitions of every timed loop")
+    ap.add_argument("--instrument", default=None, help="latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F: time lsim_sensor_instrument and "
+                    "lsim_sensor_capture_inst against lsim_sensor_capture (needs --model)")
+    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -228,6 +299,23 @@ def main():
         res = {"tool": "raycast_time --mount-jitter", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
                "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot", "model": a.model, "mount_jitter": jitter.record(),
                "cases": [measure_mount_jitter(a.num_envs, t, a.iters, a.warmup, model, jitter, a.repeats) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
+    if a.instrument:
+        if not a.model:
+            ap.error("--instrument needs --model")
+        from isaacgymloco_amd.learn.evaluate import parse_camera_instrument
+        model, instrument = parse_model(a.model), parse_camera_instrument(a.instrument)
+        if not isinstance(instrument, sensors.InstrumentError):
+            ap.error("--instrument takes ranges, not 'trained' or 'off'")
+        res = {"tool": "raycast_time --instrument", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot", "lidar": "16x360, vfov 30, far 10 m, see_robot, fov 0", "model": a.model,
+               "instrument": instrument.record(),
+               "cases": [measure_instrument(a.num_envs, t, a.iters, a.warmup, model, instrument, a.repeats) for t in a.terrains.split(",")]}
         line = json.dumps(res)
         if a.out:
             with open(a.out, "w") as f:

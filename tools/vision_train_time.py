@@ -1,7 +1,7 @@
 """Collection and update time per iteration of VisionOnPolicyRunner next to HIMOnPolicyRunner on the same env configuration, both with the
 depth camera attached (the HIM runner merely does not read it), and the encoder's own step separately.
 
-    python tools/vision_train_time.py [--envs 4096] [--iters 6] [--warmup 2] [--memory] [--mount-jitter POS,ROT_DEG] [--out profiles/vision_train_time.json]
+    python tools/vision_train_time.py [--envs 4096] [--iters 6] [--warmup 2] [--memory] [--mount-jitter POS,ROT_DEG] [--instrument RANGES] [--out profiles/vision_train_time.json]
 
 Wall clock around device synchronisations, as the runners' own last_perf; the encoder step with HIP events inside VisionPPO.update()."""
 import argparse, json, os, sys
@@ -22,10 +22,11 @@ def make(kind, a):
     env = LeggedRobot(cfg, sim_device=DEV, seed=1)
     cam = env.add_sensor("depth", sensors.depth_camera(env, a.width, a.height, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0,
                                                        model=sensors.SensorModel(period=5, stagger=True, latency=1, frames=2, normalise=True),
-                                                       mount_jitter=a.jitter if kind == "vision_jitter" else None))
+                                                       mount_jitter=a.jitter if kind == "vision_jitter" else None,
+                                                       instrument=a.inst if kind == "vision_instrument" else None))
     tc = train_cfg_dict("aliengo")
     torch.manual_seed(0)
-    if kind in ("vision", "vision_jitter", "memory"):
+    if kind in ("vision", "vision_jitter", "vision_instrument", "memory"):
         run = VisionOnPolicyRunner(env, tc, sensor="depth", device=DEV, memory=True if kind == "memory" else None)
     else:
         from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
@@ -47,7 +48,7 @@ def measure(kind, a):
             mem_ms.append((e0, e1))
             return out
         run.alg.memory_step = timed_memory_step
-    if kind in ("vision", "vision_jitter", "memory"):
+    if kind in ("vision", "vision_jitter", "vision_instrument", "memory"):
         alg, step = run.alg, run.alg.encoder_step
 
         def timed_step():
@@ -86,6 +87,8 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "vision_train_time.json"))
     ap.add_argument("--memory", action="store_true", help="also the vision runner with a depth memory (memory=True): collection, update and memory-step time")
     ap.add_argument("--mount-jitter", default=None, help="POS,ROT_DEG (metres, degrees): also the vision runner with sensors.MountJitter(pos, rot_deg) on its camera")
+    ap.add_argument("--instrument", default=None, help="latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F (evaluate's --camera-instrument): also the "
+                    "vision runner with that sensors.InstrumentError on its camera")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("vision_train_time.py needs a GPU: there is no CPU form of this measurement")
@@ -97,6 +100,11 @@ if __name__ == "__main__":
         a.jitter = MountJitter(pos=pos, rot_deg=rot)
         res["vision_jitter"] = measure("vision_jitter", a)      # one more launch per step in the collection; the update is the same
         res["mount_jitter"] = a.jitter.record()
+    if a.instrument:
+        from isaacgymloco_amd.learn.evaluate import parse_camera_instrument
+        a.inst = parse_camera_instrument(a.instrument)
+        res["vision_instrument"] = measure("vision_instrument", a)      # one more launch per step and the other capture kernel in the collection
+        res["instrument"] = a.inst.record()
     if a.memory:
         res["memory"] = measure("memory", a)          # update_s includes encoder_step_s and memory_step_s
     print(json.dumps(res))
