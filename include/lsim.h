@@ -48,7 +48,8 @@ extern "C" {
                                     lsim_depth_memory_step + lsim_depth_memory_sizes, lsim_gru_sequence_forward / _backward (a GRU cell over the depth latent);
                                     lsim_sensor_mount_jitter + LSIM_RNG_SENSOR_MOUNT (a sensor's mount pose redrawn per episode, on the device);
                                     lsim_sensor_instrument + lsim_sensor_capture_inst + LSIM_RNG_SENSOR_INSTRUMENT (a sensor's latency, noise level,
-                                    depth-scale error and field of view redrawn per episode, and the capture that reads them) */
+                                    depth-scale error and field of view redrawn per episode, and the capture that reads them);
+                                    lsim_elevation_map (a robot-centred height grid per env, fused from a sensor's depth rows and the robot's pose) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1295,6 +1296,83 @@ int lsim_sensor_instrument(const lsim_sensor_instrument_t* si, void* stream);
  *   is lsim_sensor_capture's shift.
  * LSIM_E_INVALID, checked on the host before any launch: everything lsim_sensor_capture refuses; inst NULL or not 16-byte aligned. */
 int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, void* stream);
+
+/* ---- elevation map: a robot-centred 2.5-D height grid per env, filled from the depth rows of a sensor's captures and the robot's own pose,
+ * and sampled at the points of the height scan.  ONE launch under the rules of lsim_sensor_capture (caller's stream, no host
+ * synchronisation, raw pointers only).  Enqueued BEHIND a capture on the same stream, with its tick, period, stagger, flags and
+ * episode_length, it visits the same envs, inserts for the same due set and reads the depth rows that capture just wrote.  It reads the
+ * simulator's root_states and writes only its own arrays.  All arithmetic in fp32 (a compiler may contract a product and a sum).
+ *
+ * State, per env e.  G = size, one of 16, 32, 64; res the cell size in metres; rinv = 1.0f / res, formed ONCE on the host (correctly
+ *   rounded) and multiplied with: the absolute cell of a world point (x, y) is (ix, iy) = (floor(x * rinv), floor(y * rinv)) -- a true floor,
+ *   coordinates are negative inside the terrain border.  (For res a power of two x * rinv is x / res exactly.)
+ *   The grid is WORLD-ALIGNED and TOROIDAL: absolute cell (ix, iy) lives in slot s = (ix & (G-1)) * G + (iy & (G-1)) (two's complement), and
+ *   nothing is ever shifted or copied when the robot moves.
+ *     height[e][s] f32;   stamp[e][s] i32: tick & 0x7FFFFFFF of the last write (never negative, whatever the tick), -1 never;   cell[e][s] u32: ((ix + 32768) << 16) | (iy + 32768)
+ *   A slot KNOWS absolute cell (ix, iy) when stamp >= 0 and cell equals that cell's packed word; a slot left over from a cell that has
+ *   scrolled out of the window no longer matches and reads as unknown, without a clearing pass.  A point whose floor(x * rinv) or
+ *   floor(y * rinv) is not inside (-32768, 32768) is skipped, when inserting and when looking up.
+ * Which envs.  Env e is visited when e % env_stride == 0; fill and due are lsim_sensor_capture's, on the same fields.
+ *     bad pose: a non-finite component of root_states[e][0:7] or assumed_mount[e][0:7].  Such an env inserts nothing (its three arrays are
+ *         still cleared by fill), its scan row is 0 with known 0, and it adds 1 to state[0] (int64, cumulative) per launch.
+ *     fill: all G * G stamps of the env become -1 first (a new episode starts with an empty map).
+ *     not due: height, stamp and cell of the env are not written.      Every visited env, due or not, has its scan row rewritten.
+ * Insert (due, pose finite).  (p, q) = root_states[e][0:3], [3:7];  (mpos, mq) = assumed_mount[e][0:3], [3:7];  R as in lsim_raycast.  Ray r:
+ *     d = a * depth[e * depth_stride + r] + b;      t = inv_scale ? d * inv_scale[r] : d
+ *     valid:  |d| <= FLT_MAX  and  t_lo < t  and  t < t_hi  and  (labels == NULL or labels[e * label_stride + r] == 1, terrain)
+ *     v = dirs[r] * t;   P = p + R(q) (mpos + R(mq) v);   P not finite: skipped
+ *     (ix, iy) = the cell of (P.x, P.y);   (cx, cy) = the cell of (p.x, p.y), each first clamped to [-40000, 40000] as a float
+ *     kept:  -G/2 <= ix - cx < G/2  and  -G/2 <= iy - cy < G/2                    (the window: G cells, so no two kept cells share a slot)
+ *   Within one capture a cell takes the MAXIMUM P.z of its kept points (the upper surface, what a foot meets), built in LDS with an unsigned
+ *   integer atomic max on key(z) = bits(z) ^ (bits(z) >> 31 ? 0xFFFFFFFF : 0x80000000), which orders as the floats do (-0 below +0); key 0 is
+ *   no finite float's and marks an untouched slot.  The result does not depend on ray order: reproducible bit for bit.
+ *   Behind a barrier every touched slot is overwritten -- the newest capture wins over older ones:
+ *     height[e][s] = that maximum;   stamp[e][s] = (int32)(tick & 0x7FFFFFFF);   cell[e][s] = the packed word.
+ * Scan (every visited env with a finite pose, behind a barrier after the insert).  Point j of pts [P, 2], in the base-yaw frame:
+ *     n = 1 / sqrt(q.z^2 + q.w^2)  (root and quotient correctly rounded);   qy = (0, 0, q.z n, q.w n);   w = p.xy + (R(qy) (pts[j], 0)).xy
+ *   -- LSIM_RAYCAST_FRAME_YAW's frame, the reference's quat_apply_yaw.  If the slot of w's cell knows that cell:
+ *     scan[e][j] = height,  known[e][j] = 1;      otherwise  scan[e][j] = p.z - unknown_drop,  known[e][j] = 0
+ *   (also when w is not finite, q.z = q.w = 0, or its cell is out of range).  No NaN is ever written.
+ * `assumed_mount` is a pointer of its own: pointed at a sensor's NOMINAL mount while the capture reads a jittered one, the map is wrong in
+ *   the way a robot's is.  NOT BUILT: averaging or a variance per cell, overhangs, odometry drift, latency compensation of the pose. */
+typedef struct lsim_elevation_map {
+    const float* root_states;         /* [N,13] simulator buffer, read only */
+    const float* assumed_mount;       /* [N,7] the mount pose the map believes in: position, quaternion xyzw */
+    const float* dirs;                /* [R,3] the sensor's ray directions */
+    const float* inv_scale;           /* [R] 1 / the sensor's scale, or NULL: 1 */
+    const float* depth;               /* row e starts at depth + e * depth_stride and holds R values */
+    const uint8_t* labels;            /* [N,label_stride] the capture's labels, or NULL */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    const float* pts;                 /* [P,2] scan points in the base-yaw frame */
+    float* height;                    /* [N,G,G] */
+    int32_t* stamp;                   /* [N,G,G], -1 from the caller at creation */
+    uint32_t* cell;                   /* [N,G,G] */
+    float* scan;                      /* [N,scan_stride] */
+    uint8_t* known;                   /* [N,known_stride] */
+    void* state;                      /* 1 int64, 8-byte aligned, zeroed by the caller: [0] visits of envs with a non-finite pose */
+    int64_t tick;                     /* >= 0, by value: the capture's */
+    int64_t depth_stride;             /* floats between rows of depth: >= R */
+    int32_t num_envs, num_rays;       /* N >= 1, R in 1..LSIM_RAYCAST_MAX_RAYS */
+    int32_t env_stride;               /* >= 1 */
+    int32_t label_stride;             /* bytes between rows of labels: >= R (ignored when labels == NULL) */
+    int32_t num_points;               /* P in 1..LSIM_ELEVATION_MAP_MAX_POINTS */
+    int32_t scan_stride, known_stride;/* elements between rows: >= P */
+    int32_t size;                     /* G: 16, 32 or 64 */
+    int32_t period, stagger;          /* the capture's */
+    uint32_t flags;                   /* the capture's: 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+    float res;                        /* metres per cell: finite, > 0 */
+    float a, b;                       /* depth in metres = a * stored value + b: finite */
+    float t_lo, t_hi;                 /* 0 <= t_lo < t_hi: the ranges that are inserted */
+    float unknown_drop;               /* finite: an unknown scan point reads p.z - unknown_drop */
+} lsim_elevation_map_t;
+#define LSIM_ELEVATION_MAP_MAX_POINTS 256
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: em == NULL; root_states, assumed_mount,
+ * dirs, depth, pts, height, stamp, cell or scan NULL or not 4-byte aligned; inv_scale given and not 4-byte aligned; known or episode_length
+ * NULL, episode_length or state not 8-byte aligned (state NULL); size not 16, 32 or 64; res, a, b or unknown_drop not finite; res <= 0;
+ * t_lo < 0, t_lo >= t_hi (or either NaN); P outside 1..LSIM_ELEVATION_MAP_MAX_POINTS; R outside 1..LSIM_RAYCAST_MAX_RAYS; depth_stride < R;
+ * labels given with label_stride < R; scan_stride or known_stride < P; tick < 0; period < 1; stagger outside 0..1; env_stride < 1;
+ * num_envs < 1; a flag bit other than the sensor model's two; both of them set. */
+int lsim_elevation_map(const lsim_elevation_map_t* em, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

@@ -113,6 +113,7 @@ LsimRaycastPrim = STRUCTS["lsim_raycast_prim"]
 LsimSensorModel = STRUCTS["lsim_sensor_model_t"]
 LsimSensorMountJitter = STRUCTS["lsim_sensor_mount_jitter_t"]
 LsimSensorInstrument = STRUCTS["lsim_sensor_instrument_t"]
+LsimElevationMap = STRUCTS["lsim_elevation_map_t"]
 LsimDepthEncoder = STRUCTS["lsim_depth_encoder_t"]
 LsimDepthEncoderBwd = STRUCTS["lsim_depth_encoder_bwd_t"]
 

@@ -44,6 +44,14 @@ draws the instrument's own constants -- how many captures late it is, a factor o
 a field of view a little wider or narrower.  One small launch ahead of every capture rewrites the rows of `cam.instrument_rows()` of the envs
 just reset, on the device, and the capture is lsim_sensor_capture_inst, which reads them.  spec() records the ranges and from_spec()
 rebuilds them.  Without `instrument` nothing of this is created or launched and the capture is lsim_sensor_capture.
+
+Elevation map (`cam.attach_map(ElevationMap(size=32, resolution=0.0625, source="noisy"))`, lsim_elevation_map; needs a model): what a robot
+runs next to, or instead of, a learned terrain memory -- per env a robot-centred grid of heights, filled from the depth points of every
+capture with the robot's own pose, which remembers the ground under the trunk after the camera has moved on.  One launch behind every
+capture, same stream, tick and flags, inserts the envs just captured and resamples every env's map at the points of the height scan:
+`cam.map_scan()` is the live [N, P] tensor in the layout of LSIM_BUF_MEASURED_HEIGHTS, `cam.map_known()` says which points the map
+knows.  The map believes in the NOMINAL mount, so a jittered camera bends it as it would on a robot.  Without an attached map nothing of
+this is created or launched.
 """
 import ctypes
 import math
@@ -177,6 +185,61 @@ class InstrumentError:
                 f"depth_quad={self.depth_quad}, fov={self.fov})")
 
 
+class ElevationMap:
+    """A robot-centred height grid per env, fused on the device from a sensor's captures (lsim_elevation_map; include/lsim.h states every
+    formula).  `size`: cells per side, 16, 32 or 64; `resolution`: metres per cell (a power of two keeps the cell of a coordinate exact);
+    `source`: "noisy" -- the newest capture as the instrument reports it (the newest slot of the frame history, noise, holes and
+    calibration error included; with an InstrumentError too: lsim_sensor_capture_inst keeps the newest capture in the history's last slot
+    whatever the env's latency, so the combination is supported) -- or "clean" -- the sensor's `out` rows; `max_range`: rays that report
+    this range or more are not inserted (None: 0.98 * far, which drops the misses); `points` [P, 2], P <= 256: where the map is sampled,
+    in the base-yaw frame (None: the env's measured_points_x x measured_points_y in the order of LSIM_BUF_MEASURED_HEIGHTS);
+    `unknown_drop`: a point the map does not know reads the base height minus this (None: the robot's nominal base height,
+    rewards.base_height_target of the env's config -- flat ground under a standing robot; on a mixed-robot instance that is ONE height
+    for every robot, the first config's: pass the value wanted).
+    What attach_map refuses, because the launch cannot be right with it: a sensor with frame="yaw" (the launch places the points with the
+    base's full orientation); a see_robot sensor without labels=True (the robot's own legs would be inserted as ground); with "noisy", a
+    model whose dropped pixels cannot be told from a range (dropout > 0 with drop_value strictly inside the clip range)."""
+
+    def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None):
+        self.size, self.resolution, self.source = int(size), float(resolution), str(source)
+        self.max_range = None if max_range is None else float(max_range)
+        self.unknown_drop = None if unknown_drop is None else float(unknown_drop)
+        self.points = None if points is None else [[float(x), float(y)] for x, y in np.asarray(points, dtype=np.float64).reshape(-1, 2)]
+        if self.size not in (16, 32, 64) or not (math.isfinite(self.resolution) and self.resolution > 0.0):
+            raise ValueError(f"ElevationMap: size is 16, 32 or 64 and resolution finite and > 0, got {size}, {resolution}")
+        if self.source not in ("noisy", "clean"):
+            raise ValueError(f"ElevationMap: source is 'noisy' or 'clean', got {source!r}")
+        if self.max_range is not None and not (math.isfinite(self.max_range) and self.max_range > 0.0):
+            raise ValueError(f"ElevationMap: max_range is None or finite and > 0, got {max_range}")
+        if self.unknown_drop is not None and not math.isfinite(self.unknown_drop):
+            raise ValueError(f"ElevationMap: unknown_drop is None or finite, got {unknown_drop}")
+        if self.points is not None and not 1 <= len(self.points) <= abi.DEFINES["LSIM_ELEVATION_MAP_MAX_POINTS"]:
+            raise ValueError(f"ElevationMap: 1 to {abi.DEFINES['LSIM_ELEVATION_MAP_MAX_POINTS']} points, got {len(self.points)}")
+
+    def record(self):
+        """the plain dict spec() stores and ElevationMap(**record) reads"""
+        return {"size": self.size, "resolution": self.resolution, "source": self.source, "max_range": self.max_range, "points": self.points,
+                "unknown_drop": self.unknown_drop}
+
+    def __eq__(self, other):
+        return isinstance(other, ElevationMap) and self.record() == other.record()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"ElevationMap({', '.join(f'{k}={v!r}' for k, v in self.record().items() if k != 'points')}, points={'None' if self.points is None else len(self.points)})"
+
+
+def parse_elevation_map(text):
+    """ElevationMap of 'size=32,resolution=0.0625,source=noisy,max_range=3,unknown_drop=0.4' (any subset; '' or 'default': the defaults):
+    the text the tools take"""
+    kw = {}
+    for item in ([] if text in ("", "default") else text.split(",")):
+        k, v = item.split("=")
+        kw[k] = v if k == "source" else (int(v) if k == "size" else float(v))
+    return ElevationMap(**kw)
+
+
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
@@ -194,7 +257,10 @@ class RaySensor:
     With `mount_jitter=None` `mount` is `mount_nominal` and no such launch is made.
     `instrument` (an InstrumentError; needs a model): `instrument_rows()` is the live [N, 8] tensor of each env's own latency, noise gain,
     depth-scale error and field-of-view factor, which lsim_sensor_instrument rewrites ahead of every capture for the envs that start an
-    episode, and the capture is lsim_sensor_capture_inst.  With `instrument=None` there is no such tensor and no such launch."""
+    episode, and the capture is lsim_sensor_capture_inst.  With `instrument=None` there is no such tensor and no such launch.
+    `attach_map(m)` (an ElevationMap; needs a model): lsim_elevation_map behind every capture; `map_scan()` / `map_known()` are the live
+    [N, P] samples, `map_heights()` a window-ordered copy for people and tools, `map_state()` the three raw arrays.  Without it nothing
+    of this is allocated or launched."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
                  see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
@@ -250,6 +316,7 @@ class RaySensor:
         self._rc = rc
         self._labels = None
         self._encoder = self._latent = self._memory = self._memory_h = self._memory_rows = None
+        self.map = self._em = self._map = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
@@ -448,6 +515,8 @@ class RaySensor:
                 lib.check(self._api.lsim_sensor_capture_inst(ctypes.byref(self._sm), self._inst.data_ptr(), self._stream(stream)), what="lsim_sensor_capture_inst")
             else:
                 lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
+            if self._em is not None:            # directly behind the capture: the rows it just wrote, its due set
+                self._launch_map(self.tick, int(flags), stream)
             if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
                 self._encoder.encode_device(self, self.tick, int(flags), stream)
                 if self._memory is not None:    # every env, every update: z is held between captures, the memory still ticks
@@ -480,6 +549,128 @@ class RaySensor:
         if self.tick >= 0:
             enc.encode_device(self, self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
         return enc
+
+    def attach_map(self, m):
+        """from now on every update() / refresh() is followed by lsim_elevation_map on the same stream with the same tick and flags (`m`: an
+        ElevationMap, or None: detach and free).  Inserts every env once now, from the present rows, when the sensor has captured before.
+        "noisy" reads the newest slot of the frame history with (a, b) = (1 / gain, offset), "clean" the `out` rows with (1, 0); the
+        labels are passed when the sensor has them (only terrain is ground); the assumed mount is `mount_nominal`.
+        Which ranges are points: above `near` and below max_range (None: 0.98 far) -- and for "noisy", whose values the model clamps to
+        [clip_lo, clip_hi], misses and dropped pixels included, also strictly inside that range for every ray: a value AT a clip limit is
+        a clamped one and never a point (so a hit beyond clip_hi is dropped, not inserted at clip_hi).
+        Refused (ElevationMap's docstring): frame="yaw", see_robot without labels, a drop_value inside the clip range."""
+        if m is None:
+            self.map = self._em = self._map = None
+            return None
+        if not isinstance(m, ElevationMap):
+            raise TypeError(f"attach_map: expected an ElevationMap or None, got {type(m).__name__}")
+        if self.model is None:
+            raise ValueError("attach_map needs a model (SensorModel): the tick, the period and the episode lengths that say who captured are the model's")
+        if not hasattr(self._api, "lsim_elevation_map"):
+            raise lib.LsimError("the loaded library has no lsim_elevation_map: rebuild it (there is no torch fall-back for the elevation map)")
+        if self.frame != "base":
+            raise ValueError(f"attach_map: the sensor's frame is {self.frame!r}; lsim_elevation_map places the points with the base's full orientation, "
+                             "so only a frame='base' sensor can feed a map")
+        if self.see_robot and self._labels is None:
+            raise ValueError("attach_map: a see_robot sensor needs labels=True, or the robot's own legs are inserted as ground")
+        env, dev, N, G = self.env, self._out.device, int(self.env.num_envs), m.size
+        if m.points is None:
+            t = env.cfg.terrain
+            pts = [[float(x), float(y)] for x in t.measured_points_x for y in t.measured_points_y]
+        else:
+            pts = m.points
+        if not 1 <= len(pts) <= abi.DEFINES["LSIM_ELEVATION_MAP_MAX_POINTS"]:
+            raise ValueError(f"attach_map: 1 to {abi.DEFINES['LSIM_ELEVATION_MAP_MAX_POINTS']} scan points, got {len(pts)}")
+        P = len(pts)
+        mp = {"pts": torch.tensor(pts, dtype=torch.float32, device=dev).reshape(P, 2).contiguous(),
+              "height": torch.zeros((N, G, G), dtype=torch.float32, device=dev), "stamp": torch.full((N, G, G), -1, dtype=torch.int32, device=dev),
+              "cell": torch.zeros((N, G, G), dtype=torch.int32, device=dev), "scan": torch.zeros((N, P), dtype=torch.float32, device=dev),
+              "known": torch.zeros((N, P), dtype=torch.uint8, device=dev), "state": torch.zeros(1, dtype=torch.int64, device=dev),
+              "inv_scale": None if self.scale is None else (1.0 / self.scale).contiguous()}
+        em = abi.LsimElevationMap()
+        em.root_states, em.assumed_mount, em.dirs = env.root_states.data_ptr(), self.mount_nominal.data_ptr(), self.dirs.data_ptr()
+        em.inv_scale = None if mp["inv_scale"] is None else mp["inv_scale"].data_ptr()
+        sm, stride = self._sm, self._out.shape[1]
+        if m.source == "clean":
+            em.depth, em.depth_stride, em.a, em.b = self._out.data_ptr(), stride, 1.0, 0.0
+        else:
+            K = self.model.latency + self.model.frames
+            em.depth, em.depth_stride = self._hist.data_ptr() + (K - 1) * stride * 4, K * stride
+            em.a, em.b = 1.0 / float(sm.gain), float(sm.offset)
+        if self._labels is not None:
+            em.labels, em.label_stride = self._labels.data_ptr(), self._labels.shape[1]
+        em.episode_length, em.pts = sm.episode_length, mp["pts"].data_ptr()
+        em.height, em.stamp, em.cell = mp["height"].data_ptr(), mp["stamp"].data_ptr(), mp["cell"].data_ptr()
+        em.scan, em.known, em.state = mp["scan"].data_ptr(), mp["known"].data_ptr(), mp["state"].data_ptr()
+        em.num_envs, em.num_rays, em.env_stride, em.num_points, em.scan_stride, em.known_stride, em.size = N, self.num_rays, self.env_stride, P, P, P, G
+        em.period, em.stagger = sm.period, sm.stagger
+        em.res = m.resolution
+        # the window of ranges t = d * inv_scale[r] that are points.  d_lo, d_hi bound the stored value d; a ray's t then lies strictly
+        # inside for EVERY ray when t_lo = d_lo * max(inv_scale) and t_hi = d_hi * min(inv_scale)
+        widest, narrowest = (1.0, 1.0) if mp["inv_scale"] is None else (float(mp["inv_scale"].max()), float(mp["inv_scale"].min()))
+        d_lo, d_hi = self.near, float("inf")
+        if m.source == "noisy":
+            # the model clamps every value -- misses, hits beyond the range and dropped pixels alike -- to [clip_lo, clip_hi], and "noisy"
+            # reads it back through (1 / gain, offset) with a rounding of 2-3 ulp of offset and far: 2^-20 of that magnitude lies well
+            # above it.  A value within that margin of a clip limit is a clamped one, never a point
+            clip_lo, clip_hi = float(sm.clip_lo), float(sm.clip_hi)
+            drop = min(max(float(sm.drop_value), clip_lo), clip_hi)
+            if float(sm.p_drop) > 0.0 and clip_lo < drop < clip_hi:
+                raise ValueError(f"attach_map: source='noisy' with dropout needs a drop_value at or beyond a clip limit; {drop} lies inside "
+                                 f"({clip_lo}, {clip_hi}) and a dropped pixel could not be told from a range")
+            margin = 2.0 ** -20 * max(self.far, abs(float(sm.offset)), abs(clip_hi))
+            d_lo, d_hi = max(self.near, clip_lo) + margin, clip_hi - margin
+        em.t_lo = d_lo * widest
+        em.t_hi = min(0.98 * self.far if m.max_range is None else m.max_range, d_hi * narrowest)
+        em.unknown_drop = float(env.cfg.rewards.base_height_target) if m.unknown_drop is None else m.unknown_drop
+        if not em.t_lo < em.t_hi:
+            raise ValueError(f"attach_map: no range is left between the nearest the sensor reports ({em.t_lo}) and max_range / the clip limit ({em.t_hi})")
+        self.map, self._em, self._map = m, em, mp
+        if self.tick >= 0:
+            self._launch_map(self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], None)
+        return m
+
+    def _launch_map(self, tick, flags, stream):
+        self._em.tick, self._em.flags = int(tick), int(flags)
+        lib.check(self._api.lsim_elevation_map(ctypes.byref(self._em), self._stream(stream)), what="lsim_elevation_map")
+
+    def _need_map(self):
+        if self._em is None:
+            raise ValueError("the sensor has no elevation map (attach_map)")
+        return self._map
+
+    def map_scan(self):
+        """live [N, P] tensor: the map's height at every scan point; where it knows none, the base height minus unknown_drop"""
+        return self._need_map()["scan"]
+
+    def map_known(self):
+        """live uint8 [N, P] tensor: 1 where map_scan() is a height the map holds"""
+        return self._need_map()["known"]
+
+    def map_state(self):
+        """the live raw arrays (height f32, stamp i32, cell: the u32 words held in an int32 tensor), each [N, G, G], toroidal (lsim.h)"""
+        mp = self._need_map()
+        return mp["height"], mp["stamp"], mp["cell"]
+
+    @property
+    def map_nonfinite(self):
+        """0-d device tensor: visits of envs whose pose was not finite (they insert nothing and scan zeros); must stay 0"""
+        return self._need_map()["state"][0]
+
+    def map_heights(self):
+        """[N, G, G] COPY in window order -- [e, i, j] is the cell (cx - G/2 + i, cy - G/2 + j) around env e's present position -- with NaN
+        where the map knows nothing.  For people and tools (tools/sensor_frames.py); nothing on a hot path reads it."""
+        mp, G, N = self._need_map(), self.map.size, int(self.env.num_envs)
+        rinv = float(np.float32(1.0 / float(np.float32(self.map.resolution))))
+        c = torch.floor(self.env.root_states[:, :2] * rinv).to(torch.int64).clamp(-40000, 40000)
+        off = torch.arange(G, device=c.device) - G // 2
+        ix, iy = c[:, 0:1] + off, c[:, 1:2] + off
+        idx = ((ix & (G - 1)) * G)[:, :, None] + (iy & (G - 1))[:, None, :]
+        take = lambda t: t.reshape(N, G * G).gather(1, idx.reshape(N, G * G)).reshape(N, G, G)
+        word = ((ix + 32768) << 16)[:, :, None] | (iy + 32768)[:, None, :]
+        inside = ((ix.abs() < 32768)[:, :, None] & (iy.abs() < 32768)[:, None, :])
+        known = (take(mp["stamp"]) >= 0) & ((take(mp["cell"]).to(torch.int64) & 0xFFFFFFFF) == word) & inside
+        return torch.where(known, take(mp["height"]), torch.full((), float("nan"), device=c.device))
 
     def attach_memory(self, mem):
         """from now on the encoder's launch of every update() / refresh() is followed by `mem`'s (learn.depth_memory.DepthMemory.step_device)
@@ -533,7 +724,8 @@ class RaySensor:
         dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
-        one there is no such key.  Likewise "instrument" holds an InstrumentError's record, and is absent without one."""
+        one there is no such key.  Likewise "instrument" holds an InstrumentError's record and "map" an attached ElevationMap's, each absent
+        without one."""
         out = {"kind": "rays"}
         if hasattr(self, "width") and hasattr(self, "height"):
             out.update(kind="camera", width=int(self.width), height=int(self.height))
@@ -562,6 +754,8 @@ class RaySensor:
             out["mount_jitter"] = self.mount_jitter.record()
         if self.instrument is not None:
             out["instrument"] = self.instrument.record()
+        if self.map is not None:
+            out["map"] = self.map.record()
         return out
 
     @property
@@ -608,11 +802,11 @@ def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mo
     return s
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec"):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
-    (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError."""
+    (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor)."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -636,6 +830,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
             raise ValueError(f"from_spec: instrument is 'spec', None or an InstrumentError, got {instrument!r}")
         i = spec.get("instrument")
         instrument = None if i is None else InstrumentError(**i)
+    if isinstance(elevation_map, str):
+        if elevation_map != "spec":
+            raise ValueError(f"from_spec: elevation_map is 'spec', None or an ElevationMap, got {elevation_map!r}")
+        r = spec.get("map")
+        elevation_map = None if r is None else ElevationMap(**r)
     kind = spec.get("kind", "rays")
     cls = DepthCamera if kind == "camera" else RaySensor
     sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
@@ -647,4 +846,6 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
                        mount_jitter=mount_jitter, instrument=instrument)
     if kind == "lidar":
         sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
+    if elevation_map is not None:
+        sensor.attach_map(elevation_map)
     return sensor

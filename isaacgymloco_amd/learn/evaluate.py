@@ -468,6 +468,7 @@ def parse_camera_instrument(text):
 
 
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
+MAP_METRICS = ("map_scan_error", "map_coverage")        # accepted when named and the sensor carries an elevation map; never a default
 
 
 def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, memory=None, memory_head=None):
@@ -477,9 +478,22 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
     dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
     metrics = list(metrics)
     for m in metrics:
-        if m not in VISION_METRICS:
-            raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error')")
+        if m not in VISION_METRICS + MAP_METRICS:
+            raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error', "
+                             f"with an elevation map also 'map_scan_error' and 'map_coverage')")
     scan = None
+    has_map = getattr(cam, "map", None) is not None
+    if "map_coverage" in metrics and not has_map:
+        metrics.remove("map_coverage")
+    if "map_scan_error" in metrics:         # needs the map, a privileged observation that holds the scan, and the scan's own points
+        try:
+            map_block = height_scan_block(env.cfg) if has_map else None
+        except ValueError:
+            map_block = None
+        if map_block is None or cam.map_scan().shape[1] != map_block[1]:
+            metrics.remove("map_scan_error")
+        else:
+            scan = map_block
     Lz = L - (memory.hidden if memory is not None else 0)       # the encoder's columns of the actor's depth segment
     for m, h_ in (("scan_error", head), ("memory_scan_error", memory_head if memory is not None else None)):
         if m in metrics:                # needs its head and a privileged observation that holds the scan: else dropped, not zero
@@ -524,6 +538,11 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
                 ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
             elif m == "scan_error":
                 ev.columns[:, k] = (head(live[:, :Lz]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
+            elif m == "map_scan_error":     # the map's scan in observation units, exactly as ph_build_obs turns measured_heights into the block
+                block = (env.root_states[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height)
+                ev.columns[:, k] = (block - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
+            elif m == "map_coverage":
+                ev.columns[:, k] = cam.map_known().to(torch.float32).mean(dim=1)
             else:
                 ev.columns[:, k] = (memory_head(live[:, Lz:]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
         env.step_device(actions)
@@ -547,6 +566,10 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped.
     A policy trained with a depth memory (the runner's alg.memory, or the checkpoint's vision["memory"] record) gets the memory rebuilt and
     attached behind the encoder and reads cam.memory_rows(), [z | h]; "memory_scan_error" is the memory head's error on h.
+    With an elevation map on the sensor (envs.sensors.ElevationMap, cam.attach_map) two more metrics are accepted when NAMED (they are in
+    no default): "map_scan_error" = the mean square, over the scan points, of the map's scan in observation units
+    (clip(base z - 0.5 - h, -1, 1) * obs_scales.height_measurements, as csrc/ls_post.h builds the block) minus the height scan of the
+    privileged observation -- the same units as scan_error and memory_scan_error -- and "map_coverage" = the mean of cam.map_known().
     `camera_jitter` (a vision policy only): the per-episode mount error of the camera (envs.sensors.MountJitter) -- "trained": what the
     checkpoint's record of the sensor says (a runner's camera stays as it is); None: the nominal mount; a MountJitter: that one, to
     measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's
@@ -654,8 +677,8 @@ def parse_args(argv=None):
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
     a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
-    if any(m not in VISION_METRICS for m in a.vision_metrics):
-        ap.error(f"--vision-metrics: 'depth_influence', 'scan_error' and / or 'memory_scan_error', got {a.vision_metrics}")
+    if any(m not in VISION_METRICS + MAP_METRICS for m in a.vision_metrics):
+        ap.error(f"--vision-metrics: 'depth_influence', 'scan_error', 'memory_scan_error', 'map_scan_error' and / or 'map_coverage', got {a.vision_metrics}")
     try:
         group_mask(a.group_by)
     except ValueError as exc:

@@ -1,0 +1,365 @@
+"""CPU: the elevation map through the Python surface (envs/sensors.py ElevationMap, RaySensor.attach_map, map_scan / map_known /
+map_heights / map_state, spec() / from_spec(), evaluate's map_scan_error and map_coverage) on the emulated LeggedRobot, every launch
+through the CPU builds of the kernel sources.  The launch itself is held to its reference in tests/test_elevation_map.py."""
+import numpy as np
+import pytest
+import torch
+
+import elevation_map_emu_binding as EB
+import elevation_map_reference as ER
+import eval_columns_emu_binding as CB
+import sensor_model_reference as SR
+from helpers import C
+from isaacgymloco_amd.envs import sensors
+from isaacgymloco_amd.learn.depth_encoder import DepthEncoder
+
+FAR = 5.0
+MODEL = dict(period=3, stagger=True, latency=1, frames=2, clip=(0.0, FAR))       # clean depth lies in [0, far]: the model is the identity, exactly
+ENC = dict(c1=4, k1=3, s1=2, c2=8, k2=3, s2=1, latent_dim=10)
+SPEC_KEYS = ["kind", "width", "height", "dirs", "scale", "near", "far", "env_stride", "see_robot", "labels", "frame", "ignore_bodies", "model", "mount"]
+
+
+def bits(t):
+    a = np.ascontiguousarray(t.numpy() if isinstance(t, torch.Tensor) else t)
+    return a.view(np.uint8 if a.dtype.itemsize == 1 else np.int32)
+
+
+def _env(N=8, seed=3, terrain="stairs"):
+    from emu_env import EmuLeggedRobot
+    from isaacgymloco_amd.learn.evaluate import play_cfg
+    cfg = play_cfg(C.aliengo_cfg())
+    cfg.env.num_envs = N
+    cfg.terrain.num_rows, cfg.terrain.num_cols = 2, 2
+    if terrain == "plane":
+        cfg.terrain.mesh_type = "plane"
+    else:
+        cfg.terrain.terrain_proportions = {"stairs": [0.0, 0.0, 0.0, 0.0, 0.5, 0.5], "slope": [0.0, 0.0, 1.0, 0.0]}[terrain]
+    env = EmuLeggedRobot(cfg, seed=seed)
+    env.reset()
+    return env
+
+
+def _camera(env, api, w=8, h=6, **kw):
+    kw.setdefault("model", sensors.SensorModel(**MODEL))
+    return sensors.depth_camera(env, w, h, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=FAR, api=api, **kw)
+
+
+def _logged(api, names):
+    """the api with the calls of `names` appended to a list, in order"""
+    log = []
+    for n in names:
+        def call(*a, _f=getattr(api, n), _n=n):
+            log.append(_n)
+            return _f(*a)
+        setattr(api, n, call)
+    return log
+
+
+def test_the_map_launches_right_behind_the_capture_once_per_update_for_the_captures_due_set():
+    N = 8
+    env, api = _env(N), EB.EmuApi()
+    log = _logged(api, ("lsim_sensor_capture", "lsim_elevation_map", "lsim_depth_encode"))
+    cam = _camera(env, api, 16, 12)
+    assert cam.attach_map(sensors.ElevationMap(size=32, source="clean")) is cam.map and log == []      # never captured: nothing to insert yet
+    cam.attach_encoder(DepthEncoder(12, 16, 2, **ENC))
+    env.add_sensor("depth", cam)
+    assert log == ["lsim_sensor_capture", "lsim_elevation_map", "lsim_depth_encode"]
+    h, st, ce = cam.map_state()
+    assert (st >= 0).any(dim=2).any(dim=1).all(), "add_sensor's refresh inserted every env"
+    g = torch.Generator().manual_seed(0)
+    env.step_device(torch.randn(N, 12, generator=g) * 0.3)          # tick 0 once more: add_sensor's refresh stamped with it
+    for step in range(5):
+        before = [t.clone() for t in cam.map_state()]
+        scan_b, tick = cam.map_scan().clone(), env.common_step_counter
+        env.step_device(torch.randn(N, 12, generator=g) * 0.3)
+        due = SR.due_sets(N, 1, tick, 3, 1, 0, env.episode_length_buf.numpy())[0]
+        assert cam.tick == tick and cam._em.tick == tick
+        wrote = (cam.map_state()[1] == tick).any(dim=2).any(dim=1).numpy()
+        np.testing.assert_array_equal(wrote, due, err_msg=f"step {step}")
+        for now, was in zip(cam.map_state(), before):
+            np.testing.assert_array_equal(bits(now)[~due], bits(was)[~due])
+        assert (bits(cam.map_scan()) != bits(scan_b)).any(axis=1).all(), "every env's scan follows its pose"
+    assert log == ["lsim_sensor_capture", "lsim_elevation_map", "lsim_depth_encode"] * 7
+    env.reset_idx([1])
+    assert log[-3:] == ["lsim_sensor_capture", "lsim_elevation_map", "lsim_depth_encode"] and len(log) == 24
+    st = cam.map_state()[1]
+    assert set(np.unique(st[1].numpy())) <= {-1, env.common_step_counter}, "a reset env's map holds its new episode only"
+    assert int(cam.map_nonfinite) == 0 and bool(torch.isfinite(cam.map_scan()).all())
+
+
+def test_without_a_map_nothing_is_allocated_or_launched_and_the_spec_is_the_one_of_before():
+    env, api = _env(), EB.EmuApi()
+    cam = env.add_sensor("depth", _camera(env, api))
+    for _ in range(3):
+        env.step_device(torch.zeros(8, 12))
+    assert api.calls["lsim_elevation_map"] == 0 and api.calls["lsim_sensor_capture"] == 4
+    assert cam.map is None and cam._em is None and cam._map is None and list(cam.spec()) == SPEC_KEYS
+    for getter in (cam.map_scan, cam.map_known, cam.map_heights, cam.map_state):
+        with pytest.raises(ValueError, match="attach_map"):
+            getter()
+    m = cam.attach_map(sensors.ElevationMap(size=16))
+    assert api.calls["lsim_elevation_map"] == 1 and cam.map is m, "a sensor that has captured inserts every env at once"
+    assert cam.attach_map(None) is None and cam._em is None and cam._map is None and list(cam.spec()) == SPEC_KEYS
+    env.step_device(torch.zeros(8, 12))
+    assert api.calls["lsim_elevation_map"] == 1
+
+
+def test_values_refusals_and_the_struct_the_launch_gets():
+    m = sensors.ElevationMap()
+    assert (m.size, m.resolution, m.source, m.max_range, m.points, m.unknown_drop) == (32, 0.0625, "noisy", None, None, None)
+    assert sensors.ElevationMap(**m.record()) == m and sensors.ElevationMap(size=16) != m
+    for bad in (dict(size=24), dict(resolution=0.0), dict(resolution=float("nan")), dict(source="raw"), dict(max_range=-1.0), dict(unknown_drop=float("inf")),
+                dict(points=np.zeros((257, 2))), dict(points=np.zeros((0, 2)))):
+        with pytest.raises(ValueError):
+            sensors.ElevationMap(**bad)
+    env, api = _env(), EB.EmuApi()
+    with pytest.raises(ValueError, match="model"):
+        _camera(env, api, model=None).attach_map(m)
+    with pytest.raises(TypeError):
+        _camera(env, api).attach_map({"size": 32})
+    import sensor_instrument_emu_binding as IB
+    from isaacgymloco_amd import lib
+    with pytest.raises(lib.LsimError, match="lsim_elevation_map"):
+        _camera(env, IB.EmuApi()).attach_map(m)            # a library from before the entry point
+    with pytest.raises(ValueError, match="max_range"):
+        _camera(env, api).attach_map(sensors.ElevationMap(max_range=0.01))
+    # "noisy": the newest slot of the history through the inverse of the normalisation; "clean": the out rows; the nominal mount; the labels
+    model = sensors.SensorModel(period=2, latency=1, frames=2, normalise=True)
+    cam = _camera(env, api, model=model, see_robot=True, labels=True, mount_jitter=sensors.MountJitter(rot_deg=(0, 5, 0)))
+    cam.attach_map(m)
+    em, stride = cam._em, cam._out.shape[1]
+    assert em.depth == cam._hist.data_ptr() + 2 * stride * 4 and em.depth_stride == 3 * stride
+    assert em.a == np.float32(1.0 / cam._sm.gain) and em.b == np.float32(cam._sm.offset) == np.float32((0.05 + FAR) / 2)
+    assert em.assumed_mount == cam.mount_nominal.data_ptr() != cam.mount.data_ptr()
+    assert em.labels == cam._labels.data_ptr() and em.label_stride == cam._labels.shape[1] and em.episode_length == cam._sm.episode_length
+    assert (em.period, em.stagger, em.size, em.num_points, em.num_rays) == (2, 0, 32, 187, 48) and em.t_hi == np.float32(0.98 * FAR)
+    assert em.unknown_drop == np.float32(env.cfg.rewards.base_height_target) and em.t_lo >= np.float32(0.05 / float(cam.scale.min()))
+    t = env.cfg.terrain
+    want = [[x, y] for x in t.measured_points_x for y in t.measured_points_y]
+    np.testing.assert_array_equal(cam._map["pts"].numpy(), np.array(want, np.float32))
+    cam.attach_map(sensors.ElevationMap(source="clean", points=[[0.0, 0.0], [0.5, 0.0]], unknown_drop=0.3, max_range=3.0))
+    em = cam._em
+    assert (em.depth, em.depth_stride, em.a, em.b, em.num_points, em.t_hi) == (cam._out.data_ptr(), stride, 1.0, 0.0, 2, 3.0)
+    assert em.unknown_drop == np.float32(0.3)
+
+
+def test_noisy_with_an_identity_model_is_clean_bit_for_bit_also_under_an_instrument_error():
+    """the newest capture lies in the last slot of the history whatever the latency (lsim.h, lsim_sensor_capture_inst): `noisy` with a
+    model that changes nothing, and an InstrumentError whose only error is the latency, builds the map `clean` builds"""
+    env, api = _env(), EB.EmuApi()
+    inst = sensors.InstrumentError(latency=(0, 1))
+    a = _camera(env, api, instrument=inst)
+    b = _camera(env, api)
+    a.attach_map(sensors.ElevationMap(size=32, source="noisy"))
+    b.attach_map(sensors.ElevationMap(size=32, source="clean"))
+    env.add_sensor("a", a)
+    env.add_sensor("b", b)
+    for _ in range(4):
+        env.step_device(torch.zeros(8, 12))
+    assert api.calls["lsim_sensor_capture_inst"] == 5 and api.calls["lsim_elevation_map"] == 10
+    assert set(a.instrument_rows()[:, 0].tolist()) == {0.0, 1.0}
+    for x, y in zip(a.map_state() + (a.map_scan(), a.map_known()), b.map_state() + (b.map_scan(), b.map_known())):
+        np.testing.assert_array_equal(bits(x), bits(y))
+    assert bool((a.map_state()[1] >= 0).any())
+
+
+def _drive(env, cam, poses, tick):
+    """the sensor by hand: the root poses written where the launches read them, one update on `tick`"""
+    env.root_states[:, :7] = torch.as_tensor(poses, dtype=torch.float32)
+    env.episode_length_buf[:] = 1
+    cam.update(tick=tick)
+
+
+def test_on_a_plane_every_known_value_is_the_plane_and_coverage_grows_to_the_cameras_footprint():
+    N = 4
+    env, api = _env(N, terrain="plane"), EB.EmuApi()
+    cam = _camera(env, api, 32, 24, model=sensors.SensorModel(clip=(0.0, FAR)))
+    cam.attach_map(sensors.ElevationMap(size=32, source="clean"))
+    poses = np.zeros((N, 7), np.float32)
+    poses[:, 6], poses[:, 2] = 1.0, 0.45
+    poses[:, 0], poses[:, 1] = [0.03, -7.5, 12.01, 190.0], [0.02, 3.3, -4.0, -190.0]
+    covered = []
+    for k in range(22):
+        _drive(env, cam, poses, k)
+        known, scan = cam.map_known().numpy().astype(bool), cam.map_scan().numpy()
+        # one EPS is the map's: its fp32 point against the float64 point of the stored depth.  The stored depth is fp32 work too: the
+        # capture forms o = p + R(q) mpos and d = R(q) R(mq) dirs[r] by the very chain of rotations and sums that EPS counts, and its
+        # t (one division at the ray's own magnitude, within the 120 L term) puts o + t d within one more EPS of the plane
+        tol = 2.0 * np.array([ER.eps(poses[e, :3], (0.3, 0.0, 0.05), FAR) for e in range(N)])
+        assert (np.abs(scan)[known] <= np.broadcast_to(tol[:, None], known.shape)[known]).all(), f"tick {k}: a known value is off the plane"
+        np.testing.assert_array_equal(scan[~known], np.broadcast_to((poses[:, 2:3] - np.float32(0.43)), scan.shape)[~known])
+        covered.append(known.sum(axis=1))
+        poses[:, 0] += np.float32(0.0625)
+    covered = np.array(covered)
+    assert (np.diff(covered, axis=0) >= 0).all() and (covered[-1] > covered[0] + 40).all(), "the map remembers what the camera has passed over"
+    # the lowest image row meets the ground 0.53 m ahead of the base (camera 0.5 m up, 65.4 degrees down, 0.3 m forward) and the image is
+    # 1.3 m wide there: after 21 cells (1.31 m) forward every scan point from -0.7 m to 0.5 m, |y| <= 0.3 m, has been swept
+    pts = cam._map["pts"].numpy()
+    inside = (pts[:, 0] >= -0.7 - 1e-6) & (pts[:, 0] <= 0.5 + 1e-6) & (np.abs(pts[:, 1]) <= 0.3 + 1e-6)
+    assert inside.sum() == 13 * 7 and cam.map_known().numpy()[:, inside].all(), "coverage is 1 inside the camera's footprint"
+    hts = cam.map_heights().numpy()
+    assert hts.shape == (N, 32, 32) and np.isnan(hts).any() and (np.abs(hts[~np.isnan(hts)]) <= tol.max()).all()
+    assert (~np.isnan(hts)).sum() == int((cam.map_state()[1] >= 0).sum()), "after 1.3 m straight ahead every slot written is still in the window"
+    assert api.calls["lsim_elevation_map"] == 22 and int(cam.map_nonfinite) == 0
+
+
+def test_a_clipping_model_with_dropout_and_misses_puts_no_phantom_point_into_a_noisy_map():
+    """SensorModel(clip=(0.1, 3.0), normalise=True, dropout) on a 5 m camera stores a dropped pixel as 0.1 m, and every miss and every hit
+    beyond 3 m as 3.0 m.  None of them is a point: on a plane every cell the map holds lies on the plane (a phantom would hang at the
+    camera's height 10 cm ahead of the lens, or 3 m out along a ray that met the ground farther away or not at all)"""
+    N = 4
+    env, api = _env(N, terrain="plane"), EB.EmuApi()
+    model = sensors.SensorModel(clip=(0.1, 3.0), normalise=True, dropout=0.3, latency=1, frames=2)
+    cam = _camera(env, api, 32, 24, model=model)
+    cam.attach_map(sensors.ElevationMap(size=64, resolution=0.125, source="noisy"))       # a window of +-4 m: 3 m out is inside it
+    em, inv = cam._em, 1.0 / cam.scale.numpy()
+    assert em.t_lo > np.float32(0.1 * inv.max()) and em.t_hi < np.float32(3.0 * inv.min()) and em.t_lo < em.t_hi
+    poses = np.zeros((N, 7), np.float32)
+    poses[:, 6], poses[:, 2] = 1.0, 0.45
+    poses[:, 0], poses[:, 1] = [0.03, -7.5, 12.01, 60.0], [0.02, 3.3, -4.0, -60.0]
+    for k in range(3):
+        _drive(env, cam, poses, k)
+        poses[:, 0] += np.float32(0.125)
+    newest = cam._hist[:, -1, :cam.num_rays].numpy() / np.float32(cam._sm.gain) + np.float32(cam._sm.offset)
+    clean = cam.out.numpy()
+    assert (np.abs(newest - 0.1) < 1e-6).mean() > 0.1, "the scene has dropped pixels"
+    assert (clean > 4.9 * cam.scale.numpy()).mean() > 0.1 and ((clean > 3.0) & (clean < 4.9 * cam.scale.numpy())).any(), "and misses, and hits beyond 3 m"
+    h, st, _ = cam.map_state()
+    held = (st >= 0).numpy()
+    tol = 2.0 * ER.eps(poses[:, :3].max(axis=0), (0.3, 0.0, 0.05), FAR) + 4.0 * ER.U * FAR          # the plane test's, and the normalisation there and back
+    assert held.sum() > N * 100 and (np.abs(h.numpy()[held]) <= tol).all(), float(np.abs(h.numpy()[held]).max())
+    # a drop_value the window cannot exclude is refused
+    with pytest.raises(ValueError, match="drop_value"):
+        _camera(env, api, model=sensors.SensorModel(clip=(0.1, 3.0), dropout=0.1, drop_value=1.0)).attach_map(sensors.ElevationMap())
+    _camera(env, api, model=sensors.SensorModel(clip=(0.1, 3.0), dropout=0.0, drop_value=1.0)).attach_map(sensors.ElevationMap())
+    _camera(env, api, model=sensors.SensorModel(clip=(0.1, 3.0), dropout=0.1, drop_value=1.0)).attach_map(sensors.ElevationMap(source="clean"))
+
+
+def test_a_yaw_frame_sensor_and_a_see_robot_sensor_without_labels_are_refused():
+    env, api = _env(), EB.EmuApi()
+    with pytest.raises(ValueError, match="frame"):
+        _camera(env, api, frame="yaw").attach_map(sensors.ElevationMap())
+    with pytest.raises(ValueError, match="labels"):
+        _camera(env, api, see_robot=True).attach_map(sensors.ElevationMap())
+    cam = _camera(env, api, see_robot=True, labels=True)
+    assert cam.attach_map(sensors.ElevationMap()) is cam.map and cam._em.labels == cam._labels.data_ptr()
+    assert api.calls["lsim_elevation_map"] == 0
+
+
+def _truth(env, xy):
+    """the terrain surface at world points [.., 2]: the height grid's vertices, bilinear (a smooth slope has no displaced vertex)"""
+    t = env.cfg.terrain
+    g = env.terrain.heightsamples.astype(np.float64) * t.vertical_scale
+    u = (np.asarray(xy, np.float64) + t.border_size) / t.horizontal_scale
+    i = np.clip(np.floor(u).astype(int), 0, np.array(g.shape) - 2)
+    f = u - i
+    a, b = i[..., 0], i[..., 1]
+    return (g[a, b] * (1 - f[..., 0]) * (1 - f[..., 1]) + g[a + 1, b] * f[..., 0] * (1 - f[..., 1]) + g[a, b + 1] * (1 - f[..., 0]) * f[..., 1] +
+            g[a + 1, b + 1] * f[..., 0] * f[..., 1])
+
+
+def test_a_jittered_mount_with_the_nominal_one_assumed_bends_the_map_on_a_slope():
+    N = 8
+    env, api = _env(N, terrain="slope"), EB.EmuApi()
+    model = sensors.SensorModel(clip=(0.0, FAR))
+    straight = _camera(env, api, 32, 24, model=model)
+    bent = _camera(env, api, 32, 24, model=model, mount_jitter=sensors.MountJitter(rot_deg=(0.0, 5.0, 0.0)))
+    for cam in (straight, bent):
+        cam.attach_map(sensors.ElevationMap(size=32, source="clean"))
+    origins = env.env_origins.numpy()
+    poses = np.zeros((N, 7), np.float32)
+    poses[:, 6] = 1.0
+    poses[:, 0], poses[:, 1] = origins[:, 0] + 2.2, origins[:, 1] + 0.3 * np.arange(N) / N
+    errs = {}
+    for name, cam in (("straight", straight), ("bent", bent)):
+        p = poses.copy()
+        for k in range(12):
+            p[:, 2] = _truth(env, p[:, :2]) + 0.45
+            env.root_states[:, :7] = torch.as_tensor(p)
+            env.episode_length_buf[:] = 0 if k == 0 else 1          # the first launch draws the mounts
+            cam.update(tick=k)
+            p[:, 0] += np.float32(0.0625)
+        p[:, 0] -= np.float32(0.0625)
+        known = cam.map_known().numpy().astype(bool)
+        world = p[:, None, :2] + cam._map["pts"].numpy()[None]       # identity orientation: the base-yaw frame is the world's
+        err = np.abs(cam.map_scan().numpy() - _truth(env, world))
+        assert known.sum() > N * 60
+        errs[name] = float(err[known].mean())
+    slope = np.abs(np.diff(_truth(env, np.stack((poses[:, 0] + np.array([[0.0], [1.0]]), np.broadcast_to(poses[:, 1], (2, N))), axis=-1)), axis=0))
+    assert slope.max() > 0.05, "the scene stands on a slope"
+    assert bool((bent.mount[:, 3:] != bent.mount_nominal[:, 3:]).any()) and bent._em.assumed_mount == bent.mount_nominal.data_ptr()
+    print(f"mean |map - terrain| at the known scan points: nominal mount {errs['straight']:.4f} m, pitch error up to 5 degrees {errs['bent']:.4f} m")
+    assert errs["bent"] > errs["straight"]
+
+
+def test_spec_and_from_spec_carry_the_maps_record():
+    env, api = _env(), EB.EmuApi()
+    m = sensors.ElevationMap(size=16, resolution=0.125, source="clean", max_range=3.0, points=[[0.0, 0.0], [0.25, -0.5]], unknown_drop=0.4)
+    cam = env.add_sensor("depth", _camera(env, api))
+    cam.attach_map(m)
+    spec = cam.spec()
+    assert list(spec) == SPEC_KEYS + ["map"] and spec["map"] == m.record()
+    import json
+    assert json.loads(json.dumps(spec)) == spec
+    back = sensors.from_spec(env, spec, api=api)
+    assert back.map == m and back.spec() == spec and back._em.size == 16 and back._em.res == 0.125 and back._em.num_points == 2
+    assert sensors.from_spec(env, spec, api=api, elevation_map=None).map is None
+    other = sensors.ElevationMap(size=64)
+    assert sensors.from_spec(env, spec, api=api, elevation_map=other).map == other
+    with pytest.raises(ValueError, match="elevation_map"):
+        sensors.from_spec(env, spec, api=api, elevation_map="yes")
+    default = sensors.from_spec(env, dict(spec, map=sensors.ElevationMap().record()), api=api)
+    assert default._em.num_points == 187 and default.map.points is None
+
+
+def _runner(env, cam):
+    from isaacgymloco_amd.learn import vision as V
+    from isaacgymloco_amd.learn.bench_train import train_cfg_dict
+    tc = train_cfg_dict("aliengo")
+    tc["runner"]["num_steps_per_env"] = 4
+    torch.manual_seed(7)
+    return V.VisionOnPolicyRunner(env, tc, sensor=cam, encoder=DepthEncoder(12, 16, 2, **ENC), device="cpu")
+
+
+def _evaluate(env, policy, steps=3, **kw):
+    from isaacgymloco_amd.learn.evaluate import Evaluator, evaluate
+    return evaluate(env, policy, steps, commands=(0.5, 0.0, 0.0), evaluator=Evaluator(env, api=CB.EmuApi()), **kw)
+
+
+def test_the_evaluate_columns_are_there_only_when_named_and_a_map_is_attached(tmp_path):
+    from isaacgymloco_amd.learn.evaluate import MAP_METRICS, VISION_METRICS, parse_args
+    assert VISION_METRICS == ("depth_influence", "scan_error", "memory_scan_error") and MAP_METRICS == ("map_scan_error", "map_coverage")
+    env, api = _env(terrain="plane"), EB.EmuApi()
+    cam = env.add_sensor("depth", _camera(env, api, 16, 12))
+    run = _runner(env, cam)
+    named = ("depth_influence", "map_scan_error", "map_coverage")
+    assert list(_evaluate(env, run, steps=1, vision_metrics=named).result()["total"]["columns"]) == ["depth_influence"], "named without a map: dropped"
+    cam.attach_map(sensors.ElevationMap(source="clean"))
+    assert list(_evaluate(env, run, steps=1).result()["total"]["columns"]) == ["depth_influence", "scan_error"], "with a map, not named: the defaults"
+    path = str(tmp_path / "vision.pt")
+    run.save(path)
+    assert torch.load(path, weights_only=False)["vision"]["sensor"]["map"] == cam.map.record()
+    # on the plane with "clean": the known points' block is the privileged observation's, and the rest is the fallback's distance
+    res = _evaluate(env, run, steps=3, vision_metrics=named).result()
+    cols = res["total"]["columns"]
+    assert list(cols) == list(named) and all(c["nonfinite"] == 0 for c in cols.values())
+    cov, err = cols["map_coverage"]["mean"], cols["map_scan_error"]["mean"]
+    scale = float(env.lcfg.obs_scale_height)
+    assert 0.0 < cov < 1.0 and err <= (1.0 - cov) * (scale * 0.5) ** 2 * 1.01, (cov, err)
+    from isaacgymloco_amd.learn.vision import height_scan_block
+    o, w = height_scan_block(env.cfg)
+    priv = env.get_privileged_observations()
+    block = (env.root_states[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * scale
+    known = cam.map_known().bool()
+    tol = scale * 2.0 * ER.eps(env.root_states[:, :3].abs().max().item() * np.ones(3), (0.3, 0.0, 0.05), FAR) + 2.0 * float(env.lcfg.noise_vec_height)
+    assert known.any() and float((block - priv[:, o:o + w])[known].abs().max()) <= tol
+    # a checkpoint's record rebuilds the map on a fresh env, and the command line takes the names
+    env2 = _env(terrain="plane")
+    cam2 = env2.add_sensor("depth", sensors.from_spec(env2, torch.load(path, weights_only=False)["vision"]["sensor"], api=api))
+    assert cam2.map == cam.map
+    assert list(_evaluate(env2, path, steps=1, vision_metrics=("map_coverage",)).result()["total"]["columns"]) == ["map_coverage"]
+    base = ["--task", "aliengo", "--checkpoint", "x.pt", "--out", "y.json"]
+    assert parse_args(base + ["--vision-metrics", "scan_error,map_scan_error,map_coverage"]).vision_metrics == ("scan_error", "map_scan_error", "map_coverage")
+    assert parse_args(base).vision_metrics == ("depth_influence", "scan_error")
+    with pytest.raises(SystemExit):
+        parse_args(base + ["--vision-metrics", "map_error"])

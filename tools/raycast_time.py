@@ -27,6 +27,11 @@ which it cannot take), in one process and alternating `--repeats` times, each wi
 lsim_sensor_capture as --model times it; `<sensor>_inst_neutral_us` = lsim_sensor_capture_inst on the neutral rows; `<sensor>_inst_drawn_us` =
 the same on rows drawn once for every env (the draw launch kept out of the timed loop); `draw_all_fresh_us` / `draw_none_fresh_us` =
 lsim_sensor_instrument alone with LSIM_SENSOR_FILL_ALL and with no env at episode_length 0.
+`--map size=32,resolution=0.0625,source=noisy` (any subset; needs --model; a measurement of its own, the camera only, no counters): per
+terrain, in one process and alternating `--repeats` times, each with its median and range: `capture_us` = lsim_sensor_capture as --model
+times it (the tick advancing, so a staggered period is averaged over whole periods); `map_us` = lsim_elevation_map alone over the same
+ticks, reading the rows the captures left; `map_all_due_us` = the same launch with LSIM_SENSOR_FILL_ALL (every env cleared and inserted);
+`update_with_map_us` = update() as a sensor with a map runs it in a step: the capture and the map's launch behind it.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -146,6 +151,49 @@ def measure_mount_jitter(n, terrain, iters, warmup, model, jitter, repeats):
         out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
     out["jittered_over_nominal"] = out["camera_model_jittered_us"] / out["camera_model_us"]
     out["nonfinite_rays"] = int(nominal.nonfinite_rays.item()) + int(jittered.nonfinite_rays.item())
+    return out
+
+
+def measure_map(n, terrain, iters, warmup, model, emap, repeats):
+    """the --map measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    env.episode_length_buf[:] = 20               # nobody is fresh inside the timed loops: the period alone decides who is due
+    torch.cuda.synchronize()
+    cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
+    cam.refresh(tick=0)
+    cam.attach_map(emap)
+    em = cam._em
+    whole = max(model.period, iters // model.period * model.period)
+    fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+
+    def map_ticks(flags):
+        tick = [0]
+
+        def fn():
+            cam._launch_map(tick[0], flags, None)
+            tick[0] += 1
+        return timed(fn, whole, warmup)
+    rows = {"capture_us": [], "map_us": [], "map_all_due_us": [], "update_with_map_us": []}
+    for _ in range(repeats):
+        cam._em = None                          # the capture alone
+        rows["capture_us"].append(timed_ticks(cam, whole, warmup))
+        cam._em = em
+        rows["map_us"].append(map_ticks(0))
+        rows["map_all_due_us"].append(map_ticks(fill_all))
+        rows["update_with_map_us"].append(timed_ticks(cam, whole, warmup))
+    out = {"num_envs": n, "terrain": terrain, "rays": cam.num_rays, "scan_points": int(em.num_points), "size": int(em.size),
+           "coverage": float(cam.map_known().float().mean().item()), "cells_known": float((cam.map_state()[1] >= 0).float().mean().item())}
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    out["map_over_capture"] = out["map_us"] / out["capture_us"]
+    out["nonfinite"] = int(cam.nonfinite_rays.item()) + int(cam.map_nonfinite.item())
     return out
 
 
@@ -287,7 +335,9 @@ def main():
     ap.add_argument("--mount-jitter", default=None, help="POS,ROT_DEG: time lsim_sensor_mount_jitter and lsim_sensor_capture on jittered against nominal mounts (needs --model)")
     ap.add_argument("--instrument", default=None, help="latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F: time lsim_sensor_instrument and "
                     "lsim_sensor_capture_inst against lsim_sensor_capture (needs --model)")
-    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument: alternating repetitions of every timed loop")
+    ap.add_argument("--map", default=None, nargs="?", const="default", help="size=G,resolution=RES,source=noisy|clean (any subset): time lsim_elevation_map "
+                    "next to lsim_sensor_capture (needs --model)")
+    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -299,6 +349,19 @@ def main():
         res = {"tool": "raycast_time --mount-jitter", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
                "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot", "model": a.model, "mount_jitter": jitter.record(),
                "cases": [measure_mount_jitter(a.num_envs, t, a.iters, a.warmup, model, jitter, a.repeats) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
+    if a.map:
+        if not a.model:
+            ap.error("--map needs --model")
+        model, emap = parse_model(a.model), sensors.parse_elevation_map(a.map)
+        res = {"tool": "raycast_time --map", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot, labels", "model": a.model, "map": emap.record(),
+               "cases": [measure_map(a.num_envs, t, a.iters, a.warmup, model, emap, a.repeats) for t in a.terrains.split(",")]}
         line = json.dumps(res)
         if a.out:
             with open(a.out, "w") as f:

@@ -2,11 +2,14 @@
 """Third-person depth and label frames of robots on their terrain, without a viewer: a frame="yaw" chase camera (envs/sensors.py, see_robot=True).
 
     python tools/sensor_frames.py --out frames/ [--task aliengo] [--num-envs 64] [--envs 0,1,2] [--steps 50] [--every 10]
-                                  [--checkpoint model.pt] [--width 160] [--height 120] [--terrain stairs]
+                                  [--checkpoint model.pt] [--width 128] [--height 96] [--terrain stairs]
 
 Steps the env under a checkpoint's actor (learn/evaluate.py's loader) or zero actions; every `--every` steps writes, for each chosen env,
 `depth_e<env>_s<step>.npy` (float32 [H, W] z-depth in metres), `labels_e<env>_s<step>.npy` (uint8: 0 nothing, 1 terrain, 2 + b body b) and the
-same two as 8-bit PGM (depth: near = white, far = black; labels: spread over the grey range).  A PGM is a text header plus raw bytes."""
+same two as 8-bit PGM (depth: near = white, far = black; labels: spread over the grey range).  A PGM is a text header plus raw bytes.
+`--map [size=32,resolution=0.0625,source=clean]`: the robot also carries the forward camera of the vision tasks (64 x 48, 0.3 m ahead, pitched
+30 degrees down) with an elevation map (sensors.ElevationMap), and `map_e<env>_s<step>.npy` (float32 [G, G], window order, NaN = unknown)
+and `.pgm` (unknown black, then low = dark to high = white over the map's own range) are written next to the frames."""
 import argparse
 import os
 import sys
@@ -35,6 +38,16 @@ def labels_to_gray(labels):
     return np.where(lab == 0, 0, np.where(lab == 1, 60, 80 + (lab - 2) * 10)).astype(np.uint8)
 
 
+def map_to_gray(heights):
+    h = np.asarray(heights, np.float64)
+    known = ~np.isnan(h)
+    if not known.any():
+        return np.zeros(h.shape, np.uint8)
+    lo, hi = h[known].min(), h[known].max()
+    g = 40.0 + 215.0 * (np.where(known, h, lo) - lo) / max(hi - lo, 1e-6)
+    return np.where(known, np.round(g), 0).astype(np.uint8)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out", required=True)
@@ -45,12 +58,13 @@ def main():
     ap.add_argument("--every", type=int, default=10)
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--terrain", choices=("flat", "stairs"), default="stairs")
-    ap.add_argument("--width", type=int, default=160)
-    ap.add_argument("--height", type=int, default=120)
+    ap.add_argument("--width", type=int, default=128)       # width * height <= LSIM_RAYCAST_MAX_RAYS (16384)
+    ap.add_argument("--height", type=int, default=96)
     ap.add_argument("--hfov", type=float, default=60.0)
     ap.add_argument("--mount", default="-1.2,0.0,0.7", help="camera position in the yaw frame of the base (behind and above)")
     ap.add_argument("--pitch", type=float, default=28.0)
     ap.add_argument("--far", type=float, default=5.0)
+    ap.add_argument("--map", default=None, nargs="?", const="source=clean", help="also write an elevation map: size=G,resolution=RES,source=noisy|clean")
     a = ap.parse_args()
     import torch
     from isaacgymloco_amd.envs import config as C, sensors
@@ -61,6 +75,11 @@ def main():
     env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
     cam = env.add_sensor("chase", sensors.depth_camera(env, a.width, a.height, a.hfov, mount_pos=tuple(float(v) for v in a.mount.split(",")),
                                                        pitch_deg=a.pitch, near=0.05, far=a.far, see_robot=True, labels=True, frame="yaw"))
+    front = None
+    if a.map:
+        front = env.add_sensor("front", sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=a.far,
+                                                             model=sensors.SensorModel()))
+        front.attach_map(sensors.parse_elevation_map(a.map))
     env.reset()
     policy = None
     if a.checkpoint:
@@ -75,8 +94,12 @@ def main():
         env.step_device(actions)
         if step % a.every == 0 or step == a.steps:
             depth, labels = cam.image().cpu().numpy(), cam.label_image().cpu().numpy()
+            heights = None if front is None else front.map_heights().cpu().numpy()
             for e in ids:
                 stem = f"e{e}_s{step:04d}"
+                if heights is not None:
+                    np.save(os.path.join(a.out, f"map_{stem}.npy"), heights[e])
+                    write_pgm(os.path.join(a.out, f"map_{stem}.pgm"), map_to_gray(heights[e]))
                 np.save(os.path.join(a.out, f"depth_{stem}.npy"), depth[e])
                 np.save(os.path.join(a.out, f"labels_{stem}.npy"), labels[e])
                 write_pgm(os.path.join(a.out, f"depth_{stem}.pgm"), depth_to_gray(depth[e], cam.near, cam.far))
