@@ -574,7 +574,8 @@ int lsim_rollout_gae(const lsim_rollout_storage* st, const float* last_values, f
  * line per row and chunk, with the second half evicted from the CU's 32 KB vector cache before its turn when a wave owned two tiles) --
  * bias [n_pad]; 16-byte aligned (the caller packs torch's nn.Linear parameters once per policy update).
  * mean_out [num_envs, num_actions], values_out [num_envs, 1].  LSIM_E_UNSUPPORTED for other topologies / sizes (hidden widths > 512,
- * inputs > 272): run the networks in the host framework then. */
+ * inputs > 272, a first actor layer padded beyond 272, a layer whose k_pad exceeds its predecessor's n_pad -- it would read activation
+ * columns nobody wrote): run the networks in the host framework then. */
 typedef struct lsim_mlp_layer {
     const float* weight;      /* [n_pad / 16][k_pad / 16][16][16]: see above */
     const float* bias;        /* [n_pad] */

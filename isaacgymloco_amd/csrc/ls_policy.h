@@ -409,6 +409,12 @@ static int ls_policy_launch(const lsim_him_policy* p, const float* obs, const fl
     // layers whose output lands in LDS buffer B (row stride LS_POL_STRIDE_B): second and last layer of each network
     if (p->encoder[1].n_pad > LS_POL_MAX_IN || p->actor[1].n_pad > LS_POL_MAX_IN || p->actor[3].n_pad > LS_POL_MAX_IN ||
         p->critic[1].n_pad > LS_POL_MAX_IN || p->critic[3].n_pad > LS_POL_MAX_IN) bad = 1;
+    // a layer reads k_pad columns of the buffer its predecessor filled up to n_pad: beyond that the LDS row holds whatever an earlier layer
+    // (or nobody) left there, and 0 * NaN is not 0; in buffer B it would be the next row or the end of the allocation
+    for (int l = 1; l < 4; ++l) {
+        if (l < 3 && p->encoder[l].k_pad > p->encoder[l - 1].n_pad) bad = 1;
+        if (p->actor[l].k_pad > p->actor[l - 1].n_pad || p->critic[l].k_pad > p->critic[l - 1].n_pad) bad = 1;
+    }
     if (bad) return LSIM_E_UNSUPPORTED;
     // 32 environments per block once that still fills the chip's 256 CUs with one block each; 16 per block (two blocks per CU) below that
     const bool wide = num_envs >= 2048;

@@ -29,7 +29,14 @@ class PackedHimPolicy:
             return False
         wide = max(l.out_features for l in enc + act + cri)
         second = max(enc[1].out_features, act[1].out_features, cri[1].out_features)     # these land in the narrower LDS buffer
-        return wide <= 512 and second <= 272 and ac.num_actor_obs <= 272 and cri[0].in_features <= 272 and ac.num_actions <= 16 and next(ac.parameters()).is_cuda
+        # the library's own rule (csrc/ls_policy.h, ls_policy_launch), so that a policy it would refuse takes the torch path instead of dying in
+        # lib.check: the three first layers read the 272-wide input rows, the estimator reads the whole history, and the actor's first layer is
+        # [one-step obs | 3 + latent | a vision policy's depth latent]
+        first = max(enc[0].in_features, act[0].in_features, cri[0].in_features)
+        chained = (enc[0].in_features == ac.num_actor_obs and enc[2].out_features >= 4 and act[3].out_features == ac.num_actions and cri[3].out_features == 1
+                   and act[0].in_features == ac.num_one_step_obs + enc[2].out_features + int(getattr(ac, "depth_latent_dim", 0)))
+        return (wide <= 512 and second <= 272 and (first + 15) // 16 * 16 <= 272 and chained and 1 <= ac.num_actions <= 16
+                and next(ac.parameters()).is_cuda)
 
     def __init__(self, ac):
         assert self.supported(ac)
