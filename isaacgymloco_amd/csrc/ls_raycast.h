@@ -13,6 +13,9 @@
 // the work (the dz byte: nothing of the 4 x 4 vertex block reaches up to the ray -> skip; bit 20 clear: the cell's own two triangles; set: the
 // triangles of the 3 x 3 cells around, which is what a displacement of at most one cell can stretch over this cell).  A triangle is never
 // clipped to the cell that led to it: a hit found early is a hit, and the walk ends at the first cell whose exit lies behind the best hit.
+// The ray itself (pose, non-finite rule, counters, cast, scale) is ONE function, ls_rc_value, taking the sensor-frame direction and scale as
+// arguments: ls_rc_ray hands it the tables' and stores; the two capture kernels (ls_sensor_model.h, ls_sensor_instrument.h) call it
+// directly.  ls_rc_grid is the one grid computation of the four ray launches and ls_rc_block their one block -> (env, ray) map.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -149,15 +152,20 @@ LS_RC_FN void ls_rc_count(long long* p, long long v) { *p += v; }
 LS_RC_FN void ls_rc_count(long long* p, long long v) { (void)atomicAdd((unsigned long long*)p, (unsigned long long)v); }
 #endif
 
-// ray r of env: pose, cast, scale, store
-LS_RC_FN void ls_rc_ray(const lsim_raycast_t& rc, int env, int r) {
+// THE terrain ray: the scaled range of one ray of env -- pose, cast, scale; hit = (t < far), label 1 / 0.  `s` points to the ray's direction in
+// the sensor frame (3 floats) and `sc` to its scale (NULL: 1): the table callers pass rc.dirs + 3 r and rc.scale + r, the instrument the pair
+// ls_si_ray made.  They come as pointers so that both are read where ls_rc_ray always read them, between the pose's scalar loads and the
+// cast: with that lsim_k_raycast compiles to the instructions it had when this text was its own.  Every launch that casts a ray at the
+// terrain alone calls this one function: lsim_k_raycast through ls_rc_ray, lsim_k_sensor_capture and lsim_k_sensor_capture_inst directly,
+// and the CPU shims of all three.
+LS_RC_FN float ls_rc_value(const lsim_raycast_t& rc, int env, const float* s, const float* sc, bool& hit, int& label) {
     const float* rs = rc.root_states + (size_t)13 * (size_t)env;
     const float* mt = rc.mount + (size_t)7 * (size_t)env;
     const LsRcV3 mp = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ls_rc_v3(mt[0], mt[1], mt[2]));
     const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
-    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], ls_rc_v3(rc.dirs[3 * r], rc.dirs[3 * r + 1], rc.dirs[3 * r + 2]));
+    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], ls_rc_v3(s[0], s[1], s[2]));
     const LsRcV3 d = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ds);
-    const float sc = rc.scale ? rc.scale[r] : 1.0f;
+    const float scale = sc ? *sc : 1.0f;
     long long* state = (long long*)rc.state;
     float t = rc.far;
     if (ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
@@ -171,7 +179,16 @@ LS_RC_FN void ls_rc_ray(const lsim_raycast_t& rc, int env, int r) {
     } else {
         ls_rc_count(state, 1);
     }
-    rc.out[(size_t)env * (size_t)rc.out_stride + (size_t)r] = t * sc;
+    hit = t < rc.far;
+    label = hit ? 1 : 0;
+    return t * scale;
+}
+
+// ray r of env: the value at the tables' direction and scale, stored
+LS_RC_FN void ls_rc_ray(const lsim_raycast_t& rc, int env, int r) {
+    bool hit;
+    int label;
+    rc.out[(size_t)env * (size_t)rc.out_stride + (size_t)r] = ls_rc_value(rc, env, rc.dirs + 3 * r, rc.scale ? rc.scale + r : nullptr, hit, label);
 }
 
 // ---- host side: argument checks shared by the library and the CPU shim (no launch happens before they pass)
@@ -195,11 +212,25 @@ static inline int ls_rc_validate(const lsim_raycast_t* rc) {
 }
 static inline int ls_rc_blocks_per_env(const lsim_raycast_t& rc) { return (rc.num_rays + LS_RC_BLOCK - 1) / LS_RC_BLOCK; }
 static inline int ls_rc_env_slots(const lsim_raycast_t& rc) { return (rc.num_envs + rc.env_stride - 1) / rc.env_stride; }
+// the grid of the four ray launches: blocks per env, and blocks = that times the env slots; false when a grid does not hold them
+static inline bool ls_rc_grid(const lsim_raycast_t& rc, int& blocks_per_env, unsigned& blocks) {
+    blocks_per_env = ls_rc_blocks_per_env(rc);
+    const long long n = (long long)blocks_per_env * ls_rc_env_slots(rc);
+    blocks = (unsigned)n;
+    return n <= 0x7fffffffLL;
+}
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
-__global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_raycast(const lsim_raycast_t rc, int blocks_per_env) {
+// the map of all four ray kernels: block -> env (blockIdx alone: block-uniform), lane -> ray r of that env
+__device__ __forceinline__ void ls_rc_block(const lsim_raycast_t& rc, int blocks_per_env, int& env, int& r) {
     const int slot = (int)blockIdx.x / blocks_per_env, chunk = (int)blockIdx.x - slot * blocks_per_env;
-    const int env = slot * rc.env_stride, r = chunk * LS_RC_BLOCK + (int)threadIdx.x;
+    env = slot * rc.env_stride;
+    r = chunk * LS_RC_BLOCK + (int)threadIdx.x;
+}
+
+__global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_raycast(const lsim_raycast_t rc, int blocks_per_env) {
+    int env, r;
+    ls_rc_block(rc, blocks_per_env, env, r);
     if (r >= rc.num_rays || env >= rc.num_envs) return;
     ls_rc_ray(rc, env, r);
 }
@@ -212,10 +243,10 @@ extern "C" int lsim_raycast_sizes(size_t* state_bytes) {
 extern "C" int lsim_raycast(const lsim_raycast_t* rc, void* stream) {
     const int rv = ls_rc_validate(rc);
     if (rv != LSIM_OK) return rv;
-    const int bpe = ls_rc_blocks_per_env(*rc);
-    const long long blocks = (long long)bpe * ls_rc_env_slots(*rc);
-    if (blocks > 0x7fffffffLL) return LSIM_E_INVALID;
-    hipLaunchKernelGGL(lsim_k_raycast, dim3((unsigned)blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *rc, bpe);
+    int bpe;
+    unsigned blocks;
+    if (!ls_rc_grid(*rc, bpe, blocks)) return LSIM_E_INVALID;
+    hipLaunchKernelGGL(lsim_k_raycast, dim3(blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *rc, bpe);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
 #endif

@@ -9,8 +9,10 @@
 //      body poses, relative to the base position, into LDS (lane 0 writes the base's too);
 //   2. ls_rcb_prim: one lane per primitive turns (body pose, primitive pose) into a base-relative centre, world-oriented axes, sizes and a
 //      bounding radius in LDS (48 x 16 floats = 3 KB); a primitive of a masked body gets kind -1.
-//   A __syncthreads() after each (2 reads what 1 wrote).  Both steps are a few hundred instructions of ONE wave per block, against 256 rays.
-//   3. ls_rcb_ray: a rolled loop over the primitives.  The primitive index is wave-uniform, so every lane reads the same LDS address (a broadcast,
+//   A __syncthreads() after each (2 reads what 1 wrote): ls_rcb_block, which lsim_k_sensor_capture and lsim_k_sensor_capture_inst call too.
+//   Both steps are a few hundred instructions of ONE wave per block, against 256 rays.
+//   3. ls_rcb_ray (this launch) and ls_rcb_value (the same ray for the two capture launches, which hand it the direction and scale to cast:
+//      one function where there were two; why ls_rcb_ray is not its third caller stands above ls_rcb_ray): a rolled loop over the primitives.  The primitive index is wave-uniform, so every lane reads the same LDS address (a broadcast,
 //      no bank conflict) and the switch on `kind` does not diverge.  A bounding-sphere test rejects most primitives before the exact one.  The
 //      smallest body hit then becomes `far` of the terrain walk (ls_rc_cast, shared with lsim_raycast and not changed: the walk takes its bounds
 //      from the struct it is given, and this kernel hands it a copy with the shorter `far`), so a ray that ends on a thigh walks no cell behind it.
@@ -194,7 +196,55 @@ LS_RC_FN float ls_rcb_cast(const LsRcbShared& sh, LsRcV3 o, LsRcV3 d, float near
     return best;
 }
 
-// ray r of env: pose, bodies, terrain up to the body hit, scale, store
+// The body ray of the two captures: the scaled range and the label of one ray of env -- pose (yaw frame if asked), bodies, terrain up to the
+// body hit, scale; hit = (t < far).  `s` and `sc` as ls_rc_value's: where the ray's sensor-frame direction and its scale (NULL: 1) are read.
+// lsim_k_sensor_capture, lsim_k_sensor_capture_inst and their CPU shims call it; ls_rcb_ray below does NOT (its comment says why), so a change
+// to the pose convention, the non-finite rule, the counters or the tie rule is made here and there.
+LS_RC_FN float ls_rcb_value(const lsim_raycast_bodies_t& rb, const LsRcbShared& sh, int env, const float* s, const float* sc, bool& hit, int& label) {
+    const lsim_raycast_t& rc = rb.rc;
+    const float* rs = rc.root_states + (size_t)13 * (size_t)env;
+    const float* mt = rc.mount + (size_t)7 * (size_t)env;
+    float qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
+    if (rb.flags & LSIM_RAYCAST_FRAME_YAW) {
+        const float n = 1.0f / sqrtf(qz * qz + qw * qw);
+        qx = 0.0f; qy = 0.0f; qz *= n; qw *= n;
+    }
+    const LsRcV3 mp = ls_rc_rot(qx, qy, qz, qw, ls_rc_v3(mt[0], mt[1], mt[2]));
+    const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
+    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], ls_rc_v3(s[0], s[1], s[2]));
+    const LsRcV3 d = ls_rc_rot(qx, qy, qz, qw, ds);
+    const float scale = sc ? *sc : 1.0f;
+    long long* state = (long long*)rc.state;
+    float t = rc.far;
+    label = 0;
+    const bool joints_ok = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) == 0;
+    if (joints_ok && ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
+        LsRcCount cnt;
+        cnt.cells = 0; cnt.tris = 0;
+        int tested = 0;
+        const float tb = ls_rcb_cast(sh, mp, d, rc.near, rc.far, label, tested);
+        lsim_raycast_t walk = rc;               // the shared walk, bounded by the body hit
+        walk.far = tb;
+        t = ls_rc_cast(walk, o, d, cnt);
+        if (t < tb) label = 1;                  // a tie: the body keeps the label; no body and t == far: a miss, label 0
+#if defined(LS_RAYCAST_COUNTERS)
+        ls_rc_count(state + 1, tested);
+        ls_rc_count(state + 2, cnt.cells);
+        ls_rc_count(state + 3, cnt.tris);
+#endif
+    } else {
+        ls_rc_count(state, 1);
+    }
+    hit = t < rc.far;
+    return t * scale;
+}
+
+// ray r of env: pose, bodies, terrain up to the body hit, scale, store.  The text of ls_rcb_value at the tables' direction and scale, kept as
+// text: through the function (the label then reaches ls_rcb_cast by two references instead of one) the compiler turns the tie rule's select
+// into a branch and moves a block of the primitive loop, 5 instructions more, and lsim_raycast_bodies measured 0.13 - 0.49 % over the
+// parent's slowest run on three of four workloads, in two sessions; with the label in a local of ls_rcb_value this kernel came out
+// instruction-identical and lsim_sensor_capture 0.6 - 1.0 % slower on flat ground instead (profiles/raycast_refactor_ab.json).
+// The bit-for-bit tests capture(identity) == lsim_raycast_bodies pin the two texts to each other.
 LS_RC_FN void ls_rcb_ray(const lsim_raycast_bodies_t& rb, const LsRcbShared& sh, int env, int r) {
     const lsim_raycast_t& rc = rb.rc;
     const float* rs = rc.root_states + (size_t)13 * (size_t)env;
@@ -268,15 +318,20 @@ static inline int ls_rcb_validate(const lsim_raycast_bodies_t* rb) {
 }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
-__global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_raycast_bodies(const lsim_raycast_bodies_t rb, int blocks_per_env) {
-    __shared__ LsRcbShared sh;
-    const int slot = (int)blockIdx.x / blocks_per_env, chunk = (int)blockIdx.x - slot * blocks_per_env;
-    const int env = slot * rb.rc.env_stride, lane = (int)threadIdx.x, r = chunk * LS_RC_BLOCK + lane;
-    if (env >= rb.rc.num_envs) return;          // the whole block: env is blockIdx's
+// steps 1 and 2 with their barriers: every lane of the block enters (the three kernels that see the robot return whole blocks only, before this)
+__device__ __forceinline__ void ls_rcb_block(const lsim_raycast_bodies_t& rb, LsRcbShared& sh, int env, int lane) {
     if (lane < LSIM_NUM_LEGS) ls_rcb_fk(rb, sh, env, lane);
     __syncthreads();
     if (lane < sh.nprims) ls_rcb_prim(rb, sh, env, lane);
     __syncthreads();
+}
+
+__global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_raycast_bodies(const lsim_raycast_bodies_t rb, int blocks_per_env) {
+    __shared__ LsRcbShared sh;
+    int env, r;
+    ls_rc_block(rb.rc, blocks_per_env, env, r);
+    if (env >= rb.rc.num_envs) return;          // the whole block: env is blockIdx's
+    ls_rcb_block(rb, sh, env, (int)threadIdx.x);
     if (r < rb.rc.num_rays) ls_rcb_ray(rb, sh, env, r);
 }
 
@@ -289,10 +344,10 @@ extern "C" int lsim_raycast_bodies_sizes(size_t* state_bytes, size_t* robot_byte
 extern "C" int lsim_raycast_bodies(const lsim_raycast_bodies_t* rb, void* stream) {
     const int rv = ls_rcb_validate(rb);
     if (rv != LSIM_OK) return rv;
-    const int bpe = ls_rc_blocks_per_env(rb->rc);
-    const long long blocks = (long long)bpe * ls_rc_env_slots(rb->rc);
-    if (blocks > 0x7fffffffLL) return LSIM_E_INVALID;
-    hipLaunchKernelGGL(lsim_k_raycast_bodies, dim3((unsigned)blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *rb, bpe);
+    int bpe;
+    unsigned blocks;
+    if (!ls_rc_grid(rb->rc, bpe, blocks)) return LSIM_E_INVALID;
+    hipLaunchKernelGGL(lsim_k_raycast_bodies, dim3(blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *rb, bpe);
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
 #endif

@@ -10,17 +10,19 @@
 // env is not fresh ends after one 8-byte load.  A fresh one runs 20 Philox rounds and a dozen fp32 operations and writes its 32-byte row as two
 // 16-byte stores.  At N = 4096 that is 16 blocks and 128 KB at the most: the launch is its own launch overhead.
 //
-// Shape of the capture (lsim_k_sensor_capture_inst): lsim_k_sensor_capture's, line for line -- ls_sm_due first, the prologue of
-// lsim_k_raycast_bodies unless terrain only, then per ray a cast and a store.  What differs:
+// Shape of the capture (lsim_k_sensor_capture_inst): lsim_k_sensor_capture's, through the same functions -- ls_rc_block and ls_sm_due first,
+// ls_rcb_block (the prologue of lsim_k_raycast_bodies) unless terrain only, then per ray a cast and a store.  The two early returns stand in
+// each kernel: folded into one function that returns "go on", they changed the branch layout of both kernels.  What differs:
 //   0. a due block loads its env's row once, into one VGPR (lane k holds row[k & 7]); the values are read out of it as wave-uniform scalars
 //      (v_readlane) where they are used -- tan_scale ahead of the cast, the others behind it: the cast leaves no SGPR to carry them across;
 //   1. ls_si_ray: the ray's direction and scale in the sensor frame, widened or narrowed by tan_scale.  One correctly rounded square root and
 //      one division per ray, skipped by the whole block when tan_scale == 1;
-//   2. ls_si_raw_terrain / ls_si_raw_bodies: ls_sm_raw_terrain / ls_sm_raw_bodies taking that direction and scale as arguments.  They are
-//      copies, not edits, as those two are of ls_rc_ray / ls_rcb_ray: the existing kernels inline the originals and must not move.  ls_sm_due,
-//      ls_rcb_fk, ls_rcb_prim and the casts (ls_rcb_cast, ls_rc_cast) are shared;
-//   3. ls_si_store: ls_sm_store with the calibration error and the noise gain on a hit, and the history shifted over the env's own
-//      Ke = L + frames <= K slots; the slots from Ke - 1 on all take the new value, so they never hold anything older.
+//   2. ls_si_raw_terrain / ls_si_raw_bodies: ls_rc_value / ls_rcb_value (ls_raycast.h, ls_raycast_bodies.h) on that direction and scale, the
+//      ray routines lsim_k_sensor_capture calls on the tables' own.  Nothing of the ray is restated here;
+//   3. ls_si_store: the three pieces of ls_sm_store (ls_sm_clean, ls_sm_draw, ls_sm_history) around this launch's model line -- the calibration
+//      error and the noise gain on a hit -- with the history shifted over the env's own Ke = L + frames <= K slots; the slots from Ke - 1 on
+//      all take the new value, so they never hold anything older.
+// That the neutral row writes lsim_sensor_capture's bits now follows from the source, up to the model line (ls_si_calibrated says what that takes).
 #pragma once
 #include "ls_sensor_model.h"
 #include "ls_math.h"
@@ -83,69 +85,14 @@ LS_RC_FN LsRcV3 ls_si_ray(const lsim_raycast_t& rc, int r, float tan_scale, floa
     return s;
 }
 
-// ls_sm_raw_terrain for the sensor-frame direction s and the scale sc
+// step 2: the shared ray routines at the direction s and the scale sc
 LS_RC_FN float ls_si_raw_terrain(const lsim_raycast_t& rc, int env, LsRcV3 s, float sc, bool& hit, int& label) {
-    const float* rs = rc.root_states + (size_t)13 * (size_t)env;
-    const float* mt = rc.mount + (size_t)7 * (size_t)env;
-    const LsRcV3 mp = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ls_rc_v3(mt[0], mt[1], mt[2]));
-    const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
-    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], s);
-    const LsRcV3 d = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ds);
-    long long* state = (long long*)rc.state;
-    float t = rc.far;
-    if (ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
-        LsRcCount cnt;
-        cnt.cells = 0; cnt.tris = 0;
-        t = ls_rc_cast(rc, o, d, cnt);
-#if defined(LS_RAYCAST_COUNTERS)
-        ls_rc_count(state + 2, cnt.cells);
-        ls_rc_count(state + 3, cnt.tris);
-#endif
-    } else {
-        ls_rc_count(state, 1);
-    }
-    hit = t < rc.far;
-    label = hit ? 1 : 0;
-    return t * sc;
+    const float v[3] = {s.x, s.y, s.z};
+    return ls_rc_value(rc, env, v, &sc, hit, label);
 }
-
-// ls_sm_raw_bodies for the sensor-frame direction s and the scale sc
 LS_RC_FN float ls_si_raw_bodies(const lsim_raycast_bodies_t& rb, const LsRcbShared& sh, int env, LsRcV3 s, float sc, bool& hit, int& label) {
-    const lsim_raycast_t& rc = rb.rc;
-    const float* rs = rc.root_states + (size_t)13 * (size_t)env;
-    const float* mt = rc.mount + (size_t)7 * (size_t)env;
-    float qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
-    if (rb.flags & LSIM_RAYCAST_FRAME_YAW) {
-        const float n = 1.0f / sqrtf(qz * qz + qw * qw);
-        qx = 0.0f; qy = 0.0f; qz *= n; qw *= n;
-    }
-    const LsRcV3 mp = ls_rc_rot(qx, qy, qz, qw, ls_rc_v3(mt[0], mt[1], mt[2]));
-    const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
-    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], s);
-    const LsRcV3 d = ls_rc_rot(qx, qy, qz, qw, ds);
-    long long* state = (long long*)rc.state;
-    float t = rc.far;
-    label = 0;
-    const bool joints_ok = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) == 0;
-    if (joints_ok && ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
-        LsRcCount cnt;
-        cnt.cells = 0; cnt.tris = 0;
-        int tested = 0;
-        const float tb = ls_rcb_cast(sh, mp, d, rc.near, rc.far, label, tested);
-        lsim_raycast_t walk = rc;               // the shared walk, bounded by the body hit
-        walk.far = tb;
-        t = ls_rc_cast(walk, o, d, cnt);
-        if (t < tb) label = 1;
-#if defined(LS_RAYCAST_COUNTERS)
-        ls_rc_count(state + 1, tested);
-        ls_rc_count(state + 2, cnt.cells);
-        ls_rc_count(state + 3, cnt.tris);
-#endif
-    } else {
-        ls_rc_count(state, 1);
-    }
-    hit = t < rc.far;
-    return t * sc;
+    const float v[3] = {s.x, s.y, s.z};
+    return ls_rcb_value(rb, sh, env, v, &sc, hit, label);
 }
 
 // m of the header, rounded as a product of its own.  Left to itself the compiler may fuse it into the sum that follows (m + n g as
@@ -158,33 +105,18 @@ LS_RC_FN float ls_si_calibrated(float raw, float depth_scale, float depth_quad) 
     return raw * (1.0f + (depth_scale + depth_quad * raw));
 }
 
-// step 3: ls_sm_store under the env's row
+// step 3: ls_sm_store under the env's row -- its three pieces (ls_sensor_model.h) around this launch's own model line, over the env's Ke slots
 LS_RC_FN void ls_si_store(const lsim_sensor_model_t& sm, const LsSiRow& row, int env, int r, float raw, bool hit, int label, bool fill) {
-    const lsim_raycast_bodies_t& rb = sm.rb;
-    rb.rc.out[(size_t)env * (size_t)rb.rc.out_stride + (size_t)r] = raw;
-    if (rb.labels) rb.labels[(size_t)env * (size_t)rb.label_stride + (size_t)r] = (uint8_t)label;
-    uint32_t c[4] = {(uint32_t)env, (uint32_t)sm.tick, (uint32_t)LSIM_RNG_SENSOR, (sm.stream_id << 16) | (uint32_t)r};
-    philox4x32_10(c, sm.seed, sm.rank);
-    const float u0 = u32_to_u01(c[0]), u1 = u32_to_u01(c[1]), u2 = u32_to_u01(c[2]), u3 = u32_to_u01(c[3]);
-    const float g = 2.0f * ((u0 + u1 + u2) - 1.5f);
+    ls_sm_clean(sm.rb, env, r, raw, label);
+    float u3;
+    const float g = ls_sm_draw(sm, env, r, u3);
     float v = raw;
     if (hit) {
         const float m = ls_si_calibrated(raw, row.depth_scale, row.depth_quad);
         v = m + (row.noise_gain * (row.sigma0 + row.sigma2 * raw * raw)) * g;
         if (u3 < row.p_drop) v = sm.drop_value;
     }
-    v = fminf(fmaxf(v, sm.clip_lo), sm.clip_hi);
-    const float y = (v - sm.offset) * sm.gain;
-    const int K = sm.latency + sm.frames;
-    const int Ke = row.slots;
-    const size_t hs = (size_t)sm.hist_stride;
-    float* h = sm.hist + (size_t)env * (size_t)K * hs + (size_t)r;
-    if (fill) {
-        for (int k = 0; k < K; ++k) h[(size_t)k * hs] = y;
-    } else {
-        for (int k = 0; k + 1 < Ke; ++k) h[(size_t)k * hs] = h[(size_t)(k + 1) * hs];
-        for (int k = Ke - 1; k < K; ++k) h[(size_t)k * hs] = y;
-    }
+    ls_sm_history(sm, env, r, v, row.slots, fill);
 }
 
 // ---- host side: the argument checks shared by the library and the CPU shim (no launch happens before they pass)
@@ -230,8 +162,9 @@ __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture_inst(const 
                                                                           uint32_t tick_mod) {
     __shared__ LsRcbShared sh;
     const lsim_raycast_bodies_t& rb = sm.rb;
-    const int slot = (int)blockIdx.x / blocks_per_env, chunk = (int)blockIdx.x - slot * blocks_per_env;
-    const int env = slot * rb.rc.env_stride, lane = (int)threadIdx.x, r = chunk * LS_RC_BLOCK + lane;
+    const int lane = (int)threadIdx.x;
+    int env, r;
+    ls_rc_block(rb.rc, blocks_per_env, env, r);
     if (env >= rb.rc.num_envs) return;          // the whole block: env is blockIdx's
     bool fill;
     if (!ls_sm_due(sm, env, tick_mod, fill)) return;     // the whole block again, before LDS and the barriers
@@ -248,10 +181,7 @@ __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture_inst(const 
     int label = 0;
     float raw = 0.0f, sc = 1.0f;
     if (rb.robots) {
-        if (lane < LSIM_NUM_LEGS) ls_rcb_fk(rb, sh, env, lane);
-        __syncthreads();
-        if (lane < sh.nprims) ls_rcb_prim(rb, sh, env, lane);
-        __syncthreads();
+        ls_rcb_block(rb, sh, env, lane);
         if (r < rb.rc.num_rays) {
             const LsRcV3 s = ls_si_ray(rb.rc, r, tan_scale, sc);
             raw = ls_si_raw_bodies(rb, sh, env, s, sc, hit, label);
@@ -272,10 +202,10 @@ __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture_inst(const 
 extern "C" int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, void* stream) {
     const int rv = ls_si_capture_validate(sm, inst);
     if (rv != LSIM_OK) return rv;
-    const int bpe = ls_rc_blocks_per_env(sm->rb.rc);
-    const long long blocks = (long long)bpe * ls_rc_env_slots(sm->rb.rc);
-    if (blocks > 0x7fffffffLL) return LSIM_E_INVALID;
-    hipLaunchKernelGGL(lsim_k_sensor_capture_inst, dim3((unsigned)blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *sm, inst, bpe, ls_sm_tick_mod(*sm));
+    int bpe;
+    unsigned blocks;
+    if (!ls_rc_grid(sm->rb.rc, bpe, blocks)) return LSIM_E_INVALID;
+    hipLaunchKernelGGL(lsim_k_sensor_capture_inst, dim3(blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *sm, inst, bpe, ls_sm_tick_mod(*sm));
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
 #endif

@@ -8,11 +8,15 @@
 //   0. ls_sm_due first: tick, the flags and the env are the block's, episode_length[env] is one scalar load, so the test costs a few scalar
 //      instructions and a block of an env that is not due ends before the forward kinematics, before it touches LDS and before any barrier.
 //      With period P and stagger, P - 1 blocks in P are such empty blocks;
-//   1. the prologue of lsim_k_raycast_bodies (ls_rcb_fk, ls_rcb_prim) unless the struct is of the terrain-only form, which skips it and LDS altogether;
-//   2. ls_sm_raw_bodies / ls_sm_raw_terrain: ls_rcb_ray / ls_rc_ray up to their store, returning the value instead.  They are copies, not edits:
-//      the two existing kernels inline the originals and their results must not move.  The casts themselves (ls_rcb_cast, ls_rc_cast) are shared;
+//   1. the prologue of lsim_k_raycast_bodies (ls_rcb_block: ls_rcb_fk, ls_rcb_prim and their barriers) unless the struct is of the terrain-only
+//      form, which skips it and LDS altogether;
+//   2. ls_sm_raw_bodies / ls_sm_raw_terrain: one line each, ls_rcb_value / ls_rc_value at the tables' direction and scale.  ls_rc_value is the
+//      very function ls_rc_ray stores the result of, so the terrain-only identity model writes lsim_raycast's bits by construction of the
+//      source; ls_rcb_value is shared with lsim_k_sensor_capture_inst, and ls_rcb_ray is its text once more (ls_raycast_bodies.h says why).
+//      Compared on the device against the commit that still had a copy per launch: profiles/raycast_refactor_ab.json;
 //   3. ls_sm_store: the clean value to out, one Philox block per ray, the model, and the ray's own column of hist -- K slots hist_stride floats
-//      apart, lane = consecutive r, so every slot is read and written by a wave as one coalesced 256-byte line, and no lane reads what another writes.
+//      apart, lane = consecutive r, so every slot is read and written by a wave as one coalesced 256-byte line, and no lane reads what another
+//      writes.  It is three shared pieces (ls_sm_clean, ls_sm_draw, ls_sm_history) around the model line; ls_si_store is the same three around its own.
 #pragma once
 #include "ls_raycast_bodies.h"
 #include "ls_math.h"
@@ -30,87 +34,32 @@ LS_RC_FN bool ls_sm_due(const lsim_sensor_model_t& sm, int env, uint32_t tick_mo
     return ls_sensor_due(sm.flags, sm.episode_length, sm.period, sm.stagger, env, tick_mod, fill);
 }
 
-// ls_rc_ray without its store: the value lsim_raycast writes for ray r of env; hit = (t < far), label 1 / 0
+// step 2: the value and label lsim_raycast / lsim_raycast_bodies write for ray r of env -- the shared ray routines at the tables' direction and scale
 LS_RC_FN float ls_sm_raw_terrain(const lsim_raycast_t& rc, int env, int r, bool& hit, int& label) {
-    const float* rs = rc.root_states + (size_t)13 * (size_t)env;
-    const float* mt = rc.mount + (size_t)7 * (size_t)env;
-    const LsRcV3 mp = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ls_rc_v3(mt[0], mt[1], mt[2]));
-    const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
-    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], ls_rc_v3(rc.dirs[3 * r], rc.dirs[3 * r + 1], rc.dirs[3 * r + 2]));
-    const LsRcV3 d = ls_rc_rot(rs[3], rs[4], rs[5], rs[6], ds);
-    const float sc = rc.scale ? rc.scale[r] : 1.0f;
-    long long* state = (long long*)rc.state;
-    float t = rc.far;
-    if (ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
-        LsRcCount cnt;
-        cnt.cells = 0; cnt.tris = 0;
-        t = ls_rc_cast(rc, o, d, cnt);
-#if defined(LS_RAYCAST_COUNTERS)
-        ls_rc_count(state + 2, cnt.cells);
-        ls_rc_count(state + 3, cnt.tris);
-#endif
-    } else {
-        ls_rc_count(state, 1);
-    }
-    hit = t < rc.far;
-    label = hit ? 1 : 0;
-    return t * sc;
+    return ls_rc_value(rc, env, rc.dirs + 3 * r, rc.scale ? rc.scale + r : nullptr, hit, label);
 }
-
-// ls_rcb_ray without its stores: the value and the label lsim_raycast_bodies writes for ray r of env; hit = (t < far)
 LS_RC_FN float ls_sm_raw_bodies(const lsim_raycast_bodies_t& rb, const LsRcbShared& sh, int env, int r, bool& hit, int& label) {
-    const lsim_raycast_t& rc = rb.rc;
-    const float* rs = rc.root_states + (size_t)13 * (size_t)env;
-    const float* mt = rc.mount + (size_t)7 * (size_t)env;
-    float qx = rs[3], qy = rs[4], qz = rs[5], qw = rs[6];
-    if (rb.flags & LSIM_RAYCAST_FRAME_YAW) {
-        const float n = 1.0f / sqrtf(qz * qz + qw * qw);
-        qx = 0.0f; qy = 0.0f; qz *= n; qw *= n;
-    }
-    const LsRcV3 mp = ls_rc_rot(qx, qy, qz, qw, ls_rc_v3(mt[0], mt[1], mt[2]));
-    const LsRcV3 o = ls_rc_v3(rs[0] + mp.x, rs[1] + mp.y, rs[2] + mp.z);
-    const LsRcV3 ds = ls_rc_rot(mt[3], mt[4], mt[5], mt[6], ls_rc_v3(rc.dirs[3 * r], rc.dirs[3 * r + 1], rc.dirs[3 * r + 2]));
-    const LsRcV3 d = ls_rc_rot(qx, qy, qz, qw, ds);
-    const float sc = rc.scale ? rc.scale[r] : 1.0f;
-    long long* state = (long long*)rc.state;
-    float t = rc.far;
-    label = 0;
-    const bool joints_ok = (sh.bad[0] | sh.bad[1] | sh.bad[2] | sh.bad[3]) == 0;
-    if (joints_ok && ls_rc_finite(o.x) && ls_rc_finite(o.y) && ls_rc_finite(o.z) && ls_rc_finite(d.x) && ls_rc_finite(d.y) && ls_rc_finite(d.z)) {
-        LsRcCount cnt;
-        cnt.cells = 0; cnt.tris = 0;
-        int tested = 0;
-        const float tb = ls_rcb_cast(sh, mp, d, rc.near, rc.far, label, tested);
-        lsim_raycast_t walk = rc;               // the shared walk, bounded by the body hit
-        walk.far = tb;
-        t = ls_rc_cast(walk, o, d, cnt);
-        if (t < tb) label = 1;
-#if defined(LS_RAYCAST_COUNTERS)
-        ls_rc_count(state + 1, tested);
-        ls_rc_count(state + 2, cnt.cells);
-        ls_rc_count(state + 3, cnt.tris);
-#endif
-    } else {
-        ls_rc_count(state, 1);
-    }
-    hit = t < rc.far;
-    return t * sc;
+    return ls_rcb_value(rb, sh, env, rb.rc.dirs + 3 * r, rb.rc.scale ? rb.rc.scale + r : nullptr, hit, label);
 }
 
-// step 3: the clean value and label, the model (lsim.h states every line of it) and the ray's column of the history
-LS_RC_FN void ls_sm_store(const lsim_sensor_model_t& sm, int env, int r, float raw, bool hit, int label, bool fill) {
-    const lsim_raycast_bodies_t& rb = sm.rb;
+// step 3 comes in three pieces, which ls_si_store (ls_sensor_instrument.h) shares: the two stores differ in the model line between (b) and (c)
+// and in the slot count Ke alone.
+// (a) the clean value and label
+LS_RC_FN void ls_sm_clean(const lsim_raycast_bodies_t& rb, int env, int r, float raw, int label) {
     rb.rc.out[(size_t)env * (size_t)rb.rc.out_stride + (size_t)r] = raw;
     if (rb.labels) rb.labels[(size_t)env * (size_t)rb.label_stride + (size_t)r] = (uint8_t)label;
+}
+// (b) the ray's Philox block: the bounded normal g of three uniforms, and the dropout uniform u3
+LS_RC_FN float ls_sm_draw(const lsim_sensor_model_t& sm, int env, int r, float& u3) {
     uint32_t c[4] = {(uint32_t)env, (uint32_t)sm.tick, (uint32_t)LSIM_RNG_SENSOR, (sm.stream_id << 16) | (uint32_t)r};
     philox4x32_10(c, sm.seed, sm.rank);
-    const float u0 = u32_to_u01(c[0]), u1 = u32_to_u01(c[1]), u2 = u32_to_u01(c[2]), u3 = u32_to_u01(c[3]);
-    const float g = 2.0f * ((u0 + u1 + u2) - 1.5f);
-    float v = raw;
-    if (hit) {
-        v = raw + (sm.sigma0 + sm.sigma2 * raw * raw) * g;
-        if (u3 < sm.p_drop) v = sm.drop_value;
-    }
+    const float u0 = u32_to_u01(c[0]), u1 = u32_to_u01(c[1]), u2 = u32_to_u01(c[2]);
+    u3 = u32_to_u01(c[3]);
+    return 2.0f * ((u0 + u1 + u2) - 1.5f);
+}
+// (c) clip, normalise, and the ray's column of the history: shifted over its first Ke <= K slots, the slots from Ke - 1 on taking the new value
+// (Ke = K is the plain shift of all K slots)
+LS_RC_FN void ls_sm_history(const lsim_sensor_model_t& sm, int env, int r, float v, int Ke, bool fill) {
     v = fminf(fmaxf(v, sm.clip_lo), sm.clip_hi);
     const float y = (v - sm.offset) * sm.gain;
     const int K = sm.latency + sm.frames;
@@ -119,9 +68,22 @@ LS_RC_FN void ls_sm_store(const lsim_sensor_model_t& sm, int env, int r, float r
     if (fill) {
         for (int k = 0; k < K; ++k) h[(size_t)k * hs] = y;
     } else {
-        for (int k = 0; k + 1 < K; ++k) h[(size_t)k * hs] = h[(size_t)(k + 1) * hs];
-        h[(size_t)(K - 1) * hs] = y;
+        for (int k = 0; k + 1 < Ke; ++k) h[(size_t)k * hs] = h[(size_t)(k + 1) * hs];
+        for (int k = Ke - 1; k < K; ++k) h[(size_t)k * hs] = y;
     }
+}
+
+// step 3: the clean value and label, the model (lsim.h states every line of it) and the ray's column of the history
+LS_RC_FN void ls_sm_store(const lsim_sensor_model_t& sm, int env, int r, float raw, bool hit, int label, bool fill) {
+    ls_sm_clean(sm.rb, env, r, raw, label);
+    float u3;
+    const float g = ls_sm_draw(sm, env, r, u3);
+    float v = raw;
+    if (hit) {
+        v = raw + (sm.sigma0 + sm.sigma2 * raw * raw) * g;
+        if (u3 < sm.p_drop) v = sm.drop_value;
+    }
+    ls_sm_history(sm, env, r, v, sm.latency + sm.frames, fill);
 }
 
 // ---- host side: argument checks shared by the library and the CPU shim (no launch happens before they pass)
@@ -155,8 +117,8 @@ static inline uint32_t ls_sm_tick_mod(const lsim_sensor_model_t& sm) { return (u
 __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture(const lsim_sensor_model_t sm, int blocks_per_env, uint32_t tick_mod) {
     __shared__ LsRcbShared sh;
     const lsim_raycast_bodies_t& rb = sm.rb;
-    const int slot = (int)blockIdx.x / blocks_per_env, chunk = (int)blockIdx.x - slot * blocks_per_env;
-    const int env = slot * rb.rc.env_stride, lane = (int)threadIdx.x, r = chunk * LS_RC_BLOCK + lane;
+    int env, r;
+    ls_rc_block(rb.rc, blocks_per_env, env, r);
     if (env >= rb.rc.num_envs) return;          // the whole block: env is blockIdx's
     bool fill;
     if (!ls_sm_due(sm, env, tick_mod, fill)) return;     // the whole block again, before LDS and the barriers
@@ -164,10 +126,7 @@ __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture(const lsim_
     int label = 0;
     float raw = 0.0f;
     if (rb.robots) {
-        if (lane < LSIM_NUM_LEGS) ls_rcb_fk(rb, sh, env, lane);
-        __syncthreads();
-        if (lane < sh.nprims) ls_rcb_prim(rb, sh, env, lane);
-        __syncthreads();
+        ls_rcb_block(rb, sh, env, (int)threadIdx.x);
         if (r < rb.rc.num_rays) raw = ls_sm_raw_bodies(rb, sh, env, r, hit, label);
     } else if (r < rb.rc.num_rays) {
         raw = ls_sm_raw_terrain(rb.rc, env, r, hit, label);
@@ -178,10 +137,10 @@ __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture(const lsim_
 extern "C" int lsim_sensor_capture(const lsim_sensor_model_t* sm, void* stream) {
     const int rv = ls_sm_validate(sm);
     if (rv != LSIM_OK) return rv;
-    const int bpe = ls_rc_blocks_per_env(sm->rb.rc);
-    const long long blocks = (long long)bpe * ls_rc_env_slots(sm->rb.rc);
-    if (blocks > 0x7fffffffLL) return LSIM_E_INVALID;
-    hipLaunchKernelGGL(lsim_k_sensor_capture, dim3((unsigned)blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *sm, bpe, ls_sm_tick_mod(*sm));
+    int bpe;
+    unsigned blocks;
+    if (!ls_rc_grid(sm->rb.rc, bpe, blocks)) return LSIM_E_INVALID;
+    hipLaunchKernelGGL(lsim_k_sensor_capture, dim3(blocks), dim3(LS_RC_BLOCK), 0, (hipStream_t)stream, *sm, bpe, ls_sm_tick_mod(*sm));
     return hipGetLastError() == hipSuccess ? LSIM_OK : LSIM_E_HIP;
 }
 #endif
