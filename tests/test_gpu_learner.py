@@ -953,6 +953,10 @@ def test_gradient_arena_changes_nothing_but_where_the_gradients_live(monkeypatch
     assert FL._arena is None
     for k in a:
         assert torch.equal(a[k], b[k]), k
+    gen = ra.alg.storage.mini_batch_generator(4, 1)         # the shuffled observation fields are handed out as contiguous rows
+    mb = next(gen)
+    gen.close()
+    assert mb[0].is_contiguous() and mb[1].is_contiguous() and mb[0].shape[1] == 270 and mb[1].shape[1] == 238
     FL.set_grad_arena(None)
 
 
@@ -1080,85 +1084,3 @@ def test_gather_rows_equals_advanced_indexing():
         buf = torch.full((rows - 3, ld), 7.0, device="cuda:0")
         out = _gather_rows(f, perm, out=buf[:, :cols])
         assert out.data_ptr() == buf.data_ptr() and torch.equal(out, f[perm]) and bool((buf[:, cols:] == 7.0).all()), (rows, cols, ld)
-
-
-@pytest.mark.parametrize("k_in,n_out,B", [(512, 256, 102400), (256, 128, 102400), (128, 128, 20480 + 12), (512, 256, 4099)])
-def test_weight_gradient_on_the_bf16_pipe_is_an_fp32_result(k_in, n_out, B):
-    """lsim_wgrad_split_bf16(1): the weight / bias gradient and the ELU backward of the 128-multiple layers with every fp32 operand split
-    exactly into three bf16 terms and six products per pair (csrc/ls_learn.h: lsim_k_linear_wgrad_split).  Against fp64 sums its error must
-    not exceed the default fp32-pipe kernel's (up to 1.25 x: the two sum in different orders); grad_pre is the same elementwise product, bit
-    for bit; ragged batches (rows past the last whole step of 32) and gradient-like operands (wide magnitude range, half the ELU units
-    saturated) included."""
-    import ctypes
-    from isaacgymloco_amd import lib
-    L = lib.load()
-    gen = torch.Generator(device="cuda:0").manual_seed(k_in + n_out + B)
-    x = torch.randn(B, k_in, device="cuda:0", generator=gen)
-    g = torch.randn(B, n_out, device="cuda:0", generator=gen) * torch.exp(2.0 * torch.randn(B, 1, device="cuda:0", generator=gen)) * 1e-3
-    z = torch.nn.functional.elu(torch.randn(B, n_out, device="cuda:0", generator=gen))
-    gp64 = g.double() * torch.where(z > 0, torch.ones_like(z), z + 1.0).double()
-    ref_w, ref_b = gp64.t() @ x.double(), gp64.sum(0)
-    s = torch.cuda.current_stream().cuda_stream
-
-    def run(on):
-        was = L.lsim_wgrad_split_bf16(on)
-        try:
-            need, parts = ctypes.c_size_t(), ctypes.c_int()
-            lib.check(L.lsim_linear_wgrad_workspace(B, k_in, n_out, ctypes.byref(need), ctypes.byref(parts)))
-            ws = torch.empty(need.value // 4, device="cuda:0")
-            dw, db, gy = torch.empty(n_out, k_in, device="cuda:0"), torch.empty(n_out, device="cuda:0"), torch.empty(B, n_out, device="cuda:0")
-            lib.check(L.lsim_linear_elu_wgrad(x.data_ptr(), k_in, g.data_ptr(), n_out, z.data_ptr(), n_out, B, k_in, n_out, dw.data_ptr(), db.data_ptr(),
-                                              gy.data_ptr(), ws.data_ptr(), need.value, s), what="lsim_linear_elu_wgrad")
-            dw2 = torch.empty_like(dw)
-            lib.check(L.lsim_linear_wgrad(x.data_ptr(), k_in, gy.data_ptr(), n_out, B, k_in, n_out, dw2.data_ptr(), None, ws.data_ptr(), need.value, s))
-            torch.cuda.synchronize()
-            return dw, db, gy, dw2, parts.value
-        finally:
-            L.lsim_wgrad_split_bf16(was)
-    dw0, db0, gy0, dwp0, parts0 = run(0)
-    dw1, db1, gy1, dwp1, parts1 = run(1)
-    assert torch.equal(gy0, gy1) and torch.equal(gy1, gp64.float())
-    mag = gp64.abs().t() @ x.double().abs()                                   # sum |a||b| per output: what a summation error scales with
-    e0, e1 = float(((dw0.double() - ref_w).abs() / mag).max()), float(((dw1.double() - ref_w).abs() / mag).max())
-    p0, p1 = float(((dwp0.double() - ref_w).abs() / mag).max()), float(((dwp1.double() - ref_w).abs() / mag).max())
-    assert e1 <= 1.25 * e0 + 1e-9 and p1 <= 1.25 * p0 + 1e-9, (e0, e1, p0, p1)
-    assert e1 < 2e-6 and p1 < 2e-6, (e1, p1)
-    bmag = gp64.abs().sum(0)
-    assert float(((db1.double() - ref_b).abs() / bmag).max()) < 2e-6
-    assert not torch.equal(dw0, dw1) or parts0 != parts1                       # the switch did select another kernel
-
-
-def test_padded_shuffle_rows_and_padded_first_layers_change_the_update_only_by_rounding(monkeypatch):
-    """Round 6: the shuffled 270- / 238-wide observation fields live in rows 272 / 240 floats apart (zero padding) and the networks' first layers run
-    the library's fused Linear + ELU forward against zero-padded weight copies (learn/storage.py: _shuffle, learn/fused_linear.py: linear_elu_forward).
-    Against the same two iterations with contiguous rows (LSIM_PAD_SHUFFLED=0: those layers on BLAS + torch ELU): the minibatch views hold the same
-    values, the fused first layer equals F.elu(F.linear) to fp32 rounding, and the trained weights agree far inside one optimiser step."""
-    import torch.nn.functional as F
-    from isaacgymloco_amd.learn import fused_linear as FL
-
-    def run(pad):
-        monkeypatch.setenv("LSIM_PAD_SHUFFLED", "1" if pad else "0")
-        FL.set_grad_arena(None)
-        env, r = _make(seed=9)
-        r.enable_graphs()
-        r.learn(2, init_at_random_ep_len=False)
-        st = r.alg.storage
-        gen = st.mini_batch_generator(4, 1)
-        mb = next(gen)
-        gen.close()
-        return r, {k: v.clone() for k, v in r.alg.actor_critic.state_dict().items()}, mb
-    ra, a, mba = run(True)
-    obs, crit = mba[0], mba[1]
-    assert obs.shape[1] == 270 and obs.stride(0) == 272 and crit.shape[1] == 238 and crit.stride(0) == 240 and obs.data_ptr() % 16 == 0
-    ac = ra.alg.actor_critic
-    lin = ac.critic[0]
-    with torch.no_grad():
-        z = FL.linear_elu_forward(crit, lin.weight, lin.bias)
-        ref = F.elu(F.linear(crit.contiguous().double(), lin.weight.double(), lin.bias.double())).float()
-    assert FL._padded_weights, "the padded-weight form of the fused forward did not run"
-    torch.testing.assert_close(z, ref, rtol=1e-5, atol=2e-5)
-    rb, b, mbb = run(False)
-    assert mbb[0].is_contiguous() and mbb[1].is_contiguous()
-    for k in a:        # 2 iterations x 20 Adam steps at lr 1e-3 from identical states and identical rollouts of iteration 1
-        torch.testing.assert_close(a[k], b[k], rtol=0, atol=2e-3, msg=lambda m, k=k: f"{k}: {m}")
-    FL.set_grad_arena(None)

@@ -33,7 +33,7 @@ RULES = [   # (regex on the name without its round prefix, what it is, section)
     (r"^policy_.*\.pt$", "the trained actor-critic + simulator curriculum state after 1000 iterations (tools/train_probe.py ... checkpoint.pt): input of tools/trained_policy_physics.py", "4"),
     (r"^train_curve_.*\.json$", "learning curve (tools/train_probe.py): per-iteration reward, episode length, terrain level, losses", "4"),
     (r"^wgrad_knockouts\.txt$", "the shipped weight-gradient kernels alone: product / no operand loads in the loop / no MFMAs (diagnostic knock-out builds of round 6, since removed): where the time of VERDICT r5 task 3 is", "7.3"),
-    (r"^padded_shuffle_ab\.txt$", "default train line with 16-byte-aligned shuffled observation rows + padded-weight fused first layers against contiguous rows (no gain: opt-in)", "7.3"),
+    (r"^padded_shuffle_ab\.txt$", "default train line with 16-byte-aligned shuffled observation rows + padded-weight fused first layers against contiguous rows (no gain: the path was removed later)", "7.3"),
     (r"^cpu_scaling_probe\.txt$", "the GPU box's host: cgroup CPU grant and oracle/cpu_bench.py at 8 .. 256 threads", "8"),
     (r"^kernel_a_ifetch_pmc\.txt$", "kernel A: instruction-cache and fetch counters (93 KB of code against a 64 KB cache: hit rate 99.76 %, not the limiter)", "6"),
     (r"^amp_host_enqueue\.txt$", "host time to enqueue one update against its wall time, default and AMP, before / after the sample indices stopped draining the pipeline (learn/amp.py: _IndexUploader)", "10"),
@@ -70,6 +70,7 @@ RULES = [   # (regex on the name without its round prefix, what it is, section)
 STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs, mode, actions, solver) before quoting `roofline.traffic` / `valu_issue_frac`; rewritten by every round's script", "6, 8"),
               "ref_cpu_partial.json": ("the reference's own torch post-physics stack and learner timed in the build container (no physics): SURVEY 8d legs B / C", "8"),
               "depth_chain_refactor_ab.json": ("parent commit against the commit that moved the memory's per-env buffers to the sensor, alternating runs in one session: `tools/depth_memory_time.py` and `tools/vision_train_time.py --memory` medians with the parent's run-to-run spread", "7.12"),
+              "learner_optin_retire_ab.json": ("parent commit against the commit that removed the bf16-pipe weight gradient and the padded shuffle, alternating runs in one session: `bench.py --gpus 1 --steps 1000 --warmup 100` (`value`, `learn_s_per_update`) and the same with `--full --no-cpu-baseline` (`update_host_enqueue_s`), medians with the parent's run-to-run spread", "7.3"),
               "depth_encoder_time.json": ('`tools/depth_encoder_time.py`, N = 4096, 64 × 48 camera, 2 frames, the default network: `lsim_depth_encode` with every env due and at period 5 staggered, the torch forward on the same device, `lsim_sensor_capture` and kernel A in one process', "7.8"),
               "depth_memory_time.json": ('`tools/depth_memory_time.py`, N = 4096, L = 64, P = 45, H = 64: `lsim_depth_memory_step` next to kernel A and the staggered encoder launch; `sequence_device` forward + backward, the two serial kernels alone and the `nn.GRUCell` loop at T = 99, n = 1024 / 4096, alternating samples in one process', "7.12"),
               "eval_time.json": ('`tools/eval_time.py`, N = 4096, 400 groups: `lsim_eval_accumulate` next to the env step, kernel A and the torch statements it replaces, HIP events', "7.5"),
