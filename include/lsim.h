@@ -49,7 +49,9 @@ extern "C" {
                                     lsim_sensor_mount_jitter + LSIM_RNG_SENSOR_MOUNT (a sensor's mount pose redrawn per episode, on the device);
                                     lsim_sensor_instrument + lsim_sensor_capture_inst + LSIM_RNG_SENSOR_INSTRUMENT (a sensor's latency, noise level,
                                     depth-scale error and field of view redrawn per episode, and the capture that reads them);
-                                    lsim_elevation_map (a robot-centred height grid per env, fused from a sensor's depth rows and the robot's pose) */
+                                    lsim_elevation_map (a robot-centred height grid per env, fused from a sensor's depth rows and the robot's pose);
+                                    lsim_odometry_step + LSIM_RNG_ODOMETRY (an estimated base pose that drifts with the distance travelled) and
+                                    lsim_map_rows (the map's scan as the rows an actor reads, one launch) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -170,8 +172,11 @@ enum lsim_rng_tag {
                                   (stream_id << 16) | ray -- one whole block per ray, all four words used      */
     LSIM_RNG_SENSOR_MOUNT = 16, /* lsim_sensor_mount_jitter (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: position x y z and rotation x, block 1: rotation y z, two words unused */
-    LSIM_RNG_SENSOR_INSTRUMENT = 17 /* lsim_sensor_instrument (no reference site): step word = (uint32) tick, the fourth counter word =
+    LSIM_RNG_SENSOR_INSTRUMENT = 17, /* lsim_sensor_instrument (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: latency, noise gain, depth scale, depth quad, block 1: tan scale, three words unused */
+    LSIM_RNG_ODOMETRY = 18     /* lsim_odometry_step (no reference site): step word = (uint32) tick, the fourth counter word =
+                                  (stream_id << 16) | b, b = 0, 1 -- block 0: the step's yaw, position and height noise, one word unused,
+                                  block 1: the episode's scale, yaw and height bias, one word unused */
 };
 
 /* ---- robot model: the URDF after Isaac Gym's fixed-joint collapse ----
@@ -1326,7 +1331,8 @@ int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, v
  *     scan[e][j] = height,  known[e][j] = 1;      otherwise  scan[e][j] = p.z - unknown_drop,  known[e][j] = 0
  *   (also when w is not finite, q.z = q.w = 0, or its cell is out of range).  No NaN is ever written.
  * `assumed_mount` is a pointer of its own: pointed at a sensor's NOMINAL mount while the capture reads a jittered one, the map is wrong in
- *   the way a robot's is.  NOT BUILT: averaging or a variance per cell, overhangs, odometry drift, latency compensation of the pose. */
+ *   the way a robot's is.  Pointing `root_states` at lsim_odometry_step's `est` gives the map a drifting pose.  NOT BUILT: averaging or a variance
+ *   per cell, overhangs, latency compensation of the pose. */
 typedef struct lsim_elevation_map {
     const float* root_states;         /* [N,13] simulator buffer, read only */
     const float* assumed_mount;       /* [N,7] the mount pose the map believes in: position, quaternion xyzw */
@@ -1365,6 +1371,92 @@ typedef struct lsim_elevation_map {
  * labels given with label_stride < R; scan_stride or known_stride < P; tick < 0; period < 1; stagger outside 0..1; env_stride < 1;
  * num_envs < 1; a flag bit other than the sensor model's two; both of them set. */
 int lsim_elevation_map(const lsim_elevation_map_t* em, void* stream);
+
+/* ---- odometry: an ESTIMATED base pose that drifts with the distance travelled, for whatever should see the world as a robot does (an
+ * elevation map given `est` for its root_states is placed with dead-reckoning error in scale, yaw and height).  ONE launch, one lane per
+ * visited env, under the rules of lsim_sensor_mount_jitter (caller's stream, no host synchronisation, raw pointers only, tick by value).  It
+ * reads root_states and episode_length, and reads and writes its own state `odo`; it writes rows of `est`.
+ *
+ * Which envs.  Env e is visited when e % env_stride == 0.  A visited env is FRESH when
+ *     (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0
+ *   LSIM_SENSOR_RESETS_ONLY is accepted and changes nothing here.  For an env that is not visited NOTHING is written.
+ * State.  odo[e] is 12 floats, 48 bytes: {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0} -- the position error in metres,
+ *   h the Cayley half-tangent of the yaw error (the error angle is 2 atan h), the episode's three biases, and the true xy of the last launch.
+ *   The three zeros are written at every launch.
+ * Draws.  Two Philox4x32-10 blocks, key (seed, rank), counters (e, (uint32_t)tick, LSIM_RNG_ODOMETRY, (stream_id << 16) | b), b = 0, 1:
+ *     x0..x3 = block 0, x4..x7 = block 1;   u_k = (x_k >> 8) * 2^-24,   s_k = 2 u_k - 1  (exact in fp32), k = 0, 1, 2 and 4, 5, 6;
+ *     x3 and x7 are not used.  s0..s2 are the STEP's noise (used by an env that is not fresh), s4..s6 the EPISODE's biases (used by a fresh one).
+ * (p, q) = root_states[e][0:3], [3:7].  All arithmetic in fp32 (a compiler may contract a product and a sum); square roots and quotients are
+ * correctly rounded.
+ *   Fresh env:      dx = dy = dz = h = 0;   scale = s4 * scale_range;   yaw_bias = s5 * yaw_range;   z_bias = s6 * z_range;   prev = p.xy
+ *   Otherwise, with a finite root_states[e][0:7]:
+ *     D = p.xy - prev                          (D = (0, 0) when a component of prev is not finite)
+ *     L = sqrt(D.x^2 + D.y^2)
+ *     h += 0.5 * L * (yaw_bias + yaw_noise * s0)
+ *     c = 1 / sqrt(1 + h^2);   d = (0, 0, h c, c)  xyzw         (the Cayley map, as in the mount jitter: no transcendental function)
+ *     r = R(d) (D.x, D.y, 0)                   (R as in lsim_raycast:  v + 2 w (u x v) + 2 u x (u x v))
+ *     k = 1 + (scale + pos_noise * s1)
+ *     dx += k r.x - D.x;   dy += k r.y - D.y
+ *     dz += L * (z_bias + z_noise * s2)
+ *     prev = p.xy
+ *   Otherwise (a non-finite component of root_states[e][0:7]):   dx = dy = dz = h = 0;   prev = (NaN, NaN), both words 0x7FC00000 -- the next
+ *     finite step integrates D = 0 and the drift starts again from there; the biases are kept.  (A fresh env with such a pose draws its biases
+ *     and stores prev = p.xy as it is.)
+ *   Every visited env, fresh or not, with c and d formed from the h just stored (h = 0: d = (0, 0, 0, 1)):
+ *     est[e][0:3] = p + (dx, dy, dz)
+ *     est[e][3:7] = d (x) q, the Hamilton product written out as in lsim_sensor_mount_jitter, not renormalised.  d turns about the WORLD z:
+ *         the estimate is wrong in yaw only; roll and pitch against gravity are what an IMU observes.
+ *     est[e][7:13] = root_states[e][7:13]
+ *     -- except that a non-finite root_states[e][0:7] is copied to est[e][0:7] unchanged (whatever reads est goes on counting it as bad).
+ * Consequences.  Every increment is proportional to L: a second launch on the same tick with unmoved robots changes nothing (a fresh env draws
+ *   the same biases again; the others integrate D = 0).  All-zero ranges give est[e][0:7] == root_states[e][0:7] bit for bit, up to -0 -> +0,
+ *   and dx = dy = dz = h = 0 for ever.  The yaw error bends the PATH: the increment is rotated by the error the estimate has accumulated, so a
+ *   yaw bias of b rad/m displaces the estimate by about b s^2 / 2 after s metres straight ahead. */
+typedef struct lsim_odometry {
+    const float* root_states;         /* [N,13] simulator buffer, read only, 4-byte aligned */
+    float* est;                       /* [N,13] the estimated root states; 4-byte aligned; must not be `root_states` */
+    float* odo;                       /* [N,12] the state above; 16-byte aligned; zeroed by the caller at creation */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    int64_t tick;                     /* >= 0, by value */
+    uint32_t seed, rank, stream_id;   /* as lsim_sensor_model_t's; stream_id < 65536 */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    float scale_range;                /* half-width of the episode's distance-scale error, no unit: finite, >= 0 */
+    float yaw_range;                  /* half-width of the episode's yaw bias, rad per metre travelled: finite, >= 0 */
+    float z_range;                    /* half-width of the episode's height bias, metres per metre travelled: finite, >= 0 */
+    float pos_noise, yaw_noise, z_noise;  /* half-widths of the per-step noise on the same three, in the same units: finite, >= 0 */
+} lsim_odometry_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: od == NULL; root_states or est NULL or
+ * not 4-byte aligned; odo NULL or not 16-byte aligned; episode_length NULL or not 8-byte aligned; est == root_states; num_envs < 1;
+ * env_stride < 1; tick < 0; stream_id >= 65536; one of the six ranges negative or not finite; a flag bit other than the sensor model's two;
+ * both of them set. */
+int lsim_odometry_step(const lsim_odometry_t* od, void* stream);
+
+/* ---- map rows: the elevation map's scan as the rows an actor reads (lsim_policy_extra.rows), in the units of the privileged height scan.
+ * ONE launch under the same rules, elementwise over every visited env (e % env_stride == 0) and every column:
+ *     rows[e * ld + j]     = clamp(pose[e][2] - z_offset - scan[e * scan_stride + j], -1, 1) * scale       j < P
+ *                            (two subtractions in this order, the clamp, then one product; nothing a compiler can contract)
+ *     rows[e * ld + P + j] = known[e * known_stride + j] ? 1.0f : 0.0f                                    j < P, channels == 2 only
+ *   A non-finite pose[e][2] or scan value writes 0 to the first block: no NaN is ever written.  Columns >= channels * P of a row, and rows
+ *   of envs that are not visited, are not touched.  `pose` is the pose the map was given (lsim_elevation_map_t.root_states: the estimate
+ *   with odometry, else the simulator's).  With z_offset = 0.5 and scale = obs_scales.height_measurements, fed LSIM_BUF_MEASURED_HEIGHTS and
+ *   LSIM_BUF_ROOT_STATES, the first block is the noise-free privileged observation's scan block bit for bit. */
+typedef struct lsim_map_rows {
+    const float* scan;                /* [N,scan_stride] lsim_elevation_map_t.scan; 4-byte aligned */
+    const uint8_t* known;             /* [N,known_stride] lsim_elevation_map_t.known; read only when channels == 2, NULL refused then */
+    const float* pose;                /* [N,13] root states, only [e][2] is read; 4-byte aligned */
+    float* rows;                      /* [N,ld]; 4-byte aligned */
+    int32_t num_points;               /* P in 1..LSIM_ELEVATION_MAP_MAX_POINTS */
+    int32_t channels;                 /* 1: heights; 2: heights, then known */
+    int32_t scan_stride, known_stride;/* elements between rows: >= P (known_stride ignored when channels == 1) */
+    int32_t ld;                       /* floats between rows of `rows`: >= channels * P */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    float z_offset, scale;            /* finite */
+} lsim_map_rows_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: mr == NULL; scan, pose or rows NULL or
+ * not 4-byte aligned; channels == 2 and known NULL; P outside 1..LSIM_ELEVATION_MAP_MAX_POINTS; channels outside 1..2; scan_stride < P;
+ * channels == 2 and known_stride < P; ld < channels * P; z_offset or scale not finite; num_envs < 1; env_stride < 1. */
+int lsim_map_rows(const lsim_map_rows_t* mr, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

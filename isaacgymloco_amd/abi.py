@@ -114,6 +114,8 @@ LsimSensorModel = STRUCTS["lsim_sensor_model_t"]
 LsimSensorMountJitter = STRUCTS["lsim_sensor_mount_jitter_t"]
 LsimSensorInstrument = STRUCTS["lsim_sensor_instrument_t"]
 LsimElevationMap = STRUCTS["lsim_elevation_map_t"]
+LsimOdometry = STRUCTS["lsim_odometry_t"]
+LsimMapRows = STRUCTS["lsim_map_rows_t"]
 LsimDepthEncoder = STRUCTS["lsim_depth_encoder_t"]
 LsimDepthEncoderBwd = STRUCTS["lsim_depth_encoder_bwd_t"]
 

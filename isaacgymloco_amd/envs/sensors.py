@@ -52,6 +52,17 @@ capture, same stream, tick and flags, inserts the envs just captured and resampl
 `cam.map_scan()` is the live [N, P] tensor in the layout of LSIM_BUF_MEASURED_HEIGHTS, `cam.map_known()` says which points the map
 knows.  The map believes in the NOMINAL mount, so a jittered camera bends it as it would on a robot.  Without an attached map nothing of
 this is created or launched.
+
+Odometry (`cam.attach_map(m, odometry=OdometryError(scale=0.02, yaw_per_m=0.01, z_per_m=0.01, noise=(0.005, 0.002, 0.002)))`,
+lsim_odometry_step): a robot does not know where it is, it integrates its steps -- so the map is placed with an ESTIMATED pose that drifts
+with the distance travelled, in scale, yaw and height, by biases every env draws when it starts an episode plus a per-step noise.  One
+small launch ahead of every capture integrates the step each env took since the last one; the map's launch reads `cam.odometry_pose()`
+where it read root_states, and the capture itself goes on reading the true pose: the camera is where the robot is.  Without `odometry`
+nothing of this is created or launched and the map reads root_states.
+
+Map rows (`cam.attach_map_rows(channels=("height", "known"))`, lsim_map_rows; needs a map): one launch behind the map's turns its scan into
+the rows an actor reads -- the heights relative to the pose the map was given, clipped and scaled exactly as the privileged height scan
+is, and optionally which of them the map knows; `cam.map_rows()` is the live [N, channels * P] tensor (learn/map_policy.py).
 """
 import ctypes
 import math
@@ -230,6 +241,45 @@ class ElevationMap:
         return f"ElevationMap({', '.join(f'{k}={v!r}' for k, v in self.record().items() if k != 'points')}, points={'None' if self.points is None else len(self.points)})"
 
 
+class OdometryError:
+    """Dead-reckoning error of the pose an elevation map is placed with (lsim_odometry_step; include/lsim.h states every formula).  When an
+    env starts an episode it draws three biases, uniform in [-v, v]: `scale`, the relative error of every distance travelled; `yaw_per_m`,
+    radians of heading error per metre travelled; `z_per_m`, metres of height error per metre travelled.  `noise` = (pos, yaw, z): the
+    half-widths of a uniform error of the same three kinds drawn anew at every step.  All-zero values give the true pose bit for bit."""
+
+    def __init__(self, scale=0.0, yaw_per_m=0.0, z_per_m=0.0, noise=(0.0, 0.0, 0.0)):
+        self.scale, self.yaw_per_m, self.z_per_m = float(scale), float(yaw_per_m), float(z_per_m)
+        self.noise = tuple(float(v) for v in noise)
+        values = (self.scale, self.yaw_per_m, self.z_per_m) + self.noise
+        if len(self.noise) != 3 or any(not math.isfinite(v) or v < 0.0 for v in values):
+            raise ValueError(f"OdometryError: scale, yaw_per_m, z_per_m and the three of noise are finite half-widths >= 0, got {values}")
+
+    def record(self):
+        """the plain dict spec() stores and OdometryError(**record) reads"""
+        return {"scale": self.scale, "yaw_per_m": self.yaw_per_m, "z_per_m": self.z_per_m, "noise": list(self.noise)}
+
+    def ranges(self):
+        """the six ranges in the order of lsim_odometry_t"""
+        return (self.scale, self.yaw_per_m, self.z_per_m) + self.noise
+
+    def __eq__(self, other):
+        return isinstance(other, OdometryError) and self.ranges() == other.ranges()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return f"OdometryError(scale={self.scale}, yaw_per_m={self.yaw_per_m}, z_per_m={self.z_per_m}, noise={self.noise})"
+
+
+def parse_odometry(text):
+    """OdometryError of 'scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002' (any subset): the text the tools take"""
+    kw = {}
+    for item in ([] if text in ("", "default") else text.split(",")):
+        k, v = item.split("=")
+        kw[k] = tuple(float(x) for x in v.split(":")) if k == "noise" else float(v)
+    return OdometryError(**kw)
+
+
 def parse_elevation_map(text):
     """ElevationMap of 'size=32,resolution=0.0625,source=noisy,max_range=3,unknown_drop=0.4' (any subset; '' or 'default': the defaults):
     the text the tools take"""
@@ -260,7 +310,9 @@ class RaySensor:
     episode, and the capture is lsim_sensor_capture_inst.  With `instrument=None` there is no such tensor and no such launch.
     `attach_map(m)` (an ElevationMap; needs a model): lsim_elevation_map behind every capture; `map_scan()` / `map_known()` are the live
     [N, P] samples, `map_heights()` a window-ordered copy for people and tools, `map_state()` the three raw arrays.  Without it nothing
-    of this is allocated or launched."""
+    of this is allocated or launched.  `attach_map(m, odometry=OdometryError(...))`: lsim_odometry_step ahead of every capture, and the map
+    reads `odometry_pose()` [N, 13] (its state: `odometry_state()` [N, 12]) where it read root_states.  `attach_map_rows(channels)`:
+    lsim_map_rows behind the map's launch, `map_rows()` the live [N, channels * P] rows an actor reads."""
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
                  see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
@@ -317,6 +369,8 @@ class RaySensor:
         self._labels = None
         self._encoder = self._latent = self._memory = self._memory_h = self._memory_rows = None
         self.map = self._em = self._map = None
+        self.odometry = self._od = self._odo = None
+        self.map_channels = self._mr = self._rows = None
         if self._bodies:
             self._setup_bodies(rc, ignore_bodies, labels, dev)
         if model is not None:
@@ -428,6 +482,8 @@ class RaySensor:
                 self._mj.stream_id = int(value)
             if self._si is not None:
                 self._si.stream_id = int(value)
+            if self._od is not None:
+                self._od.stream_id = int(value)
 
     def _setup_bodies(self, rc, ignore_bodies, labels, dev):
         """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
@@ -506,6 +562,8 @@ class RaySensor:
         if self.model is not None:
             self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
             self._sm.tick, self._sm.flags = self.tick, int(flags)
+            if self._od is not None:            # the pose the map will be given: the step every env took since the last update
+                self._launch_odometry(self.tick, int(flags), stream)
             if self._mj is not None:            # first: the envs that start an episode are rendered, history and all, from their new pose
                 self._mj.tick, self._mj.flags = self.tick, int(flags)
                 lib.check(self._api.lsim_sensor_mount_jitter(ctypes.byref(self._mj), self._stream(stream)), what="lsim_sensor_mount_jitter")
@@ -550,9 +608,12 @@ class RaySensor:
             enc.encode_device(self, self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
         return enc
 
-    def attach_map(self, m):
+    def attach_map(self, m, odometry=None):
         """from now on every update() / refresh() is followed by lsim_elevation_map on the same stream with the same tick and flags (`m`: an
-        ElevationMap, or None: detach and free).  Inserts every env once now, from the present rows, when the sensor has captured before.
+        ElevationMap, or None: detach and free, odometry and map rows included).  Inserts every env once now, from the present rows, when
+        the sensor has captured before.  `odometry` (an OdometryError): the map is placed with the estimated pose of lsim_odometry_step,
+        enqueued ahead of every capture for every visited env (and once now, every env fresh, when the sensor has captured before); None:
+        the map reads root_states and no such launch is made.
         "noisy" reads the newest slot of the frame history with (a, b) = (1 / gain, offset), "clean" the `out` rows with (1, 0); the
         labels are passed when the sensor has them (only terrain is ground); the assumed mount is `mount_nominal`.
         Which ranges are points: above `near` and below max_range (None: 0.98 far) -- and for "noisy", whose values the model clamps to
@@ -561,9 +622,15 @@ class RaySensor:
         Refused (ElevationMap's docstring): frame="yaw", see_robot without labels, a drop_value inside the clip range."""
         if m is None:
             self.map = self._em = self._map = None
+            self.odometry = self._od = self._odo = None
+            self.map_channels = self._mr = self._rows = None
             return None
         if not isinstance(m, ElevationMap):
             raise TypeError(f"attach_map: expected an ElevationMap or None, got {type(m).__name__}")
+        if odometry is not None and not isinstance(odometry, OdometryError):
+            raise TypeError(f"attach_map: odometry is an OdometryError or None, got {type(odometry).__name__}")
+        if odometry is not None and not hasattr(self._api, "lsim_odometry_step"):
+            raise lib.LsimError("the loaded library has no lsim_odometry_step: rebuild it (there is no torch fall-back for the odometry)")
         if self.model is None:
             raise ValueError("attach_map needs a model (SensorModel): the tick, the period and the episode lengths that say who captured are the model's")
         if not hasattr(self._api, "lsim_elevation_map"):
@@ -625,14 +692,81 @@ class RaySensor:
         em.unknown_drop = float(env.cfg.rewards.base_height_target) if m.unknown_drop is None else m.unknown_drop
         if not em.t_lo < em.t_hi:
             raise ValueError(f"attach_map: no range is left between the nearest the sensor reports ({em.t_lo}) and max_range / the clip limit ({em.t_hi})")
+        self.odometry = self._od = self._odo = None
+        self.map_channels = self._mr = self._rows = None          # a new map: the rows of the old one go with it
+        if odometry is not None:
+            od = abi.LsimOdometry()
+            self._odo = {"est": env.root_states.detach().clone().contiguous(), "odo": torch.zeros((N, 12), dtype=torch.float32, device=dev)}
+            od.root_states, od.est, od.odo, od.episode_length = env.root_states.data_ptr(), self._odo["est"].data_ptr(), self._odo["odo"].data_ptr(), sm.episode_length
+            od.seed, od.rank, od.stream_id, od.num_envs, od.env_stride = sm.seed, sm.rank, sm.stream_id, N, self.env_stride
+            od.scale_range, od.yaw_range, od.z_range, od.pos_noise, od.yaw_noise, od.z_noise = odometry.ranges()
+            em.root_states = self._odo["est"].data_ptr()
+            self.odometry, self._od = odometry, od
         self.map, self._em, self._map = m, em, mp
         if self.tick >= 0:
+            if self._od is not None:
+                self._launch_odometry(self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], None)
             self._launch_map(self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], None)
         return m
+
+    def _launch_odometry(self, tick, flags, stream):
+        self._od.tick, self._od.flags = int(tick), int(flags)
+        lib.check(self._api.lsim_odometry_step(ctypes.byref(self._od), self._stream(stream)), what="lsim_odometry_step")
 
     def _launch_map(self, tick, flags, stream):
         self._em.tick, self._em.flags = int(tick), int(flags)
         lib.check(self._api.lsim_elevation_map(ctypes.byref(self._em), self._stream(stream)), what="lsim_elevation_map")
+        if self._mr is not None:            # the scan rows just rewritten, every visited env
+            lib.check(self._api.lsim_map_rows(ctypes.byref(self._mr), self._stream(stream)), what="lsim_map_rows")
+
+    def map_pose(self):
+        """live [N, 13] tensor: the pose the map is given -- odometry_pose() with odometry, else the env's root_states"""
+        self._need_map()
+        return self._odo["est"] if self._odo is not None else self.env.root_states
+
+    def odometry_pose(self):
+        """live [N, 13] tensor: the estimated root states (attach_map(m, odometry=...)); columns 7.. are root_states' own"""
+        if self._odo is None:
+            raise ValueError("the sensor has no odometry (attach_map(m, odometry=OdometryError(...)))")
+        return self._odo["est"]
+
+    def odometry_state(self):
+        """live [N, 12] tensor: row e = {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0} of env e (lsim.h)"""
+        if self._odo is None:
+            raise ValueError("the sensor has no odometry (attach_map(m, odometry=OdometryError(...)))")
+        return self._odo["odo"]
+
+    def attach_map_rows(self, channels=("height",)):
+        """from now on the map's launch of every update() / refresh() is followed by lsim_map_rows on the same stream: `map_rows()` is the
+        live [N, len(channels) * P] tensor of the map's scan as an actor reads it -- ("height",): clip(map_pose z - 0.5 - scan, -1, 1) *
+        obs_scales.height_measurements, the privileged height scan's expression; ("height", "known"): then map_known() as 0 / 1.  Needs
+        an attached map; builds the rows once now when the sensor has captured before.  None: detach and free."""
+        if channels is None:
+            self.map_channels = self._mr = self._rows = None
+            return None
+        channels = tuple(channels)
+        if channels not in (("height",), ("height", "known")):
+            raise ValueError(f"attach_map_rows: channels is ('height',) or ('height', 'known'), got {channels}")
+        mp = self._need_map()
+        if not hasattr(self._api, "lsim_map_rows"):
+            raise lib.LsimError("the loaded library has no lsim_map_rows: rebuild it (there is no torch fall-back for the map rows)")
+        N, P, C = int(self.env.num_envs), int(self._em.num_points), len(channels)
+        self._rows = torch.zeros((N, C * P), dtype=torch.float32, device=self._out.device)
+        mr = abi.LsimMapRows()
+        mr.scan, mr.known, mr.pose, mr.rows = mp["scan"].data_ptr(), mp["known"].data_ptr(), self.map_pose().data_ptr(), self._rows.data_ptr()
+        mr.num_points, mr.channels, mr.scan_stride, mr.known_stride, mr.ld = P, C, int(self._em.scan_stride), int(self._em.known_stride), C * P
+        mr.num_envs, mr.env_stride = N, self.env_stride
+        mr.z_offset, mr.scale = 0.5, float(self.env.lcfg.obs_scale_height)
+        self.map_channels, self._mr = channels, mr
+        if self.tick >= 0:
+            lib.check(self._api.lsim_map_rows(ctypes.byref(mr), self._stream(None)), what="lsim_map_rows")
+        return self._rows
+
+    def map_rows(self):
+        """live [N, channels * P] tensor: the rows lsim_map_rows writes (attach_map_rows)"""
+        if self._rows is None:
+            raise ValueError("the sensor has no map rows (attach_map_rows)")
+        return self._rows
 
     def _need_map(self):
         if self._em is None:
@@ -658,11 +792,12 @@ class RaySensor:
         return self._need_map()["state"][0]
 
     def map_heights(self):
-        """[N, G, G] COPY in window order -- [e, i, j] is the cell (cx - G/2 + i, cy - G/2 + j) around env e's present position -- with NaN
+        """[N, G, G] COPY in window order -- [e, i, j] is the cell (cx - G/2 + i, cy - G/2 + j) around env e's present position (the one the
+        map was given: the estimate with odometry) -- with NaN
         where the map knows nothing.  For people and tools (tools/sensor_frames.py); nothing on a hot path reads it."""
         mp, G, N = self._need_map(), self.map.size, int(self.env.num_envs)
         rinv = float(np.float32(1.0 / float(np.float32(self.map.resolution))))
-        c = torch.floor(self.env.root_states[:, :2] * rinv).to(torch.int64).clamp(-40000, 40000)
+        c = torch.floor(self.map_pose()[:, :2] * rinv).to(torch.int64).clamp(-40000, 40000)          # the window of the pose the map was given
         off = torch.arange(G, device=c.device) - G // 2
         ix, iy = c[:, 0:1] + off, c[:, 1:2] + off
         idx = ((ix & (G - 1)) * G)[:, :, None] + (iy & (G - 1))[:, None, :]
@@ -724,8 +859,8 @@ class RaySensor:
         dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
-        one there is no such key.  Likewise "instrument" holds an InstrumentError's record and "map" an attached ElevationMap's, each absent
-        without one."""
+        one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's and
+        "odometry" the OdometryError the map was attached with, each absent without one."""
         out = {"kind": "rays"}
         if hasattr(self, "width") and hasattr(self, "height"):
             out.update(kind="camera", width=int(self.width), height=int(self.height))
@@ -756,6 +891,8 @@ class RaySensor:
             out["instrument"] = self.instrument.record()
         if self.map is not None:
             out["map"] = self.map.record()
+        if self.odometry is not None:
+            out["odometry"] = self.odometry.record()
         return out
 
     @property
@@ -802,11 +939,12 @@ def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mo
     return s
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec"):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
-    (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor)."""
+    (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor),
+    `odometry` for the OdometryError that map is attached with (without a map it has nothing to act on)."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -835,6 +973,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
             raise ValueError(f"from_spec: elevation_map is 'spec', None or an ElevationMap, got {elevation_map!r}")
         r = spec.get("map")
         elevation_map = None if r is None else ElevationMap(**r)
+    if isinstance(odometry, str):
+        if odometry != "spec":
+            raise ValueError(f"from_spec: odometry is 'spec', None or an OdometryError, got {odometry!r}")
+        o = spec.get("odometry")
+        odometry = None if o is None else OdometryError(**o)
     kind = spec.get("kind", "rays")
     cls = DepthCamera if kind == "camera" else RaySensor
     sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
@@ -847,5 +990,5 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     if kind == "lidar":
         sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
     if elevation_map is not None:
-        sensor.attach_map(elevation_map)
+        sensor.attach_map(elevation_map, odometry=odometry)
     return sensor

@@ -1,7 +1,8 @@
 """Evaluate a trained policy on the device: metrics per robot x terrain type x terrain level, and state traces of chosen envs.
 
     python -m isaacgymloco_amd.learn.evaluate --task aliengo [--robots aliengo=0.5,go2=0.5] --checkpoint model.pt --envs 4096 --steps 1000 \
-        --commands 1.0,0,0 --out eval.json [--trace-envs 0,1 --trace-out trace.npz] [--blind] [--vision-metrics depth_influence,scan_error]
+        --commands 1.0,0,0 --out eval.json [--trace-envs 0,1 --trace-out trace.npz] [--blind] [--vision-metrics depth_influence,scan_error] \
+        [--odometry trained|off|scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002]
 
 The evaluation half of the reference's legged_gym/scripts/play.py (fixed commands, randomisation off, deterministic actions; play.py:66-85 and
 play.py:124-133).  Every env-step costs ONE extra HIP launch, `lsim_eval_accumulate` (include/lsim.h states the semantics; csrc/ls_eval.h is the
@@ -283,7 +284,8 @@ def check_conventions(saved, live):
 def _actor_critic(env, policy, device, vision=None):
     """HIMActorCritic (or VisionActorCritic) from a module, a runner, or a checkpoint path written by runner.save.  `vision`: a dict that
     receives what a vision policy brings along -- "sensor", "encoder", "depth_head" from a VisionOnPolicyRunner; from a checkpoint its
-    "checkpoint" (the loaded dict), for _vision_parts to build encoder and head from"""
+    "checkpoint" (the loaded dict), for _vision_parts to build encoder and head from; "map_policy" (the record, from a MapOnPolicyRunner
+    or its checkpoint) marks a map policy, whose rows _map_parts finds"""
     from .modules import HIMActorCritic
     vision = vision if vision is not None else {}
     if isinstance(policy, HIMActorCritic):     # VisionActorCritic is one
@@ -294,6 +296,8 @@ def _actor_critic(env, policy, device, vision=None):
             vision.update(sensor=getattr(policy, "sensor", None), encoder=policy.alg.encoder, depth_head=policy.alg.depth_head)
             if getattr(policy.alg, "memory", None) is not None:
                 vision.update(memory=policy.alg.memory, memory_head=policy.alg.memory_head)
+        if getattr(policy, "map_policy", False):      # a MapOnPolicyRunner: the actor reads its sensor's map rows
+            vision.update(sensor=getattr(policy, "sensor", None), map_policy={"channels": list(policy.channels)})
         return policy.alg.actor_critic
     if isinstance(policy, str):
         d = torch.load(policy, map_location=device, weights_only=False)
@@ -307,11 +311,13 @@ def _actor_critic(env, policy, device, vision=None):
         if enc != [l.out_features for l in ac.estimator.encoder if isinstance(l, torch.nn.Linear)]:
             raise ValueError(f"checkpoint estimator encoder widths {enc} differ from the default HIMEstimator's: pass the HIMActorCritic itself")
         extra = sd["actor.0.weight"].shape[1] - ac.actor[0].in_features
-        if extra > 0 and "depth_encoder_state_dict" in d:       # a vision policy: the depth columns come last (learn/vision.py)
+        if extra > 0 and ("depth_encoder_state_dict" in d or "map_policy" in d):       # a vision or a map policy: the extra columns come last (learn/vision.py)
             from .vision import VisionActorCritic
             ac = VisionActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, depth_latent_dim=extra,
                                    actor_hidden_dims=tuple(actor[:-1]), critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
             vision["checkpoint"] = d
+            if "map_policy" in d:
+                vision["map_policy"] = d["map_policy"]
         ac.load_state_dict(sd)
         ac.eval()
         return ac
@@ -367,6 +373,70 @@ def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
             cam.attach_memory(mem)
         found["memory"], found["memory_head"] = mem, (mem_head.to(device).eval() if mem_head is not None else None)
     return cam, enc, head
+
+
+def _map_parts(env, ac, found, sensor):
+    """the sensor of a map policy, its map rows attached: the caller's `sensor` first, then the runner's, then env.sensors["depth"], and
+    for a checkpoint without any of them the sensor, map and odometry rebuilt from its record and added to the env as "depth" """
+    record = found.get("map_policy") or {}
+    cam = sensor if sensor is not None else found.get("sensor")
+    if cam is None:
+        cam = getattr(env, "sensors", {}).get("depth")
+    if cam is None and record.get("sensor") is not None:
+        from ..envs.sensors import from_spec
+        cam = env.add_sensor("depth", from_spec(env, record["sensor"]))
+    if cam is None or getattr(cam, "map", None) is None:
+        raise ValueError("evaluate: a map policy needs a sensor with an elevation map (sensor=..., env.add_sensor('depth', ...), or a checkpoint "
+                         "whose 'map_policy' record names one)")
+    channels = tuple(record.get("channels") or (getattr(cam, "map_channels", None) or ("height",)))
+    if getattr(cam, "map_channels", None) != channels:
+        cam.attach_map_rows(channels)
+    if cam.map_rows().shape[1] != ac.depth_latent_dim:
+        raise ValueError(f"evaluate: the map rows have {cam.map_rows().shape[1]} columns, the actor reads {ac.depth_latent_dim}")
+    return cam
+
+
+def _map_odometry(cam, found, odometry):
+    """evaluate()'s `odometry` applied to the sensor's map, as _camera_jitter applies the mount jitter: "trained" -- what the checkpoint's
+    record of the sensor says (a runner's sensor stays as it is); None -- the map is placed with the simulator's pose; an OdometryError --
+    that one.  A map whose odometry changes is attached anew: it starts empty, every env's drift at zero, and is filled once from the
+    present capture.  Returns the entry of the result's conventions."""
+    from ..envs.sensors import OdometryError
+    current = getattr(cam, "odometry", None)
+    if isinstance(odometry, str):
+        if odometry != "trained":
+            raise ValueError(f"evaluate: odometry is 'trained', None or an OdometryError, got {odometry!r}")
+        d = found.get("checkpoint")
+        record = ((d.get("map_policy") or d.get("vision") or {}).get("sensor")) if d is not None else None
+        want = current if record is None else (OdometryError(**record["odometry"]) if record.get("odometry") else None)
+        choice = "trained"
+    elif odometry is None:
+        want, choice = None, "off"
+    elif isinstance(odometry, OdometryError):
+        want, choice = odometry, "override"
+    else:
+        raise TypeError(f"evaluate: odometry is 'trained', None or an OdometryError, got {type(odometry).__name__}")
+    if want != current:
+        channels = getattr(cam, "map_channels", None)
+        cam.attach_map(cam.map, odometry=want)
+        if channels is not None:
+            cam.attach_map_rows(channels)
+    blank = {"scale": None, "yaw_per_m": None, "z_per_m": None, "noise": None}
+    return dict(blank if want is None else want.record(), choice=choice)
+
+
+def parse_odometry(text):
+    """the command line's --odometry: "trained", "off" (None), or "scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c" (any key may be left out: 0)"""
+    from ..envs import sensors
+    if text == "trained":
+        return "trained"
+    if text == "off":
+        return None
+    for item in text.split(","):
+        k, sep, _ = item.partition("=")
+        if not sep or k not in ("scale", "yaw_per_m", "z_per_m", "noise"):
+            raise ValueError(f"expected trained, off or scale=..,yaw_per_m=..,z_per_m=..,noise=a:b:c, got {text!r}")
+    return sensors.parse_odometry(text)
 
 
 def _camera_jitter(cam, found, camera_jitter):
@@ -539,7 +609,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
             elif m == "scan_error":
                 ev.columns[:, k] = (head(live[:, :Lz]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
             elif m == "map_scan_error":     # the map's scan in observation units, exactly as ph_build_obs turns measured_heights into the block
-                block = (env.root_states[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height)
+                block = (cam.map_pose()[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height)       # the height the map has
                 ev.columns[:, k] = (block - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
             elif m == "map_coverage":
                 ev.columns[:, k] = cam.map_known().to(torch.float32).mean(dim=1)
@@ -552,10 +622,68 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
     return ev
 
 
+def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
+    """evaluate()'s loop for a map policy: the actor also reads the sensor's live map rows (zeros when `blind`); of the `metrics` a map
+    policy has "depth_influence" (the action distance against zero rows), "map_scan_error" (the rows' height block against the privileged
+    observation's) and "map_coverage"; the encoder's and the memory's are dropped"""
+    from .vision import PackedVisionPolicy, height_scan_block
+    dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
+    P = int(cam.map_scan().shape[1])
+    metrics = [m for m in metrics if m in ("depth_influence",) + MAP_METRICS]
+    scan = None
+    if "map_scan_error" in metrics:
+        try:
+            scan = height_scan_block(env.cfg)
+        except ValueError:
+            scan = None
+        if scan is None or scan[1] != P:
+            metrics.remove("map_scan_error")
+    if metrics and ev.column_names != tuple(metrics):
+        ev.add_columns(metrics)
+    use_fused = PackedVisionPolicy.supported(ac) if fused is None else bool(fused)
+    if use_fused and not PackedVisionPolicy.supported(ac):
+        raise ValueError("fused=True but lsim_policy_forward_ext does not support this policy's topology")
+    if hasattr(env, "_external_call"):
+        env._external_call()
+    zeros = torch.zeros(N, L, device=dev)
+    if use_fused:
+        packed = PackedVisionPolicy(ac)
+        mean, mean0 = torch.empty(N, env.num_actions, device=dev), torch.empty(N, env.num_actions, device=dev)
+        values = torch.empty(N, 1, device=dev)
+    influence = "depth_influence" in metrics
+    obs, priv = env.get_observations(), env.get_privileged_observations()
+    for _ in range(int(steps)):
+        if cmd is not None:
+            env.commands[:, :3] = cmd
+        live = cam.map_rows()
+        rows = zeros if blind else live
+        if use_fused:
+            packed.forward(obs, priv, mean, values, rows=rows)
+            actions = mean
+            if influence and not blind:
+                packed.forward(obs, priv, mean0, values, rows=zeros)
+        else:
+            actions = ac.act_inference(obs, depth_latent=rows)
+            if influence and not blind:
+                mean0 = ac.act_inference(obs, depth_latent=zeros)
+        for k, m in enumerate(metrics):
+            if m == "depth_influence":
+                ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
+            elif m == "map_scan_error":
+                ev.columns[:, k] = (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
+            else:
+                ev.columns[:, k] = cam.map_known().to(torch.float32).mean(dim=1)
+        env.step_device(actions)
+        ev.accumulate()
+        if metrics:
+            ev.accumulate_columns()
+    return ev
+
+
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
              sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained",
-             camera_instrument="trained"):
+             camera_instrument="trained", odometry="trained"):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -575,17 +703,33 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's
     conventions["camera_jitter"].
     `camera_instrument` (a vision policy only): the same choice for the per-episode error of the camera's own constants
-    (envs.sensors.InstrumentError: latency, noise gain, depth-scale error, field of view), written to conventions["camera_instrument"]."""
+    (envs.sensors.InstrumentError: latency, noise gain, depth-scale error, field of view), written to conventions["camera_instrument"].
+    A map policy (a MapOnPolicyRunner, its checkpoint -- recognised by its "map_policy" record, from which sensor, map and rows are rebuilt
+    when the env has none -- or a VisionActorCritic with a `sensor` whose map rows are attached and no encoder anywhere) reads
+    cam.map_rows(); `blind=True` feeds zeros; "depth_influence" is the action distance against zero rows and "map_scan_error" the mean
+    square of the rows' height block minus the privileged one.
+    `odometry` (a sensor with an elevation map only): the dead-reckoning error of the pose the map is placed with
+    (envs.sensors.OdometryError) -- "trained", None or an OdometryError, as camera_jitter; written to conventions["odometry"].  With
+    odometry map_scan_error uses the ESTIMATED base height, the one the map has."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
     ac = _actor_critic(env, policy, dev, found)
     ac.eval()
     is_vision = hasattr(ac, "depth_latent_dim")
-    if is_vision:
+    is_map = is_vision and ("map_policy" in found or (encoder is None and found.get("encoder") is None and found.get("checkpoint") is None and
+                                                      getattr(sensor, "map_channels", None) is not None))
+    if is_map:
+        cam = _map_parts(env, ac, found, sensor)
+        sensor_found = {"checkpoint": {"vision": found["map_policy"]}} if found.get("checkpoint") is not None else {}    # the record sits under another key
+        jitter_entry = _camera_jitter(cam, sensor_found, camera_jitter)
+        instrument_entry = _camera_instrument(cam, sensor_found, camera_instrument)
+        odometry_entry = _map_odometry(cam, found, odometry)
+    elif is_vision:
         cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
         jitter_entry = _camera_jitter(cam, found, camera_jitter)       # after the encoder and the memory are attached: a refresh() runs them too
         instrument_entry = _camera_instrument(cam, found, camera_instrument)
+        odometry_entry = _map_odometry(cam, found, odometry) if getattr(cam, "map", None) is not None else None
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -593,7 +737,12 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         cmd = cmd.expand(env.num_envs, 3).contiguous() if cmd.dim() == 1 else cmd.contiguous()
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
+    if is_map:
+        ev.extra_conventions.update(camera_jitter=jitter_entry, camera_instrument=instrument_entry, odometry=odometry_entry)
+        return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()))
     if is_vision:
+        if odometry_entry is not None:
+            ev.extra_conventions["odometry"] = odometry_entry
         ev.extra_conventions["camera_jitter"] = jitter_entry
         ev.extra_conventions["camera_instrument"] = instrument_entry
         return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
@@ -653,6 +802,8 @@ def parse_args(argv=None):
                     "'off' (the nominal mount) or pos=METRES,rot_deg=DEGREES (one number, or x/y/z)")
     ap.add_argument("--camera-instrument", default="trained", help="a vision policy's per-episode error of the camera's own constants: 'trained' (the "
                     "checkpoint's record), 'off' or latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F (any subset)")
+    ap.add_argument("--odometry", default="trained", help="the dead-reckoning error of the pose an elevation map is placed with: 'trained' (the "
+                    "checkpoint's record), 'off' or scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c (any subset)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
@@ -660,6 +811,10 @@ def parse_args(argv=None):
         a.camera_instrument = parse_camera_instrument(a.camera_instrument)
     except ValueError as exc:
         ap.error(f"--camera-instrument: {exc}")
+    try:
+        a.odometry = parse_odometry(a.odometry)
+    except ValueError as exc:
+        ap.error(f"--odometry: {exc}")
     try:
         a.camera_jitter = parse_camera_jitter(a.camera_jitter)
     except ValueError as exc:
@@ -707,12 +862,13 @@ def main(argv=None):
     cfg.env.num_envs = a.envs
     env = LeggedRobot(cfg, sim_device=a.device, seed=a.seed)
     env.reset()
-    record = torch.load(a.checkpoint, map_location="cpu", weights_only=False).get("vision") or {}
-    if record.get("sensor") is not None:       # a vision policy's checkpoint names the camera it was trained with
+    d = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    record = d.get("vision") or d.get("map_policy") or {}
+    if record.get("sensor") is not None:       # a vision or a map policy's checkpoint names the camera it was trained with
         from ..envs.sensors import from_spec
         env.add_sensor("depth", from_spec(env, record["sensor"]))
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
-                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument)
+                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

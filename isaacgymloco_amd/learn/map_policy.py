@@ -1,0 +1,84 @@
+"""Map policy: the elevation map's scan (envs/sensors.py, ElevationMap) as one more input segment of the HIM actor, from the rollout to the
+PPO update.
+
+    cam = env.add_sensor("depth", depth_camera(env, 64, 48, 87.0, model=SensorModel(period=5, stagger=True)))
+    cam.attach_map(ElevationMap(size=32), odometry=OdometryError(scale=0.02, yaw_per_m=0.01, z_per_m=0.01))
+    runner = MapOnPolicyRunner(env, train_cfg, sensor="depth", channels=("height", "known"), device=dev)
+    runner.enable_graphs()
+    runner.learn(n)
+
+What a vision policy does with the depth encoder's latent (learn/vision.py), this does with the rows lsim_map_rows builds from the map --
+the heights around the robot in the units of the privileged height scan, and optionally which of them the map knows: the same
+VisionActorCritic with depth_latent_dim = channels * P, the same storage and the same fused launch carry "some [N, dim] rows behind the
+latent" from the rollout to the update, and a HIM policy warm-starts it through load_him_state_dict.  There is no encoder, no auxiliary loss
+and no snapshot: the rows are the map's, and no gradient goes anywhere but into the actor-critic.  One rank only."""
+import copy
+
+from .him_ppo import HIMPPO
+from .runner import _ALGOS, _POLICIES, HIMOnPolicyRunner
+from .vision import PackedVisionPolicy, VisionActorCritic, VisionPPO, VisionRollout
+
+CHANNELS = (("height",), ("height", "known"))
+
+
+class MapPPO(VisionPPO):
+    """VisionPPO without an encoder: act() records `latent_source()` (the runner passes sensor.map_rows) with the transition and the update
+    binds each minibatch's stored rows to the actor; no snapshots are kept and no encoder or memory step follows.  update() returns
+    HIMPPO.update()'s tuple."""
+
+    def __init__(self, actor_critic, latent_source=None, **kwargs):
+        super().__init__(actor_critic, **kwargs)
+        self.latent_source = latent_source
+
+    def attach(self, *a, **kw):
+        raise NotImplementedError("MapPPO: a map policy has no encoder to attach (set latent_source)")
+
+    def snapshot_steps(self):
+        return []
+
+    def snapshot_if_due(self, step, critic_obs):
+        return
+
+    def update(self):
+        return HIMPPO.update(self)
+
+
+class MapOnPolicyRunner(HIMOnPolicyRunner):
+    """HIMOnPolicyRunner for a map policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs
+    an attached ElevationMap (cam.attach_map, with or without odometry).  `channels`: ("height",) or ("height", "known"); the runner calls
+    cam.attach_map_rows(channels) and the actor reads cam.map_rows(), channels * P more columns.  train_cfg is HIMOnPolicyRunner's;
+    policy["depth_latent_dim"] is set here.  The fused policy launch takes a first actor layer of at most 272 columns: 187 points with
+    one channel (251 columns), and with two channels a map of at most 104 points (ElevationMap(points=...), e.g. 11 x 9)."""
+
+    map_policy = True
+
+    def __init__(self, env, train_cfg, sensor="depth", channels=("height",), log_dir=None, device="cpu", fast=None):
+        cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
+        if getattr(cam, "map", None) is None:
+            raise ValueError("MapOnPolicyRunner: the sensor has no elevation map (cam.attach_map(ElevationMap(...)))")
+        channels = tuple(channels)
+        if channels not in CHANNELS:
+            raise ValueError(f"MapOnPolicyRunner: channels is ('height',) or ('height', 'known'), got {channels}")
+        dim = len(channels) * int(cam.map_scan().shape[1])
+        first = env.num_one_step_obs + 3 + 16 + dim
+        if first > 272:             # LS_POL_MAX_IN (csrc/ls_policy.h): the fused policy launch's widest input row
+            raise ValueError(f"MapOnPolicyRunner: the first actor layer would read {first} columns ({env.num_one_step_obs} + 3 + 16 + map rows "
+                             f"{dim}), the fused policy launch takes at most 272")
+        _POLICIES["VisionActorCritic"], _ALGOS["MapPPO"] = VisionActorCritic, MapPPO
+        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
+        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "MapPPO"
+        cfg["policy"]["depth_latent_dim"] = dim
+        self.sensor, self.channels = cam, channels
+        super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
+        cam.attach_map_rows(channels)       # behind the parent's env.reset(): the sensor has captured, so every env's rows are built now
+        self.alg.latent_source = cam.map_rows
+
+    def _make_fused_rollout(self):
+        return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
+
+    def _extra_checkpoint_state(self):
+        out = super()._extra_checkpoint_state()
+        cam = self.sensor                   # what the policy was trained with: learn/evaluate.py rebuilds sensor, map, odometry and rows from it
+        out["map_policy"] = {"sensor": cam.spec() if hasattr(cam, "spec") else None, "channels": list(self.channels),
+                             "dim": int(self.alg.actor_critic.depth_latent_dim)}
+        return out

@@ -32,6 +32,12 @@ terrain, in one process and alternating `--repeats` times, each with its median 
 times it (the tick advancing, so a staggered period is averaged over whole periods); `map_us` = lsim_elevation_map alone over the same
 ticks, reading the rows the captures left; `map_all_due_us` = the same launch with LSIM_SENSOR_FILL_ALL (every env cleared and inserted);
 `update_with_map_us` = update() as a sensor with a map runs it in a step: the capture and the map's launch behind it.
+`--map ... --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002` and / or `--map-rows 1|2` (the map policy's two
+launches; a measurement of its own, written to profiles/map_policy_time.json unless --out names another file): per terrain, in one process
+and alternating `--repeats` times, each with its median and range: `capture_us` as above; `odometry_us` = lsim_odometry_step alone, the tick
+advancing; `map_rows_us` = lsim_map_rows alone over the map's scan; `map_rows_torch_us` = the torch statement of the same rows into the same
+buffer (two subtractions, clamp, product, and with two channels the copy of `known`: five elementwise launches, without the non-finite
+rule); `update_us` = update() as the sensor of a map policy runs it in a step: odometry, capture, map, rows.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -197,6 +203,68 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     return out
 
 
+def measure_map_policy(n, terrain, iters, warmup, model, emap, odometry, channels, repeats):
+    """the --map --odometry / --map-rows measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    env.episode_length_buf[:] = 20               # nobody is fresh inside the timed loops
+    torch.cuda.synchronize()
+    cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
+    cam.refresh(tick=0)
+    cam.attach_map(emap, odometry=odometry)
+    cam.attach_map_rows(("height", "known")[:channels])
+    L, P = env._L, int(cam._em.num_points)
+    whole = max(model.period, iters // model.period * model.period)
+    rows_buf, scan, known, scale = cam.map_rows(), cam.map_scan(), cam.map_known(), float(env.lcfg.obs_scale_height)
+    pose_z = cam.map_pose()[:, 2:3]
+
+    def odometry_ticks():
+        tick = [0]
+
+        def fn():
+            cam._launch_odometry(tick[0], 0, None)
+            tick[0] += 1
+        return timed(fn, whole, warmup)
+
+    def rows_launch():
+        lib.check(L.lsim_map_rows(ctypes.byref(cam._mr), env._stream()), what="lsim_map_rows")
+
+    def rows_torch():
+        torch.mul(torch.clamp(pose_z - 0.5 - scan, -1.0, 1.0), scale, out=rows_buf[:, :P])
+        if channels == 2:
+            rows_buf[:, P:].copy_(known)
+    rows_launch()
+    want = rows_buf.clone()
+    rows_torch()
+    same = bool(torch.equal(want, rows_buf))    # every pose and scan value is finite here: the two statements agree to the bit
+    rows = {"capture_us": [], "map_rows_us": [], "map_rows_torch_us": [], "update_us": []}
+    if odometry is not None:
+        rows["odometry_us"] = []
+    em, od, mr = cam._em, cam._od, cam._mr
+    for _ in range(repeats):
+        cam._em = cam._od = None                # the capture alone
+        rows["capture_us"].append(timed_ticks(cam, whole, warmup))
+        cam._em, cam._od = em, od
+        if odometry is not None:
+            rows["odometry_us"].append(odometry_ticks())
+        rows["map_rows_us"].append(timed(rows_launch, whole, warmup))
+        rows["map_rows_torch_us"].append(timed(rows_torch, whole, warmup))
+        rows["update_us"].append(timed_ticks(cam, whole, warmup))
+    out = {"num_envs": n, "terrain": terrain, "rays": cam.num_rays, "scan_points": P, "channels": channels, "columns": int(rows_buf.shape[1]),
+           "coverage": float(known.float().mean().item()), "rows_equal_torch_bit_for_bit": same}
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    out["map_rows_over_torch"] = out["map_rows_us"] / out["map_rows_torch_us"]
+    out["nonfinite"] = int(cam.nonfinite_rays.item()) + int(cam.map_nonfinite.item())
+    return out
+
+
 def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
     """the --instrument measurement (module docstring)"""
     cfg = C.aliengo_cfg()
@@ -337,6 +405,9 @@ def main():
                     "lsim_sensor_capture_inst against lsim_sensor_capture (needs --model)")
     ap.add_argument("--map", default=None, nargs="?", const="default", help="size=G,resolution=RES,source=noisy|clean (any subset): time lsim_elevation_map "
                     "next to lsim_sensor_capture (needs --model)")
+    ap.add_argument("--odometry", default=None, nargs="?", const="default", help="scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c (any subset): with --map, time "
+                    "lsim_odometry_step next to the capture")
+    ap.add_argument("--map-rows", type=int, default=None, choices=(1, 2), help="with --map, time lsim_map_rows with this many channels against its torch statement")
     ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
@@ -359,6 +430,18 @@ def main():
         if not a.model:
             ap.error("--map needs --model")
         model, emap = parse_model(a.model), sensors.parse_elevation_map(a.map)
+        if a.odometry is not None or a.map_rows is not None:
+            odometry = None if a.odometry is None else sensors.parse_odometry(a.odometry)
+            channels = a.map_rows or 1
+            res = {"tool": "raycast_time --map --odometry --map-rows", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats,
+                   "device": torch.cuda.get_device_name(0), "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot, labels", "model": a.model,
+                   "map": emap.record(), "odometry": None if odometry is None else odometry.record(), "channels": channels,
+                   "cases": [measure_map_policy(a.num_envs, t, a.iters, a.warmup, model, emap, odometry, channels, a.repeats) for t in a.terrains.split(",")]}
+            line = json.dumps(res)
+            with open(a.out or os.path.join(ROOT, "profiles", "map_policy_time.json"), "w") as f:
+                f.write(line + "\n")
+            print(line)
+            return
         res = {"tool": "raycast_time --map", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
                "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot, labels", "model": a.model, "map": emap.record(),
                "cases": [measure_map(a.num_envs, t, a.iters, a.warmup, model, emap, a.repeats) for t in a.terrains.split(",")]}
