@@ -101,13 +101,63 @@ def ring_dirs(channels, vfov_deg, points_per_rev):
     return v.reshape(-1, 3).astype(np.float32)
 
 
-class SensorModel:
+class _Option:
+    """What the options of a range sensor share, from two tables of the class.  FIELDS: the constructor's keywords, each kept as the
+    attribute of its name -- the record spec() stores (tuples as lists) and cls(**record) reads, equality (same class, equal records) and
+    a one-line repr.  TEXT: the grammar of parse_option -- field -> the converter of a scalar, or (converter, separator, accepted lengths)
+    of a list."""
+    FIELDS, TEXT = (), {}
+
+    def record(self):
+        """the plain dict spec() stores and cls(**record) reads"""
+        plain = lambda v: [plain(x) for x in v] if isinstance(v, (tuple, list)) else v
+        return {k: plain(getattr(self, k)) for k in self.FIELDS}
+
+    def __eq__(self, other):
+        return type(other) is type(self) and self.record() == other.record()
+
+    __hash__ = None
+
+    def _shown(self, k):
+        return repr(getattr(self, k))
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={self._shown(k)}' for k in self.FIELDS)})"
+
+
+def parse_option(cls, text):
+    """cls(...) of 'key=value,key=value' (any subset of cls.TEXT, each key once; '' or 'default': the defaults), a list as its numbers
+    joined by the field's separator: the text every tool and learn/evaluate.py's command line takes for an option"""
+    kw = {}
+    for item in ([] if text in ("", "default") else text.split(",")):
+        k, eq, v = item.partition("=")
+        if not eq or k not in cls.TEXT or k in kw:
+            raise ValueError(f"{cls.__name__}: {item!r} is no key=value with a key of {', '.join(cls.TEXT)}, each at most once (got {text!r})")
+        how = cls.TEXT[k]
+        if callable(how):
+            kw[k] = how(v)
+            continue
+        conv, sep, lengths = how
+        vals = tuple(conv(x) for x in v.split(sep))
+        if len(vals) not in lengths:
+            raise ValueError(f"{cls.__name__}: {k} takes {' or '.join(str(n) for n in lengths)} numbers joined by {sep!r}, got {v!r}")
+        kw[k] = vals[0] if len(vals) == 1 else vals
+    return cls(**kw)
+
+
+_flag = lambda v: bool(int(v))
+
+
+class SensorModel(_Option):
     """What lsim_sensor_capture adds to a ray cast (include/lsim.h states every formula).  `period`: an env captures on every period-th
     tick; `stagger`: env e captures when (tick + e) % period == 0 instead of tick % period == 0, so that every launch renders 1 env in
     `period`; `frames`: the captures a policy reads, oldest first; `latency`: how many captures old the newest of them is; `noise` =
     (sigma0, sigma2): standard deviation sigma0 + sigma2 * depth^2 on a hit; `dropout`: probability that a hit reads `drop_value`; `clip` =
     (lo, hi), None: the sensor's (near, far); `normalise`: (v - (lo + hi) / 2) / (hi - lo), in [-0.5, 0.5], instead of v.
     An env that was reset (episode_length 0) captures at once and all its frames are that capture."""
+    FIELDS = ("period", "stagger", "latency", "frames", "noise", "dropout", "drop_value", "clip", "normalise")
+    TEXT = {"period": int, "stagger": _flag, "latency": int, "frames": int, "noise": (float, ":", (2,)), "dropout": float, "drop_value": float,
+            "clip": (float, ":", (2,)), "normalise": _flag}
 
     def __init__(self, period=1, stagger=False, latency=0, frames=1, noise=(0.0, 0.0), dropout=0.0, drop_value=0.0, clip=None, normalise=False):
         self.period, self.stagger, self.latency, self.frames = int(period), bool(stagger), int(latency), int(frames)
@@ -131,11 +181,13 @@ class SensorModel:
         return (lo, hi), (lo + hi) / 2.0, 1.0 / (hi - lo)
 
 
-class MountJitter:
+class MountJitter(_Option):
     """Per-episode error of a sensor's mount pose (lsim_sensor_mount_jitter; include/lsim.h states every formula): when an env starts an
     episode its mount is the nominal one moved by uniform offsets in [-pos[k], pos[k]] metres along the base x, y, z and turned by about
     [-rot_deg[k], rot_deg[k]] degrees about the base x, y, z (rot_deg[1] is the pitch error of a forward camera).  A scalar is the same
     half-width on all three axes."""
+    FIELDS = ("pos", "rot_deg")
+    TEXT = {"pos": (float, "/", (1, 3)), "rot_deg": (float, "/", (1, 3))}
 
     def __init__(self, pos=(0.0, 0.0, 0.0), rot_deg=(0.0, 0.0, 0.0)):
         self.pos, self.rot_deg = self._three(pos, "pos"), self._three(rot_deg, "rot_deg")
@@ -147,26 +199,16 @@ class MountJitter:
             raise ValueError(f"MountJitter: {name} takes one or three finite half-widths >= 0, got {v}")
         return v
 
-    def record(self):
-        """the plain dict spec() stores and MountJitter(**record) reads"""
-        return {"pos": list(self.pos), "rot_deg": list(self.rot_deg)}
 
-    def __eq__(self, other):
-        return isinstance(other, MountJitter) and (self.pos, self.rot_deg) == (other.pos, other.rot_deg)
-
-    __hash__ = None
-
-    def __repr__(self):
-        return f"MountJitter(pos={self.pos}, rot_deg={self.rot_deg})"
-
-
-class InstrumentError:
+class InstrumentError(_Option):
     """Per-episode error of a sensor's own constants (lsim_sensor_instrument; include/lsim.h states every formula): when an env starts an
     episode it draws `latency` = (lo, hi): its latency in captures, uniform on the integers lo .. hi (None: the model's, for every env;
     hi <= the model's latency, which sizes the history); `noise_gain` = (lo, hi): a uniform factor on the model's noise; `depth_scale` and
     `depth_quad` (1 / m): half-widths of the relative depth error depth_scale + depth_quad * d of a hit at depth d; `fov`: half-width of the
     relative error of the tangent of every ray's angle to the optical axis (0.02: the image is up to 2 % wider or narrower), which needs
     rays that all look forward (a camera, not a lidar)."""
+    FIELDS = ("latency", "noise_gain", "depth_scale", "depth_quad", "fov")
+    TEXT = {"latency": (int, ":", (2,)), "noise_gain": (float, ":", (2,)), "depth_scale": float, "depth_quad": float, "fov": float}
 
     def __init__(self, latency=None, noise_gain=(1.0, 1.0), depth_scale=0.0, depth_quad=0.0, fov=0.0):
         self.latency = None if latency is None else (int(latency[0]), int(latency[1]))
@@ -178,25 +220,8 @@ class InstrumentError:
         if len(noise_gain) != 2 or any(not math.isfinite(x) or x < 0.0 for x in values) or self.noise_gain[0] > self.noise_gain[1] or self.fov >= 1.0:
             raise ValueError(f"InstrumentError: finite 0 <= noise_gain[0] <= noise_gain[1], depth_scale >= 0, depth_quad >= 0 and 0 <= fov < 1, got {values}")
 
-    def record(self):
-        """the plain dict spec() stores and InstrumentError(**record) reads"""
-        return {"latency": None if self.latency is None else list(self.latency), "noise_gain": list(self.noise_gain),
-                "depth_scale": self.depth_scale, "depth_quad": self.depth_quad, "fov": self.fov}
 
-    def _key(self):
-        return (self.latency, self.noise_gain, self.depth_scale, self.depth_quad, self.fov)
-
-    def __eq__(self, other):
-        return isinstance(other, InstrumentError) and self._key() == other._key()
-
-    __hash__ = None
-
-    def __repr__(self):
-        return (f"InstrumentError(latency={self.latency}, noise_gain={self.noise_gain}, depth_scale={self.depth_scale}, "
-                f"depth_quad={self.depth_quad}, fov={self.fov})")
-
-
-class ElevationMap:
+class ElevationMap(_Option):
     """A robot-centred height grid per env, fused on the device from a sensor's captures (lsim_elevation_map; include/lsim.h states every
     formula).  `size`: cells per side, 16, 32 or 64; `resolution`: metres per cell (a power of two keeps the cell of a coordinate exact);
     `source`: "noisy" -- the newest capture as the instrument reports it (the newest slot of the frame history, noise, holes and
@@ -210,6 +235,8 @@ class ElevationMap:
     What attach_map refuses, because the launch cannot be right with it: a sensor with frame="yaw" (the launch places the points with the
     base's full orientation); a see_robot sensor without labels=True (the robot's own legs would be inserted as ground); with "noisy", a
     model whose dropped pixels cannot be told from a range (dropout > 0 with drop_value strictly inside the clip range)."""
+    FIELDS = ("size", "resolution", "source", "max_range", "points", "unknown_drop")
+    TEXT = {"size": int, "resolution": float, "source": str, "max_range": float, "unknown_drop": float}
 
     def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None):
         self.size, self.resolution, self.source = int(size), float(resolution), str(source)
@@ -227,25 +254,17 @@ class ElevationMap:
         if self.points is not None and not 1 <= len(self.points) <= abi.DEFINES["LSIM_ELEVATION_MAP_MAX_POINTS"]:
             raise ValueError(f"ElevationMap: 1 to {abi.DEFINES['LSIM_ELEVATION_MAP_MAX_POINTS']} points, got {len(self.points)}")
 
-    def record(self):
-        """the plain dict spec() stores and ElevationMap(**record) reads"""
-        return {"size": self.size, "resolution": self.resolution, "source": self.source, "max_range": self.max_range, "points": self.points,
-                "unknown_drop": self.unknown_drop}
-
-    def __eq__(self, other):
-        return isinstance(other, ElevationMap) and self.record() == other.record()
-
-    __hash__ = None
-
-    def __repr__(self):
-        return f"ElevationMap({', '.join(f'{k}={v!r}' for k, v in self.record().items() if k != 'points')}, points={'None' if self.points is None else len(self.points)})"
+    def _shown(self, k):
+        return repr(getattr(self, k) if k != "points" or self.points is None else len(self.points))     # the number of points, not the points
 
 
-class OdometryError:
+class OdometryError(_Option):
     """Dead-reckoning error of the pose an elevation map is placed with (lsim_odometry_step; include/lsim.h states every formula).  When an
     env starts an episode it draws three biases, uniform in [-v, v]: `scale`, the relative error of every distance travelled; `yaw_per_m`,
     radians of heading error per metre travelled; `z_per_m`, metres of height error per metre travelled.  `noise` = (pos, yaw, z): the
     half-widths of a uniform error of the same three kinds drawn anew at every step.  All-zero values give the true pose bit for bit."""
+    FIELDS = ("scale", "yaw_per_m", "z_per_m", "noise")
+    TEXT = {"scale": float, "yaw_per_m": float, "z_per_m": float, "noise": (float, ":", (3,))}
 
     def __init__(self, scale=0.0, yaw_per_m=0.0, z_per_m=0.0, noise=(0.0, 0.0, 0.0)):
         self.scale, self.yaw_per_m, self.z_per_m = float(scale), float(yaw_per_m), float(z_per_m)
@@ -254,40 +273,20 @@ class OdometryError:
         if len(self.noise) != 3 or any(not math.isfinite(v) or v < 0.0 for v in values):
             raise ValueError(f"OdometryError: scale, yaw_per_m, z_per_m and the three of noise are finite half-widths >= 0, got {values}")
 
-    def record(self):
-        """the plain dict spec() stores and OdometryError(**record) reads"""
-        return {"scale": self.scale, "yaw_per_m": self.yaw_per_m, "z_per_m": self.z_per_m, "noise": list(self.noise)}
-
     def ranges(self):
         """the six ranges in the order of lsim_odometry_t"""
         return (self.scale, self.yaw_per_m, self.z_per_m) + self.noise
 
-    def __eq__(self, other):
-        return isinstance(other, OdometryError) and self.ranges() == other.ranges()
-
-    __hash__ = None
-
-    def __repr__(self):
-        return f"OdometryError(scale={self.scale}, yaw_per_m={self.yaw_per_m}, z_per_m={self.z_per_m}, noise={self.noise})"
-
 
 def parse_odometry(text):
     """OdometryError of 'scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002' (any subset): the text the tools take"""
-    kw = {}
-    for item in ([] if text in ("", "default") else text.split(",")):
-        k, v = item.split("=")
-        kw[k] = tuple(float(x) for x in v.split(":")) if k == "noise" else float(v)
-    return OdometryError(**kw)
+    return parse_option(OdometryError, text)
 
 
 def parse_elevation_map(text):
     """ElevationMap of 'size=32,resolution=0.0625,source=noisy,max_range=3,unknown_drop=0.4' (any subset; '' or 'default': the defaults):
     the text the tools take"""
-    kw = {}
-    for item in ([] if text in ("", "default") else text.split(",")):
-        k, v = item.split("=")
-        kw[k] = v if k == "source" else (int(v) if k == "size" else float(v))
-    return ElevationMap(**kw)
+    return parse_option(ElevationMap, text)
 
 
 class RaySensor:
@@ -871,10 +870,7 @@ class RaySensor:
         out.update(near=self.near, far=self.far, env_stride=self.env_stride, see_robot=self.see_robot, labels=self._labels is not None, frame=self.frame)
         mask = self.body_mask if self.see_robot else None
         out["ignore_bodies"] = [] if mask is None else [n for i, n in enumerate(self.body_names) if not mask >> i & 1]
-        m = self.model
-        out["model"] = None if m is None else {"period": m.period, "stagger": m.stagger, "latency": m.latency, "frames": m.frames, "noise": list(m.noise),
-                                               "dropout": m.dropout, "drop_value": m.drop_value, "clip": None if m.clip is None else list(m.clip),
-                                               "normalise": m.normalise}
+        out["model"] = None if self.model is None else self.model.record()
         mount = self.mount_nominal.cpu()
         pose = lambda row: {"pos": row[:3].tolist(), "quat": row[3:].tolist()}
         names, ids = getattr(self.env, "robot_names", None), getattr(self.env, "robot_ids", None)
@@ -885,14 +881,9 @@ class RaySensor:
             out["mount"] = {n: pose(r[0]) for n, r in zip(names, rows) if len(r)}
         else:
             out["mount"] = None
-        if self.mount_jitter is not None:
-            out["mount_jitter"] = self.mount_jitter.record()
-        if self.instrument is not None:
-            out["instrument"] = self.instrument.record()
-        if self.map is not None:
-            out["map"] = self.map.record()
-        if self.odometry is not None:
-            out["odometry"] = self.odometry.record()
+        for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry)):
+            if option is not None:
+                out[key] = option.record()
         return out
 
     @property
@@ -956,28 +947,17 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     quat = mount_quat if mount_quat is not None else quat
     if pos is None or quat is None:
         raise ValueError("from_spec: the recorded sensor's mount differed from env to env (spec['mount'] is None): pass mount_pos and mount_quat")
-    m = spec.get("model")
-    model = None if m is None else SensorModel(**m)
-    if isinstance(mount_jitter, str):
-        if mount_jitter != "spec":
-            raise ValueError(f"from_spec: mount_jitter is 'spec', None or a MountJitter, got {mount_jitter!r}")
-        j = spec.get("mount_jitter")
-        mount_jitter = None if j is None else MountJitter(**j)
-    if isinstance(instrument, str):
-        if instrument != "spec":
-            raise ValueError(f"from_spec: instrument is 'spec', None or an InstrumentError, got {instrument!r}")
-        i = spec.get("instrument")
-        instrument = None if i is None else InstrumentError(**i)
-    if isinstance(elevation_map, str):
-        if elevation_map != "spec":
-            raise ValueError(f"from_spec: elevation_map is 'spec', None or an ElevationMap, got {elevation_map!r}")
-        r = spec.get("map")
-        elevation_map = None if r is None else ElevationMap(**r)
-    if isinstance(odometry, str):
-        if odometry != "spec":
-            raise ValueError(f"from_spec: odometry is 'spec', None or an OdometryError, got {odometry!r}")
-        o = spec.get("odometry")
-        odometry = None if o is None else OdometryError(**o)
+    def option(name, value, cls, key):
+        """`value` of from_spec's keyword `name`: "spec" -- the record under `key` rebuilt (none: None); None or a `cls` -- that"""
+        if isinstance(value, str) and value == "spec":
+            return None if spec.get(key) is None else cls(**spec[key])
+        if value is None or isinstance(value, cls):
+            return value
+        raise ValueError(f"from_spec: {name} is 'spec', None or of class {cls.__name__}, got {value!r}")
+
+    model = option("model", "spec", SensorModel, "model")
+    mount_jitter, instrument = option("mount_jitter", mount_jitter, MountJitter, "mount_jitter"), option("instrument", instrument, InstrumentError, "instrument")
+    elevation_map, odometry = option("elevation_map", elevation_map, ElevationMap, "map"), option("odometry", odometry, OdometryError, "odometry")
     kind = spec.get("kind", "rays")
     cls = DepthCamera if kind == "camera" else RaySensor
     sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves

@@ -20,6 +20,7 @@ import torch
 
 from .. import abi, lib
 from ..envs import config as C
+from ..envs import sensors
 
 GROUP_BITS = {"robot": abi.DEFINES["LSIM_EVAL_BY_ROBOT"], "type": abi.DEFINES["LSIM_EVAL_BY_TYPE"], "level": abi.DEFINES["LSIM_EVAL_BY_LEVEL"]}
 TRACE_DIM = abi.DEFINES["LSIM_EVAL_TRACE_DIM"]
@@ -383,8 +384,7 @@ def _map_parts(env, ac, found, sensor):
     if cam is None:
         cam = getattr(env, "sensors", {}).get("depth")
     if cam is None and record.get("sensor") is not None:
-        from ..envs.sensors import from_spec
-        cam = env.add_sensor("depth", from_spec(env, record["sensor"]))
+        cam = env.add_sensor("depth", sensors.from_spec(env, record["sensor"]))
     if cam is None or getattr(cam, "map", None) is None:
         raise ValueError("evaluate: a map policy needs a sensor with an elevation map (sensor=..., env.add_sensor('depth', ...), or a checkpoint "
                          "whose 'map_policy' record names one)")
@@ -396,288 +396,186 @@ def _map_parts(env, ac, found, sensor):
     return cam
 
 
-def _map_odometry(cam, found, odometry):
-    """evaluate()'s `odometry` applied to the sensor's map, as _camera_jitter applies the mount jitter: "trained" -- what the checkpoint's
-    record of the sensor says (a runner's sensor stays as it is); None -- the map is placed with the simulator's pose; an OdometryError --
-    that one.  A map whose odometry changes is attached anew: it starts empty, every env's drift at zero, and is filled once from the
-    present capture.  Returns the entry of the result's conventions."""
-    from ..envs.sensors import OdometryError
-    current = getattr(cam, "odometry", None)
-    if isinstance(odometry, str):
-        if odometry != "trained":
-            raise ValueError(f"evaluate: odometry is 'trained', None or an OdometryError, got {odometry!r}")
-        d = found.get("checkpoint")
-        record = ((d.get("map_policy") or d.get("vision") or {}).get("sensor")) if d is not None else None
-        want = current if record is None else (OdometryError(**record["odometry"]) if record.get("odometry") else None)
-        choice = "trained"
-    elif odometry is None:
+def _sensor_option(cam, record, value, cls, key, name, apply):
+    """evaluate()'s keyword `name` applied to the sensor's option `key` (the attribute of the sensor and the key of its record alike):
+    "trained" -- what `record`, the checkpoint's record of the sensor, says (None -- a runner or a module brings no record: the sensor it
+    is given carries what it was trained with, and stays as it is); None -- off; a `cls` -- that one.  `apply(want)` puts a choice that
+    differs from what the sensor has in force.  Returns the entry of the result's conventions: the option's record, every value None
+    when off, and the choice."""
+    current = getattr(cam, key, None)
+    if isinstance(value, str):
+        if value != "trained":
+            raise ValueError(f"evaluate: {name} is 'trained', None or of class {cls.__name__}, got {value!r}")
+        want, choice = current if record is None else (cls(**record[key]) if record.get(key) else None), "trained"
+    elif value is None:
         want, choice = None, "off"
-    elif isinstance(odometry, OdometryError):
-        want, choice = odometry, "override"
+    elif isinstance(value, cls):
+        want, choice = value, "override"
     else:
-        raise TypeError(f"evaluate: odometry is 'trained', None or an OdometryError, got {type(odometry).__name__}")
+        raise TypeError(f"evaluate: {name} is 'trained', None or of class {cls.__name__}, got {type(value).__name__}")
     if want != current:
+        apply(want)
+    return dict(dict.fromkeys(cls.FIELDS) if want is None else want.record(), choice=choice)
+
+
+def _sensor_options(cam, record, camera_jitter, camera_instrument, odometry):
+    """the three options of evaluate() in their order -- behind the encoder and the memory, whose launches a refresh() runs too -- as the
+    entries of the result's conventions.  A camera whose jitter or instrument changes has every env's mount or row redrawn and history
+    refilled once (refresh()); a map whose odometry changes is attached anew: it starts empty, every env's drift at zero, and is filled
+    once from the present capture.  A sensor without a map has no odometry entry."""
+    def redrawn(setter):
+        def apply(want):
+            setter(want)
+            if cam.tick >= 0:
+                cam.refresh()
+        return apply
+
+    def reattached(want):
         channels = getattr(cam, "map_channels", None)
         cam.attach_map(cam.map, odometry=want)
         if channels is not None:
             cam.attach_map_rows(channels)
-    blank = {"scale": None, "yaw_per_m": None, "z_per_m": None, "noise": None}
-    return dict(blank if want is None else want.record(), choice=choice)
+
+    out = {"camera_jitter": _sensor_option(cam, record, camera_jitter, sensors.MountJitter, "mount_jitter", "camera_jitter", redrawn(cam.set_mount_jitter)),
+           "camera_instrument": _sensor_option(cam, record, camera_instrument, sensors.InstrumentError, "instrument", "camera_instrument", redrawn(cam.set_instrument))}
+    if getattr(cam, "map", None) is not None:
+        out["odometry"] = _sensor_option(cam, record, odometry, sensors.OdometryError, "odometry", "odometry", reattached)
+    return out
+
+
+def _parse_choice(cls, text):
+    """a command-line option of a sensor: "trained", "off" (None), or the text envs.sensors.parse_option takes for a `cls`"""
+    if text in ("trained", "off"):
+        return "trained" if text == "trained" else None
+    if text in ("", "default"):
+        raise ValueError(f"expected trained, off or key=value pairs with the keys {', '.join(cls.TEXT)}, got {text!r}")
+    return sensors.parse_option(cls, text)
 
 
 def parse_odometry(text):
     """the command line's --odometry: "trained", "off" (None), or "scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c" (any key may be left out: 0)"""
-    from ..envs import sensors
-    if text == "trained":
-        return "trained"
-    if text == "off":
-        return None
-    for item in text.split(","):
-        k, sep, _ = item.partition("=")
-        if not sep or k not in ("scale", "yaw_per_m", "z_per_m", "noise"):
-            raise ValueError(f"expected trained, off or scale=..,yaw_per_m=..,z_per_m=..,noise=a:b:c, got {text!r}")
-    return sensors.parse_odometry(text)
-
-
-def _camera_jitter(cam, found, camera_jitter):
-    """evaluate()'s `camera_jitter` applied to the camera: "trained" -- what the checkpoint's vision["sensor"] record says (a runner or a
-    module brings no record: the camera it is given carries what it was trained with, and stays as it is); None -- the nominal mount; a
-    MountJitter -- that one.  A camera whose jitter changes has every env's mount redrawn and history refilled once (refresh()).
-    Returns the entry of the result's conventions."""
-    from ..envs.sensors import MountJitter
-    current = getattr(cam, "mount_jitter", None)
-    if isinstance(camera_jitter, str):
-        if camera_jitter != "trained":
-            raise ValueError(f"evaluate: camera_jitter is 'trained', None or a MountJitter, got {camera_jitter!r}")
-        d = found.get("checkpoint")
-        record = ((d.get("vision") or {}).get("sensor")) if d is not None else None
-        want = current if record is None else (MountJitter(**record["mount_jitter"]) if record.get("mount_jitter") else None)
-        choice = "trained"
-    elif camera_jitter is None:
-        want, choice = None, "off"
-    elif isinstance(camera_jitter, MountJitter):
-        want, choice = camera_jitter, "override"
-    else:
-        raise TypeError(f"evaluate: camera_jitter is 'trained', None or a MountJitter, got {type(camera_jitter).__name__}")
-    if want != current:
-        cam.set_mount_jitter(want)
-        if cam.tick >= 0:
-            cam.refresh()
-    return {"choice": choice, "pos": None if want is None else list(want.pos), "rot_deg": None if want is None else list(want.rot_deg)}
+    return _parse_choice(sensors.OdometryError, text)
 
 
 def parse_camera_jitter(text):
     """the command line's --camera-jitter: "trained", "off" (None), or "pos=P,rot_deg=R" with P and R one number or three joined by "/"
     (either key may be left out: 0)"""
-    from ..envs.sensors import MountJitter
-    if text == "trained":
-        return "trained"
-    if text == "off":
-        return None
-    kw = {}
-    for item in text.split(","):
-        k, sep, v = item.partition("=")
-        if not sep or k not in ("pos", "rot_deg") or k in kw:
-            raise ValueError(f"expected trained, off or pos=..,rot_deg=.., got {text!r}")
-        vals = [float(x) for x in v.split("/")]
-        if len(vals) not in (1, 3):
-            raise ValueError(f"{k}: one number or three joined by '/', got {v!r}")
-        kw[k] = vals[0] if len(vals) == 1 else vals
-    return MountJitter(**kw)
-
-
-def _camera_instrument(cam, found, camera_instrument):
-    """evaluate()'s `camera_instrument` applied to the camera, as _camera_jitter applies the mount jitter: "trained" -- what the checkpoint's
-    vision["sensor"] record says (a runner's camera stays as it is); None -- the model's own constants for every env; an InstrumentError --
-    that one.  A camera whose instrument changes has every env's row redrawn and history refilled once (refresh()).
-    Returns the entry of the result's conventions."""
-    from ..envs.sensors import InstrumentError
-    current = getattr(cam, "instrument", None)
-    if isinstance(camera_instrument, str):
-        if camera_instrument != "trained":
-            raise ValueError(f"evaluate: camera_instrument is 'trained', None or an InstrumentError, got {camera_instrument!r}")
-        d = found.get("checkpoint")
-        record = ((d.get("vision") or {}).get("sensor")) if d is not None else None
-        want = current if record is None else (InstrumentError(**record["instrument"]) if record.get("instrument") else None)
-        choice = "trained"
-    elif camera_instrument is None:
-        want, choice = None, "off"
-    elif isinstance(camera_instrument, InstrumentError):
-        want, choice = camera_instrument, "override"
-    else:
-        raise TypeError(f"evaluate: camera_instrument is 'trained', None or an InstrumentError, got {type(camera_instrument).__name__}")
-    if want != current:
-        cam.set_instrument(want)
-        if cam.tick >= 0:
-            cam.refresh()
-    blank = {"latency": None, "noise_gain": None, "depth_scale": None, "depth_quad": None, "fov": None}
-    return dict(blank if want is None else want.record(), choice=choice)
+    return _parse_choice(sensors.MountJitter, text)
 
 
 def parse_camera_instrument(text):
     """the command line's --camera-instrument: "trained", "off" (None), or "latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F"
     (any key may be left out: the model's latency, gain 1, 0)"""
-    from ..envs.sensors import InstrumentError
-    if text == "trained":
-        return "trained"
-    if text == "off":
-        return None
-    kw = {}
-    for item in text.split(","):
-        k, sep, v = item.partition("=")
-        if not sep or k not in ("latency", "noise_gain", "depth_scale", "depth_quad", "fov") or k in kw:
-            raise ValueError(f"expected trained, off or latency=LO:HI,noise_gain=LO:HI,depth_scale=..,depth_quad=..,fov=.., got {text!r}")
-        if k in ("latency", "noise_gain"):
-            vals = [(int if k == "latency" else float)(x) for x in v.split(":")]
-            if len(vals) != 2:
-                raise ValueError(f"{k}: two numbers joined by ':', got {v!r}")
-            kw[k] = tuple(vals)
-        else:
-            kw[k] = float(v)
-    return InstrumentError(**kw)
+    return _parse_choice(sensors.InstrumentError, text)
 
 
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 MAP_METRICS = ("map_scan_error", "map_coverage")        # accepted when named and the sensor carries an elevation map; never a default
 
 
+def _run(env, ac, ev, steps, cmd, fused, packed_cls, rows=None, blind=False, metrics=()):
+    """evaluate()'s loop, for every kind of policy.  `packed_cls`: the fused launch's class (PackedHimPolicy; PackedVisionPolicy when the
+    actor reads more rows), used when the topology allows and `fused` is not False, else act_inference.  `rows()`: the live [N, L] tensor
+    the actor also reads (cam.latent, cam.memory_rows, cam.map_rows), zeros in its place when `blind`.  `metrics`: (name, fn) per
+    evaluator column, fn(actions, zero_mean, live, priv) -> [N] from the observation the action came from (the step's reset flags decide
+    what counts); zero_mean is the action mean over zero rows, one more policy forward per step, made only for a "depth_influence"
+    column of a policy that is not blind (None otherwise)."""
+    names = tuple(n for n, _ in metrics)
+    if names and ev.column_names != names:
+        ev.add_columns(names)
+    entry = "lsim_policy_forward" if rows is None else "lsim_policy_forward_ext"
+    use_fused = packed_cls.supported(ac) if fused is None else bool(fused)
+    if use_fused and not packed_cls.supported(ac):
+        raise ValueError(f"fused=True but {entry} does not support this policy's topology")
+    if hasattr(env, "_external_call"):
+        env._external_call()
+    dev, N = env.buf["rew"].device, env.num_envs
+    influence = "depth_influence" in names and not blind
+    zeros = torch.zeros(N, ac.depth_latent_dim, device=dev) if rows is not None else None
+    live = mean0 = None
+    fed = ()
+    if use_fused:
+        packed = packed_cls(ac)
+        mean, values = torch.empty(N, env.num_actions, device=dev), torch.empty(N, 1, device=dev)
+        mean0 = torch.empty(N, env.num_actions, device=dev) if influence else None
+    obs, priv = env.get_observations(), env.get_privileged_observations()
+    for _ in range(int(steps)):
+        if cmd is not None:
+            env.commands[:, :3] = cmd
+        if rows is not None:
+            live = rows()
+            fed = (zeros if blind else live,)
+        if use_fused:
+            packed.forward(obs, priv, mean, values, *fed)
+            actions = mean
+            if influence:
+                packed.forward(obs, priv, mean0, values, zeros)
+        else:
+            actions = ac.act_inference(obs, *fed)
+            if influence:
+                mean0 = ac.act_inference(obs, zeros)
+        for k, (_, fn) in enumerate(metrics):
+            ev.columns[:, k] = fn(actions, mean0, live, priv)
+        env.step_device(actions)
+        ev.accumulate()
+        if metrics:
+            ev.accumulate_columns()
+    return ev
+
+
+def _scan_block(env):
+    """(offset, width) of the height scan in the env's privileged observation, or None when it holds none"""
+    from .vision import height_scan_block
+    try:
+        return height_scan_block(env.cfg)
+    except ValueError:
+        return None
+
+
+def _influence(blind):
+    return lambda actions, zero_mean, live, priv: 0.0 if blind else torch.linalg.vector_norm(actions - zero_mean, dim=1)
+
+
 def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, memory=None, memory_head=None):
-    """evaluate()'s loop for a VisionActorCritic: the actor also reads the sensor's live latent rows (zeros when `blind`), and the evaluator
-    accumulates the `metrics` as columns (module docstring of learn/vision.py)"""
-    from .vision import PackedVisionPolicy, height_scan_block
-    dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
+    """evaluate() for a VisionActorCritic: the actor also reads the sensor's live latent rows -- with a memory [z | h] -- and the evaluator
+    accumulates the `metrics` as columns (module docstring of learn/vision.py).  A metric whose inputs are
+    missing -- its head, the map, a privileged observation that holds the scan, the scan's own points -- is dropped, not zero."""
+    from .vision import PackedVisionPolicy
     metrics = list(metrics)
     for m in metrics:
         if m not in VISION_METRICS + MAP_METRICS:
             raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error', "
                              f"with an elevation map also 'map_scan_error' and 'map_coverage')")
-    scan = None
     has_map = getattr(cam, "map", None) is not None
-    if "map_coverage" in metrics and not has_map:
-        metrics.remove("map_coverage")
-    if "map_scan_error" in metrics:         # needs the map, a privileged observation that holds the scan, and the scan's own points
-        try:
-            map_block = height_scan_block(env.cfg) if has_map else None
-        except ValueError:
-            map_block = None
-        if map_block is None or cam.map_scan().shape[1] != map_block[1]:
-            metrics.remove("map_scan_error")
-        else:
-            scan = map_block
-    Lz = L - (memory.hidden if memory is not None else 0)       # the encoder's columns of the actor's depth segment
-    for m, h_ in (("scan_error", head), ("memory_scan_error", memory_head if memory is not None else None)):
-        if m in metrics:                # needs its head and a privileged observation that holds the scan: else dropped, not zero
-            try:
-                found_scan = height_scan_block(env.cfg) if h_ is not None else None
-            except ValueError:
-                found_scan = None
-            if found_scan is None:
-                metrics.remove(m)
-            else:
-                scan = found_scan
-    if metrics and ev.column_names != tuple(metrics):
-        ev.add_columns(metrics)
-    use_fused = PackedVisionPolicy.supported(ac) if fused is None else bool(fused)
-    if use_fused and not PackedVisionPolicy.supported(ac):
-        raise ValueError("fused=True but lsim_policy_forward_ext does not support this policy's topology")
-    if hasattr(env, "_external_call"):
-        env._external_call()
-    zeros = torch.zeros(N, L, device=dev)
-    if use_fused:
-        packed = PackedVisionPolicy(ac)
-        mean, mean0 = torch.empty(N, env.num_actions, device=dev), torch.empty(N, env.num_actions, device=dev)
-        values = torch.empty(N, 1, device=dev)
-    influence = "depth_influence" in metrics
-    obs, priv = env.get_observations(), env.get_privileged_observations()
-    for _ in range(int(steps)):
-        if cmd is not None:
-            env.commands[:, :3] = cmd
-        live = cam.latent() if memory is None else cam.memory_rows()       # with a memory: [z | h], zeros of the same width when blind
-        rows = zeros if blind else live
-        if use_fused:
-            packed.forward(obs, priv, mean, values, rows=rows)
-            actions = mean
-            if influence and not blind:
-                packed.forward(obs, priv, mean0, values, rows=zeros)
-        else:
-            actions = ac.act_inference(obs, depth_latent=rows)
-            if influence and not blind:
-                mean0 = ac.act_inference(obs, depth_latent=zeros)
-        for k, m in enumerate(metrics):     # from the observation the action came from; the step's reset flags decide what counts
-            if m == "depth_influence":
-                ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
-            elif m == "scan_error":
-                ev.columns[:, k] = (head(live[:, :Lz]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
-            elif m == "map_scan_error":     # the map's scan in observation units, exactly as ph_build_obs turns measured_heights into the block
-                block = (cam.map_pose()[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height)       # the height the map has
-                ev.columns[:, k] = (block - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
-            elif m == "map_coverage":
-                ev.columns[:, k] = cam.map_known().to(torch.float32).mean(dim=1)
-            else:
-                ev.columns[:, k] = (memory_head(live[:, Lz:]) - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
-        env.step_device(actions)
-        ev.accumulate()
-        if metrics:
-            ev.accumulate_columns()
-    return ev
+    scan = _scan_block(env)
+    needs = {"map_coverage": has_map, "map_scan_error": has_map and scan is not None and cam.map_scan().shape[1] == scan[1],
+             "scan_error": head is not None and scan is not None, "memory_scan_error": memory is not None and memory_head is not None and scan is not None}
+    Lz = ac.depth_latent_dim - (memory.hidden if memory is not None else 0)       # the encoder's columns of the actor's depth segment
+    target = lambda priv: priv[:, scan[0]:scan[0] + scan[1]]
+    columns = {
+        "depth_influence": _influence(blind),
+        "scan_error": lambda a, a0, live, priv: (head(live[:, :Lz]) - target(priv)).square().mean(dim=1),
+        "memory_scan_error": lambda a, a0, live, priv: (memory_head(live[:, Lz:]) - target(priv)).square().mean(dim=1),
+        # the map's scan in observation units, exactly as ph_build_obs turns measured_heights into the block, from the height the map has
+        "map_scan_error": lambda a, a0, live, priv: ((cam.map_pose()[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height) - target(priv)).square().mean(dim=1),
+        "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
+    return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.latent if memory is None else cam.memory_rows, blind,
+                [(m, columns[m]) for m in metrics if needs.get(m, True)])
 
 
 def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
-    """evaluate()'s loop for a map policy: the actor also reads the sensor's live map rows (zeros when `blind`); of the `metrics` a map
-    policy has "depth_influence" (the action distance against zero rows), "map_scan_error" (the rows' height block against the privileged
-    observation's) and "map_coverage"; the encoder's and the memory's are dropped"""
-    from .vision import PackedVisionPolicy, height_scan_block
-    dev, N, L = env.buf["rew"].device, env.num_envs, ac.depth_latent_dim
-    P = int(cam.map_scan().shape[1])
-    metrics = [m for m in metrics if m in ("depth_influence",) + MAP_METRICS]
-    scan = None
-    if "map_scan_error" in metrics:
-        try:
-            scan = height_scan_block(env.cfg)
-        except ValueError:
-            scan = None
-        if scan is None or scan[1] != P:
-            metrics.remove("map_scan_error")
-    if metrics and ev.column_names != tuple(metrics):
-        ev.add_columns(metrics)
-    use_fused = PackedVisionPolicy.supported(ac) if fused is None else bool(fused)
-    if use_fused and not PackedVisionPolicy.supported(ac):
-        raise ValueError("fused=True but lsim_policy_forward_ext does not support this policy's topology")
-    if hasattr(env, "_external_call"):
-        env._external_call()
-    zeros = torch.zeros(N, L, device=dev)
-    if use_fused:
-        packed = PackedVisionPolicy(ac)
-        mean, mean0 = torch.empty(N, env.num_actions, device=dev), torch.empty(N, env.num_actions, device=dev)
-        values = torch.empty(N, 1, device=dev)
-    influence = "depth_influence" in metrics
-    obs, priv = env.get_observations(), env.get_privileged_observations()
-    for _ in range(int(steps)):
-        if cmd is not None:
-            env.commands[:, :3] = cmd
-        live = cam.map_rows()
-        rows = zeros if blind else live
-        if use_fused:
-            packed.forward(obs, priv, mean, values, rows=rows)
-            actions = mean
-            if influence and not blind:
-                packed.forward(obs, priv, mean0, values, rows=zeros)
-        else:
-            actions = ac.act_inference(obs, depth_latent=rows)
-            if influence and not blind:
-                mean0 = ac.act_inference(obs, depth_latent=zeros)
-        for k, m in enumerate(metrics):
-            if m == "depth_influence":
-                ev.columns[:, k] = 0.0 if blind else torch.linalg.vector_norm(actions - mean0, dim=1)
-            elif m == "map_scan_error":
-                ev.columns[:, k] = (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1)
-            else:
-                ev.columns[:, k] = cam.map_known().to(torch.float32).mean(dim=1)
-        env.step_device(actions)
-        ev.accumulate()
-        if metrics:
-            ev.accumulate_columns()
-    return ev
+    """evaluate() for a map policy: the actor also reads the sensor's live map rows; of the `metrics` a map policy has "depth_influence"
+    (the action distance against zero rows), "map_scan_error" (the rows' height block against the privileged observation's) and
+    "map_coverage"; the encoder's and the memory's are dropped"""
+    from .vision import PackedVisionPolicy
+    P, scan = int(cam.map_scan().shape[1]), _scan_block(env)
+    needs = {"map_scan_error": scan is not None and scan[1] == P}
+    columns = {
+        "depth_influence": _influence(blind),
+        "map_scan_error": lambda a, a0, live, priv: (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1),
+        "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
+    return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.map_rows, blind,
+                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
 
 
 @torch.no_grad()
@@ -719,17 +617,14 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     is_vision = hasattr(ac, "depth_latent_dim")
     is_map = is_vision and ("map_policy" in found or (encoder is None and found.get("encoder") is None and found.get("checkpoint") is None and
                                                       getattr(sensor, "map_channels", None) is not None))
-    if is_map:
-        cam = _map_parts(env, ac, found, sensor)
-        sensor_found = {"checkpoint": {"vision": found["map_policy"]}} if found.get("checkpoint") is not None else {}    # the record sits under another key
-        jitter_entry = _camera_jitter(cam, sensor_found, camera_jitter)
-        instrument_entry = _camera_instrument(cam, sensor_found, camera_instrument)
-        odometry_entry = _map_odometry(cam, found, odometry)
-    elif is_vision:
-        cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
-        jitter_entry = _camera_jitter(cam, found, camera_jitter)       # after the encoder and the memory are attached: a refresh() runs them too
-        instrument_entry = _camera_instrument(cam, found, camera_instrument)
-        odometry_entry = _map_odometry(cam, found, odometry) if getattr(cam, "map", None) is not None else None
+    if is_vision:
+        if is_map:
+            cam, head = _map_parts(env, ac, found, sensor), None
+        else:
+            cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
+        d = found.get("checkpoint") or {}
+        record = (d.get("map_policy") or d.get("vision") or {}).get("sensor")        # the checkpoint's record of the sensor; None: a runner, a module
+        conventions = _sensor_options(cam, record, camera_jitter, camera_instrument, odometry)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -737,37 +632,13 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         cmd = cmd.expand(env.num_envs, 3).contiguous() if cmd.dim() == 1 else cmd.contiguous()
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
+    if not is_vision:
+        return _run(env, ac, ev, steps, cmd, fused, PackedHimPolicy)
+    ev.extra_conventions.update(conventions)
     if is_map:
-        ev.extra_conventions.update(camera_jitter=jitter_entry, camera_instrument=instrument_entry, odometry=odometry_entry)
         return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()))
-    if is_vision:
-        if odometry_entry is not None:
-            ev.extra_conventions["odometry"] = odometry_entry
-        ev.extra_conventions["camera_jitter"] = jitter_entry
-        ev.extra_conventions["camera_instrument"] = instrument_entry
-        return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
-                                memory=found.get("memory"), memory_head=found.get("memory_head"))
-    use_fused = PackedHimPolicy.supported(ac) if fused is None else bool(fused)
-    if use_fused and not PackedHimPolicy.supported(ac):
-        raise ValueError("fused=True but lsim_policy_forward does not support this policy's topology")
-    if hasattr(env, "_external_call"):
-        env._external_call()
-    if use_fused:
-        packed = PackedHimPolicy(ac)
-        mean = torch.empty(env.num_envs, env.num_actions, device=dev)
-        values = torch.empty(env.num_envs, 1, device=dev)
-    obs, priv = env.get_observations(), env.get_privileged_observations()
-    for _ in range(int(steps)):
-        if cmd is not None:
-            env.commands[:, :3] = cmd
-        if use_fused:
-            packed.forward(obs, priv, mean, values)
-            actions = mean
-        else:
-            actions = ac.act_inference(obs)
-        env.step_device(actions)
-        ev.accumulate()
-    return ev
+    return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
+                            memory=found.get("memory"), memory_head=found.get("memory_head"))
 
 
 def format_table(result):
@@ -807,18 +678,11 @@ def parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
-    try:
-        a.camera_instrument = parse_camera_instrument(a.camera_instrument)
-    except ValueError as exc:
-        ap.error(f"--camera-instrument: {exc}")
-    try:
-        a.odometry = parse_odometry(a.odometry)
-    except ValueError as exc:
-        ap.error(f"--odometry: {exc}")
-    try:
-        a.camera_jitter = parse_camera_jitter(a.camera_jitter)
-    except ValueError as exc:
-        ap.error(f"--camera-jitter: {exc}")
+    for name, parse in (("camera_instrument", parse_camera_instrument), ("odometry", parse_odometry), ("camera_jitter", parse_camera_jitter)):
+        try:
+            setattr(a, name, parse(getattr(a, name)))
+        except ValueError as exc:
+            ap.error(f"--{name.replace('_', '-')}: {exc}")
     if a.envs < 1 or a.steps < 1:
         ap.error("--envs and --steps must be positive")
     if a.commands == "env":
@@ -865,8 +729,7 @@ def main(argv=None):
     d = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     record = d.get("vision") or d.get("map_policy") or {}
     if record.get("sensor") is not None:       # a vision or a map policy's checkpoint names the camera it was trained with
-        from ..envs.sensors import from_spec
-        env.add_sensor("depth", from_spec(env, record["sensor"]))
+        env.add_sensor("depth", sensors.from_spec(env, record["sensor"]))
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
                   vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry)
     res = ev.result()

@@ -14,36 +14,19 @@ latent" from the rollout to the update, and a HIM policy warm-starts it through 
 and no snapshot: the rows are the map's, and no gradient goes anywhere but into the actor-critic.  One rank only."""
 import copy
 
-from .him_ppo import HIMPPO
-from .runner import _ALGOS, _POLICIES, HIMOnPolicyRunner
-from .vision import PackedVisionPolicy, VisionActorCritic, VisionPPO, VisionRollout
+from .runner import _ALGOS, _POLICIES
+from .vision import ActorRowsPPO, ActorRowsRunner, VisionActorCritic
 
 CHANNELS = (("height",), ("height", "known"))
 
 
-class MapPPO(VisionPPO):
-    """VisionPPO without an encoder: act() records `latent_source()` (the runner passes sensor.map_rows) with the transition and the update
-    binds each minibatch's stored rows to the actor; no snapshots are kept and no encoder or memory step follows.  update() returns
+class MapPPO(ActorRowsPPO):
+    """act() records `latent_source()` (the runner passes sensor.map_rows) with the transition and the update binds each minibatch's
+    stored rows to the actor; there is no encoder, so no snapshots are kept and no encoder or memory step follows.  update() returns
     HIMPPO.update()'s tuple."""
 
-    def __init__(self, actor_critic, latent_source=None, **kwargs):
-        super().__init__(actor_critic, **kwargs)
-        self.latent_source = latent_source
 
-    def attach(self, *a, **kw):
-        raise NotImplementedError("MapPPO: a map policy has no encoder to attach (set latent_source)")
-
-    def snapshot_steps(self):
-        return []
-
-    def snapshot_if_due(self, step, critic_obs):
-        return
-
-    def update(self):
-        return HIMPPO.update(self)
-
-
-class MapOnPolicyRunner(HIMOnPolicyRunner):
+class MapOnPolicyRunner(ActorRowsRunner):
     """HIMOnPolicyRunner for a map policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs
     an attached ElevationMap (cam.attach_map, with or without odometry).  `channels`: ("height",) or ("height", "known"); the runner calls
     cam.attach_map_rows(channels) and the actor reads cam.map_rows(), channels * P more columns.  train_cfg is HIMOnPolicyRunner's;
@@ -60,10 +43,7 @@ class MapOnPolicyRunner(HIMOnPolicyRunner):
         if channels not in CHANNELS:
             raise ValueError(f"MapOnPolicyRunner: channels is ('height',) or ('height', 'known'), got {channels}")
         dim = len(channels) * int(cam.map_scan().shape[1])
-        first = env.num_one_step_obs + 3 + 16 + dim
-        if first > 272:             # LS_POL_MAX_IN (csrc/ls_policy.h): the fused policy launch's widest input row
-            raise ValueError(f"MapOnPolicyRunner: the first actor layer would read {first} columns ({env.num_one_step_obs} + 3 + 16 + map rows "
-                             f"{dim}), the fused policy launch takes at most 272")
+        self._check_first_layer(env, **{"map rows": dim})
         _POLICIES["VisionActorCritic"], _ALGOS["MapPPO"] = VisionActorCritic, MapPPO
         cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
         cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "MapPPO"
@@ -72,9 +52,6 @@ class MapOnPolicyRunner(HIMOnPolicyRunner):
         super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
         cam.attach_map_rows(channels)       # behind the parent's env.reset(): the sensor has captured, so every env's rows are built now
         self.alg.latent_source = cam.map_rows
-
-    def _make_fused_rollout(self):
-        return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
 
     def _extra_checkpoint_state(self):
         out = super()._extra_checkpoint_state()

@@ -150,22 +150,59 @@ class VisionRolloutStorage(HIMRolloutStorage):
         return (self.depth_latent.flatten(0, 1),)
 
 
-class VisionPPO(HIMPPO):
-    """HIMPPO over a VisionActorCritic.  act() records `latent_source()` (the runner passes sensor.latent) with the transition, the update binds
-    each minibatch's stored rows to the actor, and behind it the encoder takes its own steps: `aux_snapshots` rollout steps, spread evenly
-    over the T steps, each keep a copy of (frames_source(), height scan of the same step's critic observation); one pass over them, one
-    minibatch per snapshot, of  z = encoder(frames), loss = mse(head(z), target), Adam(aux_learning_rate) over encoder and head.
-    update() returns HIMPPO's values plus the mean auxiliary loss."""
+class ActorRowsPPO(HIMPPO):
+    """HIMPPO over a VisionActorCritic, whatever the extra actor rows are: act() records `latent_source()` ([N, L], live) with the
+    transition and the update binds each minibatch's stored rows to the actor.  Nothing but the actor-critic is trained and update()
+    returns HIMPPO.update()'s tuple: learn/map_policy.py's MapPPO is this class; VisionPPO adds the encoder.  One rank only."""
+    encoder = None          # VisionPPO's
 
-    def __init__(self, actor_critic, encoder=None, latent_source=None, frames_source=None, height_scan=None, aux_snapshots=4, aux_learning_rate=1e-3,
-                 memory_env_minibatches=4, memory_learning_rate=1e-3, dist_ctx=None, **kwargs):
+    def __init__(self, actor_critic, latent_source=None, dist_ctx=None, **kwargs):
         if dist_ctx is not None and getattr(dist_ctx, "world", 1) > 1:
             raise NotImplementedError("VisionPPO: one rank only (the encoder's gradients are not reduced over ranks)")
         super().__init__(actor_critic, dist_ctx=dist_ctx, **kwargs)
         self.transition = VisionRolloutStorage.Transition()
+        self.latent_source = latent_source
+
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+        self.storage = VisionRolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape,
+                                            self.actor_critic.depth_latent_dim, self.device)
+
+    def _latent_now(self):
+        if self.latent_source is None:
+            raise RuntimeError("VisionPPO: no latent source (attach(encoder, latent_source, frames_source))")
+        return self.latent_source()
+
+    def snapshot_steps(self):
+        return []
+
+    def snapshot_if_due(self, step, critic_obs):
+        """called once per rollout step, before the env steps (act(), VisionRollout._act): nothing to keep here"""
+
+    def act(self, obs, critic_obs):
+        rows = self._latent_now().detach().clone()          # a live sensor buffer: the transition keeps what the actor saw
+        self.snapshot_if_due(self.storage.step, critic_obs)
+        with self.actor_critic.bound_latent(rows):
+            actions = super().act(obs, critic_obs)
+        self.transition.depth_latent = rows
+        return actions
+
+    def _mb_forward(self, ac, batch, two_streams):
+        with ac.bound_latent(batch[10]):
+            return super()._mb_forward(ac, batch[:10], two_streams)
+
+
+class VisionPPO(ActorRowsPPO):
+    """ActorRowsPPO whose rows are a depth encoder's latent (the runner passes sensor.latent), with the encoder's own steps behind the
+    update: `aux_snapshots` rollout steps, spread evenly over the T steps, each keep a copy of (frames_source(), height scan of the same
+    step's critic observation); one pass over them, one minibatch per snapshot, of  z = encoder(frames), loss = mse(head(z), target),
+    Adam(aux_learning_rate) over encoder and head.  update() returns HIMPPO's values plus the mean auxiliary loss."""
+
+    def __init__(self, actor_critic, encoder=None, latent_source=None, frames_source=None, height_scan=None, aux_snapshots=4, aux_learning_rate=1e-3,
+                 memory_env_minibatches=4, memory_learning_rate=1e-3, dist_ctx=None, **kwargs):
+        super().__init__(actor_critic, dist_ctx=dist_ctx, **kwargs)
         self.aux_snapshots, self.aux_learning_rate = int(aux_snapshots), float(aux_learning_rate)
         self.encoder = self.depth_head = self.aux_optimizer = None
-        self.latent_source = self.frames_source = self.height_scan = None
+        self.frames_source = self.height_scan = None
         self._snap, self._snap_filled = [], []
         self.last_aux_loss = float("nan")
         self.memory = self.memory_head = self.memory_optimizer = None
@@ -194,23 +231,6 @@ class VisionPPO(HIMPPO):
             self.memory_head = nn.Linear(memory.hidden, self.height_scan[1]).to(self.device)
             self.memory_optimizer = torch.optim.Adam(list(self.memory.parameters()) + list(self.memory_head.parameters()), lr=self.memory_learning_rate)
 
-    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
-        self.storage = VisionRolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape,
-                                            self.actor_critic.depth_latent_dim, self.device)
-
-    def _latent_now(self):
-        if self.latent_source is None:
-            raise RuntimeError("VisionPPO: no latent source (attach(encoder, latent_source, frames_source))")
-        return self.latent_source()
-
-    def act(self, obs, critic_obs):
-        rows = self._latent_now().detach().clone()          # a live sensor buffer: the transition keeps what the actor saw
-        self.snapshot_if_due(self.storage.step, critic_obs)
-        with self.actor_critic.bound_latent(rows):
-            actions = super().act(obs, critic_obs)
-        self.transition.depth_latent = rows
-        return actions
-
     # ---- the encoder's own training data: a few (frames, target) pairs per rollout
     def snapshot_steps(self):
         T = self.storage.num_transitions_per_env
@@ -237,10 +257,6 @@ class VisionPPO(HIMPPO):
         self._snap[slot][0].copy_(frames)
         self._snap[slot][1].copy_(critic_obs[:, off:off + width])
         self._snap_filled[slot] = True
-
-    def _mb_forward(self, ac, batch, two_streams):
-        with ac.bound_latent(batch[10]):
-            return super()._mb_forward(ac, batch[:10], two_streams)
 
     def encoder_step(self):
         """one pass over this rollout's snapshots -> mean loss (a 0-d tensor), or None without a snapshot"""
@@ -375,7 +391,20 @@ class VisionRollout(GraphedRollout):
                                 self.mean, self.values, self.actions, prev=prev, rows=self.alg._latent_now(), store=self.storage.depth_latent)
 
 
-class VisionOnPolicyRunner(HIMOnPolicyRunner):
+class ActorRowsRunner(HIMOnPolicyRunner):
+    """what the runners of a policy whose actor reads a sensor's rows (`self.sensor`) share: the fused policy launch's width limit and rollout"""
+
+    def _check_first_layer(self, env, **widths):
+        first = env.num_one_step_obs + 3 + 16 + sum(widths.values())
+        if first > 272:         # LS_POL_MAX_IN (csrc/ls_policy.h): the fused policy launch's widest input row
+            raise ValueError(f"{type(self).__name__}: the first actor layer would read {first} columns ({env.num_one_step_obs} + 3 + 16 + "
+                             f"{' + '.join(f'{k} {v}' for k, v in widths.items())}), the fused policy launch takes at most 272")
+
+    def _make_fused_rollout(self):
+        return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
+
+
+class VisionOnPolicyRunner(ActorRowsRunner):
     """HIMOnPolicyRunner for a vision policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs a
     SensorModel (the frame history).  `encoder`: a DepthEncoder for its frames; default DepthEncoder(height, width, frames).  The runner
     attaches the encoder to the sensor.  train_cfg is HIMOnPolicyRunner's; policy["depth_latent_dim"] is set from the encoder and
@@ -407,10 +436,7 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
                                  f"the encoder writes {encoder.latent_dim} and a one-step observation has {env.num_one_step_obs}")
             memory = memory.to(device)
             cfg["policy"]["depth_latent_dim"] = encoder.latent_dim + memory.hidden
-            first = env.num_one_step_obs + 3 + 16 + encoder.latent_dim + memory.hidden
-            if first > 272:         # LS_POL_MAX_IN (csrc/ls_policy.h): the fused policy launch's widest input row
-                raise ValueError(f"VisionOnPolicyRunner: the first actor layer would read {first} columns ({env.num_one_step_obs} + 3 + 16 + latent "
-                                 f"{encoder.latent_dim} + hidden {memory.hidden}), the fused policy launch takes at most 272")
+            self._check_first_layer(env, latent=encoder.latent_dim, hidden=memory.hidden)
         else:
             memory = None
         self.sensor, self.memory = cam, memory
@@ -422,9 +448,6 @@ class VisionOnPolicyRunner(HIMOnPolicyRunner):
         else:
             cam.attach_memory(memory)       # every env steps once from h = 0
             self.alg.attach(encoder, cam.memory_rows, frames, scan, memory=memory)
-
-    def _make_fused_rollout(self):
-        return VisionRollout(self, self.sensor) if PackedVisionPolicy.supported(self.alg.actor_critic) else None
 
     def _extra_checkpoint_state(self):
         out = super()._extra_checkpoint_state()

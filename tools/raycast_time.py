@@ -95,18 +95,7 @@ def counters_bodies(sensor, count_lib):
 
 def parse_model(text):
     """sensors.SensorModel from key=value pairs: period, stagger, latency, frames, noise=sigma0:sigma2, dropout, drop_value, clip=lo:hi, normalise"""
-    kw = {}
-    for item in text.split(","):
-        k, v = item.split("=")
-        if k in ("noise", "clip"):
-            kw[k] = tuple(float(x) for x in v.split(":"))
-        elif k in ("dropout", "drop_value"):
-            kw[k] = float(v)
-        elif k in ("stagger", "normalise"):
-            kw[k] = bool(int(v))
-        else:
-            kw[k] = int(v)
-    return sensors.SensorModel(**kw)
+    return sensors.parse_option(sensors.SensorModel, text)
 
 
 def timed_ticks(sensor, iters, warmup):
