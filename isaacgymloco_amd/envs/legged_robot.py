@@ -337,11 +337,8 @@ class LeggedRobot:
         return sensor
 
     def _update_sensors(self, model_flags=0):
-        for s in self.sensors.values():
-            if getattr(s, "model", None) is None:
-                s.update()
-            else:
-                s.update(tick=self.common_step_counter, flags=model_flags)
+        for s in self.sensors.values():         # a sensor without a model ignores both
+            s.update(tick=self.common_step_counter, flags=model_flags)
 
     def step(self, actions):
         """LeggedRobot.step (LR:122-176): same 7-tuple (8 with terminal AMP states when using_amp)."""

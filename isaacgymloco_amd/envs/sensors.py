@@ -289,6 +289,38 @@ def parse_elevation_map(text):
     return parse_option(ElevationMap, text)
 
 
+_ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "map_rows", "encoder", "memory")      # a chain's launch order
+_DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory",)}                                             # who goes with whom
+_ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
+           "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
+           "memory": "memory (attach_memory)"}
+_FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+
+
+class Stage:
+    """One launch of a sensor's chain.  `entry`: the name of the entry point it launches; `struct`: its ctypes struct (None: `run`, the
+    launch of an encoder or a memory, builds its own); `buffers`: the tensors the stage allocated and nobody else owns, by name;
+    `option`: what it was attached with (the MountJitter, the ElevationMap, the encoder ...).  Dropping the stage drops all of them."""
+
+    def __init__(self, sensor, name, entry, struct, buffers=None, option=None, run=None):
+        self.name, self.entry, self.struct, self.option, self.args = name, entry, struct, option, ()
+        self.buffers = {} if buffers is None else buffers
+        self._sensor, self._run, self._ticks, self._ref = sensor, run, hasattr(struct, "tick"), None if struct is None else ctypes.byref(struct)
+
+    def launch(self, tick, flags, stream=None):
+        """the launch on `stream` (default: the sensor's), with `tick` and `flags` where the entry point takes them"""
+        if self._run is not None:
+            return self._run(tick, flags, stream)
+        if self._ticks:
+            self.struct.tick, self.struct.flags = tick, flags
+        sensor = self._sensor
+        lib.check(getattr(sensor._api, self.entry)(self._ref, *self.args, sensor._stream(stream)), what=self.entry)
+
+
+def _option(name):
+    return property(lambda self: getattr(self._stages.get(name), "option", None), doc=f"what the stage {name!r} was attached with; None without it")
+
+
 class RaySensor:
     """R rays per env against the terrain.  `dirs` [R, 3] unit vectors in the sensor frame; `mount_pos` (3) / `mount_quat` (4, xyzw): one pose, a
     dict {robot name: pose} for a mixed-robot instance, or one per env ([N, 3] / [N, 4]); `scale` [R] or None; every `env_stride`-th env is
@@ -311,25 +343,36 @@ class RaySensor:
     [N, P] samples, `map_heights()` a window-ordered copy for people and tools, `map_state()` the three raw arrays.  Without it nothing
     of this is allocated or launched.  `attach_map(m, odometry=OdometryError(...))`: lsim_odometry_step ahead of every capture, and the map
     reads `odometry_pose()` [N, 13] (its state: `odometry_state()` [N, 12]) where it read root_states.  `attach_map_rows(channels)`:
-    lsim_map_rows behind the map's launch, `map_rows()` the live [N, channels * P] rows an actor reads."""
+    lsim_map_rows behind the map's launch, `map_rows()` the live [N, channels * P] rows an actor reads.
+    `kind`: the record spec() opens with -- {"kind": "camera", "width", "height"}, {"kind": "lidar", "channels", "points_per_rev"}, None:
+    {"kind": "rays"} -- whose numbers are also attributes of the sensor.
+
+    The chain: every launch behind update() is a Stage, kept by name and launched in the order of _ORDER; `chain()` names
+    the entry points, `stage(name)` hands one out (None: not attached); without a model it is the one stage "rays".  ONE ray struct, the
+    outermost that is launched: `ray_struct` and `bodies_struct` (None in the terrain-only form) are views into it.  `out_rows` /
+    `label_rows`: the padded tensors `out` / `labels()` are views of; `history()`: the raw frame history."""
+
+    mount_jitter, instrument, map, odometry, map_channels = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "map_rows"))
+    encoder, memory = _option("encoder"), _option("memory")
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None):
         self.env = env
         self.model = model
         self._api = api if api is not None else env._L
+        self.kind = {"kind": "rays"} if kind is None else {k: v if k == "kind" else int(v) for k, v in kind.items()}
+        vars(self).update({k: v for k, v in self.kind.items() if k != "kind"})
         if frame not in ("base", "yaw"):
             raise ValueError(f"frame: expected 'base' or 'yaw', got {frame!r}")
         self.see_robot, self.frame = bool(see_robot), frame
         self.body_mask, self.body_names = None, []
-        self._bodies = self.see_robot or frame == "yaw"       # the yaw frame is the new entry point's, with or without bodies
+        bodies = self.see_robot or frame == "yaw"             # the yaw frame is the new entry point's, with or without bodies
         if (labels or len(tuple(ignore_bodies))) and not self.see_robot:
             raise ValueError("labels / ignore_bodies need see_robot=True")
-        need = "lsim_raycast_bodies" if self._bodies else "lsim_raycast"
-        if not hasattr(self._api, need):
-            raise lib.LsimError(f"the loaded library has no {need}: rebuild it (there is no torch fall-back for the range sensors)")
-        if model is not None and not hasattr(self._api, "lsim_sensor_capture"):
-            raise lib.LsimError("the loaded library has no lsim_sensor_capture: rebuild it (there is no torch fall-back for the sensor model)")
+        rays = "lsim_raycast_bodies" if bodies else "lsim_raycast"
+        lib.entry(self._api, rays, "the range sensors")
+        if model is not None:
+            lib.entry(self._api, "lsim_sensor_capture", "the sensor model")
         dev = env.root_states.device
         N = int(env.num_envs)
         self.dirs = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3), device=dev).contiguous()
@@ -337,26 +380,28 @@ class RaySensor:
         self.near, self.far, self.env_stride = float(near), float(far), int(env_stride)
         self.scale = None if scale is None else torch.as_tensor(np.ascontiguousarray(scale, dtype=np.float32).reshape(R), device=dev).contiguous()
         self.mount = self.mount_nominal = torch.cat((self._per_env(mount_pos, 3, dev), self._per_env(mount_quat, 4, dev)), dim=1).contiguous()
-        self.mount_jitter = self._mj = None
-        self.instrument = self._si = self._inst = None
         stride = (R + 3) // 4 * 4
-        self._out = torch.full((N, stride), self.far, dtype=torch.float32, device=dev)
+        self.out_rows = torch.full((N, stride), self.far, dtype=torch.float32, device=dev)
         if self.scale is not None:
-            self._out[:, :R] *= self.scale
-        self.out = self._out[:, :R]
+            self.out_rows[:, :R] *= self.scale
+        self.out, self.label_rows = self.out_rows[:, :R], None
         nbytes, rbytes = ctypes.c_size_t(), ctypes.c_size_t()
-        if self._bodies:
+        if bodies:
             lib.check(self._api.lsim_raycast_bodies_sizes(ctypes.byref(nbytes), ctypes.byref(rbytes)), what="lsim_raycast_bodies_sizes")
             if rbytes.value != ctypes.sizeof(abi.LsimRaycastRobot):
                 raise lib.LsimError("lsim_raycast_robot: the library's layout differs from include/lsim.h; rebuild")
         else:
             lib.check(self._api.lsim_raycast_sizes(ctypes.byref(nbytes)), what="lsim_raycast_sizes")
         self.state = torch.zeros(nbytes.value // 8, dtype=torch.int64, device=dev)
+        # the one struct that is launched; the inner ones are views into its memory (with a model and no bodies, sm.rb keeps robots NULL,
+        # num_robots 0, flags 0: the terrain-only form)
+        top = abi.LsimSensorModel() if model is not None else abi.LsimRaycastBodies() if bodies else abi.LsimRaycast()
+        self.bodies_struct = None if not bodies else top.rb if model is not None else top
+        rc = self.ray_struct = top.rb.rc if model is not None else top.rc if bodies else top
         lc = env.lcfg
-        rc = abi.LsimRaycast()
         rc.root_states, rc.mount, rc.dirs = env.root_states.data_ptr(), self.mount.data_ptr(), self.dirs.data_ptr()
         rc.scale = None if self.scale is None else self.scale.data_ptr()
-        rc.out, rc.state = self._out.data_ptr(), self.state.data_ptr()
+        rc.out, rc.state = self.out_rows.data_ptr(), self.state.data_ptr()
         rc.mesh_type = int(lc.mesh_type)
         if rc.mesh_type != 0:
             rc.mesh = env.buf["terrain_mesh"].data_ptr()
@@ -364,27 +409,90 @@ class RaySensor:
         rc.horizontal_scale, rc.vertical_scale, rc.border_size = lc.horizontal_scale, lc.vertical_scale, lc.border_size
         rc.num_envs, rc.num_rays, rc.env_stride, rc.out_stride = N, R, self.env_stride, stride
         rc.near, rc.far = self.near, self.far
-        self._rc = rc
-        self._labels = None
-        self._encoder = self._latent = self._memory = self._memory_h = self._memory_rows = None
-        self.map = self._em = self._map = None
-        self.odometry = self._od = self._odo = None
-        self.map_channels = self._mr = self._rows = None
-        if self._bodies:
-            self._setup_bodies(rc, ignore_bodies, labels, dev)
-        if model is not None:
-            self._setup_model(model, dev)
+        self._stages, self._chain, self._spare = {}, (), {}
+        if bodies:
+            self._setup_bodies(self.bodies_struct, ignore_bodies, labels, dev)
+        if model is None:
+            self._attach(Stage(self, "rays", rays, top))
+        else:
+            self._setup_model(top, model, dev)
         if mount_jitter is not None:
             self.set_mount_jitter(mount_jitter)
         if instrument is not None:
             self.set_instrument(instrument)
 
+    # ---- the chain
+    def chain(self):
+        """the entry points update() launches, in launch order"""
+        return tuple(s.entry for s in self._chain)
+
+    def stage(self, name):
+        """the Stage `name` (one of _ORDER), or None when it is not attached"""
+        return self._stages.get(name)
+
+    def _need(self, name):
+        if name not in self._stages:
+            raise ValueError(f"the sensor has no {_ABSENT[name]}")
+        return self._stages[name]
+
+    # the private names of before the chain, read-only, for scripts outside the repository that reached them (nothing inside does, DESIGN.md
+    # 7.17): name -> (stage, what of it); None while the stage is not attached, as the fields were
+    _BEFORE = {"_mj": ("mount_jitter", "struct"), "_si": ("instrument", "struct"), "_inst": ("instrument", "inst"), "_em": ("map", "struct"),
+               "_map": ("map", "buffers"), "_od": ("odometry", "struct"), "_odo": ("odometry", "buffers"), "_mr": ("map_rows", "struct"),
+               "_rows": ("map_rows", "rows"), "_encoder": ("encoder", "option"), "_memory": ("memory", "option"), "_memory_h": ("memory", "h"),
+               "_memory_rows": ("memory", "rows"), "_sm": ("capture", "struct"), "_hist": ("capture", "hist")}
+    _BEFORE_FIXED = {"_rc": "ray_struct", "_rb": "bodies_struct", "_out": "out_rows", "_labels": "label_rows"}
+
+    def __getattr__(self, name):            # reached only for a name the object does not have
+        stages = self.__dict__.get("_stages")
+        if stages is not None and name in self._BEFORE:
+            owner, what = self._BEFORE[name]
+            if owner in stages:
+                return getattr(stages[owner], what) if hasattr(stages[owner], what) else stages[owner].buffers[what]
+            if owner != "capture":          # _sm and _hist did not exist without a model, _rb not without bodies
+                return None
+        elif stages is not None and name == "_latent":
+            return self._latent_held().get("latent")
+        elif name in self._BEFORE_FIXED and (name != "_rb" or self.__dict__.get("bodies_struct") is not None):
+            return getattr(self, self._BEFORE_FIXED[name])
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
+
+    def _attach(self, stage):
+        """`stage` joins the chain, in place of the one of its name.  What every stage has in common with the capture -- who starts an
+        episode, the noise stream, the envs visited -- is written here, into the fields its struct has"""
+        if stage.struct is not None and stage.name not in ("rays", "capture"):
+            for src, fields in ((self._stages["capture"].struct, ("episode_length", "seed", "rank", "stream_id")), (self.ray_struct, ("num_envs", "env_stride"))):
+                for f in fields:
+                    if hasattr(stage.struct, f):
+                        setattr(stage.struct, f, getattr(src, f))
+        self._stages[stage.name] = stage
+        self._rebuild()
+        return stage
+
+    def _drop(self, name):
+        """the stage `name` leaves the chain and with it its struct, its buffers and the stages that need it"""
+        for n in (name,) + _DEPENDENTS.get(name, ()):
+            self._stages.pop(n, None)
+        self._rebuild()
+
+    def _rebuild(self):
+        cap, inst = self._stages.get("capture"), self._stages.get("instrument")
+        if cap is not None:                 # the capture that reads the instrument's rows, or the plain one
+            cap.entry, cap.args = ("lsim_sensor_capture", ()) if inst is None else ("lsim_sensor_capture_inst", (inst.buffers["inst"].data_ptr(),))
+        self._chain = tuple(self._stages[n] for n in _ORDER if n in self._stages)
+
+    def _kept(self, name, make):
+        """the buffers the stage `name` holds already (set again: what was drawn so far stays), else make()"""
+        return self._stages[name].buffers if name in self._stages else make()
+
+    def _zeros(self, *shape, dtype=torch.float32):
+        return torch.zeros(shape, dtype=dtype, device=self.out_rows.device)
+
     def set_instrument(self, instrument):
         """`instrument` (an InstrumentError) from now on, or None: back to lsim_sensor_capture, no launch and no rows.  Until the next
         refresh() (every env) or, env by env, until episodes start, the rows are the neutral ones: the model's own constants"""
         if instrument is None:
-            self.instrument = self._si = self._inst = None
-            return
+            return self._drop("instrument")
         if not isinstance(instrument, InstrumentError):
             raise TypeError(f"instrument: expected an InstrumentError or None, got {type(instrument).__name__}")
         if self.model is None:
@@ -395,97 +503,81 @@ class RaySensor:
         if instrument.fov > 0.0 and bool((self.dirs[:, 0] <= 0.0).any()):
             raise ValueError("instrument: fov > 0 needs rays that all look forward (dirs[:, 0] > 0): a ray at or behind the image plane has no tangent to scale")
         for need in ("lsim_sensor_instrument", "lsim_sensor_capture_inst"):
-            if not hasattr(self._api, need):
-                raise lib.LsimError(f"the loaded library has no {need}: rebuild it (there is no torch fall-back for the instrument error)")
-        N = int(self.env.num_envs)
-        if self._inst is None:
-            self._inst = torch.zeros((N, 8), dtype=torch.float32, device=self._out.device)
-            self._inst[:, 0], self._inst[:, 1], self._inst[:, 4] = float(self.model.latency), 1.0, 1.0
+            lib.entry(self._api, need, "the instrument error")
+
+        def neutral():
+            rows = self._zeros(int(self.env.num_envs), 8)
+            rows[:, 0], rows[:, 1], rows[:, 4] = float(self.model.latency), 1.0, 1.0
+            return {"inst": rows}
+        buffers = self._kept("instrument", neutral)
         si = abi.LsimSensorInstrument()
-        si.inst, si.episode_length = self._inst.data_ptr(), self._sm.episode_length
-        si.seed, si.rank, si.stream_id = self._sm.seed, self._sm.rank, self._sm.stream_id
-        si.num_envs, si.env_stride = N, self.env_stride
+        si.inst = buffers["inst"].data_ptr()
         si.lat_lo, si.lat_hi = lat
         si.gain_lo, si.gain_hi = instrument.noise_gain
         si.scale_range, si.quad_range, si.fov_range = instrument.depth_scale, instrument.depth_quad, instrument.fov
-        self.instrument, self._si = instrument, si
+        self._attach(Stage(self, "instrument", "lsim_sensor_instrument", si, buffers, instrument))
 
     def instrument_rows(self):
         """live [N, 8] tensor: row e = {latency, noise gain, depth_scale, depth_quad, tan_scale, 0, 0, 0} of env e (instrument=...)"""
-        if self._inst is None:
-            raise ValueError("the sensor has no instrument error (instrument=InstrumentError(...))")
-        return self._inst
+        return self._need("instrument").buffers["inst"]
 
     def set_mount_jitter(self, jitter):
         """`jitter` (a MountJitter) from now on, or None: back to the nominal mount and no launch.  The new poses are drawn by the next
         refresh() (every env) or, env by env, as episodes start"""
         if jitter is None:
-            self.mount_jitter = self._mj = None
-            self._point_mount(self.mount_nominal)
-            return
+            self._drop("mount_jitter")
+            return self._point_mount(self.mount_nominal)
         if not isinstance(jitter, MountJitter):
             raise TypeError(f"mount_jitter: expected a MountJitter or None, got {type(jitter).__name__}")
         if self.model is None:
             raise ValueError("mount_jitter needs a model (SensorModel): the tick and the episode lengths that say who starts an episode are the model's")
-        if not hasattr(self._api, "lsim_sensor_mount_jitter"):
-            raise lib.LsimError("the loaded library has no lsim_sensor_mount_jitter: rebuild it (there is no torch fall-back for the mount jitter)")
-        if self.mount is self.mount_nominal:
-            self._point_mount(self.mount_nominal.clone())
+        lib.entry(self._api, "lsim_sensor_mount_jitter", "the mount jitter")
+        buffers = self._kept("mount_jitter", lambda: {"mount": self.mount_nominal.clone()})
+        self._point_mount(buffers["mount"])
         mj = abi.LsimSensorMountJitter()
-        mj.nominal, mj.mount, mj.episode_length = self.mount_nominal.data_ptr(), self.mount.data_ptr(), self._sm.episode_length
-        mj.seed, mj.rank, mj.stream_id = self._sm.seed, self._sm.rank, self._sm.stream_id
-        mj.num_envs, mj.env_stride = int(self.env.num_envs), self.env_stride
+        mj.nominal, mj.mount = self.mount_nominal.data_ptr(), self.mount.data_ptr()
         for k in range(3):
             mj.pos_range[k], mj.rot_range[k] = jitter.pos[k], math.radians(jitter.rot_deg[k])
-        self.mount_jitter, self._mj = jitter, mj
+        self._attach(Stage(self, "mount_jitter", "lsim_sensor_mount_jitter", mj, buffers, jitter))
 
     def _point_mount(self, mount):
-        """`mount` is what every launch of this sensor reads from now on (the structs hold copies of one another)"""
+        """`mount` is what every launch of this sensor reads from now on"""
         self.mount = mount
-        self._rc.mount = mount.data_ptr()
-        if self._bodies:
-            self._rb.rc.mount = mount.data_ptr()
-        if self.model is not None:
-            self._sm.rb.rc.mount = mount.data_ptr()
+        self.ray_struct.mount = mount.data_ptr()
 
-    def _setup_model(self, model, dev):
-        """the lsim_sensor_model struct around the sensor's lsim_raycast_bodies (or, terrain only, around its lsim_raycast) and the history"""
-        env, N = self.env, int(self.env.num_envs)
-        sm = abi.LsimSensorModel()
-        if self._bodies:
-            sm.rb = self._rb
-        else:
-            sm.rb.rc = self._rc               # robots NULL, num_robots 0, flags 0: the terrain-only form
+    def _setup_model(self, sm, model, dev):
+        """the lsim_sensor_model fields around the ray struct, and the history: the stage "capture" """
+        env = self.env
         self._episode_length = env.episode_length_buf
         sm.episode_length = self._episode_length.data_ptr()
-        K, stride = model.latency + model.frames, self._out.shape[1]
-        self._hist = torch.zeros((N, K, stride), dtype=torch.float32, device=dev)
-        sm.hist, sm.hist_stride = self._hist.data_ptr(), stride
+        K, stride = model.latency + model.frames, self.out_rows.shape[1]
+        hist = self._zeros(int(env.num_envs), K, stride)
+        sm.hist, sm.hist_stride = hist.data_ptr(), stride
         sm.seed, sm.rank, sm.stream_id = int(env.lcfg.seed), int(env.lcfg.rank), 0
         sm.period, sm.stagger, sm.latency, sm.frames = model.period, int(model.stagger), model.latency, model.frames
         sm.sigma0, sm.sigma2 = model.noise
         sm.p_drop, sm.drop_value = model.dropout, model.drop_value
         (sm.clip_lo, sm.clip_hi), sm.offset, sm.gain = model.offset_gain(self.near, self.far)
-        self._sm = sm
+        self._attach(Stage(self, "capture", "lsim_sensor_capture", sm, {"hist": hist}, model))
         self.tick = -1
 
     @property
     def stream_id(self):
-        return int(self._sm.stream_id) if self.model is not None else 0
+        return int(self._stages["capture"].struct.stream_id) if self.model is not None else 0
 
     @stream_id.setter
     def stream_id(self, value):
-        if self.model is not None:
-            self._sm.stream_id = int(value)
-            if self._mj is not None:
-                self._mj.stream_id = int(value)
-            if self._si is not None:
-                self._si.stream_id = int(value)
-            if self._od is not None:
-                self._od.stream_id = int(value)
+        for s in self._chain:
+            if hasattr(s.struct, "stream_id"):
+                s.struct.stream_id = int(value)
 
-    def _setup_bodies(self, rc, ignore_bodies, labels, dev):
-        """the lsim_raycast_bodies struct around `rc`: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
+    @property
+    def episode_length_ptr(self):
+        """the address of the env's episode lengths, as the capture reads them (a model only)"""
+        return self._stages["capture"].struct.episode_length
+
+    def _setup_bodies(self, rb, ignore_bodies, labels, dev):
+        """the lsim_raycast_bodies fields around the ray struct: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
         from ..robots.model import build_sensor_table
         env = self.env
         tables = getattr(env, "sensor_tables", None)          # (tables, body names) given by the env (the test doubles), else from its config
@@ -515,8 +607,6 @@ class RaySensor:
             for i in hit:
                 mask &= ~(1 << i)
         self.body_mask = mask
-        rb = abi.LsimRaycastBodies()
-        rb.rc = rc
         rb.dof_state = env.dof_state.data_ptr()
         rb.robots = self._robots_dev.data_ptr()
         rb.robots_host = ctypes.addressof(self._robots_host)
@@ -527,10 +617,8 @@ class RaySensor:
         rb.body_mask = mask
         rb.flags = abi.RAYCAST_FRAME_YAW if self.frame == "yaw" else 0
         if labels:
-            R = self.num_rays
-            self._labels = torch.zeros((int(env.num_envs), (R + 3) // 4 * 4), dtype=torch.uint8, device=dev)
-            rb.labels, rb.label_stride = self._labels.data_ptr(), self._labels.shape[1]
-        self._rb = rb
+            self.label_rows = self._zeros(int(env.num_envs), (self.num_rays + 3) // 4 * 4, dtype=torch.uint8)
+            rb.labels, rb.label_stride = self.label_rows.data_ptr(), self.label_rows.shape[1]
 
     def _per_env(self, pose, width, dev):
         N = int(self.env.num_envs)
@@ -553,58 +641,47 @@ class RaySensor:
     def _stream(self, stream):
         if stream is not None:
             return stream
-        return self.env._stream() if self._out.is_cuda else None
+        return self.env._stream() if self.out_rows.is_cuda else None
 
     def update(self, stream=None, tick=None, flags=0):
-        """one launch on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor.  With a model: the
-        envs due on `tick` (default: the env's common_step_counter), `flags` = 0 or one of LSIM_SENSOR_FILL_ALL / LSIM_SENSOR_RESETS_ONLY"""
+        """the chain's launches on `stream` (default: the current one), no host synchronisation; returns the live [N, R] tensor.  With a
+        model: the envs due on `tick` (default: the env's common_step_counter), `flags` = 0 or one of LSIM_SENSOR_FILL_ALL /
+        LSIM_SENSOR_RESETS_ONLY, the same for every stage; without one both are ignored"""
         if self.model is not None:
-            self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
-            self._sm.tick, self._sm.flags = self.tick, int(flags)
-            if self._od is not None:            # the pose the map will be given: the step every env took since the last update
-                self._launch_odometry(self.tick, int(flags), stream)
-            if self._mj is not None:            # first: the envs that start an episode are rendered, history and all, from their new pose
-                self._mj.tick, self._mj.flags = self.tick, int(flags)
-                lib.check(self._api.lsim_sensor_mount_jitter(ctypes.byref(self._mj), self._stream(stream)), what="lsim_sensor_mount_jitter")
-            if self._si is not None:            # then the instrument of those envs, and the capture that reads the rows
-                self._si.tick, self._si.flags = self.tick, int(flags)
-                lib.check(self._api.lsim_sensor_instrument(ctypes.byref(self._si), self._stream(stream)), what="lsim_sensor_instrument")
-                lib.check(self._api.lsim_sensor_capture_inst(ctypes.byref(self._sm), self._inst.data_ptr(), self._stream(stream)), what="lsim_sensor_capture_inst")
-            else:
-                lib.check(self._api.lsim_sensor_capture(ctypes.byref(self._sm), self._stream(stream)), what="lsim_sensor_capture")
-            if self._em is not None:            # directly behind the capture: the rows it just wrote, its due set
-                self._launch_map(self.tick, int(flags), stream)
-            if self._encoder is not None:       # the envs just captured, and no others: same stream, tick and flags
-                self._encoder.encode_device(self, self.tick, int(flags), stream)
-                if self._memory is not None:    # every env, every update: z is held between captures, the memory still ticks
-                    self._memory.step_device(self, int(flags), stream)
-            return self.out
-        if self._bodies:
-            lib.check(self._api.lsim_raycast_bodies(ctypes.byref(self._rb), self._stream(stream)), what="lsim_raycast_bodies")
-        else:
-            lib.check(self._api.lsim_raycast(ctypes.byref(self._rc), self._stream(stream)), what="lsim_raycast")
+            tick = self.tick = int(getattr(self.env, "common_step_counter", 0)) if tick is None else int(tick)
+        tick, flags = tick or 0, int(flags)
+        for s in self._chain:
+            s.launch(tick, flags, stream)
         return self.out
 
     def refresh(self, stream=None, tick=None):
         """capture every env now and fill its whole history with that capture (a model only)"""
         if self.model is None:
             raise ValueError("the sensor was created without a model")
-        return self.update(stream, tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+        return self.update(stream, tick, _FILL_ALL)
+
+    def history(self):
+        """live raw [N, latency + frames, stride] tensor: the frame history as the capture keeps it, padded rows and all (a model only)"""
+        if self.model is None:
+            raise ValueError("the sensor was created without a model")
+        return self._stages["capture"].buffers["hist"]
 
     def frames(self):
         """live [N, frames, R] view of the history: what the model reports, oldest first; the last one is `latency` captures old"""
-        if self.model is None:
-            raise ValueError("the sensor was created without a model")
-        return self._hist[:, :self.model.frames, :self.num_rays]
+        return self.history()[:, :self.model.frames, :self.num_rays]
 
     def attach_encoder(self, enc):
         """from now on every update() / refresh() is followed by `enc`'s launch (learn.depth_encoder.DepthEncoder.encode_device) on the same
-        stream with the same tick and flags; encodes every env once now, from the present history, when the sensor has captured before"""
+        stream with the same tick and flags; encodes every env once now, from the present history, when the sensor has captured before.
+        None: detach, the latent and an attached memory with it"""
+        if enc is None:
+            return self._drop("encoder")
         if self.model is None:
             raise ValueError("attach_encoder: the sensor was created without a model, so it has no frame history to encode")
-        self._encoder = enc
+        buffers, self._spare = self._kept("encoder", lambda: self._spare), {}       # the latent of an encoder launched by hand, if any
+        stage = self._attach(Stage(self, "encoder", "lsim_depth_encode", None, buffers, enc, run=lambda tick, flags, stream: enc.encode_device(self, tick, flags, stream)))
         if self.tick >= 0:
-            enc.encode_device(self, self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+            stage.launch(self.tick, _FILL_ALL)
         return enc
 
     def attach_map(self, m, odometry=None):
@@ -620,26 +697,22 @@ class RaySensor:
         a clamped one and never a point (so a hit beyond clip_hi is dropped, not inserted at clip_hi).
         Refused (ElevationMap's docstring): frame="yaw", see_robot without labels, a drop_value inside the clip range."""
         if m is None:
-            self.map = self._em = self._map = None
-            self.odometry = self._od = self._odo = None
-            self.map_channels = self._mr = self._rows = None
-            return None
+            return self._drop("map")
         if not isinstance(m, ElevationMap):
             raise TypeError(f"attach_map: expected an ElevationMap or None, got {type(m).__name__}")
         if odometry is not None and not isinstance(odometry, OdometryError):
             raise TypeError(f"attach_map: odometry is an OdometryError or None, got {type(odometry).__name__}")
-        if odometry is not None and not hasattr(self._api, "lsim_odometry_step"):
-            raise lib.LsimError("the loaded library has no lsim_odometry_step: rebuild it (there is no torch fall-back for the odometry)")
+        if odometry is not None:
+            lib.entry(self._api, "lsim_odometry_step", "the odometry")
         if self.model is None:
             raise ValueError("attach_map needs a model (SensorModel): the tick, the period and the episode lengths that say who captured are the model's")
-        if not hasattr(self._api, "lsim_elevation_map"):
-            raise lib.LsimError("the loaded library has no lsim_elevation_map: rebuild it (there is no torch fall-back for the elevation map)")
+        lib.entry(self._api, "lsim_elevation_map", "the elevation map")
         if self.frame != "base":
             raise ValueError(f"attach_map: the sensor's frame is {self.frame!r}; lsim_elevation_map places the points with the base's full orientation, "
                              "so only a frame='base' sensor can feed a map")
-        if self.see_robot and self._labels is None:
+        if self.see_robot and self.label_rows is None:
             raise ValueError("attach_map: a see_robot sensor needs labels=True, or the robot's own legs are inserted as ground")
-        env, dev, N, G = self.env, self._out.device, int(self.env.num_envs), m.size
+        env, N, G = self.env, int(self.env.num_envs), m.size
         if m.points is None:
             t = env.cfg.terrain
             pts = [[float(x), float(y)] for x in t.measured_points_x for y in t.measured_points_y]
@@ -648,32 +721,32 @@ class RaySensor:
         if not 1 <= len(pts) <= abi.DEFINES["LSIM_ELEVATION_MAP_MAX_POINTS"]:
             raise ValueError(f"attach_map: 1 to {abi.DEFINES['LSIM_ELEVATION_MAP_MAX_POINTS']} scan points, got {len(pts)}")
         P = len(pts)
-        mp = {"pts": torch.tensor(pts, dtype=torch.float32, device=dev).reshape(P, 2).contiguous(),
-              "height": torch.zeros((N, G, G), dtype=torch.float32, device=dev), "stamp": torch.full((N, G, G), -1, dtype=torch.int32, device=dev),
-              "cell": torch.zeros((N, G, G), dtype=torch.int32, device=dev), "scan": torch.zeros((N, P), dtype=torch.float32, device=dev),
-              "known": torch.zeros((N, P), dtype=torch.uint8, device=dev), "state": torch.zeros(1, dtype=torch.int64, device=dev),
-              "inv_scale": None if self.scale is None else (1.0 / self.scale).contiguous()}
+        mp = {"pts": torch.tensor(pts, dtype=torch.float32, device=self.out_rows.device).reshape(P, 2).contiguous(),
+              "height": self._zeros(N, G, G), "stamp": self._zeros(N, G, G, dtype=torch.int32).fill_(-1), "cell": self._zeros(N, G, G, dtype=torch.int32),
+              "scan": self._zeros(N, P), "known": self._zeros(N, P, dtype=torch.uint8), "state": self._zeros(1, dtype=torch.int64)}
         em = abi.LsimElevationMap()
         em.root_states, em.assumed_mount, em.dirs = env.root_states.data_ptr(), self.mount_nominal.data_ptr(), self.dirs.data_ptr()
-        em.inv_scale = None if mp["inv_scale"] is None else mp["inv_scale"].data_ptr()
-        sm, stride = self._sm, self._out.shape[1]
+        widest = narrowest = 1.0
+        if self.scale is not None:
+            inv = mp["inv_scale"] = (1.0 / self.scale).contiguous()
+            em.inv_scale, widest, narrowest = inv.data_ptr(), float(inv.max()), float(inv.min())
+        sm, stride = self._stages["capture"].struct, self.out_rows.shape[1]
         if m.source == "clean":
-            em.depth, em.depth_stride, em.a, em.b = self._out.data_ptr(), stride, 1.0, 0.0
+            em.depth, em.depth_stride, em.a, em.b = self.out_rows.data_ptr(), stride, 1.0, 0.0
         else:
             K = self.model.latency + self.model.frames
-            em.depth, em.depth_stride = self._hist.data_ptr() + (K - 1) * stride * 4, K * stride
+            em.depth, em.depth_stride = self.history().data_ptr() + (K - 1) * stride * 4, K * stride
             em.a, em.b = 1.0 / float(sm.gain), float(sm.offset)
-        if self._labels is not None:
-            em.labels, em.label_stride = self._labels.data_ptr(), self._labels.shape[1]
-        em.episode_length, em.pts = sm.episode_length, mp["pts"].data_ptr()
+        if self.label_rows is not None:
+            em.labels, em.label_stride = self.label_rows.data_ptr(), self.label_rows.shape[1]
+        em.pts = mp["pts"].data_ptr()
         em.height, em.stamp, em.cell = mp["height"].data_ptr(), mp["stamp"].data_ptr(), mp["cell"].data_ptr()
         em.scan, em.known, em.state = mp["scan"].data_ptr(), mp["known"].data_ptr(), mp["state"].data_ptr()
-        em.num_envs, em.num_rays, em.env_stride, em.num_points, em.scan_stride, em.known_stride, em.size = N, self.num_rays, self.env_stride, P, P, P, G
+        em.num_rays, em.num_points, em.scan_stride, em.known_stride, em.size = self.num_rays, P, P, P, G
         em.period, em.stagger = sm.period, sm.stagger
         em.res = m.resolution
         # the window of ranges t = d * inv_scale[r] that are points.  d_lo, d_hi bound the stored value d; a ray's t then lies strictly
         # inside for EVERY ray when t_lo = d_lo * max(inv_scale) and t_hi = d_hi * min(inv_scale)
-        widest, narrowest = (1.0, 1.0) if mp["inv_scale"] is None else (float(mp["inv_scale"].max()), float(mp["inv_scale"].min()))
         d_lo, d_hi = self.near, float("inf")
         if m.source == "noisy":
             # the model clamps every value -- misses, hits beyond the range and dropped pixels alike -- to [clip_lo, clip_hi], and "noisy"
@@ -691,49 +764,33 @@ class RaySensor:
         em.unknown_drop = float(env.cfg.rewards.base_height_target) if m.unknown_drop is None else m.unknown_drop
         if not em.t_lo < em.t_hi:
             raise ValueError(f"attach_map: no range is left between the nearest the sensor reports ({em.t_lo}) and max_range / the clip limit ({em.t_hi})")
-        self.odometry = self._od = self._odo = None
-        self.map_channels = self._mr = self._rows = None          # a new map: the rows of the old one go with it
+        self._drop("map")                   # a new map: the odometry and the rows of the old one go with it
+        launches = []
         if odometry is not None:
             od = abi.LsimOdometry()
-            self._odo = {"est": env.root_states.detach().clone().contiguous(), "odo": torch.zeros((N, 12), dtype=torch.float32, device=dev)}
-            od.root_states, od.est, od.odo, od.episode_length = env.root_states.data_ptr(), self._odo["est"].data_ptr(), self._odo["odo"].data_ptr(), sm.episode_length
-            od.seed, od.rank, od.stream_id, od.num_envs, od.env_stride = sm.seed, sm.rank, sm.stream_id, N, self.env_stride
+            held = {"est": env.root_states.detach().clone().contiguous(), "odo": self._zeros(N, 12)}
+            od.root_states, od.est, od.odo = env.root_states.data_ptr(), held["est"].data_ptr(), held["odo"].data_ptr()
             od.scale_range, od.yaw_range, od.z_range, od.pos_noise, od.yaw_noise, od.z_noise = odometry.ranges()
-            em.root_states = self._odo["est"].data_ptr()
-            self.odometry, self._od = odometry, od
-        self.map, self._em, self._map = m, em, mp
+            em.root_states = od.est
+            launches.append(self._attach(Stage(self, "odometry", "lsim_odometry_step", od, held, odometry)))
+        launches.append(self._attach(Stage(self, "map", "lsim_elevation_map", em, mp, m)))
         if self.tick >= 0:
-            if self._od is not None:
-                self._launch_odometry(self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], None)
-            self._launch_map(self.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], None)
+            for s in launches:
+                s.launch(self.tick, _FILL_ALL)
         return m
-
-    def _launch_odometry(self, tick, flags, stream):
-        self._od.tick, self._od.flags = int(tick), int(flags)
-        lib.check(self._api.lsim_odometry_step(ctypes.byref(self._od), self._stream(stream)), what="lsim_odometry_step")
-
-    def _launch_map(self, tick, flags, stream):
-        self._em.tick, self._em.flags = int(tick), int(flags)
-        lib.check(self._api.lsim_elevation_map(ctypes.byref(self._em), self._stream(stream)), what="lsim_elevation_map")
-        if self._mr is not None:            # the scan rows just rewritten, every visited env
-            lib.check(self._api.lsim_map_rows(ctypes.byref(self._mr), self._stream(stream)), what="lsim_map_rows")
 
     def map_pose(self):
         """live [N, 13] tensor: the pose the map is given -- odometry_pose() with odometry, else the env's root_states"""
-        self._need_map()
-        return self._odo["est"] if self._odo is not None else self.env.root_states
+        self._need("map")
+        return self._stages["odometry"].buffers["est"] if "odometry" in self._stages else self.env.root_states
 
     def odometry_pose(self):
         """live [N, 13] tensor: the estimated root states (attach_map(m, odometry=...)); columns 7.. are root_states' own"""
-        if self._odo is None:
-            raise ValueError("the sensor has no odometry (attach_map(m, odometry=OdometryError(...)))")
-        return self._odo["est"]
+        return self._need("odometry").buffers["est"]
 
     def odometry_state(self):
         """live [N, 12] tensor: row e = {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0} of env e (lsim.h)"""
-        if self._odo is None:
-            raise ValueError("the sensor has no odometry (attach_map(m, odometry=OdometryError(...)))")
-        return self._odo["odo"]
+        return self._need("odometry").buffers["odo"]
 
     def attach_map_rows(self, channels=("height",)):
         """from now on the map's launch of every update() / refresh() is followed by lsim_map_rows on the same stream: `map_rows()` is the
@@ -741,60 +798,50 @@ class RaySensor:
         obs_scales.height_measurements, the privileged height scan's expression; ("height", "known"): then map_known() as 0 / 1.  Needs
         an attached map; builds the rows once now when the sensor has captured before.  None: detach and free."""
         if channels is None:
-            self.map_channels = self._mr = self._rows = None
-            return None
+            return self._drop("map_rows")
         channels = tuple(channels)
         if channels not in (("height",), ("height", "known")):
             raise ValueError(f"attach_map_rows: channels is ('height',) or ('height', 'known'), got {channels}")
-        mp = self._need_map()
-        if not hasattr(self._api, "lsim_map_rows"):
-            raise lib.LsimError("the loaded library has no lsim_map_rows: rebuild it (there is no torch fall-back for the map rows)")
-        N, P, C = int(self.env.num_envs), int(self._em.num_points), len(channels)
-        self._rows = torch.zeros((N, C * P), dtype=torch.float32, device=self._out.device)
+        em, mp = self._need("map").struct, self._need("map").buffers
+        lib.entry(self._api, "lsim_map_rows", "the map rows")
+        P, C = int(em.num_points), len(channels)
+        rows = self._zeros(int(self.env.num_envs), C * P)
         mr = abi.LsimMapRows()
-        mr.scan, mr.known, mr.pose, mr.rows = mp["scan"].data_ptr(), mp["known"].data_ptr(), self.map_pose().data_ptr(), self._rows.data_ptr()
-        mr.num_points, mr.channels, mr.scan_stride, mr.known_stride, mr.ld = P, C, int(self._em.scan_stride), int(self._em.known_stride), C * P
-        mr.num_envs, mr.env_stride = N, self.env_stride
+        mr.scan, mr.known, mr.pose, mr.rows = mp["scan"].data_ptr(), mp["known"].data_ptr(), self.map_pose().data_ptr(), rows.data_ptr()
+        mr.num_points, mr.channels, mr.scan_stride, mr.known_stride, mr.ld = P, C, int(em.scan_stride), int(em.known_stride), C * P
         mr.z_offset, mr.scale = 0.5, float(self.env.lcfg.obs_scale_height)
-        self.map_channels, self._mr = channels, mr
+        stage = self._attach(Stage(self, "map_rows", "lsim_map_rows", mr, {"rows": rows}, channels))
         if self.tick >= 0:
-            lib.check(self._api.lsim_map_rows(ctypes.byref(mr), self._stream(None)), what="lsim_map_rows")
-        return self._rows
+            stage.launch(self.tick, _FILL_ALL)
+        return rows
 
     def map_rows(self):
         """live [N, channels * P] tensor: the rows lsim_map_rows writes (attach_map_rows)"""
-        if self._rows is None:
-            raise ValueError("the sensor has no map rows (attach_map_rows)")
-        return self._rows
-
-    def _need_map(self):
-        if self._em is None:
-            raise ValueError("the sensor has no elevation map (attach_map)")
-        return self._map
+        return self._need("map_rows").buffers["rows"]
 
     def map_scan(self):
         """live [N, P] tensor: the map's height at every scan point; where it knows none, the base height minus unknown_drop"""
-        return self._need_map()["scan"]
+        return self._need("map").buffers["scan"]
 
     def map_known(self):
         """live uint8 [N, P] tensor: 1 where map_scan() is a height the map holds"""
-        return self._need_map()["known"]
+        return self._need("map").buffers["known"]
 
     def map_state(self):
         """the live raw arrays (height f32, stamp i32, cell: the u32 words held in an int32 tensor), each [N, G, G], toroidal (lsim.h)"""
-        mp = self._need_map()
+        mp = self._need("map").buffers
         return mp["height"], mp["stamp"], mp["cell"]
 
     @property
     def map_nonfinite(self):
         """0-d device tensor: visits of envs whose pose was not finite (they insert nothing and scan zeros); must stay 0"""
-        return self._need_map()["state"][0]
+        return self._need("map").buffers["state"][0]
 
     def map_heights(self):
         """[N, G, G] COPY in window order -- [e, i, j] is the cell (cx - G/2 + i, cy - G/2 + j) around env e's present position (the one the
         map was given: the estimate with odometry) -- with NaN
         where the map knows nothing.  For people and tools (tools/sensor_frames.py); nothing on a hot path reads it."""
-        mp, G, N = self._need_map(), self.map.size, int(self.env.num_envs)
+        mp, G, N = self._need("map").buffers, self.map.size, int(self.env.num_envs)
         rinv = float(np.float32(1.0 / float(np.float32(self.map.resolution))))
         c = torch.floor(self.map_pose()[:, :2] * rinv).to(torch.int64).clamp(-40000, 40000)          # the window of the pose the map was given
         off = torch.arange(G, device=c.device) - G // 2
@@ -809,48 +856,52 @@ class RaySensor:
     def attach_memory(self, mem):
         """from now on the encoder's launch of every update() / refresh() is followed by `mem`'s (learn.depth_memory.DepthMemory.step_device)
         on the same stream with the same flags; steps every env once now from h = 0 (LSIM_SENSOR_FILL_ALL).  Needs an attached encoder.
-        The hidden state h [N, H] and the rows [N, L + H] are this sensor's, like its latent: one `mem` may serve several sensors."""
-        if self._encoder is None:
+        The hidden state h [N, H] and the rows [N, L + H] are this sensor's, like its latent: one `mem` may serve several sensors.
+        None: detach and free."""
+        if mem is None:
+            return self._drop("memory")
+        if self.encoder is None:
             raise ValueError("attach_memory: the sensor has no encoder (attach_encoder first): the memory reads its latent rows")
-        self._latent_buffer(self._encoder.latent_dim)
+        self.latent_buffer(self.encoder.latent_dim)
         N, widths = int(self.env.num_envs), (mem.hidden, mem.latent_dim + mem.hidden)
-        if self._memory_h is None or (self._memory_h.shape[1], self._memory_rows.shape[1]) != widths:
-            self._memory_h, self._memory_rows = (torch.zeros((N, w), dtype=torch.float32, device=self._out.device) for w in widths)
-        self._memory = mem
-        mem.step_device(self, abi.DEFINES["LSIM_SENSOR_FILL_ALL"])
+        buffers = self._kept("memory", dict)
+        if [t.shape[1] for t in buffers.values()] != list(widths):
+            buffers = {"h": self._zeros(N, widths[0]), "rows": self._zeros(N, widths[1])}
+        stage = self._attach(Stage(self, "memory", "lsim_depth_memory_step", None, buffers, mem, run=lambda tick, flags, stream: mem.step_device(self, flags, stream)))
+        stage.launch(self.tick, _FILL_ALL)
         return mem
 
     def memory_rows(self):
         """live [N, L + H] tensor: row e = [latent of env e | its memory's hidden state] (attach_memory)"""
-        if self._memory is None:
-            raise ValueError("the sensor has no memory (attach_memory)")
-        return self._memory_rows
+        return self._need("memory").buffers["rows"]
 
     def memory_state(self):
         """live [N, H] tensor: the hidden state of every env's memory (attach_memory)"""
-        if self._memory is None:
-            raise ValueError("the sensor has no memory (attach_memory)")
-        return self._memory_h
+        return self._need("memory").buffers["h"]
 
-    def _latent_buffer(self, latent_dim):
+    def _latent_held(self):
+        """where the latent lives: the encoder stage's buffers, or the sensor's spare ones for an encoder launched by hand"""
+        return self._stages["encoder"].buffers if "encoder" in self._stages else self._spare
+
+    def latent_buffer(self, latent_dim):
         """the [N, stride] buffer an encoder's launch writes; created on first use"""
-        stride = (int(latent_dim) + 3) // 4 * 4
-        if self._latent is None or self._latent.shape[1] != stride:
-            self._latent = torch.zeros((int(self.env.num_envs), stride), dtype=torch.float32, device=self._out.device)
+        held, stride = self._latent_held(), (int(latent_dim) + 3) // 4 * 4
+        if "latent" not in held or held["latent"].shape[1] != stride:
+            held["latent"] = self._zeros(int(self.env.num_envs), stride)
         self._latent_dim = int(latent_dim)
-        return self._latent
+        return held["latent"]
 
     def latent(self):
         """live [N, latent_dim] tensor: row e is the encoding of env e's frames at its last capture (attach_encoder)"""
-        if self._latent is None:
-            raise ValueError("the sensor has no encoder (attach_encoder)")
-        return self._latent[:, :self._latent_dim]
+        if "latent" not in self._latent_held():
+            raise ValueError(f"the sensor has no {_ABSENT['encoder']}")
+        return self._latent_held()["latent"][:, :self._latent_dim]
 
     def labels(self):
         """live uint8 [N, R] tensor of the latest launch (labels=True): 0 nothing within [near, far], 1 terrain, 2 + b body b (`body_names[b]`)"""
-        if self._labels is None:
+        if self.label_rows is None:
             raise ValueError("the sensor was created without labels=True")
-        return self._labels[:, :self.num_rays]
+        return self.label_rows[:, :self.num_rays]
 
     def spec(self):
         """What rebuilds this sensor on another env (from_spec), as a dict of plain Python values and lists -- a checkpoint's record of the
@@ -860,14 +911,10 @@ class RaySensor:
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
         one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's and
         "odometry" the OdometryError the map was attached with, each absent without one."""
-        out = {"kind": "rays"}
-        if hasattr(self, "width") and hasattr(self, "height"):
-            out.update(kind="camera", width=int(self.width), height=int(self.height))
-        elif hasattr(self, "channels") and hasattr(self, "points_per_rev"):
-            out.update(kind="lidar", channels=int(self.channels), points_per_rev=int(self.points_per_rev))
+        out = dict(self.kind)
         out["dirs"] = self.dirs.cpu().tolist()
         out["scale"] = None if self.scale is None else self.scale.cpu().tolist()
-        out.update(near=self.near, far=self.far, env_stride=self.env_stride, see_robot=self.see_robot, labels=self._labels is not None, frame=self.frame)
+        out.update(near=self.near, far=self.far, env_stride=self.env_stride, see_robot=self.see_robot, labels=self.label_rows is not None, frame=self.frame)
         mask = self.body_mask if self.see_robot else None
         out["ignore_bodies"] = [] if mask is None else [n for i, n in enumerate(self.body_names) if not mask >> i & 1]
         out["model"] = None if self.model is None else self.model.record()
@@ -893,10 +940,13 @@ class RaySensor:
 
 
 class DepthCamera(RaySensor):
-    def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None, **bodies):
-        dirs, scale = pinhole_dirs(width, height, hfov_deg)
-        self.width, self.height = int(width), int(height)
-        super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg), near, far, scale=scale, env_stride=env_stride, api=api, **bodies)
+    """`rays` = (dirs, scale) and `mount_quat`: a recorded camera's own (from_spec), in place of the pinhole's of `hfov_deg` and `pitch_deg`"""
+
+    def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
+                 rays=None, mount_quat=None, **options):
+        dirs, scale = pinhole_dirs(width, height, hfov_deg) if rays is None else rays
+        super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg) if mount_quat is None else mount_quat, near, far, scale=scale,
+                         env_stride=env_stride, api=api, kind={"kind": "camera", "width": width, "height": height}, **options)
 
     def image(self):
         """[N, H, W] view of the output: z-depth along the optical axis in metres, far * cos where nothing is hit"""
@@ -911,23 +961,22 @@ class DepthCamera(RaySensor):
         return self.frames().unflatten(2, (self.height, self.width))
 
 
-def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
-    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and the last seven keywords as RaySensor's"""
-    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api,
-                       see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter,
-                       instrument=instrument)
+def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None, **options):
+    """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and `options` (see_robot, ignore_bodies,
+    labels, frame, model, mount_jitter, instrument) as RaySensor's"""
+    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api, **options)
 
 
 def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
-          see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None):
+          **options):
     """a spinning lidar: `channels` rings over the vertical field of view `vfov_deg` (a width centred on the horizon, or (low, high) degrees),
-    `points_per_rev` azimuths each; reports range (scale=None); the last seven keywords as RaySensor's"""
-    s = RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
-                  see_robot=see_robot, ignore_bodies=ignore_bodies, labels=labels, frame=frame, model=model, mount_jitter=mount_jitter,
-                  instrument=instrument)
-    s.channels, s.points_per_rev = int(channels), int(points_per_rev)
-    return s
+    `points_per_rev` azimuths each; reports range (scale=None); `options` (see_robot, ignore_bodies, labels, frame, model, mount_jitter,
+    instrument) as RaySensor's"""
+    return RaySensor(env, ring_dirs(channels, vfov_deg, points_per_rev), mount_pos, mount_quat, near, far, scale=None, env_stride=env_stride, api=api,
+                     kind={"kind": "lidar", "channels": channels, "points_per_rev": points_per_rev}, **options)
+
+
+_KIND_KEYS = {"rays": (), "camera": ("width", "height"), "lidar": ("channels", "points_per_rev")}
 
 
 def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec"):
@@ -958,17 +1007,15 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     model = option("model", "spec", SensorModel, "model")
     mount_jitter, instrument = option("mount_jitter", mount_jitter, MountJitter, "mount_jitter"), option("instrument", instrument, InstrumentError, "instrument")
     elevation_map, odometry = option("elevation_map", elevation_map, ElevationMap, "map"), option("odometry", odometry, OdometryError, "odometry")
-    kind = spec.get("kind", "rays")
-    cls = DepthCamera if kind == "camera" else RaySensor
-    sensor = cls.__new__(cls)               # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
-    if kind == "camera":
-        sensor.width, sensor.height = int(spec["width"]), int(spec["height"])
-    RaySensor.__init__(sensor, env, np.asarray(spec["dirs"], dtype=np.float32), pos, quat, spec["near"], spec["far"],
-                       scale=None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32), env_stride=spec["env_stride"], api=api,
-                       see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"], frame=spec["frame"], model=model,
-                       mount_jitter=mount_jitter, instrument=instrument)
-    if kind == "lidar":
-        sensor.channels, sensor.points_per_rev = int(spec["channels"]), int(spec["points_per_rev"])
+    kind = spec.get("kind", "rays") if spec.get("kind") in _KIND_KEYS else "rays"
+    dirs, scale = np.asarray(spec["dirs"], dtype=np.float32), None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32)
+    options = dict(env_stride=spec["env_stride"], api=api, see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"],
+                   frame=spec["frame"], model=model, mount_jitter=mount_jitter, instrument=instrument)
+    if kind == "camera":                    # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
+        sensor = DepthCamera(env, spec["width"], spec["height"], None, pos, near=spec["near"], far=spec["far"], rays=(dirs, scale), mount_quat=quat, **options)
+    else:
+        sensor = RaySensor(env, dirs, pos, quat, spec["near"], spec["far"], scale=scale, kind={"kind": kind, **{k: spec[k] for k in _KIND_KEYS[kind]}}, **options)
     if elevation_map is not None:
         sensor.attach_map(elevation_map, odometry=odometry)
     return sensor
+

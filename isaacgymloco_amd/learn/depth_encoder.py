@@ -158,14 +158,12 @@ class DepthEncoder(nn.Module):
         if sensor.num_rays != self.height * self.width or model.frames != self.frames:
             raise ValueError(f"encode_device: the encoder expects {self.frames} frames of {self.height} x {self.width} rays, the sensor has "
                              f"{model.frames} of {sensor.num_rays}")
-        entry = getattr(sensor._api, "lsim_depth_encode", None)
-        if entry is None:
-            raise lib.LsimError("the loaded library has no lsim_depth_encode: rebuild it (there is no torch fall-back for the depth encoder)")
-        hist = sensor._hist
+        entry = lib.entry(sensor._api, "lsim_depth_encode", "the depth encoder")
+        hist = sensor.history()
         params = self.device_params()
         check_params("encode_device", _PARAM_NAMES, params, hist.device)
-        latent = sensor._latent_buffer(self.latent_dim)
-        de = _launch_struct(self, hist.data_ptr(), hist.shape[2], hist.shape[1], sensor._sm.episode_length, hist.shape[0], sensor.env_stride,
+        latent = sensor.latent_buffer(self.latent_dim)
+        de = _launch_struct(self, hist.data_ptr(), hist.shape[2], hist.shape[1], sensor.episode_length_ptr, hist.shape[0], sensor.env_stride,
                             latent, params, tick, model.period, model.stagger, flags)
         lib.check(entry(ctypes.byref(de), sensor._stream(stream)), what="lsim_depth_encode")
         return latent[:, :self.latent_dim]
@@ -177,8 +175,7 @@ class DepthEncoder(nn.Module):
         through a padded copy.  The frames are sensor data: there is no gradient with respect to them, and frames that ask for one raise."""
         api = api if api is not None else lib.load()
         for name in ("lsim_depth_encode", "lsim_depth_encode_backward_sizes", "lsim_depth_encode_backward"):
-            if getattr(api, name, None) is None:
-                raise lib.LsimError(f"the loaded library has no {name}: rebuild it (there is no torch fall-back for the depth encoder)")
+            lib.entry(api, name, "the depth encoder")
         if frames.requires_grad:
             raise ValueError("forward_device: frames.requires_grad is set, but the depth encoder has no gradient with respect to its frames")
         if frames.dim() != 4 or tuple(frames.shape[1:]) != (self.frames, self.height, self.width) or frames.shape[0] < 1:

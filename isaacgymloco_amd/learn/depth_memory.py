@@ -30,10 +30,7 @@ _ENTRIES = ("lsim_depth_memory_step", "lsim_gru_sequence_forward", "lsim_gru_seq
 
 
 def _entry(api, name):
-    fn = getattr(api, name, None)
-    if fn is None:
-        raise lib.LsimError(f"the loaded library has no {name}: rebuild it (there is no torch fall-back for the depth memory)")
-    return fn
+    return lib.entry(api, name, "the depth memory")
 
 
 def _stream_of(t):
@@ -162,13 +159,15 @@ class DepthMemory(nn.Module):
         proprio_dim columns of the env's obs_buf, freshness from the env's episode_length, h and the rows [N, L + H] the sensor's own
         (RaySensor.attach_memory).  Returns the live rows."""
         entry = _entry(sensor._api, "lsim_depth_memory_step")
-        if getattr(sensor, "_latent", None) is None:
-            raise ValueError("step_device: the sensor has no encoder (attach_encoder), so no latent rows")
-        z = sensor.latent()
+        try:
+            z = sensor.latent()
+        except ValueError:
+            raise ValueError("step_device: the sensor has no encoder (attach_encoder), so no latent rows") from None
         if z.shape[1] != self.latent_dim:
             raise ValueError(f"step_device: the memory reads {self.latent_dim} latent columns, the sensor's encoder writes {z.shape[1]}")
         check_params("step_device", _PARAM_NAMES, self.device_params(), z.device)
-        h, rows = getattr(sensor, "_memory_h", None), getattr(sensor, "_memory_rows", None)
+        held = sensor.stage("memory").buffers if sensor.stage("memory") is not None else {}
+        h, rows = held.get("h"), held.get("rows")
         if h is None or h.shape[1] != self.hidden or rows.shape[1] != self.latent_dim + self.hidden:
             raise ValueError(f"step_device: the sensor holds no memory buffers of this cell's widths ({self.latent_dim} latent columns, "
                              f"{self.hidden} hidden): attach the memory to it (RaySensor.attach_memory)")
@@ -179,7 +178,7 @@ class DepthMemory(nn.Module):
             if obs.dim() != 2 or obs.shape[1] < self.proprio_dim or obs.stride(1) != 1 or obs.dtype != torch.float32 or obs.device != z.device:
                 raise ValueError(f"step_device: the env's obs_buf must be fp32 [N, >= {self.proprio_dim}] on {z.device}")
             dm.p, dm.p_ld = obs.data_ptr(), obs.stride(0)
-        dm.episode_length = sensor._sm.episode_length
+        dm.episode_length = sensor.episode_length_ptr
         dm.weight_ih, dm.weight_hh, dm.bias_ih, dm.bias_hh = (p.data_ptr() for p in self.device_params())
         dm.h, dm.h_ld, dm.rows, dm.rows_ld = h.data_ptr(), h.stride(0), rows.data_ptr(), rows.stride(0)
         dm.num_envs, dm.latent_dim, dm.proprio_dim, dm.hidden, dm.flags = z.shape[0], self.latent_dim, self.proprio_dim, self.hidden, int(flags)

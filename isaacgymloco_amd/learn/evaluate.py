@@ -366,11 +366,11 @@ def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
                          f", the actor reads {ac.depth_latent_dim}")
     enc = enc.to(device).eval()
     head = head.to(device).eval() if head is not None else None
-    if getattr(cam, "_encoder", None) is not enc:
+    if getattr(cam, "encoder", None) is not enc:
         cam.attach_encoder(enc)
     if mem is not None:
         mem = mem.to(device).eval()
-        if getattr(cam, "_memory", None) is not mem:
+        if getattr(cam, "memory", None) is not mem:
             cam.attach_memory(mem)
         found["memory"], found["memory_head"] = mem, (mem_head.to(device).eval() if mem_head is not None else None)
     return cam, enc, head

@@ -80,6 +80,13 @@ class roctx_range:
         return False
 
 
+def entry(api, name, what):
+    """`api`'s entry point `name`; a library (or a CPU shim of the tests) without it raises: nothing falls back to torch for `what`"""
+    if not hasattr(api, name):
+        raise LsimError(f"the loaded library has no {name}: rebuild it (there is no torch fall-back for {what})")
+    return getattr(api, name)
+
+
 def check(rc, handle=None, what="lsim call"):
     if rc != 0:
         msg = ""

@@ -129,7 +129,7 @@ def test_attach_encoder_on_the_emulated_env():
     bare = env.add_sensor("bare", sensors.depth_camera(env, 6, 4, 87.0, model=sensors.SensorModel(period=2, frames=2), **kw))
     env.step_device(torch.zeros(4, 12))
     assert api.calls == {"lsim_raycast": 0, "lsim_raycast_bodies": 1, "lsim_sensor_capture": 2, "lsim_depth_encode": 0}
-    assert plain._latent is None and bare._latent is None and bare._encoder is None
+    assert plain.stage("encoder") is None and bare.stage("encoder") is None and bare.encoder is None
     with pytest.raises(ValueError):
         bare.latent()
 

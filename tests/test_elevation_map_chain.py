@@ -73,7 +73,7 @@ def test_the_map_launches_right_behind_the_capture_once_per_update_for_the_captu
         scan_b, tick = cam.map_scan().clone(), env.common_step_counter
         env.step_device(torch.randn(N, 12, generator=g) * 0.3)
         due = SR.due_sets(N, 1, tick, 3, 1, 0, env.episode_length_buf.numpy())[0]
-        assert cam.tick == tick and cam._em.tick == tick
+        assert cam.tick == tick and cam.stage("map").struct.tick == tick
         wrote = (cam.map_state()[1] == tick).any(dim=2).any(dim=1).numpy()
         np.testing.assert_array_equal(wrote, due, err_msg=f"step {step}")
         for now, was in zip(cam.map_state(), before):
@@ -93,13 +93,13 @@ def test_without_a_map_nothing_is_allocated_or_launched_and_the_spec_is_the_one_
     for _ in range(3):
         env.step_device(torch.zeros(8, 12))
     assert api.calls["lsim_elevation_map"] == 0 and api.calls["lsim_sensor_capture"] == 4
-    assert cam.map is None and cam._em is None and cam._map is None and list(cam.spec()) == SPEC_KEYS
+    assert cam.map is None and cam.stage("map") is None and list(cam.spec()) == SPEC_KEYS
     for getter in (cam.map_scan, cam.map_known, cam.map_heights, cam.map_state):
         with pytest.raises(ValueError, match="attach_map"):
             getter()
     m = cam.attach_map(sensors.ElevationMap(size=16))
     assert api.calls["lsim_elevation_map"] == 1 and cam.map is m, "a sensor that has captured inserts every env at once"
-    assert cam.attach_map(None) is None and cam._em is None and cam._map is None and list(cam.spec()) == SPEC_KEYS
+    assert cam.attach_map(None) is None and cam.stage("map") is None and list(cam.spec()) == SPEC_KEYS
     env.step_device(torch.zeros(8, 12))
     assert api.calls["lsim_elevation_map"] == 1
 
@@ -127,19 +127,19 @@ def test_values_refusals_and_the_struct_the_launch_gets():
     model = sensors.SensorModel(period=2, latency=1, frames=2, normalise=True)
     cam = _camera(env, api, model=model, see_robot=True, labels=True, mount_jitter=sensors.MountJitter(rot_deg=(0, 5, 0)))
     cam.attach_map(m)
-    em, stride = cam._em, cam._out.shape[1]
-    assert em.depth == cam._hist.data_ptr() + 2 * stride * 4 and em.depth_stride == 3 * stride
-    assert em.a == np.float32(1.0 / cam._sm.gain) and em.b == np.float32(cam._sm.offset) == np.float32((0.05 + FAR) / 2)
+    em, stride = cam.stage("map").struct, cam.out_rows.shape[1]
+    assert em.depth == cam.history().data_ptr() + 2 * stride * 4 and em.depth_stride == 3 * stride
+    assert em.a == np.float32(1.0 / cam.stage("capture").struct.gain) and em.b == np.float32(cam.stage("capture").struct.offset) == np.float32((0.05 + FAR) / 2)
     assert em.assumed_mount == cam.mount_nominal.data_ptr() != cam.mount.data_ptr()
-    assert em.labels == cam._labels.data_ptr() and em.label_stride == cam._labels.shape[1] and em.episode_length == cam._sm.episode_length
+    assert em.labels == cam.label_rows.data_ptr() and em.label_stride == cam.label_rows.shape[1] and em.episode_length == cam.stage("capture").struct.episode_length
     assert (em.period, em.stagger, em.size, em.num_points, em.num_rays) == (2, 0, 32, 187, 48) and em.t_hi == np.float32(0.98 * FAR)
     assert em.unknown_drop == np.float32(env.cfg.rewards.base_height_target) and em.t_lo >= np.float32(0.05 / float(cam.scale.min()))
     t = env.cfg.terrain
     want = [[x, y] for x in t.measured_points_x for y in t.measured_points_y]
-    np.testing.assert_array_equal(cam._map["pts"].numpy(), np.array(want, np.float32))
+    np.testing.assert_array_equal(cam.stage("map").buffers["pts"].numpy(), np.array(want, np.float32))
     cam.attach_map(sensors.ElevationMap(source="clean", points=[[0.0, 0.0], [0.5, 0.0]], unknown_drop=0.3, max_range=3.0))
-    em = cam._em
-    assert (em.depth, em.depth_stride, em.a, em.b, em.num_points, em.t_hi) == (cam._out.data_ptr(), stride, 1.0, 0.0, 2, 3.0)
+    em = cam.stage("map").struct
+    assert (em.depth, em.depth_stride, em.a, em.b, em.num_points, em.t_hi) == (cam.out_rows.data_ptr(), stride, 1.0, 0.0, 2, 3.0)
     assert em.unknown_drop == np.float32(0.3)
 
 
@@ -194,7 +194,7 @@ def test_on_a_plane_every_known_value_is_the_plane_and_coverage_grows_to_the_cam
     assert (np.diff(covered, axis=0) >= 0).all() and (covered[-1] > covered[0] + 40).all(), "the map remembers what the camera has passed over"
     # the lowest image row meets the ground 0.53 m ahead of the base (camera 0.5 m up, 65.4 degrees down, 0.3 m forward) and the image is
     # 1.3 m wide there: after 21 cells (1.31 m) forward every scan point from -0.7 m to 0.5 m, |y| <= 0.3 m, has been swept
-    pts = cam._map["pts"].numpy()
+    pts = cam.stage("map").buffers["pts"].numpy()
     inside = (pts[:, 0] >= -0.7 - 1e-6) & (pts[:, 0] <= 0.5 + 1e-6) & (np.abs(pts[:, 1]) <= 0.3 + 1e-6)
     assert inside.sum() == 13 * 7 and cam.map_known().numpy()[:, inside].all(), "coverage is 1 inside the camera's footprint"
     hts = cam.map_heights().numpy()
@@ -212,7 +212,7 @@ def test_a_clipping_model_with_dropout_and_misses_puts_no_phantom_point_into_a_n
     model = sensors.SensorModel(clip=(0.1, 3.0), normalise=True, dropout=0.3, latency=1, frames=2)
     cam = _camera(env, api, 32, 24, model=model)
     cam.attach_map(sensors.ElevationMap(size=64, resolution=0.125, source="noisy"))       # a window of +-4 m: 3 m out is inside it
-    em, inv = cam._em, 1.0 / cam.scale.numpy()
+    em, inv = cam.stage("map").struct, 1.0 / cam.scale.numpy()
     assert em.t_lo > np.float32(0.1 * inv.max()) and em.t_hi < np.float32(3.0 * inv.min()) and em.t_lo < em.t_hi
     poses = np.zeros((N, 7), np.float32)
     poses[:, 6], poses[:, 2] = 1.0, 0.45
@@ -220,7 +220,7 @@ def test_a_clipping_model_with_dropout_and_misses_puts_no_phantom_point_into_a_n
     for k in range(3):
         _drive(env, cam, poses, k)
         poses[:, 0] += np.float32(0.125)
-    newest = cam._hist[:, -1, :cam.num_rays].numpy() / np.float32(cam._sm.gain) + np.float32(cam._sm.offset)
+    newest = cam.history()[:, -1, :cam.num_rays].numpy() / np.float32(cam.stage("capture").struct.gain) + np.float32(cam.stage("capture").struct.offset)
     clean = cam.out.numpy()
     assert (np.abs(newest - 0.1) < 1e-6).mean() > 0.1, "the scene has dropped pixels"
     assert (clean > 4.9 * cam.scale.numpy()).mean() > 0.1 and ((clean > 3.0) & (clean < 4.9 * cam.scale.numpy())).any(), "and misses, and hits beyond 3 m"
@@ -242,7 +242,7 @@ def test_a_yaw_frame_sensor_and_a_see_robot_sensor_without_labels_are_refused():
     with pytest.raises(ValueError, match="labels"):
         _camera(env, api, see_robot=True).attach_map(sensors.ElevationMap())
     cam = _camera(env, api, see_robot=True, labels=True)
-    assert cam.attach_map(sensors.ElevationMap()) is cam.map and cam._em.labels == cam._labels.data_ptr()
+    assert cam.attach_map(sensors.ElevationMap()) is cam.map and cam.stage("map").struct.labels == cam.label_rows.data_ptr()
     assert api.calls["lsim_elevation_map"] == 0
 
 
@@ -281,13 +281,13 @@ def test_a_jittered_mount_with_the_nominal_one_assumed_bends_the_map_on_a_slope(
             p[:, 0] += np.float32(0.0625)
         p[:, 0] -= np.float32(0.0625)
         known = cam.map_known().numpy().astype(bool)
-        world = p[:, None, :2] + cam._map["pts"].numpy()[None]       # identity orientation: the base-yaw frame is the world's
+        world = p[:, None, :2] + cam.stage("map").buffers["pts"].numpy()[None]       # identity orientation: the base-yaw frame is the world's
         err = np.abs(cam.map_scan().numpy() - _truth(env, world))
         assert known.sum() > N * 60
         errs[name] = float(err[known].mean())
     slope = np.abs(np.diff(_truth(env, np.stack((poses[:, 0] + np.array([[0.0], [1.0]]), np.broadcast_to(poses[:, 1], (2, N))), axis=-1)), axis=0))
     assert slope.max() > 0.05, "the scene stands on a slope"
-    assert bool((bent.mount[:, 3:] != bent.mount_nominal[:, 3:]).any()) and bent._em.assumed_mount == bent.mount_nominal.data_ptr()
+    assert bool((bent.mount[:, 3:] != bent.mount_nominal[:, 3:]).any()) and bent.stage("map").struct.assumed_mount == bent.mount_nominal.data_ptr()
     print(f"mean |map - terrain| at the known scan points: nominal mount {errs['straight']:.4f} m, pitch error up to 5 degrees {errs['bent']:.4f} m")
     assert errs["bent"] > errs["straight"]
 
@@ -302,14 +302,14 @@ def test_spec_and_from_spec_carry_the_maps_record():
     import json
     assert json.loads(json.dumps(spec)) == spec
     back = sensors.from_spec(env, spec, api=api)
-    assert back.map == m and back.spec() == spec and back._em.size == 16 and back._em.res == 0.125 and back._em.num_points == 2
+    assert back.map == m and back.spec() == spec and back.stage("map").struct.size == 16 and back.stage("map").struct.res == 0.125 and back.stage("map").struct.num_points == 2
     assert sensors.from_spec(env, spec, api=api, elevation_map=None).map is None
     other = sensors.ElevationMap(size=64)
     assert sensors.from_spec(env, spec, api=api, elevation_map=other).map == other
     with pytest.raises(ValueError, match="elevation_map"):
         sensors.from_spec(env, spec, api=api, elevation_map="yes")
     default = sensors.from_spec(env, dict(spec, map=sensors.ElevationMap().record()), api=api)
-    assert default._em.num_points == 187 and default.map.points is None
+    assert default.stage("map").struct.num_points == 187 and default.map.points is None
 
 
 def _runner(env, cam):

@@ -37,7 +37,7 @@ def envelope_violations(env, cam):
     hs, res = float(t.horizontal_scale), cam.map.resolution
     grid = env.terrain.heightsamples.astype(np.float64) * t.vertical_scale
     rs = env.root_states[:, :7].cpu().numpy().astype(np.float64)
-    pts, scan, known = cam._map["pts"].cpu().numpy().astype(np.float64), cam.map_scan().cpu().numpy(), cam.map_known().cpu().numpy().astype(bool)
+    pts, scan, known = cam.stage("map").buffers["pts"].cpu().numpy().astype(np.float64), cam.map_scan().cpu().numpy(), cam.map_known().cpu().numpy().astype(bool)
     n = 1.0 / np.sqrt(rs[:, 5] ** 2 + rs[:, 6] ** 2)
     qy = np.stack((np.zeros(len(rs)), np.zeros(len(rs)), rs[:, 5] * n, rs[:, 6] * n), axis=1)
     w = rs[:, None, :2] + ER.rot(qy[:, None, :], np.concatenate((pts, np.zeros((len(pts), 1))), axis=1)[None])[..., :2]

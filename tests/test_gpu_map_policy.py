@@ -107,7 +107,7 @@ def test_on_stairs_with_a_drifting_pose_every_known_scan_value_stays_inside_the_
     hs, res = float(t.horizontal_scale), cam.map.resolution
     grid = env.terrain.heightsamples.astype(np.float64) * t.vertical_scale
     est = cam.odometry_pose()[:, :7].cpu().numpy().astype(np.float64)
-    pts, scan, known = cam._map["pts"].cpu().numpy().astype(np.float64), cam.map_scan().cpu().numpy(), cam.map_known().cpu().numpy().astype(bool)
+    pts, scan, known = cam.stage("map").buffers["pts"].cpu().numpy().astype(np.float64), cam.map_scan().cpu().numpy(), cam.map_known().cpu().numpy().astype(bool)
     n = 1.0 / np.sqrt(est[:, 5] ** 2 + est[:, 6] ** 2)
     qy = np.stack((np.zeros(N), np.zeros(N), est[:, 5] * n, est[:, 6] * n), axis=1)
     w = est[:, None, :2] + ER.rot(qy[:, None, :], np.concatenate((pts, np.zeros((len(pts), 1))), axis=1)[None])[..., :2]

@@ -134,12 +134,12 @@ def test_captured_graph_replay_equals_eager_bit_for_bit():
     g = torch.Generator().manual_seed(3)
     for _ in range(5):
         env.step_device((torch.randn(64, 12, generator=g) * 0.5).to("cuda:0"))
-    cam._out.fill_(-1.0)
+    cam.out_rows.fill_(-1.0)
     graph.replay()
     torch.cuda.synchronize()
     replayed = cam.out.clone()
     assert bool((replayed > 0).all())
-    cam._out.fill_(-1.0)
+    cam.out_rows.fill_(-1.0)
     eager = cam.update().clone()
     torch.cuda.synchronize()
     assert torch.equal(replayed.view(torch.int32), eager.view(torch.int32))

@@ -83,11 +83,11 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
     def fresh_equal_the_twin(envs, what):
         """lsim_sensor_capture_inst, FILL_ALL, on the camera's present mounts and rows, tick and stream: the whole history of a fresh env"""
         twin.mount.copy_(cam.mount)
-        twin._sm.tick, twin._sm.flags, twin._sm.stream_id = cam.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], cam.stream_id
+        twin.stage("capture").struct.tick, twin.stage("capture").struct.flags, twin.stage("capture").struct.stream_id = cam.tick, abi.DEFINES["LSIM_SENSOR_FILL_ALL"], cam.stream_id
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        assert env._L.lsim_sensor_capture_inst(ctypes.byref(twin._sm), cam.instrument_rows().data_ptr(), stream) == 0
+        assert env._L.lsim_sensor_capture_inst(ctypes.byref(twin.stage("capture").struct), cam.instrument_rows().data_ptr(), stream) == 0
         torch.cuda.synchronize()
-        np.testing.assert_array_equal(bits(cam._hist)[envs], bits(twin._hist)[envs], err_msg=what)
+        np.testing.assert_array_equal(bits(cam.history())[envs], bits(twin.history())[envs], err_msg=what)
 
     fresh_equal_the_twin(np.arange(N), "add_sensor")
     k = torch.arange(N, device=DEV) % 16
@@ -104,7 +104,7 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
             assert fresh[[2, 9]].all()
             np.testing.assert_array_equal((bits(cam.instrument_rows()) != bits(before)).any(axis=1), fresh)
             fresh_equal_the_twin(np.nonzero(fresh)[0], "reset_idx by hand")
-        before, hist_b, tick = cam.instrument_rows().clone(), cam._hist.clone(), env.common_step_counter
+        before, hist_b, tick = cam.instrument_rows().clone(), cam.history().clone(), env.common_step_counter
         env.step_device((torch.randn(N, 12, generator=g) * 0.5).to(DEV))
         torch.cuda.synchronize()
         reset = env.reset_buf.cpu().numpy().astype(bool)
@@ -112,13 +112,13 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
         np.testing.assert_array_equal(changed, reset, err_msg=f"step {step}")
         fresh_equal_the_twin(np.nonzero(reset)[0], f"step {step}")
         due = reset | ((tick + np.arange(N)) % 4 == 0)
-        np.testing.assert_array_equal(bits(cam._hist)[~due], bits(hist_b)[~due])
-        assert (bits(cam._hist)[due] != bits(hist_b)[due]).any(axis=(1, 2)).all()
+        np.testing.assert_array_equal(bits(cam.history())[~due], bits(hist_b)[~due])
+        assert (bits(cam.history())[due] != bits(hist_b)[due]).any(axis=(1, 2)).all()
         resets += int(reset.sum())
     assert resets >= 16, "the time-outs happened"
     assert api.calls == {"lsim_sensor_mount_jitter": 14, "lsim_sensor_instrument": 14, "lsim_sensor_capture_inst": 14, "lsim_sensor_capture": 0}
     assert int(cam.nonfinite_rays) == 0 and int(twin.nonfinite_rays) == 0 and int(env.nonfinite_envs) == 0
-    assert bool(torch.isfinite(cam._hist).all())
+    assert bool(torch.isfinite(cam.history()).all())
 
 
 def _runner(env):
@@ -164,7 +164,7 @@ def test_train_save_and_evaluate_with_the_recorded_instrument(tmp_path):
         if choice == "trained":
             assert entry == dict(_instrument().record(), choice="trained") and cam2.instrument == _instrument()
         elif choice is None:
-            assert entry == dict(blank, choice="off") and cam2.instrument is None and cam2._inst is None
+            assert entry == dict(blank, choice="off") and cam2.instrument is None and cam2.stage("instrument") is None
         else:
             assert entry == dict(wide.record(), choice="override") and cam2.instrument == wide
             assert float(cam2.instrument_rows()[:, 2].abs().max()) > 0.02
@@ -180,4 +180,4 @@ def test_a_runner_whose_camera_has_no_instrument_launches_neither_kernel():
     run.learn(1)
     torch.cuda.synchronize()
     assert api.calls["lsim_sensor_instrument"] == api.calls["lsim_sensor_capture_inst"] == 0 and api.calls["lsim_sensor_capture"] >= 1 + 6
-    assert cam.instrument is None and cam._inst is None and "instrument" not in cam.spec()
+    assert cam.instrument is None and cam.stage("instrument") is None and "instrument" not in cam.spec()

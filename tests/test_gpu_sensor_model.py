@@ -107,19 +107,19 @@ def test_modelled_camera_on_a_mixed_robot_env_on_stairs():
     twin = env.add_sensor("twin", sensors.depth_camera(env, 12, 8, 87.0, **kw))
     assert cam.frames().shape == (256, 2, 96) and cam.frame_images().shape == (256, 2, 8, 12) and cam.stream_id == 0
     torch.cuda.synchronize()
-    h0 = cam._hist.cpu().numpy()
+    h0 = cam.history().cpu().numpy()
     assert (h0[:, 1:] == h0[:, :1]).all(), "add_sensor fills every slot"
     g = torch.Generator().manual_seed(2)
     resets = shifts = 0
     for _ in range(12):
         tick = env.common_step_counter
-        hist_b, out_b = cam._hist.clone(), cam.out.clone()
+        hist_b, out_b = cam.history().clone(), cam.out.clone()
         env.step_device((torch.randn(256, 12, generator=g) * 0.5).to("cuda:0"))
         torch.cuda.synchronize()
         assert cam.tick == tick
         fill = (env.episode_length_buf == 0).cpu().numpy()
         due = fill | ((tick + np.arange(256)) % 4 == 0)
-        hist_a, out_a, tw = cam._hist.cpu().numpy(), cam.out.cpu().numpy(), twin.out.cpu().numpy()
+        hist_a, out_a, tw = cam.history().cpu().numpy(), cam.out.cpu().numpy(), twin.out.cpu().numpy()
         hist_b, out_b = hist_b.cpu().numpy(), out_b.cpu().numpy()
         np.testing.assert_array_equal(SC.bits(out_a[due]), SC.bits(tw[due]))
         y = np.clip(out_a, np.float32(0.05), np.float32(5.0))               # the default model: clip to (near, far), nothing else

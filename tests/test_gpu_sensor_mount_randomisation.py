@@ -65,7 +65,7 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
     def twin_equals(envs, what):
         twin.mount.copy_(cam.mount)
         want = twin.update().cpu().numpy()
-        hist = cam._hist.cpu().numpy()[:, :, :cam.num_rays]
+        hist = cam.history().cpu().numpy()[:, :, :cam.num_rays]
         for k in range(hist.shape[1]):
             np.testing.assert_array_equal(bits(hist[envs, k]), bits(want[envs]), err_msg=f"{what}: slot {k}")
         return want
@@ -77,7 +77,7 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
     g = torch.Generator().manual_seed(2)
     resets = 0
     for step in range(12):
-        before, hist_b, tick = cam.mount.clone(), cam._hist.clone(), env.common_step_counter
+        before, hist_b, tick = cam.mount.clone(), cam.history().clone(), env.common_step_counter
         env.step_device((torch.randn(N, 12, generator=g) * 0.5).to(DEV))
         torch.cuda.synchronize()
         reset = env.reset_buf.cpu().numpy().astype(bool)
@@ -86,7 +86,7 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
         np.testing.assert_array_equal(bits(cam.mount)[~reset], bits(before)[~reset])
         clean = twin_equals(np.nonzero(reset)[0], f"step {step}")
         due = reset | ((tick + np.arange(N)) % 4 == 0)
-        hist = cam._hist.cpu().numpy()
+        hist = cam.history().cpu().numpy()
         np.testing.assert_array_equal(bits(hist[due, -1, :cam.num_rays]), bits(clean[due]))
         np.testing.assert_array_equal(bits(hist[~due]), bits(hist_b)[~due])
         resets += int(reset.sum())

@@ -161,4 +161,4 @@ def test_exported_module_on_the_cpu_against_the_device_pipeline(trained, tmp_pat
     print("act: max |export - device|", float((got - mean.cpu()).abs().max()), "scale", float(mean.abs().max()))
     torch.testing.assert_close(got, mean.cpu(), rtol=2e-4, atol=2e-5 * float(mean.abs().max()))
     # and the clip / normalisation constants are the sensor's
-    assert (mod.clip_lo, mod.clip_hi, mod.offset, mod.gain) == tuple(float(getattr(cam._sm, k)) for k in ("clip_lo", "clip_hi", "offset", "gain"))
+    assert (mod.clip_lo, mod.clip_hi, mod.offset, mod.gain) == tuple(float(getattr(cam.stage("capture").struct, k)) for k in ("clip_lo", "clip_hi", "offset", "gain"))

@@ -53,7 +53,7 @@ def trained(tmp_path_factory):
     k = torch.arange(N, device=DEV) % 16            # behind the runner's own reset: some envs time out on the way
     env.episode_length_buf.copy_(torch.where((k >= 3) & (k <= 6), int(env.max_episode_length) - 2 - k, torch.zeros_like(k)).to(env.episode_length_buf.dtype))
     mem = run.alg.memory
-    assert mem is run.memory and cam._memory is mem and run.alg.actor_critic.depth_latent_dim == L + H
+    assert mem is run.memory and cam.memory is mem and run.alg.actor_critic.depth_latent_dim == L + H
     # ---- one rollout, recorded: what the sensor showed before every env step
     seen = []
     step = env.step_device
@@ -137,7 +137,7 @@ def test_learn_save_load_learn_evaluate_and_export(trained, tmp_path):
         env = _env(9)
         env.add_sensor("depth", sensors.from_spec(env, d["vision"]["sensor"]))
         ev = evaluate(env, path, 20, commands=(0.8, 0.0, 0.0), fused=fused)
-        assert env.sensors["depth"]._memory is not None and env.sensors["depth"].memory_rows().shape == (N, L + H)
+        assert env.sensors["depth"].memory is not None and env.sensors["depth"].memory_rows().shape == (N, L + H)
         res[fused] = ev.result()
         cols = res[fused]["total"]["columns"]
         assert res[fused]["conventions"]["columns"] == ["depth_influence", "scan_error", "memory_scan_error"]
@@ -178,7 +178,7 @@ def test_evaluate_on_a_second_env_leaves_the_training_sensors_rows_alone(trained
     cam2 = env2.add_sensor("depth", _camera(env2))
     evaluate(env2, run, 5, commands=(0.8, 0.0, 0.0), sensor=cam2)
     torch.cuda.synchronize()
-    assert cam2._memory is mem and cam._memory is mem
+    assert cam2.memory is mem and cam.memory is mem
     assert cam.memory_rows().data_ptr() == ptr and cam.memory_rows().shape == (N, L + H) and torch.equal(cam.memory_rows(), bits)
     assert cam2.memory_rows().shape == (48, L + H)
     run.learn(1)
@@ -194,7 +194,7 @@ def test_a_runner_without_memory_launches_no_memory_kernel():
     proxy = type("Api", (), {"__getattr__": lambda self, name: (calls.append(name), getattr(real, name))[1]})()
     cam._api = proxy
     run = _runner(env, None)
-    assert run.memory is None and run.alg.memory is None and cam._memory is None
+    assert run.memory is None and run.alg.memory is None and cam.memory is None
     run.learn(1)
     assert "lsim_depth_encode" in calls and not any("memory" in c or "gru" in c for c in calls)
     assert len(run.last_update) == 5 and run.alg.storage.depth_latent.shape == (T, N, L)

@@ -38,21 +38,21 @@ def test_launch_order_is_odometry_capture_map_rows_with_the_captures_tick_and_fl
     assert cam.attach_map_rows(("height", "known")) is cam.map_rows() and log == [], "never captured: nothing to integrate, insert or build yet"
     env.add_sensor("depth", cam)
     assert log == CHAIN
-    assert cam._od.stream_id == cam._sm.stream_id == cam.stream_id and (cam._od.seed, cam._od.rank) == (cam._sm.seed, cam._sm.rank)
+    assert cam.stage("odometry").struct.stream_id == cam.stage("capture").struct.stream_id == cam.stream_id and (cam.stage("odometry").struct.seed, cam.stage("odometry").struct.rank) == (cam.stage("capture").struct.seed, cam.stage("capture").struct.rank)
     assert bool((cam.odometry_state()[:, 0:4] == 0).all()) and bool((cam.odometry_state()[:, 4:7] != 0).all()), "add_sensor's refresh made every env fresh"
     g = torch.Generator().manual_seed(0)
     for step in range(4):
         tick = env.common_step_counter
         env.step_device(torch.randn(N, 12, generator=g) * 0.3)
-        assert cam._od.tick == cam._sm.tick == cam._em.tick == tick and cam._od.flags == cam._sm.flags == cam._em.flags
+        assert cam.stage("odometry").struct.tick == cam.stage("capture").struct.tick == cam.stage("map").struct.tick == tick and cam.stage("odometry").struct.flags == cam.stage("capture").struct.flags == cam.stage("map").struct.flags
     assert log == CHAIN * 5 and api.calls["lsim_odometry_step"] == 5 and api.calls["lsim_map_rows"] == 5
     odo, est = cam.odometry_state(), cam.odometry_pose()
     moved = env.episode_length_buf > 1
     assert bool(moved.any()) and bool((odo[moved][:, 0:3] != 0).all()), "every env that walked has drifted"
     assert torch.equal(odo[:, 8:10], env.root_states[:, 0:2]) and torch.equal(est[:, 7:13], env.root_states[:, 7:13])
     assert torch.equal(est[:, 0:3], env.root_states[:, 0:3] + odo[:, 0:3])
-    assert cam._em.root_states == est.data_ptr() != env.root_states.data_ptr() and cam._sm.rb.rc.root_states == env.root_states.data_ptr()
-    assert cam._mr.pose == est.data_ptr() and cam.map_pose() is est
+    assert cam.stage("map").struct.root_states == est.data_ptr() != env.root_states.data_ptr() and cam.stage("capture").struct.rb.rc.root_states == env.root_states.data_ptr()
+    assert cam.stage("map_rows").struct.pose == est.data_ptr() and cam.map_pose() is est
     env.reset_idx([1])
     assert log[-4:] == CHAIN and len(log) == 24
     assert bool((cam.odometry_state()[1, 0:4] == 0).all()) and bool((cam.odometry_state()[0, 0:3] != 0).all())
@@ -63,7 +63,7 @@ def test_launch_order_is_odometry_capture_map_rows_with_the_captures_tick_and_fl
     np.testing.assert_array_equal(bits(rows[:, :P]), bits(want))
     cam.attach_map_rows(None)
     env.step_device(torch.zeros(N, 12))
-    assert log[-3:] == CHAIN[:3] and cam._mr is None and cam._rows is None
+    assert log[-3:] == CHAIN[:3] and cam.stage("map_rows") is None
     with pytest.raises(ValueError, match="attach_map_rows"):
         cam.map_rows()
 
@@ -73,12 +73,12 @@ def test_without_odometry_and_rows_nothing_is_allocated_or_launched_and_the_maps
     cam = env.add_sensor("depth", _camera(env, api))
     m = sensors.ElevationMap(size=16)
     cam.attach_map(m)
-    plain = bytes(cam._em)
+    plain = bytes(cam.stage("map").struct)
     for _ in range(2):
         env.step_device(torch.zeros(8, 12))
     assert api.calls["lsim_odometry_step"] == 0 and api.calls["lsim_map_rows"] == 0 and api.calls["lsim_elevation_map"] == 3
-    assert cam.odometry is None and cam._od is None and cam._odo is None and cam._mr is None and cam._rows is None and cam.map_channels is None
-    assert cam._em.root_states == env.root_states.data_ptr() and cam.map_pose() is env.root_states
+    assert cam.odometry is None and cam.stage("odometry") is None and cam.stage("map_rows") is None and cam.map_channels is None
+    assert cam.stage("map").struct.root_states == env.root_states.data_ptr() and cam.map_pose() is env.root_states
     assert list(cam.spec()) == SPEC_KEYS + ["map"]
     for getter in (cam.odometry_pose, cam.odometry_state):
         with pytest.raises(ValueError, match="odometry"):
@@ -88,14 +88,14 @@ def test_without_odometry_and_rows_nothing_is_allocated_or_launched_and_the_maps
     # the struct attach_map fills: field for field the one without the parameter, but for the arrays it allocated anew and the tick it ran on
     def fields(em, skip=("pts", "height", "stamp", "cell", "scan", "known", "state", "inv_scale", "tick", "flags")):
         return {f: getattr(em, f) for f, _ in em._fields_ if f not in skip}
-    before = fields(cam._em)
+    before = fields(cam.stage("map").struct)
     cam.attach_map(m, odometry=None)
-    assert fields(cam._em) == before and len(bytes(cam._em)) == len(plain)
+    assert fields(cam.stage("map").struct) == before and len(bytes(cam.stage("map").struct)) == len(plain)
     cam.attach_map(m, odometry=ODO)
-    with_odo = fields(cam._em)
+    with_odo = fields(cam.stage("map").struct)
     assert {k for k in before if before[k] != with_odo[k]} == {"root_states"} and api.calls["lsim_odometry_step"] == 1
     cam.attach_map_rows(("height",))
-    assert cam.attach_map(None) is None and cam._od is None and cam._odo is None and cam._mr is None and cam._rows is None and cam.odometry is None
+    assert cam.attach_map(None) is None and cam.stage("odometry") is None and cam.stage("map_rows") is None and cam.odometry is None
     assert list(cam.spec()) == SPEC_KEYS
     with pytest.raises(TypeError):
         cam.attach_map(m, odometry={"scale": 0.1})
@@ -157,7 +157,7 @@ def test_a_yaw_drift_bends_the_map_on_a_slope():
         p[:, 0] -= np.float32(0.0442)
         p[:, 1] -= np.float32(0.0442)
         known = cam.map_known().numpy().astype(bool)
-        world = p[:, None, :2] + cam._map["pts"].numpy()[None]       # identity orientation: the base-yaw frame is the world's
+        world = p[:, None, :2] + cam.stage("map").buffers["pts"].numpy()[None]       # identity orientation: the base-yaw frame is the world's
         err = np.abs(cam.map_scan().numpy() - _truth(env, world))
         assert known.sum() > N * 40
         errs[name] = float(err[known].mean())
@@ -176,8 +176,8 @@ def test_spec_and_from_spec_carry_the_odometrys_record():
     spec = cam.spec()
     assert list(spec) == SPEC_KEYS + ["map", "odometry"] and spec["odometry"] == ODO.record() and json.loads(json.dumps(spec)) == spec
     back = sensors.from_spec(env, spec, api=api)
-    assert back.odometry == ODO and back.map == m and back.spec() == spec and back._em.root_states == back.odometry_pose().data_ptr()
-    assert [getattr(back._od, n) for n in ("scale_range", "yaw_range", "z_range", "pos_noise", "yaw_noise", "z_noise")] == [np.float32(v) for v in ODO.ranges()]
+    assert back.odometry == ODO and back.map == m and back.spec() == spec and back.stage("map").struct.root_states == back.odometry_pose().data_ptr()
+    assert [getattr(back.stage("odometry").struct, n) for n in ("scale_range", "yaw_range", "z_range", "pos_noise", "yaw_noise", "z_noise")] == [np.float32(v) for v in ODO.ranges()]
     assert sensors.from_spec(env, spec, api=api, odometry=None).odometry is None
     other = sensors.OdometryError(scale=0.1)
     assert sensors.from_spec(env, spec, api=api, odometry=other).odometry == other
@@ -309,7 +309,7 @@ def test_evaluate_on_a_map_policy_blind_the_three_odometry_forms_and_the_scan_er
     env3, api3, cam3 = _map_env(points=None)
     off_ = _evaluate(env3, path, sensor=cam3, odometry=None, vision_metrics=named).result()
     assert off_["conventions"]["odometry"] == {"scale": None, "yaw_per_m": None, "z_per_m": None, "noise": None, "choice": "off"}
-    assert cam3.odometry is None and cam3._od is None and cam3.map_pose() is env3.root_states and cam3.map_channels == ("height",)
+    assert cam3.odometry is None and cam3.stage("odometry") is None and cam3.map_pose() is env3.root_states and cam3.map_channels == ("height",)
     wide = sensors.OdometryError(scale=0.2, yaw_per_m=0.5, z_per_m=0.2)
     over = _evaluate(env3, path, sensor=cam3, odometry=wide, vision_metrics=named, steps=6).result()
     assert over["conventions"]["odometry"] == dict(wide.record(), choice="override") and cam3.odometry == wide

@@ -299,7 +299,7 @@ def test_sensors_module_defaults_keywords_and_mixed_mounts():
     # the defaults: lsim_raycast exactly as before, nothing of the new path allocated or called
     plain = sensors.depth_camera(env, S.CAM_W, S.CAM_H, S.CAM_HFOV, mount_pos=BS.MOUNTS, pitch_deg=30.0, near=BS.NEAR, far=BS.FAR, api=api)
     terrain_only = plain.update().clone()
-    assert api.calls == {"lsim_raycast": 1, "lsim_raycast_bodies": 0} and not hasattr(plain, "_rb") and plain._labels is None
+    assert api.calls == {"lsim_raycast": 1, "lsim_raycast_bodies": 0} and plain.bodies_struct is None and plain.label_rows is None
     with pytest.raises(ValueError):
         plain.labels()
     mt0 = plain.mount.numpy()

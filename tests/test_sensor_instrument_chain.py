@@ -68,7 +68,7 @@ def test_without_an_instrument_nothing_is_launched_and_the_spec_is_the_one_of_be
         env.step_device(torch.randn(8, 12, generator=g) * 0.3)
     env.reset_idx([1])
     assert api.calls == dict.fromkeys(LAUNCHES, 0) | {"lsim_sensor_capture": 5}
-    assert cam.instrument is None and cam._si is None and cam._inst is None
+    assert cam.instrument is None and cam.stage("instrument") is None
     with pytest.raises(ValueError):
         cam.instrument_rows()
     assert list(cam.spec()) == ["kind", "width", "height", "dirs", "scale", "near", "far", "env_stride", "see_robot", "labels", "frame", "ignore_bodies",
@@ -100,9 +100,9 @@ def _twin_history(cam, twin, api):
     """lsim_sensor_capture_inst, FILL_ALL, on the camera's present mounts and rows, tick and stream: what the whole history of a just-reset
     env must hold, bit for bit"""
     twin.mount.copy_(cam.mount)
-    twin._sm.tick, twin._sm.flags, twin._sm.stream_id = cam.tick, FILL_ALL, cam.stream_id
-    assert api.lsim_sensor_capture_inst(ctypes.byref(twin._sm), cam.instrument_rows().data_ptr(), None) == 0
-    return twin._hist.numpy().copy()
+    twin.stage("capture").struct.tick, twin.stage("capture").struct.flags, twin.stage("capture").struct.stream_id = cam.tick, FILL_ALL, cam.stream_id
+    assert api.lsim_sensor_capture_inst(ctypes.byref(twin.stage("capture").struct), cam.instrument_rows().data_ptr(), None) == 0
+    return twin.history().numpy().copy()
 
 
 def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
@@ -115,12 +115,12 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
     env.add_sensor("first", _camera(env, api, model=None))                  # so that the camera's stream_id is 1
     env.add_sensor("depth", cam)
     assert api.calls["lsim_sensor_instrument"] == api.calls["lsim_sensor_capture_inst"] == api.calls["lsim_sensor_mount_jitter"] == 1
-    assert api.calls["lsim_sensor_capture"] == 0 and cam.stream_id == cam._si.stream_id == 1
+    assert api.calls["lsim_sensor_capture"] == 0 and cam.stream_id == cam.stage("instrument").struct.stream_id == 1
     twin = _camera(env, api, see_robot=True)
     calls_twin = 0
     # add_sensor drew every env: the header's formulas on the camera's own seed, rank, stream and tick
     rows = cam.instrument_rows().numpy().copy()
-    r = {k: getattr(cam._si, k) for k in IB.RANGES}
+    r = {k: getattr(cam.stage("instrument").struct, k) for k in IB.RANGES}
     assert (r["lat_lo"], r["lat_hi"]) == (0, 2) and r["gain_lo"] == 0.5 and r["fov_range"] == np.float32(0.02)
     want, tol = IR.expected(rows, np.ones(N, bool), env.lcfg.seed, env.lcfg.rank, env.common_step_counter, 1, r)
     assert (np.abs(rows - want) <= tol).all() and (rows[:, 1:5] != IB.neutral_rows(N, 2)[:, 1:5]).all()
@@ -129,7 +129,7 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
         nonlocal calls_twin
         calls_twin += 1
         want = _twin_history(cam, twin, api)
-        np.testing.assert_array_equal(bits(cam._hist.numpy()[envs]), bits(want[envs]), err_msg=what)
+        np.testing.assert_array_equal(bits(cam.history().numpy()[envs]), bits(want[envs]), err_msg=what)
 
     fresh_equal_the_twin(np.arange(N), "add_sensor")
     el = torch.full((N,), 5, dtype=env.episode_length_buf.dtype)
@@ -146,7 +146,7 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
             np.testing.assert_array_equal((bits(cam.instrument_rows()) != bits(before)).any(axis=1), fresh)
             fresh_equal_the_twin(np.nonzero(fresh)[0], "reset_idx by hand")
             by_hand = cam.instrument_rows().clone()
-        before, hist_b, tick = cam.instrument_rows().clone(), cam._hist.clone(), env.common_step_counter
+        before, hist_b, tick = cam.instrument_rows().clone(), cam.history().clone(), env.common_step_counter
         env.step_device(torch.randn(N, 12, generator=g) * 0.3)
         reset = env.reset_buf.numpy().astype(bool)
         np.testing.assert_array_equal(reset, env.episode_length_buf.numpy() == 0)
@@ -154,7 +154,7 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
         np.testing.assert_array_equal(changed, reset, err_msg=f"step {step}")
         fresh_equal_the_twin(np.nonzero(reset)[0], f"step {step}")
         due = reset | ((tick + np.arange(N)) % 3 == 0)
-        np.testing.assert_array_equal(bits(cam._hist[~torch.from_numpy(due)]), bits(hist_b[~torch.from_numpy(due)]))
+        np.testing.assert_array_equal(bits(cam.history()[~torch.from_numpy(due)]), bits(hist_b[~torch.from_numpy(due)]))
         if step == 5:                           # the step that shares the by-hand reset's tick leaves those rows as they are
             np.testing.assert_array_equal(bits(cam.instrument_rows()[[2, 5]]), bits(by_hand[[2, 5]]))
         seen |= set(np.nonzero(reset)[0].tolist())
@@ -167,13 +167,13 @@ def test_reset_envs_draw_a_new_row_and_their_history_is_rendered_under_it():
     assert api.calls["lsim_sensor_capture"] == 0
     # back to the shared constants, and on again
     cam.set_instrument(None)
-    assert cam.instrument is None and cam._inst is None and "instrument" not in cam.spec()
+    assert cam.instrument is None and cam.stage("instrument") is None and "instrument" not in cam.spec()
     env.step_device(torch.zeros(N, 12))
     assert api.calls["lsim_sensor_instrument"] == n and api.calls["lsim_sensor_capture"] == 1
     cam.set_instrument(inst)
     np.testing.assert_array_equal(cam.instrument_rows().numpy(), IB.neutral_rows(N, 2))
     cam.refresh()
-    assert (cam.instrument_rows().numpy()[:, 1:5] != IB.neutral_rows(N, 2)[:, 1:5]).all() and cam.stream_id == cam._si.stream_id == 1
+    assert (cam.instrument_rows().numpy()[:, 1:5] != IB.neutral_rows(N, 2)[:, 1:5]).all() and cam.stream_id == cam.stage("instrument").struct.stream_id == 1
 
 
 def test_the_draw_comes_before_the_capture():
@@ -192,7 +192,7 @@ def test_the_draw_comes_before_the_capture():
     assert (bits(cam.instrument_rows()) != bits(before)).any(axis=1).all() and not held
     api.lsim_sensor_instrument, api.lsim_sensor_capture_inst = draw, capture
     want = _twin_history(cam, twin, api)
-    assert (bits(cam._hist.numpy()) != bits(want)).any(axis=(1, 2)).all()
+    assert (bits(cam.history().numpy()) != bits(want)).any(axis=(1, 2)).all()
 
 
 def test_spec_round_trips_the_instrument():
@@ -204,12 +204,12 @@ def test_spec_round_trips_the_instrument():
     assert json.loads(json.dumps(spec)) == spec and spec["instrument"] == inst.record() and list(spec)[-2:] == ["mount_jitter", "instrument"]
     back = sensors.from_spec(env, spec, api=api)
     assert back.instrument == inst and back.mount_jitter == cam.mount_jitter and back.spec() == spec
-    assert all(getattr(back._si, k) == getattr(cam._si, k) for k in IB.RANGES)
+    assert all(getattr(back.stage("instrument").struct, k) == getattr(cam.stage("instrument").struct, k) for k in IB.RANGES)
     plain = sensors.from_spec(env, spec, api=api, instrument=None)
-    assert plain.instrument is None and plain._inst is None and plain.spec() == {k: v for k, v in spec.items() if k != "instrument"}
+    assert plain.instrument is None and plain.stage("instrument") is None and plain.spec() == {k: v for k, v in spec.items() if k != "instrument"}
     other = sensors.from_spec(env, spec, api=api, instrument=sensors.InstrumentError(depth_scale=0.05))
     assert other.spec()["instrument"] == {"latency": None, "noise_gain": [1.0, 1.0], "depth_scale": 0.05, "depth_quad": 0.0, "fov": 0.0}
-    assert (other._si.lat_lo, other._si.lat_hi) == (2, 2)                # None: the model's latency for every env
+    assert (other.stage("instrument").struct.lat_lo, other.stage("instrument").struct.lat_hi) == (2, 2)                # None: the model's latency for every env
     assert sensors.from_spec(env, plain.spec(), api=api).instrument is None
     with pytest.raises(ValueError):
         sensors.from_spec(env, spec, api=api, instrument="trained")
@@ -265,7 +265,7 @@ def test_a_vision_checkpoint_records_the_instrument_and_evaluate_honours_the_cho
     calls = dict(api.calls)
     res = _evaluate(env4, path, camera_instrument=None).result()
     assert res["conventions"]["camera_instrument"] == {"choice": "off", "latency": None, "noise_gain": None, "depth_scale": None, "depth_quad": None, "fov": None}
-    assert cam4.instrument is None and cam4._inst is None
+    assert cam4.instrument is None and cam4.stage("instrument") is None
     assert api.calls["lsim_sensor_instrument"] == calls["lsim_sensor_instrument"] and api.calls["lsim_sensor_capture"] > calls["lsim_sensor_capture"]
     # an override beyond the trained range
     env5, cam5 = fresh()

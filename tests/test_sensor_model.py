@@ -133,7 +133,7 @@ def test_ray_sensor_with_a_model_on_the_emulated_env():
     # model=None: the launch and the allocations of before
     plain = env.add_sensor("plain", sensors.depth_camera(env, 6, 4, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, api=api, see_robot=True))
     assert api.calls == {"lsim_raycast": 0, "lsim_raycast_bodies": 0, "lsim_sensor_capture": 0}
-    assert plain.model is None and not hasattr(plain, "_sm") and not hasattr(plain, "_hist") and plain.stream_id == 0
+    assert plain.model is None and plain.stage("capture") is None and plain.chain() == ("lsim_raycast_bodies",) and plain.stream_id == 0
     with pytest.raises(ValueError):
         plain.frames()
     with pytest.raises(ValueError):
@@ -153,39 +153,39 @@ def test_ray_sensor_with_a_model_on_the_emulated_env():
     assert env.add_sensor("depth", cam) is cam
     # add_sensor: stream_id = the index in env.sensors, one refresh()
     assert seen == [(env.common_step_counter, SR.FILL_ALL, 1)] and cam.stream_id == 1 and cam.tick == env.common_step_counter
-    sm = cam._sm
+    sm = cam.stage("capture").struct
     assert (sm.seed, sm.rank) == (env.lcfg.seed, env.lcfg.rank) and sm.episode_length == env.episode_length_buf.data_ptr()
     assert abs(sm.offset - 1.55) < 1e-6 and abs(sm.gain - 1 / 2.9) < 1e-6 and (sm.clip_lo, sm.clip_hi) == (np.float32(0.1), np.float32(3.0))
-    assert cam.frames().shape == (4, 2, 24) and cam.frame_images().shape == (4, 2, 4, 6) and cam.frame_images().data_ptr() == cam._hist.data_ptr()
-    assert cam._hist.shape == (4, 3, 24)
-    h = cam._hist.numpy()
+    assert cam.frames().shape == (4, 2, 24) and cam.frame_images().shape == (4, 2, 4, 6) and cam.frame_images().data_ptr() == cam.history().data_ptr()
+    assert cam.history().shape == (4, 3, 24)
+    h = cam.history().numpy()
     assert (h[:, 1:] == h[:, :1]).all() and np.abs(h).max() <= 0.5
     plain.update()
     np.testing.assert_array_equal(cam.out.numpy(), plain.out.numpy())
     np.testing.assert_array_equal(h[:, 0], (np.clip(cam.out.numpy(), np.float32(0.1), np.float32(3.0)) - sm.offset) * sm.gain)
     # default clip and no normalisation
     lid = sensors.lidar(env, 2, 20.0, 8, far=6.0, api=api, model=sensors.SensorModel())
-    assert (lid._sm.clip_lo, lid._sm.clip_hi, lid._sm.offset, lid._sm.gain) == (np.float32(0.05), 6.0, 0.0, 1.0) and lid._sm.rb.robots is None
+    assert (lid.stage("capture").struct.clip_lo, lid.stage("capture").struct.clip_hi, lid.stage("capture").struct.offset, lid.stage("capture").struct.gain) == (np.float32(0.05), 6.0, 0.0, 1.0) and lid.stage("capture").struct.rb.robots is None
     # step_device: the tick is common_step_counter before its increment, no flag
     del seen[:]
     g = torch.Generator().manual_seed(4)
     for k in range(2):
-        before, t = cam._hist.numpy().copy(), env.common_step_counter
+        before, t = cam.history().numpy().copy(), env.common_step_counter
         env.step_device(torch.randn(4, 12, generator=g) * 0.3)
         assert seen[-1] == (t, 0, 1) and cam.tick == t and env.common_step_counter == t + 1
         el = env.episode_length_buf.numpy()
         due, fill = SR.due_sets(4, 1, t, 2, True, 0, el)
-        after = cam._hist.numpy()
+        after = cam.history().numpy()
         np.testing.assert_array_equal(after[~due], before[~due])
         keep = due & ~fill
         np.testing.assert_array_equal(after[keep, :2], before[keep, 1:])
         assert keep.any() and not (after[keep, 2] == before[keep, 2]).all()
     assert api.calls["lsim_sensor_capture"] == 3 and api.calls["lsim_raycast_bodies"] == 3
     # reset_idx by hand: RESETS_ONLY, only the env that was reset changes
-    before = cam._hist.numpy().copy()
+    before = cam.history().numpy().copy()
     env.reset_idx([2])
     assert seen[-1] == (env.common_step_counter, SR.RESETS_ONLY, 1)
-    after = cam._hist.numpy()
+    after = cam.history().numpy()
     others = np.array([True, True, False, True])
     np.testing.assert_array_equal(after[others], before[others])
     assert (after[2, 1:] == after[2, :1]).all() and not (after[2] == before[2]).all()

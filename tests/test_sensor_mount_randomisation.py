@@ -59,7 +59,7 @@ def test_without_a_jitter_nothing_is_launched_and_the_spec_is_the_one_of_before(
         env.step_device(torch.randn(8, 12, generator=g) * 0.3)
     env.reset_idx([1])
     assert api.calls["lsim_sensor_mount_jitter"] == 0 and api.calls["lsim_sensor_capture"] == 5
-    assert cam.mount is cam.mount_nominal and cam.mount_jitter is None and cam._mj is None and cam._sm.rb.rc.mount == cam.mount.data_ptr()
+    assert cam.mount is cam.mount_nominal and cam.mount_jitter is None and cam.stage("mount_jitter") is None and cam.stage("capture").struct.rb.rc.mount == cam.mount.data_ptr()
     assert list(cam.spec()) == ["kind", "width", "height", "dirs", "scale", "near", "far", "env_stride", "see_robot", "labels", "frame", "ignore_bodies",
                                 "model", "mount"]
     plain = _camera(env, api, model=None)
@@ -85,7 +85,7 @@ def _twin_equals(cam, twin, envs, what):
     """the plain ray cast from cam's present mount rows: what every slot of a just-filled history must hold (identity model), bit for bit"""
     twin.mount.copy_(cam.mount)
     want = twin.update().numpy()
-    hist = cam._hist.numpy()[:, :, :cam.num_rays]
+    hist = cam.history().numpy()[:, :, :cam.num_rays]
     for e in envs:
         for k in range(hist.shape[1]):
             np.testing.assert_array_equal(bits(hist[e, k]), bits(want[e]), err_msg=f"{what}: env {e} slot {k}")
@@ -98,10 +98,10 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
     jit = sensors.MountJitter(**JITTER)
     cam = _camera(env, api, see_robot=True, mount_jitter=jit)
     assert cam.mount is not cam.mount_nominal and torch.equal(cam.mount, cam.mount_nominal) and api.calls == COUNTS0
-    assert cam._sm.rb.rc.mount == cam._rb.rc.mount == cam._rc.mount == cam.mount.data_ptr() != cam.mount_nominal.data_ptr()
+    assert cam.stage("capture").struct.rb.rc.mount == cam.bodies_struct.rc.mount == cam.ray_struct.mount == cam.mount.data_ptr() != cam.mount_nominal.data_ptr()
     env.add_sensor("first", _camera(env, api, model=None))                  # so that the camera's stream_id is 1
     env.add_sensor("depth", cam)
-    assert api.calls["lsim_sensor_mount_jitter"] == 1 and cam.stream_id == cam._mj.stream_id == 1
+    assert api.calls["lsim_sensor_mount_jitter"] == 1 and cam.stream_id == cam.stage("mount_jitter").struct.stream_id == 1
     twin = _camera(env, api, see_robot=True, model=None, mount_pos=cam.mount[:, :3])
     # add_sensor drew every env: the header's formulas on the camera's own seed, rank, stream and tick, degrees turned into radians
     nominal = cam.mount_nominal.numpy()
@@ -128,7 +128,7 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
             np.testing.assert_array_equal(changed, fresh)
             _twin_equals(cam, twin, np.nonzero(fresh)[0], "reset_idx by hand")
             by_hand = cam.mount.clone()
-        before, hist_b, tick = cam.mount.clone(), cam._hist.clone(), env.common_step_counter
+        before, hist_b, tick = cam.mount.clone(), cam.history().clone(), env.common_step_counter
         env.step_device(torch.randn(N, 12, generator=g) * 0.3)
         reset = env.reset_buf.numpy().astype(bool)
         np.testing.assert_array_equal(reset, env.episode_length_buf.numpy() == 0)
@@ -137,9 +137,9 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
         np.testing.assert_array_equal(bits(cam.mount[~torch.from_numpy(reset)]), bits(before[~torch.from_numpy(reset)]))
         clean = _twin_equals(cam, twin, np.nonzero(reset)[0], f"step {step}")
         due = reset | ((tick + np.arange(N)) % 3 == 0)
-        hist = cam._hist.numpy()[:, :, :cam.num_rays]
+        hist = cam.history().numpy()[:, :, :cam.num_rays]
         np.testing.assert_array_equal(bits(hist[due, -1]), bits(clean[due]))                       # every capture is from the present rows
-        np.testing.assert_array_equal(bits(cam._hist[~torch.from_numpy(due)]), bits(hist_b[~torch.from_numpy(due)]))
+        np.testing.assert_array_equal(bits(cam.history()[~torch.from_numpy(due)]), bits(hist_b[~torch.from_numpy(due)]))
         if step == 5:                           # the step that shares the by-hand reset's tick leaves those rows as they are
             np.testing.assert_array_equal(bits(cam.mount[[2, 5]]), bits(by_hand[[2, 5]]))
         seen |= set(np.nonzero(reset)[0].tolist())
@@ -148,7 +148,7 @@ def test_reset_envs_get_a_new_mount_and_their_history_is_rendered_from_it():
     assert api.calls["lsim_sensor_mount_jitter"] == api.calls["lsim_sensor_capture"] == 1 + 9 + 1
     # back to the nominal mount, and on again
     cam.set_mount_jitter(None)
-    assert cam.mount is cam.mount_nominal and cam._sm.rb.rc.mount == cam.mount_nominal.data_ptr() and "mount_jitter" not in cam.spec()
+    assert cam.mount is cam.mount_nominal and cam.stage("capture").struct.rb.rc.mount == cam.mount_nominal.data_ptr() and "mount_jitter" not in cam.spec()
     calls = api.calls["lsim_sensor_mount_jitter"]
     env.step_device(torch.zeros(N, 12))
     assert api.calls["lsim_sensor_mount_jitter"] == calls
@@ -166,8 +166,8 @@ def test_spec_round_trips_the_nominal_mount_and_the_jitter():
     assert spec["mount"] == _camera(env, api).spec()["mount"] and not torch.equal(cam.mount, cam.mount_nominal)      # the nominal pose, not the drawn ones
     back = sensors.from_spec(env, spec, api=api)
     assert back.mount_jitter == jit and torch.equal(back.mount_nominal, cam.mount_nominal) and back.spec() == spec
-    assert [back._mj.pos_range[k] for k in range(3)] == [cam._mj.pos_range[k] for k in range(3)]
-    assert [back._mj.rot_range[k] for k in range(3)] == [cam._mj.rot_range[k] for k in range(3)] == [np.float32(math.radians(d)) for d in jit.rot_deg]
+    assert [back.stage("mount_jitter").struct.pos_range[k] for k in range(3)] == [cam.stage("mount_jitter").struct.pos_range[k] for k in range(3)]
+    assert [back.stage("mount_jitter").struct.rot_range[k] for k in range(3)] == [cam.stage("mount_jitter").struct.rot_range[k] for k in range(3)] == [np.float32(math.radians(d)) for d in jit.rot_deg]
     plain = sensors.from_spec(env, spec, api=api, mount_jitter=None)
     assert plain.mount_jitter is None and plain.mount is plain.mount_nominal and "mount_jitter" not in plain.spec()
     assert plain.spec() == {k: v for k, v in spec.items() if k != "mount_jitter"}

@@ -156,10 +156,10 @@ def test_spec_round_trips_through_from_spec():
     twin = sensors.from_spec(env, spec, api=api)
     assert isinstance(twin, sensors.DepthCamera) and (twin.width, twin.height) == (8, 6)
     assert torch.equal(twin.dirs, cam.dirs) and torch.equal(twin.scale, cam.scale) and torch.equal(twin.mount, cam.mount)
-    assert twin.body_mask == cam.body_mask and twin.body_mask != (1 << 17) - 1 and twin.frame == "yaw" and twin.see_robot and twin._labels is not None
+    assert twin.body_mask == cam.body_mask and twin.body_mask != (1 << 17) - 1 and twin.frame == "yaw" and twin.see_robot and twin.label_rows is not None
     assert (twin.near, twin.far, twin.env_stride) == (cam.near, cam.far, cam.env_stride)
     for k in ("period", "stagger", "latency", "frames", "sigma0", "sigma2", "p_drop", "drop_value", "clip_lo", "clip_hi", "offset", "gain"):
-        assert getattr(twin._sm, k) == getattr(cam._sm, k), k
+        assert getattr(twin.stage("capture").struct, k) == getattr(cam.stage("capture").struct, k), k
     assert twin.spec() == spec
     # one pose for all envs; a lidar; a mount that differs from env to env
     one = sensors.depth_camera(env, 8, 6, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, api=api).spec()
@@ -226,7 +226,7 @@ def test_checkpoint_holds_the_vision_record_and_evaluates(tmp_path):
     ev, recorded = _evaluate(env2, path)
     res = ev.result()
     assert res["steps"] == 8 and len(recorded) == 8 and res["conventions"]["columns"] == ["depth_influence", "scan_error"]
-    assert cam2._encoder is not None and all(torch.equal(a, b) for a, b in zip(cam2._encoder.state_dict().values(), run.alg.encoder.state_dict().values()))
+    assert cam2.encoder is not None and all(torch.equal(a, b) for a, b in zip(cam2.encoder.state_dict().values(), run.alg.encoder.state_dict().values()))
     tot = res["total"]
     assert tot["samples"] + tot["episodes"] == 64 and tot["samples"] > 0
     assert tot["columns"]["depth_influence"]["mean"] > 0 and tot["columns"]["scan_error"]["mean"] > 0

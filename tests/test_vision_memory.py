@@ -152,9 +152,9 @@ def test_memory_data_slices_and_alignment_of_a_stored_rollout_on_the_emulated_en
         bare.memory_state()
     cam = env.add_sensor("depth", sensors.depth_camera(env, 6, 4, 87.0, model=m, **kw))
     cam.attach_encoder(enc)
-    assert api.calls["lsim_depth_memory_step"] == 0 and cam._memory is None          # without attach_memory nothing is allocated or launched
+    assert api.calls["lsim_depth_memory_step"] == 0 and cam.memory is None          # without attach_memory nothing is allocated or launched
     env.step_device(torch.zeros(4, 12))
-    assert api.calls["lsim_depth_memory_step"] == 0 and cam._memory_h is None and cam._memory_rows is None
+    assert api.calls["lsim_depth_memory_step"] == 0 and cam.stage("memory") is None
     assert cam.attach_memory(mem) is mem and api.calls["lsim_depth_memory_step"] == 1
     prm = tuple(p.detach().numpy() for p in mem.device_params())
     want, bound = R.step(cam.latent().numpy(), env.obs_buf[:, :Pm].numpy(), np.zeros((4, H)), np.ones(4, bool), prm)

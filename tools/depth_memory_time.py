@@ -77,7 +77,7 @@ def step_time(n, samples):
         return 1000.0 * sorted(ms_a[:cnt.value])[cnt.value // 2]
     a_before = kernel_a()                               # without the memory attached
     cam.attach_memory(mem)                              # h and the rows are the sensor's; steps every env once from h = 0
-    t = alternate({"step": lambda: mem.step_device(cam), "encode_staggered": lambda: cam._encoder.encode_device(cam, 1)}, samples, iters)
+    t = alternate({"step": lambda: mem.step_device(cam), "encode_staggered": lambda: cam.stage("encoder").launch(1, 0)}, samples, iters)
     a_after = kernel_a()
     return {"num_envs": n, "cell": {"latent_dim": 64, "proprio_dim": env.num_one_step_obs, "hidden": 64}, "lds_bytes": list(mem.lds_bytes(L)),
             "step_us": [1000.0 * v for v in t["step"]], "encode_staggered_us": [1000.0 * v for v in t["encode_staggered"]],

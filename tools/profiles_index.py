@@ -77,6 +77,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "elevation_map_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_elevation_map` alone over the same ticks (1 env in 5 due) and with every env due, `update()` with both; `bench.py` alternating with the parent's tree", '7.15'),
               "map_policy_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002 --map-rows 2`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_odometry_step` alone, `lsim_map_rows` alone and the torch statement of the same rows, `update()` with odometry, capture, map and rows; `bench.py` alternating with the parent's tree", '7.16'),
               "sensor_options_refactor_ab.json": ("parent commit against the commit that gave the sensor options one record, one text grammar and one resolver, `learn/evaluate.py` one step loop and `MapPPO` a base class of its own: `evaluate(...).result()` of a HIM, a vision (with and without memory) and a map policy under every form of `blind`, `camera_jitter`, `camera_instrument` and `odometry`, on the emulated env and on the device (equal), then a 500-step `evaluate()` at N = 4096 and `bench.py --gpus 1 --steps 1000 --warmup 100` in three alternating pairs each, with the parent's run-to-run spread, and the code lines of the four files", "7.16"),
+              "sensor_chain_refactor_ab.json": ("parent commit against the commit that made every launch behind `RaySensor.update()` a stage of one chain (host-side Python only, the same library): SHA-256 of every sensor output tensor of twelve chain configurations at N = 8 and N = 4096 (equal), then `tools/raycast_time.py --model … --instrument … --map --odometry --map-rows 2` at N = 4096 and N = 64 and `tools/vision_train_time.py --memory` in five alternating pairs each and one `bench.py` pair, with the parent's run-to-run spread, the host time of `update()` with no-op launches and the code lines of the five files", "7.17"),
               "depth_encoder_time.json": ('`tools/depth_encoder_time.py`, N = 4096, 64 × 48 camera, 2 frames, the default network: `lsim_depth_encode` with every env due and at period 5 staggered, the torch forward on the same device, `lsim_sensor_capture` and kernel A in one process', "7.8"),
               "depth_memory_time.json": ('`tools/depth_memory_time.py`, N = 4096, L = 64, P = 45, H = 64: `lsim_depth_memory_step` next to kernel A and the staggered encoder launch; `sequence_device` forward + backward, the two serial kernels alone and the `nn.GRUCell` loop at T = 99, n = 1024 / 4096, alternating samples in one process', "7.12"),
               "eval_time.json": ('`tools/eval_time.py`, N = 4096, 400 groups: `lsim_eval_accumulate` next to the env step, kernel A and the torch statements it replaces, HIP events', "7.5"),

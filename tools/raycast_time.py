@@ -74,7 +74,7 @@ def timed(fn, iters, warmup):
 def counters(sensor, count_lib):
     """(cells, triangles) per ray of one launch through the counters build, on the sensor's own struct"""
     sensor.state.zero_()
-    lib.check(count_lib.lsim_raycast(ctypes.byref(sensor._rc), sensor.env._stream()), what="lsim_raycast (counters build)")
+    lib.check(count_lib.lsim_raycast(ctypes.byref(sensor.ray_struct), sensor.env._stream()), what="lsim_raycast (counters build)")
     torch.cuda.synchronize()
     st = sensor.state.cpu().tolist()
     rays = sensor.num_rays * ((sensor.env.num_envs + sensor.env_stride - 1) // sensor.env_stride)
@@ -85,7 +85,7 @@ def counters(sensor, count_lib):
 def counters_bodies(sensor, count_lib):
     """(primitives past the bounding test, cells, triangles) per ray of one lsim_raycast_bodies launch through the counters build"""
     sensor.state.zero_()
-    lib.check(count_lib.lsim_raycast_bodies(ctypes.byref(sensor._rb), sensor.env._stream()), what="lsim_raycast_bodies (counters build)")
+    lib.check(count_lib.lsim_raycast_bodies(ctypes.byref(sensor.bodies_struct), sensor.env._stream()), what="lsim_raycast_bodies (counters build)")
     torch.cuda.synchronize()
     st = sensor.state.cpu().tolist()
     rays = sensor.num_rays * sensor.env.num_envs
@@ -98,12 +98,13 @@ def parse_model(text):
     return sensors.parse_option(sensors.SensorModel, text)
 
 
-def timed_ticks(sensor, iters, warmup):
-    """`timed` over launches whose tick advances by one each"""
+def timed_ticks(what, iters, warmup, flags=0):
+    """`timed` over launches whose tick advances by one each: `what` is a sensor (its update()) or one stage of its chain (that launch alone)"""
+    run = what.launch if isinstance(what, sensors.Stage) else lambda tick, flags: what.update(tick=tick, flags=flags)
     tick = [0]
 
     def fn():
-        sensor.update(tick=tick[0])
+        run(tick[0], flags)
         tick[0] += 1
     return timed(fn, iters, warmup)
 
@@ -126,11 +127,7 @@ def measure_mount_jitter(n, terrain, iters, warmup, model, jitter, repeats):
     jittered.refresh(tick=0)                    # draws every env's mount once
     out = {"num_envs": n, "terrain": terrain, "resetting_envs": int((env.episode_length_buf == 0).sum().item()),
            "mount_offset_max_m": float((jittered.mount[:, :3] - jittered.mount_nominal[:, :3]).abs().max().item())}
-    mj, L = jittered._mj, env._L
-
-    def launch(flags):
-        mj.tick, mj.flags = 0, flags
-        lib.check(L.lsim_sensor_mount_jitter(ctypes.byref(mj), env._stream()), what="lsim_sensor_mount_jitter")
+    launch = lambda flags: jittered.stage("mount_jitter").launch(0, flags)
     fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
     whole = max(model.period, iters // model.period * model.period)
     rows = {"jitter_all_fresh_us": [], "jitter_none_fresh_us": [], "camera_model_us": [], "camera_model_jittered_us": [], "camera_model_update_with_jitter_us": []}
@@ -138,9 +135,7 @@ def measure_mount_jitter(n, terrain, iters, warmup, model, jitter, repeats):
         rows["jitter_all_fresh_us"].append(timed(lambda: launch(fill_all), iters, warmup))
         rows["jitter_none_fresh_us"].append(timed(lambda: launch(0), iters, warmup))
         rows["camera_model_us"].append(timed_ticks(nominal, whole, warmup))
-        jittered._mj = None                     # the capture alone, reading the mounts drawn above
-        rows["camera_model_jittered_us"].append(timed_ticks(jittered, whole, warmup))
-        jittered._mj = mj
+        rows["camera_model_jittered_us"].append(timed_ticks(jittered.stage("capture"), whole, warmup))     # the capture alone, reading the mounts drawn above
         rows["camera_model_update_with_jitter_us"].append(timed_ticks(jittered, whole, warmup))
     for k, v in rows.items():
         out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
@@ -164,24 +159,14 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
     cam.refresh(tick=0)
     cam.attach_map(emap)
-    em = cam._em
+    em = cam.stage("map").struct
     whole = max(model.period, iters // model.period * model.period)
     fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
-
-    def map_ticks(flags):
-        tick = [0]
-
-        def fn():
-            cam._launch_map(tick[0], flags, None)
-            tick[0] += 1
-        return timed(fn, whole, warmup)
     rows = {"capture_us": [], "map_us": [], "map_all_due_us": [], "update_with_map_us": []}
     for _ in range(repeats):
-        cam._em = None                          # the capture alone
-        rows["capture_us"].append(timed_ticks(cam, whole, warmup))
-        cam._em = em
-        rows["map_us"].append(map_ticks(0))
-        rows["map_all_due_us"].append(map_ticks(fill_all))
+        rows["capture_us"].append(timed_ticks(cam.stage("capture"), whole, warmup))      # the capture alone
+        rows["map_us"].append(timed_ticks(cam.stage("map"), whole, warmup))
+        rows["map_all_due_us"].append(timed_ticks(cam.stage("map"), whole, warmup, fill_all))
         rows["update_with_map_us"].append(timed_ticks(cam, whole, warmup))
     out = {"num_envs": n, "terrain": terrain, "rays": cam.num_rays, "scan_points": int(em.num_points), "size": int(em.size),
            "coverage": float(cam.map_known().float().mean().item()), "cells_known": float((cam.map_state()[1] >= 0).float().mean().item())}
@@ -208,21 +193,12 @@ def measure_map_policy(n, terrain, iters, warmup, model, emap, odometry, channel
     cam.refresh(tick=0)
     cam.attach_map(emap, odometry=odometry)
     cam.attach_map_rows(("height", "known")[:channels])
-    L, P = env._L, int(cam._em.num_points)
+    P = int(cam.stage("map").struct.num_points)
     whole = max(model.period, iters // model.period * model.period)
     rows_buf, scan, known, scale = cam.map_rows(), cam.map_scan(), cam.map_known(), float(env.lcfg.obs_scale_height)
     pose_z = cam.map_pose()[:, 2:3]
 
-    def odometry_ticks():
-        tick = [0]
-
-        def fn():
-            cam._launch_odometry(tick[0], 0, None)
-            tick[0] += 1
-        return timed(fn, whole, warmup)
-
-    def rows_launch():
-        lib.check(L.lsim_map_rows(ctypes.byref(cam._mr), env._stream()), what="lsim_map_rows")
+    rows_launch = lambda: cam.stage("map_rows").launch(0, 0)
 
     def rows_torch():
         torch.mul(torch.clamp(pose_z - 0.5 - scan, -1.0, 1.0), scale, out=rows_buf[:, :P])
@@ -235,13 +211,10 @@ def measure_map_policy(n, terrain, iters, warmup, model, emap, odometry, channel
     rows = {"capture_us": [], "map_rows_us": [], "map_rows_torch_us": [], "update_us": []}
     if odometry is not None:
         rows["odometry_us"] = []
-    em, od, mr = cam._em, cam._od, cam._mr
     for _ in range(repeats):
-        cam._em = cam._od = None                # the capture alone
-        rows["capture_us"].append(timed_ticks(cam, whole, warmup))
-        cam._em, cam._od = em, od
+        rows["capture_us"].append(timed_ticks(cam.stage("capture"), whole, warmup))      # the capture alone
         if odometry is not None:
-            rows["odometry_us"].append(odometry_ticks())
+            rows["odometry_us"].append(timed_ticks(cam.stage("odometry"), whole, warmup))
         rows["map_rows_us"].append(timed(rows_launch, whole, warmup))
         rows["map_rows_torch_us"].append(timed(rows_torch, whole, warmup))
         rows["update_us"].append(timed_ticks(cam, whole, warmup))
@@ -271,7 +244,7 @@ def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
               "lidar": (lambda **kw: sensors.lidar(env, 16, 30.0, 360, mount_pos=(0.0, 0.0, 0.15), near=0.05, far=10.0, see_robot=True, labels=True,
                                                    model=model, **kw), no_fov)}
     out = {"num_envs": n, "terrain": terrain, "resetting_envs": int((env.episode_length_buf == 0).sum().item())}
-    L, fill_all = env._L, abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+    fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
     whole = max(model.period, iters // model.period * model.period)
     rows, nonfinite = {}, 0
     sensors_ = {}
@@ -279,29 +252,16 @@ def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
         plain, neutral, drawn = make(), make(instrument=inst), make(instrument=inst)
         for s_ in (plain, neutral, drawn):
             s_.refresh(tick=0)                  # `drawn`: draws every env's row once
-        neutral._inst.zero_()                   # back to the neutral rows {latency, 1, 0, 0, 1, 0, 0, 0}
-        neutral._inst[:, 0], neutral._inst[:, 1], neutral._inst[:, 4] = float(model.latency), 1.0, 1.0
-        sensors_[name] = (plain, neutral, drawn, drawn._si)
+        rows_ = neutral.instrument_rows().zero_()       # back to the neutral rows {latency, 1, 0, 0, 1, 0, 0, 0}
+        rows_[:, 0], rows_[:, 1], rows_[:, 4] = float(model.latency), 1.0, 1.0
+        sensors_[name] = (plain, neutral, drawn)
         for k in ("capture", "inst_neutral", "inst_drawn"):
             rows[f"{name}_{k}_us"] = []
     rows["draw_all_fresh_us"], rows["draw_none_fresh_us"] = [], []
-    si = sensors_["camera"][3]
-
-    def draw(flags):
-        si.tick, si.flags = 0, flags
-        lib.check(L.lsim_sensor_instrument(ctypes.byref(si), env._stream()), what="lsim_sensor_instrument")
-
-    def capture_only(sensor):
-        """update() without the draw launch: lsim_sensor_capture_inst on the rows as they are"""
-        tick = [0]
-
-        def fn():
-            sensor._sm.tick, sensor._sm.flags = tick[0], 0
-            lib.check(L.lsim_sensor_capture_inst(ctypes.byref(sensor._sm), sensor._inst.data_ptr(), env._stream()), what="lsim_sensor_capture_inst")
-            tick[0] += 1
-        return timed(fn, whole, warmup)
+    draw = lambda flags: sensors_["camera"][2].stage("instrument").launch(0, flags)
+    capture_only = lambda sensor: timed_ticks(sensor.stage("capture"), whole, warmup)     # lsim_sensor_capture_inst on the rows as they are, no draw
     for _ in range(repeats):                    # the draw at tick 0 rewrites the rows refresh(tick=0) drew: the same bits
-        for name, (plain, neutral, drawn, _) in sensors_.items():
+        for name, (plain, neutral, drawn) in sensors_.items():
             rows[f"{name}_capture_us"].append(timed_ticks(plain, whole, warmup))
             rows[f"{name}_inst_neutral_us"].append(capture_only(neutral))
             rows[f"{name}_inst_drawn_us"].append(capture_only(drawn))
@@ -309,7 +269,7 @@ def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
         rows["draw_none_fresh_us"].append(timed(lambda: draw(0), iters, warmup))
     for k, v in rows.items():
         out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
-    for name, (plain, neutral, drawn, _) in sensors_.items():
+    for name, (plain, neutral, drawn) in sensors_.items():
         out[f"{name}_neutral_over_capture"] = out[f"{name}_inst_neutral_us"] / out[f"{name}_capture_us"]
         out[f"{name}_drawn_over_capture"] = out[f"{name}_inst_drawn_us"] / out[f"{name}_capture_us"]
         nonfinite += sum(int(s_.nonfinite_rays.item()) for s_ in (plain, neutral, drawn))
