@@ -51,7 +51,9 @@ extern "C" {
                                     depth-scale error and field of view redrawn per episode, and the capture that reads them);
                                     lsim_elevation_map (a robot-centred height grid per env, fused from a sensor's depth rows and the robot's pose);
                                     lsim_odometry_step + LSIM_RNG_ODOMETRY (an estimated base pose that drifts with the distance travelled) and
-                                    lsim_map_rows (the map's scan as the rows an actor reads, one launch) */
+                                    lsim_map_rows (the map's scan as the rows an actor reads, one launch);
+                                    lsim_sensor_frames_log (the images a rollout's captures produced, logged once each, behind the capture) and
+                                    lsim_latent_rows_grad (a minibatch's latent gradients summed per logged image) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1518,6 +1520,85 @@ int lsim_depth_encode_sizes(const lsim_depth_encoder_t* de, size_t* lds_bytes);
  * outside 0..1; latent_stride < latent_dim or not a multiple of 4; the LDS bytes above the limit; tick < 0; period < 1; stagger outside 0..1;
  * a flag bit other than the sensor model's two; both of them set. */
 int lsim_depth_encode(const lsim_depth_encoder_t* de, void* stream);
+
+/* ---- frame log: the images a rollout's captures produced, each logged ONCE, so that the update can encode them again under autograd (the PPO
+ * gradient into the encoder, isaacgymloco_amd/learn/vision.py).  Launched behind the sensor's capture with its tick and flags; same rules as
+ * lsim_depth_encode: the caller's stream, no host synchronisation, raw pointers only, capturable in a graph.  TWO launches per call (the rows
+ * are assigned by the first and copied by the second).  It reads hist, episode_length, row_of[step - 1] and state, and writes log, row_of[step],
+ * row_src and state; nothing else.
+ *
+ * Input.  hist, hist_stride, hist_slots, episode_length, tick, period, stagger, flags, num_envs, env_stride: exactly lsim_depth_encode's, and
+ *   the due rule is that launch's:  fill = (flags & LSIM_SENSOR_FILL_ALL) || episode_length[e] == 0;
+ *     due = fill || ( !(flags & LSIM_SENSOR_RESETS_ONLY) && (tick + (stagger ? e : 0)) % period == 0 ).
+ *   `pixels` = height * width floats of each of the first `frames` slots are an env's image.  `step` in 0 .. num_steps - 1 is the storage row
+ *   whose latent this capture produces: the chain run behind env step s - 1 belongs to row s, the one that starts a rollout to row 0.
+ * Output.  log [capacity, frames, row_stride]: row_stride a multiple of 4, >= pixels, so lsim_depth_encode and its backward read log in place
+ *   as a batch with hist = log, hist_slots = frames, hist_stride = row_stride.  row_of [num_steps, N]: the row of log that holds the image env e
+ *   showed the encoder for storage row t, or -1.  row_src [capacity]: the (t, e) that wrote a row, as t * N + e.  state: int32 words,
+ *   [LSIM_FRAMES_LOG_COUNT] the rows in use, [LSIM_FRAMES_LOG_OVERFLOW] the images that found no room since the caller last zeroed it,
+ *   [LSIM_FRAMES_LOG_BASE], [LSIM_FRAMES_LOG_NEXT] the range of rows the last call wrote (what its second launch reads).  The caller zeroes
+ *   state once at creation.
+ * Rules.  With LSIM_SENSOR_FILL_ALL -- the start of a rollout, step 0 -- count is first taken as 0 and every visited env (e % env_stride == 0)
+ *   is LOGGED; otherwise the visited envs that are due are.  A logged env e gets
+ *       row = count_before + (the number of logged envs of this call with an index < e):
+ *   a function of the inputs alone, no atomic on a shared counter.  If row < capacity: log[row][f][0 .. pixels) = hist[(e * hist_slots + f) *
+ *   hist_stride + 0 .. pixels) for f < frames, log[row][f][pixels .. row_stride) = 0, row_of[step][e] = row, row_src[row] = step * N + e.
+ *   Otherwise row_of[step][e] = -1 and overflow grows by one.  count grows by the number of rows written.
+ *   A visited env that is not logged gets row_of[step][e] = row_of[step - 1][e] -- except in a LSIM_SENSOR_RESETS_ONLY call (a reset by hand in
+ *   the middle of a step), which leaves its entry as it is.  An env that is not visited gets row_of[step][e] = -1.
+ *   Rows of log and row_src at or above count are never written. */
+#define LSIM_FRAMES_LOG_COUNT 0
+#define LSIM_FRAMES_LOG_OVERFLOW 1
+#define LSIM_FRAMES_LOG_BASE 2
+#define LSIM_FRAMES_LOG_NEXT 3
+#define LSIM_FRAMES_LOG_STATE_WORDS 4
+typedef struct lsim_frames_log {
+    const float* hist;                /* [N, hist_slots, hist_stride]: lsim_sensor_model_t.hist, read only, 16-byte aligned */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    float* log;                       /* [capacity, frames, row_stride], 16-byte aligned */
+    int32_t* row_of;                  /* [num_steps, N], 4-byte aligned like the next two */
+    int32_t* row_src;                 /* [capacity] */
+    int32_t* state;                   /* [LSIM_FRAMES_LOG_STATE_WORDS] */
+    int64_t tick;                     /* >= 0, by value: the tick of the sensor's capture */
+    int32_t hist_stride, hist_slots;  /* as in lsim_depth_encoder_t: >= pixels and a multiple of 4; frames <= hist_slots <= LSIM_SENSOR_MAX_HISTORY */
+    int32_t num_envs, env_stride;     /* >= 1 */
+    int32_t frames, pixels;           /* >= 1 */
+    int32_t row_stride;               /* floats between the frames of log: >= pixels, a multiple of 4 */
+    int32_t step, num_steps;          /* 0 <= step < num_steps, by value; num_steps * num_envs < 2^31 */
+    int32_t capacity;                 /* rows of log and row_src: >= 1 */
+    int32_t period, stagger;          /* as lsim_sensor_model_t's */
+    uint32_t flags;                   /* 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+} lsim_frames_log_t;
+/* the call described above.  LSIM_E_INVALID, checked on the host before any launch (nothing is written): fl == NULL; hist or log NULL or not
+ * 16-byte aligned; episode_length NULL or not 8-byte aligned; row_of, row_src or state NULL or not 4-byte aligned; num_envs, env_stride, frames
+ * or pixels < 1; frames > hist_slots; hist_slots > LSIM_SENSOR_MAX_HISTORY; pixels > hist_stride; hist_stride not a multiple of 4;
+ * row_stride < pixels or not a multiple of 4; num_steps < 1; step outside 0 .. num_steps - 1; step == 0 without LSIM_SENSOR_FILL_ALL;
+ * capacity < 1; num_steps * num_envs >= 2^31; tick < 0; period < 1; stagger outside 0..1; a flag bit other than the sensor model's two; both
+ * of them set. */
+int lsim_sensor_frames_log(const lsim_frames_log_t* fl, void* stream);
+
+/* ---- gradient rows: d loss / d latent of a minibatch's transitions summed per logged image, the input of lsim_depth_encode_backward over
+ * log[0 .. R).  ONE launch under the same rules.  With row_of, row_src as the frame log wrote them and mb_of[t * N + e] the position of
+ * transition (t, e) in the minibatch (its row of g), or -1: for r < rows, (t0, e) = (row_src[r] / N, row_src[r] % N),
+ *     G[r * G_stride + j] = sum of g[mb_of[t * N + e] * g_stride + j]  over t = t0, t0 + 1, ...  while t < num_steps and row_of[t][e] == r,
+ *   for j < latent_dim, terms with mb_of < 0 (or >= batch) skipped: an fp32 sum in ascending t from 0.0f, so two calls with the same inputs
+ *   write the same bits.  G is WRITTEN, not accumulated; a row no transition of the minibatch reads is zeros, and so is one whose row_src lies
+ *   outside 0 .. num_steps * N - 1.  Columns >= latent_dim and rows >= `rows` of G are not touched.  It reads g, mb_of, row_of and row_src. */
+typedef struct lsim_latent_rows_grad {
+    const float* g;                   /* [batch, g_stride], 4-byte aligned like every pointer here */
+    const int32_t* mb_of;             /* [num_steps * N] */
+    const int32_t* row_of;            /* [num_steps, N] */
+    const int32_t* row_src;           /* [>= rows] */
+    float* G;                         /* [rows, G_stride] */
+    int32_t batch;                    /* B >= 1 */
+    int32_t rows;                     /* R >= 0, by value (0: nothing is launched) */
+    int32_t latent_dim;               /* >= 1 */
+    int32_t g_stride, G_stride;       /* floats between rows: >= latent_dim */
+    int32_t num_steps, num_envs;      /* >= 1; num_steps * num_envs < 2^31 */
+} lsim_latent_rows_grad_t;
+/* LSIM_E_INVALID, checked on the host before any launch (nothing is written): lg == NULL; a pointer NULL or not 4-byte aligned; batch < 1;
+ * rows < 0; latent_dim < 1; g_stride or G_stride < latent_dim; num_steps or num_envs < 1; num_steps * num_envs >= 2^31. */
+int lsim_latent_rows_grad(const lsim_latent_rows_grad_t* lg, void* stream);
 
 /* ---- depth encoder, BACKWARD: the gradients of the six parameters from the gradient of `latent`, for a batch of images.  Same rules as every
  * launch here: the caller's stream, no host synchronisation, raw pointers only, capturable in a graph.  THREE launches per call, whatever the

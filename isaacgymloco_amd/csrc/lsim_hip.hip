@@ -33,6 +33,7 @@ static void lsbk_prof_free(lsim_sim* s);
 #include "ls_depth_encoder.h"    // the depth encoder (lsim_depth_encode): conv - conv - linear over that frame history for the envs that are due, activations in LDS
 #include "ls_depth_encoder_bwd.h"    // its backward pass (lsim_depth_encode_backward): the parameter gradients, activations recomputed per sample in LDS
 #include "ls_depth_memory.h"    // the depth memory (lsim_depth_memory_step, lsim_gru_sequence_forward / _backward): a GRU cell over the latent, one tile of 16 envs per workgroup
+#include "ls_frames_log.h"      // the PPO gradient into the encoder: the images of a rollout logged once each (lsim_sensor_frames_log) and a minibatch's latent gradients summed per image (lsim_latent_rows_grad)
 
 // Each XCD (8 per chip, block b is dispatched to XCD b % 8) works on its own slices of the env range, so a
 // robot's state lines stay in one XCD's L2 and neighbouring robots do not false-share lines across XCD L2s.

@@ -60,6 +60,12 @@ small launch ahead of every capture integrates the step each env took since the 
 where it read root_states, and the capture itself goes on reading the true pose: the camera is where the robot is.  Without `odometry`
 nothing of this is created or launched and the map reads root_states.
 
+Frame log (`cam.attach_frames_log(steps)`, lsim_sensor_frames_log; needs an encoder): what a PPO gradient into the encoder trains on
+(learn/vision.py, end_to_end=True) -- every image a rollout's captures showed the encoder, kept ONCE: one launch behind the capture copies
+the frames of the envs just captured into `frames_log()` and writes, per rollout step and env, which row of the log holds the image its
+latent came from (`frame_rows()`).  It launches only while a rollout drives it (begin_rollout(), set_frames_log_step()); an evaluation
+rollout or an env.reset() between two rollouts finds it idle.  Without it nothing of this is created or launched.
+
 Map rows (`cam.attach_map_rows(channels=("height", "known"))`, lsim_map_rows; needs a map): one launch behind the map's turns its scan into
 the rows an actor reads -- the heights relative to the pose the map was given, clipped and scaled exactly as the privileged height scan
 is, and optionally which of them the map knows; `cam.map_rows()` is the live [N, channels * P] tensor (learn/map_policy.py).
@@ -290,10 +296,12 @@ def parse_elevation_map(text):
 
 
 _ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "map_rows", "encoder", "memory")      # a chain's launch order
-_DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory",)}                                             # who goes with whom
+_BEHIND = {"frames_log": "capture"}         # a training buffer's stage is no part of the instrument: launched directly behind the stage named
+_LAUNCH_ORDER = tuple(n for o in _ORDER for n in (o,) + tuple(k for k, v in _BEHIND.items() if v == o))
+_DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory", "frames_log")}                                # who goes with whom
 _ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
            "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
-           "memory": "memory (attach_memory)"}
+           "memory": "memory (attach_memory)", "frames_log": "frame log (attach_frames_log)"}
 _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
 
 
@@ -344,6 +352,9 @@ class RaySensor:
     of this is allocated or launched.  `attach_map(m, odometry=OdometryError(...))`: lsim_odometry_step ahead of every capture, and the map
     reads `odometry_pose()` [N, 13] (its state: `odometry_state()` [N, 12]) where it read root_states.  `attach_map_rows(channels)`:
     lsim_map_rows behind the map's launch, `map_rows()` the live [N, channels * P] rows an actor reads.
+    `attach_frames_log(steps)` (needs an encoder): lsim_sensor_frames_log directly behind the capture while a rollout drives it
+    (begin_rollout(), set_frames_log_step()) -- `frames_log()` keeps every image the rollout's captures showed the encoder once,
+    `frame_rows()` [steps, N] says which row each storage row's latent came from.  A training buffer: no part of spec().
     `kind`: the record spec() opens with -- {"kind": "camera", "width", "height"}, {"kind": "lidar", "channels", "points_per_rev"}, None:
     {"kind": "rays"} -- whose numbers are also attributes of the sensor.
 
@@ -479,7 +490,7 @@ class RaySensor:
         cap, inst = self._stages.get("capture"), self._stages.get("instrument")
         if cap is not None:                 # the capture that reads the instrument's rows, or the plain one
             cap.entry, cap.args = ("lsim_sensor_capture", ()) if inst is None else ("lsim_sensor_capture_inst", (inst.buffers["inst"].data_ptr(),))
-        self._chain = tuple(self._stages[n] for n in _ORDER if n in self._stages)
+        self._chain = tuple(self._stages[n] for n in _LAUNCH_ORDER if n in self._stages)
 
     def _kept(self, name, make):
         """the buffers the stage `name` holds already (set again: what was drawn so far stays), else make()"""
@@ -852,6 +863,87 @@ class RaySensor:
         inside = ((ix.abs() < 32768)[:, :, None] & (iy.abs() < 32768)[:, None, :])
         known = (take(mp["stamp"]) >= 0) & ((take(mp["cell"]).to(torch.int64) & 0xFFFFFFFF) == word) & inside
         return torch.where(known, take(mp["height"]), torch.full((), float("nan"), device=c.device))
+
+    def attach_frames_log(self, steps, capacity=None, row_of=None):
+        """the stage "frames_log", directly behind the capture: while a rollout of `steps` storage rows drives it, every update() is
+        followed by lsim_sensor_frames_log on the same stream with the same tick and flags, which copies the image (slots 0 .. frames - 1
+        of the history) of every env just captured into the next rows of the log and records in row `step` of frame_rows() which row of
+        the log each env's latent of that storage row came from.  `capacity`: rows of the log; default N * (1 + ceil((steps - 1) /
+        period) + 2) -- the start of the rollout, every tick-due capture, and room for two resets per env per rollout; an image that
+        finds no room gets row -1 and counts in frames_log_state()[1].  `row_of`: a contiguous int32 [steps, N] tensor on the sensor's
+        device to use as frame_rows() (a rollout storage's own field); default: one of the stage's.  The stage owns its buffers and
+        goes with the encoder.  It needs env_stride == 1 and an attached encoder, else ValueError.  None: detach and free.
+        Driving it: begin_rollout() logs every env's present image as storage row 0; set_frames_log_step(s) names the row the NEXT
+        capture belongs to (the chain run behind env step s - 1 produces the latent of row s), None or s >= steps: idle."""
+        if steps is None:
+            return self._drop("frames_log")
+        if self.model is None or self.encoder is None:
+            raise ValueError("attach_frames_log: the sensor has no encoder (attach_encoder first): the log keeps the images the encoder reads")
+        if self.env_stride != 1:
+            raise ValueError(f"attach_frames_log: env_stride is {self.env_stride}; the log's rows are those of a rollout storage, which holds every env")
+        lib.entry(self._api, "lsim_sensor_frames_log", "the frame log")
+        steps, N, hist = int(steps), int(self.env.num_envs), self.history()
+        if steps < 1:
+            raise ValueError(f"attach_frames_log: steps >= 1, got {steps}")
+        capacity = N * (1 + -(-(steps - 1) // self.model.period) + 2) if capacity is None else int(capacity)
+        if capacity < 1:
+            raise ValueError(f"attach_frames_log: capacity >= 1, got {capacity}")
+        if row_of is None:
+            row_of = self._zeros(steps, N, dtype=torch.int32).fill_(-1)
+        elif not (row_of.dtype == torch.int32 and tuple(row_of.shape) == (steps, N) and row_of.is_contiguous() and row_of.device == hist.device):
+            raise ValueError(f"attach_frames_log: row_of must be a contiguous int32 [{steps}, {N}] tensor on {hist.device}")
+        F, stride = self.model.frames, hist.shape[2]
+        held = {"log": self._zeros(capacity, F, stride), "row_of": row_of, "row_src": self._zeros(capacity, dtype=torch.int32).fill_(-1),
+                "state": self._zeros(abi.DEFINES["LSIM_FRAMES_LOG_STATE_WORDS"], dtype=torch.int32)}
+        fl = abi.LsimFramesLog()
+        fl.hist, fl.hist_stride, fl.hist_slots = hist.data_ptr(), stride, hist.shape[1]
+        fl.log, fl.row_of, fl.row_src, fl.state = (held[k].data_ptr() for k in ("log", "row_of", "row_src", "state"))
+        fl.frames, fl.pixels, fl.row_stride, fl.num_steps, fl.capacity = F, self.num_rays, stride, steps, capacity
+        fl.period, fl.stagger = self.model.period, int(self.model.stagger)
+
+        def run(tick, flags, stream):
+            if stage.step is None:                      # no rollout drives the log: an evaluation rollout, env.reset(), refresh()
+                return
+            if flags & _FILL_ALL and stage.step != 0:
+                raise RuntimeError("the frame log is in the middle of a rollout (storage row %d): refresh() would start its rows again" % stage.step)
+            fl.tick, fl.flags, fl.step = tick, flags, stage.step
+            lib.check(self._api.lsim_sensor_frames_log(ctypes.byref(fl), self._stream(stream)), what="lsim_sensor_frames_log")
+        stage = self._attach(Stage(self, "frames_log", "lsim_sensor_frames_log", fl, held, (steps, capacity), run=run))
+        stage.step = None
+        return stage
+
+    def begin_rollout(self, stream=None):
+        """the start of a rollout: ONE launch of the frame log with LSIM_SENSOR_FILL_ALL and storage row 0 -- the log starts again and
+        every env's present image, the one its latent row was encoded from, becomes a row.  The stage then waits for row 1"""
+        stage = self._need("frames_log")
+        stage.step = 0
+        try:
+            stage.launch(max(self.tick, 0), _FILL_ALL, stream)
+        finally:
+            stage.step = None
+        self.set_frames_log_step(1)
+
+    def set_frames_log_step(self, step):
+        """the storage row the next capture's images belong to; None, or a row the rollout does not have: the stage is idle"""
+        stage = self._need("frames_log")
+        stage.step = None if step is None or not 0 < int(step) < stage.option[0] else int(step)
+
+    def frames_log(self):
+        """live [capacity, frames, stride] tensor: the logged images, rows 0 .. frames_log_state()[0] - 1 in use; lsim_depth_encode reads
+        it in place as a batch (hist_slots = frames)"""
+        return self._need("frames_log").buffers["log"]
+
+    def frame_rows(self):
+        """live int32 [steps, N] tensor: the row of frames_log() that holds the image env e's latent of storage row t came from, or -1"""
+        return self._need("frames_log").buffers["row_of"]
+
+    def frames_log_sources(self):
+        """live int32 [capacity] tensor: t * N + e of the storage row and env that wrote each row of the log"""
+        return self._need("frames_log").buffers["row_src"]
+
+    def frames_log_state(self):
+        """live int32 tensor: [0] the rows in use, [1] the images that found no room (never reset by the launch), then the launch's own words"""
+        return self._need("frames_log").buffers["state"]
 
     def attach_memory(self, mem):
         """from now on the encoder's launch of every update() / refresh() is followed by `mem`'s (learn.depth_memory.DepthMemory.step_device)

@@ -194,3 +194,19 @@ class DepthEncoder(nn.Module):
                 hist = torch.zeros(frames.shape[0], self.frames, stride, device=dev, dtype=torch.float32)
                 hist[:, :, :R] = frames.reshape(frames.shape[0], self.frames, R)
             return _DepthEncodeFn.apply(self, api, hist, stride, *params)
+
+    def forward_device_rows(self, rows, api=None):
+        """forward_device over images that already lie as the launch reads them -- [B >= 1, frames, stride] fp32, contiguous, 16-byte
+        aligned, stride >= height * width a multiple of 4 (a sensor's frame log) -- read in place whatever height * width is"""
+        api = api if api is not None else lib.load()
+        for name in ("lsim_depth_encode", "lsim_depth_encode_backward_sizes", "lsim_depth_encode_backward"):
+            lib.entry(api, name, "the depth encoder")
+        params = self.device_params()
+        dev = params[0].device
+        ok = (rows.dim() == 3 and rows.shape[0] >= 1 and rows.shape[1] == self.frames and rows.shape[2] >= self.height * self.width and rows.shape[2] % 4 == 0
+              and rows.dtype == torch.float32 and rows.device == dev and rows.is_contiguous() and rows.data_ptr() % 16 == 0 and not rows.requires_grad)
+        if not ok:
+            raise ValueError(f"forward_device_rows: rows must be contiguous, 16-byte aligned fp32 [B >= 1, {self.frames}, stride] on {dev} without "
+                             f"a gradient, stride >= {self.height * self.width} a multiple of 4, got {tuple(rows.shape)} {rows.dtype} on {rows.device}")
+        check_params("forward_device_rows", _PARAM_NAMES, params, dev)
+        return _DepthEncodeFn.apply(self, api, rows, rows.shape[2], *params)

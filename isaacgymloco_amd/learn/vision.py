@@ -8,8 +8,12 @@ the PPO update.
 
 Three decisions bound the memory and the code:
   1. The actor reads the latent DETACHED, as it reads the estimator's output (HAC:136-141): the rollout stores, per transition, the row the
-     actor saw ([T, N, L] floats; the frames would be [T, N, frames, H, W]) and the update feeds that row back.  No PPO gradient reaches
-     the encoder.
+     actor saw ([T, N, L] floats; the frames would be [T, N, frames, H, W]) and the update feeds that row back.  By default no PPO gradient
+     reaches the encoder.  `end_to_end=True` adds one: the sensor logs every image a capture of the rollout showed
+     the encoder ONCE (envs/sensors.py, attach_frames_log: with a period-5 camera a fifth of the transitions), the storage keeps per
+     transition the row of that log (frame_row), and in the first `e2e_epochs` epochs of the update every minibatch encodes the logged
+     images again under autograd, the actor reads those rows, and lsim_latent_rows_grad sums the minibatch's latent gradients per image
+     for the encoder's backward.  The encoder then takes an Adam step of its own behind the minibatch's PPO step.
   2. The encoder is trained by an auxiliary regression of its own: frames -> latent -> linear head -> the height scan the critic already
      receives as privileged information, on a few snapshots of one rollout, with its own Adam.  Encoder, head and that optimiser belong to
      VisionPPO, not to the actor-critic: HIMPPO.optimizer, the GradArena buckets and the fused clip + Adam step see the parameters they
@@ -59,16 +63,17 @@ class VisionActorCritic(HIMActorCritic):
             raise ValueError("VisionActorCritic: depth_latent_dim >= 1")
         self.num_him_actor_inputs = self.actor[0].in_features
         self.actor = mlp([self.num_him_actor_inputs + self.depth_latent_dim, *actor_hidden_dims, num_actions], get_activation(activation))
-        self._bound_latent = None
+        self._bound_latent, self._latent_live = None, False
 
     @contextlib.contextmanager
-    def bound_latent(self, rows):
-        """inside the block the actor reads `rows` [B, L] wherever no latent is passed (one minibatch of the update)"""
-        prev, self._bound_latent = self._bound_latent, rows
+    def bound_latent(self, rows, live=False):
+        """inside the block the actor reads `rows` [B, L] wherever no latent is passed (one minibatch of the update).  `live`: the rows
+        keep their autograd history, so a loss on the actor's output reaches whatever produced them (the end-to-end update)"""
+        prev, self._bound_latent, self._latent_live = (self._bound_latent, self._latent_live), rows, bool(live)
         try:
             yield self
         finally:
-            self._bound_latent = prev
+            self._bound_latent, self._latent_live = prev
 
     def _latent_rows(self, depth_latent, batch):
         rows = depth_latent if depth_latent is not None else self._bound_latent
@@ -76,14 +81,14 @@ class VisionActorCritic(HIMActorCritic):
             raise ValueError("VisionActorCritic: no depth latent (pass depth_latent=..., or evaluate inside `with bound_latent(rows):`)")
         if rows.dim() != 2 or rows.shape[0] != batch or rows.shape[1] != self.depth_latent_dim:
             raise ValueError(f"VisionActorCritic: the depth latent must be [{batch}, {self.depth_latent_dim}], got {tuple(rows.shape)}")
-        return rows.detach()
+        return rows if depth_latent is None and self._latent_live else rows.detach()
 
     def _actor_input(self, obs_history, depth_latent=None):
         rows = self._latent_rows(depth_latent, obs_history.shape[0])
         return torch.cat((super()._actor_input(obs_history), rows), dim=-1)
 
     def update_distribution(self, obs_history, depth_latent=None):
-        with self.bound_latent(self._latent_rows(depth_latent, obs_history.shape[0])):
+        with self.bound_latent(self._latent_rows(depth_latent, obs_history.shape[0]), live=self._latent_live):
             super().update_distribution(obs_history)
 
     def act(self, obs_history=None, depth_latent=None, **kwargs):
@@ -131,12 +136,18 @@ class VisionTransition:
 
 class VisionRolloutStorage(HIMRolloutStorage):
     """HIMRolloutStorage + depth_latent [T, N, L]: the row the actor saw at each transition; the minibatch generator yields it as an
-    eleventh field, gathered through the same permutation (and, on the GPU, into a persistent shuffle buffer like the other ten)"""
+    eleventh field, gathered through the same permutation (and, on the GPU, into a persistent shuffle buffer like the other ten).
+    `frame_rows=True` (the end-to-end update): + frame_row [T, N] int32, the row of the sensor's frame log that holds the image the latent
+    came from, or -1 -- the log's own row_of, which the sensor's stage writes in place -- yielded as a twelfth field; `last_perm` is then
+    the permutation of the latest mini_batch_generator (minibatch i holds the transitions last_perm[i * mb : (i + 1) * mb])."""
     Transition = VisionTransition
+    frame_row = last_perm = None
 
-    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, depth_latent_dim, device="cpu"):
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, depth_latent_dim, device="cpu", frame_rows=False):
         super().__init__(num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device)
         self.depth_latent = torch.zeros(num_transitions_per_env, num_envs, int(depth_latent_dim), device=device)
+        if frame_rows:
+            self.frame_row = torch.full((num_transitions_per_env, num_envs), -1, dtype=torch.int32, device=device)
 
     def add_transitions(self, t):
         if self.step >= self.num_transitions_per_env:
@@ -147,7 +158,14 @@ class VisionRolloutStorage(HIMRolloutStorage):
         super().add_transitions(t)
 
     def _extra_fields(self):
-        return (self.depth_latent.flatten(0, 1),)
+        if self.frame_row is None:
+            return (self.depth_latent.flatten(0, 1),)
+        return (self.depth_latent.flatten(0, 1), self.frame_row.flatten(0, 1))
+
+    def _shuffle(self, fields, perm):
+        if self.frame_row is not None:
+            self.last_perm = perm
+        return super()._shuffle(fields, perm)
 
 
 class ActorRowsPPO(HIMPPO):
@@ -165,7 +183,13 @@ class ActorRowsPPO(HIMPPO):
 
     def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
         self.storage = VisionRolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape,
-                                            self.actor_critic.depth_latent_dim, self.device)
+                                            self.actor_critic.depth_latent_dim, self.device, **self._storage_options())
+
+    def _storage_options(self):
+        return {}
+
+    def drive_frame_log(self, step):
+        """called once per rollout step, before the env steps (act(), VisionRollout._act): nothing to drive here"""
 
     def _latent_now(self):
         if self.latent_source is None:
@@ -180,6 +204,7 @@ class ActorRowsPPO(HIMPPO):
 
     def act(self, obs, critic_obs):
         rows = self._latent_now().detach().clone()          # a live sensor buffer: the transition keeps what the actor saw
+        self.drive_frame_log(self.storage.step)
         self.snapshot_if_due(self.storage.step, critic_obs)
         with self.actor_critic.bound_latent(rows):
             actions = super().act(obs, critic_obs)
@@ -191,6 +216,43 @@ class ActorRowsPPO(HIMPPO):
             return super()._mb_forward(ac, batch[:10], two_streams)
 
 
+class _LatentJoinFn(torch.autograd.Function):
+    """The rows a minibatch's actor reads in an end-to-end epoch: column j < L of row i is z_live[frame_row[i]][j] where frame_row[i] >= 0,
+    else stored[i][j]; the columns from L on (a memory's hidden state) are stored[i]'s and stay data.  Backward: G [R, L], the gradient of
+    z_live, is lsim_latent_rows_grad over the minibatch's gradient rows on the device -- one fixed-order sum per logged image -- and the
+    index_add_ of the same terms elsewhere.  `mb_of`, `row_of`, `row_src`: as in include/lsim.h."""
+
+    @staticmethod
+    def forward(ctx, z_live, stored, frame_row, mb_of, row_of, row_src):
+        L = z_live.shape[1]
+        frame_row = frame_row.reshape(-1)
+        logged = frame_row >= 0
+        z = torch.where(logged.unsqueeze(1), z_live.index_select(0, frame_row.clamp_min(0).long()), stored[:, :L].to(z_live.dtype))
+        ctx.save_for_backward(frame_row, mb_of, row_of, row_src)
+        ctx.shape = tuple(z_live.shape)
+        return z if stored.shape[1] == L else torch.cat((z, stored[:, L:].to(z.dtype)), dim=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        frame_row, mb_of, row_of, row_src = ctx.saved_tensors
+        R, L = ctx.shape
+        if not (g.is_cuda and g.dtype == torch.float32):
+            logged = frame_row >= 0
+            G = torch.zeros(R, L, dtype=g.dtype, device=g.device)
+            G.index_add_(0, frame_row[logged].long(), g[logged][:, :L])
+            return G, None, None, None, None, None
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        G = torch.empty(R, (L + 3) // 4 * 4, device=g.device, dtype=torch.float32)
+        lg = abi.LsimLatentRowsGrad()
+        lg.g, lg.mb_of, lg.row_of, lg.row_src, lg.G = g.data_ptr(), mb_of.data_ptr(), row_of.data_ptr(), row_src.data_ptr(), G.data_ptr()
+        lg.batch, lg.rows, lg.latent_dim, lg.g_stride, lg.G_stride = g.shape[0], R, L, g.stride(0), G.stride(0)
+        lg.num_steps, lg.num_envs = row_of.shape
+        entry = lib.entry(lib.load(), "lsim_latent_rows_grad", "the end-to-end update")
+        lib.check(entry(ctypes.byref(lg), torch.cuda.current_stream(g.device).cuda_stream), what="lsim_latent_rows_grad")
+        return G[:, :L], None, None, None, None, None
+
+
 class VisionPPO(ActorRowsPPO):
     """ActorRowsPPO whose rows are a depth encoder's latent (the runner passes sensor.latent), with the encoder's own steps behind the
     update: `aux_snapshots` rollout steps, spread evenly over the T steps, each keep a copy of (frames_source(), height scan of the same
@@ -198,9 +260,17 @@ class VisionPPO(ActorRowsPPO):
     Adam(aux_learning_rate) over encoder and head.  update() returns HIMPPO's values plus the mean auxiliary loss."""
 
     def __init__(self, actor_critic, encoder=None, latent_source=None, frames_source=None, height_scan=None, aux_snapshots=4, aux_learning_rate=1e-3,
-                 memory_env_minibatches=4, memory_learning_rate=1e-3, dist_ctx=None, **kwargs):
+                 memory_env_minibatches=4, memory_learning_rate=1e-3, end_to_end=False, e2e_epochs=1, e2e_learning_rate=None, e2e_capacity=None,
+                 dist_ctx=None, **kwargs):
         super().__init__(actor_critic, dist_ctx=dist_ctx, **kwargs)
         self.aux_snapshots, self.aux_learning_rate = int(aux_snapshots), float(aux_learning_rate)
+        # the PPO gradient into the encoder (module docstring, decision 1): off unless the runner was built with end_to_end=True
+        self.end_to_end, self.e2e_epochs = bool(end_to_end), int(e2e_epochs)
+        self.e2e_learning_rate = self.aux_learning_rate if e2e_learning_rate is None else float(e2e_learning_rate)
+        self.e2e_capacity = None if e2e_capacity is None else int(e2e_capacity)
+        self.e2e_optimizer = self.frame_log = None
+        self._e2e_minibatch, self._e2e_rows = None, 0
+        self.last_e2e_overflow = 0
         self.encoder = self.depth_head = self.aux_optimizer = None
         self.frames_source = self.height_scan = None
         self._snap, self._snap_filled = [], []
@@ -230,6 +300,88 @@ class VisionPPO(ActorRowsPPO):
             self.memory = memory.to(self.device)
             self.memory_head = nn.Linear(memory.hidden, self.height_scan[1]).to(self.device)
             self.memory_optimizer = torch.optim.Adam(list(self.memory.parameters()) + list(self.memory_head.parameters()), lr=self.memory_learning_rate)
+        if self.end_to_end:
+            self.e2e_optimizer = torch.optim.Adam(list(self.encoder.parameters()), lr=self.e2e_learning_rate)
+
+    # ---- the PPO gradient into the encoder (end_to_end=True): the sensor's frame log, driven by the rollout and read by the update
+    def _storage_options(self):
+        return {"frame_rows": True} if self.end_to_end else {}
+
+    def attach_frame_log(self, sensor):
+        """`sensor`: the one whose latent the actor reads, with its frame log attached over this storage's frame_row
+        (sensor.attach_frames_log(T, capacity, row_of=storage.frame_row))"""
+        if not self.end_to_end or self.encoder is None:
+            raise RuntimeError("VisionPPO: attach_frame_log needs end_to_end=True and an attached encoder")
+        if sensor.frame_rows().data_ptr() != self.storage.frame_row.data_ptr():
+            raise ValueError("VisionPPO: the sensor's frame log must write the storage's frame_row (attach_frames_log(..., row_of=storage.frame_row))")
+        self.frame_log = sensor
+
+    def drive_frame_log(self, step):
+        """the start of a rollout logs every env's present image as row 0; then the capture behind this step's env step belongs to row
+        step + 1, and after the rollout's last step the stage is idle"""
+        if self.frame_log is None:
+            return
+        if step == 0:
+            self.frame_log.begin_rollout()
+        self.frame_log.set_frames_log_step(step + 1)
+
+    def _sample_stream(self):
+        if self.frame_log is None:
+            if self.end_to_end:
+                raise RuntimeError("VisionPPO: end_to_end=True but no frame log (attach_frame_log(sensor))")
+            yield from super()._sample_stream()
+            return
+        state = self.frame_log.frames_log_state()[:2].tolist()       # the feature's one read-back per update: the rows in use, the images that found no room
+        self._e2e_rows, self.last_e2e_overflow = int(state[0]), int(state[1])
+        if self.last_e2e_overflow:
+            self.frame_log.frames_log_state()[1].zero_()
+        try:
+            for k, item in enumerate(super()._sample_stream()):
+                self._e2e_minibatch = k % self.num_mini_batches if k < self.e2e_epochs * self.num_mini_batches and self._e2e_rows > 0 else None
+                yield item
+        finally:
+            self._e2e_minibatch = None
+
+    def live_latent(self):
+        """the latent of every logged image under the present weights, with autograd to the encoder: [R, L]"""
+        cam, enc, R = self.frame_log, self.encoder, self._e2e_rows
+        log = cam.frames_log()[:R]
+        if next(enc.parameters()).is_cuda:
+            return enc.forward_device_rows(log)
+        frames = log[:, :, :enc.height * enc.width].unflatten(2, (enc.height, enc.width))
+        return enc(frames.to(next(enc.parameters()).dtype))
+
+    def joined_rows(self, stored, frame_row, minibatch):
+        """the rows the actor reads for minibatch `minibatch` of the latest permutation in an end-to-end epoch (_LatentJoinFn): the live
+        latent of the logged images where the transition has a frame row, the stored row elsewhere and in a memory's h columns"""
+        st, cam = self.storage, self.frame_log
+        B = stored.shape[0]
+        picked = st.last_perm[minibatch * B:(minibatch + 1) * B]
+        mb_of = torch.full((st.num_transitions_per_env * st.num_envs,), -1, dtype=torch.int32, device=stored.device)
+        mb_of[picked] = torch.arange(B, dtype=torch.int32, device=stored.device)
+        return _LatentJoinFn.apply(self.live_latent(), stored, frame_row, mb_of, st.frame_row, cam.frames_log_sources())
+
+    def _mb_forward(self, ac, batch, two_streams):
+        if self._e2e_minibatch is None:
+            return super()._mb_forward(ac, batch[:11], two_streams)
+        for p in self.encoder.parameters():                     # whatever the encoder's own step left behind is not this minibatch's
+            p.grad = None
+        rows = self.joined_rows(batch[10], batch[11], self._e2e_minibatch)
+        with ac.bound_latent(rows, live=True):
+            return HIMPPO._mb_forward(self, ac, batch[:10], two_streams)
+
+    def _after_step(self, ac, mb):
+        """behind the minibatch's PPO step of an end-to-end epoch: the encoder's own clipped Adam step on the gradient the PPO backward
+        left, then no gradient -- encoder_step() and memory_step() find the encoder as they always did"""
+        super()._after_step(ac, mb)
+        if self._e2e_minibatch is None:
+            return
+        params = [p for p in self.encoder.parameters() if p.grad is not None]
+        if params:
+            nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+            self.e2e_optimizer.step()
+        for p in self.encoder.parameters():
+            p.grad = None
 
     # ---- the encoder's own training data: a few (frames, target) pairs per rollout
     def snapshot_steps(self):
@@ -385,6 +537,7 @@ class VisionRollout(GraphedRollout):
 
     def _act(self):
         env, ac = self.env, self.alg.actor_critic
+        self.alg.drive_frame_log(self.storage.step)
         self.alg.snapshot_if_due(self.storage.step, env.privileged_obs_buf)
         prev, self._pending_post = self._pending_post, None
         self.packed.forward_act(self._S, self.storage.step, self._draw_host, env.obs_buf, env.privileged_obs_buf, ac.std, self._seed, self._rank,
@@ -411,9 +564,13 @@ class VisionOnPolicyRunner(ActorRowsRunner):
     algorithm["aux_snapshots"] / ["aux_learning_rate"] are optional.  `memory`: True builds DepthMemory(L, env.num_one_step_obs, 64), an
     instance is taken as is; the actor then reads [z | h] (policy["depth_latent_dim"] = L + H, the stored row likewise) and VisionPPO trains
     the cell behind the encoder's step (algorithm["memory_env_minibatches"] / ["memory_learning_rate"] are optional).  Without it nothing
-    is allocated, launched, stored or saved that was not before."""
+    is allocated, launched, stored or saved that was not before.  `end_to_end=True`: the PPO gradient reaches the encoder (module
+    docstring, decision 1) -- the sensor gets a frame log over the storage's frame_row (algorithm["e2e_capacity"] rows, default the
+    stage's), the first algorithm["e2e_epochs"] (default 1) learning epochs carry the gradient and the encoder steps with
+    algorithm["e2e_learning_rate"] (default aux_learning_rate); one rank, and no gradient through the memory.  Without it, likewise,
+    nothing is allocated, launched, stored or saved that was not before."""
 
-    def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None, memory=None):
+    def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None, memory=None, end_to_end=False):
         cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
         if getattr(cam, "model", None) is None:
             raise ValueError("VisionOnPolicyRunner: the sensor has no SensorModel, so no frame history to encode")
@@ -439,6 +596,10 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             self._check_first_layer(env, latent=encoder.latent_dim, hidden=memory.hidden)
         else:
             memory = None
+        if end_to_end:
+            if getattr(cam, "env_stride", 1) != 1:
+                raise ValueError("VisionOnPolicyRunner: end_to_end needs a sensor that renders every env (env_stride == 1)")
+            cfg["algorithm"]["end_to_end"] = True
         self.sensor, self.memory = cam, memory
         super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
         cam.attach_encoder(encoder)         # behind the parent's env.reset(): the sensor has captured, so every env is encoded now
@@ -448,6 +609,9 @@ class VisionOnPolicyRunner(ActorRowsRunner):
         else:
             cam.attach_memory(memory)       # every env steps once from h = 0
             self.alg.attach(encoder, cam.memory_rows, frames, scan, memory=memory)
+        if end_to_end:
+            cam.attach_frames_log(self.num_steps_per_env, capacity=self.alg.e2e_capacity, row_of=self.alg.storage.frame_row)
+            self.alg.attach_frame_log(cam)
 
     def _extra_checkpoint_state(self):
         out = super()._extra_checkpoint_state()
@@ -461,6 +625,10 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             out.update(depth_memory_state_dict=alg.memory.state_dict(), depth_memory_head_state_dict=alg.memory_head.state_dict(),
                        depth_memory_optimizer_state_dict=alg.memory_optimizer.state_dict())
             out["vision"]["memory"] = alg.memory.config()
+        if alg.end_to_end:
+            out["depth_e2e_optimizer_state_dict"] = alg.e2e_optimizer.state_dict()
+            out["vision"]["end_to_end"] = {"epochs": alg.e2e_epochs, "learning_rate": alg.e2e_learning_rate,
+                                           "capacity": int(self.sensor.frames_log().shape[0])}
         return out
 
     def export(self, path):
@@ -480,3 +648,5 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             alg.memory.load_state_dict(d["depth_memory_state_dict"])
             alg.memory_head.load_state_dict(d["depth_memory_head_state_dict"])
             alg.memory_optimizer.load_state_dict(d["depth_memory_optimizer_state_dict"])
+        if alg.end_to_end and "depth_e2e_optimizer_state_dict" in d:
+            alg.e2e_optimizer.load_state_dict(d["depth_e2e_optimizer_state_dict"])
