@@ -670,11 +670,20 @@ int lsim_amp_step(const lsim_amp_disc* d, const float* amp_obs, const float* nex
 
 /* ---- learner-side kernel: weight / bias gradient of a small Linear layer over a tall minibatch,
  *   dw[n, k] = sum_b g[b, n] * x[b, k],   db[n] = sum_b g[b, n]      (torch.nn.Linear backward: grad_weight = g^T x, grad_bias = g.sum(0))
- * for ceil(n_out / 16) * ceil(k_in / 16) <= 32 (each <= 8): the heads and narrow layers of HAC:66-95 / HES:36-54 / DISC:18-25, whose
- * K = 102 400 reductions BLAS runs at a few percent of peak.  x [batch, k_in] with row stride ldx, g [batch, n_out] with row stride ldg
- * (floats), dw [n_out, k_in] and db [n_out] (db may be NULL) contiguous.  `workspace` is a caller-allocated device buffer of at least
- * lsim_linear_wgrad_workspace() bytes holding the per-wave partial results (summed in a fixed order: deterministic).
- * Returns LSIM_E_UNSUPPORTED for larger layers (use BLAS). */
+ * for any batch >= 1 and any layer of k_in * n_out <= 140 000 weights.  Two forms: layers with ceil(n_out / 16) * ceil(k_in / 16) <= 32 (each
+ * <= 8) and k_in * n_out <= 4096 -- the heads and narrow layers of HAC:66-95 / HES:36-54 / DISC:18-25, whose K = 102 400 reductions BLAS runs at
+ * a few percent of peak -- keep the whole result in one wave's accumulators (the single-wave form); every other layer runs as 64 x 64 / 64 x 128
+ * output tiles (the tiled form).  x [batch, k_in] with row stride ldx >= k_in, g [batch, n_out] with row stride ldg >= n_out (floats), dw
+ * [n_out, k_in] and db [n_out] (db may be NULL) contiguous, 4-byte aligned (a slice of a gradient arena).
+ * What the tiled form relies on:
+ *   - a row pitch ld % 4 == 0 on a 16-byte aligned pointer (ld % 2 == 0 on an 8-byte aligned one, for x) is read in whole 16-byte (8-byte)
+ *     vectors up to the pitch: the floats between a row's width and its pitch must be readable, their values (NaN included) never reach a
+ *     result.  Any other pitch or alignment is read float by float, inside the width;
+ *   - `workspace` is 16-byte aligned when k_in % 4 == 0 (LSIM_E_INVALID otherwise).
+ * `workspace` is a caller-allocated device buffer of at least lsim_linear_wgrad_workspace() bytes holding the partial results, one per
+ * `num_waves` batch slices (summed in a fixed order: deterministic); every byte of it may be overwritten, none needs initialising.
+ * Returns LSIM_E_UNSUPPORTED for batch <= 0 and for larger layers (use BLAS), LSIM_E_INVALID for a NULL x, g, dw or workspace, a pitch below
+ * the width or a workspace that is too small. */
 int lsim_linear_wgrad_workspace(long batch, int k_in, int n_out, size_t* bytes, int* num_waves);
 int lsim_linear_wgrad(const float* x, int64_t ldx, const float* g, int64_t ldg, int64_t batch, int k_in, int n_out,
                       float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream);
@@ -693,8 +702,10 @@ int lsim_linear_elu_forward(const float* x, int64_t ldx, const float* weight, co
  * operand of the weight-gradient kernel and written once -- [batch, n_out] contiguous -- for the caller's input-gradient GEMM
  * (grad_pre @ W); dw / db as lsim_linear_wgrad.  One pass over grad_out and z instead of elu_backward + column sum + wgrad.
  * grad_pre may be NULL when no input gradient will be formed (the first layer of a network): the gradient of the pre-activation is then
- * only used inside the kernel and never written.
- * Same workspace as lsim_linear_wgrad; LSIM_E_UNSUPPORTED for shapes lsim_linear_wgrad handles in its single-wave form (<= 4096 outputs). */
+ * only used inside the kernel and never written.  grad_pre has no pitch argument: row b starts at grad_pre + b * n_out; it is written in
+ * 16-byte vectors when n_out % 4 == 0 and must then be 16-byte aligned (LSIM_E_INVALID otherwise).  elu_out [batch, n_out] with row stride
+ * ldz >= n_out is read like g; g is read in 16-byte vectors only when g and elu_out both allow it.
+ * Same workspace as lsim_linear_wgrad; LSIM_E_UNSUPPORTED for shapes lsim_linear_wgrad handles in its single-wave form (k_in * n_out <= 4096). */
 int lsim_linear_elu_wgrad(const float* x, int64_t ldx, const float* grad_out, int64_t ldg, const float* elu_out, int64_t ldz, int64_t batch,
                           int k_in, int n_out, float* dw, float* db, float* grad_pre, void* workspace, size_t workspace_bytes, void* stream);
 

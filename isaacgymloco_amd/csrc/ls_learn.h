@@ -590,6 +590,10 @@ static int ls_linear_wgrad_impl(const float* x, int64_t ldx, const float* g, int
     if (workspace_bytes < ls_wgrad_workspace_bytes(p, k_in, n_out) || ldx < k_in || ldg < n_out) return LSIM_E_INVALID;
     const bool fz = z != nullptr;
     if (fz && (p.small || ldz < n_out)) return p.small ? LSIM_E_UNSUPPORTED : LSIM_E_INVALID;
+    // the tiled kernel stores whole 16-byte vectors: partial tiles when k_in % 4 == 0 (every slice's tile then starts a multiple of 16 bytes
+    // behind the workspace), grad_pre rows when n_out % 4 == 0
+    if (!p.small && (k_in & 3) == 0 && ((uintptr_t)workspace & 15) != 0) return LSIM_E_INVALID;
+    if (!p.small && gy && (n_out & 3) == 0 && ((uintptr_t)gy & 15) != 0) return LSIM_E_INVALID;
     float* pdw = (float*)workspace;
     float* pdb = db ? pdw + (size_t)p.partials * n_out * k_in : nullptr;
     hipStream_t s = (hipStream_t)stream;
