@@ -53,7 +53,8 @@ extern "C" {
                                     lsim_odometry_step + LSIM_RNG_ODOMETRY (an estimated base pose that drifts with the distance travelled) and
                                     lsim_map_rows (the map's scan as the rows an actor reads, one launch);
                                     lsim_sensor_frames_log (the images a rollout's captures produced, logged once each, behind the capture) and
-                                    lsim_latent_rows_grad (a minibatch's latent gradients summed per logged image) */
+                                    lsim_latent_rows_grad (a minibatch's latent gradients summed per logged image);
+                                    lsim_distill_loss (a minibatch's action means against a teacher's, gathered through the shuffle's permutation) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1610,6 +1611,43 @@ typedef struct lsim_latent_rows_grad {
 /* LSIM_E_INVALID, checked on the host before any launch (nothing is written): lg == NULL; a pointer NULL or not 4-byte aligned; batch < 1;
  * rows < 0; latent_dim < 1; g_stride or G_stride < latent_dim; num_steps or num_envs < 1; num_steps * num_envs >= 2^31. */
 int lsim_latent_rows_grad(const lsim_latent_rows_grad_t* lg, void* stream);
+
+/* ---- distillation loss: the squared error between a minibatch's action means and a teacher's means of the same transitions, its gradient
+ * and its per-workgroup sums.  ONE launch under the same rules: the caller's stream, no host synchronisation, raw pointers only, capturable in
+ * a graph.  `target` holds the teacher's means of EVERY transition of the rollout and index[i] names the transition minibatch row i holds (the
+ * slice of the shuffle's permutation), so no gathered copy of the labels exists.  For i < batch, j < actions, with t = index[i]:
+ *     0 <= t < target_rows:   d = mu[i * mu_stride + j] - target[t * target_stride + j];     g[i * g_stride + j] = d * scale
+ *     otherwise (the row carries no loss):   g[i * g_stride + j] = +0.0f, the row adds nothing to any sum, and neither target nor the
+ *                                            values of mu's row enter the result (they may be anything, NaN included)
+ *   One subtraction and one product per element, both fp32 and correctly rounded: nothing can be fused, so g is the same bits on every
+ *   implementation.  Columns >= actions of g, and the words between `actions` and a stride of mu and target, are neither read nor written.
+ *   partial[p], p < LSIM_DISTILL_PARTIALS, is the fp32 sum of d * d over the rows workgroup p owns -- rows p * chunk .. min(batch, (p + 1) *
+ *   chunk) - 1 with chunk = ceil(batch / LSIM_DISTILL_PARTIALS) --, UNSCALED; a workgroup that owns no row, or only rows without a loss,
+ *   writes 0.  All LSIM_DISTILL_PARTIALS words are written by every call.  The caller forms the loss, 0.5 * scale * sum_p partial[p] (with
+ *   scale = 2 / (batch * actions): the mean squared error, of which g is the gradient).  The grid is LSIM_DISTILL_PARTIALS workgroups whatever
+ *   batch is; the order of every sum is a function of batch, actions and that constant only (and of which of the two paths below runs): no
+ *   floating-point atomic, nothing passes between workgroups, and two calls with the same inputs write the same bits to g and partial.
+ *   Paths.  With actions and the three strides multiples of 4 and mu, target and g 16-byte aligned the launch moves 128 bits per access;
+ *   otherwise one element.  g is identical on both; partial may differ in rounding.
+ *   It reads mu, target and index and writes g and partial; nothing else. */
+#define LSIM_DISTILL_PARTIALS 256
+#define LSIM_DISTILL_MAX_ACTIONS 16
+typedef struct lsim_distill_loss {
+    const float* mu;                  /* [batch, mu_stride]: the student's action means of a minibatch, 4-byte aligned like every pointer here */
+    const float* target;              /* [target_rows, target_stride]: the teacher's means of every transition of the rollout */
+    const int32_t* index;             /* [batch]: the row of target for minibatch row i; outside 0 .. target_rows - 1: the row carries no loss */
+    float* g;                         /* [batch, g_stride], WRITTEN: d loss / d mu */
+    float* partial;                   /* [LSIM_DISTILL_PARTIALS], WRITTEN, all of it: per-workgroup sums of d * d, unscaled */
+    int32_t batch;                    /* >= 1 */
+    int32_t actions;                  /* 1 .. LSIM_DISTILL_MAX_ACTIONS */
+    int32_t target_rows;              /* >= 1 */
+    int32_t mu_stride, target_stride, g_stride;   /* floats between rows: >= actions */
+    float scale;                      /* finite, by value: 2 / (batch * actions) as the caller formed it in fp32 */
+} lsim_distill_loss_t;
+/* LSIM_E_INVALID, checked on the host before the launch (nothing is written): dl == NULL; mu, target, index, g or partial NULL or not 4-byte
+ * aligned; batch < 1; actions < 1 or > LSIM_DISTILL_MAX_ACTIONS; target_rows < 1; mu_stride, target_stride or g_stride < actions; scale not
+ * finite. */
+int lsim_distill_loss(const lsim_distill_loss_t* dl, void* stream);
 
 /* ---- depth encoder, BACKWARD: the gradients of the six parameters from the gradient of `latent`, for a batch of images.  Same rules as every
  * launch here: the caller's stream, no host synchronisation, raw pointers only, capturable in a graph.  THREE launches per call, whatever the

@@ -120,6 +120,7 @@ LsimDepthEncoder = STRUCTS["lsim_depth_encoder_t"]
 LsimDepthEncoderBwd = STRUCTS["lsim_depth_encoder_bwd_t"]
 LsimFramesLog = STRUCTS["lsim_frames_log_t"]
 LsimLatentRowsGrad = STRUCTS["lsim_latent_rows_grad_t"]
+LsimDistillLoss = STRUCTS["lsim_distill_loss_t"]
 
 REWARD_IDS = {k[len("LSIM_R_"):].lower(): v for k, v in ENUMS["lsim_reward_id"].items() if k.startswith("LSIM_R_")}
 NUM_REWARD_TERMS = ENUMS["lsim_reward_id"]["LSIM_NUM_REWARD_TERMS"]

@@ -10,10 +10,11 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "liblsim.so")
-# two translation units, two flag sets: (source, headers it depends on, extra flags)
+# three translation units, two flag sets: (source, headers it depends on, extra flags)
 SIM_HEADERS = ["ls_math.h", "ls_shared.h", "ls_physics.h", "ls_post.h", "ls_kernels.h", "ls_api_impl.h", "ls_eval.h", "ls_eval_columns.h", "ls_raycast.h", "ls_raycast_bodies.h",
                "ls_sensor_model.h", "ls_sensor_mount_jitter.h", "ls_sensor_instrument.h", "ls_elevation_map.h", "ls_odometry.h", "ls_depth_encoder.h", "ls_depth_encoder_bwd.h", "ls_depth_memory.h", "ls_frames_log.h"]
 LEARN_HEADERS = ["ls_math.h", "ls_rollout.h", "ls_learn.h", "ls_gemm.h", "ls_policy.h", "ls_amp.h"]
+DISTILL_HEADERS = ["ls_distill.h"]
 # The simulator kernels' time is their vector instruction count, so ITS flags (SIM_FLAGS) are chosen for that:
 # -fno-hip-fp32-correctly-rounded-divide-sqrt: ~150 divisions per sub-step cost ~12 instructions each when IEEE-rounded; quotients that
 #   must be exact use ls_div_exact (ls_math.h)
@@ -25,7 +26,9 @@ LEARN_HEADERS = ["ls_math.h", "ls_rollout.h", "ls_learn.h", "ls_gemm.h", "ls_pol
 # kernels they replace (Adam's exp_avg_sq of tiny gradients, sqrt / division in lsim_k_adam_apply and the normalisations).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-pass-failed", "-fno-slp-vectorize"]
 SIM_FLAGS = ["-fno-hip-fp32-correctly-rounded-divide-sqrt", "-fgpu-flush-denormals-to-zero"]
-UNITS = [("lsim_hip.hip", SIM_HEADERS, SIM_FLAGS), ("lsim_learn.hip", LEARN_HEADERS, [])]
+# lsim_distill.hip (vision distillation's loss joint) takes the learner's flags but is a unit of its own, so that the learner's code object
+# is byte for byte the one of a library without it
+UNITS = [("lsim_hip.hip", SIM_HEADERS, SIM_FLAGS), ("lsim_learn.hip", LEARN_HEADERS, []), ("lsim_distill.hip", DISTILL_HEADERS, [])]
 
 
 def _deps(src, headers):
@@ -69,7 +72,7 @@ def build(force=False, verbose=False):
 
 
 def build_variant(out, extra_flags=(), workdir=None):
-    """a diagnostics / from-source build of the whole library into `out`: both translation units compiled from source with `extra_flags`
+    """a diagnostics / from-source build of the whole library into `out`: every translation unit compiled from source with `extra_flags`
     added (objects go to `workdir`, default next to `out`), never touching the in-tree objects or liblsim.so"""
     hipcc = os.environ.get("HIPCC", "hipcc")
     out = os.path.abspath(out)

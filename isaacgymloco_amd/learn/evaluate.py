@@ -299,6 +299,8 @@ def _actor_critic(env, policy, device, vision=None):
                 vision.update(memory=policy.alg.memory, memory_head=policy.alg.memory_head)
         if getattr(policy, "map_policy", False):      # a MapOnPolicyRunner: the actor reads its sensor's map rows
             vision.update(sensor=getattr(policy, "sensor", None), map_policy={"channels": list(policy.channels)})
+        if getattr(policy, "scan_policy", False):     # a ScanOnPolicyRunner: the actor reads the scan block of the privileged observation
+            vision["scan_policy"] = policy.scan_record()
         return policy.alg.actor_critic
     if isinstance(policy, str):
         d = torch.load(policy, map_location=device, weights_only=False)
@@ -312,13 +314,15 @@ def _actor_critic(env, policy, device, vision=None):
         if enc != [l.out_features for l in ac.estimator.encoder if isinstance(l, torch.nn.Linear)]:
             raise ValueError(f"checkpoint estimator encoder widths {enc} differ from the default HIMEstimator's: pass the HIMActorCritic itself")
         extra = sd["actor.0.weight"].shape[1] - ac.actor[0].in_features
-        if extra > 0 and ("depth_encoder_state_dict" in d or "map_policy" in d):       # a vision or a map policy: the extra columns come last (learn/vision.py)
+        if extra > 0 and ("depth_encoder_state_dict" in d or "map_policy" in d or "scan_policy" in d):       # a vision, map or scan policy: the extra columns come last (learn/vision.py)
             from .vision import VisionActorCritic
             ac = VisionActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, depth_latent_dim=extra,
                                    actor_hidden_dims=tuple(actor[:-1]), critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
             vision["checkpoint"] = d
             if "map_policy" in d:
                 vision["map_policy"] = d["map_policy"]
+            if "scan_policy" in d:
+                vision["scan_policy"] = d["scan_policy"]
         ac.load_state_dict(sd)
         ac.eval()
         return ac
@@ -578,6 +582,21 @@ def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
 
 
+def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, explicit):
+    """evaluate() for a scan policy (learn/scan_policy.py): the actor also reads the scan block of the live privileged observation --
+    a column-slice view, so the fused launch takes it with ld = num_priv_obs and nothing is copied.  Only the base columns are reported:
+    there is no sensor, encoder or map to measure, so vision metrics that were NAMED are refused."""
+    from .vision import PackedVisionPolicy, height_scan_block
+    if explicit and metrics:
+        raise ValueError(f"evaluate: a scan policy reads the privileged height scan itself -- it has no sensor, encoder or map, so no vision "
+                         f"metrics; got {tuple(metrics)} (pass vision_metrics=())")
+    off, width = height_scan_block(env.cfg)
+    if (int(record.get("offset", off)), int(record.get("width", width))) != (off, width) or width != ac.depth_latent_dim:
+        raise ValueError(f"evaluate: the scan policy read the block {record}, the env's is offset {off}, width {width}; the actor reads {ac.depth_latent_dim}")
+    priv = env.get_privileged_observations()
+    return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, lambda: priv[:, off:off + width], blind)
+
+
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
              sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained",
@@ -608,16 +627,20 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     square of the rows' height block minus the privileged one.
     `odometry` (a sensor with an elevation map only): the dead-reckoning error of the pose the map is placed with
     (envs.sensors.OdometryError) -- "trained", None or an OdometryError, as camera_jitter; written to conventions["odometry"].  With
-    odometry map_scan_error uses the ESTIMATED base height, the one the map has."""
+    odometry map_scan_error uses the ESTIMATED base height, the one the map has.
+    A scan policy (a ScanOnPolicyRunner or its checkpoint, recognised by its "scan_policy" record) reads the scan block of the live
+    privileged observation; `blind=True` feeds zeros; only the base columns are reported and `vision_metrics` other than the default
+    or an empty tuple are refused: there is nothing of a camera to measure."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
     ac = _actor_critic(env, policy, dev, found)
     ac.eval()
     is_vision = hasattr(ac, "depth_latent_dim")
-    is_map = is_vision and ("map_policy" in found or (encoder is None and found.get("encoder") is None and found.get("checkpoint") is None and
+    is_scan = is_vision and "scan_policy" in found
+    is_map = is_vision and not is_scan and ("map_policy" in found or (encoder is None and found.get("encoder") is None and found.get("checkpoint") is None and
                                                       getattr(sensor, "map_channels", None) is not None))
-    if is_vision:
+    if is_vision and not is_scan:
         if is_map:
             cam, head = _map_parts(env, ac, found, sensor), None
         else:
@@ -634,6 +657,9 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
     if not is_vision:
         return _run(env, ac, ev, steps, cmd, fused, PackedHimPolicy)
+    if is_scan:
+        return _evaluate_scan(env, ac, ev, steps, cmd, fused, found["scan_policy"], bool(blind), tuple(vision_metrics or ()),
+                              explicit=vision_metrics is not VISION_METRICS)
     ev.extra_conventions.update(conventions)
     if is_map:
         return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()))
@@ -730,6 +756,9 @@ def main(argv=None):
     record = d.get("vision") or d.get("map_policy") or {}
     if record.get("sensor") is not None:       # a vision or a map policy's checkpoint names the camera it was trained with
         env.add_sensor("depth", sensors.from_spec(env, record["sensor"]))
+    named = any(str(v).startswith("--vision-metrics") for v in (sys.argv[1:] if argv is None else argv))
+    if "scan_policy" in d and not named:       # a scan policy has no vision metrics: the option's default means none, a named one is refused
+        a.vision_metrics = ()
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
                   vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry)
     res = ev.result()

@@ -134,7 +134,8 @@ class HIMOnPolicyRunner:
             from .. import lib as _lib
             with _lib.roctx_range("ppo_update"):
                 update_out = self.alg.update()  # HIMPPO: 4 values; HybridPPO: 8 (adds AMP loss, grad penalty, policy / expert prediction)
-            mean_value_loss, mean_surrogate_loss, mean_estimation_loss, mean_swap_loss = update_out[:4]
+            # a learner without these four losses (learn/distill.py: VisionDistill returns two of its own) logs NaN in their places
+            mean_value_loss, mean_surrogate_loss, mean_estimation_loss, mean_swap_loss = update_out[:4] if len(update_out) >= 4 else (float("nan"),) * 4
             self.last_update = update_out
             if self.device != "cpu" and torch.cuda.is_available():
                 torch.cuda.synchronize()

@@ -1,0 +1,60 @@
+"""Scan policy: the TRUE height scan -- the block of the privileged observation the critic already reads -- as one more input segment of the
+HIM actor, from the rollout to the PPO update.
+
+    runner = ScanOnPolicyRunner(env, train_cfg, device=dev)
+    runner.enable_graphs()
+    runner.learn(n)
+
+This is the privileged teacher of vision distillation (learn/distill.py): a policy that sees the terrain around it exactly, which no robot
+does, trained so that a camera student can be regressed onto its action means.  What a map policy does with the elevation map's rows
+(learn/map_policy.py), this does with a column slice of the live privileged observation: the same VisionActorCritic with depth_latent_dim =
+LSIM_NUM_HEIGHT_PTS, the same storage and the same fused launch, whose extra segment takes a row pitch (lsim_policy_extra.ld =
+num_priv_obs), so NO launch and no buffer is added -- the rows are what the critic's blocks of the same launch stage anyway.  There is no
+sensor, no encoder and no auxiliary loss, and a HIM policy warm-starts it through load_him_state_dict.  One rank only."""
+import copy
+
+from .. import abi
+from .runner import _ALGOS, _POLICIES
+from .vision import ActorRowsPPO, ActorRowsRunner, VisionActorCritic, height_scan_block
+
+
+class ScanPPO(ActorRowsPPO):
+    """act() records `latent_source()` (the runner passes the scan block of env.privileged_obs_buf, a column-slice view) with the
+    transition, so storage.depth_latent[t] is storage.privileged_observations[t][:, off:off + w] bit for bit, and the update binds each
+    minibatch's stored rows to the actor.  update() returns HIMPPO.update()'s tuple."""
+
+
+class ScanOnPolicyRunner(ActorRowsRunner):
+    """HIMOnPolicyRunner for a scan policy.  The env's config needs terrain.measure_heights (height_scan_block raises without it: the
+    block would hold zeros).  train_cfg is HIMOnPolicyRunner's; policy["depth_latent_dim"] is set here.  The first actor layer reads
+    45 + 3 + 16 + 187 = 251 columns, inside the fused policy launch's 272."""
+
+    scan_policy = True
+    sensor = None           # VisionRollout's: the rows come from the env, not from a sensor
+
+    def __init__(self, env, train_cfg, log_dir=None, device="cpu", fast=None):
+        off, width = height_scan_block(env.cfg)
+        if env.num_privileged_obs is None or env.num_privileged_obs < off + width:
+            raise ValueError(f"ScanOnPolicyRunner: the env's privileged observation has {env.num_privileged_obs} columns, the height scan is [{off}, {off + width})")
+        if width != abi.DEFINES["LSIM_NUM_HEIGHT_PTS"]:
+            raise ValueError(f"ScanOnPolicyRunner: the height scan has {width} points, the layout {abi.DEFINES['LSIM_NUM_HEIGHT_PTS']}")
+        self._check_first_layer(env, **{"scan points": width})
+        _POLICIES["VisionActorCritic"], _ALGOS["ScanPPO"] = VisionActorCritic, ScanPPO
+        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
+        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "ScanPPO"
+        cfg["policy"]["depth_latent_dim"] = width
+        self.scan = (off, width)
+        super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
+        self.alg.latent_source = lambda: env.privileged_obs_buf[:, off:off + width]
+
+    def load_him_state_dict(self, sd):
+        """warm start from a HIM policy: the scan columns of the first actor layer are zero (VisionActorCritic.load_him_state_dict)"""
+        return self.alg.actor_critic.load_him_state_dict(sd)
+
+    def scan_record(self):
+        return {"offset": int(self.scan[0]), "width": int(self.scan[1]), "dim": int(self.alg.actor_critic.depth_latent_dim)}
+
+    def _extra_checkpoint_state(self):
+        out = super()._extra_checkpoint_state()
+        out["scan_policy"] = self.scan_record()     # learn/evaluate.py and learn/distill.py find the rows from it
+        return out

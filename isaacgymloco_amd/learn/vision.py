@@ -127,6 +127,21 @@ class VisionActorCritic(HIMActorCritic):
         sd["actor.0.weight"] = wide
         return self.load_state_dict(sd)
 
+    @torch.no_grad()
+    def load_scan_teacher_state_dict(self, sd, scan_dim):
+        """warm start a camera student from a scan policy's state dict (learn/scan_policy.py; learn/distill.py): everything is copied,
+        of actor.0.weight the first n1 + 3 + nl columns; the teacher's `scan_dim` scan columns are dropped and this policy's depth columns
+        are zero -- the student starts as the teacher with a flat scan of zeros, whatever its camera shows"""
+        sd = dict(sd)
+        w = sd["actor.0.weight"]
+        k = self.num_him_actor_inputs
+        if tuple(w.shape) != (self.actor[0].out_features, k + int(scan_dim)):
+            raise ValueError(f"load_scan_teacher_state_dict: actor.0.weight must be {(self.actor[0].out_features, k + int(scan_dim))}, got {tuple(w.shape)}")
+        wide = torch.zeros_like(self.actor[0].weight)
+        wide[:, :k] = w[:, :k]
+        sd["actor.0.weight"] = wide
+        return self.load_state_dict(sd)
+
 
 class VisionTransition:
     __slots__ = Transition.__slots__ + ("depth_latent",)
@@ -570,6 +585,8 @@ class VisionOnPolicyRunner(ActorRowsRunner):
     algorithm["e2e_learning_rate"] (default aux_learning_rate); one rank, and no gradient through the memory.  Without it, likewise,
     nothing is allocated, launched, stored or saved that was not before."""
 
+    algorithm_class = None      # the learner: VisionPPO; learn/distill.py's DistillRunner names VisionDistill
+
     def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None, memory=None, end_to_end=False):
         cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
         if getattr(cam, "model", None) is None:
@@ -581,9 +598,10 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             from .depth_encoder import DepthEncoder
             encoder = DepthEncoder(cam.height, cam.width, cam.model.frames)
         encoder = encoder.to(device)
-        _POLICIES["VisionActorCritic"], _ALGOS["VisionPPO"] = VisionActorCritic, VisionPPO
+        learner = self.algorithm_class or VisionPPO
+        _POLICIES["VisionActorCritic"], _ALGOS[learner.__name__] = VisionActorCritic, learner
         cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
-        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "VisionPPO"
+        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", learner.__name__
         cfg["policy"]["depth_latent_dim"] = encoder.latent_dim
         if memory is not None and memory is not False:
             from .depth_memory import DepthMemory

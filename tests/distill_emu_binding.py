@@ -1,0 +1,137 @@
+"""TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_distill.cpp (the CPU shim of isaacgymloco_amd/csrc/ls_distill.h compiled by g++
+under LS_EMU), and the rig of lsim_distill_loss: one struct with the arrays it points to, in host memory for the shim or in device memory
+for the HIP library.  Both arrays a call writes have GUARD elements behind them, pre-filled and checked.  The checks both
+tests/test_distill.py (shim) and tests/test_gpu_distill.py (device) run are here too."""
+import ctypes
+
+import numpy as np
+
+import distill_reference as R
+import emu_binding
+from helpers import abi
+from odometry_emu_binding import _Arrays
+
+HEADERS = ["ls_distill.h"]
+GUARD = 16
+G_FILL, P_FILL = np.float32(-7.25), np.float32(-3.5)
+LsimDistillLoss = abi.STRUCTS["lsim_distill_loss_t"]
+assert R.PARTIALS == abi.DEFINES["LSIM_DISTILL_PARTIALS"] and max(R.ACTIONS) <= abi.DEFINES["LSIM_DISTILL_MAX_ACTIONS"] == 16
+
+
+def lib():
+    return emu_binding.load_shim("distill", HEADERS)
+
+
+class Rig(_Arrays):
+    """mu, target and index are inputs; g [batch, g_stride] and partial [PARTIALS] are outputs, pre-filled, each with GUARD elements behind it.
+    `device`: None -- numpy arrays and the shim -- or a torch device and `entry` = the library's lsim_distill_loss."""
+
+    def __init__(self, mu, target, index, actions, g_stride, device=None, entry=None):
+        self.device, self.batch, self.actions, self.g_stride = device, mu.shape[0], int(actions), int(g_stride)
+        al = emu_binding.aligned
+        a = {"mu": al(mu.shape, np.float32), "target": al(target.shape, np.float32), "index": al(index.shape, np.int32),
+             "g": al((self.batch * self.g_stride + GUARD,), np.float32), "partial": al((R.PARTIALS + GUARD,), np.float32)}
+        a["mu"][...], a["target"][...], a["index"][...] = mu, target, index
+        a["g"][:] = G_FILL
+        a["partial"][:] = P_FILL
+        self.a = a
+        self._to_device()
+        dl = LsimDistillLoss()
+        dl.mu, dl.target, dl.index, dl.g, dl.partial = (self._ptr(k) for k in ("mu", "target", "index", "g", "partial"))
+        dl.batch, dl.actions, dl.target_rows = self.batch, self.actions, target.shape[0]
+        dl.mu_stride, dl.target_stride, dl.g_stride = mu.shape[1], target.shape[1], self.g_stride
+        dl.scale = float(R.scale_of(self.batch, self.actions))
+        self.dl = dl
+        self._entry = entry if device is not None else lib().emu_distill_loss
+
+    def launch(self, edit=None, stream=None):
+        dl = LsimDistillLoss.from_buffer_copy(self.dl)
+        if edit:
+            edit(dl)
+        return self._entry(ctypes.byref(dl), self._stream(stream))
+
+    def raw(self):
+        return {k: self.get(k) for k in ("g", "partial")}
+
+    def read(self):
+        """(g [batch, g_stride], partial [PARTIALS]); asserts both guards intact"""
+        raw = self.raw()
+        n = self.batch * self.g_stride
+        assert (raw["g"][n:] == G_FILL).all(), "the guard behind g was overwritten"
+        assert (raw["partial"][R.PARTIALS:] == P_FILL).all(), "the guard behind partial was overwritten"
+        return raw["g"][:n].reshape(self.batch, self.g_stride), raw["partial"][:R.PARTIALS]
+
+
+def check_case(make_rig, kind, actions, pad):
+    """one case of distill_reference.cases(): g bit for bit, skipped rows +0.0, untouched columns and guards, a second launch with the same
+    bits, the sums within the bound of the header"""
+    mu, target, index, strides, vector = R.make_case(kind, actions, pad)
+    batch = mu.shape[0]
+    rig = make_rig(mu, target, index, actions, strides[2])
+    if rig.device is None:
+        assert bool(lib().emu_distill_loss_path(ctypes.byref(rig.dl))) == vector
+    want_g, want_sums, ok = R.reference(mu, target, index, actions, rig.dl.scale, np.full((batch, strides[2]), G_FILL, dtype=np.float32))
+    if batch > 1:
+        assert (~ok).sum() >= 2 and (index == -1).any() and (index == target.shape[0]).any() and np.isnan(mu[~ok]).all()
+    if kind == "above one pass":
+        per_row = actions // 4 if vector else actions
+        assert -(-batch // R.PARTIALS) * per_row > R.BLOCK >= (-(-batch // R.PARTIALS) - 1) * per_row, "a lane loops, just"
+    assert rig.launch() == 0
+    g, partial = rig.read()
+    what = (kind, actions, pad, "vector" if vector else "scalar")
+    assert np.array_equal(g.view(np.uint32), want_g.view(np.uint32)), what
+    assert (g[~ok, :actions].view(np.uint32) == 0).all(), what                  # exactly +0.0
+    assert (g[:, actions:] == G_FILL).all(), what
+    assert np.isfinite(partial).all() and (partial >= 0).all(), what
+    chunk = -(-batch // R.PARTIALS)
+    idle = np.arange(R.PARTIALS) * chunk >= batch
+    assert (partial[idle].view(np.uint32) == 0).all(), what
+    assert idle.any() == (batch < R.PARTIALS)
+    # non-negative terms, so every rounding is a relative one: a term passes through its own product, the additions of its lane (the items a
+    # lane takes times the terms of an item), 6 butterfly steps and 3 additions over the waves; the total below through numpy's pairwise sum of 256 words, at most 16 + 3 + 1 more
+    per_row = actions // 4 if vector else actions
+    roundings = 1 + -(-chunk * per_row // R.BLOCK) * (4 if vector else 1) + 6 + 3
+    assert (roundings + 20) * 2.0 ** -24 < 1e-5
+    assert np.all(np.abs(partial.astype(np.float64) - want_sums) <= 1e-5 * want_sums), what
+    total = float(partial.sum(dtype=np.float32))
+    assert abs(total - want_sums.sum()) <= 1e-5 * want_sums.sum(), (what, total, want_sums.sum())
+    assert rig.launch() == 0                                                    # a second launch: the same bits
+    g2, partial2 = rig.read()
+    assert np.array_equal(g2.view(np.uint32), g.view(np.uint32)) and np.array_equal(partial2.view(np.uint32), partial.view(np.uint32)), what
+    return rig
+
+
+def _bad_pointer(name, off):
+    def edit(s):
+        setattr(s, name, (getattr(s, name) or 0) + off if off else None)
+    return edit
+
+
+def _set(**kw):
+    def edit(s):
+        for k, v in kw.items():
+            setattr(s, k, v)
+    return edit
+
+
+REFUSALS = {
+    **{f"{n} NULL": _bad_pointer(n, 0) for n in ("mu", "target", "index", "g", "partial")},
+    **{f"{n} misaligned": _bad_pointer(n, 2) for n in ("mu", "target", "index", "g", "partial")},
+    "batch 0": _set(batch=0), "actions 0": _set(actions=0), "actions 17": _set(actions=17, mu_stride=32, target_stride=32, g_stride=32),
+    "target_rows 0": _set(target_rows=0), "mu_stride < actions": _set(mu_stride=11), "target_stride < actions": _set(target_stride=11),
+    "g_stride < actions": _set(g_stride=11), "scale inf": _set(scale=float("inf")), "scale -inf": _set(scale=float("-inf")),
+    "scale NaN": _set(scale=float("nan"))}
+
+
+def check_refusals(make_rig, null_call):
+    """every listed argument error returns LSIM_E_INVALID and leaves both outputs, guards included, as they were"""
+    mu, target, index, strides, _ = R.make_case("seventy", 12, 0)
+    rig = make_rig(mu, target, index, 12, strides[2])
+    before = rig.raw()
+    assert null_call() == abi.E_INVALID
+    for name, edit in REFUSALS.items():
+        assert rig.launch(edit=edit) == abi.E_INVALID, name
+        after = rig.raw()
+        for k in before:
+            assert np.array_equal(before[k].view(np.uint8), after[k].view(np.uint8)), f"{name}: {k} was written"
+    assert rig.launch() == 0

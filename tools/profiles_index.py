@@ -79,6 +79,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "sensor_options_refactor_ab.json": ("parent commit against the commit that gave the sensor options one record, one text grammar and one resolver, `learn/evaluate.py` one step loop and `MapPPO` a base class of its own: `evaluate(...).result()` of a HIM, a vision (with and without memory) and a map policy under every form of `blind`, `camera_jitter`, `camera_instrument` and `odometry`, on the emulated env and on the device (equal), then a 500-step `evaluate()` at N = 4096 and `bench.py --gpus 1 --steps 1000 --warmup 100` in three alternating pairs each, with the parent's run-to-run spread, and the code lines of the four files", "7.16"),
               "sensor_chain_refactor_ab.json": ("parent commit against the commit that made every launch behind `RaySensor.update()` a stage of one chain (host-side Python only, the same library): SHA-256 of every sensor output tensor of twelve chain configurations at N = 8 and N = 4096 (equal), then `tools/raycast_time.py --model … --instrument … --map --odometry --map-rows 2` at N = 4096 and N = 64 and `tools/vision_train_time.py --memory` in five alternating pairs each and one `bench.py` pair, with the parent's run-to-run spread, the host time of `update()` with no-op launches and the code lines of the five files", "7.17"),
               "depth_encoder_time.json": ('`tools/depth_encoder_time.py`, N = 4096, 64 × 48 camera, 2 frames, the default network: `lsim_depth_encode` with every env due and at period 5 staggered, the torch forward on the same device, `lsim_sensor_capture` and kernel A in one process', "7.8"),
+              "distill_time.json": ('`tools/distill_time.py`, N = 4096, 64 × 48 camera at period 5, T = 24: the labelling pass, one `lsim_distill_loss` launch and the whole distillation update, with the `end_to_end=True` PPO update of the same shapes at the parent commit and in this tree as context', "7.19"),
               "depth_memory_time.json": ('`tools/depth_memory_time.py`, N = 4096, L = 64, P = 45, H = 64: `lsim_depth_memory_step` next to kernel A and the staggered encoder launch; `sequence_device` forward + backward, the two serial kernels alone and the `nn.GRUCell` loop at T = 99, n = 1024 / 4096, alternating samples in one process', "7.12"),
               "eval_time.json": ('`tools/eval_time.py`, N = 4096, 400 groups: `lsim_eval_accumulate` next to the env step, kernel A and the torch statements it replaces, HIP events', "7.5"),
               "policy_ext_time.json": ('`tools/policy_time.py --ext`, N = 4096, L = 64: `lsim_policy_forward_ext` / `lsim_policy_act_post_at_ext` against the plain launches in one process, alternating', "7.10"),
