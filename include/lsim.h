@@ -783,7 +783,10 @@ int lsim_normalize_rows(float* w, int rows, int cols, float eps, void* stream);
  *   out5 = { mean surrogate, mean value loss, mean entropy, mean KL, total = surrogate + value_loss_coef * value - entropy_coef * entropy }
  *   grad_mu [B, A], grad_sigma [B, A], grad_value [B] = d total / d (mu, sigma, value), torch's sub-gradient conventions.
  * mu, sigma, actions, old_mu, old_sigma [B, A]; value, old_logp, advantages, returns, target_values [B], all contiguous fp32.
- * target_values may be NULL when use_clipped_value_loss == 0.  workspace: lsim_ppo_loss_workspace() bytes; deterministic. */
+ * target_values may be NULL when use_clipped_value_loss == 0.  workspace: lsim_ppo_loss_workspace() bytes; deterministic.
+ * The sub-gradients, as torch forms them: max(a, b) gives each side 1/2 where a == b, clamp passes the gradient on the CLOSED interval
+ * (ratio == 1 +- clip_param and v - target == +-clip_param pass).  Rows with advantage 0 get grad_mu = 0 exactly and only the entropy
+ * term in grad_sigma.  num_actions is unbounded here.  The operands are read only; every element of the outputs is written. */
 int lsim_ppo_loss_workspace(long batch, size_t* bytes);
 int lsim_ppo_loss(const float* mu, const float* sigma, const float* value, const float* actions, const float* old_logp, const float* advantages,
                   const float* returns, const float* target_values, const float* old_mu, const float* old_sigma, int64_t batch, int num_actions,
@@ -792,7 +795,8 @@ int lsim_ppo_loss(const float* mu, const float* sigma, const float* value, const
 /* The same with the state-independent standard deviation of HIMActorCritic (HAC:93: `std`, one value per action) passed as what it is: `std`
  * [A] instead of its broadcast sigma [B, A] (the reference forms mean * 0 + std, HAC:147), and grad_std [A] = the column sums of what
  * grad_sigma would hold, added up in a fixed order -- the broadcast, its backward and the column sum (five launches and 10 MB per minibatch)
- * disappear.  workspace: lsim_ppo_loss_std_workspace() bytes.  num_actions <= 60. */
+ * disappear.  workspace: lsim_ppo_loss_std_workspace() bytes.  num_actions <= 60 (LSIM_E_INVALID above).  grad_std must not be NULL and is
+ * overwritten, not accumulated into; no grad_sigma [B, A] is formed or needed anywhere. */
 int lsim_ppo_loss_std_workspace(long batch, int num_actions, size_t* bytes);
 int lsim_ppo_loss_std(const float* mu, const float* std, const float* value, const float* actions, const float* old_logp, const float* advantages,
                       const float* returns, const float* target_values, const float* old_mu, const float* old_sigma, int64_t batch, int num_actions,
@@ -809,7 +813,10 @@ int lsim_adaptive_lr(const float* kl_mean_dev, float desired_kl, float lr_min, f
  *   Q = exp(scores / eps)^T;  Q /= sum(Q);  iters x { Q /= rowsum; Q /= K; Q /= colsum; Q /= B };  out = (Q * B)^T
  * scores [batch, K] with row stride lds (floats), K <= 64, out [batch, K] contiguous.  Computed as E * u[k] * v[b] with 2 * iters + 1
  * small launches instead of ~26 passes over the matrix; `workspace` holds E and the per-block partial sums
- * (lsim_sinkhorn_workspace() bytes, 16-byte aligned like `out`); sums are formed in a fixed order (deterministic). */
+ * (lsim_sinkhorn_workspace() bytes, 16-byte aligned like `out`); sums are formed in a fixed order (deterministic).
+ * `workspace` and `out` must be 16-byte aligned whatever K is (LSIM_E_INVALID otherwise); `scores` needs 4-byte alignment only: rows are read
+ * with 16-byte loads when K % 4 == 0, lds % 4 == 0 and the pointer is 16-byte aligned, one float at a time otherwise.  lds >= K, eps > 0,
+ * iters >= 1, batch >= 1.  exp(scores / eps) must stay finite in fp32 (cosine scores and eps = 0.05 reach exp(20)). */
 int lsim_sinkhorn_workspace(long batch, int K, size_t* bytes);
 int lsim_sinkhorn(const float* scores, int64_t lds, int64_t batch, int K, float eps, int iters, float* out,
                   void* workspace, size_t workspace_bytes, void* stream);
@@ -821,7 +828,12 @@ int lsim_sinkhorn(const float* scores, int64_t lds, int64_t batch, int K, float 
  *   q_t log_softmax(S_s / T)), est = mse(pred_vel, vel).
  *   losses3 = { est, swap, est + swap };  grad_enc [batch, 3 + latent], grad_tgt [batch, latent], grad_proto [K, latent] contiguous =
  *   d (est + swap) / d (enc_out, tgt_out, proto).  latent <= 32, K <= 64.  10 launches; sums in a fixed order (deterministic).
- * workspace: lsim_estimator_loss_workspace() bytes, 16-byte aligned. */
+ * workspace: lsim_estimator_loss_workspace() bytes, 16-byte aligned.  It is scratch: nothing in it survives the call or is read from an
+ * earlier one, and the caller may hand the same bytes to any other entry afterwards.
+ * The prototypes are used as given: nothing here normalises them or assumes unit rows, and grad_proto is the gradient with respect to the rows
+ * as passed (the caller's normalisation, lsim_normalize_rows, is not differentiated).  A latent row with norm below 1e-12 takes F.normalize's
+ * clamped branch: z = x * 1e12 and d x = d z * 1e12, without the projection.  enc_out, tgt_out and vel need 4-byte alignment only; the four
+ * operands are read only; every element of the four outputs is written.  temperature > 0, sinkhorn_eps > 0, sinkhorn_iters >= 1. */
 int lsim_estimator_loss_workspace(int64_t batch, int latent, int K, size_t* bytes);
 int lsim_estimator_loss(const float* enc_out, int64_t ld_enc, const float* tgt_out, int64_t ld_tgt, const float* proto, const float* vel,
                         int64_t ld_vel, int64_t batch, int latent, int K, float temperature, float sinkhorn_eps, int sinkhorn_iters,
@@ -833,7 +845,9 @@ int lsim_estimator_loss(const float* enc_out, int64_t ld_enc, const float* tgt_o
  * each, their gradients (rescaled in place by min(max_grad_norm / (||g|| + 1e-6), 1), as clip_grad_norm_ does; max_grad_norm <= 0: no
  * clipping), first / second moment estimates and per-parameter step counters (float scalars, incremented).  The pointer tables are HOST
  * arrays of device pointers.  Learning rate: *lr_dev if lr_dev != NULL (device scalar, see lsim_adaptive_lr), else lr_host.
- * grad_norm_out (device, may be NULL) receives the total norm before clipping.  workspace: lsim_adam_clip_step_workspace(count) bytes. */
+ * grad_norm_out (device, may be NULL) receives the total norm before clipping.  workspace: lsim_adam_clip_step_workspace(count) bytes.
+ * Every tensor uses ITS OWN step counter for the bias corrections (counters may differ); the counters hold integers as floats.  0 <= beta < 1,
+ * eps > 0, 1 <= numel[i] < 2^31; tensors need 4-byte alignment only and must not overlap. */
 int lsim_adam_clip_step_workspace(int count, size_t* bytes);
 int lsim_adam_clip_step(int count, const int64_t* numel, float* const* params, float* const* grads, float* const* exp_avg,
                         float* const* exp_avg_sq, float* const* steps, const float* lr_dev, float lr_host, float beta1, float beta2,
@@ -842,7 +856,8 @@ int lsim_adam_clip_step(int count, const int64_t* numel, float* const* params, f
 /* lsim_adam_clip_step for an optimiser with several parameter groups (HybridPPO, HYBP:86-92 + HYBP:270-273: one Adam over the actor-critic,
  * the discriminator trunk with weight decay 1e-3 and its head with weight decay 1e-1, gradient clipping over the actor-critic's parameters
  * only): weight_decay[i] >= 0 per tensor (torch.optim.Adam's L2 form, grad + weight_decay * param, applied after the clipping and not written
- * back to the gradient; NULL = none), and only tensors [0, clip_count) enter the clipped norm and are rescaled.  grad_norm_out = that norm. */
+ * back to the gradient; NULL = none), and only tensors [0, clip_count) enter the clipped norm and are rescaled.  grad_norm_out = that norm
+ * (0 for clip_count == 0, where nothing is rescaled).  0 <= clip_count <= count. */
 int lsim_adam_clip_step_ex(int count, const int64_t* numel, float* const* params, float* const* grads, float* const* exp_avg,
                            float* const* exp_avg_sq, float* const* steps, const float* weight_decay, int clip_count,
                            const float* lr_dev, float lr_host, float beta1, float beta2, float eps, float max_grad_norm,

@@ -605,7 +605,7 @@ def test_reference_style_step_tuple_and_strict_runner_path():
 
 def test_fused_estimator_loss_matches_torch_autograd():
     """lsim_estimator_loss (normalise, scores, Sinkhorn, log-softmax, swap + regression losses, backward) against the fp64 torch statement
-    of HES:76-108 with autograd; losses to 1e-5 relative, gradients to 1e-3 of their scale"""
+    of HES:76-108 with autograd; losses to 1e-5 relative, gradients to the fp32 twins' tolerance (about 1e-5 of their scale)"""
     from isaacgymloco_amd.learn.fused_linear import estimator_loss_hip
     g = torch.Generator(device="cuda:0").manual_seed(11)
     for B, D, K in ((102400, 16, 32), (5000, 16, 32), (777, 9, 50)):
@@ -633,9 +633,22 @@ def test_fused_estimator_loss_matches_torch_autograd():
         (est + swap).backward()
         torch.testing.assert_close(parts.double(), torch.stack([est, swap]).detach(), rtol=1e-5, atol=1e-7)
         torch.testing.assert_close(total.double(), (est + swap).detach(), rtol=1e-5, atol=1e-7)
-        for got, ref in ((enc.grad, e64.grad), (tgt.grad, t64.grad), (proto.grad, p64.grad)):
+        # the bound: 4 x the distance of the statement's fp32 twins from its fp64 form on THESE inputs, floored at 4 * 2^-23 of the gradient's scale
+        # (tests/loss_heads_reference.py; about 1e-5 of the scale here, never above the 1e-3 this test used to allow)
+        # -- the velocity and latent columns of enc.grad each against their own scale: the latent's gradient is 1000 x smaller
+        import numpy as np
+        import loss_heads_reference as LH
+        host = [t.detach().cpu().numpy() for t in (enc, tgt, proto, vel)]
+        grads = lambda o: dict(vel=o["d_vel"], lat=o["d_lat"], tgt=o["d_tgt"], proto=o["d_proto"])
+        tol = LH.tolerances(grads(LH.estimator_loss(*host, 3.0, 0.05, 3)),
+                            [grads(LH.estimator_loss(*host, 3.0, 0.05, 3, dtype=np.float32, form=f)) for f in LH.EST_TWINS], "estimator (%d, %d, %d)" % (B, D, K))
+        for key, got, ref in (("vel", enc.grad[:, :3], e64.grad[:, :3]), ("lat", enc.grad[:, 3:], e64.grad[:, 3:]), ("tgt", tgt.grad, t64.grad),
+                              ("proto", proto.grad, p64.grad)):
             scale = ref.abs().max()
-            assert ((got.double() - ref).abs().max() / scale) < 1e-3, ((got.double() - ref).abs().max(), scale)
+            bound = min(1e-3, tol[key]["tol"] / tol[key]["scale"])
+            err = float((got.double() - ref).abs().max() / scale)
+            print("estimator gradient", (B, D, K), key, "error / scale %.3e bound %.3e" % (err, bound))
+            assert err < bound, (key, err, bound, float(scale))
         enc2 = enc.detach().clone().requires_grad_(True)
         total2, _ = estimator_loss_hip(enc2, tgt.detach(), proto.detach(), vel, 3.0)
         total2.backward()
