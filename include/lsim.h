@@ -694,7 +694,12 @@ int lsim_linear_wgrad(const float* x, int64_t ldx, const float* g, int64_t ldg, 
  * runs them on minibatches of 102 400 rows, him_ppo.py:136-150).  fp32 MFMA with the activation applied to the accumulators: the layer's
  * output is written once instead of BLAS output + elementwise read + write.  x [batch, k_in] with leading dimension ldx, weight
  * [n_out, k_in] contiguous (nn.Linear.weight), bias [n_out] or NULL, out [batch, n_out] with leading dimension ldo.
- * LSIM_E_UNSUPPORTED unless n_out % 4 == 0, ldo % 4 == 0 and out is 16-byte aligned (use BLAS + ELU). */
+ * LSIM_E_UNSUPPORTED unless n_out % 4 == 0, ldo % 4 == 0 and out is 16-byte aligned (use BLAS + ELU).  x and weight are read at ANY 4-byte
+ * alignment, pitch and k_in: the loads are 16 bytes wide where both operands allow it (k_in % 4 == 0, ldx % 4 == 0, both pointers 16-byte aligned),
+ * 8 bytes where both allow that, single floats otherwise; only out (and mask_src below) must be 16-byte aligned.  Rows >= batch and the columns
+ * between k_in and ldx are never read, the columns between n_out and ldo never written.  The ELU's negative side is exp(x) - 1 with the hardware
+ * exponential: for a given pre-activation x <= 0 its absolute error is at most 1.2e-7 (2^-24 for the exponential, (2^-24 + 1.4e-8) / e for the
+ * rounding of x log2(e), 2^-25 for the subtraction); elu(0) is +0.0 and elu(x) is exactly -1 for x <= -18; positive x pass unchanged. */
 int lsim_linear_elu_forward(const float* x, int64_t ldx, const float* weight, const float* bias, int64_t batch, int k_in, int n_out,
                             float* out, int64_t ldo, void* stream);
 
@@ -722,9 +727,10 @@ int lsim_linear_masked_forward(const float* x, int64_t ldx, const float* weight,
 
 /* ---- discriminator update (HybridPPO.update, hybrid_ppo.py:236-281): the elementwise passes between the GEMMs of the LSGAN loss / gradient penalty.
  * lsim_relu_head_backward: for the head d = relu_out . head_weight + b on relu_out [batch, n] (leading dimension ld) and grad_d [batch] = d loss / d d:
- *   grad_pre[b, j] = relu_out[b, j] > 0 ? grad_d[b] * head_weight[j] : 0  ([batch, n] contiguous),  grad_bias[j] = sum_b grad_pre[b, j],
+ *   grad_pre[b, j] = relu_out[b, j] > 0 ? grad_d[b] * head_weight[j] : 0  (one fp32 product; rows DENSE: grad_pre has no pitch argument, row b starts
+ *   at grad_pre + b * n, 16-byte aligned; +0.0 and -0.0 in relu_out count as masked),  grad_bias[j] = sum_b grad_pre[b, j],
  *   grad_head [n + 4]: [j < n] = sum_b relu_out[b, j] * grad_d[b],  [n] = sum_b grad_d[b], three zeros  -- one pass, sums in a fixed order.
- * lsim_masked_colsum: out[j] = sum_b (mask_src[b, j] > 0 ? v[b, j] : 0).
+ * lsim_masked_colsum: out[j] = sum_b (mask_src[b, j] > 0 ? v[b, j] : 0) -- a select, not a product: v may hold anything where the mask is not positive.
  * n % 4 == 0, n <= 1024, n / 4 a divisor of 256; 16-byte aligned rows; workspace lsim_relu_cols_workspace() bytes.  LSIM_E_UNSUPPORTED otherwise. */
 int lsim_relu_cols_workspace(int64_t batch, int n, size_t* bytes);
 int lsim_relu_head_backward(const float* relu_out, int64_t ld, const float* grad_d, const float* head_weight, int64_t batch, int n,
@@ -734,7 +740,11 @@ int lsim_masked_colsum(const float* v, int64_t ldv, const float* mask_src, int64
 
 /* Normalizer.update (utils/utils.py:86-106; twice per minibatch at hybrid_ppo.py:279-281): the batch moments of x [batch, dim <= 64] merged into the
  * float64 running mean / var / count (device arrays [dim], [dim], [1], updated in place) with the parallel-variance formula; batch sums in float64.
- * Two launches, no host round trip.  workspace: lsim_running_moments_workspace() bytes, 8-byte aligned. */
+ * Two launches, no host round trip.  workspace: lsim_running_moments_workspace() bytes, 8-byte aligned.
+ * The batch variance is the one-pass form sum x^2 / n - mean^2 in float64: its absolute error is bounded by about 3 D 2^-53 times the column's
+ * mean square, D = rows per thread + slices / 4 + 6 (below 200 up to 10^5 rows).  On a (nearly) constant column the batch variance IS that rounding
+ * noise, of either sign -- negligible next to the Normalizer's epsilon of 1e-4 for |x| up to a few thousand, not beyond: the MERGED variance is
+ * therefore clamped at 0 (it is never negative; a NaN stays a NaN).  count becomes count + batch exactly (one float64 addition). */
 int lsim_running_moments_workspace(size_t* bytes);
 int lsim_running_moments_update(const float* x, int64_t ldx, int64_t batch, int dim, double* mean, double* var, double* count,
                                 void* workspace, size_t workspace_bytes, void* stream);

@@ -409,7 +409,10 @@ __global__ __launch_bounds__(256) void lsim_k_moments_merge(const double* __rest
         const double delta = bmean - mean[c];                                                           // UT:96-106
         const double m2 = var[c] * cnt + bvar * n + delta * delta * cnt * n / tot;
         mean[c] += delta * n / tot;
-        var[c] = m2 / tot;
+        // b / n - bmean^2 cancels: on a (nearly) constant column it is rounding noise of either sign, about 2^-53 x rows-per-sum x mean^2, which at a
+        // mean of 1e5 exceeds the Normalizer's epsilon of 1e-4 -- sqrt(var + epsilon) would be NaN.  A variance is not negative: clamp the merged one
+        const double merged = m2 / tot;
+        var[c] = merged < 0.0 ? 0.0 : merged;                                                           // (a NaN stays a NaN)
     }
     __builtin_amdgcn_wave_barrier();
     if (c == 0) count[0] = tot;          // after this wave's reads of count[0] above (one wave: program order)
