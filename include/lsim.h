@@ -54,7 +54,9 @@ extern "C" {
                                     lsim_map_rows (the map's scan as the rows an actor reads, one launch);
                                     lsim_sensor_frames_log (the images a rollout's captures produced, logged once each, behind the capture) and
                                     lsim_latent_rows_grad (a minibatch's latent gradients summed per logged image);
-                                    lsim_distill_loss (a minibatch's action means against a teacher's, gathered through the shuffle's permutation) */
+                                    lsim_distill_loss (a minibatch's action means against a teacher's, gathered through the shuffle's permutation);
+                                    lsim_elevation_map_fused (the elevation map with a banded mean per capture and a variance per cell, fused over the
+                                    captures by a scalar Kalman filter) and lsim_map_rows_fused (the map's rows with a confidence block) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1370,8 +1372,8 @@ int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, v
  *     scan[e][j] = height,  known[e][j] = 1;      otherwise  scan[e][j] = p.z - unknown_drop,  known[e][j] = 0
  *   (also when w is not finite, q.z = q.w = 0, or its cell is out of range).  No NaN is ever written.
  * `assumed_mount` is a pointer of its own: pointed at a sensor's NOMINAL mount while the capture reads a jittered one, the map is wrong in
- *   the way a robot's is.  Pointing `root_states` at lsim_odometry_step's `est` gives the map a drifting pose.  NOT BUILT: averaging or a variance
- *   per cell, overhangs, latency compensation of the pose. */
+ *   the way a robot's is.  Pointing `root_states` at lsim_odometry_step's `est` gives the map a drifting pose.  Averaging and a variance per cell:
+ *   lsim_elevation_map_fused below.  NOT BUILT: overhangs, latency compensation of the pose. */
 typedef struct lsim_elevation_map {
     const float* root_states;         /* [N,13] simulator buffer, read only */
     const float* assumed_mount;       /* [N,7] the mount pose the map believes in: position, quaternion xyzw */
@@ -1496,6 +1498,75 @@ typedef struct lsim_map_rows {
  * not 4-byte aligned; channels == 2 and known NULL; P outside 1..LSIM_ELEVATION_MAP_MAX_POINTS; channels outside 1..2; scan_stride < P;
  * channels == 2 and known_stride < P; ld < channels * P; z_offset or scale not finite; num_envs < 1; env_stride < 1. */
 int lsim_map_rows(const lsim_map_rows_t* mr, void* stream);
+
+/* ---- elevation map with a variance per cell: lsim_elevation_map whose cells AVERAGE the points of a capture and are fused over the captures
+ * by a scalar Kalman filter.  ONE launch under the rules of lsim_elevation_map, which it replaces in a sensor's chain (same position,
+ * stream, tick and flags).  `em` is that launch's own struct and everything said there holds unchanged: which envs are visited, fill and
+ * due, a bad pose, a ray's validity, its point P and its cell, the window, the words written to stamp and cell, the scan lookup, scan and
+ * known.  Fill clears the stamps only: the var of a slot that knows no cell is never read.  All arithmetic in fp32 (a compiler may contract a
+ * product and a sum); every quotient below is correctly rounded; int-to-float conversions round to nearest.
+ *
+ * State.  var[e][s] f32 next to height[e][s]: the variance of the stored height, in m^2; meaningful where the slot knows a cell.
+ * Insert (due, pose finite), two passes over the rays and three words of LDS per slot (key, an int32 sum, an int32 count):
+ *   Pass 1.  key(z) maximum per slot over the kept points, as lsim_elevation_map's:  zmax.
+ *   Pass 2, behind a barrier, over the same rays, every point formed again by the same operations:
+ *     df = zmax - P.z   (one fp32 subtraction, >= 0);     the point TAKES PART when df <= band:
+ *     sum += q,  q = (int32)(df * 65536.0f + 0.5f)  (the product is exact);     count += 1              (32-bit integer LDS atomics)
+ *   Integer sums are associative: the result does not depend on ray order and two launches write the same bits.  band <= 0.5 keeps
+ *   q <= 32769 and R * 32769 < 2^31 for every legal R: no sum overflows.  The point that set zmax has df = 0, so count >= 1 -- by construction, not by arithmetic:
+ *   both passes form P.z with the SAME code on the same inputs and so get the same bits.  An implementation guards the quotient all the same
+ *   (count == 0 reads as zm = zmax), and a sum added to a slot whose key is 0 is never read.
+ * Measurement of a touched slot (key != 0) that holds absolute cell (ix, iy), p = root_states[e][0:3] as given to the map:
+ *     zm  = zmax - ((float) sum / (float) count) * 2^-16
+ *     X = ((float) ix + 0.5f) * res,  Y = ((float) iy + 0.5f) * res;      rho2 = (X - p.x)^2 + (Y - p.y)^2
+ *     sigma = sigma0 + sigma2 * (rho2 + range_z2)                  (the sensor's noise at the range of the CELL, not of the rays)
+ *     vm  = sigma * sigma / (float) min(count, count_cap) + var_floor
+ * Commit, behind a barrier.  With the slot's words as they were before this launch's write (after fill):
+ *     age = (float) (((uint32) tick - (uint32) stamp) & 0x7FFFFFFF)             (ticks since the last write, across the stamp's 31-bit wrap)
+ *     vp  = var + var_growth * age;      d = zm - height;      S = vp + vm
+ *   fuse, when the slot knows this cell and S is finite and d * d < gate2 * S (strict):
+ *     K = vp / S;      height = height + K * d;      var = K * vm
+ *   otherwise (a new cell, a surface that changed, an estimate that ran away -- the newest capture wins, as it always did):
+ *     height = zm;     var = vm
+ *   then var = min(max(var, var_floor), var_max), and stamp and cell as lsim_elevation_map writes them.
+ * Scan.  scan and known as lsim_elevation_map's.  A known point reports, with the age formed at THIS launch's tick from the slot's stamp,
+ *     scan_var[e][j] = min(var + var_growth * age, var_max)
+ *   and an unknown point or a bad pose var_max.  No NaN is ever written.
+ * Consequences.  band = 0 and gate2 = 0: zmax - 0.0f is zmax and the gate never opens, so height, stamp, cell, scan and known are
+ *   lsim_elevation_map's bit for bit.  A cell the camera has left ages: its scan_var grows by var_growth per tick up to var_max.
+ * NOT BUILT: variance growth per metre travelled, latency compensation of the pose, overhangs, clearing cells the camera looks through. */
+typedef struct lsim_elevation_map_fused {
+    lsim_elevation_map_t em;          /* everything lsim_elevation_map takes, with its meaning and its checks */
+    float* var;                       /* [N,G,G] 4-byte aligned */
+    float* scan_var;                  /* [N,var_stride] 4-byte aligned */
+    float sigma0, sigma2;             /* the noise model: sigma = sigma0 + sigma2 * range^2, metres */
+    float range_z2;                   /* the square of the camera's height above the ground, m^2 */
+    float band;                       /* metres below the cell's highest point that are averaged: 0 .. 0.5 */
+    float var_floor, var_growth;      /* m^2; m^2 per tick */
+    float var_max;                    /* m^2: >= var_floor */
+    float gate2;                      /* the square of the gate in standard deviations */
+    int32_t count_cap;                /* >= 1: more points than this do not lower vm further (their errors are correlated) */
+    int32_t var_stride;               /* elements between rows of scan_var: >= P */
+} lsim_elevation_map_fused_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: ef == NULL; everything
+ * lsim_elevation_map refuses of ef->em; var or scan_var NULL or not 4-byte aligned; var_stride < P; one of sigma0, sigma2, range_z2, band,
+ * var_floor, var_growth, var_max, gate2 negative or not finite; band > 0.5; var_floor > var_max; count_cap < 1. */
+int lsim_elevation_map_fused(const lsim_elevation_map_fused_t* ef, void* stream);
+
+/* ---- map rows with a confidence: lsim_map_rows whose second block says how far each height can be trusted.  ONE launch, elementwise:
+ *     rows[e * ld + j]     = lsim_map_rows's first block, from the same fields of `mr`                      j < P
+ *     rows[e * ld + P + j] = known[e * known_stride + j] ? var_ref / (var_ref + scan_var[e * var_stride + j]) : 0.0f       j < P, channels == 2 only
+ *   (one sum, one correctly rounded quotient): in (0, 1] for a known point -- 1/2 where the variance is var_ref -- and 0 for an unknown
+ *   one.  A scan_var that is not finite or negative reads as 0 confidence: no NaN is ever written. */
+typedef struct lsim_map_rows_fused {
+    lsim_map_rows_t mr;               /* everything lsim_map_rows takes; channels == 2: heights, then the confidence */
+    const float* scan_var;            /* [N,var_stride] lsim_elevation_map_fused_t.scan_var; read only when channels == 2, NULL refused then */
+    int32_t var_stride;               /* elements between rows of scan_var: >= P (ignored when channels == 1) */
+    float var_ref;                    /* m^2: finite, > 0 */
+} lsim_map_rows_fused_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: mf == NULL; everything lsim_map_rows
+ * refuses of mf->mr; var_ref not finite or <= 0; channels == 2 and scan_var NULL, not 4-byte aligned or var_stride < P. */
+int lsim_map_rows_fused(const lsim_map_rows_fused_t* mf, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

@@ -53,6 +53,11 @@ capture, same stream, tick and flags, inserts the envs just captured and resampl
 knows.  The map believes in the NOMINAL mount, so a jittered camera bends it as it would on a robot.  Without an attached map nothing of
 this is created or launched.
 
+Map fusion (`ElevationMap(..., fusion=MapFusion())`, lsim_elevation_map_fused in lsim_elevation_map's place): a cell is the mean of a
+capture's points near its top instead of their biased maximum, the captures are fused by a variance the map keeps per cell, and cells the
+camera has left age; `cam.map_variance()` is the live [N, P] variance of map_scan(), `attach_map_rows(("height", "confidence"))`
+(lsim_map_rows_fused) the actor's rows with var_ref / (var_ref + variance) as the second block.  Without `fusion` nothing of this exists.
+
 Odometry (`cam.attach_map(m, odometry=OdometryError(scale=0.02, yaw_per_m=0.01, z_per_m=0.01, noise=(0.005, 0.002, 0.002)))`,
 lsim_odometry_step): a robot does not know where it is, it integrates its steps -- so the map is placed with an ESTIMATED pose that drifts
 with the distance travelled, in scale, yaw and height, by biases every env draws when it starts an episode plus a per-step noise.  One
@@ -227,6 +232,52 @@ class InstrumentError(_Option):
             raise ValueError(f"InstrumentError: finite 0 <= noise_gain[0] <= noise_gain[1], depth_scale >= 0, depth_quad >= 0 and 0 <= fov < 1, got {values}")
 
 
+class MapFusion(_Option):
+    """A variance per cell of an ElevationMap and the fusion by it (lsim_elevation_map_fused; include/lsim.h states every formula).  Within
+    a capture a cell takes the MEAN of the points that lie at most `band` metres below its highest one -- the maximum of k noisy points
+    lies about 1.5 sigma above the surface for k = 10, the mean does not -- and over the captures a scalar Kalman filter fuses the means
+    by their variances.  `band` (None: 5 sigma at 1.5 m, clipped to [0.02, 0.25]; at most 0.5): a band under about 5 sigma cuts the lower
+    tail of the noise off and brings the bias back (one cell, 10 points, sigma 0.02 m, 8 captures: RMS error 0.002 m at 5 sigma, 0.009 m
+    at 2.5 sigma, 0.033 m for the plain map).  `noise` = (sigma0, sigma2) (None: the sensor model's): a capture's standard deviation at
+    range r is sigma0 + sigma2 * r^2, r^2 = the cell's horizontal distance squared + `camera_height`^2 (None: the nominal mount's z plus
+    rewards.base_height_target); its variance is that squared over min(points, `count_cap`) plus `var_floor`.  `var_growth`: what a
+    cell's variance gains per tick it is not seen, up to `var_max`.  `gate`: a mean further than this many standard deviations from the
+    stored height replaces it instead of being fused (the surface changed; 0: every capture replaces)."""
+    FIELDS = ("band", "noise", "var_floor", "var_growth", "gate", "count_cap", "var_max", "camera_height")
+    TEXT = {"band": float, "noise": (float, ":", (2,)), "var_floor": float, "var_growth": float, "gate": float, "count_cap": int, "var_max": float,
+            "camera_height": float}
+
+    def __init__(self, band=None, noise=None, var_floor=2.5e-5, var_growth=1e-6, gate=3.0, count_cap=4, var_max=0.25, camera_height=None):
+        self.band = None if band is None else float(band)
+        self.noise = None if noise is None else (float(noise[0]), float(noise[1]))
+        self.var_floor, self.var_growth, self.gate, self.var_max = float(var_floor), float(var_growth), float(gate), float(var_max)
+        self.count_cap = int(count_cap)
+        self.camera_height = None if camera_height is None else float(camera_height)
+        values = (self.var_floor, self.var_growth, self.gate, self.var_max) + (() if self.noise is None else self.noise) + \
+            (() if self.camera_height is None else (self.camera_height,))
+        if any(not math.isfinite(v) or v < 0.0 for v in values) or self.var_floor > self.var_max or self.count_cap < 1:
+            raise ValueError(f"MapFusion: noise, var_floor <= var_max, var_growth, gate and camera_height are finite and >= 0 and count_cap >= 1, got {values}, {count_cap}")
+        if self.band is not None and not 0.0 <= self.band <= 0.5:
+            raise ValueError(f"MapFusion: band is None or in [0, 0.5] metres, got {band}")
+
+    def resolve(self, model_noise, camera_height):
+        """the by-value fields of lsim_elevation_map_fused_t, in its order, with the defaults taken from the sensor: (sigma0, sigma2,
+        range_z2, band, var_floor, var_growth, var_max, gate2, count_cap)"""
+        s0, s2 = model_noise if self.noise is None else self.noise
+        h = camera_height if self.camera_height is None else self.camera_height
+        z2 = h * h
+        band = min(max(5.0 * (s0 + s2 * (1.5 ** 2 + z2)), 0.02), 0.25) if self.band is None else self.band
+        return (s0, s2, z2, band, self.var_floor, self.var_growth, self.var_max, self.gate * self.gate, self.count_cap)
+
+
+def parse_map_fusion(text):
+    """MapFusion of 'band:0.1/gate:3/noise:0.01:0.002' (any subset of its fields, key:value joined by '/'; '1', '' or 'default': the
+    defaults): the form a fusion takes INSIDE the text of an elevation map, whose own separators are ',' and '='"""
+    if text in ("1", "", "default"):
+        return MapFusion()
+    return parse_option(MapFusion, ",".join(item.replace(":", "=", 1) for item in text.split("/")))
+
+
 class ElevationMap(_Option):
     """A robot-centred height grid per env, fused on the device from a sensor's captures (lsim_elevation_map; include/lsim.h states every
     formula).  `size`: cells per side, 16, 32 or 64; `resolution`: metres per cell (a power of two keeps the cell of a coordinate exact);
@@ -240,11 +291,17 @@ class ElevationMap(_Option):
     for every robot, the first config's: pass the value wanted).
     What attach_map refuses, because the launch cannot be right with it: a sensor with frame="yaw" (the launch places the points with the
     base's full orientation); a see_robot sensor without labels=True (the robot's own legs would be inserted as ground); with "noisy", a
-    model whose dropped pixels cannot be told from a range (dropout > 0 with drop_value strictly inside the clip range)."""
+    model whose dropped pixels cannot be told from a range (dropout > 0 with drop_value strictly inside the clip range).
+    `fusion` (a MapFusion, or its record): the launch is lsim_elevation_map_fused -- a cell is the mean of a capture's points near its
+    top, fused over the captures by a variance the map keeps per cell; None: the plain map, and nothing of that exists.  The record
+    carries the key "fusion" only when one is set."""
     FIELDS = ("size", "resolution", "source", "max_range", "points", "unknown_drop")
-    TEXT = {"size": int, "resolution": float, "source": str, "max_range": float, "unknown_drop": float}
+    TEXT = {"size": int, "resolution": float, "source": str, "max_range": float, "unknown_drop": float, "fusion": parse_map_fusion}
 
-    def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None):
+    def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None, fusion=None):
+        self.fusion = MapFusion(**fusion) if isinstance(fusion, dict) else fusion
+        if self.fusion is not None and not isinstance(self.fusion, MapFusion):
+            raise TypeError(f"ElevationMap: fusion is a MapFusion, its record or None, got {type(fusion).__name__}")
         self.size, self.resolution, self.source = int(size), float(resolution), str(source)
         self.max_range = None if max_range is None else float(max_range)
         self.unknown_drop = None if unknown_drop is None else float(unknown_drop)
@@ -260,8 +317,17 @@ class ElevationMap(_Option):
         if self.points is not None and not 1 <= len(self.points) <= abi.DEFINES["LSIM_ELEVATION_MAP_MAX_POINTS"]:
             raise ValueError(f"ElevationMap: 1 to {abi.DEFINES['LSIM_ELEVATION_MAP_MAX_POINTS']} points, got {len(self.points)}")
 
+    def record(self):
+        out = super().record()
+        if self.fusion is not None:
+            out["fusion"] = self.fusion.record()
+        return out
+
     def _shown(self, k):
         return repr(getattr(self, k) if k != "points" or self.points is None else len(self.points))     # the number of points, not the points
+
+    def __repr__(self):
+        return super().__repr__() if self.fusion is None else f"{super().__repr__()[:-1]}, fusion={self.fusion!r})"
 
 
 class OdometryError(_Option):
@@ -308,12 +374,15 @@ _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
 class Stage:
     """One launch of a sensor's chain.  `entry`: the name of the entry point it launches; `struct`: its ctypes struct (None: `run`, the
     launch of an encoder or a memory, builds its own); `buffers`: the tensors the stage allocated and nobody else owns, by name;
-    `option`: what it was attached with (the MountJitter, the ElevationMap, the encoder ...).  Dropping the stage drops all of them."""
+    `option`: what it was attached with (the MountJitter, the ElevationMap, the encoder ...).  Dropping the stage drops all of them.
+    `outer`: the struct the entry point takes when `struct` is a view of its first member (a fused map's lsim_elevation_map_fused_t
+    around the lsim_elevation_map_t everybody reads and writes the fields of)."""
 
-    def __init__(self, sensor, name, entry, struct, buffers=None, option=None, run=None):
-        self.name, self.entry, self.struct, self.option, self.args = name, entry, struct, option, ()
+    def __init__(self, sensor, name, entry, struct, buffers=None, option=None, run=None, outer=None):
+        self.name, self.entry, self.struct, self.option, self.args, self.outer = name, entry, struct, option, (), outer
         self.buffers = {} if buffers is None else buffers
-        self._sensor, self._run, self._ticks, self._ref = sensor, run, hasattr(struct, "tick"), None if struct is None else ctypes.byref(struct)
+        self._sensor, self._run, self._ticks = sensor, run, hasattr(struct, "tick")
+        self._ref = None if struct is None else ctypes.byref(struct if outer is None else outer)
 
     def launch(self, tick, flags, stream=None):
         """the launch on `stream` (default: the sensor's), with `tick` and `flags` where the entry point takes them"""
@@ -717,7 +786,8 @@ class RaySensor:
             lib.entry(self._api, "lsim_odometry_step", "the odometry")
         if self.model is None:
             raise ValueError("attach_map needs a model (SensorModel): the tick, the period and the episode lengths that say who captured are the model's")
-        lib.entry(self._api, "lsim_elevation_map", "the elevation map")
+        entry = "lsim_elevation_map" if m.fusion is None else "lsim_elevation_map_fused"
+        lib.entry(self._api, entry, "the elevation map")
         if self.frame != "base":
             raise ValueError(f"attach_map: the sensor's frame is {self.frame!r}; lsim_elevation_map places the points with the base's full orientation, "
                              "so only a frame='base' sensor can feed a map")
@@ -735,7 +805,15 @@ class RaySensor:
         mp = {"pts": torch.tensor(pts, dtype=torch.float32, device=self.out_rows.device).reshape(P, 2).contiguous(),
               "height": self._zeros(N, G, G), "stamp": self._zeros(N, G, G, dtype=torch.int32).fill_(-1), "cell": self._zeros(N, G, G, dtype=torch.int32),
               "scan": self._zeros(N, P), "known": self._zeros(N, P, dtype=torch.uint8), "state": self._zeros(1, dtype=torch.int64)}
-        em = abi.LsimElevationMap()
+        ef = None if m.fusion is None else abi.LsimElevationMapFused()
+        em = abi.LsimElevationMap() if ef is None else ef.em           # a view: the fused launch's struct opens with the plain one's
+        if ef is not None:
+            mp["var"], mp["scan_var"] = self._zeros(N, G, G), self._zeros(N, P)
+            ef.var, ef.scan_var, ef.var_stride = mp["var"].data_ptr(), mp["scan_var"].data_ptr(), P
+            height = float(self.mount_nominal[0, 2]) + float(env.cfg.rewards.base_height_target)
+            (ef.sigma0, ef.sigma2, ef.range_z2, ef.band, ef.var_floor, ef.var_growth, ef.var_max, ef.gate2,
+             ef.count_cap) = m.fusion.resolve(self.model.noise, height)
+            mp["scan_var"].fill_(float(ef.var_max))
         em.root_states, em.assumed_mount, em.dirs = env.root_states.data_ptr(), self.mount_nominal.data_ptr(), self.dirs.data_ptr()
         widest = narrowest = 1.0
         if self.scale is not None:
@@ -784,7 +862,7 @@ class RaySensor:
             od.scale_range, od.yaw_range, od.z_range, od.pos_noise, od.yaw_noise, od.z_noise = odometry.ranges()
             em.root_states = od.est
             launches.append(self._attach(Stage(self, "odometry", "lsim_odometry_step", od, held, odometry)))
-        launches.append(self._attach(Stage(self, "map", "lsim_elevation_map", em, mp, m)))
+        launches.append(self._attach(Stage(self, "map", entry, em, mp, m, outer=ef)))
         if self.tick >= 0:
             for s in launches:
                 s.launch(self.tick, _FILL_ALL)
@@ -803,25 +881,39 @@ class RaySensor:
         """live [N, 12] tensor: row e = {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0} of env e (lsim.h)"""
         return self._need("odometry").buffers["odo"]
 
-    def attach_map_rows(self, channels=("height",)):
+    def attach_map_rows(self, channels=("height",), var_ref=None):
         """from now on the map's launch of every update() / refresh() is followed by lsim_map_rows on the same stream: `map_rows()` is the
         live [N, len(channels) * P] tensor of the map's scan as an actor reads it -- ("height",): clip(map_pose z - 0.5 - scan, -1, 1) *
         obs_scales.height_measurements, the privileged height scan's expression; ("height", "known"): then map_known() as 0 / 1.  Needs
-        an attached map; builds the rows once now when the sensor has captured before.  None: detach and free."""
+        an attached map; builds the rows once now when the sensor has captured before.  None: detach and free.
+        ("height", "confidence") (lsim_map_rows_fused; needs a map with a fusion): then var_ref / (var_ref + map_variance()) where the
+        map knows the point and 0 where it does not -- 1/2 at a variance of `var_ref` (None: 16 times the fusion's var_floor)."""
         if channels is None:
             return self._drop("map_rows")
         channels = tuple(channels)
-        if channels not in (("height",), ("height", "known")):
-            raise ValueError(f"attach_map_rows: channels is ('height',) or ('height', 'known'), got {channels}")
+        if channels not in (("height",), ("height", "known"), ("height", "confidence")):
+            raise ValueError(f"attach_map_rows: channels is ('height',), ('height', 'known') or ('height', 'confidence'), got {channels}")
         em, mp = self._need("map").struct, self._need("map").buffers
-        lib.entry(self._api, "lsim_map_rows", "the map rows")
+        fused = channels[-1] == "confidence"
+        if fused and self.map.fusion is None:
+            raise ValueError("attach_map_rows: the channel 'confidence' needs a map with a fusion (ElevationMap(fusion=MapFusion(...)))")
+        if var_ref is not None and not fused:
+            raise ValueError("attach_map_rows: var_ref belongs to the channel 'confidence'")
+        entry = "lsim_map_rows_fused" if fused else "lsim_map_rows"
+        lib.entry(self._api, entry, "the map rows")
         P, C = int(em.num_points), len(channels)
         rows = self._zeros(int(self.env.num_envs), C * P)
-        mr = abi.LsimMapRows()
+        mf = abi.LsimMapRowsFused() if fused else None
+        mr = abi.LsimMapRows() if mf is None else mf.mr
+        if fused:
+            mf.scan_var, mf.var_stride = mp["scan_var"].data_ptr(), P
+            mf.var_ref = 16.0 * self.map.fusion.var_floor if var_ref is None else float(var_ref)
+            if not (math.isfinite(mf.var_ref) and mf.var_ref > 0.0):
+                raise ValueError(f"attach_map_rows: var_ref is finite and > 0, got {mf.var_ref} (a fusion with var_floor 0 needs one given)")
         mr.scan, mr.known, mr.pose, mr.rows = mp["scan"].data_ptr(), mp["known"].data_ptr(), self.map_pose().data_ptr(), rows.data_ptr()
         mr.num_points, mr.channels, mr.scan_stride, mr.known_stride, mr.ld = P, C, int(em.scan_stride), int(em.known_stride), C * P
         mr.z_offset, mr.scale = 0.5, float(self.env.lcfg.obs_scale_height)
-        stage = self._attach(Stage(self, "map_rows", "lsim_map_rows", mr, {"rows": rows}, channels))
+        stage = self._attach(Stage(self, "map_rows", entry, mr, {"rows": rows}, channels, outer=mf))
         if self.tick >= 0:
             stage.launch(self.tick, _FILL_ALL)
         return rows
@@ -839,9 +931,18 @@ class RaySensor:
         return self._need("map").buffers["known"]
 
     def map_state(self):
-        """the live raw arrays (height f32, stamp i32, cell: the u32 words held in an int32 tensor), each [N, G, G], toroidal (lsim.h)"""
+        """the live raw arrays (height f32, stamp i32, cell: the u32 words held in an int32 tensor, and with a fusion var f32), each
+        [N, G, G], toroidal (lsim.h)"""
         mp = self._need("map").buffers
-        return mp["height"], mp["stamp"], mp["cell"]
+        return (mp["height"], mp["stamp"], mp["cell"]) + ((mp["var"],) if "var" in mp else ())
+
+    def map_variance(self):
+        """live [N, P] tensor: the variance (m^2) of map_scan() at every scan point, aged to the last launch's tick; var_max where the map
+        knows nothing (an ElevationMap with a fusion only)"""
+        mp = self._need("map").buffers
+        if "scan_var" not in mp:
+            raise ValueError("the sensor's elevation map has no fusion (ElevationMap(fusion=MapFusion(...)))")
+        return mp["scan_var"]
 
     @property
     def map_nonfinite(self):

@@ -475,6 +475,26 @@ def parse_camera_instrument(text):
 
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 MAP_METRICS = ("map_scan_error", "map_coverage")        # accepted when named and the sensor carries an elevation map; never a default
+MAP_FUSION_METRICS = ("map_variance", "map_z2")         # likewise, of a map with a fusion (envs.sensors.MapFusion); dropped without one
+
+
+def _map_fusion_columns(env, cam):
+    """{name: fn} of MAP_FUSION_METRICS for a sensor whose map has a fusion, else {}.  "map_variance": the mean of cam.map_variance()
+    over the points the map knows; "map_z2": the mean over those points of (map scan - true height)^2 / variance, the truth being
+    LSIM_BUF_MEASURED_HEIGHTS moved by the error of the base height the map was given (odometry) -- 1 when the variance is honest.
+    An env whose map knows no point reports 0.  map_z2 needs the map's points to be the env's measured ones."""
+    if getattr(getattr(cam, "map", None), "fusion", None) is None:
+        return {}
+    known = lambda: cam.map_known().to(torch.float32)
+    over_known = lambda v: (v * known()).sum(dim=1) / known().sum(dim=1).clamp(min=1.0)
+    out = {"map_variance": lambda a, a0, live, priv: over_known(cam.map_variance())}
+    truth = env.buf.get("measured_heights") if hasattr(env, "buf") else None
+    if truth is not None and truth.shape[1] == cam.map_scan().shape[1]:
+        def z2(a, a0, live, priv):
+            err = cam.map_scan() - (truth + (cam.map_pose()[:, 2:3] - env.root_states[:, 2:3]))
+            return over_known(err.square() / cam.map_variance().clamp(min=1e-12))
+        out["map_z2"] = z2
+    return out
 
 
 def _run(env, ac, ev, steps, cmd, fused, packed_cls, rows=None, blind=False, metrics=()):
@@ -547,9 +567,9 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
     from .vision import PackedVisionPolicy
     metrics = list(metrics)
     for m in metrics:
-        if m not in VISION_METRICS + MAP_METRICS:
+        if m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS:
             raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error', "
-                             f"with an elevation map also 'map_scan_error' and 'map_coverage')")
+                             f"with an elevation map also 'map_scan_error' and 'map_coverage', with a fused one also 'map_variance' and 'map_z2')")
     has_map = getattr(cam, "map", None) is not None
     scan = _scan_block(env)
     needs = {"map_coverage": has_map, "map_scan_error": has_map and scan is not None and cam.map_scan().shape[1] == scan[1],
@@ -563,8 +583,9 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
         # the map's scan in observation units, exactly as ph_build_obs turns measured_heights into the block, from the height the map has
         "map_scan_error": lambda a, a0, live, priv: ((cam.map_pose()[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height) - target(priv)).square().mean(dim=1),
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
+    columns.update(_map_fusion_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.latent if memory is None else cam.memory_rows, blind,
-                [(m, columns[m]) for m in metrics if needs.get(m, True)])
+                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
 
 
 def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
@@ -578,6 +599,7 @@ def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
         "depth_influence": _influence(blind),
         "map_scan_error": lambda a, a0, live, priv: (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1),
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
+    columns.update(_map_fusion_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.map_rows, blind,
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
 
@@ -694,7 +716,9 @@ def parse_args(argv=None):
     ap.add_argument("--trace-envs", default="")
     ap.add_argument("--trace-out", default=None)
     ap.add_argument("--blind", action="store_true", help="a vision policy acts on a zero latent instead of its camera's")
-    ap.add_argument("--vision-metrics", default="depth_influence,scan_error", help="columns a vision policy adds to the result; empty: none")
+    ap.add_argument("--vision-metrics", default="depth_influence,scan_error",
+                    help="columns a vision policy adds to the result; empty: none.  A column whose inputs are missing is dropped, not zero: map_variance and "
+                         "map_z2 need a map with a fusion, and map_z2 also a map sampled at the env's own measured points (LSIM_BUF_MEASURED_HEIGHTS is its truth)")
     ap.add_argument("--camera-jitter", default="trained", help="a vision policy's per-episode camera mount error: 'trained' (the checkpoint's record), "
                     "'off' (the nominal mount) or pos=METRES,rot_deg=DEGREES (one number, or x/y/z)")
     ap.add_argument("--camera-instrument", default="trained", help="a vision policy's per-episode error of the camera's own constants: 'trained' (the "
@@ -722,8 +746,9 @@ def parse_args(argv=None):
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
     a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
-    if any(m not in VISION_METRICS + MAP_METRICS for m in a.vision_metrics):
-        ap.error(f"--vision-metrics: 'depth_influence', 'scan_error', 'memory_scan_error', 'map_scan_error' and / or 'map_coverage', got {a.vision_metrics}")
+    if any(m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS for m in a.vision_metrics):
+        ap.error(f"--vision-metrics: 'depth_influence', 'scan_error', 'memory_scan_error', 'map_scan_error' and / or 'map_coverage', got {a.vision_metrics}"
+                 " (a map with a fusion also has 'map_variance' and 'map_z2')")
     try:
         group_mask(a.group_by)
     except ValueError as exc:

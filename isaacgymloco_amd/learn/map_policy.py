@@ -17,7 +17,7 @@ import copy
 from .runner import _ALGOS, _POLICIES
 from .vision import ActorRowsPPO, ActorRowsRunner, VisionActorCritic
 
-CHANNELS = (("height",), ("height", "known"))
+CHANNELS = (("height",), ("height", "known"), ("height", "confidence"))
 
 
 class MapPPO(ActorRowsPPO):
@@ -28,7 +28,8 @@ class MapPPO(ActorRowsPPO):
 
 class MapOnPolicyRunner(ActorRowsRunner):
     """HIMOnPolicyRunner for a map policy.  `sensor`: the name of a sensor already added to the env (env.add_sensor), or the sensor; it needs
-    an attached ElevationMap (cam.attach_map, with or without odometry).  `channels`: ("height",) or ("height", "known"); the runner calls
+    an attached ElevationMap (cam.attach_map, with or without odometry).  `channels`: ("height",), ("height", "known") or, for a map with a
+    fusion, ("height", "confidence") -- how far each height can be trusted, lsim_map_rows_fused, under the width rule of two channels; the runner calls
     cam.attach_map_rows(channels) and the actor reads cam.map_rows(), channels * P more columns.  train_cfg is HIMOnPolicyRunner's;
     policy["depth_latent_dim"] is set here.  The fused policy launch takes a first actor layer of at most 272 columns: 187 points with
     one channel (251 columns), and with two channels a map of at most 104 points (ElevationMap(points=...), e.g. 11 x 9)."""
@@ -41,7 +42,9 @@ class MapOnPolicyRunner(ActorRowsRunner):
             raise ValueError("MapOnPolicyRunner: the sensor has no elevation map (cam.attach_map(ElevationMap(...)))")
         channels = tuple(channels)
         if channels not in CHANNELS:
-            raise ValueError(f"MapOnPolicyRunner: channels is ('height',) or ('height', 'known'), got {channels}")
+            raise ValueError(f"MapOnPolicyRunner: channels is ('height',), ('height', 'known') or ('height', 'confidence'), got {channels}")
+        if channels[-1] == "confidence" and getattr(cam.map, "fusion", None) is None:
+            raise ValueError("MapOnPolicyRunner: the channel 'confidence' needs a map with a fusion (ElevationMap(fusion=MapFusion(...)))")
         dim = len(channels) * int(cam.map_scan().shape[1])
         self._check_first_layer(env, **{"map rows": dim})
         _POLICIES["VisionActorCritic"], _ALGOS["MapPPO"] = VisionActorCritic, MapPPO

@@ -75,6 +75,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "sensor_mount_jitter_time.json": ("`tools/raycast_time.py --model … --mount-jitter 0.01,5`, N = 4096: `lsim_sensor_mount_jitter` alone (all / no env fresh), `lsim_sensor_capture` on jittered against nominal mounts with the parent commit's nominal columns of the same call; `tools/vision_train_time.py --mount-jitter`; `bench.py` alternating with the parent's tree", '7.13'),
               "sensor_instrument_time.json": ("`tools/raycast_time.py --model … --instrument latency=0:1,noise_gain=0.5:2,depth_scale=0.02,depth_quad=0.005,fov=0.02`, N = 4096, camera and lidar on flat ground and stairs: `lsim_sensor_capture` against `lsim_sensor_capture_inst` on neutral and on drawn rows, `lsim_sensor_instrument` alone (all / no env fresh), the parent commit's `lsim_sensor_capture` of the same call; `tools/vision_train_time.py --instrument`; `bench.py` alternating with the parent's tree", '7.14'),
               "elevation_map_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_elevation_map` alone over the same ticks (1 env in 5 due) and with every env due, `update()` with both; `bench.py` alternating with the parent's tree", '7.15'),
+              "elevation_fuse_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,fusion=default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_elevation_map_fused` (`map_us`, `map_all_due_us`) next to `lsim_elevation_map` of the same map on the same ticks (`plain_map_us`, `plain_map_all_due_us`), `update()` with the fused launch; `error_columns`: `evaluate`'s map columns for the plain and the fused map on 64 envs on stairs, same seeds; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.20'),
               "map_policy_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002 --map-rows 2`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_odometry_step` alone, `lsim_map_rows` alone and the torch statement of the same rows, `update()` with odometry, capture, map and rows; `bench.py` alternating with the parent's tree", '7.16'),
               "sensor_options_refactor_ab.json": ("parent commit against the commit that gave the sensor options one record, one text grammar and one resolver, `learn/evaluate.py` one step loop and `MapPPO` a base class of its own: `evaluate(...).result()` of a HIM, a vision (with and without memory) and a map policy under every form of `blind`, `camera_jitter`, `camera_instrument` and `odometry`, on the emulated env and on the device (equal), then a 500-step `evaluate()` at N = 4096 and `bench.py --gpus 1 --steps 1000 --warmup 100` in three alternating pairs each, with the parent's run-to-run spread, and the code lines of the four files", "7.16"),
               "sensor_chain_refactor_ab.json": ("parent commit against the commit that made every launch behind `RaySensor.update()` a stage of one chain (host-side Python only, the same library): SHA-256 of every sensor output tensor of twelve chain configurations at N = 8 and N = 4096 (equal), then `tools/raycast_time.py --model … --instrument … --map --odometry --map-rows 2` at N = 4096 and N = 64 and `tools/vision_train_time.py --memory` in five alternating pairs each and one `bench.py` pair, with the parent's run-to-run spread, the host time of `update()` with no-op launches and the code lines of the five files", "7.17"),

@@ -32,6 +32,8 @@ terrain, in one process and alternating `--repeats` times, each with its median 
 times it (the tick advancing, so a staggered period is averaged over whole periods); `map_us` = lsim_elevation_map alone over the same
 ticks, reading the rows the captures left; `map_all_due_us` = the same launch with LSIM_SENSOR_FILL_ALL (every env cleared and inserted);
 `update_with_map_us` = update() as a sensor with a map runs it in a step: the capture and the map's launch behind it.
+`--map ...,fusion=default` (or `fusion=band:0.1/gate:3`, sensors.parse_map_fusion): the map's launch is lsim_elevation_map_fused, and
+`plain_map_us` / `plain_map_all_due_us` time lsim_elevation_map of the same map on the same ticks, in the same repetition.
 `--map ... --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002` and / or `--map-rows 1|2` (the map policy's two
 launches; a measurement of its own, written to profiles/map_policy_time.json unless --out names another file): per terrain, in one process
 and alternating `--repeats` times, each with its median and range: `capture_us` as above; `odometry_us` = lsim_odometry_step alone, the tick
@@ -158,12 +160,24 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     torch.cuda.synchronize()
     cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
     cam.refresh(tick=0)
+    plain = None
+    if emap.fusion is not None:                  # ...,fusion=...: lsim_elevation_map of the same map is timed next to the fused launch, on the same ticks
+        cam.attach_map(sensors.ElevationMap(**{k: v for k, v in emap.record().items() if k != "fusion"}))
+        plain = cam.stage("map")                 # a Stage owns its struct and its tensors (Stage.buffers): held here, they outlive its place in the chain
     cam.attach_map(emap)
+    if plain is not None:
+        held = plain.buffers
+        assert all(getattr(plain.struct, k) == held[k].data_ptr() for k in ("height", "stamp", "cell", "scan", "known", "pts", "state")), "the plain map's stage lost its arrays"
     em = cam.stage("map").struct
     whole = max(model.period, iters // model.period * model.period)
     fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
     rows = {"capture_us": [], "map_us": [], "map_all_due_us": [], "update_with_map_us": []}
+    if plain is not None:
+        rows.update(plain_map_us=[], plain_map_all_due_us=[])
     for _ in range(repeats):
+        if plain is not None:
+            rows["plain_map_us"].append(timed_ticks(plain, whole, warmup))
+            rows["plain_map_all_due_us"].append(timed_ticks(plain, whole, warmup, fill_all))
         rows["capture_us"].append(timed_ticks(cam.stage("capture"), whole, warmup))      # the capture alone
         rows["map_us"].append(timed_ticks(cam.stage("map"), whole, warmup))
         rows["map_all_due_us"].append(timed_ticks(cam.stage("map"), whole, warmup, fill_all))
