@@ -56,7 +56,9 @@ extern "C" {
                                     lsim_latent_rows_grad (a minibatch's latent gradients summed per logged image);
                                     lsim_distill_loss (a minibatch's action means against a teacher's, gathered through the shuffle's permutation);
                                     lsim_elevation_map_fused (the elevation map with a banded mean per capture and a variance per cell, fused over the
-                                    captures by a scalar Kalman filter) and lsim_map_rows_fused (the map's rows with a confidence block) */
+                                    captures by a scalar Kalman filter) and lsim_map_rows_fused (the map's rows with a confidence block);
+                                    lsim_sensor_stereo + lsim_sensor_stereo_sizes + LSIM_RNG_SENSOR_STEREO (a stereo camera's occlusion shadows, minimum
+                                    range and depth-edge artefacts, written into the frame history behind a capture) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -179,9 +181,11 @@ enum lsim_rng_tag {
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: position x y z and rotation x, block 1: rotation y z, two words unused */
     LSIM_RNG_SENSOR_INSTRUMENT = 17, /* lsim_sensor_instrument (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: latency, noise gain, depth scale, depth quad, block 1: tan scale, three words unused */
-    LSIM_RNG_ODOMETRY = 18     /* lsim_odometry_step (no reference site): step word = (uint32) tick, the fourth counter word =
+    LSIM_RNG_ODOMETRY = 18,    /* lsim_odometry_step (no reference site): step word = (uint32) tick, the fourth counter word =
                                   (stream_id << 16) | b, b = 0, 1 -- block 0: the step's yaw, position and height noise, one word unused,
                                   block 1: the episode's scale, yaw and height bias, one word unused */
+    LSIM_RNG_SENSOR_STEREO = 19 /* lsim_sensor_stereo (no reference site): step word = (uint32) tick, the fourth counter word =
+                                  (stream_id << 16) | pixel -- one block per pixel, the first word used */
 };
 
 /* ---- robot model: the URDF after Isaac Gym's fixed-joint collapse ----
@@ -1334,6 +1338,85 @@ int lsim_sensor_instrument(const lsim_sensor_instrument_t* si, void* stream);
  *   is lsim_sensor_capture's shift.
  * LSIM_E_INVALID, checked on the host before any launch: everything lsim_sensor_capture refuses; inst NULL or not 16-byte aligned. */
 int lsim_sensor_capture_inst(const lsim_sensor_model_t* sm, const float* inst, void* stream);
+
+/* ---- stereo artefacts: what a stereo pair does to the image lsim_sensor_capture reports -- no depth where only one imager sees (occlusion
+ * shadows), none below a minimum range, and depth edges that lose pixels or smear the foreground over the background.  ONE launch under the
+ * rules of lsim_sensor_capture (caller's stream, no host synchronisation, raw pointers only, capturable in a graph).  Enqueued BEHIND a
+ * capture on the same stream, with its tick, period, stagger, flags, episode_length, seed, rank and stream_id, it visits the same envs and
+ * rewrites pixels of the history slots that capture just wrote.  It reads the clean depth rows (rb.rc.out of a z-depth camera), the labels
+ * when there are any, episode_length and optionally the instrument rows; it reads and writes hist, adds to state, and writes nothing else.
+ *
+ * The image.  R = width * height pixels, r = row * width + c, rows top to bottom, columns left to right.  The image belongs to the LEFT
+ *   imager; the second one sits `baseline` metres to its RIGHT.  fb = (focal length in pixels) * baseline, formed once on the host.
+ * Which envs.  Env e is visited when e % env_stride == 0; fill and due are lsim_sensor_capture's, on the same fields.  For an env that is
+ *   not due NOTHING is written.
+ * Per pixel r of a due env, all arithmetic in fp32, every quotient correctly rounded, no two operations fused; the result is a function of
+ * the stored bits of depth:
+ *   1. Z = depth[e * depth_stride + r];   t = inv_scale ? Z * inv_scale[r] : Z
+ *      valid = |Z| <= FLT_MAX  and  t_lo < t  and  t < t_hi  and  (labels == NULL or labels[e * label_stride + r] != 0)
+ *      (lsim_elevation_map's rule for a range, with any label but "nothing")
+ *   2. fbe = (inst && inst[8 e + 4] != 1.0f) ? fb / inst[8 e + 4] : fb            (the instrument's tan_scale shortens the focal length)
+ *      delta = fbe / Z;      u = (float)c - delta        (the column at which the second imager sees the point)
+ *   3. shadowed:  valid, and some column c' with c < c' <= min(width - 1, c + window) of the same row is valid and has u(c') <= u(c)
+ *      (the second imager's ray to this pixel passes behind a nearer surface; a surface both imagers see keeps u strictly increasing along
+ *      a row and casts nothing; a foreground object shadows the background on its LEFT side only)
+ *   4. too near:  valid and delta > max_disparity                                 (such a pixel still occludes others)
+ *   5. edge:  valid, not shadowed, not too near, and some valid pixel r' of the image within Chebyshev distance edge_radius of r has
+ *      Z(r') < Z(r) * (1 - edge_rel)   (1 - edge_rel rounded, then the product rounded).  The pixel's FOREGROUND is the r' of smallest Z
+ *      among those, on ties the smallest index r'.
+ *   6. x0..x3 = Philox4x32-10, key (seed, rank), counter (e, (uint32_t)tick, LSIM_RNG_SENSOR_STEREO, (stream_id << 16) | r);  u0 = (x0 >> 8) * 2^-24
+ *   7. HOLE when shadowed, or too near, or (edge and u0 < p_edge_hole);  else FATTEN when edge and u0 < p_edge_cum  (p_edge_cum is the fp32
+ *      sum p_edge_hole + p_edge_fatten, formed on the host);  else the pixel is kept.
+ *   8. a hole writes y_hole = (min(max(drop_value, clip_lo), clip_hi) - offset) * gain, what the capture writes for a dropped pixel;
+ *      a fattened pixel writes the value the CAPTURE wrote to slot K - 1 of its foreground pixel, K = latency + frames -- whether this
+ *      launch rewrites that foreground pixel too plays no part; a kept pixel writes nothing.  The value goes to the slots the capture
+ *      wrote its y to:  every k < K under fill;  otherwise k = Ke - 1 .. K - 1, Ke = K without inst and
+ *      Ke = min(max((int) inst[8 e], 0), latency) + frames with it (lsim_sensor_capture_inst's rule).
+ *   9. state[0] += the holes written, state[1] += the fattened pixels (int64, cumulative).
+ * With fb = 0, max_disparity = FLT_MAX and both probabilities 0 the launch writes nothing.  Two launches on the same inputs write the same
+ * bits (no floating-point atomic; the draw depends on (e, tick, stream_id, r) and the key only).  tick is by value, as the capture's.
+ * NOT BUILT: a projector or texture model, holes correlated over regions, the firmware's filters, a vertical baseline. */
+#define LSIM_STEREO_MAX_WINDOW 128
+#define LSIM_STEREO_MAX_LDS_BYTES 163840
+typedef struct lsim_sensor_stereo {
+    const float* depth;               /* row e starts at depth + e * depth_stride and holds R clean z-depths; read only, 4-byte aligned */
+    const uint8_t* labels;            /* [N,label_stride] the capture's labels, or NULL */
+    const float* inv_scale;           /* [R] 1 / the sensor's scale, or NULL: 1; 4-byte aligned */
+    const int64_t* episode_length;    /* [N] LSIM_BUF_EPISODE_LENGTH, read only, 8-byte aligned */
+    const float* inst;                /* [N,8] lsim_sensor_instrument's rows, 16-byte aligned, or NULL */
+    float* hist;                      /* [N, K, hist_stride] the capture's, K = latency + frames, 16-byte aligned */
+    void* state;                      /* 2 int64, 8-byte aligned, zeroed by the caller: [0] holes written, [1] pixels fattened */
+    int64_t tick;                     /* >= 0, by value: the capture's */
+    int64_t depth_stride;             /* floats between rows of depth: >= R */
+    int32_t label_stride;             /* bytes between rows of labels: >= R (ignored when labels == NULL) */
+    int32_t hist_stride;              /* the capture's: >= R, a multiple of 4 */
+    int32_t latency, frames;          /* the capture's: latency >= 0, frames >= 1, latency + frames <= LSIM_SENSOR_MAX_HISTORY */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    int32_t width, height;            /* >= 1; R = width * height must be an image lsim_sensor_stereo_sizes accepts */
+    int32_t period, stagger;          /* the capture's */
+    uint32_t flags;                   /* the capture's: 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY */
+    uint32_t seed, rank, stream_id;   /* the capture's; stream_id < 65536 */
+    float fb;                         /* focal length in pixels * baseline in metres: finite, >= 0 */
+    float max_disparity;              /* pixels: > 0 (FLT_MAX or infinity: no minimum range) */
+    int32_t window;                   /* columns searched for an occluder: 1 .. LSIM_STEREO_MAX_WINDOW */
+    float t_lo, t_hi;                 /* 0 <= t_lo < t_hi: the ranges that carry a depth */
+    int32_t edge_radius;              /* 0 .. 3 (0: no edge artefacts) */
+    float edge_rel;                   /* finite, 0 <= edge_rel < 1 */
+    float p_edge_hole, p_edge_cum;    /* 0 <= p_edge_hole <= p_edge_cum <= 1 */
+    float drop_value, clip_lo, clip_hi, offset, gain;   /* the capture's: finite, clip_lo <= clip_hi */
+} lsim_sensor_stereo_t;
+/* bytes of dynamic LDS the launch needs for a width x height image (Z, u and the value to write as floats, the outcome as a byte, per pixel,
+ * and two counters).  LSIM_E_INVALID: lds_bytes NULL, width or height < 1, or a plan above LSIM_STEREO_MAX_LDS_BYTES (R > 12601). */
+int lsim_sensor_stereo_sizes(int32_t width, int32_t height, size_t* lds_bytes);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: st == NULL; depth or hist NULL or
+ * misaligned (4 and 16 bytes); inv_scale given and not 4-byte aligned; inst given and not 16-byte aligned; episode_length or state NULL or
+ * not 8-byte aligned; width or height < 1 or an image lsim_sensor_stereo_sizes refuses; depth_stride < R; labels given with
+ * label_stride < R; hist_stride < R or not a multiple of 4; latency < 0; frames < 1; latency + frames > LSIM_SENSOR_MAX_HISTORY;
+ * num_envs < 1; env_stride < 1; tick < 0; stream_id >= 65536; period < 1; stagger outside 0..1; a flag bit other than the sensor model's
+ * two, or both; window outside 1..LSIM_STEREO_MAX_WINDOW; edge_radius outside 0..3; fb, edge_rel, p_edge_hole or p_edge_cum negative or
+ * not finite; edge_rel >= 1; p_edge_cum > 1 or < p_edge_hole; max_disparity <= 0 or NaN; t_lo < 0, t_lo >= t_hi (or either NaN);
+ * drop_value, clip_lo, clip_hi, offset or gain not finite; clip_lo > clip_hi. */
+int lsim_sensor_stereo(const lsim_sensor_stereo_t* st, void* stream);
 
 /* ---- elevation map: a robot-centred 2.5-D height grid per env, filled from the depth rows of a sensor's captures and the robot's own pose,
  * and sampled at the points of the height scan.  ONE launch under the rules of lsim_sensor_capture (caller's stream, no host

@@ -113,6 +113,7 @@ LsimRaycastPrim = STRUCTS["lsim_raycast_prim"]
 LsimSensorModel = STRUCTS["lsim_sensor_model_t"]
 LsimSensorMountJitter = STRUCTS["lsim_sensor_mount_jitter_t"]
 LsimSensorInstrument = STRUCTS["lsim_sensor_instrument_t"]
+LsimSensorStereo = STRUCTS["lsim_sensor_stereo_t"]
 LsimElevationMap = STRUCTS["lsim_elevation_map_t"]
 LsimOdometry = STRUCTS["lsim_odometry_t"]
 LsimMapRows = STRUCTS["lsim_map_rows_t"]

@@ -45,6 +45,13 @@ a field of view a little wider or narrower.  One small launch ahead of every cap
 just reset, on the device, and the capture is lsim_sensor_capture_inst, which reads them.  spec() records the ranges and from_spec()
 rebuilds them.  Without `instrument` nothing of this is created or launched and the capture is lsim_sensor_capture.
 
+Stereo artefacts (`stereo=StereoArtifacts(baseline=0.05)`, lsim_sensor_stereo; a pinhole camera with a model): a stereo pair reports no
+depth for what only one of its imagers sees, none below a minimum range, and its matcher loses or smears depth edges.  One launch directly
+behind every capture, same stream, tick and flags, rewrites those pixels of the frame history the capture just wrote -- holes read the
+model's drop_value, a fattened pixel its foreground's captured value -- so frames(), the encoder, the frame log and a "noisy" map all
+see them; `out` / image() stay clean and `cam.stereo_counts()` counts holes and fattened pixels.  spec() records the option and
+from_spec() rebuilds it.  Without `stereo` nothing of this is created or launched.
+
 Elevation map (`cam.attach_map(ElevationMap(size=32, resolution=0.0625, source="noisy"))`, lsim_elevation_map; needs a model): what a robot
 runs next to, or instead of, a learned terrain memory -- per env a robot-centred grid of heights, filled from the depth points of every
 capture with the robot's own pose, which remembers the ground under the trunk after the camera has moved on.  One launch behind every
@@ -157,6 +164,7 @@ def parse_option(cls, text):
 
 
 _flag = lambda v: bool(int(v))
+_or_none = lambda conv: lambda v: None if v.lower() == "none" else conv(v)       # a field whose default is "derived": the text 'none' asks for it
 
 
 class SensorModel(_Option):
@@ -230,6 +238,42 @@ class InstrumentError(_Option):
         values = self.noise_gain + (self.depth_scale, self.depth_quad, self.fov)
         if len(noise_gain) != 2 or any(not math.isfinite(x) or x < 0.0 for x in values) or self.noise_gain[0] > self.noise_gain[1] or self.fov >= 1.0:
             raise ValueError(f"InstrumentError: finite 0 <= noise_gain[0] <= noise_gain[1], depth_scale >= 0, depth_quad >= 0 and 0 <= fov < 1, got {values}")
+
+
+class StereoArtifacts(_Option):
+    """What a stereo pair does to the image (lsim_sensor_stereo behind the capture; include/lsim.h states every formula).  The image is the
+    LEFT imager's; the second one sits `baseline` metres to its right, and a pixel only one of them sees has no depth: to the left of every
+    near object lies a band of holes as wide as the disparity difference between foreground and background.  `max_disparity` (pixels;
+    None: no limit): a nearer pixel has no match and is a hole too; `window` (columns; None: what the nearest range can shadow, at most
+    128): how far an occluder is searched; `max_range` (None: 0.98 far): the largest range that carries a depth; a pixel within
+    `edge_radius` (0..3, Chebyshev) of a valid pixel nearer than (1 - `edge_rel`) times its own depth loses its depth with probability
+    `edge_hole` and takes that foreground's value with probability `edge_fatten` (the matcher's window smearing the foreground over the edge).
+    The defaults are STATED GUESSES: 0.05 m is the baseline of a D435-class camera, and the edge figures are fitted to nothing -- no
+    recorded frames of a real camera were at hand."""
+    FIELDS = ("baseline", "max_disparity", "window", "max_range", "edge_radius", "edge_rel", "edge_hole", "edge_fatten")
+    TEXT = {"baseline": float, "max_disparity": _or_none(float), "window": _or_none(int), "max_range": _or_none(float), "edge_radius": int,
+            "edge_rel": float, "edge_hole": float, "edge_fatten": float}
+
+    def __init__(self, baseline=0.05, max_disparity=None, window=None, max_range=None, edge_radius=1, edge_rel=0.05, edge_hole=0.25, edge_fatten=0.25):
+        self.baseline, self.edge_rel, self.edge_hole, self.edge_fatten = float(baseline), float(edge_rel), float(edge_hole), float(edge_fatten)
+        self.max_disparity = None if max_disparity is None else float(max_disparity)
+        self.max_range = None if max_range is None else float(max_range)
+        self.window, self.edge_radius = None if window is None else int(window), int(edge_radius)
+        wmax = abi.DEFINES["LSIM_STEREO_MAX_WINDOW"]
+        values = (self.baseline, self.edge_rel, self.edge_hole, self.edge_fatten)
+        if any(not math.isfinite(x) or x < 0.0 for x in values) or self.edge_rel >= 1.0 or self.edge_hole + self.edge_fatten > 1.0:
+            raise ValueError(f"StereoArtifacts: finite baseline >= 0, 0 <= edge_rel < 1, edge_hole >= 0, edge_fatten >= 0 and edge_hole + edge_fatten <= 1, got {values}")
+        if self.max_disparity is not None and not self.max_disparity > 0.0:
+            raise ValueError(f"StereoArtifacts: max_disparity is None or > 0, got {max_disparity}")
+        if self.max_range is not None and not (math.isfinite(self.max_range) and self.max_range > 0.0):
+            raise ValueError(f"StereoArtifacts: max_range is None or finite and > 0, got {max_range}")
+        if (self.window is not None and not 1 <= self.window <= wmax) or not 0 <= self.edge_radius <= 3:
+            raise ValueError(f"StereoArtifacts: window is None or 1 .. {wmax} and edge_radius 0 .. 3, got {window}, {edge_radius}")
+
+
+def parse_stereo(text):
+    """a StereoArtifacts of 'baseline=0.05,edge_hole=0.25,window=none,...' ('' or 'default': the defaults): the text the tools take"""
+    return parse_option(StereoArtifacts, text)
 
 
 class MapFusion(_Option):
@@ -362,11 +406,13 @@ def parse_elevation_map(text):
 
 
 _ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "map_rows", "encoder", "memory")      # a chain's launch order
-_BEHIND = {"frames_log": "capture"}         # a training buffer's stage is no part of the instrument: launched directly behind the stage named
+# launched directly behind the stage named, in this order: the stereo artefacts rewrite what the capture wrote before anybody reads it
+# (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument
+_BEHIND = {"stereo": "capture", "frames_log": "capture"}
 _LAUNCH_ORDER = tuple(n for o in _ORDER for n in (o,) + tuple(k for k, v in _BEHIND.items() if v == o))
 _DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory", "frames_log")}                                # who goes with whom
 _ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
-           "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
+           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
            "memory": "memory (attach_memory)", "frames_log": "frame log (attach_frames_log)"}
 _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
 
@@ -416,6 +462,9 @@ class RaySensor:
     `instrument` (an InstrumentError; needs a model): `instrument_rows()` is the live [N, 8] tensor of each env's own latency, noise gain,
     depth-scale error and field-of-view factor, which lsim_sensor_instrument rewrites ahead of every capture for the envs that start an
     episode, and the capture is lsim_sensor_capture_inst.  With `instrument=None` there is no such tensor and no such launch.
+    `stereo` (a StereoArtifacts; a pinhole camera with a model): lsim_sensor_stereo directly behind every capture rewrites the pixels of the
+    frame history a stereo pair has no or a wrong depth for; `set_stereo(opt | None)`, `stereo_counts()` the live [2] int64 of holes and
+    fattened pixels.  With `stereo=None` nothing of this is allocated or launched.
     `attach_map(m)` (an ElevationMap; needs a model): lsim_elevation_map behind every capture; `map_scan()` / `map_known()` are the live
     [N, P] samples, `map_heights()` a window-ordered copy for people and tools, `map_state()` the three raw arrays.  Without it nothing
     of this is allocated or launched.  `attach_map(m, odometry=OdometryError(...))`: lsim_odometry_step ahead of every capture, and the map
@@ -433,10 +482,10 @@ class RaySensor:
     `label_rows`: the padded tensors `out` / `labels()` are views of; `history()`: the raw frame history."""
 
     mount_jitter, instrument, map, odometry, map_channels = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "map_rows"))
-    encoder, memory = _option("encoder"), _option("memory")
+    encoder, memory, stereo = _option("encoder"), _option("memory"), _option("stereo")
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None, stereo=None):
         self.env = env
         self.model = model
         self._api = api if api is not None else env._L
@@ -500,6 +549,8 @@ class RaySensor:
             self.set_mount_jitter(mount_jitter)
         if instrument is not None:
             self.set_instrument(instrument)
+        if stereo is not None:
+            self.set_stereo(stereo)
 
     # ---- the chain
     def chain(self):
@@ -559,6 +610,8 @@ class RaySensor:
         cap, inst = self._stages.get("capture"), self._stages.get("instrument")
         if cap is not None:                 # the capture that reads the instrument's rows, or the plain one
             cap.entry, cap.args = ("lsim_sensor_capture", ()) if inst is None else ("lsim_sensor_capture_inst", (inst.buffers["inst"].data_ptr(),))
+        if "stereo" in self._stages:        # the artefacts follow the instrument's focal length and latency, or the model's own
+            self._stages["stereo"].struct.inst = None if inst is None else inst.buffers["inst"].data_ptr()
         self._chain = tuple(self._stages[n] for n in _LAUNCH_ORDER if n in self._stages)
 
     def _kept(self, name, make):
@@ -600,6 +653,67 @@ class RaySensor:
     def instrument_rows(self):
         """live [N, 8] tensor: row e = {latency, noise gain, depth_scale, depth_quad, tan_scale, 0, 0, 0} of env e (instrument=...)"""
         return self._need("instrument").buffers["inst"]
+
+    def _holes_tellable(self, who, source, stereo):
+        """the map's rule for source="noisy": a hole -- a dropped pixel or a stereo artefact -- must read as a clamped value, never as a range"""
+        sm = self._stages["capture"].struct
+        clip_lo, clip_hi = float(sm.clip_lo), float(sm.clip_hi)
+        drop = min(max(float(sm.drop_value), clip_lo), clip_hi)
+        if source == "noisy" and (float(sm.p_drop) > 0.0 or stereo is not None) and clip_lo < drop < clip_hi:
+            raise ValueError(f"{who}: source='noisy' with dropout or stereo artefacts needs a drop_value at or beyond a clip limit; {drop} lies inside "
+                             f"({clip_lo}, {clip_hi}) and a dropped pixel could not be told from a range")
+
+    def _tan_half_hfov(self):
+        """the tangent of half the horizontal field of view of a pinhole camera: from hfov_deg, or from the recorded rays (pinhole_dirs' layout)"""
+        if getattr(self, "hfov_deg", None) is not None:
+            return math.tan(math.radians(self.hfov_deg) / 2.0)
+        d = self.dirs[0].cpu().double()
+        return float(d[1] / d[0]) / (1.0 - 1.0 / self.width)
+
+    def set_stereo(self, stereo):
+        """`stereo` (a StereoArtifacts) from now on, or None: no launch and no buffers.  It applies from the next capture: nothing is
+        launched here, whatever the sensor has captured before"""
+        if stereo is None:
+            return self._drop("stereo")
+        if not isinstance(stereo, StereoArtifacts):
+            raise TypeError(f"stereo: expected a StereoArtifacts or None, got {type(stereo).__name__}")
+        if self.model is None:
+            raise ValueError("stereo needs a model (SensorModel): the artefacts are written into the model's frame history")
+        if self.kind["kind"] != "camera" or self.scale is None or self.width < 2:
+            raise ValueError("stereo needs a pinhole depth camera at least two columns wide (depth_camera): a lidar has no second imager")
+        for need in ("lsim_sensor_stereo", "lsim_sensor_stereo_sizes"):
+            lib.entry(self._api, need, "the stereo artefacts")
+        W, H, lds = self.width, self.height, ctypes.c_size_t()
+        if self._api.lsim_sensor_stereo_sizes(W, H, ctypes.byref(lds)) != 0:
+            raise ValueError(f"stereo: a {W} x {H} image needs more LDS than lsim_sensor_stereo has ({abi.DEFINES['LSIM_STEREO_MAX_LDS_BYTES']} bytes)")
+        if "map" in self._stages:
+            self._holes_tellable("set_stereo", self.map.source, stereo)
+        buffers = self._kept("stereo", lambda: {"state": self._zeros(2, dtype=torch.int64), "inv_scale": (1.0 / self.scale).contiguous()})
+        sm, inv = self._stages["capture"].struct, buffers["inv_scale"]
+        st = abi.LsimSensorStereo()
+        st.depth, st.depth_stride, st.inv_scale, st.state = self.out_rows.data_ptr(), self.out_rows.shape[1], inv.data_ptr(), buffers["state"].data_ptr()
+        if self.label_rows is not None:
+            st.labels, st.label_stride = self.label_rows.data_ptr(), self.label_rows.shape[1]
+        for f in ("hist", "hist_stride", "latency", "frames", "period", "stagger", "drop_value", "clip_lo", "clip_hi", "offset", "gain"):
+            setattr(st, f, getattr(sm, f))
+        st.width, st.height = W, H
+        fb = (W / 2.0) / self._tan_half_hfov() * stereo.baseline
+        nearest = self.near * float(self.scale.min())               # the smallest z-depth the camera reports
+        widest = math.ceil(fb / nearest) + 1 if nearest > 0.0 and math.isfinite(fb / nearest) else abi.DEFINES["LSIM_STEREO_MAX_WINDOW"]
+        st.fb = fb
+        st.window = max(1, min(W - 1, abi.DEFINES["LSIM_STEREO_MAX_WINDOW"], widest) if stereo.window is None else min(stereo.window, W - 1))
+        st.max_disparity = float(np.finfo(np.float32).max) if stereo.max_disparity is None else stereo.max_disparity
+        st.t_lo = self.near * float(inv.max())
+        st.t_hi = (0.98 * self.far if stereo.max_range is None else stereo.max_range) * float(inv.min())
+        if not st.t_lo < st.t_hi:
+            raise ValueError(f"stereo: no range is left between near ({st.t_lo}) and max_range ({st.t_hi})")
+        st.edge_radius, st.edge_rel, st.p_edge_hole = stereo.edge_radius, stereo.edge_rel, stereo.edge_hole
+        st.p_edge_cum = min(float(np.float32(stereo.edge_hole) + np.float32(stereo.edge_fatten)), 1.0)
+        self._attach(Stage(self, "stereo", "lsim_sensor_stereo", st, buffers, stereo))
+
+    def stereo_counts(self):
+        """live [2] int64 tensor: the holes written and the pixels fattened so far (stereo=...)"""
+        return self._need("stereo").buffers["state"]
 
     def set_mount_jitter(self, jitter):
         """`jitter` (a MountJitter) from now on, or None: back to the nominal mount and no launch.  The new poses are drawn by the next
@@ -775,7 +889,8 @@ class RaySensor:
         Which ranges are points: above `near` and below max_range (None: 0.98 far) -- and for "noisy", whose values the model clamps to
         [clip_lo, clip_hi], misses and dropped pixels included, also strictly inside that range for every ray: a value AT a clip limit is
         a clamped one and never a point (so a hit beyond clip_hi is dropped, not inserted at clip_hi).
-        Refused (ElevationMap's docstring): frame="yaw", see_robot without labels, a drop_value inside the clip range."""
+        Refused (ElevationMap's docstring): frame="yaw", see_robot without labels, a drop_value inside the clip range with dropout or
+        with stereo artefacts (set_stereo() checks the same on a sensor that has its map already)."""
         if m is None:
             return self._drop("map")
         if not isinstance(m, ElevationMap):
@@ -842,10 +957,7 @@ class RaySensor:
             # reads it back through (1 / gain, offset) with a rounding of 2-3 ulp of offset and far: 2^-20 of that magnitude lies well
             # above it.  A value within that margin of a clip limit is a clamped one, never a point
             clip_lo, clip_hi = float(sm.clip_lo), float(sm.clip_hi)
-            drop = min(max(float(sm.drop_value), clip_lo), clip_hi)
-            if float(sm.p_drop) > 0.0 and clip_lo < drop < clip_hi:
-                raise ValueError(f"attach_map: source='noisy' with dropout needs a drop_value at or beyond a clip limit; {drop} lies inside "
-                                 f"({clip_lo}, {clip_hi}) and a dropped pixel could not be told from a range")
+            self._holes_tellable("attach_map", m.source, self.stereo)
             margin = 2.0 ** -20 * max(self.far, abs(float(sm.offset)), abs(clip_hi))
             d_lo, d_hi = max(self.near, clip_lo) + margin, clip_hi - margin
         em.t_lo = d_lo * widest
@@ -1102,8 +1214,8 @@ class RaySensor:
         dirs, scale, near, far, env_stride, see_robot, the names of the ignored bodies, labels, frame, the SensorModel's fields (None
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
-        one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's and
-        "odometry" the OdometryError the map was attached with, each absent without one."""
+        one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's,
+        "odometry" the OdometryError the map was attached with and "stereo" a StereoArtifacts', each absent without one."""
         out = dict(self.kind)
         out["dirs"] = self.dirs.cpu().tolist()
         out["scale"] = None if self.scale is None else self.scale.cpu().tolist()
@@ -1121,7 +1233,7 @@ class RaySensor:
             out["mount"] = {n: pose(r[0]) for n, r in zip(names, rows) if len(r)}
         else:
             out["mount"] = None
-        for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry)):
+        for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry), ("stereo", self.stereo)):
             if option is not None:
                 out[key] = option.record()
         return out
@@ -1138,6 +1250,7 @@ class DepthCamera(RaySensor):
     def __init__(self, env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None,
                  rays=None, mount_quat=None, **options):
         dirs, scale = pinhole_dirs(width, height, hfov_deg) if rays is None else rays
+        self.hfov_deg = None if rays is not None else float(hfov_deg)
         super().__init__(env, dirs, mount_pos, quat_from_pitch(pitch_deg) if mount_quat is None else mount_quat, near, far, scale=scale,
                          env_stride=env_stride, api=api, kind={"kind": "camera", "width": width, "height": height}, **options)
 
@@ -1156,7 +1269,7 @@ class DepthCamera(RaySensor):
 
 def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None, **options):
     """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and `options` (see_robot, ignore_bodies,
-    labels, frame, model, mount_jitter, instrument) as RaySensor's"""
+    labels, frame, model, mount_jitter, instrument, stereo) as RaySensor's"""
     return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api, **options)
 
 
@@ -1172,12 +1285,13 @@ def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mo
 _KIND_KEYS = {"rays": (), "camera": ("width", "height"), "lidar": ("channels", "points_per_rev")}
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec"):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec", stereo="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
     (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor),
-    `odometry` for the OdometryError that map is attached with (without a map it has nothing to act on)."""
+    `odometry` for the OdometryError that map is attached with (without a map it has nothing to act on), `stereo` for the recorded
+    StereoArtifacts."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -1200,10 +1314,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     model = option("model", "spec", SensorModel, "model")
     mount_jitter, instrument = option("mount_jitter", mount_jitter, MountJitter, "mount_jitter"), option("instrument", instrument, InstrumentError, "instrument")
     elevation_map, odometry = option("elevation_map", elevation_map, ElevationMap, "map"), option("odometry", odometry, OdometryError, "odometry")
+    stereo = option("stereo", stereo, StereoArtifacts, "stereo")
     kind = spec.get("kind", "rays") if spec.get("kind") in _KIND_KEYS else "rays"
     dirs, scale = np.asarray(spec["dirs"], dtype=np.float32), None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32)
     options = dict(env_stride=spec["env_stride"], api=api, see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"],
-                   frame=spec["frame"], model=model, mount_jitter=mount_jitter, instrument=instrument)
+                   frame=spec["frame"], model=model, mount_jitter=mount_jitter, instrument=instrument, stereo=stereo)
     if kind == "camera":                    # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
         sensor = DepthCamera(env, spec["width"], spec["height"], None, pos, near=spec["near"], far=spec["far"], rays=(dirs, scale), mount_quat=quat, **options)
     else:

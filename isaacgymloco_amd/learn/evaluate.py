@@ -422,8 +422,8 @@ def _sensor_option(cam, record, value, cls, key, name, apply):
     return dict(dict.fromkeys(cls.FIELDS) if want is None else want.record(), choice=choice)
 
 
-def _sensor_options(cam, record, camera_jitter, camera_instrument, odometry):
-    """the three options of evaluate() in their order -- behind the encoder and the memory, whose launches a refresh() runs too -- as the
+def _sensor_options(cam, record, camera_jitter, camera_instrument, odometry, camera_stereo="trained"):
+    """the four options of evaluate() in their order -- behind the encoder and the memory, whose launches a refresh() runs too -- as the
     entries of the result's conventions.  A camera whose jitter or instrument changes has every env's mount or row redrawn and history
     refilled once (refresh()); a map whose odometry changes is attached anew: it starts empty, every env's drift at zero, and is filled
     once from the present capture.  A sensor without a map has no odometry entry."""
@@ -442,6 +442,7 @@ def _sensor_options(cam, record, camera_jitter, camera_instrument, odometry):
 
     out = {"camera_jitter": _sensor_option(cam, record, camera_jitter, sensors.MountJitter, "mount_jitter", "camera_jitter", redrawn(cam.set_mount_jitter)),
            "camera_instrument": _sensor_option(cam, record, camera_instrument, sensors.InstrumentError, "instrument", "camera_instrument", redrawn(cam.set_instrument))}
+    out["camera_stereo"] = _sensor_option(cam, record, camera_stereo, sensors.StereoArtifacts, "stereo", "camera_stereo", redrawn(cam.set_stereo))
     if getattr(cam, "map", None) is not None:
         out["odometry"] = _sensor_option(cam, record, odometry, sensors.OdometryError, "odometry", "odometry", reattached)
     return out
@@ -471,6 +472,12 @@ def parse_camera_instrument(text):
     """the command line's --camera-instrument: "trained", "off" (None), or "latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F"
     (any key may be left out: the model's latency, gain 1, 0)"""
     return _parse_choice(sensors.InstrumentError, text)
+
+
+def parse_camera_stereo(text):
+    """the command line's --camera-stereo: "trained", "off" (None), or "baseline=B,max_disparity=D,window=W,max_range=R,edge_radius=N,edge_rel=E,
+    edge_hole=P,edge_fatten=Q" (any key may be left out: envs.sensors.StereoArtifacts' defaults)"""
+    return _parse_choice(sensors.StereoArtifacts, text)
 
 
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
@@ -622,7 +629,7 @@ def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, expli
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
              sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained",
-             camera_instrument="trained", odometry="trained"):
+             camera_instrument="trained", odometry="trained", camera_stereo="trained"):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -643,6 +650,8 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     conventions["camera_jitter"].
     `camera_instrument` (a vision policy only): the same choice for the per-episode error of the camera's own constants
     (envs.sensors.InstrumentError: latency, noise gain, depth-scale error, field of view), written to conventions["camera_instrument"].
+    `camera_stereo` (likewise): the same choice for the stereo pair's artefacts -- occlusion shadows, minimum range, depth-edge holes and
+    fattening (envs.sensors.StereoArtifacts) --, written to conventions["camera_stereo"].
     A map policy (a MapOnPolicyRunner, its checkpoint -- recognised by its "map_policy" record, from which sensor, map and rows are rebuilt
     when the env has none -- or a VisionActorCritic with a `sensor` whose map rows are attached and no encoder anywhere) reads
     cam.map_rows(); `blind=True` feeds zeros; "depth_influence" is the action distance against zero rows and "map_scan_error" the mean
@@ -669,7 +678,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
             cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
         d = found.get("checkpoint") or {}
         record = (d.get("map_policy") or d.get("vision") or {}).get("sensor")        # the checkpoint's record of the sensor; None: a runner, a module
-        conventions = _sensor_options(cam, record, camera_jitter, camera_instrument, odometry)
+        conventions = _sensor_options(cam, record, camera_jitter, camera_instrument, odometry, camera_stereo)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     cmd = None
     if commands is not None:
@@ -723,12 +732,15 @@ def parse_args(argv=None):
                     "'off' (the nominal mount) or pos=METRES,rot_deg=DEGREES (one number, or x/y/z)")
     ap.add_argument("--camera-instrument", default="trained", help="a vision policy's per-episode error of the camera's own constants: 'trained' (the "
                     "checkpoint's record), 'off' or latency=LO:HI,noise_gain=LO:HI,depth_scale=S,depth_quad=Q,fov=F (any subset)")
+    ap.add_argument("--camera-stereo", default="trained", help="a vision policy's stereo artefacts (occlusion shadows, depth-edge holes and fattening): "
+                    "'trained' (the checkpoint's record), 'off' or baseline=B,max_disparity=D,window=W,max_range=R,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q (any subset)")
     ap.add_argument("--odometry", default="trained", help="the dead-reckoning error of the pose an elevation map is placed with: 'trained' (the "
                     "checkpoint's record), 'off' or scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c (any subset)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
-    for name, parse in (("camera_instrument", parse_camera_instrument), ("odometry", parse_odometry), ("camera_jitter", parse_camera_jitter)):
+    for name, parse in (("camera_instrument", parse_camera_instrument), ("odometry", parse_odometry), ("camera_jitter", parse_camera_jitter),
+                        ("camera_stereo", parse_camera_stereo)):
         try:
             setattr(a, name, parse(getattr(a, name)))
         except ValueError as exc:
@@ -785,7 +797,8 @@ def main(argv=None):
     if "scan_policy" in d and not named:       # a scan policy has no vision metrics: the option's default means none, a named one is refused
         a.vision_metrics = ()
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
-                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry)
+                  vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry,
+                  camera_stereo=a.camera_stereo)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

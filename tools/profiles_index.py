@@ -74,6 +74,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "raycast_refactor_ab.json": ("parent commit against the commit that folded the copies of the range-sensor chain's ray routines and stores into one: digests of every output array of the four ray launches on the test scenes and at N = 4096 (bit-identical), then `tools/raycast_time.py` (plain and `--instrument`) in five alternating pairs and one `bench.py` pair, with the parent's run-to-run spread", '7.7'),
               "sensor_mount_jitter_time.json": ("`tools/raycast_time.py --model … --mount-jitter 0.01,5`, N = 4096: `lsim_sensor_mount_jitter` alone (all / no env fresh), `lsim_sensor_capture` on jittered against nominal mounts with the parent commit's nominal columns of the same call; `tools/vision_train_time.py --mount-jitter`; `bench.py` alternating with the parent's tree", '7.13'),
               "sensor_instrument_time.json": ("`tools/raycast_time.py --model … --instrument latency=0:1,noise_gain=0.5:2,depth_scale=0.02,depth_quad=0.005,fov=0.02`, N = 4096, camera and lidar on flat ground and stairs: `lsim_sensor_capture` against `lsim_sensor_capture_inst` on neutral and on drawn rows, `lsim_sensor_instrument` alone (all / no env fresh), the parent commit's `lsim_sensor_capture` of the same call; `tools/vision_train_time.py --instrument`; `bench.py` alternating with the parent's tree", '7.14'),
+              "sensor_stereo_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --stereo default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_stereo` alone (`stereo_us`, `stereo_all_due_us`) next to the capture alone on the same ticks (`capture_us`, `capture_all_due_us`), `update()` without and with the option, the share of a whole capture's pixels the stage rewrites; `counts`: `stereo_counts()` of 64 envs on stairs over 30 steps; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.21'),
               "elevation_map_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_elevation_map` alone over the same ticks (1 env in 5 due) and with every env due, `update()` with both; `bench.py` alternating with the parent's tree", '7.15'),
               "elevation_fuse_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,fusion=default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_elevation_map_fused` (`map_us`, `map_all_due_us`) next to `lsim_elevation_map` of the same map on the same ticks (`plain_map_us`, `plain_map_all_due_us`), `update()` with the fused launch; `error_columns`: `evaluate`'s map columns for the plain and the fused map on 64 envs on stairs, same seeds; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.20'),
               "map_policy_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002 --map-rows 2`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_odometry_step` alone, `lsim_map_rows` alone and the torch statement of the same rows, `update()` with odometry, capture, map and rows; `bench.py` alternating with the parent's tree", '7.16'),

@@ -34,6 +34,12 @@ ticks, reading the rows the captures left; `map_all_due_us` = the same launch wi
 `update_with_map_us` = update() as a sensor with a map runs it in a step: the capture and the map's launch behind it.
 `--map ...,fusion=default` (or `fusion=band:0.1/gate:3`, sensors.parse_map_fusion): the map's launch is lsim_elevation_map_fused, and
 `plain_map_us` / `plain_map_all_due_us` time lsim_elevation_map of the same map on the same ticks, in the same repetition.
+`--model ... --stereo default` (or `--stereo baseline=0.05,edge_hole=0.25,...`, sensors.parse_stereo; a measurement of its own, written to
+profiles/sensor_stereo_time.json unless --out names another file): per terrain, in one process and alternating `--repeats` times, each
+with its median and range: `capture_us` / `capture_all_due_us` = the capture alone over whole periods and with LSIM_SENSOR_FILL_ALL;
+`stereo_us` / `stereo_all_due_us` = lsim_sensor_stereo alone over the same ticks, on the rows the captures left; `update_us` and
+`update_with_stereo_us` = update() of a camera without and with the option; `hole_share` / `fattened_share` = the share of one whole
+capture's pixels the stage rewrites (stereo_counts()).
 `--map ... --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002` and / or `--map-rows 1|2` (the map policy's two
 launches; a measurement of its own, written to profiles/map_policy_time.json unless --out names another file): per terrain, in one process
 and alternating `--repeats` times, each with its median and range: `capture_us` as above; `odometry_us` = lsim_odometry_step alone, the tick
@@ -188,6 +194,46 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
         out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
     out["map_over_capture"] = out["map_us"] / out["capture_us"]
     out["nonfinite"] = int(cam.nonfinite_rays.item()) + int(cam.map_nonfinite.item())
+    return out
+
+
+def measure_stereo(n, terrain, iters, warmup, model, stereo, repeats):
+    """the --stereo measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    env.episode_length_buf[:] = 20               # nobody is fresh inside the timed loops: the period alone decides who is due
+    torch.cuda.synchronize()
+    make = lambda **kw: sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True,
+                                             model=model, **kw)
+    plain, cam = make(), make(stereo=stereo)
+    plain.refresh(tick=0)
+    cam.refresh(tick=0)
+    st = cam.stage("stereo").struct
+    whole = max(model.period, iters // model.period * model.period)
+    fill_all = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
+    rows = {"capture_us": [], "capture_all_due_us": [], "stereo_us": [], "stereo_all_due_us": [], "update_us": [], "update_with_stereo_us": []}
+    for _ in range(repeats):
+        rows["capture_us"].append(timed_ticks(cam.stage("capture"), whole, warmup))      # the capture alone
+        rows["capture_all_due_us"].append(timed_ticks(cam.stage("capture"), whole, warmup, fill_all))
+        rows["stereo_us"].append(timed_ticks(cam.stage("stereo"), whole, warmup))        # the stage alone, over the same ticks, on the rows the captures left
+        rows["stereo_all_due_us"].append(timed_ticks(cam.stage("stereo"), whole, warmup, fill_all))
+        rows["update_us"].append(timed_ticks(plain, whole, warmup))
+        rows["update_with_stereo_us"].append(timed_ticks(cam, whole, warmup))
+    counts = cam.stereo_counts().clone()
+    cam.refresh(tick=0)                          # one capture of every env: the share of its pixels the stage rewrites
+    torch.cuda.synchronize()
+    holes, fat = ((cam.stereo_counts() - counts).double() / (n * cam.num_rays)).tolist()
+    out = {"num_envs": n, "terrain": terrain, "rays": cam.num_rays, "fb": float(st.fb), "window": int(st.window), "hole_share": holes, "fattened_share": fat}
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    out["stereo_over_capture"] = out["stereo_us"] / out["capture_us"]
+    out["nonfinite_rays"] = int(cam.nonfinite_rays.item())
     return out
 
 
@@ -371,7 +417,9 @@ def main():
     ap.add_argument("--odometry", default=None, nargs="?", const="default", help="scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c (any subset): with --map, time "
                     "lsim_odometry_step next to the capture")
     ap.add_argument("--map-rows", type=int, default=None, choices=(1, 2), help="with --map, time lsim_map_rows with this many channels against its torch statement")
-    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map: alternating repetitions of every timed loop")
+    ap.add_argument("--stereo", default=None, nargs="?", const="default", help="baseline=B,max_disparity=D,window=W,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q "
+                    "(any subset; 'default'): time lsim_sensor_stereo next to the capture it follows (needs --model)")
+    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map / --stereo: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -387,6 +435,18 @@ def main():
         if a.out:
             with open(a.out, "w") as f:
                 f.write(line + "\n")
+        print(line)
+        return
+    if a.stereo is not None:
+        if not a.model:
+            ap.error("--stereo needs --model")
+        model, stereo = parse_model(a.model), sensors.parse_stereo(a.stereo)
+        res = {"tool": "raycast_time --stereo", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot, labels", "model": a.model, "stereo": stereo.record(),
+               "cases": [measure_stereo(a.num_envs, t, a.iters, a.warmup, model, stereo, a.repeats) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        with open(a.out or os.path.join(ROOT, "profiles", "sensor_stereo_time.json"), "w") as f:
+            f.write(line + "\n")
         print(line)
         return
     if a.map:

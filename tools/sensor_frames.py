@@ -9,7 +9,11 @@ Steps the env under a checkpoint's actor (learn/evaluate.py's loader) or zero ac
 same two as 8-bit PGM (depth: near = white, far = black; labels: spread over the grey range).  A PGM is a text header plus raw bytes.
 `--map [size=32,resolution=0.0625,source=clean]`: the robot also carries the forward camera of the vision tasks (64 x 48, 0.3 m ahead, pitched
 30 degrees down) with an elevation map (sensors.ElevationMap), and `map_e<env>_s<step>.npy` (float32 [G, G], window order, NaN = unknown)
-and `.pgm` (unknown black, then low = dark to high = white over the map's own range) are written next to the frames."""
+and `.pgm` (unknown black, then low = dark to high = white over the map's own range) are written next to the frames.
+`--stereo [baseline=0.05,edge_hole=0.25,...]` (sensors.parse_stereo): the robot carries that forward camera as a stereo pair
+(sensors.StereoArtifacts, see_robot and labels on), and `stereo_e<env>_s<step>.npy` / `.pgm` hold what it reports -- the newest frame with
+the occlusion shadows, the minimum range and the depth-edge artefacts, holes at the near end of the grey range -- next to the clean
+`front_e<env>_s<step>.npy` / `.pgm`."""
 import argparse
 import os
 import sys
@@ -65,6 +69,8 @@ def main():
     ap.add_argument("--pitch", type=float, default=28.0)
     ap.add_argument("--far", type=float, default=5.0)
     ap.add_argument("--map", default=None, nargs="?", const="source=clean", help="also write an elevation map: size=G,resolution=RES,source=noisy|clean")
+    ap.add_argument("--stereo", default=None, nargs="?", const="default", help="also write the forward camera's frames with stereo artefacts: "
+                    "baseline=B,max_disparity=D,window=W,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q (any subset)")
     a = ap.parse_args()
     import torch
     from isaacgymloco_amd.envs import config as C, sensors
@@ -80,6 +86,10 @@ def main():
         front = env.add_sensor("front", sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=a.far,
                                                              model=sensors.SensorModel()))
         front.attach_map(sensors.parse_elevation_map(a.map))
+    pair = None
+    if a.stereo is not None:
+        pair = env.add_sensor("stereo", sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=a.far, see_robot=True,
+                                                             labels=True, model=sensors.SensorModel(), stereo=sensors.parse_stereo(a.stereo)))
     env.reset()
     policy = None
     if a.checkpoint:
@@ -95,8 +105,12 @@ def main():
         if step % a.every == 0 or step == a.steps:
             depth, labels = cam.image().cpu().numpy(), cam.label_image().cpu().numpy()
             heights = None if front is None else front.map_heights().cpu().numpy()
+            seen = None if pair is None else (pair.frame_images()[:, -1].cpu().numpy(), pair.image().cpu().numpy())
             for e in ids:
                 stem = f"e{e}_s{step:04d}"
+                for name, img in (() if seen is None else (("stereo", seen[0][e]), ("front", seen[1][e]))):
+                    np.save(os.path.join(a.out, f"{name}_{stem}.npy"), img)
+                    write_pgm(os.path.join(a.out, f"{name}_{stem}.pgm"), depth_to_gray(img, pair.near, pair.far))
                 if heights is not None:
                     np.save(os.path.join(a.out, f"map_{stem}.npy"), heights[e])
                     write_pgm(os.path.join(a.out, f"map_{stem}.pgm"), map_to_gray(heights[e]))
