@@ -94,8 +94,7 @@ static inline int ls_de_validate(const lsim_depth_encoder_t* de, LsDePlan& p) {
     if (de->final_act < 0 || de->final_act > 1) return LSIM_E_INVALID;
     if (de->latent_stride < de->latent_dim || (de->latent_stride & 3) != 0) return LSIM_E_INVALID;
     if (de->tick < 0 || de->period < 1 || de->stagger < 0 || de->stagger > 1) return LSIM_E_INVALID;
-    if ((de->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((de->flags & LSIM_SENSOR_FILL_ALL) && (de->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(de->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
 static inline int ls_de_sizes(const lsim_depth_encoder_t* de, size_t* lds_bytes) {
@@ -104,8 +103,8 @@ static inline int ls_de_sizes(const lsim_depth_encoder_t* de, size_t* lds_bytes)
     *lds_bytes = (size_t)p.words * 4u;
     return LSIM_OK;
 }
-static inline uint32_t ls_de_tick_mod(const lsim_depth_encoder_t& de) { return (uint32_t)(de.tick % (int64_t)de.period); }
-static inline int ls_de_env_slots(const lsim_depth_encoder_t& de) { return (de.num_envs + de.env_stride - 1) / de.env_stride; }
+static inline uint32_t ls_de_tick_mod(const lsim_depth_encoder_t& de) { return ls_sensor_tick_mod(de.tick, de.period); }
+static inline int ls_de_env_slots(const lsim_depth_encoder_t& de) { return ls_sensor_env_slots(de.num_envs, de.env_stride); }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
 #define LS_DE_GLOBAL __attribute__((address_space(1)))

@@ -56,7 +56,7 @@ static inline int ls_gru_tiles(int n) { return (n + LS_GRU_TILE - 1) / LS_GRU_TI
 // ---- index arithmetic and the cell's scalar math, shared by the kernels and the CPU shim
 LS_RC_FN int ls_gru_unit(int ht, int q, int r) { return ht * 16 + 4 * q + r; }                      // the unit of D row 4 q + r of hidden tile ht
 LS_RC_FN size_t ls_gru_at(int t, int n, int env, int width) { return ((size_t)t * (size_t)n + (size_t)env) * (size_t)width; }       // row (t, env) of a [T, n, width] array
-LS_RC_FN bool ls_gru_fresh(uint32_t flags, const int64_t* episode_length, int env) { return (flags & LSIM_SENSOR_FILL_ALL) != 0u || episode_length[env] == 0; }
+LS_RC_FN bool ls_gru_fresh(uint32_t flags, const int64_t* episode_length, int env) { return ls_sensor_fresh(flags, episode_length, env); }
 LS_RC_FN bool ls_gru_stepped(uint32_t flags, bool fresh) { return fresh || (flags & LSIM_SENSOR_RESETS_ONLY) == 0u; }
 LS_RC_FN float ls_gru_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 // pre-activations -> (r, u, n, h'); gh_n without r applied
@@ -87,8 +87,7 @@ static inline int ls_dm_validate(const lsim_depth_memory_t* dm, LsGruPlan& p) {
     if (dm->proprio_dim > 0 && (!ls_rc_aligned(dm->p, 4) || dm->p_ld < dm->proprio_dim)) return LSIM_E_INVALID;
     if (dm->z_ld < dm->latent_dim || dm->h_ld < dm->hidden) return LSIM_E_INVALID;
     if (dm->rows && (!ls_rc_aligned(dm->rows, 4) || dm->rows_ld < dm->latent_dim + dm->hidden)) return LSIM_E_INVALID;
-    if ((dm->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((dm->flags & LSIM_SENSOR_FILL_ALL) && (dm->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(dm->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
 static inline int ls_gs_validate(const lsim_gru_sequence_t* gs, bool backward, LsGruPlan& p) {

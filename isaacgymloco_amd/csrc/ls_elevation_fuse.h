@@ -1,18 +1,23 @@
 // ls_elevation_fuse.h -- the elevation map with a variance per cell (include/lsim.h, lsim_elevation_map_fused) and the map rows with a
 // confidence block (lsim_map_rows_fused).  lsim.h states every formula; this file is that text in code.
 //
-// It stands on ls_elevation_map.h, whose pose, fill, cell / slot / key helpers, scan geometry and argument check it uses unchanged, and on
-// ls_odometry.h for the first block of the rows.  tests/emu/emu_elevation_fuse.cpp compiles this file with g++ under LS_EMU and runs the same
-// per-lane functions, the lanes looped and the LDS arrays plain arrays.
+// It stands on ls_elevation_map.h and restates nothing of it: the pose, the fill, the cell / slot / key helpers, the point of a ray
+// (ls_em_point, behind both passes here), the window's cell of a slot (ls_em_window_cell), the scan's lookup (ls_em_lookup) and the
+// argument check are that file's own functions, so a change to how a depth sample becomes a map point, or to how a scan point finds its cell,
+// is made in that file alone (where the point's text stands twice, side by side: ls_em_insert says why).  What is here is what the variance
+// adds: the two passes around the point, the fusion, and the variance next to the scan.  Compared against the commit that still had a text per launch:
+// profiles/elevation_refactor_ab.json.  It stands on ls_odometry.h for the first block of the rows.
+// tests/emu/emu_elevation_fuse.cpp compiles this file with g++ under LS_EMU and runs the same per-lane functions, the lanes looped and the LDS
+// arrays plain arrays.
 //
 // Shape of the launch (lsim_k_elevation_map_fused): lsim_k_elevation_map's -- ONE workgroup of 256 lanes per visited env -- with
 // 3 * G * G * 4 bytes of dynamic LDS (3, 12 or 48 KB): the keys, an int32 sum and an int32 count per slot.
 //   0. the pose and ls_sensor_due;   1. fill: the stamps to -1;
-//   2. due: the three LDS arrays to 0, barrier; pass 1 over the rays (r = lane, lane + 256, ...), each kept point one ds_max_u32 on its
-//      slot's key; barrier; pass 2 over the same rays, the point formed again by the same code (nothing is cached: 16 K rays would need
+//   2. due: the three LDS arrays to 0, barrier; pass 1 over the rays (r = lane, lane + 256, ...), each kept point one ds_max_u32
+//      on its slot's key; barrier; pass 2 over the same rays, the point formed again by ls_em_point (nothing is cached: 16 K rays would need
 //      scratch), each point within the band one ds_add_u32 on the slot's sum and one on its count; barrier; the lanes sweep the slots, and a
 //      touched one reads its three words and var, fuses, and writes four dwords;
-//   3. barrier; lane j < P looks its scan point up as lsim_k_elevation_map does and reads var too: one more load and one more store.
+//   3. barrier; lane j < P looks its scan point up with ls_em_lookup, as lsim_k_elevation_map does, and reads var too: one more load and one more store.
 // Only 32-bit integer LDS atomics, no float atomic: integer sums do not depend on the order of the rays.  Every branch around a barrier is on
 // values the whole workgroup shares (env, fill, due, the pose).
 #pragma once
@@ -25,50 +30,31 @@ LS_RC_FN void ls_ef_add(int32_t* p, int32_t v) { *p += v; }
 LS_RC_FN void ls_ef_add(int32_t* p, int32_t v) { (void)atomicAdd(p, v); }
 #endif
 
-// ray r of the env as a point of the map: lsim_elevation_map's rules (ls_em_insert), operation for operation.  false: not kept
-LS_RC_FN bool ls_ef_point(const lsim_elevation_map_t& em, const LsEmPose& s, const float* row, const uint8_t* lab, int r, float rinv, int& slot, float& zout) {
-    const int G = em.size, half = G >> 1;
-    const float d = em.a * row[r] + em.b;
-    const float t = em.inv_scale ? d * em.inv_scale[r] : d;
-    if (!ls_rc_finite(d) || !(em.t_lo < t) || !(t < em.t_hi)) return false;
-    if (lab && lab[r] != (uint8_t)1) return false;
-    const LsRcV3 v = ls_rc_v3(em.dirs[3 * r] * t, em.dirs[3 * r + 1] * t, em.dirs[3 * r + 2] * t);
-    const LsRcV3 m = ls_rc_rot(s.ax, s.ay, s.az, s.aw, v);
-    const LsRcV3 b = ls_rc_rot(s.qx, s.qy, s.qz, s.qw, ls_rc_v3(s.mx + m.x, s.my + m.y, s.mz + m.z));
-    const float x = s.px + b.x, y = s.py + b.y, z = s.pz + b.z;
-    if (!ls_rc_finite(x) || !ls_rc_finite(y) || !ls_rc_finite(z)) return false;
-    const float fx = ls_em_cellf(x, rinv), fy = ls_em_cellf(y, rinv);
-    if (!ls_em_in_range(fx) || !ls_em_in_range(fy)) return false;
-    const int ix = (int)fx, iy = (int)fy, dx = ix - s.cx, dy = iy - s.cy;
-    if (dx < -half || dx >= half || dy < -half || dy >= half) return false;
-    slot = ls_em_slot(ix, iy, G);
-    zout = z;
-    return true;
-}
-
 LS_RC_FN void ls_ef_lds_clear(const lsim_elevation_map_t& em, uint32_t* keys, int32_t* sum, int32_t* cnt, int lane) {
     const int G2 = em.size * em.size;
     for (int s = lane; s < G2; s += LS_EM_BLOCK) { keys[s] = 0u; sum[s] = 0; cnt[s] = 0; }
 }
 
-// pass 1: this lane's rays into the keys
+// pass 1: this lane's rays into the keys.  Both passes form the point with ls_em_point, so pass 2 never meets a slot or a height that pass 1
+// did not: ls_em_insert's own text (ls_elevation_map.h says why it has one) is kept out of this kernel
 LS_RC_FN void ls_ef_pass_max(const lsim_elevation_map_t& em, const LsEmPose& s, int env, int lane, float rinv, uint32_t* keys) {
     const float* row = em.depth + (size_t)env * (size_t)em.depth_stride;
     const uint8_t* lab = em.labels ? em.labels + (size_t)env * (size_t)em.label_stride : (const uint8_t*)0;
     for (int r = lane; r < em.num_rays; r += LS_EM_BLOCK) {
         int slot; float z;
-        if (ls_ef_point(em, s, row, lab, r, rinv, slot, z)) ls_em_max(keys + slot, ls_em_key(z));
+        if (ls_em_point(em, s, row, lab, r, rinv, slot, z)) ls_em_max(keys + slot, ls_em_key(z));
     }
 }
 
-// pass 2: the same rays again; a point within `band` of its slot's maximum joins the slot's sum and count
+// pass 2: the same rays again, each point formed by ls_em_point as pass 1 formed it; a point within `band` of its
+// slot's maximum joins the slot's sum and count
 LS_RC_FN void ls_ef_pass_sum(const lsim_elevation_map_fused_t& ef, const LsEmPose& s, int env, int lane, float rinv, const uint32_t* keys, int32_t* sum, int32_t* cnt) {
     const lsim_elevation_map_t& em = ef.em;
     const float* row = em.depth + (size_t)env * (size_t)em.depth_stride;
     const uint8_t* lab = em.labels ? em.labels + (size_t)env * (size_t)em.label_stride : (const uint8_t*)0;
     for (int r = lane; r < em.num_rays; r += LS_EM_BLOCK) {
         int slot; float z;
-        if (!ls_ef_point(em, s, row, lab, r, rinv, slot, z)) continue;
+        if (!ls_em_point(em, s, row, lab, r, rinv, slot, z)) continue;
         const float df = ls_em_unkey(keys[slot]) - z;
         if (!(df <= ef.band)) continue;
         ls_ef_add(sum + slot, (int32_t)(df * 65536.0f + 0.5f));
@@ -81,14 +67,13 @@ LS_RC_FN float ls_ef_age(int64_t tick, int32_t stamp) { return (float)(((uint32_
 // the touched slots: the measurement, then the fusion with what the slot held
 LS_RC_FN void ls_ef_commit(const lsim_elevation_map_fused_t& ef, const LsEmPose& s, int env, int lane, const uint32_t* keys, const int32_t* sum, const int32_t* cnt) {
     const lsim_elevation_map_t& em = ef.em;
-    const int G = em.size, G2 = G * G, half = G >> 1;
+    const int G = em.size, G2 = G * G;
     const size_t base = (size_t)env * (size_t)G2;
-    const int wx = s.cx - half, wy = s.cy - half;
     for (int k = lane; k < G2; k += LS_EM_BLOCK) {
         const uint32_t key = keys[k];
         if (key == 0u) continue;
-        const int sx = k / G, sy = k - sx * G;
-        const int ix = wx + ((sx - wx) & (G - 1)), iy = wy + ((sy - wy) & (G - 1));
+        int ix, iy;
+        ls_em_window_cell(s, G, k, ix, iy);
         const uint32_t word = ls_em_pack(ix, iy);
         const float zmax = ls_em_unkey(key);
         const int32_t n = cnt[k];
@@ -120,11 +105,10 @@ LS_RC_FN void ls_ef_commit(const lsim_elevation_map_fused_t& ef, const LsEmPose&
     }
 }
 
-// this lane's scan points: ls_em_scan's lookup, and the variance next to the height
+// this lane's scan points: ls_em_scan with the aged variance next to the height
 LS_RC_FN void ls_ef_scan(const lsim_elevation_map_fused_t& ef, const LsEmPose& s, int env, int lane, float rinv) {
     const lsim_elevation_map_t& em = ef.em;
-    const int G = em.size;
-    const size_t base = (size_t)env * (size_t)(G * G);
+    const size_t base = (size_t)env * (size_t)(em.size * em.size);
     float* scan = em.scan + (size_t)env * (size_t)em.scan_stride;
     float* svar = ef.scan_var + (size_t)env * (size_t)ef.var_stride;
     uint8_t* known = em.known + (size_t)env * (size_t)em.known_stride;
@@ -135,20 +119,14 @@ LS_RC_FN void ls_ef_scan(const lsim_elevation_map_fused_t& ef, const LsEmPose& s
             known[j] = (uint8_t)0;
             continue;
         }
-        const float n = ls_div_exact(1.0f, ls_sqrt_exact(s.qz * s.qz + s.qw * s.qw));
-        const LsRcV3 o = ls_rc_rot(0.0f, 0.0f, s.qz * n, s.qw * n, ls_rc_v3(em.pts[2 * j], em.pts[2 * j + 1], 0.0f));
-        const float fx = ls_em_cellf(s.px + o.x, rinv), fy = ls_em_cellf(s.py + o.y, rinv);
+        int32_t stamp;
+        const int k = ls_em_lookup(em, s, j, base, rinv, stamp);
         float h = s.pz - em.unknown_drop, v = ef.var_max;
         uint8_t kn = (uint8_t)0;
-        if (ls_em_in_range(fx) && ls_em_in_range(fy)) {
-            const int ix = (int)fx, iy = (int)fy;
-            const size_t k = base + (size_t)ls_em_slot(ix, iy, G);
-            const int32_t stamp = em.stamp[k];
-            if (stamp >= 0 && em.cell[k] == ls_em_pack(ix, iy)) {
-                h = em.height[k];
-                v = fminf(ef.var[k] + ef.var_growth * ls_ef_age(em.tick, stamp), ef.var_max);       // fminf: a NaN operand yields the other
-                kn = (uint8_t)1;
-            }
+        if (k >= 0) {
+            kn = (uint8_t)1;
+            h = em.height[base + (size_t)k];
+            v = fminf(ef.var[base + (size_t)k] + ef.var_growth * ls_ef_age(em.tick, stamp), ef.var_max);       // fminf: a NaN operand yields the other
         }
         scan[j] = h;
         svar[j] = v;

@@ -2,7 +2,7 @@
 // from the depth rows a capture just wrote and the robot's own pose, and sampled at the points of the height scan.  lsim.h states every
 // formula; this file is that text in code.
 //
-// Self-contained like ls_sensor_mount_jitter.h (lsim.h, the helpers of ls_raycast.h, the due rule of ls_sensor_model.h, ls_math.h and the C
+// Self-contained like ls_sensor_mount_jitter.h (lsim.h, the helpers of ls_raycast.h, the visit rule of ls_sensor_model.h, ls_math.h and the C
 // library): tests/emu/emu_elevation_map.cpp compiles this file with g++ under LS_EMU and runs the same per-lane functions, the lanes looped and
 // the LDS array a plain array.
 //
@@ -71,7 +71,36 @@ LS_RC_FN void ls_em_keys_clear(const lsim_elevation_map_t& em, uint32_t* keys, i
     for (int s = lane; s < G2; s += LS_EM_BLOCK) keys[s] = 0u;
 }
 
-// step 2, first half: this lane's rays into the keys
+// ray r of the env as a point of the map (row, lab: the env's depth row and label row, or null).  false: not kept; true: its slot and world
+// height.  Both passes of the fused map (ls_elevation_fuse.h) call it; ls_em_insert below holds the same text once more
+LS_RC_FN bool ls_em_point(const lsim_elevation_map_t& em, const LsEmPose& s, const float* row, const uint8_t* lab, int r, float rinv, int& slot, float& zout) {
+    const int G = em.size, half = G >> 1;
+    const float d = em.a * row[r] + em.b;
+    const float t = em.inv_scale ? d * em.inv_scale[r] : d;
+    if (!ls_rc_finite(d) || !(em.t_lo < t) || !(t < em.t_hi)) return false;
+    if (lab && lab[r] != (uint8_t)1) return false;
+    const LsRcV3 v = ls_rc_v3(em.dirs[3 * r] * t, em.dirs[3 * r + 1] * t, em.dirs[3 * r + 2] * t);
+    const LsRcV3 m = ls_rc_rot(s.ax, s.ay, s.az, s.aw, v);
+    const LsRcV3 b = ls_rc_rot(s.qx, s.qy, s.qz, s.qw, ls_rc_v3(s.mx + m.x, s.my + m.y, s.mz + m.z));
+    const float x = s.px + b.x, y = s.py + b.y, z = s.pz + b.z;
+    if (!ls_rc_finite(x) || !ls_rc_finite(y) || !ls_rc_finite(z)) return false;
+    const float fx = ls_em_cellf(x, rinv), fy = ls_em_cellf(y, rinv);
+    if (!ls_em_in_range(fx) || !ls_em_in_range(fy)) return false;
+    const int ix = (int)fx, iy = (int)fy, dx = ix - s.cx, dy = iy - s.cy;
+    if (dx < -half || dx >= half || dy < -half || dy >= half) return false;
+    slot = ls_em_slot(ix, iy, G);
+    zout = z;
+    return true;
+}
+
+// step 2, first half: this lane's rays into the keys.  The loop body is ls_em_point's text ONCE MORE, with `continue` for `return false` and
+// the maximum taken where the point is kept: called through ls_em_point, the compiler carries "kept" as a lane mask out of five nested
+// regions and takes the maximum behind them (16 instructions, 2 VGPRs and 8 SGPRs more), and lsim_elevation_map measured 2.6 - 2.8 % slower
+// (profiles/elevation_refactor_ab.json).  The copy serves this launch alone: the fused kernel forms the point with
+// ls_em_point in both of its passes.  What pins the two texts to each other bit for bit is the fused map with band 0 and gate 0, whose
+// maxima come from ls_em_point and which must equal this launch's map: tests/test_elevation_fuse.py::
+// test_band_zero_gate_zero_is_the_plain_map_bit_for_bit and ::test_identity_on_general_poses, and on the device tests/test_gpu_elevation_fuse.py::
+// test_identity_against_the_librarys_plain_map_on_the_exact_scenes and ::test_general_poses_identity_and_the_references_bracket.
 LS_RC_FN void ls_em_insert(const lsim_elevation_map_t& em, const LsEmPose& s, int env, int lane, float rinv, uint32_t* keys) {
     const int G = em.size, half = G >> 1;
     const float* row = em.depth + (size_t)env * (size_t)em.depth_stride;
@@ -94,26 +123,45 @@ LS_RC_FN void ls_em_insert(const lsim_elevation_map_t& em, const LsEmPose& s, in
     }
 }
 
-// step 2, second half: the touched slots; slot (sx, sy) holds the one cell of the window that maps to it
+// slot k = (sx, sy) holds the one cell (ix, iy) of the window centred on the pose that maps to it
+LS_RC_FN void ls_em_window_cell(const LsEmPose& s, int G, int k, int& ix, int& iy) {
+    const int wx = s.cx - (G >> 1), wy = s.cy - (G >> 1);
+    const int sx = k / G, sy = k - sx * G;
+    ix = wx + ((sx - wx) & (G - 1));
+    iy = wy + ((sy - wy) & (G - 1));
+}
+
+// step 2, second half: the touched slots
 LS_RC_FN void ls_em_commit(const lsim_elevation_map_t& em, const LsEmPose& s, int env, int lane, const uint32_t* keys) {
-    const int G = em.size, G2 = G * G, half = G >> 1;
+    const int G = em.size, G2 = G * G;
     const size_t base = (size_t)env * (size_t)G2;
-    const int wx = s.cx - half, wy = s.cy - half;
     for (int k = lane; k < G2; k += LS_EM_BLOCK) {
         const uint32_t key = keys[k];
         if (key == 0u) continue;
-        const int sx = k / G, sy = k - sx * G;
-        const int ix = wx + ((sx - wx) & (G - 1)), iy = wy + ((sy - wy) & (G - 1));
+        int ix, iy;
+        ls_em_window_cell(s, G, k, ix, iy);
         em.height[base + (size_t)k] = ls_em_unkey(key);
         em.stamp[base + (size_t)k] = (int32_t)(em.tick & 0x7FFFFFFF);        // the low 31 bits: a stamp is never negative
         em.cell[base + (size_t)k] = ls_em_pack(ix, iy);
     }
 }
 
+// scan point j of an env with a finite pose, turned by the yaw alone: the slot of its cell where the map (base: the env's first slot) knows
+// that cell, or -1.  `stamp` is the slot's (set for a slot that is returned): the fused scan ages the variance by it, and a second load of it
+// there is not merged with this one by the compiler
+LS_RC_FN int ls_em_lookup(const lsim_elevation_map_t& em, const LsEmPose& s, int j, size_t base, float rinv, int32_t& stamp) {
+    const float n = ls_div_exact(1.0f, ls_sqrt_exact(s.qz * s.qz + s.qw * s.qw));
+    const LsRcV3 o = ls_rc_rot(0.0f, 0.0f, s.qz * n, s.qw * n, ls_rc_v3(em.pts[2 * j], em.pts[2 * j + 1], 0.0f));
+    const float fx = ls_em_cellf(s.px + o.x, rinv), fy = ls_em_cellf(s.py + o.y, rinv);
+    if (!ls_em_in_range(fx) || !ls_em_in_range(fy)) return -1;
+    const int ix = (int)fx, iy = (int)fy, k = ls_em_slot(ix, iy, em.size);
+    stamp = em.stamp[base + (size_t)k];
+    return stamp >= 0 && em.cell[base + (size_t)k] == ls_em_pack(ix, iy) ? k : -1;
+}
+
 // step 3: this lane's scan points
 LS_RC_FN void ls_em_scan(const lsim_elevation_map_t& em, const LsEmPose& s, int env, int lane, float rinv) {
-    const int G = em.size;
-    const size_t base = (size_t)env * (size_t)(G * G);
+    const size_t base = (size_t)env * (size_t)(em.size * em.size);
     float* scan = em.scan + (size_t)env * (size_t)em.scan_stride;
     uint8_t* known = em.known + (size_t)env * (size_t)em.known_stride;
     for (int j = lane; j < em.num_points; j += LS_EM_BLOCK) {
@@ -122,18 +170,13 @@ LS_RC_FN void ls_em_scan(const lsim_elevation_map_t& em, const LsEmPose& s, int 
             known[j] = (uint8_t)0;
             continue;
         }
-        const float n = ls_div_exact(1.0f, ls_sqrt_exact(s.qz * s.qz + s.qw * s.qw));
-        const LsRcV3 o = ls_rc_rot(0.0f, 0.0f, s.qz * n, s.qw * n, ls_rc_v3(em.pts[2 * j], em.pts[2 * j + 1], 0.0f));
-        const float fx = ls_em_cellf(s.px + o.x, rinv), fy = ls_em_cellf(s.py + o.y, rinv);
+        int32_t stamp;
+        const int k = ls_em_lookup(em, s, j, base, rinv, stamp);
         float h = s.pz - em.unknown_drop;
         uint8_t kn = (uint8_t)0;
-        if (ls_em_in_range(fx) && ls_em_in_range(fy)) {
-            const int ix = (int)fx, iy = (int)fy;
-            const size_t k = base + (size_t)ls_em_slot(ix, iy, G);
-            if (em.stamp[k] >= 0 && em.cell[k] == ls_em_pack(ix, iy)) {
-                h = em.height[k];
-                kn = (uint8_t)1;
-            }
+        if (k >= 0) {
+            h = em.height[base + (size_t)k];
+            kn = (uint8_t)1;
         }
         scan[j] = h;
         known[j] = kn;
@@ -156,12 +199,11 @@ static inline int ls_em_validate(const lsim_elevation_map_t* em) {
     if (em->depth_stride < (int64_t)em->num_rays || (em->labels && em->label_stride < em->num_rays)) return LSIM_E_INVALID;
     if (em->scan_stride < em->num_points || em->known_stride < em->num_points) return LSIM_E_INVALID;
     if (em->tick < 0 || em->period < 1 || em->stagger < 0 || em->stagger > 1 || em->env_stride < 1 || em->num_envs < 1) return LSIM_E_INVALID;
-    if ((em->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((em->flags & LSIM_SENSOR_FILL_ALL) && (em->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(em->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline int ls_em_env_slots(const lsim_elevation_map_t& em) { return (em.num_envs - 1) / em.env_stride + 1; }
-static inline uint32_t ls_em_tick_mod(const lsim_elevation_map_t& em) { return (uint32_t)(em.tick % (int64_t)em.period); }
+static inline int ls_em_env_slots(const lsim_elevation_map_t& em) { return ls_sensor_env_slots(em.num_envs, em.env_stride); }
+static inline uint32_t ls_em_tick_mod(const lsim_elevation_map_t& em) { return ls_sensor_tick_mod(em.tick, em.period); }
 static inline float ls_em_rinv(const lsim_elevation_map_t& em) { return (float)(1.0 / (double)em.res); }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)

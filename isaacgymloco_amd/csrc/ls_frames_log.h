@@ -106,15 +106,14 @@ static inline int ls_fl_validate(const lsim_frames_log_t* fl) {
     if (fl->num_steps < 1 || fl->step < 0 || fl->step >= fl->num_steps || fl->capacity < 1) return LSIM_E_INVALID;
     if ((long long)fl->num_steps * (long long)fl->num_envs > 0x7FFFFFFFLL) return LSIM_E_INVALID;
     if (fl->tick < 0 || fl->period < 1 || fl->stagger < 0 || fl->stagger > 1) return LSIM_E_INVALID;
-    if ((fl->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((fl->flags & LSIM_SENSOR_FILL_ALL) && (fl->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(fl->flags)) return LSIM_E_INVALID;
     if (fl->step == 0 && !(fl->flags & LSIM_SENSOR_FILL_ALL)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline uint32_t ls_fl_tick_mod(const lsim_frames_log_t& fl) { return (uint32_t)(fl.tick % (int64_t)fl.period); }
+static inline uint32_t ls_fl_tick_mod(const lsim_frames_log_t& fl) { return ls_sensor_tick_mod(fl.tick, fl.period); }
 // blocks of the copy: the envs the host knows to be logged -- every visited one under FILL_ALL, one in `period` otherwise -- capped
 static inline unsigned ls_fl_copy_blocks(const lsim_frames_log_t& fl) {
-    const long long slots = ((long long)fl.num_envs - 1) / fl.env_stride + 1;
+    const long long slots = ls_sensor_env_slots(fl.num_envs, fl.env_stride);
     long long blocks = (fl.flags & LSIM_SENSOR_FILL_ALL) ? slots : (slots + fl.period - 1) / fl.period;
     if (blocks > (long long)fl.capacity) blocks = fl.capacity;
     if (blocks > LS_FL_MAX_COPY_BLOCKS) blocks = LS_FL_MAX_COPY_BLOCKS;

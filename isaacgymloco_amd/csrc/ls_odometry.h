@@ -2,9 +2,9 @@
 // the distance travelled, and lsim_map_rows, the elevation map's scan as the rows an actor reads.  lsim.h states every formula; this file is
 // that text in code.
 //
-// Self-contained like ls_elevation_map.h (lsim.h, the helpers of ls_raycast.h / ls_raycast_bodies.h, the Philox of ls_math.h and the C
-// library): tests/emu/emu_odometry.cpp and tests/emu/emu_map_rows.cpp compile this file with g++ under LS_EMU and run the same per-lane code
-// over plain arrays.
+// Self-contained like ls_elevation_map.h (lsim.h, the helpers of ls_raycast.h / ls_raycast_bodies.h, the visit rule of ls_sensor_model.h, the
+// Philox of ls_math.h and the C library): tests/emu/emu_odometry.cpp and tests/emu/emu_map_rows.cpp compile this file with g++ under LS_EMU
+// and run the same per-lane code over plain arrays.
 //
 // Shape of lsim_k_odometry_step: lsim_k_sensor_mount_jitter's -- one lane per VISITED env (lane i of the grid is env i * env_stride), blocks
 // of 256.  Every lane reads its 52-byte row of root_states (dword loads: rows are 52 bytes apart) and its 48-byte row of odo (three 16-byte
@@ -17,14 +17,10 @@
 // rows row, all coalesced; pose[e][2] is one dword that the lanes of an env share (one cache line per env).  One integer division per lane
 // finds the env.  Nothing is staged, nothing is reduced: 4 + 1 bytes read and 8 written per point.
 #pragma once
-#include "ls_raycast_bodies.h"
+#include "ls_sensor_model.h"
 #include "ls_math.h"
 
 // ------------------------------------------------------------------------------------------------ odometry
-LS_RC_FN bool ls_odo_fresh(const lsim_odometry_t& od, int env) {
-    return (od.flags & LSIM_SENSOR_FILL_ALL) != 0u || od.episode_length[env] == 0;
-}
-
 struct LsOdoRow { float v[12]; };         // {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0}
 
 #if defined(LS_EMU) || !defined(__HIPCC__)
@@ -56,7 +52,7 @@ LS_RC_FN void ls_odo_env(const lsim_odometry_t& od, int env) {
     for (int k = 0; k < 13; ++k) p[k] = rs[k];
     bool finite = true;
     for (int k = 0; k < 7; ++k) finite = finite && ls_rc_finite(p[k]);
-    const bool fresh = ls_odo_fresh(od, env);
+    const bool fresh = ls_sensor_fresh(od.flags, od.episode_length, env);
     // one block per lane: the episode's biases (block 1) for a fresh env, the step's noise (block 0) for the others; the fourth word is unused
     uint32_t c[4] = {(uint32_t)env, (uint32_t)od.tick, (uint32_t)LSIM_RNG_ODOMETRY, (od.stream_id << 16) | (fresh ? 1u : 0u)};
     philox4x32_10(c, od.seed, od.rank);
@@ -117,11 +113,10 @@ static inline int ls_odo_validate(const lsim_odometry_t* od) {
     if (od->num_envs < 1 || od->env_stride < 1 || od->tick < 0 || od->stream_id >= 65536u) return LSIM_E_INVALID;
     const float ranges[6] = {od->scale_range, od->yaw_range, od->z_range, od->pos_noise, od->yaw_noise, od->z_noise};
     for (int k = 0; k < 6; ++k) if (!ls_rc_host_finite(ranges[k]) || !(ranges[k] >= 0.0f)) return LSIM_E_INVALID;
-    if ((od->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((od->flags & LSIM_SENSOR_FILL_ALL) && (od->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(od->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline int ls_odo_env_slots(const lsim_odometry_t& od) { return (od.num_envs - 1) / od.env_stride + 1; }
+static inline int ls_odo_env_slots(const lsim_odometry_t& od) { return ls_sensor_env_slots(od.num_envs, od.env_stride); }
 
 // ------------------------------------------------------------------------------------------------ map rows
 // element i of the launch: env slot i / (channels * P), column i % (channels * P)
@@ -151,7 +146,7 @@ static inline int ls_mr_validate(const lsim_map_rows_t* mr) {
     return LSIM_OK;
 }
 static inline long long ls_mr_elements(const lsim_map_rows_t& mr) {
-    return (long long)((mr.num_envs - 1) / mr.env_stride + 1) * (long long)(mr.channels * mr.num_points);
+    return (long long)ls_sensor_env_slots(mr.num_envs, mr.env_stride) * (long long)(mr.channels * mr.num_points);
 }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)

@@ -39,9 +39,7 @@ LS_RC_FN int ls_si_slots(const lsim_sensor_model_t& sm, float lat) {
 }
 
 // ---- the draw launch
-LS_RC_FN bool ls_si_fresh(const lsim_sensor_instrument_t& si, int env) {
-    return (si.flags & LSIM_SENSOR_FILL_ALL) != 0u || si.episode_length[env] == 0;
-}
+LS_RC_FN bool ls_si_fresh(const lsim_sensor_instrument_t& si, int env) { return ls_sensor_fresh(si.flags, si.episode_length, env); }
 
 LS_RC_FN void ls_si_store_row(float* p, float a, float b, float c, float d, float e) {
 #if defined(__HIPCC__) && !defined(LS_EMU)
@@ -129,11 +127,10 @@ static inline int ls_si_validate(const lsim_sensor_instrument_t* si) {
     for (int k = 0; k < 5; ++k)
         if (!ls_rc_host_finite(ranges[k]) || !(ranges[k] >= 0.0f)) return LSIM_E_INVALID;
     if (!(si->gain_lo <= si->gain_hi) || !(si->fov_range < 1.0f)) return LSIM_E_INVALID;
-    if ((si->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((si->flags & LSIM_SENSOR_FILL_ALL) && (si->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(si->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline int ls_si_env_slots(const lsim_sensor_instrument_t& si) { return (si.num_envs - 1) / si.env_stride + 1; }
+static inline int ls_si_env_slots(const lsim_sensor_instrument_t& si) { return ls_sensor_env_slots(si.num_envs, si.env_stride); }
 static inline int ls_si_capture_validate(const lsim_sensor_model_t* sm, const float* inst) {
     const int rv = ls_sm_validate(sm);
     if (rv != LSIM_OK) return rv;

@@ -21,15 +21,29 @@
 #include "ls_raycast_bodies.h"
 #include "ls_math.h"
 
-// is env due on this tick, and is its whole history filled?  tick_mod = tick % period (formed on the host: no 64-bit division on the device)
-// The rule itself, on the fields it reads: lsim_k_sensor_capture and lsim_k_depth_encode (ls_depth_encoder.h) both decide with this function.
+// ---- the visit rule of the sensor chain, on the fields it reads: every launch that takes `flags` decides with these functions
+// the legal values of flags: 0, LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY
+static inline bool ls_sensor_flags_ok(uint32_t flags) {
+    if ((flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return false;
+    return !((flags & LSIM_SENSOR_FILL_ALL) && (flags & LSIM_SENSOR_RESETS_ONLY));
+}
+// the env slots a launch visits (slot i is env i * env_stride), for the num_envs >= 1 and env_stride >= 1 every validator demands
+static inline int ls_sensor_env_slots(int num_envs, int env_stride) { return (num_envs - 1) / env_stride + 1; }
+// tick % period, formed on the host: no 64-bit division on the device
+static inline uint32_t ls_sensor_tick_mod(int64_t tick, int period) { return (uint32_t)(tick % (int64_t)period); }
+// does env start an episode (or does the call say that all do)?
+LS_RC_FN bool ls_sensor_fresh(uint32_t flags, const int64_t* episode_length, int env) {
+    return (flags & LSIM_SENSOR_FILL_ALL) != 0u || episode_length[env] == 0;
+}
+// is env due on this tick, and is its whole history filled?  tick_mod = ls_sensor_tick_mod(tick, period)
 LS_RC_FN bool ls_sensor_due(uint32_t flags, const int64_t* episode_length, int period, int stagger, int env, uint32_t tick_mod, bool& fill) {
-    fill = (flags & LSIM_SENSOR_FILL_ALL) != 0u || episode_length[env] == 0;
+    fill = ls_sensor_fresh(flags, episode_length, env);
     if (fill) return true;
     if (flags & LSIM_SENSOR_RESETS_ONLY) return false;
     const uint32_t p = (uint32_t)period;
     return (tick_mod + (stagger ? (uint32_t)env % p : 0u)) % p == 0u;      // both terms < p <= 2^31: no wrap
 }
+// the rule on the sensor model's own fields, under the names the CPU shims call
 LS_RC_FN bool ls_sm_due(const lsim_sensor_model_t& sm, int env, uint32_t tick_mod, bool& fill) {
     return ls_sensor_due(sm.flags, sm.episode_length, sm.period, sm.stagger, env, tick_mod, fill);
 }
@@ -107,11 +121,10 @@ static inline int ls_sm_validate(const lsim_sensor_model_t* sm) {
     if (!(sm->p_drop >= 0.0f) || !(sm->p_drop <= 1.0f) || !ls_rc_host_finite(sm->drop_value)) return LSIM_E_INVALID;
     if (!ls_rc_host_finite(sm->clip_lo) || !ls_rc_host_finite(sm->clip_hi) || !(sm->clip_lo <= sm->clip_hi)) return LSIM_E_INVALID;
     if (!ls_rc_host_finite(sm->offset) || !ls_rc_host_finite(sm->gain)) return LSIM_E_INVALID;
-    if ((sm->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((sm->flags & LSIM_SENSOR_FILL_ALL) && (sm->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(sm->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline uint32_t ls_sm_tick_mod(const lsim_sensor_model_t& sm) { return (uint32_t)(sm.tick % (int64_t)sm.period); }
+static inline uint32_t ls_sm_tick_mod(const lsim_sensor_model_t& sm) { return ls_sensor_tick_mod(sm.tick, sm.period); }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
 __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_capture(const lsim_sensor_model_t sm, int blocks_per_env, uint32_t tick_mod) {

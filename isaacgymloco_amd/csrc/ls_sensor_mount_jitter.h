@@ -14,9 +14,7 @@
 #include "ls_sensor_model.h"
 #include "ls_math.h"
 
-LS_RC_FN bool ls_smj_fresh(const lsim_sensor_mount_jitter_t& mj, int env) {
-    return (mj.flags & LSIM_SENSOR_FILL_ALL) != 0u || mj.episode_length[env] == 0;
-}
+LS_RC_FN bool ls_smj_fresh(const lsim_sensor_mount_jitter_t& mj, int env) { return ls_sensor_fresh(mj.flags, mj.episode_length, env); }
 
 // the row of one fresh env
 LS_RC_FN void ls_smj_env(const lsim_sensor_mount_jitter_t& mj, int env) {
@@ -50,11 +48,10 @@ static inline int ls_smj_validate(const lsim_sensor_mount_jitter_t* mj) {
         if (!ls_rc_host_finite(mj->pos_range[k]) || !(mj->pos_range[k] >= 0.0f)) return LSIM_E_INVALID;
         if (!ls_rc_host_finite(mj->rot_range[k]) || !(mj->rot_range[k] >= 0.0f)) return LSIM_E_INVALID;
     }
-    if ((mj->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((mj->flags & LSIM_SENSOR_FILL_ALL) && (mj->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(mj->flags)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline int ls_smj_env_slots(const lsim_sensor_mount_jitter_t& mj) { return (mj.num_envs - 1) / mj.env_stride + 1; }
+static inline int ls_smj_env_slots(const lsim_sensor_mount_jitter_t& mj) { return ls_sensor_env_slots(mj.num_envs, mj.env_stride); }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
 __global__ __launch_bounds__(LS_RC_BLOCK) void lsim_k_sensor_mount_jitter(const lsim_sensor_mount_jitter_t mj, int slots) {

@@ -171,8 +171,7 @@ static inline int ls_st_validate(const lsim_sensor_stereo_t* st) {
     if (st->latency < 0 || st->frames < 1 || st->latency > LSIM_SENSOR_MAX_HISTORY || st->frames > LSIM_SENSOR_MAX_HISTORY ||
         st->latency + st->frames > LSIM_SENSOR_MAX_HISTORY) return LSIM_E_INVALID;
     if (st->num_envs < 1 || st->env_stride < 1 || st->tick < 0 || st->stream_id >= 65536u || st->period < 1 || st->stagger < 0 || st->stagger > 1) return LSIM_E_INVALID;
-    if ((st->flags & ~(uint32_t)(LSIM_SENSOR_FILL_ALL | LSIM_SENSOR_RESETS_ONLY)) != 0u) return LSIM_E_INVALID;
-    if ((st->flags & LSIM_SENSOR_FILL_ALL) && (st->flags & LSIM_SENSOR_RESETS_ONLY)) return LSIM_E_INVALID;
+    if (!ls_sensor_flags_ok(st->flags)) return LSIM_E_INVALID;
     if (st->window < 1 || st->window > LSIM_STEREO_MAX_WINDOW || st->edge_radius < 0 || st->edge_radius > 3) return LSIM_E_INVALID;
     if (!ls_rc_host_finite(st->fb) || !(st->fb >= 0.0f) || !ls_rc_host_finite(st->edge_rel) || !(st->edge_rel >= 0.0f) || !(st->edge_rel < 1.0f)) return LSIM_E_INVALID;
     if (!ls_rc_host_finite(st->p_edge_hole) || !(st->p_edge_hole >= 0.0f) || !ls_rc_host_finite(st->p_edge_cum) || !(st->p_edge_cum <= 1.0f) ||
@@ -183,8 +182,8 @@ static inline int ls_st_validate(const lsim_sensor_stereo_t* st) {
         !ls_rc_host_finite(st->offset) || !ls_rc_host_finite(st->gain)) return LSIM_E_INVALID;
     return LSIM_OK;
 }
-static inline int ls_st_env_slots(const lsim_sensor_stereo_t& st) { return (st.num_envs - 1) / st.env_stride + 1; }
-static inline uint32_t ls_st_tick_mod(const lsim_sensor_stereo_t& st) { return (uint32_t)(st.tick % (int64_t)st.period); }
+static inline int ls_st_env_slots(const lsim_sensor_stereo_t& st) { return ls_sensor_env_slots(st.num_envs, st.env_stride); }
+static inline uint32_t ls_st_tick_mod(const lsim_sensor_stereo_t& st) { return ls_sensor_tick_mod(st.tick, st.period); }
 
 #if defined(__HIPCC__) && !defined(LS_EMU)
 __global__ __launch_bounds__(LS_ST_BLOCK) void lsim_k_sensor_stereo(const lsim_sensor_stereo_t st, uint32_t tick_mod) {

@@ -72,6 +72,8 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "depth_chain_refactor_ab.json": ("parent commit against the commit that moved the memory's per-env buffers to the sensor, alternating runs in one session: `tools/depth_memory_time.py` and `tools/vision_train_time.py --memory` medians with the parent's run-to-run spread", "7.12"),
               "learner_optin_retire_ab.json": ("parent commit against the commit that removed the bf16-pipe weight gradient and the padded shuffle, alternating runs in one session: `bench.py --gpus 1 --steps 1000 --warmup 100` (`value`, `learn_s_per_update`) and the same with `--full --no-cpu-baseline` (`update_host_enqueue_s`), medians with the parent's run-to-run spread", "7.3"),
               "raycast_refactor_ab.json": ("parent commit against the commit that folded the copies of the range-sensor chain's ray routines and stores into one: digests of every output array of the four ray launches on the test scenes and at N = 4096 (bit-identical), then `tools/raycast_time.py` (plain and `--instrument`) in five alternating pairs and one `bench.py` pair, with the parent's run-to-run spread", '7.7'),
+              "vision_e2e_time.json": ("`tools/vision_train_time.py` with the end-to-end switch: parent commit against this tree with the switch off (alternating, N = 4096, 100 steps), then `--steps 24 --e2e` (collection, update and frame-log time, logged images, the log's bytes), and the encoder-gradient errors of the device test", '7.18'),
+              "elevation_refactor_ab.json": ("parent commit against the commit that folded the elevation map's copied kernel text and the sensor chain's visit rule into one text each: digests of every array of the touched launches on the test scenes (CPU shims and device) and at N = 4096 (bit-identical), register tables and the assembly comparison, then `tools/raycast_time.py --map` (with `--odometry --map-rows 2`, and with `fusion=default`) in five alternating rounds with the parent's library against itself as the null pair, three sessions, and one `bench.py` pair", '7.20'),
               "sensor_mount_jitter_time.json": ("`tools/raycast_time.py --model … --mount-jitter 0.01,5`, N = 4096: `lsim_sensor_mount_jitter` alone (all / no env fresh), `lsim_sensor_capture` on jittered against nominal mounts with the parent commit's nominal columns of the same call; `tools/vision_train_time.py --mount-jitter`; `bench.py` alternating with the parent's tree", '7.13'),
               "sensor_instrument_time.json": ("`tools/raycast_time.py --model … --instrument latency=0:1,noise_gain=0.5:2,depth_scale=0.02,depth_quad=0.005,fov=0.02`, N = 4096, camera and lidar on flat ground and stairs: `lsim_sensor_capture` against `lsim_sensor_capture_inst` on neutral and on drawn rows, `lsim_sensor_instrument` alone (all / no env fresh), the parent commit's `lsim_sensor_capture` of the same call; `tools/vision_train_time.py --instrument`; `bench.py` alternating with the parent's tree", '7.14'),
               "sensor_stereo_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --stereo default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_stereo` alone (`stereo_us`, `stereo_all_due_us`) next to the capture alone on the same ticks (`capture_us`, `capture_all_due_us`), `update()` without and with the option, the share of a whole capture's pixels the stage rewrites; `counts`: `stereo_counts()` of 64 envs on stairs over 30 steps; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.21'),
