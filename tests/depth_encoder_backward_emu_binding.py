@@ -10,19 +10,17 @@ import numpy as np
 import depth_encoder_backward_reference as RB
 import depth_encoder_emu_binding as DB
 import emu_binding
-import raycast_emu_binding as EMU
 from helpers import abi
+from launch_rig import EditRig
 
-HEADERS = DB.HEADERS + ["ls_depth_encoder_bwd.h"]
 PARAMS = ("w1", "b1", "w2", "b2", "w3", "b3")
-GUARD = 4          # words behind each gradient buffer that no launch may touch
 # (shape, grid_limit): 0 = the kernel's own choice (one workgroup per sample at these batches), 2 = several samples per workgroup; A's seven
 # samples at 3 = workgroups of three, two and two
 MATRIX = [(n, gl) for n in sorted(DB.SHAPES) for gl in (0, 2)] + [("A", 3)]
 
 
 def lib():
-    return emu_binding.load_shim("depth_encoder_backward", HEADERS)
+    return emu_binding.shim("depth_encoder_backward")
 
 
 @functools.lru_cache(maxsize=None)
@@ -37,96 +35,55 @@ def case(name, seed=0):
     return s, params, hist, g, grads, bounds, lat.astype(np.float32)
 
 
-class Rig:
+class Rig(EditRig):
     """`shape`: an entry of SHAPES; `params`: (w1 .. b3) numpy; `hist`: images(shape); g [B, L]; latent [B, L] fp32.  `device`: None -- numpy
     arrays and the shim -- or a torch device with `entry` / `sizes` = the library's two functions.  The six gradient buffers start as NaN with
-    the bit pattern PREFILL, GUARD words longer than their extents; the workspace has the size of grid_limit 0, the largest."""
+    the bit pattern PREFILL, each with guard words behind it that no launch may touch; the workspace has the size of grid_limit 0, the largest."""
     PREFILL = 0x7FC00ABC
 
     def __init__(self, shape, params, hist, g, latent, device=None, entry=None, sizes=None, grid_limit=0):
         s = self.shape = shape
-        self.B, self.L, self.device = s["N"], s["latent_dim"], device
+        super().__init__(device)
+        self.B, self.L = s["N"], s["latent_dim"]
         self.gstride, self.lstride = self.L + 3, (self.L + 3) // 4 * 4 + 4
-        a = {k: EMU.aligned(v.shape, np.float32) for k, v in zip(PARAMS, params)}
         for k, v in zip(PARAMS, params):
-            a[k][...] = v
-        a["hist"] = EMU.aligned(hist.shape, np.float32)
-        a["hist"][...] = hist
-        a["g"] = EMU.aligned((self.B, self.gstride), np.float32)
-        a["g"][:, :self.L] = g
-        a["latent"] = EMU.aligned((self.B, self.lstride), np.float32)
-        a["latent"][:, :self.L] = latent
+            self.add(k, np.asarray(v, np.float32))
+        self.add("hist", np.asarray(hist, np.float32))
+        for k, v, ld in (("g", g, self.gstride), ("latent", latent, self.lstride)):
+            rows = np.zeros((self.B, ld), np.float32)
+            rows[:, :self.L] = v
+            self.add(k, rows)
         self.extent = {"g" + k: int(np.prod(v.shape)) for k, v in zip(PARAMS, params)}
-        for k, n in self.extent.items():
-            a[k] = EMU.aligned((n + GUARD,), np.uint32)
-            a[k][:] = self.PREFILL
-            a[k] = a[k].view(np.float32)
+        for k, v in zip(PARAMS, params):
+            self.add("g" + k, np.full(v.shape, self.PREFILL, np.uint32).view(np.float32), guard=True)
         db = abi.LsimDepthEncoderBwd()
         db.hist_stride, db.hist_slots, db.batch = hist.shape[2], hist.shape[1], self.B
         for k in ("height", "width", "frames", "c1", "k1", "s1", "c2", "k2", "s2", "latent_dim"):
             setattr(db, k, s[k])
         db.final_act, db.g_stride, db.latent_stride, db.grid_limit = int(s.get("final_act", True)), self.gstride, self.lstride, 0
         self._sizes = sizes if device is not None else lib().emu_depth_encode_backward_sizes
-        self._entry = entry if device is not None else lib().emu_depth_encode_backward
         self.lds_bytes, need = self.sizes(db)
-        a["workspace"] = EMU.aligned((need // 4,), np.float32)
-        if device is not None:
-            import torch
-            a = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in a.items()}
-        self.a = a
-        for k in a:
-            setattr(db, k, self._ptr(k))
+        self.add("workspace", np.zeros(need // 4, np.float32), guard=True)
+        self.point(db, list(self.a))
         db.workspace_bytes, db.grid_limit = need, grid_limit
-        self.db = db
+        self.db = self.bind(db, entry if device is not None else lib().emu_depth_encode_backward)
 
     def sizes(self, db):
         lds, ws = ctypes.c_size_t(), ctypes.c_size_t()
         assert self._sizes(ctypes.byref(db), ctypes.byref(lds), ctypes.byref(ws)) == 0
         return lds.value, ws.value
 
-    def _ptr(self, k):
-        return self.a[k].data_ptr() if self.device is not None else self.a[k].ctypes.data
-
-    def put(self, name, value):
-        if self.device is not None:
-            import torch
-            self.a[name].copy_(torch.from_numpy(np.ascontiguousarray(value, np.float32)).to(self.device))
-        else:
-            self.a[name][...] = value
-
-    def get(self, name):
-        if self.device is not None:
-            import torch
-            torch.cuda.synchronize()
-            return self.a[name].cpu().numpy().copy()
-        return self.a[name].copy()
-
-    def launch(self, edit=None):
-        """one call; `edit(db)` changes a copy of the struct first; returns the entry point's value"""
-        db = abi.LsimDepthEncoderBwd.from_buffer_copy(self.db)
-        if edit:
-            edit(db)
-        stream = None
-        if self.device is not None:
-            import torch
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        return self._entry(ctypes.byref(db), stream)
-
     def bits(self):
-        """{name: uint32 [extent + GUARD]} of the six gradient buffers, guard included"""
-        return {k: self.get(k).view(np.uint32) for k in self.extent}
+        """{name: uint32 [extent + guard]} of the six gradient buffers, guard included"""
+        return {k: self.raw(k).view(np.uint32) for k in self.extent}
 
     def untouched(self):
-        return all((b == self.PREFILL).all() for b in self.bits().values())
+        return self.guards_intact() and all((b[:self.extent[k]] == self.PREFILL).all() for k, b in self.bits().items())
 
     def grads(self):
-        """{name: fp32 array of the parameter's shape}; asserts that every guard word still holds the pre-fill"""
-        out = {}
-        for k, n in self.extent.items():
-            v = self.get(k)
-            assert (v.view(np.uint32)[n:] == self.PREFILL).all(), f"{k}: written past its extent"
-            out[k] = v[:n].reshape(self.a[k[1:]].shape)
-        return out
+        """{name: fp32 array of the parameter's shape}; asserts that every guard word still holds its pattern"""
+        self.assert_guards()
+        return {k: self.get(k) for k in self.extent}
 
 
 def make(name, cls_kw=None, grid_limit=0):

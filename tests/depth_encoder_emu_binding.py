@@ -1,17 +1,12 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_depth_encoder.cpp (the CPU shim of the depth-encoder launch,
 isaacgymloco_amd/csrc/ls_depth_encoder.h compiled by g++ under LS_EMU), the shapes both depth-encoder test files run, and Rig: one
 lsim_depth_encoder with the arrays it points to, in host memory for the shim or in device memory for the HIP library."""
-import ctypes
-
 import numpy as np
 
 import emu_binding
-import raycast_bodies_emu_binding as BE
-import raycast_emu_binding as EMU
-import sensor_model_emu_binding as SB
 from helpers import abi
+from launch_rig import LaunchRig
 
-HEADERS = SB.HEADERS + ["ls_depth_encoder.h"]
 FILL_ALL, RESETS_ONLY = abi.DEFINES["LSIM_SENSOR_FILL_ALL"], abi.DEFINES["LSIM_SENSOR_RESETS_ONLY"]
 
 # name -> extents.  A: nothing a multiple of a tile, hist_stride > R, fewer frames than slots, strided envs; B: one frame, one channel tile,
@@ -26,13 +21,13 @@ SHAPES = {
 
 
 def lib():
-    return emu_binding.load_shim("depth_encoder", HEADERS)
+    return emu_binding.shim("depth_encoder")
 
 
 def EmuApi():
     """the range-sensor entry points of the three sensor shims and lsim_depth_encode of this one, for envs.sensors.RaySensor(api=...); counts the launches"""
-    return emu_binding.EmuApi(EMU.lib(), BE.lib(), SB.lib(), lib(),
-                              count=("lsim_raycast", "lsim_raycast_bodies", "lsim_sensor_capture", "lsim_depth_encode"))
+    return emu_binding.api("raycast", "raycast_bodies", "sensor_model", "depth_encoder",
+                           count=("lsim_raycast", "lsim_raycast_bodies", "lsim_sensor_capture", "lsim_depth_encode"))
 
 
 def module(shape, seed=0):
@@ -61,76 +56,37 @@ def frames_of(shape, hist):
     return hist[:, :s["frames"], :s["height"] * s["width"]].reshape(s["N"], s["frames"], s["height"], s["width"])
 
 
-class Rig:
+class Rig(LaunchRig):
     """`shape`: an entry of SHAPES; `params`: (w1, b1, w2, b2, w3, b3) numpy; `hist`: images(shape).  `device`: None -- numpy arrays and the
-    shim -- or a torch device and `entry` = the library's lsim_depth_encode.  `latent` starts as NaN with the bit pattern PREFILL;
+    shim -- or a torch device and `entry` = the library's lsim_depth_encode.  `latent` starts as NaN with the bit pattern PREFILL, with a guard behind it;
     episode_length as 1.  period / stagger: keywords."""
     PREFILL = 0x7FC00ABC
 
     def __init__(self, shape, params, hist, device=None, entry=None, period=1, stagger=0):
         s = self.shape = shape
-        self.N, self.L, self.device = s["N"], s["latent_dim"], device
+        super().__init__(device)
+        self.N, self.L = s["N"], s["latent_dim"]
         self.lstride = (self.L + 3) // 4 * 4 + 4
-        a = {k: EMU.aligned(v.shape, np.float32) for k, v in zip(("w1", "b1", "w2", "b2", "w3", "b3"), params)}
         for k, v in zip(("w1", "b1", "w2", "b2", "w3", "b3"), params):
-            a[k][...] = v
-        a["hist"] = EMU.aligned(hist.shape, np.float32)
-        a["hist"][...] = hist
-        a["episode_length"] = EMU.aligned((self.N,), np.int64)
-        a["episode_length"][:] = 1
-        a["latent"] = EMU.aligned((self.N, self.lstride), np.uint32)
-        a["latent"][:] = self.PREFILL
-        a["latent"] = a["latent"].view(np.float32)
-        if device is not None:
-            import torch
-            a = {k: torch.from_numpy(np.ascontiguousarray(v)).to(device) for k, v in a.items()}
-        self.a = a
+            self.add(k, np.asarray(v, np.float32))
+        self.add("hist", np.asarray(hist, np.float32))
+        self.add("episode_length", np.ones(self.N, np.int64))
+        self.add("latent", np.full((self.N, self.lstride), self.PREFILL, np.uint32).view(np.float32), guard=True)
         de = abi.LsimDepthEncoder()
-        for k in ("hist", "episode_length", "latent", "w1", "b1", "w2", "b2", "w3", "b3"):
-            setattr(de, k, self._ptr(k))
+        self.point(de, ("hist", "episode_length", "latent", "w1", "b1", "w2", "b2", "w3", "b3"))
         de.hist_stride, de.hist_slots, de.num_envs, de.env_stride = hist.shape[2], hist.shape[1], self.N, s.get("env_stride", 1)
         for k in ("height", "width", "frames", "c1", "k1", "s1", "c2", "k2", "s2", "latent_dim"):
             setattr(de, k, s[k])
         de.final_act, de.latent_stride, de.period, de.stagger = int(s.get("final_act", True)), self.lstride, int(period), int(stagger)
-        self.de = de
-        self._entry = entry if device is not None else lib().emu_depth_encode
-
-    def _ptr(self, k):
-        return self.a[k].data_ptr() if self.device is not None else self.a[k].ctypes.data
-
-    def put(self, name, value):
-        if self.device is not None:
-            import torch
-            cur = self.a[name]
-            v = np.broadcast_to(np.asarray(value, dtype=self.get(name).dtype), tuple(cur.shape)).copy()
-            cur.copy_(torch.from_numpy(v).to(self.device))
-        else:
-            self.a[name][...] = value
-
-    def get(self, name):
-        if self.device is not None:
-            import torch
-            torch.cuda.synchronize()
-            return self.a[name].cpu().numpy().copy()
-        return self.a[name].copy()
-
-    def launch(self, tick=0, flags=0, edit=None):
-        """one launch; `edit(de)` changes a copy of the struct first; returns the entry point's value"""
-        de = abi.LsimDepthEncoder.from_buffer_copy(self.de)
-        de.tick, de.flags = tick, flags
-        if edit:
-            edit(de)
-        stream = None
-        if self.device is not None:
-            import torch
-            stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        return self._entry(ctypes.byref(de), stream)
+        self.de = self.bind(de, entry if device is not None else lib().emu_depth_encode)
 
     def latent_bits(self):
-        """[N, lstride] uint32: the whole buffer, padding included"""
+        """[N, lstride] uint32: the whole buffer, padding included; asserts the guard behind it intact"""
+        self.assert_guards()
         return self.get("latent").view(np.uint32)
 
     def latent(self):
+        self.assert_guards()
         return self.get("latent")[:, :self.L]
 
 

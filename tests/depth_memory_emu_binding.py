@@ -1,18 +1,14 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_depth_memory.cpp (the CPU shim of the depth-memory launches,
 isaacgymloco_amd/csrc/ls_depth_memory.h compiled by g++ under LS_EMU), the shapes both depth-memory test files run, and the two rigs: the
-arrays of one lsim_depth_memory_t / lsim_gru_sequence_t with guard words behind each, in host memory for the shim or in device memory for
+arrays of one lsim_depth_memory_t / lsim_gru_sequence_t with guard words behind each (inputs included), in host memory for the shim or in device memory for
 the HIP library, and the checks that run on either."""
-import ctypes
-
 import numpy as np
 
 import emu_binding
 import depth_memory_reference as R
-import raycast_emu_binding as EMU
-import sensor_model_emu_binding as SB
 from helpers import abi
+from launch_rig import LaunchRig
 
-HEADERS = SB.HEADERS + ["ls_depth_memory.h"]
 FILL_ALL, RESETS_ONLY = abi.DEFINES["LSIM_SENSOR_FILL_ALL"], abi.DEFINES["LSIM_SENSOR_RESETS_ONLY"]
 LsimDepthMemory, LsimGruSequence = abi.STRUCTS["lsim_depth_memory_t"], abi.STRUCTS["lsim_gru_sequence_t"]
 
@@ -25,19 +21,16 @@ SHAPES = {
     "D": dict(N=16, L=12, P=0, H=48, T=3),
     "E": dict(N=33, L=8, P=4, H=96, T=1),
 }
-PREFILL, GUARD = 0x7FC00ABC, 0x7FC0FEED          # two NaNs: an output not written, a word behind a buffer
-GUARD_WORDS = 16
+PREFILL = 0x7FC00ABC          # a NaN: an output not written
 
 
 def lib():
-    return emu_binding.load_shim("depth_memory", HEADERS)
+    return emu_binding.shim("depth_memory")
 
 
 def EmuApi(*more, count=()):
-    """the sensor and encoder shims plus this one, for envs.sensors.RaySensor(api=...); counts the launches named in `count`"""
-    import depth_encoder_emu_binding as DB
-    import raycast_bodies_emu_binding as BE
-    return emu_binding.EmuApi(EMU.lib(), BE.lib(), SB.lib(), DB.lib(), lib(), *more, count=count)
+    """the sensor and encoder shims plus this one (and the libraries `more`), for envs.sensors.RaySensor(api=...); counts the launches named in `count`"""
+    return emu_binding.api("raycast", "raycast_bodies", "sensor_model", "depth_encoder", "depth_memory", *more, count=count)
 
 
 def params(shape, seed=0):
@@ -59,61 +52,11 @@ def resets(shape, seed=0):
     return r
 
 
-class _Buffers:
-    """named flat arrays, each followed by GUARD_WORDS guard words; on the host (numpy) or on `device` (torch)"""
-
-    def __init__(self, device):
-        self.device, self.a, self.n = device, {}, {}
-
-    def add(self, name, value):
-        v = np.ascontiguousarray(value)
-        raw = EMU.aligned((v.nbytes + 4 * GUARD_WORDS,), np.uint8)
-        raw[:v.nbytes] = v.reshape(-1).view(np.uint8)
-        raw[v.nbytes:].view(np.uint32)[:] = GUARD
-        self.n[name] = (v.shape, v.dtype)
-        if self.device is not None:
-            import torch
-            raw = torch.from_numpy(raw.copy()).to(self.device)
-        self.a[name] = raw
-
-    def ptr(self, name):
-        return self.a[name].data_ptr() if self.device is not None else self.a[name].ctypes.data
-
-    def _host(self, name):
-        if self.device is not None:
-            import torch
-            torch.cuda.synchronize()
-            return self.a[name].cpu().numpy()
-        return self.a[name]
-
-    def get(self, name):
-        shape, dt = self.n[name]
-        return self._host(name)[:int(np.prod(shape)) * dt.itemsize].copy().view(dt).reshape(shape)
-
-    def put(self, name, value):
-        shape, dt = self.n[name]
-        v = np.broadcast_to(np.asarray(value, dt), shape).copy().reshape(-1).view(np.uint8)
-        if self.device is not None:
-            import torch
-            self.a[name][:v.size].copy_(torch.from_numpy(v).to(self.device))
-        else:
-            self.a[name][:v.size] = v
-
-    def guards_intact(self):
-        return all((self._host(k)[-4 * GUARD_WORDS:].view(np.uint32) == GUARD).all() for k in self.a)
-
-    def stream(self, stream=None):
-        if self.device is None:
-            return None
-        import torch
-        return ctypes.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
-
-
 def nan_fill(shape):
     return np.full(shape, PREFILL, np.uint32).view(np.float32)
 
 
-class StepRig(_Buffers):
+class StepRig(LaunchRig):
     """one lsim_depth_memory_t: z, p, h, rows with the row pitches of `shape` (width + pad), episode_length, the four parameters"""
 
     def __init__(self, shape, prm, z, p, h, episode_length, device=None, entry=None):
@@ -127,28 +70,22 @@ class StepRig(_Buffers):
             out = nan_fill((N, ld))
             out[:, :v.shape[1]] = v
             return out
-        self.add("z", padded(z, self.ld["z"]))
+        self.add("z", padded(z, self.ld["z"]), guard=True)
         if P:
-            self.add("p", padded(p, self.ld["p"]))
-        self.add("h", padded(h, self.ld["h"]))
-        self.add("rows", nan_fill((N, self.ld["rows"])))
-        self.add("episode_length", np.asarray(episode_length, np.int64))
+            self.add("p", padded(p, self.ld["p"]), guard=True)
+        self.add("h", padded(h, self.ld["h"]), guard=True)
+        self.add("rows", nan_fill((N, self.ld["rows"])), guard=True)
+        self.add("episode_length", np.asarray(episode_length, np.int64), guard=True)
         for k, v in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), prm):
-            self.add(k, v)
+            self.add(k, v, guard=True)
         dm = LsimDepthMemory()
-        for k in self.a:
-            setattr(dm, k, self.ptr(k))
+        self.point(dm, list(self.a))
         dm.num_envs, dm.latent_dim, dm.proprio_dim, dm.hidden = N, L, P, H
         dm.z_ld, dm.p_ld, dm.h_ld, dm.rows_ld = self.ld["z"], self.ld["p"], self.ld["h"], self.ld["rows"]
-        self.dm = dm
-        self._entry = entry if device is not None else lib().emu_depth_memory_step
+        self.dm = self.bind(dm, entry if device is not None else lib().emu_depth_memory_step)
 
     def launch(self, flags=0, edit=None, stream=None):
-        dm = LsimDepthMemory.from_buffer_copy(self.dm)
-        dm.flags = flags
-        if edit:
-            edit(dm)
-        return self._entry(ctypes.byref(dm), self.stream(stream))
+        return super().launch(None, flags, edit, stream)
 
     def h(self):
         return self.get("h")[:, :self.shape["H"]]
@@ -232,53 +169,35 @@ def scale_weights(rig):
     """multiply weight_hh and bias_ih in place by -1.5 / +2; returns the parameters the next launch must see"""
     prm = [rig.get(k) for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
     prm[1], prm[2] = (prm[1] * np.float32(-1.5)).astype(np.float32), (prm[2] * np.float32(2.0)).astype(np.float32)
-    if rig.device is not None:
-        import torch
-        for k, f in (("weight_hh", -1.5), ("bias_ih", 2.0)):
-            shape, dt = rig.n[k]
-            rig.a[k][:int(np.prod(shape)) * 4].view(torch.float32).mul_(f)          # in place, on the device
-    else:
-        for k, f in (("weight_hh", -1.5), ("bias_ih", 2.0)):
-            shape, dt = rig.n[k]
-            rig.a[k][:int(np.prod(shape)) * 4].view(np.float32)[:] *= np.float32(f)
+    for k, f in (("weight_hh", -1.5), ("bias_ih", 2.0)):
+        rig.a[k][:int(np.prod(rig.n[k][0]))] *= f        # in place, on the host or on the device
     return tuple(prm)
 
 
-class SeqRig(_Buffers):
+class SeqRig(LaunchRig):
     """one lsim_gru_sequence_t with contiguous [T, n, .] arrays; outputs start as NaN with the bit pattern PREFILL"""
 
     def __init__(self, shape, prm, gi, h0, reset, dhs, device=None, entries=None):
         super().__init__(device)
         s = self.shape = shape
         T, n, H = s["T"], s["N"], s["H"]
-        self.add("gi", gi)
-        self.add("h0", h0)
-        self.add("reset", np.asarray(reset, np.uint8))
-        self.add("weight_hh", prm[1])
-        self.add("bias_hh", prm[3])
-        self.add("dhs", dhs)
+        for k, v in (("gi", gi), ("h0", h0), ("reset", np.asarray(reset, np.uint8)), ("weight_hh", prm[1]), ("bias_hh", prm[3]), ("dhs", dhs)):
+            self.add(k, v, guard=True)
         for k, w in (("hs", H), ("save", 4 * H), ("dgi", 3 * H), ("dghn", H)):
-            self.add(k, nan_fill((T, n, w)))
-        self.add("dh0", nan_fill((n, H)))
+            self.add(k, nan_fill((T, n, w)), guard=True)
+        self.add("dh0", nan_fill((n, H)), guard=True)
         gs = LsimGruSequence()
-        for k in self.a:
-            setattr(gs, k, self.ptr(k))
+        self.point(gs, list(self.a))
         gs.steps, gs.num_envs, gs.hidden = T, n, H
-        self.gs = gs
         L = lib() if device is None else None
         self._fwd, self._bwd = entries if device is not None else (L.emu_gru_sequence_forward, L.emu_gru_sequence_backward)
-
-    def _launch(self, fn, edit, stream):
-        gs = LsimGruSequence.from_buffer_copy(self.gs)
-        if edit:
-            edit(gs)
-        return fn(ctypes.byref(gs), self.stream(stream))
+        self.gs = self.bind(gs, self._fwd)
 
     def forward(self, edit=None, stream=None):
-        return self._launch(self._fwd, edit, stream)
+        return self.launch(edit=edit, stream=stream)
 
     def backward(self, edit=None, stream=None):
-        return self._launch(self._bwd, edit, stream)
+        return self.launch(edit=edit, stream=stream, entry=self._bwd)
 
     OUT = ("hs", "save", "dgi", "dghn", "dh0")
 

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_distill.cpp (the CPU shim of isaacgymloco_amd/csrc/ls_distill.h compiled by g++
 under LS_EMU), and the rig of lsim_distill_loss: one struct with the arrays it points to, in host memory for the shim or in device memory
-for the HIP library.  Both arrays a call writes have GUARD elements behind them, pre-filled and checked.  The checks both
+for the HIP library.  Both arrays a call writes have guard elements behind them, pre-filled and checked.  The checks both
 tests/test_distill.py (shim) and tests/test_gpu_distill.py (device) run are here too."""
 import ctypes
 
@@ -9,57 +9,43 @@ import numpy as np
 import distill_reference as R
 import emu_binding
 from helpers import abi
-from odometry_emu_binding import _Arrays
+from launch_rig import EditRig
 
-HEADERS = ["ls_distill.h"]
-GUARD = 16
 G_FILL, P_FILL = np.float32(-7.25), np.float32(-3.5)
 LsimDistillLoss = abi.STRUCTS["lsim_distill_loss_t"]
 assert R.PARTIALS == abi.DEFINES["LSIM_DISTILL_PARTIALS"] and max(R.ACTIONS) <= abi.DEFINES["LSIM_DISTILL_MAX_ACTIONS"] == 16
 
 
 def lib():
-    return emu_binding.load_shim("distill", HEADERS)
+    return emu_binding.shim("distill")
 
 
-class Rig(_Arrays):
-    """mu, target and index are inputs; g [batch, g_stride] and partial [PARTIALS] are outputs, pre-filled, each with GUARD elements behind it.
+class Rig(EditRig):
+    """mu, target and index are inputs; g [batch, g_stride] and partial [PARTIALS] are outputs, pre-filled, each with guard elements behind it.
     `device`: None -- numpy arrays and the shim -- or a torch device and `entry` = the library's lsim_distill_loss."""
 
     def __init__(self, mu, target, index, actions, g_stride, device=None, entry=None):
-        self.device, self.batch, self.actions, self.g_stride = device, mu.shape[0], int(actions), int(g_stride)
-        al = emu_binding.aligned
-        a = {"mu": al(mu.shape, np.float32), "target": al(target.shape, np.float32), "index": al(index.shape, np.int32),
-             "g": al((self.batch * self.g_stride + GUARD,), np.float32), "partial": al((R.PARTIALS + GUARD,), np.float32)}
-        a["mu"][...], a["target"][...], a["index"][...] = mu, target, index
-        a["g"][:] = G_FILL
-        a["partial"][:] = P_FILL
-        self.a = a
-        self._to_device()
+        super().__init__(device)
+        self.batch, self.actions, self.g_stride = mu.shape[0], int(actions), int(g_stride)
+        self.add("mu", np.asarray(mu, np.float32))
+        self.add("target", np.asarray(target, np.float32))
+        self.add("index", np.asarray(index, np.int32))
+        self.add("g", np.full((self.batch, self.g_stride), G_FILL, np.float32), guard=G_FILL)
+        self.add("partial", np.full(R.PARTIALS, P_FILL, np.float32), guard=P_FILL)
         dl = LsimDistillLoss()
-        dl.mu, dl.target, dl.index, dl.g, dl.partial = (self._ptr(k) for k in ("mu", "target", "index", "g", "partial"))
+        self.point(dl, ("mu", "target", "index", "g", "partial"))
         dl.batch, dl.actions, dl.target_rows = self.batch, self.actions, target.shape[0]
         dl.mu_stride, dl.target_stride, dl.g_stride = mu.shape[1], target.shape[1], self.g_stride
         dl.scale = float(R.scale_of(self.batch, self.actions))
-        self.dl = dl
-        self._entry = entry if device is not None else lib().emu_distill_loss
+        self.dl = self.bind(dl, entry if device is not None else lib().emu_distill_loss)
 
-    def launch(self, edit=None, stream=None):
-        dl = LsimDistillLoss.from_buffer_copy(self.dl)
-        if edit:
-            edit(dl)
-        return self._entry(ctypes.byref(dl), self._stream(stream))
-
-    def raw(self):
-        return {k: self.get(k) for k in ("g", "partial")}
+    def outputs_raw(self):
+        return {k: self.raw(k) for k in ("g", "partial")}
 
     def read(self):
         """(g [batch, g_stride], partial [PARTIALS]); asserts both guards intact"""
-        raw = self.raw()
-        n = self.batch * self.g_stride
-        assert (raw["g"][n:] == G_FILL).all(), "the guard behind g was overwritten"
-        assert (raw["partial"][R.PARTIALS:] == P_FILL).all(), "the guard behind partial was overwritten"
-        return raw["g"][:n].reshape(self.batch, self.g_stride), raw["partial"][:R.PARTIALS]
+        self.assert_guards()
+        return self.get("g"), self.get("partial")
 
 
 def check_case(make_rig, kind, actions, pad):
@@ -127,11 +113,11 @@ def check_refusals(make_rig, null_call):
     """every listed argument error returns LSIM_E_INVALID and leaves both outputs, guards included, as they were"""
     mu, target, index, strides, _ = R.make_case("seventy", 12, 0)
     rig = make_rig(mu, target, index, 12, strides[2])
-    before = rig.raw()
+    before = rig.outputs_raw()
     assert null_call() == abi.E_INVALID
     for name, edit in REFUSALS.items():
         assert rig.launch(edit=edit) == abi.E_INVALID, name
-        after = rig.raw()
+        after = rig.outputs_raw()
         for k in before:
             assert np.array_equal(before[k].view(np.uint8), after[k].view(np.uint8)), f"{name}: {k} was written"
     assert rig.launch() == 0

@@ -26,8 +26,6 @@ MUTANTS, each with the scene of tests/test_elevation_fuse.py that misses its bou
   no_clamp                                                 clamps        no_cap (min(count, cap) dropped)             counts
   no_wrap (the age's 31-bit wrap dropped)                  wrap          band_on_z (z <= band)                        spread
   sum_all (the second pass sums every kept point)          spread"""
-import ctypes
-
 import numpy as np
 
 import elevation_map_emu_binding as EB
@@ -40,13 +38,12 @@ U = 2.0 ** -24
 MUTANTS = ("no_growth", "K_swapped", "gate_inclusive", "no_gate", "no_clamp", "no_cap", "no_wrap", "band_on_z", "sum_all")
 FIELDS = ("sigma0", "sigma2", "range_z2", "band", "var_floor", "var_growth", "var_max", "gate2")
 DEFAULTS = dict(sigma0=0.01, sigma2=0.002, range_z2=0.16, band=0.0625, var_floor=2.5e-5, var_growth=1e-6, var_max=0.25, gate2=9.0, count_cap=4)
-WRITTEN = {"var": np.float32, "scan_var": np.float32}
 GUARD_VALUE = {"var": -77.25, "scan_var": -55.5}
 INITIAL = {"var": 333.0, "scan_var": 444.0}
 
 
 def lib():
-    return emu_binding.load_shim("elevation_fuse", EB.HEADERS + ["ls_odometry.h", "ls_elevation_fuse.h"])
+    return emu_binding.shim("elevation_fuse")
 
 
 class FusedRig(EB.Rig):
@@ -56,41 +53,30 @@ class FusedRig(EB.Rig):
     def __init__(self, N, G, dirs, pts, fusion=None, device=None, entry=None, **kw):
         super().__init__(N, G, dirs, pts, device=device, entry=entry, **kw)
         self.var_stride = self.P + 3
-        self.sizes.update(var=self.N * G * G, scan_var=self.N * self.var_stride)
-        for k, dt in WRITTEN.items():
-            a = emu_binding.aligned((self.sizes[k] + EB.GUARD,), dt)
-            a[:self.sizes[k]], a[self.sizes[k]:] = INITIAL[k], GUARD_VALUE[k]
-            if device is not None:
-                import torch
-                a = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            self.a[k] = a
+        self.add("var", np.full((self.N, G, G), INITIAL["var"], F), guard=GUARD_VALUE["var"])
+        self.add("scan_var", np.full((self.N, self.var_stride), INITIAL["scan_var"], F), guard=GUARD_VALUE["scan_var"])
         self.fusion = dict(DEFAULTS, **(fusion or {}))
-        self._fused_entry = entry if device is not None else lib().emu_elevation_map_fused
-
-    def launch(self, tick, flags=0, edit=None, stream=None, edit_fused=None):
         ef = abi.LsimElevationMapFused()
         ef.em = self.em
-        ef.em.tick, ef.em.flags = tick, flags
-        ef.var, ef.scan_var, ef.var_stride = self._ptr("var"), self._ptr("scan_var"), self.var_stride
+        self.point(ef, ("var", "scan_var"))
+        ef.var_stride = self.var_stride
         for k, v in self.fusion.items():
             setattr(ef, k, v)
-        if edit:
-            edit(ef.em)
-        if edit_fused:
-            edit_fused(ef)
-        if self.device is not None and stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        return self._fused_entry(ctypes.byref(ef), None if stream is None else ctypes.c_void_p(stream))
+        self.em = self.bind(ef, entry if device is not None else lib().emu_elevation_map_fused).em        # the inner struct, in place
+
+    def launch(self, tick, flags=0, edit=None, stream=None, edit_fused=None):
+        def edits(ef):
+            ef.em.tick, ef.em.flags = tick, flags
+            if edit:
+                edit(ef.em)
+            if edit_fused:
+                edit_fused(ef)
+        return super().launch(edit=edits, stream=stream)
 
     def read(self):
         out = super().read()
-        for k in WRITTEN:
-            v = self.get(k, guard=True)
-            assert (v[self.sizes[k]:] == F(GUARD_VALUE[k])).all(), f"guard of {k} overwritten"
-            out[k] = v[:self.sizes[k]]
-        out["var"] = out["var"].reshape(self.N, self.G, self.G)
-        rows = out["scan_var"].reshape(self.N, self.var_stride)
+        out["var"] = self.get("var")
+        rows = self.get("scan_var")
         out["scan_var"], out["scan_var_pad"] = rows[:, :self.P], rows[:, self.P:]
         return out
 

@@ -12,6 +12,16 @@ from helpers import ROOT, abi
 CSRC = os.path.join(ROOT, "isaacgymloco_amd", "csrc")
 _NP = {abi.DT_F32: np.float32, abi.DT_I64: np.int64, abi.DT_U8: np.uint8, abi.DT_I32: np.int32, abi.DT_I16: np.int16}
 _shims = {}
+_SENSOR = ["ls_raycast.h", "ls_raycast_bodies.h", "ls_sensor_model.h", "ls_math.h"]
+# shim name (tests/emu/emu_<name>.cpp) -> the headers of csrc it is rebuilt for
+SHIMS = {
+    "raycast": ["ls_raycast.h"], "raycast_bodies": ["ls_raycast.h", "ls_raycast_bodies.h"], "sensor_model": _SENSOR,
+    "eval": ["ls_eval.h"], "eval_columns": ["ls_eval.h", "ls_eval_columns.h"], "distill": ["ls_distill.h"],
+    **{name: _SENSOR + [f"ls_{name}.h"] for name in ("sensor_stereo", "sensor_instrument", "sensor_mount_jitter", "elevation_map", "odometry",
+                                                      "frames_log", "depth_encoder", "depth_memory")},
+    "map_rows": _SENSOR + ["ls_odometry.h"], "depth_encoder_backward": _SENSOR + ["ls_depth_encoder.h", "ls_depth_encoder_bwd.h"],
+    "elevation_fuse": _SENSOR + ["ls_elevation_map.h", "ls_odometry.h", "ls_elevation_fuse.h"],
+}
 
 
 def build_shim(src, out, deps, defines=()):
@@ -35,6 +45,16 @@ def load_shim(what, headers, counters=False):
         if hasattr(L, "emu_sizeof_config"):
             abi.check_abi(L, prefix="emu")
     return _shims[what, counters]
+
+
+def shim(name, counters=False):
+    """the shim `name` of SHIMS, built and bound"""
+    return load_shim(name, SHIMS[name], counters)
+
+
+def api(*shims, count=()):
+    """EmuApi of exactly the named shims of SHIMS (or libraries already loaded), in that order; counts the calls of the names in `count`"""
+    return EmuApi(*(shim(s) if isinstance(s, str) else s for s in shims), count=count)
 
 
 def lib():

@@ -19,14 +19,14 @@ SPECIALS = np.array([np.nan, np.inf, -np.inf, 3.0e6, -3.0e6, 1.0e-12, 0.0, -0.0,
 
 
 def lib():
-    L = emu_binding.load_shim("eval_columns", ["ls_eval.h", "ls_eval_columns.h"])
+    L = emu_binding.shim("eval_columns")
     L.emu_eval_columns_accumulate_ordered.argtypes = [ctypes.POINTER(abi.LsimEvalColumns), ctypes.c_void_p]       # test-only: the env order permutation
     return L
 
 
 def EmuApi():
     """lsim_eval_* of the evaluator's shim and lsim_eval_columns_* of this one, for learn.evaluate.Evaluator(api=...)"""
-    return emu_binding.EmuApi(EE.lib(), lib(), count=("lsim_eval_accumulate", "lsim_eval_columns_accumulate", "lsim_eval_columns_clear"))
+    return emu_binding.api("eval", "eval_columns", count=("lsim_eval_accumulate", "lsim_eval_columns_accumulate", "lsim_eval_columns_clear"))
 
 
 def start_slot(group):

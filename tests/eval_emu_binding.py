@@ -17,14 +17,14 @@ FIELDS = {"rew": (np.float32, ()), "reset_buf": (np.uint8, ()), "time_out_buf": 
 
 
 def lib():
-    L = emu_binding.load_shim("eval", ["ls_eval.h"])
+    L = emu_binding.shim("eval")
     L.emu_eval_accumulate_ordered.argtypes = [ctypes.POINTER(abi.LsimEval), ctypes.c_void_p]       # test-only: the env order permutation
     return L
 
 
 def EmuApi():
     """lsim_eval_sizes / _clear / _accumulate of the shim, for learn.evaluate.Evaluator(api=...)"""
-    return emu_binding.EmuApi(lib())
+    return emu_binding.api("eval")
 
 
 class EmuEval:

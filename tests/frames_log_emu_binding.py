@@ -1,19 +1,14 @@
 """TEST INFRASTRUCTURE -- builds and binds tests/emu/emu_frames_log.cpp (the CPU shim of the two entry points of
 isaacgymloco_amd/csrc/ls_frames_log.h compiled by g++ under LS_EMU), and their rigs: one struct with the arrays it points to, in host memory
-for the shim or in device memory for the HIP library, driven call by call.  Every array a call writes has GUARD elements behind it,
+for the shim or in device memory for the HIP library, driven call by call.  Every array a call writes has guard elements behind it,
 pre-filled and checked.  The checks both tests/test_frames_log.py (shim) and tests/test_gpu_frames_log.py (device) run are here too."""
-import ctypes
-
 import numpy as np
 
 import emu_binding
 import frames_log_reference as R
-import sensor_model_emu_binding as SB
 from helpers import abi
-from odometry_emu_binding import _Arrays
+from launch_rig import EditRig, LaunchRig
 
-HEADERS = SB.HEADERS + ["ls_frames_log.h"]
-GUARD = 16
 LOG_FILL, INT_FILL = np.float32(-7.25), -99
 LsimFramesLog = abi.STRUCTS["lsim_frames_log_t"]
 LsimLatentRowsGrad = abi.STRUCTS["lsim_latent_rows_grad_t"]
@@ -22,62 +17,54 @@ assert (R.COUNT, R.OVERFLOW, R.BASE, R.NEXT) == tuple(abi.DEFINES["LSIM_FRAMES_L
 
 
 def lib():
-    return emu_binding.load_shim("frames_log", HEADERS)
+    return emu_binding.shim("frames_log")
 
 
 def EmuApi():
     """the sensor, encoder and memory shims plus this one, for envs.sensors.RaySensor(api=...)"""
-    import depth_memory_emu_binding as GB
-    return GB.EmuApi(lib())
+    return emu_binding.api("raycast", "raycast_bodies", "sensor_model", "depth_encoder", "depth_memory", "frames_log")
 
 
-class Rig(_Arrays):
+class Rig(LaunchRig):
     """the arrays of one frame log for N envs: hist [N, slots, stride] and episode_length are inputs a call replaces; log, row_of, row_src
-    and state are outputs, pre-filled as frames_log_reference.FramesLog pre-fills its own, each with GUARD elements behind it.
+    and state are outputs, pre-filled as frames_log_reference.FramesLog pre-fills its own, each with guard elements behind it.
     `device`: None -- numpy arrays and the shim -- or a torch device and `entry` = the library's lsim_sensor_frames_log."""
 
     def __init__(self, N, capacity, pixels=R.PIXELS, env_stride=1, device=None, entry=None):
-        self.N, self.capacity, self.pixels, self.device = int(N), int(capacity), int(pixels), device
-        al = emu_binding.aligned
-        self.sizes = {"log": capacity * R.FRAMES * R.ROW_STRIDE, "row_of": R.STEPS * N, "row_src": capacity, "state": 4}
-        a = {"hist": al((N, R.SLOTS, R.HIST_STRIDE), np.float32), "episode_length": al((N,), np.int64),
-             "log": al((self.sizes["log"] + GUARD,), np.float32), "row_of": al((self.sizes["row_of"] + GUARD,), np.int32),
-             "row_src": al((self.sizes["row_src"] + GUARD,), np.int32), "state": al((4 + GUARD,), np.int32)}
-        a["log"][:] = LOG_FILL
-        a["row_of"][:] = INT_FILL
-        a["row_src"][:] = INT_FILL
-        a["state"][4:] = INT_FILL
-        self.a = a
-        self._to_device()
+        super().__init__(device)
+        self.N, self.capacity, self.pixels = int(N), int(capacity), int(pixels)
+        self.add("hist", np.zeros((N, R.SLOTS, R.HIST_STRIDE), np.float32))
+        self.add("episode_length", np.zeros(N, np.int64))
+        self.add("log", np.full((capacity, R.FRAMES, R.ROW_STRIDE), LOG_FILL, np.float32), guard=LOG_FILL)
+        self.add("row_of", np.full((R.STEPS, N), INT_FILL, np.int32), guard=INT_FILL)
+        self.add("row_src", np.full(capacity, INT_FILL, np.int32), guard=INT_FILL)
+        self.add("state", np.zeros(4, np.int32), guard=INT_FILL)
         fl = LsimFramesLog()
-        fl.hist, fl.episode_length, fl.log, fl.row_of, fl.row_src, fl.state = (self._ptr(k) for k in ("hist", "episode_length", "log", "row_of", "row_src", "state"))
+        self.point(fl, ("hist", "episode_length", "log", "row_of", "row_src", "state"))
         fl.hist_stride, fl.hist_slots, fl.num_envs, fl.env_stride = R.HIST_STRIDE, R.SLOTS, self.N, int(env_stride)
         fl.frames, fl.pixels, fl.row_stride, fl.num_steps, fl.capacity = R.FRAMES, self.pixels, R.ROW_STRIDE, R.STEPS, self.capacity
         fl.period, fl.stagger = R.PERIOD, 1
-        self.fl = fl
-        self._entry = entry if device is not None else lib().emu_sensor_frames_log
+        self.fl = self.bind(fl, entry if device is not None else lib().emu_sensor_frames_log)
 
     def launch(self, hist, episode_length, tick, step, flags, edit=None, stream=None):
         """one call on new inputs; `edit(fl)` changes a copy of the struct first; returns the entry point's value"""
         self.put("hist", hist)
         self.put("episode_length", episode_length)
-        fl = LsimFramesLog.from_buffer_copy(self.fl)
-        fl.tick, fl.step, fl.flags = int(tick), int(step), int(flags)
-        if edit:
-            edit(fl)
-        return self._entry(ctypes.byref(fl), self._stream(stream))
 
-    def raw(self):
+        def edits(fl):
+            fl.step = int(step)
+            if edit:
+                edit(fl)
+        return super().launch(int(tick), int(flags), edits, stream)
+
+    def outputs_raw(self):
         """copies of the four outputs, guards included"""
-        return {k: self.get(k) for k in ("log", "row_of", "row_src", "state")}
+        return {k: self.raw(k) for k in ("log", "row_of", "row_src", "state")}
 
     def read(self):
         """(log [capacity, frames, row_stride], row_of [T, N], row_src [capacity], state [4]); asserts the four guards intact"""
-        raw = self.raw()
-        for k, fill in (("log", LOG_FILL), ("row_of", INT_FILL), ("row_src", INT_FILL), ("state", INT_FILL)):
-            assert (raw[k][self.sizes[k]:] == fill).all(), f"the guard behind {k} was overwritten"
-        return (raw["log"][:self.sizes["log"]].reshape(self.capacity, R.FRAMES, R.ROW_STRIDE), raw["row_of"][:self.sizes["row_of"]].reshape(R.STEPS, self.N),
-                raw["row_src"][:self.capacity], raw["state"][:4])
+        self.assert_guards()
+        return tuple(self.get(k) for k in ("log", "row_of", "row_src", "state"))
 
 
 def check_scenario(make_rig, N, pixels=R.PIXELS):
@@ -143,47 +130,36 @@ def check_refusals(make_rig, null_call):
     calls = R.launches(N)
     for call in calls[:2]:
         assert rig.launch(*call) == 0
-    before = rig.raw()
+    before = rig.outputs_raw()
     assert null_call() == abi.E_INVALID
     for name, edit in FRAMES_LOG_REFUSALS.items():
         assert rig.launch(*calls[2], edit=edit) == abi.E_INVALID, name
-        after = rig.raw()
+        after = rig.outputs_raw()
         for k in before:
             assert np.array_equal(before[k].view(np.uint8), after[k].view(np.uint8)), f"{name}: {k} was written"
     assert rig.launch(*calls[2]) == 0
 
 
-class GradRig(_Arrays):
-    """g [B, g_stride], mb_of, row_of, row_src and G [rows + 2, G_stride] (+ GUARD), G pre-filled with LOG_FILL"""
+class GradRig(EditRig):
+    """g [B, g_stride], mb_of, row_of, row_src and G [rows + 2, G_stride] (guarded), G pre-filled with LOG_FILL"""
 
     def __init__(self, g, mb_of, row_of, row_src, rows, latent_dim, G_stride, device=None, entry=None):
-        self.device, self.rows, self.G_stride = device, int(rows), int(G_stride)
+        super().__init__(device)
+        self.rows, self.G_stride = int(rows), int(G_stride)
         T, N = row_of.shape
-        al = emu_binding.aligned
-        a = {"g": al(g.shape, np.float32), "mb_of": al(mb_of.shape, np.int32), "row_of": al(row_of.shape, np.int32), "row_src": al(row_src.shape, np.int32),
-             "G": al(((rows + 2) * G_stride + GUARD,), np.float32)}
-        a["g"][...], a["mb_of"][...], a["row_of"][...], a["row_src"][...] = g, mb_of, row_of, row_src
-        a["G"][:] = LOG_FILL
-        self.a = a
-        self._to_device()
+        self.add("g", np.asarray(g, np.float32))
+        for k, v in (("mb_of", mb_of), ("row_of", row_of), ("row_src", row_src)):
+            self.add(k, np.asarray(v, np.int32))
+        self.add("G", np.full((self.rows + 2, self.G_stride), LOG_FILL, np.float32), guard=LOG_FILL)
         lg = LsimLatentRowsGrad()
-        lg.g, lg.mb_of, lg.row_of, lg.row_src, lg.G = (self._ptr(k) for k in ("g", "mb_of", "row_of", "row_src", "G"))
+        self.point(lg, ("g", "mb_of", "row_of", "row_src", "G"))
         lg.batch, lg.rows, lg.latent_dim, lg.g_stride, lg.G_stride, lg.num_steps, lg.num_envs = g.shape[0], self.rows, int(latent_dim), g.shape[1], self.G_stride, T, N
-        self.lg = lg
-        self._entry = entry if device is not None else lib().emu_latent_rows_grad
-
-    def launch(self, edit=None, stream=None):
-        lg = LsimLatentRowsGrad.from_buffer_copy(self.lg)
-        if edit:
-            edit(lg)
-        return self._entry(ctypes.byref(lg), self._stream(stream))
+        self.lg = self.bind(lg, entry if device is not None else lib().emu_latent_rows_grad)
 
     def read(self):
         """G [rows + 2, G_stride] with the guard checked"""
-        G = self.get("G")
-        n = (self.rows + 2) * self.G_stride
-        assert (G[n:] == LOG_FILL).all(), "the guard behind G was overwritten"
-        return G[:n].reshape(self.rows + 2, self.G_stride)
+        self.assert_guards()
+        return self.get("G")
 
 
 GRAD_REFUSALS = {
@@ -231,7 +207,7 @@ def check_grad(make_rig, N, latent_dim, null_call=None):
     if null_call is not None:
         assert null_call() == abi.E_INVALID
         for name, edit in GRAD_REFUSALS.items():
-            rig.put("G", np.full_like(rig.get("G"), LOG_FILL))
+            rig.put("G", LOG_FILL)
             assert rig.launch(edit=edit) == abi.E_INVALID, name
-            assert (rig.get("G") == LOG_FILL).all(), f"{name}: G was written"
-        assert rig.launch(edit=_set(rows=0)) == 0 and (rig.get("G") == LOG_FILL).all()
+            assert (rig.raw("G") == LOG_FILL).all(), f"{name}: G was written"
+        assert rig.launch(edit=_set(rows=0)) == 0 and (rig.raw("G") == LOG_FILL).all()

@@ -10,14 +10,14 @@ from helpers import abi
 
 
 def lib(counters=False):
-    L = emu_binding.load_shim("raycast_bodies", ["ls_raycast.h", "ls_raycast_bodies.h"], counters)
+    L = emu_binding.shim("raycast_bodies", counters)
     L.emu_raycast_bodies_poses.argtypes = [ctypes.POINTER(abi.LsimRaycastBodies), ctypes.c_void_p]       # test-only: the body pose output
     return L
 
 
 def EmuApi():
     """the four range-sensor entry points of the two shims, for envs.sensors.RaySensor(api=...); counts the launches"""
-    return emu_binding.EmuApi(EMU.lib(), lib(), count=("lsim_raycast", "lsim_raycast_bodies"))
+    return emu_binding.api("raycast", "raycast_bodies", count=("lsim_raycast", "lsim_raycast_bodies"))
 
 
 def fill(scene, tables, env_robot, root_states, dof_pos, mount, dirs, near, far, scale=None, env_stride=1, body_mask=0x1FFFF, flags=0, labels=True,

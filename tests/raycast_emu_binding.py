@@ -10,12 +10,12 @@ from helpers import abi
 
 
 def lib(counters=False):
-    return emu_binding.load_shim("raycast", ["ls_raycast.h"], counters)
+    return emu_binding.shim("raycast", counters)
 
 
 def EmuApi():
     """lsim_raycast_sizes / lsim_raycast of the shim, for envs.sensors.RaySensor(api=...)"""
-    return emu_binding.EmuApi(lib())
+    return emu_binding.api("raycast")
 
 
 def fill(scene, root_states, mount, dirs, near, far, scale=None, env_stride=1, out_fill=np.nan):

@@ -11,22 +11,10 @@ import torch
 
 import amp_update_reference as R
 import mlp_shapes_rig as G
+from launch_rig import NanDevice as _Device, bits32 as _bits32, current_stream as _stream, device_lib as _lib
 
 pytestmark = pytest.mark.gpu
 DEV = G.DEV
-
-
-def _lib():
-    from isaacgymloco_amd import lib
-    return lib.load()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _bits32(a):
-    return (np.asarray(a, dtype=np.float32) + np.float32(0.0)).view(np.int32)
 
 
 def _up(flat):
@@ -147,21 +135,6 @@ def test_masked_colsum(name):
     print("colsum", name, "out", "twin distance", dist, "tolerance", tol, "max |device - fp64|", err, "device / tolerance", err / tol if tol else 0.0,
           "scale", float(np.abs(want).max()))
     assert err <= tol, (name, err, tol)
-
-
-class _Device:
-    def __init__(self):
-        self.keep = []
-
-    def address(self, floats):
-        t = torch.full((floats + 4,), float("nan"), device=DEV)
-        assert t.data_ptr() % 16 == 0
-        self.keep.append(t)
-        return t.data_ptr()
-
-    def untouched(self):
-        torch.cuda.synchronize()
-        return all(bool(torch.isnan(t).all()) for t in self.keep)
 
 
 def test_column_entries_refuse_before_any_launch():

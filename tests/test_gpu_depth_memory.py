@@ -39,7 +39,7 @@ def test_sequence_after_an_in_place_weight_change():
     prm = list(c["prm"])
     prm[1] = (prm[1] * np.float32(-1.5)).astype(np.float32)
     import torch
-    rig.a["weight_hh"][:prm[1].size * 4].view(torch.float32).mul_(-1.5)
+    rig.a["weight_hh"][:prm[1].size].mul_(-1.5)
     assert rig.forward() == 0
     want = R.sequence(c["gi"], c["h0"], c["reset"], prm)
     got = rig.get("hs")

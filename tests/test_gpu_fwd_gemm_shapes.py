@@ -10,16 +10,12 @@ import torch
 
 import fwd_gemm_reference as R
 import mlp_shapes_rig as G
+from launch_rig import NanDevice as _Device, bits32 as _bits32, device_lib as _lib
 
 pytestmark = pytest.mark.gpu
 DEV = G.DEV
 KEYS = list(R.by_key(256))
 GENERAL_KEYS = [c["key"] for c in R.cases(256).values() if c["general"] and c["name"] in R.GENERAL]
-
-
-def _lib():
-    from isaacgymloco_amd import lib
-    return lib.load()
 
 
 def _cus():
@@ -84,11 +80,6 @@ class Launch:
         return self.out[:, :self.c["n_out"]].cpu().numpy()
 
 
-def _bits32(a):
-    """fp32 bits; + 0.0 turns a -0.0 of the statement into the +0.0 an accumulator that starts from +0.0 holds"""
-    return (np.asarray(a, dtype=np.float32) + np.float32(0.0)).view(np.int32)
-
-
 @pytest.mark.parametrize("key", KEYS)
 def test_exact_scene(key):
     """small-integer operands: every partial sum in any order is exact in fp32.  The masked product equals the statement bit for bit, element for
@@ -134,21 +125,6 @@ def test_the_table_reaches_every_class_on_this_device():
     cus = _cus()
     got = set().union(*(R.case_classes(c, cus) for c in R.cases(cus).values()))
     assert R.classes() <= got, sorted(R.classes() - got)
-
-
-class _Device:
-    def __init__(self):
-        self.keep = []
-
-    def address(self, floats):
-        t = torch.full((floats + 4,), float("nan"), device=DEV)
-        assert t.data_ptr() % 16 == 0
-        self.keep.append(t)
-        return t.data_ptr()
-
-    def untouched(self):
-        torch.cuda.synchronize()
-        return all(bool(torch.isnan(t).all()) for t in self.keep)
 
 
 def test_entries_refuse_before_any_launch():

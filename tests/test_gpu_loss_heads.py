@@ -10,19 +10,11 @@ import torch
 
 import loss_heads_reference as R
 import mlp_shapes_rig as G
+from launch_rig import NanDevice as _Device, current_stream as _stream, device_lib as _lib
 import wgrad_shapes_reference as W
 
 pytestmark = pytest.mark.gpu
 DEV = G.DEV
-
-
-def _lib():
-    from isaacgymloco_amd import lib
-    return lib.load()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _rows(a, width=None):
@@ -313,21 +305,6 @@ def test_adam_norm_and_coefficient_of_integer_gradients(name):
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------------
-class _Device:
-    def __init__(self):
-        self.keep = []
-
-    def address(self, floats):
-        t = torch.full((floats + 4,), float("nan"), device=DEV)
-        assert t.data_ptr() % 16 == 0
-        self.keep.append(t)
-        return t.data_ptr()
-
-    def untouched(self):
-        torch.cuda.synchronize()
-        return all(bool(torch.isnan(t).all()) for t in self.keep)
-
-
 def test_entries_refuse_before_any_launch():
     """the refusals of tests/test_loss_heads.py on device buffers: the tabulated code, nothing written, no HIP error left behind -- a valid call of
     every entry succeeds afterwards.  Every refused call is answered by the entry's argument checks on the host"""

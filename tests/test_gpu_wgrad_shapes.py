@@ -10,16 +10,12 @@ import pytest
 import torch
 
 import mlp_shapes_rig as G
+from launch_rig import NanDevice as _Device, bits32 as _bits32, device_lib as _lib
 import wgrad_shapes_reference as R
 
 pytestmark = pytest.mark.gpu
 DEV = G.DEV
 NAMES = list(R.CASES)
-
-
-def _lib():
-    from isaacgymloco_amd import lib
-    return lib.load()
 
 
 def _guarded_at(shape, off):
@@ -104,11 +100,6 @@ class Launch:
         return dict(dw=get(self.dw), db=get(self.db), gy=get(self.gy))
 
 
-def _bits32(a):
-    """fp32 bits; + 0.0 turns the reference's -0.0 sums into the +0.0 an accumulator that starts from +0.0 holds"""
-    return (np.asarray(a, dtype=np.float32) + np.float32(0.0)).view(np.int32)
-
-
 @pytest.mark.parametrize("name", NAMES)
 def test_exact_scene_bit_for_bit(name):
     """integer operands and activation factors that are multiples of 1/4: every partial sum in any order is exact in fp32, so dw, db and grad_pre
@@ -187,21 +178,6 @@ def test_deferred_sum_equals_the_immediate_entries_bit_for_bit():
         la.check_memory()
         for a, b in zip(w, la.outputs()):
             assert torch.equal(G.bits(a), G.bits(b)), (n, "deferred and immediate sums differ")
-
-
-class _Device:
-    def __init__(self):
-        self.keep = []
-
-    def address(self, floats):
-        t = torch.full((floats + 4,), float("nan"), device=DEV)
-        assert t.data_ptr() % 16 == 0
-        self.keep.append(t)
-        return t.data_ptr()
-
-    def untouched(self):
-        torch.cuda.synchronize()
-        return all(bool(torch.isnan(t).all()) for t in self.keep)
 
 
 def test_entries_refuse_before_any_launch():

@@ -216,7 +216,7 @@ def capture_refusals(make_rig, null_call):
     for what, edit in _capture_edits().items():
         assert rv(edit) == abi.E_INVALID, what
     rig = IS.plane_rig(make_rig, **IS.SCHED)
-    base = rig._ptr("inst")
+    base = rig.ptr("inst")
     assert rv(inst=None) == abi.E_INVALID and rv(inst=base + 4) == abi.E_INVALID and rv(inst=base + 8) == abi.E_INVALID
     del rig
 
@@ -240,5 +240,5 @@ def test_the_library_refuses_the_same_capture_arguments_before_any_launch():
         assert rig.launch(3, IR.FILL_ALL, edit) == abi.E_INVALID, what
         assert (rig.get("hist") == -7.0).all(), what
     rig = IS.plane_rig(host_rig, **IS.SCHED)
-    assert rig.launch(3, 0, inst=None) == abi.E_INVALID and rig.launch(3, 0, inst=rig._ptr("inst") + 4) == abi.E_INVALID
+    assert rig.launch(3, 0, inst=None) == abi.E_INVALID and rig.launch(3, 0, inst=rig.ptr("inst") + 4) == abi.E_INVALID
     assert (rig.get("hist") == -7.0).all()
