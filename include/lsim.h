@@ -58,7 +58,9 @@ extern "C" {
                                     lsim_elevation_map_fused (the elevation map with a banded mean per capture and a variance per cell, fused over the
                                     captures by a scalar Kalman filter) and lsim_map_rows_fused (the map's rows with a confidence block);
                                     lsim_sensor_stereo + lsim_sensor_stereo_sizes + LSIM_RNG_SENSOR_STEREO (a stereo camera's occlusion shadows, minimum
-                                    range and depth-edge artefacts, written into the frame history behind a capture) */
+                                    range and depth-edge artefacts, written into the frame history behind a capture);
+                                    lsim_sensor_shade + lsim_sensor_shade_sizes (a shaded colour frame behind lsim_raycast_bodies: the surface normal at
+                                    every hit, whether the sun reaches it, a colour per pixel) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1174,6 +1176,70 @@ int lsim_raycast_bodies_sizes(size_t* state_bytes, size_t* robot_bytes);
  * 0..11) or whose joint_pos / joint_axis is not finite; a primitive with kind outside 0..3, body outside 0..16, a non-finite pos or quat, or a
  * size entry it uses (sphere 1, box 3, capsule / cylinder 2) that is not finite and > 0. */
 int lsim_raycast_bodies(const lsim_raycast_bodies_t* rb, void* stream);
+
+/* ---- shaded frames: what turns the range and the label of lsim_raycast_bodies into a picture -- the surface normal at every hit, whether
+ * the sun reaches that point, and a colour.  ONE launch under the rules of lsim_raycast_bodies (caller's stream, no host synchronisation, raw
+ * pointers only, capturable in a graph, read-only on the simulator's buffers), enqueued BEHIND an lsim_raycast_bodies of the same `rb` on
+ * the same stream: it reads what that launch wrote, rb.rc.out and rb.labels (required), visits the same envs e = 0, env_stride, ... and
+ * writes rgba, surface and state[0] only.  Other envs' robots are neither drawn nor do they cast shadows.  All arithmetic in fp32.
+ *
+ * Per pixel r of a visited env e:
+ *   1. Ray.  o, o' = R(q or qy) mount_pos[e] and d exactly as lsim_raycast_bodies forms them (the yaw frame under LSIM_RAYCAST_FRAME_YAW).
+ *      A non-finite component of o or d, or of any of the env's twelve joint positions: the pixel is SKY (step 6) and counted in
+ *      rb.rc.state[0] (so a bad env counts once in the ray launch and once here).  L = labels[e][r]; L == 0 or L > 1 + LSIM_NUM_BODIES: SKY.
+ *   2. Range.  t0 = out[e][r] / scale[r] (scale == NULL: out[e][r]).
+ *   3. Terrain, L == 1.  mesh_type 0 or mesh == NULL: t = t0, m = (0, 0, 1).  Otherwise the cell (i, j) of P0 = o + t0 d,
+ *        i = clamp(floor((P0.x + border_size) / horizontal_scale), 0, grid_rows - 2), j likewise from P0.y and grid_cols;
+ *      over the cells (i - 1 + c / 3, j - 1 + c % 3), c = 0..8, that exist, and in each its two triangles in the order of lsim_raycast,
+ *      the FIRST triangle whose own intersection value t_k with this ray (lsim_raycast's triangle rule with near = rc.near and no upper
+ *      bound) minimises |t_k - t0| is the face of the hit: t = t_k, m = e1 x e2 of that triangle (the walk found its hit among these
+ *      triangles from the same o and d, so t_k reproduces the walk's value; t0 differs from it by the rounding of the scale only).
+ *      No triangle of the nine cells met: t = t0, m = (0, 0, 1).  n = m / |m|, negated when m . d > 0 (turned against the ray).
+ *      P = o + t d.
+ *   4. Body, L == 2 + b.  Among the SEEN primitives of body b, in table order, the first whose t_in for the ray o' + t d (the
+ *      primitive's interval of lsim_raycast_bodies) minimises |t_in - t0|: t = t_in; none: SKY.  With x = the hit point in the
+ *      primitive's frame (centre at 0), its OUTWARD normal there, n_l:
+ *        sphere    x / |x|
+ *        box       the axis k with the largest |x_k| - size[k] (the first on ties; the face of the entered slab): sign(x_k) e_k
+ *        cylinder  rho = sqrt(x_0^2 + x_1^2);  rho - r >= |x_2| - h: the side, (x_0, x_1, 0) / rho;  else the cap, (0, 0, sign(x_2))
+ *        capsule   c = (0, 0, clamp(x_2, -h, h)), the nearest point of its segment: (x - c) / |x - c|
+ *      n = n_l in world orientation (sum of n_l[k] times local axis k); it is not turned: a front face has n . d <= 0 up to rounding.
+ *      P = o + t d and P' = o' + t d.
+ *   5. Light.  c = n . sun.  light = 0 when c <= 0;  1 without LSIM_SHADE_SHADOWS;  otherwise 0 exactly when the shadow ray is occluded.
+ *      The shadow ray has direction `sun` and runs over [0, shadow_far] from P + shadow_bias n (P' + shadow_bias n for the bodies).  It is
+ *      occluded when lsim_raycast_bodies' body test with near = 0, far = shadow_far finds a contributing primitive (a seen primitive of
+ *      the env's own robot whose FRONT face is met at 0 <= t_in <= shadow_far; a primitive the point lies inside contributes nothing),
+ *      or when lsim_raycast's terrain result with near = 0, far = shadow_far is < shadow_far.  A pixel with c <= 0 casts no shadow ray.
+ *   6. Colour.  k = ambient + (1 - ambient) * light * c.  The albedo is palette[L] = r | g << 8 | b << 16, each channel a_c = byte * (1 / 255).
+ *      Terrain with checker > 0: g = k * checker_gain when (int) floor(P.x / checker) + (int) floor(P.y / checker) is odd (the checker
+ *      is anchored in the world), else g = k.  Each channel of the pixel is (uint) floor(255 * min(max(a_c * g, 0), 1) + 0.5);
+ *      rgba[e][r] = r | g << 8 | b << 16 | 255 << 24 and surface[e][r] = (n.x, n.y, n.z, light).
+ *      SKY: rgba[e][r] = (palette[0] & 0xFFFFFF) | 255 << 24, surface[e][r] = (0, 0, 0, 0).  No NaN is ever written.
+ * Two launches on the same inputs write the same bits (no atomic but the int64 count of state[0]).
+ * NOT BUILT: textures, anti-aliasing, soft shadows, specular terms, visual meshes (the collision primitives are what is drawn), frames
+ * above LSIM_RAYCAST_MAX_RAYS pixels. */
+#define LSIM_SHADE_SHADOWS 1u              /* shade_flags: cast a shadow ray from every lit pixel */
+typedef struct lsim_sensor_shade {
+    lsim_raycast_bodies_t rb;         /* the struct lsim_raycast_bodies was launched with; labels != NULL */
+    uint32_t* rgba;                   /* [N,rgba_stride] one word per pixel, 16-byte aligned */
+    float* surface;                   /* [N,R,4] normal xyz and light, 16-byte aligned, or NULL */
+    const uint32_t* palette;          /* [2 + LSIM_NUM_BODIES] rgb words by label: 0 the sky, 1 the terrain, 2 + b body b; 4-byte aligned */
+    float sun[3];                     /* unit vector TOWARDS the sun, world frame, sun[2] > 0 */
+    float ambient;                    /* 0..1 */
+    float checker;                    /* metres, >= 0 (0: none) */
+    float checker_gain;               /* factor on the darker squares: finite, >= 0 */
+    float shadow_bias, shadow_far;    /* metres, finite, >= 0 */
+    int32_t rgba_stride;              /* words between rows of rgba: >= R, a multiple of 4 */
+    uint32_t shade_flags;             /* LSIM_SHADE_SHADOWS or 0 */
+} lsim_sensor_shade_t;
+/* bytes of rb.rc.state (lsim_raycast's) and of `palette`.  LSIM_E_INVALID: a NULL output pointer */
+int lsim_sensor_shade_sizes(size_t* state_bytes, size_t* palette_bytes);
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: ss == NULL; anything
+ * lsim_raycast_bodies refuses in ss->rb; rb.labels == NULL; rgba NULL or not 16-byte aligned; surface given and not 16-byte aligned;
+ * palette NULL or not 4-byte aligned; rgba_stride < R or not a multiple of 4; a component of sun not finite, | |sun|^2 - 1 | > 1e-3 or
+ * sun[2] <= 0; ambient outside [0, 1] (or NaN); checker, checker_gain, shadow_bias or shadow_far negative or not finite; a bit of
+ * shade_flags other than LSIM_SHADE_SHADOWS. */
+int lsim_sensor_shade(const lsim_sensor_shade_t* ss, void* stream);
 
 /* ---- sensor model: a range sensor as a real instrument -- an update period, latency, a short history of frames, noise, dropout, clipping.
  * ONE launch, same rules as lsim_raycast_bodies (caller's stream, no host synchronisation, read-only on the simulator's buffers).  The launch

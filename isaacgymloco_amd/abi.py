@@ -114,6 +114,7 @@ LsimSensorModel = STRUCTS["lsim_sensor_model_t"]
 LsimSensorMountJitter = STRUCTS["lsim_sensor_mount_jitter_t"]
 LsimSensorInstrument = STRUCTS["lsim_sensor_instrument_t"]
 LsimSensorStereo = STRUCTS["lsim_sensor_stereo_t"]
+LsimSensorShade = STRUCTS["lsim_sensor_shade_t"]
 LsimElevationMap = STRUCTS["lsim_elevation_map_t"]
 LsimOdometry = STRUCTS["lsim_odometry_t"]
 LsimMapRows = STRUCTS["lsim_map_rows_t"]

@@ -28,6 +28,7 @@ static void lsbk_prof_free(lsim_sim* s);
 #include "ls_sensor_model.h"     // the sensor model (lsim_sensor_capture): the same casts for the envs that are due, then noise / dropout / clip and the frame history
 #include "ls_sensor_mount_jitter.h"    // per-episode jitter of a sensor's mount pose (lsim_sensor_mount_jitter): rewrites the mount rows of the envs just reset, ahead of the capture
 #include "ls_sensor_instrument.h"      // per-episode error of a sensor's own constants (lsim_sensor_instrument) and the capture that reads the rows (lsim_sensor_capture_inst)
+#include "ls_sensor_shade.h"    // shaded colour frames behind lsim_raycast_bodies (lsim_sensor_shade): the normal at every hit, a sun shadow ray through the same two casts, a colour per pixel
 #include "ls_sensor_stereo.h"   // stereo artefacts behind a capture (lsim_sensor_stereo): occlusion shadows, the minimum range and depth-edge holes / fattening, written into the frame history
 #include "ls_elevation_map.h"   // the elevation map (lsim_elevation_map): a per-env height grid fused from the depth rows a capture wrote, sampled at the height-scan points
 #include "ls_odometry.h"        // the map policy's per-step launches: an estimated pose that drifts (lsim_odometry_step) and the map's scan as actor rows (lsim_map_rows)

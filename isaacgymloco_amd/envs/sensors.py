@@ -52,6 +52,13 @@ model's drop_value, a fattened pixel its foreground's captured value -- so frame
 see them; `out` / image() stay clean and `cam.stereo_counts()` counts holes and fattened pixels.  spec() records the option and
 from_spec() rebuilds it.  Without `stereo` nothing of this is created or launched.
 
+Shaded frames (`shading=Shading(sun=(145, 50))`, lsim_sensor_shade; a camera with see_robot=True, labels=True and no model): what a
+person watches -- one launch directly behind the rays finds the surface normal at every hit, casts one shadow ray towards the sun against
+the terrain and the env's own robot, and writes a colour per pixel from a palette by label, with a world-anchored checker on the ground.
+`cam.rgb_image()` is the live uint8 [N, H, W, 3] frame, `cam.surface()` the normals and the light term.  `chase_camera(env)` is the
+viewer's camera: behind and above the robot in the yaw frame, shaded (tools/sensor_frames.py --shade, learn/evaluate.py frames=...).
+spec() records the option and from_spec() rebuilds it.  Without `shading` nothing of this is created or launched.
+
 Elevation map (`cam.attach_map(ElevationMap(size=32, resolution=0.0625, source="noisy"))`, lsim_elevation_map; needs a model): what a robot
 runs next to, or instead of, a learned terrain memory -- per env a robot-centred grid of heights, filled from the depth points of every
 capture with the robot's own pose, which remembers the ground under the trunk after the camera has moved on.  One launch behind every
@@ -90,6 +97,16 @@ import torch
 
 from .. import abi, lib
 from . import config
+
+
+def write_ppm(path, rgb):
+    """binary PPM (P6) of a uint8 [H, W, 3] array: a text header plus raw bytes, what every image tool opens"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError(f"write_ppm: expected [H, W, 3], got {rgb.shape}")
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        f.write(rgb.tobytes())
 
 
 def quat_from_pitch(pitch_deg):
@@ -276,6 +293,63 @@ def parse_stereo(text):
     return parse_option(StereoArtifacts, text)
 
 
+def _rgb(r, g, b):
+    return r | g << 8 | b << 16
+
+
+def _default_palette():
+    """sky, terrain, trunk, then per leg hip / thigh / calf / foot: one hue per kind of body, a little darker from leg to leg"""
+    kinds = ((235, 130, 40), (60, 110, 210), (70, 175, 90), (225, 50, 50))          # hip orange, thigh blue, calf green, foot red
+    legs = [_rgb(*(int(c * (1.0 - 0.08 * leg)) for c in kinds[k])) for leg in range(4) for k in range(4)]
+    return (_rgb(135, 206, 235), _rgb(150, 140, 120), _rgb(205, 205, 210)) + tuple(legs)
+
+
+def _palette_text(v):
+    return None if v.lower() == "none" else tuple(int(x, 16) for x in v.split(":"))
+
+
+class Shading(_Option):
+    """What lsim_sensor_shade adds behind the rays of a camera that sees the robot and labels its pixels (include/lsim.h states every
+    formula): a colour per pixel.  `sun` = (azimuth_deg, elevation_deg): where the sun stands, azimuth counter-clockwise from the world
+    +x, elevation above the horizon in (0, 90]; `ambient`: the light a surface turned away from the sun, or shadowed, still gets;
+    `shadows`: one shadow ray per lit pixel, against the terrain and the env's own robot, over `shadow_far` metres from `shadow_bias`
+    metres off the surface; `checker` (metres, 0: none): a world-anchored checker on the terrain whose darker squares are
+    `checker_gain` as bright -- what shows motion over flat ground; `palette`: 2 + 17 words r | g << 8 | b << 16 by label (sky,
+    terrain, body 0..16), None: one hue each for trunk, hips, thighs, calves and feet.
+    The defaults are STATED GUESSES: a mid-afternoon sun behind the robot's left shoulder at spawn yaw 0, and figures chosen for
+    frames that read well, fitted to nothing."""
+    FIELDS = ("sun", "ambient", "shadows", "checker", "checker_gain", "palette", "shadow_bias", "shadow_far")
+    TEXT = {"sun": (float, ":", (2,)), "ambient": float, "shadows": _flag, "checker": float, "checker_gain": float, "palette": _palette_text,
+            "shadow_bias": float, "shadow_far": float}
+
+    def __init__(self, sun=(145.0, 50.0), ambient=0.35, shadows=True, checker=0.5, checker_gain=0.8, palette=None, shadow_bias=2e-3, shadow_far=4.0):
+        self.sun = (float(sun[0]), float(sun[1]))
+        self.ambient, self.shadows, self.checker, self.checker_gain = float(ambient), bool(shadows), float(checker), float(checker_gain)
+        self.shadow_bias, self.shadow_far = float(shadow_bias), float(shadow_far)
+        self.palette = None if palette is None else tuple(int(w) for w in palette)
+        words = 2 + abi.DEFINES["LSIM_NUM_BODIES"]
+        if len(sun) != 2 or not all(math.isfinite(x) for x in self.sun) or not 0.0 < self.sun[1] <= 90.0:
+            raise ValueError(f"Shading: sun is (azimuth_deg, elevation_deg) with 0 < elevation <= 90, got {sun}")
+        values = (self.checker, self.checker_gain, self.shadow_bias, self.shadow_far)
+        if not 0.0 <= self.ambient <= 1.0 or any(not math.isfinite(x) or x < 0.0 for x in values):
+            raise ValueError(f"Shading: 0 <= ambient <= 1 and finite checker, checker_gain, shadow_bias, shadow_far >= 0, got {(self.ambient,) + values}")
+        if self.palette is not None and (len(self.palette) != words or any(not 0 <= w <= 0xFFFFFF for w in self.palette)):
+            raise ValueError(f"Shading: palette is None or {words} words r | g << 8 | b << 16 (sky, terrain, body 0..16)")
+
+    def sun_vector(self):
+        """the unit vector towards the sun, world frame"""
+        az, el = math.radians(self.sun[0]), math.radians(self.sun[1])
+        return (math.cos(el) * math.cos(az), math.cos(el) * math.sin(az), math.sin(el))
+
+    def palette_words(self):
+        return _default_palette() if self.palette is None else self.palette
+
+
+def parse_shading(text):
+    """a Shading of 'sun=145:50,ambient=0.35,shadows=1,checker=0.5,...' ('' or 'default': the defaults): the text the tools take"""
+    return parse_option(Shading, text)
+
+
 class MapFusion(_Option):
     """A variance per cell of an ElevationMap and the fusion by it (lsim_elevation_map_fused; include/lsim.h states every formula).  Within
     a capture a cell takes the MEAN of the points that lie at most `band` metres below its highest one -- the maximum of k noisy points
@@ -407,12 +481,12 @@ def parse_elevation_map(text):
 
 _ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "map_rows", "encoder", "memory")      # a chain's launch order
 # launched directly behind the stage named, in this order: the stereo artefacts rewrite what the capture wrote before anybody reads it
-# (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument
-_BEHIND = {"stereo": "capture", "frames_log": "capture"}
+# (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument; the shading reads what the rays just wrote
+_BEHIND = {"shade": "rays", "stereo": "capture", "frames_log": "capture"}
 _LAUNCH_ORDER = tuple(n for o in _ORDER for n in (o,) + tuple(k for k, v in _BEHIND.items() if v == o))
 _DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory", "frames_log")}                                # who goes with whom
 _ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
-           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
+           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "shade": "shading (shading=Shading(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
            "memory": "memory (attach_memory)", "frames_log": "frame log (attach_frames_log)"}
 _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
 
@@ -465,6 +539,9 @@ class RaySensor:
     `stereo` (a StereoArtifacts; a pinhole camera with a model): lsim_sensor_stereo directly behind every capture rewrites the pixels of the
     frame history a stereo pair has no or a wrong depth for; `set_stereo(opt | None)`, `stereo_counts()` the live [2] int64 of holes and
     fattened pixels.  With `stereo=None` nothing of this is allocated or launched.
+    `shading` (a Shading; see_robot and labels, no model): lsim_sensor_shade directly behind the rays writes a colour per pixel and the
+    surface normal and light term of every hit; `set_shading(opt | None)`, `rgba()` the live uint8 [N, R, 4] colours (a camera:
+    `rgba_image()` / `rgb_image()`), `surface()` the live [N, R, 4].  With `shading=None` nothing of this is allocated or launched.
     `attach_map(m)` (an ElevationMap; needs a model): lsim_elevation_map behind every capture; `map_scan()` / `map_known()` are the live
     [N, P] samples, `map_heights()` a window-ordered copy for people and tools, `map_state()` the three raw arrays.  Without it nothing
     of this is allocated or launched.  `attach_map(m, odometry=OdometryError(...))`: lsim_odometry_step ahead of every capture, and the map
@@ -482,10 +559,10 @@ class RaySensor:
     `label_rows`: the padded tensors `out` / `labels()` are views of; `history()`: the raw frame history."""
 
     mount_jitter, instrument, map, odometry, map_channels = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "map_rows"))
-    encoder, memory, stereo = _option("encoder"), _option("memory"), _option("stereo")
+    encoder, memory, stereo, shading = _option("encoder"), _option("memory"), _option("stereo"), _option("shade")
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
-                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None, stereo=None):
+                 see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None, stereo=None, shading=None):
         self.env = env
         self.model = model
         self._api = api if api is not None else env._L
@@ -551,6 +628,8 @@ class RaySensor:
             self.set_instrument(instrument)
         if stereo is not None:
             self.set_stereo(stereo)
+        if shading is not None:
+            self.set_shading(shading)
 
     # ---- the chain
     def chain(self):
@@ -592,9 +671,10 @@ class RaySensor:
         """`stage` joins the chain, in place of the one of its name.  What every stage has in common with the capture -- who starts an
         episode, the noise stream, the envs visited -- is written here, into the fields its struct has"""
         if stage.struct is not None and stage.name not in ("rays", "capture"):
-            for src, fields in ((self._stages["capture"].struct, ("episode_length", "seed", "rank", "stream_id")), (self.ray_struct, ("num_envs", "env_stride"))):
+            cap = self._stages.get("capture")           # none behind plain rays: the shading, which has none of its fields
+            for src, fields in ((getattr(cap, "struct", None), ("episode_length", "seed", "rank", "stream_id")), (self.ray_struct, ("num_envs", "env_stride"))):
                 for f in fields:
-                    if hasattr(stage.struct, f):
+                    if src is not None and hasattr(stage.struct, f):
                         setattr(stage.struct, f, getattr(src, f))
         self._stages[stage.name] = stage
         self._rebuild()
@@ -714,6 +794,49 @@ class RaySensor:
     def stereo_counts(self):
         """live [2] int64 tensor: the holes written and the pixels fattened so far (stereo=...)"""
         return self._need("stereo").buffers["state"]
+
+    def set_shading(self, shading):
+        """`shading` (a Shading) from now on, or None: no launch and no buffers.  One launch directly behind the rays, which reads the
+        range and the label they just wrote; it applies from the next update()"""
+        if shading is None:
+            return self._drop("shade")
+        if not isinstance(shading, Shading):
+            raise TypeError(f"shading: expected a Shading or None, got {type(shading).__name__}")
+        if self.label_rows is None:
+            raise ValueError("shading needs see_robot=True and labels=True: the colour of a pixel is the colour of what its label names")
+        if self.model is not None:
+            raise ValueError("shading takes no model (SensorModel): an env that is not due would be shaded from a stale range under a fresh pose")
+        for need in ("lsim_sensor_shade", "lsim_sensor_shade_sizes"):
+            if not hasattr(self._api, need):
+                raise ValueError(f"shading: the loaded library has no {need}; rebuild it (there is no torch fall-back for the shaded frames)")
+        nbytes, pbytes = ctypes.c_size_t(), ctypes.c_size_t()
+        lib.check(self._api.lsim_sensor_shade_sizes(ctypes.byref(nbytes), ctypes.byref(pbytes)), what="lsim_sensor_shade_sizes")
+        words = shading.palette_words()
+        if pbytes.value != 4 * len(words):
+            raise lib.LsimError("lsim_sensor_shade: the library's palette differs from include/lsim.h; rebuild")
+        N, R = int(self.env.num_envs), self.num_rays
+        stride = (R + 3) // 4 * 4
+        buffers = self._kept("shade", lambda: {"rgba": self._zeros(N, 4 * stride, dtype=torch.uint8), "surface": self._zeros(N, R, 4)})
+        buffers["palette"] = torch.tensor(words, dtype=torch.int32, device=self.out_rows.device)
+        ss = abi.LsimSensorShade()
+        ctypes.memmove(ctypes.addressof(ss.rb), ctypes.addressof(self.bodies_struct), ctypes.sizeof(abi.LsimRaycastBodies))
+        ss.rgba, ss.surface, ss.palette, ss.rgba_stride = buffers["rgba"].data_ptr(), buffers["surface"].data_ptr(), buffers["palette"].data_ptr(), stride
+        sun = np.asarray(shading.sun_vector(), np.float32)
+        for k in range(3):
+            ss.sun[k] = float(sun[k])
+        ss.ambient, ss.checker, ss.checker_gain = shading.ambient, shading.checker, shading.checker_gain
+        ss.shadow_bias, ss.shadow_far = shading.shadow_bias, shading.shadow_far
+        ss.shade_flags = abi.DEFINES["LSIM_SHADE_SHADOWS"] if shading.shadows else 0
+        self._attach(Stage(self, "shade", "lsim_sensor_shade", ss, buffers, shading))
+
+    def rgba(self):
+        """live uint8 [N, R, 4] view of the colour words of the latest launch: red, green, blue, 255 (shading=...)"""
+        return self._need("shade").buffers["rgba"][:, :4 * self.num_rays].unflatten(1, (self.num_rays, 4))
+
+    def surface(self):
+        """live [N, R, 4] tensor of the latest launch: the unit surface normal at every hit, world frame, and the light term 0 / 1; zeros
+        where nothing is hit (shading=...)"""
+        return self._need("shade").buffers["surface"]
 
     def set_mount_jitter(self, jitter):
         """`jitter` (a MountJitter) from now on, or None: back to the nominal mount and no launch.  The new poses are drawn by the next
@@ -1215,7 +1338,8 @@ class RaySensor:
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
         one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's,
-        "odometry" the OdometryError the map was attached with and "stereo" a StereoArtifacts', each absent without one."""
+        "odometry" the OdometryError the map was attached with, "stereo" a StereoArtifacts' and "shading" a Shading's, each absent
+        without one."""
         out = dict(self.kind)
         out["dirs"] = self.dirs.cpu().tolist()
         out["scale"] = None if self.scale is None else self.scale.cpu().tolist()
@@ -1233,7 +1357,8 @@ class RaySensor:
             out["mount"] = {n: pose(r[0]) for n, r in zip(names, rows) if len(r)}
         else:
             out["mount"] = None
-        for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry), ("stereo", self.stereo)):
+        for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry), ("stereo", self.stereo),
+                            ("shading", self.shading)):
             if option is not None:
                 out[key] = option.record()
         return out
@@ -1266,11 +1391,31 @@ class DepthCamera(RaySensor):
         """[N, frames, H, W] view of frames()"""
         return self.frames().unflatten(2, (self.height, self.width))
 
+    def rgba_image(self):
+        """live uint8 [N, H, W, 4] view of the shaded frame: red, green, blue, 255 (shading=...)"""
+        return self.rgba().unflatten(1, (self.height, self.width))
+
+    def rgb_image(self):
+        """[N, H, W, 3] view of rgba_image(): what a PPM holds"""
+        return self.rgba_image()[..., :3]
+
 
 def depth_camera(env, width, height, hfov_deg, mount_pos=(0.0, 0.0, 0.0), pitch_deg=0.0, near=0.05, far=5.0, env_stride=1, api=None, **options):
     """a pinhole depth camera looking along the base x axis pitched down by `pitch_deg`; `mount_pos` and `options` (see_robot, ignore_bodies,
-    labels, frame, model, mount_jitter, instrument, stereo) as RaySensor's"""
+    labels, frame, model, mount_jitter, instrument, stereo, shading) as RaySensor's"""
     return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api, **options)
+
+
+def chase_camera(env, width=128, height=96, hfov_deg=60.0, mount_pos=(-1.2, 0.0, 0.7), pitch_deg=28.0, near=0.05, far=8.0, env_stride=1, api=None,
+                 shading="default", **options):
+    """the viewer's camera: behind and above the robot, following its position and yaw only (frame="yaw"), seeing the robot, labelled and
+    shaded (`shading`: a Shading, None for depth and labels only; by default Shading()).  `rgb_image()` is the frame; width * height stays
+    within LSIM_RAYCAST_MAX_RAYS.  `far` 8 m is a stated guess: the horizon of a 28 degree pitch over flat ground lies beyond any far."""
+    if width * height > abi.DEFINES["LSIM_RAYCAST_MAX_RAYS"]:
+        raise ValueError(f"chase_camera: {width} x {height} exceeds LSIM_RAYCAST_MAX_RAYS = {abi.DEFINES['LSIM_RAYCAST_MAX_RAYS']} pixels")
+    shading = Shading() if isinstance(shading, str) and shading == "default" else shading
+    return DepthCamera(env, width, height, hfov_deg, mount_pos, pitch_deg, near, far, env_stride, api, see_robot=True, labels=True, frame="yaw",
+                       shading=shading, **options)
 
 
 def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.05, far=10.0, env_stride=1, api=None,
@@ -1285,13 +1430,14 @@ def lidar(env, channels, vfov_deg, points_per_rev, mount_pos=(0.0, 0.0, 0.0), mo
 _KIND_KEYS = {"rays": (), "camera": ("width", "height"), "lidar": ("channels", "points_per_rev")}
 
 
-def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec", stereo="spec"):
+def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec", stereo="spec",
+              shading="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
     (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor),
     `odometry` for the OdometryError that map is attached with (without a map it has nothing to act on), `stereo` for the recorded
-    StereoArtifacts."""
+    StereoArtifacts, `shading` for the recorded Shading."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -1314,11 +1460,11 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     model = option("model", "spec", SensorModel, "model")
     mount_jitter, instrument = option("mount_jitter", mount_jitter, MountJitter, "mount_jitter"), option("instrument", instrument, InstrumentError, "instrument")
     elevation_map, odometry = option("elevation_map", elevation_map, ElevationMap, "map"), option("odometry", odometry, OdometryError, "odometry")
-    stereo = option("stereo", stereo, StereoArtifacts, "stereo")
+    stereo, shading = option("stereo", stereo, StereoArtifacts, "stereo"), option("shading", shading, Shading, "shading")
     kind = spec.get("kind", "rays") if spec.get("kind") in _KIND_KEYS else "rays"
     dirs, scale = np.asarray(spec["dirs"], dtype=np.float32), None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32)
     options = dict(env_stride=spec["env_stride"], api=api, see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"],
-                   frame=spec["frame"], model=model, mount_jitter=mount_jitter, instrument=instrument, stereo=stereo)
+                   frame=spec["frame"], model=model, mount_jitter=mount_jitter, instrument=instrument, stereo=stereo, shading=shading)
     if kind == "camera":                    # DepthCamera's constructor derives the rays from a field of view; the record holds the rays themselves
         sensor = DepthCamera(env, spec["width"], spec["height"], None, pos, near=spec["near"], far=spec["far"], rays=(dirs, scale), mount_quat=quat, **options)
     else:

@@ -13,6 +13,8 @@ import argparse
 import copy
 import ctypes
 import json
+import math
+import os
 import sys
 
 import numpy as np
@@ -504,13 +506,67 @@ def _map_fusion_columns(env, cam):
     return out
 
 
-def _run(env, ac, ev, steps, cmd, fused, packed_cls, rows=None, blind=False, metrics=()):
+class FrameWriter:
+    """evaluate(frames=...): a shaded chase camera (envs.sensors.chase_camera) on the evaluated env and one PPM per chosen env every
+    `every` steps.  {"dir", "every" (default 10), "envs" (default (0,)), "size" (W, H) (default (128, 96)), "shading" (a Shading; None:
+    the default one)}; "api": the library the camera launches through (default: the env's).  The camera renders only every g-th env,
+    g the greatest common divisor of the chosen envs (one env: that env's multiples; env 0 alone: env 0 only), and is launched only on
+    the steps that write: one device-to-host copy per written frame and none otherwise.  finish() also writes `e<env>.gif` per env
+    when PIL can be imported."""
+
+    def __init__(self, env, frames):
+        unknown = set(frames) - {"dir", "every", "envs", "size", "shading", "api"}
+        if unknown or "dir" not in frames:
+            raise ValueError(f"evaluate: frames is a dict with 'dir' and optionally 'every', 'envs', 'size', 'shading'; got {sorted(frames)}")
+        self.dir, self.every = str(frames["dir"]), int(frames.get("every", 10))
+        self.envs = tuple(int(e) for e in frames.get("envs", (0,)))
+        W, H = (int(v) for v in frames.get("size", (128, 96)))
+        N = int(env.num_envs)
+        if self.every < 1 or not self.envs or any(not 0 <= e < N for e in self.envs):
+            raise ValueError(f"evaluate: frames needs every >= 1 and envs in [0, {N}), got every={self.every}, envs={self.envs}")
+        shading = frames.get("shading")
+        stride = math.gcd(*self.envs) or N
+        self.cam = sensors.chase_camera(env, W, H, env_stride=stride, api=frames.get("api"), shading=sensors.Shading() if shading is None else shading)
+        os.makedirs(self.dir, exist_ok=True)
+        self.step, self.written = 0, []
+
+    def after_step(self):
+        """called behind env.step_device(): on every `every`-th step launch the camera and write the chosen envs' frames"""
+        self.step += 1
+        if self.step % self.every:
+            return
+        self.cam.update()
+        rgb = self.cam.rgb_image()
+        for e in self.envs:
+            img = rgb[e].cpu().numpy()             # the one device-to-host copy of this frame
+            path = os.path.join(self.dir, f"e{e}_s{self.step:05d}.ppm")
+            sensors.write_ppm(path, img)
+            self.written.append((e, path, img))
+
+    def finish(self):
+        """the GIFs, when PIL is there; returns what was written: {"frames": [...paths], "gifs": [...paths]}"""
+        gifs = []
+        try:
+            from PIL import Image
+        except ImportError:
+            Image = None
+        for e in (self.envs if Image is not None else ()):
+            images = [Image.fromarray(img) for env_id, _, img in self.written if env_id == e]
+            if images:
+                path = os.path.join(self.dir, f"e{e}.gif")
+                images[0].save(path, save_all=True, append_images=images[1:], duration=20 * self.every, loop=0)
+                gifs.append(path)
+        print(f"evaluate: {len(self.written)} frames (PPM) under {self.dir}" + (f", {len(gifs)} GIF" if gifs else "; no PIL, so no GIF"))
+        return {"frames": [p for _, p, _ in self.written], "gifs": gifs}
+
+
+def _run(env, ac, ev, steps, cmd, fused, packed_cls, rows=None, blind=False, metrics=(), frames=None):
     """evaluate()'s loop, for every kind of policy.  `packed_cls`: the fused launch's class (PackedHimPolicy; PackedVisionPolicy when the
     actor reads more rows), used when the topology allows and `fused` is not False, else act_inference.  `rows()`: the live [N, L] tensor
     the actor also reads (cam.latent, cam.memory_rows, cam.map_rows), zeros in its place when `blind`.  `metrics`: (name, fn) per
     evaluator column, fn(actions, zero_mean, live, priv) -> [N] from the observation the action came from (the step's reset flags decide
     what counts); zero_mean is the action mean over zero rows, one more policy forward per step, made only for a "depth_influence"
-    column of a policy that is not blind (None otherwise)."""
+    column of a policy that is not blind (None otherwise).  `frames`: a FrameWriter, told of every step behind step_device()."""
     names = tuple(n for n, _ in metrics)
     if names and ev.column_names != names:
         ev.add_columns(names)
@@ -551,6 +607,10 @@ def _run(env, ac, ev, steps, cmd, fused, packed_cls, rows=None, blind=False, met
         ev.accumulate()
         if metrics:
             ev.accumulate_columns()
+        if frames is not None:
+            frames.after_step()
+    if frames is not None:
+        ev.frames_written = frames.finish()
     return ev
 
 
@@ -567,7 +627,7 @@ def _influence(blind):
     return lambda actions, zero_mean, live, priv: 0.0 if blind else torch.linalg.vector_norm(actions - zero_mean, dim=1)
 
 
-def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, memory=None, memory_head=None):
+def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, memory=None, memory_head=None, frames=None):
     """evaluate() for a VisionActorCritic: the actor also reads the sensor's live latent rows -- with a memory [z | h] -- and the evaluator
     accumulates the `metrics` as columns (module docstring of learn/vision.py).  A metric whose inputs are
     missing -- its head, the map, a privileged observation that holds the scan, the scan's own points -- is dropped, not zero."""
@@ -592,10 +652,10 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.latent if memory is None else cam.memory_rows, blind,
-                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
+                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
 
 
-def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
+def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics, frames=None):
     """evaluate() for a map policy: the actor also reads the sensor's live map rows; of the `metrics` a map policy has "depth_influence"
     (the action distance against zero rows), "map_scan_error" (the rows' height block against the privileged observation's) and
     "map_coverage"; the encoder's and the memory's are dropped"""
@@ -608,10 +668,10 @@ def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics):
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.map_rows, blind,
-                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)])
+                [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
 
 
-def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, explicit):
+def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, explicit, frames=None):
     """evaluate() for a scan policy (learn/scan_policy.py): the actor also reads the scan block of the live privileged observation --
     a column-slice view, so the fused launch takes it with ld = num_priv_obs and nothing is copied.  Only the base columns are reported:
     there is no sensor, encoder or map to measure, so vision metrics that were NAMED are refused."""
@@ -623,13 +683,13 @@ def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, expli
     if (int(record.get("offset", off)), int(record.get("width", width))) != (off, width) or width != ac.depth_latent_dim:
         raise ValueError(f"evaluate: the scan policy read the block {record}, the env's is offset {off}, width {width}; the actor reads {ac.depth_latent_dim}")
     priv = env.get_privileged_observations()
-    return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, lambda: priv[:, off:off + width], blind)
+    return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, lambda: priv[:, off:off + width], blind, frames=frames)
 
 
 @torch.no_grad()
 def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "level"), trace_envs=(), trace_capacity=None, fused=None, evaluator=None,
              sensor=None, encoder=None, depth_head=None, blind=False, vision_metrics=VISION_METRICS, camera_jitter="trained",
-             camera_instrument="trained", odometry="trained", camera_stereo="trained"):
+             camera_instrument="trained", odometry="trained", camera_stereo="trained", frames=None):
     """The loop of play.py:124-133 on the device: per step write the commands (when given: (vx, vy, yaw) or a tensor [N, 3]), take the MEAN
     action (fused lsim_policy_forward when the topology allows and `fused` is not False, HIMActorCritic.act_inference otherwise), step, accumulate.
     No host synchronisation inside the loop.  Returns the Evaluator (`.result()`, `.trace()`).
@@ -661,7 +721,11 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     odometry map_scan_error uses the ESTIMATED base height, the one the map has.
     A scan policy (a ScanOnPolicyRunner or its checkpoint, recognised by its "scan_policy" record) reads the scan block of the live
     privileged observation; `blind=True` feeds zeros; only the base columns are reported and `vision_metrics` other than the default
-    or an empty tuple are refused: there is nothing of a camera to measure."""
+    or an empty tuple are refused: there is nothing of a camera to measure.
+    `frames` (None: nothing of this is allocated, launched or written): {"dir": ..., "every": K, "envs": (...), "size": (W, H), "shading":
+    Shading | None} -- what a person watches (FrameWriter): a shaded chase camera (envs.sensors.chase_camera, lsim_sensor_shade) follows
+    the chosen envs and `dir/e<env>_s<step>.ppm` is written every K steps, plus one `e<env>.gif` per env at the end when PIL can be
+    imported; the Evaluator's `frames_written` lists the files.  The result is the one without frames."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
     found = {}
@@ -680,6 +744,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         record = (d.get("map_policy") or d.get("vision") or {}).get("sensor")        # the checkpoint's record of the sensor; None: a runner, a module
         conventions = _sensor_options(cam, record, camera_jitter, camera_instrument, odometry, camera_stereo)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
+    frames = None if frames is None else FrameWriter(env, frames)
     cmd = None
     if commands is not None:
         cmd = torch.as_tensor(commands, dtype=torch.float32, device=dev)
@@ -687,15 +752,15 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
     if not is_vision:
-        return _run(env, ac, ev, steps, cmd, fused, PackedHimPolicy)
+        return _run(env, ac, ev, steps, cmd, fused, PackedHimPolicy, frames=frames)
     if is_scan:
         return _evaluate_scan(env, ac, ev, steps, cmd, fused, found["scan_policy"], bool(blind), tuple(vision_metrics or ()),
-                              explicit=vision_metrics is not VISION_METRICS)
+                              explicit=vision_metrics is not VISION_METRICS, frames=frames)
     ev.extra_conventions.update(conventions)
     if is_map:
-        return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()))
+        return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()), frames=frames)
     return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
-                            memory=found.get("memory"), memory_head=found.get("memory_head"))
+                            memory=found.get("memory"), memory_head=found.get("memory_head"), frames=frames)
 
 
 def format_table(result):
@@ -736,9 +801,23 @@ def parse_args(argv=None):
                     "'trained' (the checkpoint's record), 'off' or baseline=B,max_disparity=D,window=W,max_range=R,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q (any subset)")
     ap.add_argument("--odometry", default="trained", help="the dead-reckoning error of the pose an elevation map is placed with: 'trained' (the "
                     "checkpoint's record), 'off' or scale=S,yaw_per_m=Y,z_per_m=Z,noise=a:b:c (any subset)")
+    ap.add_argument("--frames", default=None, metavar="DIR", help="write shaded chase-camera frames of the chosen envs here: e<env>_s<step>.ppm, and e<env>.gif when PIL is there")
+    ap.add_argument("--frames-every", type=int, default=10, help="a frame every K steps")
+    ap.add_argument("--frames-envs", default="0", help="the envs to follow, e.g. 0,7")
+    ap.add_argument("--frames-size", default="128x96", help="WIDTHxHEIGHT, at most LSIM_RAYCAST_MAX_RAYS pixels")
+    ap.add_argument("--frames-shading", default="default", help="sun=AZ:EL,ambient=A,shadows=0|1,checker=M,checker_gain=G,shadow_bias=B,shadow_far=F (any subset)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.frames is not None:
+        try:
+            size = tuple(int(v) for v in a.frames_size.lower().split("x"))
+            if len(size) != 2:
+                raise ValueError(f"--frames-size takes WIDTHxHEIGHT, got {a.frames_size!r}")
+            a.frames = {"dir": a.frames, "every": a.frames_every, "envs": tuple(int(v) for v in a.frames_envs.split(",") if v), "size": size,
+                        "shading": sensors.parse_shading(a.frames_shading)}
+        except ValueError as exc:
+            ap.error(f"--frames: {exc}")
     for name, parse in (("camera_instrument", parse_camera_instrument), ("odometry", parse_odometry), ("camera_jitter", parse_camera_jitter),
                         ("camera_stereo", parse_camera_stereo)):
         try:
@@ -798,7 +877,7 @@ def main(argv=None):
         a.vision_metrics = ()
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
                   vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry,
-                  camera_stereo=a.camera_stereo)
+                  camera_stereo=a.camera_stereo, frames=a.frames)
     res = ev.result()
     print(format_table(res))
     with open(a.out, "w") as f:

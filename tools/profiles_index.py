@@ -76,6 +76,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "elevation_refactor_ab.json": ("parent commit against the commit that folded the elevation map's copied kernel text and the sensor chain's visit rule into one text each: digests of every array of the touched launches on the test scenes (CPU shims and device) and at N = 4096 (bit-identical), register tables and the assembly comparison, then `tools/raycast_time.py --map` (with `--odometry --map-rows 2`, and with `fusion=default`) in five alternating rounds with the parent's library against itself as the null pair, three sessions, and one `bench.py` pair", '7.20'),
               "sensor_mount_jitter_time.json": ("`tools/raycast_time.py --model … --mount-jitter 0.01,5`, N = 4096: `lsim_sensor_mount_jitter` alone (all / no env fresh), `lsim_sensor_capture` on jittered against nominal mounts with the parent commit's nominal columns of the same call; `tools/vision_train_time.py --mount-jitter`; `bench.py` alternating with the parent's tree", '7.13'),
               "sensor_instrument_time.json": ("`tools/raycast_time.py --model … --instrument latency=0:1,noise_gain=0.5:2,depth_scale=0.02,depth_quad=0.005,fov=0.02`, N = 4096, camera and lidar on flat ground and stairs: `lsim_sensor_capture` against `lsim_sensor_capture_inst` on neutral and on drawn rows, `lsim_sensor_instrument` alone (all / no env fresh), the parent commit's `lsim_sensor_capture` of the same call; `tools/vision_train_time.py --instrument`; `bench.py` alternating with the parent's tree", '7.14'),
+              "sensor_shade_time.json": ("`tools/raycast_time.py --shade --parent-lib <the parent commit's liblsim.so>`, N = 4096, the 128 × 96 chase camera on flat ground and stairs, HIP events, five alternating repetitions, every env drawn and `env_stride = N`: `lsim_raycast_bodies` of this tree and of the parent's library on the same struct (`rays_us`, `rays_parent_us`), `lsim_sensor_shade` alone with and without shadows (`shade_us`, `shade_plain_us`), the pair as `update()` runs it; `bench_pairs`: `bench.py --gpus 1 --steps 200 --warmup 20` alternating with the parent's tree", '7.22'),
               "sensor_stereo_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --stereo default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_stereo` alone (`stereo_us`, `stereo_all_due_us`) next to the capture alone on the same ticks (`capture_us`, `capture_all_due_us`), `update()` without and with the option, the share of a whole capture's pixels the stage rewrites; `counts`: `stereo_counts()` of 64 envs on stairs over 30 steps; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.21'),
               "elevation_map_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_elevation_map` alone over the same ticks (1 env in 5 due) and with every env due, `update()` with both; `bench.py` alternating with the parent's tree", '7.15'),
               "elevation_fuse_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,fusion=default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_elevation_map_fused` (`map_us`, `map_all_due_us`) next to `lsim_elevation_map` of the same map on the same ticks (`plain_map_us`, `plain_map_all_due_us`), `update()` with the fused launch; `error_columns`: `evaluate`'s map columns for the plain and the fused map on 64 envs on stairs, same seeds; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.20'),

@@ -46,6 +46,13 @@ and alternating `--repeats` times, each with its median and range: `capture_us` 
 advancing; `map_rows_us` = lsim_map_rows alone over the map's scan; `map_rows_torch_us` = the torch statement of the same rows into the same
 buffer (two subtractions, clamp, product, and with two channels the copy of `known`: five elementwise launches, without the non-finite
 rule); `update_us` = update() as the sensor of a map policy runs it in a step: odometry, capture, map, rows.
+`--shade` (or `--shade sun=145:50,shadows=1,...`, sensors.parse_shading; a measurement of its own, written to
+profiles/sensor_shade_time.json unless --out names another file): the 128 x 96 chase camera of sensors.chase_camera, per terrain, in one
+process and alternating `--repeats` times, each with its median and range, once with every env drawn and once with env_stride = N (the
+viewer's case: env 0 alone, 50 times the iterations): `rays_us` = lsim_raycast_bodies alone, `shade_us` = lsim_sensor_shade alone on the rows the rays left,
+`shade_plain_us` = the same launch without LSIM_SHADE_SHADOWS, `update_us` = the pair as update() runs it; `shade_over_rays` their ratio;
+`lit_share` / `shadowed_share` = the share of the drawn pixels that face the sun lit and dark.  `--parent-lib PATH` (a liblsim.so built from
+the parent commit) also times that library's lsim_raycast_bodies on the same struct in the same loops: `rays_parent_us`.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -237,6 +244,55 @@ def measure_stereo(n, terrain, iters, warmup, model, stereo, repeats):
     return out
 
 
+def measure_shade(n, terrain, base_iters, warmup, shading, repeats, parent=None):
+    """the --shade measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    torch.cuda.synchronize()
+    shadows = abi.DEFINES["LSIM_SHADE_SHADOWS"]
+    out = {"num_envs": n, "terrain": terrain, "camera": "128x96 chase, hfov 60, frame yaw, far 8 m"}
+    for name, stride in (("all_envs", 1), ("one_env", n)):
+        cam = sensors.chase_camera(env, 128, 96, env_stride=stride, shading=shading)
+        iters = base_iters * (50 if stride > 1 else 1)        # one env is 1 / N of the work: the timed window stays a good fraction of a second
+        rays, shade = cam.stage("rays"), cam.stage("shade")
+        rows = {"rays_us": [], "shade_us": [], "shade_plain_us": [], "update_us": []}
+        if parent is not None:
+            rows["rays_parent_us"] = []
+            stream = env._stream()
+            old = lambda: lib.check(parent.lsim_raycast_bodies(ctypes.byref(cam.bodies_struct), stream), what="lsim_raycast_bodies (parent)")
+        cam.update()
+        for _ in range(repeats):
+            rows["rays_us"].append(timed(lambda: rays.launch(0, 0), iters, warmup))
+            if parent is not None:
+                rows["rays_parent_us"].append(timed(old, iters, warmup))
+            rows["shade_us"].append(timed(lambda: shade.launch(0, 0), iters, warmup))
+            shade.struct.shade_flags = 0
+            rows["shade_plain_us"].append(timed(lambda: shade.launch(0, 0), iters, warmup))
+            shade.struct.shade_flags = shadows if shading.shadows else 0
+            rows["update_us"].append(timed(cam.update, iters, warmup))
+        cam.update()
+        torch.cuda.synchronize()
+        surf, lab = cam.surface()[::stride], cam.labels()[::stride]
+        sun = torch.tensor(shading.sun_vector(), device=surf.device, dtype=torch.float32)
+        facing = (lab > 0) & ((surf[..., :3] * sun).sum(-1) > 0)
+        case = {"rays": cam.num_rays, "envs_drawn": int(lab.shape[0]), "lit_share": float(((surf[..., 3] > 0) & facing).float().mean()),
+                "shadowed_share": float(((surf[..., 3] == 0) & facing).float().mean()), "body_share": float((lab >= 2).float().mean()),
+                "nonfinite_rays": int(cam.nonfinite_rays.item()), "iters": iters}
+        for k, v in rows.items():
+            case[k], case[k + "_range"], case[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+        case["shade_over_rays"] = case["shade_us"] / case["rays_us"]
+        out[name] = case
+        del cam, rays, shade, surf, lab
+        torch.cuda.empty_cache()
+    return out
+
+
 def measure_map_policy(n, terrain, iters, warmup, model, emap, odometry, channels, repeats):
     """the --map --odometry / --map-rows measurement (module docstring)"""
     cfg = C.aliengo_cfg()
@@ -419,7 +475,10 @@ def main():
     ap.add_argument("--map-rows", type=int, default=None, choices=(1, 2), help="with --map, time lsim_map_rows with this many channels against its torch statement")
     ap.add_argument("--stereo", default=None, nargs="?", const="default", help="baseline=B,max_disparity=D,window=W,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q "
                     "(any subset; 'default'): time lsim_sensor_stereo next to the capture it follows (needs --model)")
-    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map / --stereo: alternating repetitions of every timed loop")
+    ap.add_argument("--shade", default=None, nargs="?", const="default", help="sun=AZ:EL,ambient=A,shadows=0|1,checker=M,... (any subset; 'default'): time "
+                    "lsim_sensor_shade next to the lsim_raycast_bodies it follows, on the 128 x 96 chase camera")
+    ap.add_argument("--parent-lib", default=None, help="with --shade: a liblsim.so of the parent commit, whose lsim_raycast_bodies is timed in the same loops")
+    ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map / --stereo / --shade: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -435,6 +494,18 @@ def main():
         if a.out:
             with open(a.out, "w") as f:
                 f.write(line + "\n")
+        print(line)
+        return
+    if a.shade is not None:
+        shading = sensors.parse_shading(a.shade)
+        # the parent's library has no lsim_sensor_shade: only the entry that is timed is bound
+        parent = None if a.parent_lib is None else abi.bind(ctypes.CDLL(os.path.abspath(a.parent_lib)), names=["lsim_raycast_bodies"])
+        res = {"tool": "raycast_time --shade", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "shading": shading.record(), "parent_lib": a.parent_lib is not None,
+               "cases": [measure_shade(a.num_envs, t, a.iters, a.warmup, shading, a.repeats, parent) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        with open(a.out or os.path.join(ROOT, "profiles", "sensor_shade_time.json"), "w") as f:
+            f.write(line + "\n")
         print(line)
         return
     if a.stereo is not None:

@@ -13,7 +13,10 @@ and `.pgm` (unknown black, then low = dark to high = white over the map's own ra
 `--stereo [baseline=0.05,edge_hole=0.25,...]` (sensors.parse_stereo): the robot carries that forward camera as a stereo pair
 (sensors.StereoArtifacts, see_robot and labels on), and `stereo_e<env>_s<step>.npy` / `.pgm` hold what it reports -- the newest frame with
 the occlusion shadows, the minimum range and the depth-edge artefacts, holes at the near end of the grey range -- next to the clean
-`front_e<env>_s<step>.npy` / `.pgm`."""
+`front_e<env>_s<step>.npy` / `.pgm`.
+`--shade [sun=145:50,ambient=0.35,shadows=1,checker=0.5,...]` (sensors.parse_shading): the chase camera is also shaded (sensors.Shading,
+lsim_sensor_shade: surface normals, sun shadows, a colour by label), and `rgb_e<env>_s<step>.ppm` (binary P6) and `.npy` (uint8 [H, W, 3])
+are written next to the depth and label frames."""
 import argparse
 import os
 import sys
@@ -30,6 +33,14 @@ def write_pgm(path, img8):
     with open(path, "wb") as f:
         f.write(b"P5\n%d %d\n255\n" % (img8.shape[1], img8.shape[0]))
         f.write(img8.tobytes())
+
+
+def write_ppm(path, rgb):
+    """binary PPM (P6) of a uint8 [H, W, 3] array"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+        f.write(rgb.tobytes())
 
 
 def depth_to_gray(depth, near, far):
@@ -71,6 +82,8 @@ def main():
     ap.add_argument("--map", default=None, nargs="?", const="source=clean", help="also write an elevation map: size=G,resolution=RES,source=noisy|clean")
     ap.add_argument("--stereo", default=None, nargs="?", const="default", help="also write the forward camera's frames with stereo artefacts: "
                     "baseline=B,max_disparity=D,window=W,edge_radius=N,edge_rel=E,edge_hole=P,edge_fatten=Q (any subset)")
+    ap.add_argument("--shade", default=None, nargs="?", const="default", help="also write the chase camera's shaded colour frames: "
+                    "sun=AZ:EL,ambient=A,shadows=0|1,checker=M,checker_gain=G,shadow_bias=B,shadow_far=F (any subset)")
     a = ap.parse_args()
     import torch
     from isaacgymloco_amd.envs import config as C, sensors
@@ -80,7 +93,8 @@ def main():
     cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if a.terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
     env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
     cam = env.add_sensor("chase", sensors.depth_camera(env, a.width, a.height, a.hfov, mount_pos=tuple(float(v) for v in a.mount.split(",")),
-                                                       pitch_deg=a.pitch, near=0.05, far=a.far, see_robot=True, labels=True, frame="yaw"))
+                                                       pitch_deg=a.pitch, near=0.05, far=a.far, see_robot=True, labels=True, frame="yaw",
+                                                       shading=None if a.shade is None else sensors.parse_shading(a.shade)))
     front = None
     if a.map:
         front = env.add_sensor("front", sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=a.far,
@@ -104,6 +118,7 @@ def main():
         env.step_device(actions)
         if step % a.every == 0 or step == a.steps:
             depth, labels = cam.image().cpu().numpy(), cam.label_image().cpu().numpy()
+            rgb = None if a.shade is None else cam.rgb_image().cpu().numpy()
             heights = None if front is None else front.map_heights().cpu().numpy()
             seen = None if pair is None else (pair.frame_images()[:, -1].cpu().numpy(), pair.image().cpu().numpy())
             for e in ids:
@@ -114,6 +129,9 @@ def main():
                 if heights is not None:
                     np.save(os.path.join(a.out, f"map_{stem}.npy"), heights[e])
                     write_pgm(os.path.join(a.out, f"map_{stem}.pgm"), map_to_gray(heights[e]))
+                if rgb is not None:
+                    np.save(os.path.join(a.out, f"rgb_{stem}.npy"), rgb[e])
+                    write_ppm(os.path.join(a.out, f"rgb_{stem}.ppm"), rgb[e])
                 np.save(os.path.join(a.out, f"depth_{stem}.npy"), depth[e])
                 np.save(os.path.join(a.out, f"labels_{stem}.npy"), labels[e])
                 write_pgm(os.path.join(a.out, f"depth_{stem}.pgm"), depth_to_gray(depth[e], cam.near, cam.far))
