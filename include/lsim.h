@@ -60,7 +60,9 @@ extern "C" {
                                     lsim_sensor_stereo + lsim_sensor_stereo_sizes + LSIM_RNG_SENSOR_STEREO (a stereo camera's occlusion shadows, minimum
                                     range and depth-edge artefacts, written into the frame history behind a capture);
                                     lsim_sensor_shade + lsim_sensor_shade_sizes (a shaded colour frame behind lsim_raycast_bodies: the surface normal at
-                                    every hit, whether the sun reaches it, a colour per pixel) */
+                                    every hit, whether the sun reaches it, a colour per pixel);
+                                    lsim_elevation_map_cleanup (cells of the elevation map that a capture's rays pass over, well below the height
+                                    the map holds, are forgotten: one launch between the capture and the map's) */
 
 /* ---- fixed sizes of the robot family on this path (12-DoF quadrupeds) ---- */
 #define LSIM_NUM_DOF 12
@@ -1683,7 +1685,8 @@ int lsim_map_rows(const lsim_map_rows_t* mr, void* stream);
  *   and an unknown point or a bad pose var_max.  No NaN is ever written.
  * Consequences.  band = 0 and gate2 = 0: zmax - 0.0f is zmax and the gate never opens, so height, stamp, cell, scan and known are
  *   lsim_elevation_map's bit for bit.  A cell the camera has left ages: its scan_var grows by var_growth per tick up to var_max.
- * NOT BUILT: variance growth per metre travelled, latency compensation of the pose, overhangs, clearing cells the camera looks through. */
+ * NOT BUILT: variance growth per metre travelled, latency compensation of the pose, overhangs.  (Clearing cells the camera looks through:
+ *   lsim_elevation_map_cleanup below, a launch of its own ahead of this one.) */
 typedef struct lsim_elevation_map_fused {
     lsim_elevation_map_t em;          /* everything lsim_elevation_map takes, with its meaning and its checks */
     float* var;                       /* [N,G,G] 4-byte aligned */
@@ -1716,6 +1719,69 @@ typedef struct lsim_map_rows_fused {
 /* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: mf == NULL; everything lsim_map_rows
  * refuses of mf->mr; var_ref not finite or <= 0; channels == 2 and scan_var NULL, not 4-byte aligned or var_stride < P. */
 int lsim_map_rows_fused(const lsim_map_rows_fused_t* mf, void* stream);
+
+/* ---- elevation map, visibility clean-up: a cell that the newest capture's rays pass over, well below the height the map holds for it, on
+ * their way to ground further away is FORGOTTEN (its stamp becomes -1).  The map launches only ever add; a maximum lifted by noise, a
+ * stereo-fattened depth edge or a stretch placed with a pose that has since drifted otherwise stays for the whole episode.  ONE launch
+ * under the rules of lsim_elevation_map, enqueued BETWEEN the capture and the map's launch of the same tick, with the same stream, tick and
+ * flags: the newest capture's rays are tested against the map of the EARLIER captures, and the map's launch then inserts the new points and
+ * writes scan / known from the cleaned map.  `em` is the map's own struct and means what it means there (plain or fused); its scan, known,
+ * pts and state are not touched, and neither are height, cell and var: only stamp and cleared are written.  All arithmetic in fp32 (a
+ * compiler may contract a product and a sum); the square roots and the quotient below are correctly rounded.
+ *
+ * Which envs.  Visited, fill and due are lsim_elevation_map's, on em's fields.
+ *     fill (a fresh env):  cleared[e] = 0 and nothing else -- the map's launch of this tick empties the env, so it is never cleaned.
+ *     due, not fill, pose finite (lsim_elevation_map's "bad pose" on root_states and assumed_mount):  the env is cleaned, as below.
+ *     otherwise (not visited; not due; a bad pose, which the map's launch counts and this one does not):  NOTHING is written.
+ *   So a launch with LSIM_SENSOR_FILL_ALL or LSIM_SENSOR_RESETS_ONLY writes nothing but those zeros.
+ * Stage.  One threshold and one int32 count (0) per slot s of the env, in LDS (2 * G * G * 4 bytes).  With (ix, iy) the one cell of the
+ *   window centred on the pose that lives in slot s:
+ *     the slot knows that cell (stamp >= 0 and cell == its packed word):
+ *         thr[s] = (height[e][s] - clear_margin) - clear_sigma * sqrt(var[e][s])          (the last term only when var != NULL)
+ *     otherwise (never written, forgotten, or a cell of an older window):   thr[s] = -infinity
+ *   A var that is negative or NaN makes thr NaN, and a NaN thr is never undercut: such a cell stays.
+ * Rays, behind a barrier.  Ray r with d and t as lsim_elevation_map forms them is USED when  |d| <= FLT_MAX,  t_lo < t < t_hi,  the label is
+ *   terrain where labels are given  -- that launch's range and label tests; its end point does NOT have to lie inside the window --  and
+ *   t > end_gap.  With P(t') = p + R(q) (mpos + R(mq) (dirs[r] * t')), the operations and their order those of lsim_elevation_map's P:
+ *     O = p + R(q) mpos   (the camera);      E = P(t - end_gap)   (one subtraction);      the ray is skipped when a component of O or E is not finite
+ *   In CELL units  o = O.xy * rinv,  e = E.xy * rinv  (skipped when a floor of the four is not inside (-32768, 32768)),  dxy = e - o,  and
+ *     dz = E.z - O.z,      L = sqrt((E.x - O.x)^2 + (E.y - O.y)^2)   (metres),      z(u) = O.z + u * dz,   u in [0, 1]
+ *   the segment's xy projection is walked cell by cell (Amanatides - Woo) from (ix, iy) = (floor o.x, floor o.y).  Per axis a, when
+ *   |d_a| >= 2^-20 cells:  the next boundary b_a = i_a + 1 (d_a > 0) or i_a (d_a < 0),  k_a = 1 / d_a,  u_a = ((float) b_a - o_a) * k_a, formed
+ *   anew from the integer boundary after every step (nothing accumulates); an axis that moves less never steps (u_a = +infinity).
+ *   At most 2 G + 2 cells are visited, the first included.  With u_in = 0 for the first cell:
+ *     u_out = min(u_x, u_y, 1)
+ *     the cell COUNTS when it lies inside the window (-G/2 <= i - c < G/2 on both axes, lsim_elevation_map's) and u_out > u_in:
+ *         hi = max(z(u_in), z(u_out));      rho = u_out * L;      count[slot] += 1   when   hi + clear_slope * rho < thr[slot]
+ *     (a 32-bit integer LDS atomic).  Cells outside the window are stepped over (and once the walk has been inside the window and left it,
+ *     it may stop: the window is convex and a segment does not come back).
+ *     the walk ends when u_out >= 1;  otherwise the axis with the smaller u steps (x on a tie: the cell entered and left at the same u does not
+ *     count), its u is formed anew, and u_in = u_out.
+ *   A segment visits a cell at most once and no two window cells share a slot, so a ray adds at most 1 to a slot.  The counts are integers:
+ *   they do not depend on ray order and two launches on the same inputs write the same bits (no floating-point atomic).
+ *   What the three margins are for:  clear_margin absorbs the sensor's noise;  clear_slope * rho the error of the pose's pitch and roll, which
+ *   grows with the distance from the camera;  clear_sigma * sqrt(var) what the fused map itself admits not to know.  hi is the HIGHER end of the
+ *   ray's passage through the cell, so a ray that dives into a riser inside the cell does not clear it, and end_gap keeps the ray's own last
+ *   cells -- where floor() may have put its point into the neighbour -- out of the test.  A true surface under a clean capture and the true
+ *   pose is never forgotten when clear_margin exceeds the height a ray gains across one cell of its own end: sqrt(2) * res * (terrain slope).
+ * Sweep, behind a barrier.  A slot with count >= min_rays:  stamp[e][s] = -1;  cleared[e] += the number of such slots (int32, since fill).
+ *   height, cell and var keep their bits; a forgotten slot reads unknown and is simply overwritten by its next measurement (the fused map
+ *   starts such a cell anew: "the slot knows this cell" is false).
+ * NOT BUILT: misses and dropped pixels as free-space rays, overhangs, other envs' robots, lowering a cell instead of forgetting it. */
+typedef struct lsim_elevation_map_cleanup {
+    lsim_elevation_map_t em;          /* the map's own struct: same meaning, same checks (scan, known, pts and state are not touched) */
+    const float* var;                 /* [N,G,G] the fused map's variance, 4-byte aligned, or NULL (plain map) */
+    int32_t* cleared;                 /* [N] cells forgotten since the env's episode began; 4-byte aligned */
+    float clear_margin;               /* metres: finite, >= 0 */
+    float clear_slope;                /* metres per metre of horizontal distance from the camera: finite, >= 0 */
+    float clear_sigma;                /* standard deviations of the cell's own variance: finite, >= 0 */
+    float end_gap;                    /* metres cut off the ray's end: finite, >= 0 */
+    int32_t min_rays;                 /* >= 1: rays that must pass below the threshold */
+} lsim_elevation_map_cleanup_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: ec == NULL; everything
+ * lsim_elevation_map refuses of ec->em; cleared NULL or not 4-byte aligned; var given and not 4-byte aligned; clear_margin, clear_slope,
+ * clear_sigma or end_gap negative or not finite; min_rays < 1. */
+int lsim_elevation_map_cleanup(const lsim_elevation_map_cleanup_t* ec, void* stream);
 
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no

@@ -71,6 +71,9 @@ Map fusion (`ElevationMap(..., fusion=MapFusion())`, lsim_elevation_map_fused in
 capture's points near its top instead of their biased maximum, the captures are fused by a variance the map keeps per cell, and cells the
 camera has left age; `cam.map_variance()` is the live [N, P] variance of map_scan(), `attach_map_rows(("height", "confidence"))`
 (lsim_map_rows_fused) the actor's rows with var_ref / (var_ref + variance) as the second block.  Without `fusion` nothing of this exists.
+Map clean-up (`ElevationMap(..., cleanup=MapCleanup())`, lsim_elevation_map_cleanup between the capture and the map's launch): a cell the
+newest capture's rays pass over, well below the height the map holds, is forgotten; `map_cleared()` counts them per env and episode.
+Without `cleanup` nothing of this exists.
 
 Odometry (`cam.attach_map(m, odometry=OdometryError(scale=0.02, yaw_per_m=0.01, z_per_m=0.01, noise=(0.005, 0.002, 0.002)))`,
 lsim_odometry_step): a robot does not know where it is, it integrates its steps -- so the map is placed with an ESTIMATED pose that drifts
@@ -396,6 +399,39 @@ def parse_map_fusion(text):
     return parse_option(MapFusion, ",".join(item.replace(":", "=", 1) for item in text.split("/")))
 
 
+class MapCleanup(_Option):
+    """The visibility clean-up of an ElevationMap (lsim_elevation_map_cleanup, one launch between the capture and the map's; include/lsim.h
+    states every formula): a cell that at least `min_rays` rays of the newest capture pass over, on their way to ground further away, more
+    than `margin` metres below the height the map holds for it is forgotten -- a maximum lifted by noise, a stereo-fattened depth edge or a
+    stretch placed with a pose that has since drifted does not stay for the whole episode.  `slope`: metres of allowance per metre of
+    horizontal distance from the camera (the pose's pitch and roll error grows with it); `sigma`: standard deviations of a fused map's own
+    variance that protect a cell (ignored by a plain map); `end_gap` (metres, None: 1.5 times the map's resolution): how much of a ray's
+    end is left out, so that a ray never clears the cells around its own point.
+    The defaults are STATED GUESSES, fitted to nothing: 0.05 m is about 2.5 sigma of the default noise at 1.5 m and exceeds what a ray
+    gains across one cell of stairs-steep ground (sqrt(2) * resolution * slope)."""
+    FIELDS = ("margin", "slope", "sigma", "min_rays", "end_gap")
+    TEXT = {"margin": float, "slope": float, "sigma": float, "min_rays": int, "end_gap": _or_none(float)}
+
+    def __init__(self, margin=0.05, slope=0.05, sigma=3.0, min_rays=2, end_gap=None):
+        self.margin, self.slope, self.sigma, self.min_rays = float(margin), float(slope), float(sigma), int(min_rays)
+        self.end_gap = None if end_gap is None else float(end_gap)
+        values = (self.margin, self.slope, self.sigma) + (() if self.end_gap is None else (self.end_gap,))
+        if any(not math.isfinite(v) or v < 0.0 for v in values) or self.min_rays < 1:
+            raise ValueError(f"MapCleanup: margin, slope, sigma and end_gap are finite and >= 0 and min_rays >= 1, got {values}, {min_rays}")
+
+    def resolve(self, resolution):
+        """the by-value fields of lsim_elevation_map_cleanup_t, in its order: (clear_margin, clear_slope, clear_sigma, end_gap, min_rays)"""
+        return (self.margin, self.slope, self.sigma, 1.5 * resolution if self.end_gap is None else self.end_gap, self.min_rays)
+
+
+def parse_map_cleanup(text):
+    """MapCleanup of 'margin:0.05/min_rays:2' (any subset of its fields, key:value joined by '/'; '1', '' or 'default': the defaults): the
+    form a clean-up takes INSIDE the text of an elevation map, as a fusion does"""
+    if text in ("1", "", "default"):
+        return MapCleanup()
+    return parse_option(MapCleanup, ",".join(item.replace(":", "=", 1) for item in text.split("/")))
+
+
 class ElevationMap(_Option):
     """A robot-centred height grid per env, fused on the device from a sensor's captures (lsim_elevation_map; include/lsim.h states every
     formula).  `size`: cells per side, 16, 32 or 64; `resolution`: metres per cell (a power of two keeps the cell of a coordinate exact);
@@ -412,14 +448,20 @@ class ElevationMap(_Option):
     model whose dropped pixels cannot be told from a range (dropout > 0 with drop_value strictly inside the clip range).
     `fusion` (a MapFusion, or its record): the launch is lsim_elevation_map_fused -- a cell is the mean of a capture's points near its
     top, fused over the captures by a variance the map keeps per cell; None: the plain map, and nothing of that exists.  The record
-    carries the key "fusion" only when one is set."""
+    carries the key "fusion" only when one is set.
+    `cleanup` (a MapCleanup, or its record): lsim_elevation_map_cleanup runs between every capture and the map's launch and forgets the
+    cells the camera sees through; None: nothing of that is allocated or launched.  The record carries the key "cleanup" only when one is set."""
     FIELDS = ("size", "resolution", "source", "max_range", "points", "unknown_drop")
-    TEXT = {"size": int, "resolution": float, "source": str, "max_range": float, "unknown_drop": float, "fusion": parse_map_fusion}
+    TEXT = {"size": int, "resolution": float, "source": str, "max_range": float, "unknown_drop": float, "fusion": parse_map_fusion,
+            "cleanup": parse_map_cleanup}
 
-    def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None, fusion=None):
+    def __init__(self, size=32, resolution=0.0625, source="noisy", max_range=None, points=None, unknown_drop=None, fusion=None, cleanup=None):
         self.fusion = MapFusion(**fusion) if isinstance(fusion, dict) else fusion
         if self.fusion is not None and not isinstance(self.fusion, MapFusion):
             raise TypeError(f"ElevationMap: fusion is a MapFusion, its record or None, got {type(fusion).__name__}")
+        self.cleanup = MapCleanup(**cleanup) if isinstance(cleanup, dict) else cleanup
+        if self.cleanup is not None and not isinstance(self.cleanup, MapCleanup):
+            raise TypeError(f"ElevationMap: cleanup is a MapCleanup, its record or None, got {type(cleanup).__name__}")
         self.size, self.resolution, self.source = int(size), float(resolution), str(source)
         self.max_range = None if max_range is None else float(max_range)
         self.unknown_drop = None if unknown_drop is None else float(unknown_drop)
@@ -439,13 +481,16 @@ class ElevationMap(_Option):
         out = super().record()
         if self.fusion is not None:
             out["fusion"] = self.fusion.record()
+        if self.cleanup is not None:
+            out["cleanup"] = self.cleanup.record()
         return out
 
     def _shown(self, k):
         return repr(getattr(self, k) if k != "points" or self.points is None else len(self.points))     # the number of points, not the points
 
     def __repr__(self):
-        return super().__repr__() if self.fusion is None else f"{super().__repr__()[:-1]}, fusion={self.fusion!r})"
+        extra = "".join(f", {k}={v!r}" for k, v in (("fusion", self.fusion), ("cleanup", self.cleanup)) if v is not None)
+        return f"{super().__repr__()[:-1]}{extra})"
 
 
 class OdometryError(_Option):
@@ -481,12 +526,14 @@ def parse_elevation_map(text):
 
 _ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "map_rows", "encoder", "memory")      # a chain's launch order
 # launched directly behind the stage named, in this order: the stereo artefacts rewrite what the capture wrote before anybody reads it
-# (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument; the shading reads what the rays just wrote
-_BEHIND = {"shade": "rays", "stereo": "capture", "frames_log": "capture"}
+# (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument; the shading reads what the rays just wrote;
+# the map's clean-up tests the capture as the artefacts left it against the map of the earlier captures, ahead of the map's own launch
+_BEHIND = {"shade": "rays", "stereo": "capture", "frames_log": "capture", "map_cleanup": "capture"}
 _LAUNCH_ORDER = tuple(n for o in _ORDER for n in (o,) + tuple(k for k, v in _BEHIND.items() if v == o))
-_DEPENDENTS = {"map": ("odometry", "map_rows"), "encoder": ("memory", "frames_log")}                                # who goes with whom
+_DEPENDENTS = {"map": ("odometry", "map_rows", "map_cleanup"), "encoder": ("memory", "frames_log")}                                # who goes with whom
 _ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
-           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "shade": "shading (shading=Shading(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "encoder": "encoder (attach_encoder)",
+           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "shade": "shading (shading=Shading(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)",
+           "map_cleanup": "map clean-up (ElevationMap(cleanup=MapCleanup(...)))", "encoder": "encoder (attach_encoder)",
            "memory": "memory (attach_memory)", "frames_log": "frame log (attach_frames_log)"}
 _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
 
@@ -559,7 +606,7 @@ class RaySensor:
     `label_rows`: the padded tensors `out` / `labels()` are views of; `history()`: the raw frame history."""
 
     mount_jitter, instrument, map, odometry, map_channels = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "map_rows"))
-    encoder, memory, stereo, shading = _option("encoder"), _option("memory"), _option("stereo"), _option("shade")
+    encoder, memory, stereo, shading, map_cleanup = _option("encoder"), _option("memory"), _option("stereo"), _option("shade"), _option("map_cleanup")
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
                  see_robot=False, ignore_bodies=(), labels=False, frame="base", model=None, mount_jitter=None, instrument=None, kind=None, stereo=None, shading=None):
@@ -1026,6 +1073,8 @@ class RaySensor:
             raise ValueError("attach_map needs a model (SensorModel): the tick, the period and the episode lengths that say who captured are the model's")
         entry = "lsim_elevation_map" if m.fusion is None else "lsim_elevation_map_fused"
         lib.entry(self._api, entry, "the elevation map")
+        if m.cleanup is not None:
+            lib.entry(self._api, "lsim_elevation_map_cleanup", "the map's clean-up")
         if self.frame != "base":
             raise ValueError(f"attach_map: the sensor's frame is {self.frame!r}; lsim_elevation_map places the points with the base's full orientation, "
                              "so only a frame='base' sensor can feed a map")
@@ -1097,7 +1146,15 @@ class RaySensor:
             od.scale_range, od.yaw_range, od.z_range, od.pos_noise, od.yaw_noise, od.z_noise = odometry.ranges()
             em.root_states = od.est
             launches.append(self._attach(Stage(self, "odometry", "lsim_odometry_step", od, held, odometry)))
-        launches.append(self._attach(Stage(self, "map", entry, em, mp, m, outer=ef)))
+        stage = self._attach(Stage(self, "map", entry, em, mp, m, outer=ef))
+        if m.cleanup is not None:           # ahead of the map's launch: the same struct, and the fused map's variance when there is one
+            ec = abi.LsimElevationMapCleanup()
+            ctypes.memmove(ctypes.addressof(ec.em), ctypes.addressof(em), ctypes.sizeof(em))
+            held = {"cleared": self._zeros(N, dtype=torch.int32)}
+            ec.cleared, ec.var = held["cleared"].data_ptr(), mp["var"].data_ptr() if "var" in mp else None
+            ec.clear_margin, ec.clear_slope, ec.clear_sigma, ec.end_gap, ec.min_rays = m.cleanup.resolve(m.resolution)
+            launches.append(self._attach(Stage(self, "map_cleanup", "lsim_elevation_map_cleanup", ec.em, held, m.cleanup, outer=ec)))
+        launches.append(stage)
         if self.tick >= 0:
             for s in launches:
                 s.launch(self.tick, _FILL_ALL)
@@ -1164,6 +1221,10 @@ class RaySensor:
     def map_known(self):
         """live uint8 [N, P] tensor: 1 where map_scan() is a height the map holds"""
         return self._need("map").buffers["known"]
+
+    def map_cleared(self):
+        """live int32 [N] tensor: the cells the clean-up has forgotten since each env's episode began (ElevationMap(cleanup=...))"""
+        return self._need("map_cleanup").buffers["cleared"]
 
     def map_state(self):
         """the live raw arrays (height f32, stamp i32, cell: the u32 words held in an int32 tensor, and with a fusion var f32), each

@@ -485,6 +485,7 @@ def parse_camera_stereo(text):
 VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 MAP_METRICS = ("map_scan_error", "map_coverage")        # accepted when named and the sensor carries an elevation map; never a default
 MAP_FUSION_METRICS = ("map_variance", "map_z2")         # likewise, of a map with a fusion (envs.sensors.MapFusion); dropped without one
+MAP_CLEANUP_METRICS = ("map_cleared",)                  # likewise, of a map with a clean-up (envs.sensors.MapCleanup); dropped without one
 
 
 def _map_fusion_columns(env, cam):
@@ -504,6 +505,22 @@ def _map_fusion_columns(env, cam):
             return over_known(err.square() / cam.map_variance().clamp(min=1e-12))
         out["map_z2"] = z2
     return out
+
+
+def _map_cleanup_columns(env, cam):
+    """{name: fn} of MAP_CLEANUP_METRICS for a sensor whose map has a clean-up, else {}.  "map_cleared": the cells the clean-up forgot
+    in this step, per env -- the growth of cam.map_cleared() since the step before (the counter starts again when an env's episode does:
+    its value then is what was forgotten since)"""
+    if getattr(getattr(cam, "map", None), "cleanup", None) is None:
+        return {}
+    last = [cam.map_cleared().clone()]
+
+    def cleared(a, a0, live, priv):
+        now = cam.map_cleared().clone()
+        grown = torch.where(now >= last[0], now - last[0], now).to(torch.float32)
+        last[0] = now
+        return grown
+    return {"map_cleared": cleared}
 
 
 class FrameWriter:
@@ -634,9 +651,9 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
     from .vision import PackedVisionPolicy
     metrics = list(metrics)
     for m in metrics:
-        if m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS:
+        if m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS:
             raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error', "
-                             f"with an elevation map also 'map_scan_error' and 'map_coverage', with a fused one also 'map_variance' and 'map_z2')")
+                             f"with an elevation map also 'map_scan_error' and 'map_coverage', with a fused one also 'map_variance' and 'map_z2', with a clean-up also 'map_cleared')")
     has_map = getattr(cam, "map", None) is not None
     scan = _scan_block(env)
     needs = {"map_coverage": has_map, "map_scan_error": has_map and scan is not None and cam.map_scan().shape[1] == scan[1],
@@ -651,6 +668,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
         "map_scan_error": lambda a, a0, live, priv: ((cam.map_pose()[:, 2:3] - 0.5 - cam.map_scan()).clamp(-1.0, 1.0) * float(env.lcfg.obs_scale_height) - target(priv)).square().mean(dim=1),
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
+    columns.update(_map_cleanup_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.latent if memory is None else cam.memory_rows, blind,
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
 
@@ -667,6 +685,7 @@ def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics, frames=No
         "map_scan_error": lambda a, a0, live, priv: (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1),
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
+    columns.update(_map_cleanup_columns(env, cam))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.map_rows, blind,
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
 
@@ -837,9 +856,9 @@ def parse_args(argv=None):
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
     a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
-    if any(m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS for m in a.vision_metrics):
+    if any(m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS for m in a.vision_metrics):
         ap.error(f"--vision-metrics: 'depth_influence', 'scan_error', 'memory_scan_error', 'map_scan_error' and / or 'map_coverage', got {a.vision_metrics}"
-                 " (a map with a fusion also has 'map_variance' and 'map_z2')")
+                 " (a map with a fusion also has 'map_variance' and 'map_z2', one with a clean-up 'map_cleared')")
     try:
         group_mask(a.group_by)
     except ValueError as exc:

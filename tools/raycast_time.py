@@ -34,6 +34,9 @@ ticks, reading the rows the captures left; `map_all_due_us` = the same launch wi
 `update_with_map_us` = update() as a sensor with a map runs it in a step: the capture and the map's launch behind it.
 `--map ...,fusion=default` (or `fusion=band:0.1/gate:3`, sensors.parse_map_fusion): the map's launch is lsim_elevation_map_fused, and
 `plain_map_us` / `plain_map_all_due_us` time lsim_elevation_map of the same map on the same ticks, in the same repetition.
+`--map ...,cleanup=default` (or `cleanup=margin:0.05/min_rays:2`, sensors.parse_map_cleanup): `cleanup_us` = lsim_elevation_map_cleanup alone
+over the same ticks, `cleanup_all_due_us` = the same with period 1 (every env due; LSIM_SENSOR_FILL_ALL would only zero its counters),
+`update_without_cleanup_us` = update() of a second camera whose map lacks the option; `update_with_map_us` then includes the clean-up.
 `--model ... --stereo default` (or `--stereo baseline=0.05,edge_hole=0.25,...`, sensors.parse_stereo; a measurement of its own, written to
 profiles/sensor_stereo_time.json unless --out names another file): per terrain, in one process and alternating `--repeats` times, each
 with its median and range: `capture_us` / `capture_all_due_us` = the capture alone over whole periods and with LSIM_SENSOR_FILL_ALL;
@@ -175,7 +178,7 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     cam.refresh(tick=0)
     plain = None
     if emap.fusion is not None:                  # ...,fusion=...: lsim_elevation_map of the same map is timed next to the fused launch, on the same ticks
-        cam.attach_map(sensors.ElevationMap(**{k: v for k, v in emap.record().items() if k != "fusion"}))
+        cam.attach_map(sensors.ElevationMap(**{k: v for k, v in emap.record().items() if k not in ("fusion", "cleanup")}))
         plain = cam.stage("map")                 # a Stage owns its struct and its tensors (Stage.buffers): held here, they outlive its place in the chain
     cam.attach_map(emap)
     if plain is not None:
@@ -187,7 +190,24 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     rows = {"capture_us": [], "map_us": [], "map_all_due_us": [], "update_with_map_us": []}
     if plain is not None:
         rows.update(plain_map_us=[], plain_map_all_due_us=[])
+    clean = cam.stage("map_cleanup")             # ...,cleanup=...: the clean-up's launch alone, next to the map's on the same ticks
+    if clean is not None:
+        rows.update(cleanup_us=[], cleanup_all_due_us=[], update_without_cleanup_us=[])
+        bare = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
+        bare.refresh(tick=0)
+        bare.attach_map(sensors.ElevationMap(**{k: v for k, v in emap.record().items() if k != "cleanup"}))
+
+    def every_env(stage):
+        """the clean-up with period 1: every env due and none fresh (LSIM_SENSOR_FILL_ALL would only zero its counters)"""
+        period, stage.struct.period = stage.struct.period, 1
+        t = timed_ticks(stage, whole, warmup)
+        stage.struct.period = period
+        return t
     for _ in range(repeats):
+        if clean is not None:
+            rows["cleanup_us"].append(timed_ticks(clean, whole, warmup))
+            rows["cleanup_all_due_us"].append(every_env(clean))
+            rows["update_without_cleanup_us"].append(timed_ticks(bare, whole, warmup))
         if plain is not None:
             rows["plain_map_us"].append(timed_ticks(plain, whole, warmup))
             rows["plain_map_all_due_us"].append(timed_ticks(plain, whole, warmup, fill_all))
@@ -200,6 +220,8 @@ def measure_map(n, terrain, iters, warmup, model, emap, repeats):
     for k, v in rows.items():
         out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
     out["map_over_capture"] = out["map_us"] / out["capture_us"]
+    if clean is not None:
+        out["cleanup_over_map"], out["cells_forgotten"] = out["cleanup_us"] / out["map_us"], int(cam.map_cleared().sum().item())
     out["nonfinite"] = int(cam.nonfinite_rays.item()) + int(cam.map_nonfinite.item())
     return out
 
