@@ -27,8 +27,9 @@ import torch.nn as nn
 
 from .. import abi, lib
 from . import fused_linear as FL
+from . import policy_io
 from .scan_policy import ScanOnPolicyRunner
-from .vision import PackedVisionPolicy, VisionActorCritic, VisionOnPolicyRunner, VisionPPO, height_scan_block
+from .vision import PackedVisionPolicy, VisionOnPolicyRunner, VisionPPO, height_scan_block
 
 
 class _DistillLossFn(torch.autograd.Function):
@@ -182,17 +183,19 @@ class VisionDistill(VisionPPO):
 
 
 def _teacher_checkpoint(teacher, device):
-    """(model state dict, "scan_policy" record) of `teacher`: a checkpoint path, a loaded checkpoint dict, or a ScanOnPolicyRunner"""
+    """(model state dict, the scan policy's record) of `teacher`: a checkpoint path, a loaded checkpoint dict, or a ScanOnPolicyRunner.
+    The module itself is built behind DistillRunner's own checks of the widths against the env."""
     if isinstance(teacher, ScanOnPolicyRunner):
-        teacher.get_inference_policy()
-        return {k: v.detach().clone() for k, v in teacher.alg.actor_critic.state_dict().items()}, teacher.scan_record()
+        parts = policy_io.policy_parts(None, teacher)
+        return {k: v.detach().clone() for k, v in parts.actor_critic.state_dict().items()}, parts.scan
     if isinstance(teacher, str):
         teacher = torch.load(teacher, map_location=device, weights_only=False)
     if not isinstance(teacher, dict) or "model_state_dict" not in teacher:
         raise TypeError("DistillRunner: teacher is a checkpoint path, a loaded checkpoint dict or a ScanOnPolicyRunner")
-    if "scan_policy" not in teacher:
+    kind, record = policy_io.policy_record(teacher)
+    if kind != "scan":
         raise ValueError("DistillRunner: the teacher's checkpoint has no 'scan_policy' record (it is no ScanOnPolicyRunner's)")
-    return teacher["model_state_dict"], dict(teacher["scan_policy"])
+    return teacher["model_state_dict"], dict(record)
 
 
 class DistillRunner(VisionOnPolicyRunner):
@@ -215,19 +218,14 @@ class DistillRunner(VisionOnPolicyRunner):
         if (int(record["offset"]), int(record["width"])) != (off, width) or int(record["dim"]) != width:
             raise ValueError(f"DistillRunner: the teacher read the scan block {record}, the env's is offset {off}, width {width}")
         num_critic_obs = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
-        hidden = lambda prefix: [sd[k].shape[0] for k in sorted((k for k in sd if k.startswith(prefix) and k.endswith(".weight")), key=lambda k: int(k.split(".")[-2]))]
-        actor, critic = hidden("actor."), hidden("critic.")
+        actor = policy_io.layer_widths(sd)[0]
         want = {"estimator.encoder.0.weight": env.num_obs, "critic.0.weight": num_critic_obs, "actor.0.weight": env.num_one_step_obs + 3 + 16 + width}
         for key, cols in want.items():
             if sd[key].shape[1] != cols:
                 raise ValueError(f"DistillRunner: the teacher's {key} reads {sd[key].shape[1]} columns, the env gives {cols}")
         if actor[-1] != env.num_actions:
             raise ValueError(f"DistillRunner: the teacher has {actor[-1]} actions, the env {env.num_actions}")
-        policy_cfg = train_cfg["policy"]
-        teacher_ac = VisionActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, depth_latent_dim=width,
-                                       actor_hidden_dims=tuple(actor[:-1]), critic_hidden_dims=tuple(critic[:-1]),
-                                       activation=policy_cfg.get("activation", "elu"))
-        teacher_ac.load_state_dict(sd)
+        teacher_ac = policy_io.actor_critic_from_state_dict(env, sd, rows=True, activation=train_cfg["policy"].get("activation", "elu"))
         super().__init__(env, train_cfg, sensor=sensor, encoder=encoder, log_dir=log_dir, device=device, fast=fast, memory=None, end_to_end=True)
         dtype = next(self.alg.actor_critic.parameters()).dtype
         self.alg.actor_critic.load_scan_teacher_state_dict(sd, width)
@@ -235,11 +233,9 @@ class DistillRunner(VisionOnPolicyRunner):
         self.teacher_record = {"offset": off, "width": width, "dim": width}
 
     def _extra_checkpoint_state(self):
-        out = super()._extra_checkpoint_state()
         alg = self.alg
-        out["distill"] = {"teacher": dict(self.teacher_record), "epochs": alg.distill_epochs, "learning_rate": alg.distill_learning_rate,
-                          "distill_optimizer_state_dict": alg.distill_optimizer.state_dict()}
-        return out
+        return {**super()._extra_checkpoint_state(), "distill": {"teacher": dict(self.teacher_record), "epochs": alg.distill_epochs,
+                "learning_rate": alg.distill_learning_rate, "distill_optimizer_state_dict": alg.distill_optimizer.state_dict()}}
 
     def _load_extra_checkpoint_state(self, d):
         super()._load_extra_checkpoint_state(d)

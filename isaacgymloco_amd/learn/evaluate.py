@@ -23,6 +23,7 @@ import torch
 from .. import abi, lib
 from ..envs import config as C
 from ..envs import sensors
+from .policy_io import policy_parts, policy_record
 
 GROUP_BITS = {"robot": abi.DEFINES["LSIM_EVAL_BY_ROBOT"], "type": abi.DEFINES["LSIM_EVAL_BY_TYPE"], "level": abi.DEFINES["LSIM_EVAL_BY_LEVEL"]}
 TRACE_DIM = abi.DEFINES["LSIM_EVAL_TRACE_DIM"]
@@ -275,130 +276,41 @@ class Evaluator:
         return out
 
 
-def check_conventions(saved, live):
-    """refuse a checkpoint made under other simulator conventions or another robot mix, naming the first differing key"""
-    if saved is None:
-        return
-    for k in ("robots", "lin_vel_at_com", "tgs_limit_passes", "solver_type", "num_position_iterations"):
-        if saved.get(k) != live.get(k):
-            raise ValueError(f"checkpoint conventions differ from the env's in {k!r}: saved {saved.get(k)!r}, live {live.get(k)!r}")
-
-
-def _actor_critic(env, policy, device, vision=None):
-    """HIMActorCritic (or VisionActorCritic) from a module, a runner, or a checkpoint path written by runner.save.  `vision`: a dict that
-    receives what a vision policy brings along -- "sensor", "encoder", "depth_head" from a VisionOnPolicyRunner; from a checkpoint its
-    "checkpoint" (the loaded dict), for _vision_parts to build encoder and head from; "map_policy" (the record, from a MapOnPolicyRunner
-    or its checkpoint) marks a map policy, whose rows _map_parts finds"""
-    from .modules import HIMActorCritic
-    vision = vision if vision is not None else {}
-    if isinstance(policy, HIMActorCritic):     # VisionActorCritic is one
-        return policy
-    if hasattr(policy, "alg"):                 # a runner
-        policy.get_inference_policy()          # flushes a deferred rollout store, eval mode
-        if getattr(policy.alg, "encoder", None) is not None:
-            vision.update(sensor=getattr(policy, "sensor", None), encoder=policy.alg.encoder, depth_head=policy.alg.depth_head)
-            if getattr(policy.alg, "memory", None) is not None:
-                vision.update(memory=policy.alg.memory, memory_head=policy.alg.memory_head)
-        if getattr(policy, "map_policy", False):      # a MapOnPolicyRunner: the actor reads its sensor's map rows
-            vision.update(sensor=getattr(policy, "sensor", None), map_policy={"channels": list(policy.channels)})
-        if getattr(policy, "scan_policy", False):     # a ScanOnPolicyRunner: the actor reads the scan block of the privileged observation
-            vision["scan_policy"] = policy.scan_record()
-        return policy.alg.actor_critic
-    if isinstance(policy, str):
-        d = torch.load(policy, map_location=device, weights_only=False)
-        check_conventions((d.get("env_state_dict") or {}).get("conventions"), env._conventions())
-        sd = d["model_state_dict"]
-        hidden = lambda prefix: [sd[k].shape[0] for k in sorted((k for k in sd if k.startswith(prefix) and k.endswith(".weight")), key=lambda k: int(k.split(".")[-2]))]
-        actor, critic, enc = hidden("actor."), hidden("critic."), hidden("estimator.encoder.")
-        num_critic_obs = env.num_privileged_obs if env.num_privileged_obs is not None else env.num_obs
-        ac = HIMActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, actor_hidden_dims=tuple(actor[:-1]),
-                            critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
-        if enc != [l.out_features for l in ac.estimator.encoder if isinstance(l, torch.nn.Linear)]:
-            raise ValueError(f"checkpoint estimator encoder widths {enc} differ from the default HIMEstimator's: pass the HIMActorCritic itself")
-        extra = sd["actor.0.weight"].shape[1] - ac.actor[0].in_features
-        if extra > 0 and ("depth_encoder_state_dict" in d or "map_policy" in d or "scan_policy" in d):       # a vision, map or scan policy: the extra columns come last (learn/vision.py)
-            from .vision import VisionActorCritic
-            ac = VisionActorCritic(env.num_obs, num_critic_obs, env.num_one_step_obs, env.num_actions, depth_latent_dim=extra,
-                                   actor_hidden_dims=tuple(actor[:-1]), critic_hidden_dims=tuple(critic[:-1]), init_noise_std=1.0).to(device)
-            vision["checkpoint"] = d
-            if "map_policy" in d:
-                vision["map_policy"] = d["map_policy"]
-            if "scan_policy" in d:
-                vision["scan_policy"] = d["scan_policy"]
-        ac.load_state_dict(sd)
-        ac.eval()
-        return ac
-    raise TypeError(f"policy must be a HIMActorCritic, a runner or a checkpoint path, got {type(policy).__name__}")
-
-
-def _vision_parts(env, ac, found, sensor, encoder, depth_head, device):
-    """(sensor, encoder, depth head or None) of a vision policy: the caller's keywords first, then what the runner or the checkpoint
-    brought (`found`, from _actor_critic).  The encoder ends up attached to the sensor (every capture is followed by its launch)."""
-    from .depth_encoder import DepthEncoder
-    cam = sensor if sensor is not None else found.get("sensor")
-    if cam is None:
-        cam = getattr(env, "sensors", {}).get("depth")
+def _policy_sensor(env, parts, device):
+    """The sensor a vision or a map policy's rows come from -- the caller's, else the runner's (both in parts.sensor), else
+    env.sensors["depth"], else, for a map policy's checkpoint, rebuilt with map and odometry from its record and added to the env as
+    "depth" -- with what feeds the actor attached: the map rows, or the encoder and the memory (every capture is followed by their
+    launches; the modules of `parts` end up on `device` in eval mode)."""
+    ac, cam = parts.actor_critic, parts.sensor if parts.sensor is not None else getattr(env, "sensors", {}).get("depth")
+    if parts.kind == "map":
+        if cam is None and parts.sensor_record is not None:
+            cam = env.add_sensor("depth", sensors.from_spec(env, parts.sensor_record))
+        if cam is None or getattr(cam, "map", None) is None:
+            raise ValueError("evaluate: a map policy needs a sensor with an elevation map (sensor=..., env.add_sensor('depth', ...), or a checkpoint "
+                             "whose 'map_policy' record names one)")
+        channels = tuple(parts.channels or getattr(cam, "map_channels", None) or ("height",))
+        if getattr(cam, "map_channels", None) != channels:
+            cam.attach_map_rows(channels)
+        if cam.map_rows().shape[1] != ac.depth_latent_dim:
+            raise ValueError(f"evaluate: the map rows have {cam.map_rows().shape[1]} columns, the actor reads {ac.depth_latent_dim}")
+        return cam
     if cam is None or getattr(cam, "model", None) is None:
         raise ValueError("evaluate: a vision policy needs a sensor with a SensorModel (sensor=..., or env.add_sensor('depth', ...))")
-    enc = encoder if encoder is not None else found.get("encoder")
-    head = depth_head if depth_head is not None else found.get("depth_head")
-    d = found.get("checkpoint")
-    if d is not None:
-        if enc is None:
-            record = (d.get("vision") or {}).get("encoder")
-            if record is None:
-                raise ValueError("evaluate: the checkpoint has no 'vision' record (vision['encoder'], the depth encoder's hyperparameters): "
-                                 "pass encoder=DepthEncoder(...) with the shapes it was trained with")
-            enc = DepthEncoder(**record)
-        enc.load_state_dict(d["depth_encoder_state_dict"])
-        if head is None and "depth_head_state_dict" in d:
-            w = d["depth_head_state_dict"]["weight"]
-            head = torch.nn.Linear(w.shape[1], w.shape[0])
-            head.load_state_dict(d["depth_head_state_dict"])
+    enc, mem = parts.encoder, parts.memory
     if enc is None:
-        raise ValueError("evaluate: a VisionActorCritic needs its depth encoder (encoder=...): nobody else can hand it a latent")
-    mem, mem_head = found.get("memory"), found.get("memory_head")
-    record = ((d.get("vision") or {}).get("memory")) if d is not None else None
-    if mem is None and record is not None:      # a checkpoint of a policy trained with a depth memory: rebuilt from its record
-        from .depth_memory import DepthMemory
-        mem = DepthMemory(**record)
-        mem.load_state_dict(d["depth_memory_state_dict"])
-        if "depth_memory_head_state_dict" in d:
-            w = d["depth_memory_head_state_dict"]["weight"]
-            mem_head = torch.nn.Linear(w.shape[1], w.shape[0])
-            mem_head.load_state_dict(d["depth_memory_head_state_dict"])
+        raise ValueError("evaluate: the checkpoint has no 'vision' record (vision['encoder'], the depth encoder's hyperparameters): "
+                         "pass encoder=DepthEncoder(...) with the shapes it was trained with" if parts.checkpoint is not None else
+                         "evaluate: a VisionActorCritic needs its depth encoder (encoder=...): nobody else can hand it a latent")
     if enc.latent_dim + (mem.hidden if mem is not None else 0) != ac.depth_latent_dim:
         raise ValueError(f"evaluate: the encoder's latent has {enc.latent_dim} columns" + (f" and the memory {mem.hidden}" if mem is not None else "") +
                          f", the actor reads {ac.depth_latent_dim}")
-    enc = enc.to(device).eval()
-    head = head.to(device).eval() if head is not None else None
+    for module in (enc, parts.depth_head, mem, parts.memory_head):
+        if module is not None:
+            module.to(device).eval()
     if getattr(cam, "encoder", None) is not enc:
         cam.attach_encoder(enc)
-    if mem is not None:
-        mem = mem.to(device).eval()
-        if getattr(cam, "memory", None) is not mem:
-            cam.attach_memory(mem)
-        found["memory"], found["memory_head"] = mem, (mem_head.to(device).eval() if mem_head is not None else None)
-    return cam, enc, head
-
-
-def _map_parts(env, ac, found, sensor):
-    """the sensor of a map policy, its map rows attached: the caller's `sensor` first, then the runner's, then env.sensors["depth"], and
-    for a checkpoint without any of them the sensor, map and odometry rebuilt from its record and added to the env as "depth" """
-    record = found.get("map_policy") or {}
-    cam = sensor if sensor is not None else found.get("sensor")
-    if cam is None:
-        cam = getattr(env, "sensors", {}).get("depth")
-    if cam is None and record.get("sensor") is not None:
-        cam = env.add_sensor("depth", sensors.from_spec(env, record["sensor"]))
-    if cam is None or getattr(cam, "map", None) is None:
-        raise ValueError("evaluate: a map policy needs a sensor with an elevation map (sensor=..., env.add_sensor('depth', ...), or a checkpoint "
-                         "whose 'map_policy' record names one)")
-    channels = tuple(record.get("channels") or (getattr(cam, "map_channels", None) or ("height",)))
-    if getattr(cam, "map_channels", None) != channels:
-        cam.attach_map_rows(channels)
-    if cam.map_rows().shape[1] != ac.depth_latent_dim:
-        raise ValueError(f"evaluate: the map rows have {cam.map_rows().shape[1]} columns, the actor reads {ac.depth_latent_dim}")
+    if mem is not None and getattr(cam, "memory", None) is not mem:
+        cam.attach_memory(mem)
     return cam
 
 
@@ -717,7 +629,7 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     `blind=True` feeds zeros instead.  `vision_metrics` become columns of the result: "depth_influence" = the L2 distance of the action
     mean from the mean with a zero latent (one more policy forward per step), "scan_error" = the mean square error of `depth_head` (the
     encoder's auxiliary head) against the height scan of the privileged observation; a metric whose inputs are missing is dropped.
-    A policy trained with a depth memory (the runner's alg.memory, or the checkpoint's vision["memory"] record) gets the memory rebuilt and
+    A policy trained with a depth memory (the runner's alg.memory, or the memory record of the checkpoint) gets the memory rebuilt and
     attached behind the encoder and reads cam.memory_rows(), [z | h]; "memory_scan_error" is the memory head's error on h.
     With an elevation map on the sensor (envs.sensors.ElevationMap, cam.attach_map) two more metrics are accepted when NAMED (they are in
     no default): "map_scan_error" = the mean square, over the scan points, of the map's scan in observation units
@@ -725,42 +637,31 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     privileged observation -- the same units as scan_error and memory_scan_error -- and "map_coverage" = the mean of cam.map_known().
     `camera_jitter` (a vision policy only): the per-episode mount error of the camera (envs.sensors.MountJitter) -- "trained": what the
     checkpoint's record of the sensor says (a runner's camera stays as it is); None: the nominal mount; a MountJitter: that one, to
-    measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's
-    conventions["camera_jitter"].
+    measure robustness beyond the trained range.  The choice and the ranges in force are written to the result's conventions["camera_jitter"].
     `camera_instrument` (a vision policy only): the same choice for the per-episode error of the camera's own constants
     (envs.sensors.InstrumentError: latency, noise gain, depth-scale error, field of view), written to conventions["camera_instrument"].
     `camera_stereo` (likewise): the same choice for the stereo pair's artefacts -- occlusion shadows, minimum range, depth-edge holes and
     fattening (envs.sensors.StereoArtifacts) --, written to conventions["camera_stereo"].
-    A map policy (a MapOnPolicyRunner, its checkpoint -- recognised by its "map_policy" record, from which sensor, map and rows are rebuilt
-    when the env has none -- or a VisionActorCritic with a `sensor` whose map rows are attached and no encoder anywhere) reads
-    cam.map_rows(); `blind=True` feeds zeros; "depth_influence" is the action distance against zero rows and "map_scan_error" the mean
-    square of the rows' height block minus the privileged one.
+    A map policy (a MapOnPolicyRunner, its checkpoint -- from whose record sensor, map and rows are rebuilt when the env has none -- or a
+    bare module that learn/policy_io.py's policy_parts takes for one) reads cam.map_rows(); `blind=True` feeds zeros; "depth_influence" is
+    the action distance against zero rows and "map_scan_error" the mean square of the rows' height block minus the privileged one.
     `odometry` (a sensor with an elevation map only): the dead-reckoning error of the pose the map is placed with
     (envs.sensors.OdometryError) -- "trained", None or an OdometryError, as camera_jitter; written to conventions["odometry"].  With
     odometry map_scan_error uses the ESTIMATED base height, the one the map has.
-    A scan policy (a ScanOnPolicyRunner or its checkpoint, recognised by its "scan_policy" record) reads the scan block of the live
-    privileged observation; `blind=True` feeds zeros; only the base columns are reported and `vision_metrics` other than the default
-    or an empty tuple are refused: there is nothing of a camera to measure.
+    A scan policy (a ScanOnPolicyRunner or its checkpoint) reads the scan block of the live privileged observation; `blind=True` feeds
+    zeros; only the base columns are reported and `vision_metrics` other than the default or an empty tuple are refused: no camera to measure.
     `frames` (None: nothing of this is allocated, launched or written): {"dir": ..., "every": K, "envs": (...), "size": (W, H), "shading":
     Shading | None} -- what a person watches (FrameWriter): a shaded chase camera (envs.sensors.chase_camera, lsim_sensor_shade) follows
     the chosen envs and `dir/e<env>_s<step>.ppm` is written every K steps, plus one `e<env>.gif` per env at the end when PIL can be
     imported; the Evaluator's `frames_written` lists the files.  The result is the one without frames."""
     from .fused_policy import PackedHimPolicy
     dev = env.buf["rew"].device
-    found = {}
-    ac = _actor_critic(env, policy, dev, found)
-    ac.eval()
-    is_vision = hasattr(ac, "depth_latent_dim")
-    is_scan = is_vision and "scan_policy" in found
-    is_map = is_vision and not is_scan and ("map_policy" in found or (encoder is None and found.get("encoder") is None and found.get("checkpoint") is None and
-                                                      getattr(sensor, "map_channels", None) is not None))
-    if is_vision and not is_scan:
-        if is_map:
-            cam, head = _map_parts(env, ac, found, sensor), None
-        else:
-            cam, _, head = _vision_parts(env, ac, found, sensor, encoder, depth_head, dev)
-        d = found.get("checkpoint") or {}
-        record = (d.get("map_policy") or d.get("vision") or {}).get("sensor")        # the checkpoint's record of the sensor; None: a runner, a module
+    parts = policy_parts(env, policy, dev, sensor=sensor, encoder=encoder, depth_head=depth_head)      # the caller's own parts come first
+    ac, kind = parts.actor_critic.eval(), parts.kind
+    if kind in ("vision", "map"):
+        cam = _policy_sensor(env, parts, dev)
+        # a checkpoint's record of the sensor; a runner's or a module's sensor carries what it was trained with, and stays as it is
+        record = parts.sensor_record if parts.checkpoint is not None else None
         conventions = _sensor_options(cam, record, camera_jitter, camera_instrument, odometry, camera_stereo)
     ev = evaluator or Evaluator(env, group_by, trace_envs, trace_capacity if trace_capacity is not None else max(int(steps), 1))
     frames = None if frames is None else FrameWriter(env, frames)
@@ -770,16 +671,16 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
         cmd = cmd.expand(env.num_envs, 3).contiguous() if cmd.dim() == 1 else cmd.contiguous()
         if tuple(cmd.shape) != (env.num_envs, 3):
             raise ValueError(f"commands must be (vx, vy, yaw) or [num_envs, 3], got shape {tuple(cmd.shape)}")
-    if not is_vision:
+    if kind == "him":
         return _run(env, ac, ev, steps, cmd, fused, PackedHimPolicy, frames=frames)
-    if is_scan:
-        return _evaluate_scan(env, ac, ev, steps, cmd, fused, found["scan_policy"], bool(blind), tuple(vision_metrics or ()),
+    if kind == "scan":
+        return _evaluate_scan(env, ac, ev, steps, cmd, fused, parts.scan, bool(blind), tuple(vision_metrics or ()),
                               explicit=vision_metrics is not VISION_METRICS, frames=frames)
     ev.extra_conventions.update(conventions)
-    if is_map:
+    if kind == "map":
         return _evaluate_map(env, ac, ev, steps, cmd, fused, cam, bool(blind), tuple(vision_metrics or ()), frames=frames)
-    return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, bool(blind), tuple(vision_metrics or ()),
-                            memory=found.get("memory"), memory_head=found.get("memory_head"), frames=frames)
+    return _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, parts.depth_head, bool(blind), tuple(vision_metrics or ()),
+                            memory=parts.memory, memory_head=parts.memory_head, frames=frames)
 
 
 def format_table(result):
@@ -887,12 +788,11 @@ def main(argv=None):
     cfg.env.num_envs = a.envs
     env = LeggedRobot(cfg, sim_device=a.device, seed=a.seed)
     env.reset()
-    d = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
-    record = d.get("vision") or d.get("map_policy") or {}
+    kind, record = policy_record(torch.load(a.checkpoint, map_location="cpu", weights_only=False))
     if record.get("sensor") is not None:       # a vision or a map policy's checkpoint names the camera it was trained with
         env.add_sensor("depth", sensors.from_spec(env, record["sensor"]))
     named = any(str(v).startswith("--vision-metrics") for v in (sys.argv[1:] if argv is None else argv))
-    if "scan_policy" in d and not named:       # a scan policy has no vision metrics: the option's default means none, a named one is refused
+    if kind == "scan" and not named:       # a scan policy has no vision metrics: the option's default means none, a named one is refused
         a.vision_metrics = ()
     ev = evaluate(env, a.checkpoint, a.steps, commands=a.commands, group_by=a.group_by, trace_envs=a.trace_envs, blind=a.blind,
                   vision_metrics=a.vision_metrics, camera_jitter=a.camera_jitter, camera_instrument=a.camera_instrument, odometry=a.odometry,

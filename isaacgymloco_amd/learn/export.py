@@ -62,13 +62,13 @@ class PolicyExporterHIM(nn.Module):
         return path
 
 
-class PolicyExporterVision(nn.Module):
+class PolicyExporterVision(PolicyExporterHIM):
     """A VisionActorCritic with its DepthEncoder and the constants of the sensor it was trained with.  `sensor`: a RaySensor with a
-    SensorModel (envs/sensors.py) or its spec() (a checkpoint's vision["sensor"]).  Attributes clip_lo, clip_hi, offset, gain (lsim_sensor_capture's
+    SensorModel (envs/sensors.py) or its spec() (a checkpoint's record of it, learn/policy_io.py's sensor_record).  Attributes clip_lo, clip_hi, offset, gain (lsim_sensor_capture's
     clip and normalisation), period, latency, frames (how the robot must pace and delay its captures), height, width."""
 
     def __init__(self, actor_critic, encoder, sensor):
-        super().__init__()
+        super().__init__(actor_critic)          # actor, estimator and their two widths
         from ..envs.sensors import SensorModel
         spec = sensor if isinstance(sensor, dict) else sensor.spec()
         m = spec.get("model")
@@ -78,10 +78,6 @@ class PolicyExporterVision(nn.Module):
         if encoder.frames != model.frames or encoder.latent_dim + self._memory_columns() != actor_critic.depth_latent_dim:
             raise ValueError(f"PolicyExporterVision: the encoder reads {encoder.frames} frames and writes {encoder.latent_dim} columns; the sensor "
                              f"keeps {model.frames}, the actor reads {actor_critic.depth_latent_dim}")
-        self.actor = plain_sequential(actor_critic.actor)
-        self.estimator = plain_sequential(actor_critic.estimator.encoder)
-        self.num_one_step_obs = int(actor_critic.num_one_step_obs)
-        self.num_enc_out = int(actor_critic.estimator.num_latent) + 3
         self.conv1, self.conv2, self.fc = copy.deepcopy(encoder.conv1).cpu(), copy.deepcopy(encoder.conv2).cpu(), copy.deepcopy(encoder.fc).cpu()
         for p in self.parameters():
             p.requires_grad_(False)
@@ -127,13 +123,6 @@ class PolicyExporterVision(nn.Module):
 
     def forward(self, obs_history: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
         return self.act(obs_history, self.encode(frames))
-
-    def export(self, path):
-        os.makedirs(path, exist_ok=True)
-        path = os.path.join(path, "policy.pt")
-        self.to("cpu")
-        torch.jit.script(self).save(path)
-        return path
 
 
 class PolicyExporterVisionMemory(PolicyExporterVision):

@@ -12,10 +12,7 @@ the heights around the robot in the units of the privileged height scan, and opt
 VisionActorCritic with depth_latent_dim = channels * P, the same storage and the same fused launch carry "some [N, dim] rows behind the
 latent" from the rollout to the update, and a HIM policy warm-starts it through load_him_state_dict.  There is no encoder, no auxiliary loss
 and no snapshot: the rows are the map's, and no gradient goes anywhere but into the actor-critic.  One rank only."""
-import copy
-
-from .runner import _ALGOS, _POLICIES
-from .vision import ActorRowsPPO, ActorRowsRunner, VisionActorCritic
+from .vision import ActorRowsPPO, ActorRowsRunner
 
 CHANNELS = (("height",), ("height", "known"), ("height", "confidence"))
 
@@ -34,7 +31,7 @@ class MapOnPolicyRunner(ActorRowsRunner):
     policy["depth_latent_dim"] is set here.  The fused policy launch takes a first actor layer of at most 272 columns: 187 points with
     one channel (251 columns), and with two channels a map of at most 104 points (ElevationMap(points=...), e.g. 11 x 9)."""
 
-    map_policy = True
+    policy_kind = "map"
 
     def __init__(self, env, train_cfg, sensor="depth", channels=("height",), log_dir=None, device="cpu", fast=None):
         cam = env.sensors[sensor] if isinstance(sensor, str) else sensor
@@ -47,18 +44,11 @@ class MapOnPolicyRunner(ActorRowsRunner):
             raise ValueError("MapOnPolicyRunner: the channel 'confidence' needs a map with a fusion (ElevationMap(fusion=MapFusion(...)))")
         dim = len(channels) * int(cam.map_scan().shape[1])
         self._check_first_layer(env, **{"map rows": dim})
-        _POLICIES["VisionActorCritic"], _ALGOS["MapPPO"] = VisionActorCritic, MapPPO
-        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
-        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "MapPPO"
-        cfg["policy"]["depth_latent_dim"] = dim
         self.sensor, self.channels = cam, channels
-        super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
+        super().__init__(env, self._rows_cfg(train_cfg, MapPPO, dim), log_dir=log_dir, device=device, fast=fast)
         cam.attach_map_rows(channels)       # behind the parent's env.reset(): the sensor has captured, so every env's rows are built now
         self.alg.latent_source = cam.map_rows
 
-    def _extra_checkpoint_state(self):
-        out = super()._extra_checkpoint_state()
+    def policy_record(self):
         cam = self.sensor                   # what the policy was trained with: learn/evaluate.py rebuilds sensor, map, odometry and rows from it
-        out["map_policy"] = {"sensor": cam.spec() if hasattr(cam, "spec") else None, "channels": list(self.channels),
-                             "dim": int(self.alg.actor_critic.depth_latent_dim)}
-        return out
+        return {"sensor": cam.spec() if hasattr(cam, "spec") else None, "channels": list(self.channels), "dim": int(self.alg.actor_critic.depth_latent_dim)}

@@ -44,6 +44,7 @@ class HIMOnPolicyRunner:
         self.graphs = None
         env.reset()
 
+    policy_kind = "him"   # what the actor reads beside the observation (learn/policy_io.py KINDS); the runners of learn/vision.py name theirs
     graphs = None   # GraphedRollout once enable_graphs() succeeded (subclasses with their own __init__ inherit the default)
     _pending_draw_counter = None   # a checkpoint's sampler counter loaded before enable_graphs()
 

@@ -11,11 +11,8 @@ does, trained so that a camera student can be regressed onto its action means.  
 LSIM_NUM_HEIGHT_PTS, the same storage and the same fused launch, whose extra segment takes a row pitch (lsim_policy_extra.ld =
 num_priv_obs), so NO launch and no buffer is added -- the rows are what the critic's blocks of the same launch stage anyway.  There is no
 sensor, no encoder and no auxiliary loss, and a HIM policy warm-starts it through load_him_state_dict.  One rank only."""
-import copy
-
 from .. import abi
-from .runner import _ALGOS, _POLICIES
-from .vision import ActorRowsPPO, ActorRowsRunner, VisionActorCritic, height_scan_block
+from .vision import ActorRowsPPO, ActorRowsRunner, height_scan_block
 
 
 class ScanPPO(ActorRowsPPO):
@@ -29,7 +26,7 @@ class ScanOnPolicyRunner(ActorRowsRunner):
     block would hold zeros).  train_cfg is HIMOnPolicyRunner's; policy["depth_latent_dim"] is set here.  The first actor layer reads
     45 + 3 + 16 + 187 = 251 columns, inside the fused policy launch's 272."""
 
-    scan_policy = True
+    policy_kind = "scan"
     sensor = None           # VisionRollout's: the rows come from the env, not from a sensor
 
     def __init__(self, env, train_cfg, log_dir=None, device="cpu", fast=None):
@@ -39,22 +36,14 @@ class ScanOnPolicyRunner(ActorRowsRunner):
         if width != abi.DEFINES["LSIM_NUM_HEIGHT_PTS"]:
             raise ValueError(f"ScanOnPolicyRunner: the height scan has {width} points, the layout {abi.DEFINES['LSIM_NUM_HEIGHT_PTS']}")
         self._check_first_layer(env, **{"scan points": width})
-        _POLICIES["VisionActorCritic"], _ALGOS["ScanPPO"] = VisionActorCritic, ScanPPO
-        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
-        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", "ScanPPO"
-        cfg["policy"]["depth_latent_dim"] = width
         self.scan = (off, width)
-        super().__init__(env, cfg, log_dir=log_dir, device=device, fast=fast)
+        super().__init__(env, self._rows_cfg(train_cfg, ScanPPO, width), log_dir=log_dir, device=device, fast=fast)
         self.alg.latent_source = lambda: env.privileged_obs_buf[:, off:off + width]
 
     def load_him_state_dict(self, sd):
         """warm start from a HIM policy: the scan columns of the first actor layer are zero (VisionActorCritic.load_him_state_dict)"""
         return self.alg.actor_critic.load_him_state_dict(sd)
 
-    def scan_record(self):
+    def policy_record(self):
+        """the checkpoint's record, and what learn/policy_io.py reads of a runner: learn/evaluate.py and learn/distill.py find the rows from it"""
         return {"offset": int(self.scan[0]), "width": int(self.scan[1]), "dim": int(self.alg.actor_critic.depth_latent_dim)}
-
-    def _extra_checkpoint_state(self):
-        out = super()._extra_checkpoint_state()
-        out["scan_policy"] = self.scan_record()     # learn/evaluate.py and learn/distill.py find the rows from it
-        return out

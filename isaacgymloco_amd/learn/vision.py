@@ -32,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import abi, lib
+from . import policy_io
 from .fused_policy import PackedHimPolicy
 from .graph_rollout import GraphedRollout
 from .him_ppo import HIMPPO
@@ -560,7 +561,23 @@ class VisionRollout(GraphedRollout):
 
 
 class ActorRowsRunner(HIMOnPolicyRunner):
-    """what the runners of a policy whose actor reads a sensor's rows (`self.sensor`) share: the fused policy launch's width limit and rollout"""
+    """what the runners of a policy whose actor reads a sensor's rows (`self.sensor`) share: the train_cfg, the fused policy launch's width
+    limit and rollout, and the checkpoint's parts (learn/policy_io.py).  A subclass sets `policy_kind` and has policy_record()."""
+
+    def _rows_cfg(self, train_cfg, learner, depth_latent_dim):
+        """a copy of `train_cfg` for a VisionActorCritic that reads `depth_latent_dim` more columns, trained by `learner`, both registered"""
+        _POLICIES["VisionActorCritic"], _ALGOS[learner.__name__] = VisionActorCritic, learner
+        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
+        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", learner.__name__
+        cfg["policy"]["depth_latent_dim"] = int(depth_latent_dim)
+        return cfg
+
+    def _extra_checkpoint_state(self):
+        return {**super()._extra_checkpoint_state(), **policy_io.checkpoint_state(self.alg, self.policy_kind, self.policy_record())}
+
+    def _load_extra_checkpoint_state(self, d):
+        super()._load_extra_checkpoint_state(d)
+        policy_io.load_checkpoint_state(self.alg, d)
 
     def _check_first_layer(self, env, **widths):
         first = env.num_one_step_obs + 3 + 16 + sum(widths.values())
@@ -585,6 +602,7 @@ class VisionOnPolicyRunner(ActorRowsRunner):
     algorithm["e2e_learning_rate"] (default aux_learning_rate); one rank, and no gradient through the memory.  Without it, likewise,
     nothing is allocated, launched, stored or saved that was not before."""
 
+    policy_kind = "vision"
     algorithm_class = None      # the learner: VisionPPO; learn/distill.py's DistillRunner names VisionDistill
 
     def __init__(self, env, train_cfg, sensor="depth", encoder=None, log_dir=None, device="cpu", fast=None, memory=None, end_to_end=False):
@@ -598,11 +616,6 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             from .depth_encoder import DepthEncoder
             encoder = DepthEncoder(cam.height, cam.width, cam.model.frames)
         encoder = encoder.to(device)
-        learner = self.algorithm_class or VisionPPO
-        _POLICIES["VisionActorCritic"], _ALGOS[learner.__name__] = VisionActorCritic, learner
-        cfg = {k: copy.copy(v) for k, v in train_cfg.items()}
-        cfg["runner"]["policy_class_name"], cfg["runner"]["algorithm_class_name"] = "VisionActorCritic", learner.__name__
-        cfg["policy"]["depth_latent_dim"] = encoder.latent_dim
         if memory is not None and memory is not False:
             from .depth_memory import DepthMemory
             memory = DepthMemory(encoder.latent_dim, env.num_one_step_obs, 64) if memory is True else memory
@@ -610,10 +623,10 @@ class VisionOnPolicyRunner(ActorRowsRunner):
                 raise ValueError(f"VisionOnPolicyRunner: the memory reads {memory.latent_dim} latent and {memory.proprio_dim} observation columns, "
                                  f"the encoder writes {encoder.latent_dim} and a one-step observation has {env.num_one_step_obs}")
             memory = memory.to(device)
-            cfg["policy"]["depth_latent_dim"] = encoder.latent_dim + memory.hidden
             self._check_first_layer(env, latent=encoder.latent_dim, hidden=memory.hidden)
         else:
             memory = None
+        cfg = self._rows_cfg(train_cfg, self.algorithm_class or VisionPPO, encoder.latent_dim + (memory.hidden if memory is not None else 0))
         if end_to_end:
             if getattr(cam, "env_stride", 1) != 1:
                 raise ValueError("VisionOnPolicyRunner: end_to_end needs a sensor that renders every env (env_stride == 1)")
@@ -631,40 +644,19 @@ class VisionOnPolicyRunner(ActorRowsRunner):
             cam.attach_frames_log(self.num_steps_per_env, capacity=self.alg.e2e_capacity, row_of=self.alg.storage.frame_row)
             self.alg.attach_frame_log(cam)
 
-    def _extra_checkpoint_state(self):
-        out = super()._extra_checkpoint_state()
-        alg = self.alg
-        out.update(depth_encoder_state_dict=alg.encoder.state_dict(), depth_head_state_dict=alg.depth_head.state_dict(),
-                   depth_optimizer_state_dict=alg.aux_optimizer.state_dict())
-        cam = getattr(self, "sensor", None)           # what the policy was trained with: learn/evaluate.py and the exporter rebuild the pipeline from it
-        out["vision"] = {"encoder": alg.encoder.config(), "sensor": cam.spec() if hasattr(cam, "spec") else None,
-                         "latent_dim": int(alg.actor_critic.depth_latent_dim)}
+    def policy_record(self):
+        """what the policy was trained with: learn/policy_io.py rebuilds encoder and memory from it, learn/evaluate.py the camera"""
+        alg, cam = self.alg, getattr(self, "sensor", None)
+        record = {"encoder": alg.encoder.config(), "sensor": cam.spec() if hasattr(cam, "spec") else None,
+                  "latent_dim": int(alg.actor_critic.depth_latent_dim)}
         if alg.memory is not None:
-            out.update(depth_memory_state_dict=alg.memory.state_dict(), depth_memory_head_state_dict=alg.memory_head.state_dict(),
-                       depth_memory_optimizer_state_dict=alg.memory_optimizer.state_dict())
-            out["vision"]["memory"] = alg.memory.config()
+            record["memory"] = alg.memory.config()
         if alg.end_to_end:
-            out["depth_e2e_optimizer_state_dict"] = alg.e2e_optimizer.state_dict()
-            out["vision"]["end_to_end"] = {"epochs": alg.e2e_epochs, "learning_rate": alg.e2e_learning_rate,
-                                           "capacity": int(self.sensor.frames_log().shape[0])}
-        return out
+            record["end_to_end"] = {"epochs": alg.e2e_epochs, "learning_rate": alg.e2e_learning_rate, "capacity": int(self.sensor.frames_log().shape[0])}
+        return record
 
     def export(self, path):
         """learn/export.py: export_policy_as_jit of this runner's actor-critic, encoder and sensor; `path` is a directory"""
         from .export import export_policy_as_jit
         self.get_inference_policy()
         return export_policy_as_jit(self.alg.actor_critic, path, encoder=self.alg.encoder, sensor=self.sensor, memory=self.alg.memory)
-
-    def _load_extra_checkpoint_state(self, d):
-        super()._load_extra_checkpoint_state(d)
-        alg = self.alg
-        if "depth_encoder_state_dict" in d:
-            alg.encoder.load_state_dict(d["depth_encoder_state_dict"])
-            alg.depth_head.load_state_dict(d["depth_head_state_dict"])
-            alg.aux_optimizer.load_state_dict(d["depth_optimizer_state_dict"])
-        if alg.memory is not None and "depth_memory_state_dict" in d:
-            alg.memory.load_state_dict(d["depth_memory_state_dict"])
-            alg.memory_head.load_state_dict(d["depth_memory_head_state_dict"])
-            alg.memory_optimizer.load_state_dict(d["depth_memory_optimizer_state_dict"])
-        if alg.end_to_end and "depth_e2e_optimizer_state_dict" in d:
-            alg.e2e_optimizer.load_state_dict(d["depth_e2e_optimizer_state_dict"])

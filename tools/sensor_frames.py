@@ -4,7 +4,7 @@
     python tools/sensor_frames.py --out frames/ [--task aliengo] [--num-envs 64] [--envs 0,1,2] [--steps 50] [--every 10]
                                   [--checkpoint model.pt] [--width 128] [--height 96] [--terrain stairs]
 
-Steps the env under a checkpoint's actor (learn/evaluate.py's loader) or zero actions; every `--every` steps writes, for each chosen env,
+Steps the env under a checkpoint's actor (learn/policy_io.py's loader) or zero actions; every `--every` steps writes, for each chosen env,
 `depth_e<env>_s<step>.npy` (float32 [H, W] z-depth in metres), `labels_e<env>_s<step>.npy` (uint8: 0 nothing, 1 terrain, 2 + b body b) and the
 same two as 8-bit PGM (depth: near = white, far = black; labels: spread over the grey range).  A PGM is a text header plus raw bytes.
 `--map [size=32,resolution=0.0625,source=clean]`: the robot also carries the forward camera of the vision tasks (64 x 48, 0.3 m ahead, pitched
@@ -107,8 +107,8 @@ def main():
     env.reset()
     policy = None
     if a.checkpoint:
-        from isaacgymloco_amd.learn import evaluate
-        policy = evaluate._actor_critic(env, a.checkpoint, "cuda:0").act_inference
+        from isaacgymloco_amd.learn.policy_io import policy_parts
+        policy = policy_parts(env, a.checkpoint, "cuda:0").actor_critic.act_inference
     ids = [int(v) for v in a.envs.split(",")]
     os.makedirs(a.out, exist_ok=True)
     zero = torch.zeros(a.num_envs, 12, device="cuda:0")
