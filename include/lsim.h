@@ -1783,6 +1783,87 @@ typedef struct lsim_elevation_map_cleanup {
  * clear_sigma or end_gap negative or not finite; min_rays < 1. */
 int lsim_elevation_map_cleanup(const lsim_elevation_map_cleanup_t* ec, void* stream);
 
+/* ---- foot scans: heights at a small pattern of points around each of the four feet, read from the true terrain or from an elevation map,
+ * as the rows an actor reads.  ONE launch under the rules of lsim_map_rows (caller's stream, no host synchronisation, raw pointers only,
+ * capturable).  It is STATELESS: no tick, no flags, no due rule -- every visited env (e % env_stride == 0) has its rows rewritten at every
+ * launch; for an env that is not visited NOTHING is written.  It reads `pose`, dof_state, the robot tables, `pattern` and the arrays of its
+ * source, and writes rows, heights, known and state only.  All arithmetic in fp32; a compiler may contract a product and a sum except where
+ * this text says it may not.
+ *
+ * Per visited env e, with (p, q) = pose[e][0:3], [3:7]:
+ * Foot centres, by forward kinematics from `pose` and th_j = dof_state[e][j][0] ONLY (rigid_body_states is not read: its rows are stale for an
+ *   env that reset inside the step).  k = env_robot[e] (NULL: 0) selects robots[k] as in lsim_raycast_bodies; only its `bodies` are read.  The
+ *   recursion is lsim_raycast_bodies', in coordinates relative to p:
+ *     P_0 = 0, Q_0 = q;      body b > 0 with parent a:  P_b = P_a + R(Q_a) joint_pos_b,
+ *     Q_b = Q_a * (joint_axis_b sin(th/2), cos(th/2)), th = th_dof_b, or 0 when dof_b < 0;      (a * b: R(a * b) = R(a) R(b), xyzw; R as in lsim_raycast)
+ *   Foot l = 0..3 is body 4 + 4l:  F_l = P_{4+4l}  (base-relative, world orientation)  and its centre is c_l = p + F_l.  With `pose` pointed at
+ *   lsim_odometry_step's `est` the feet are placed as the robot would place them: its estimated base pose plus its joint encoders.
+ * Points.  pattern [K, 2] holds offsets in the yaw frame of q, 1 <= K <= LSIM_FOOT_SCAN_MAX_POINTS, the same for every foot:
+ *     n = 1 / sqrt(q.z^2 + q.w^2)  (root and quotient correctly rounded);   qy = (0, 0, q.z n, q.w n)       -- lsim_elevation_map's scan frame
+ *     o = R(qy) (pattern[j], 0);      w = ((p.x + F_l.x) + o.x,  (p.y + F_l.y) + o.y)                        point j of foot l
+ * Source LSIM_FOOT_SCAN_TERRAIN: the reference's height sampler (LR:1342-1355), what LSIM_BUF_MEASURED_HEIGHTS is sampled with.
+ *     fx = (w.x + border_size) / horizontal_scale,  fy likewise   (one sum, one correctly rounded IEEE quotient each, NOT contracted)
+ *     (px, py) = (fx, fy) truncated toward zero (NaN: 0; saturating), then clipped to [0, grid_rows - 2] x [0, grid_cols - 2]
+ *     h = vertical_scale * min(g[px][py], g[px + 1][py], g[px][py + 1])       g = height_grid [grid_rows, grid_cols] int16 (LSIM_BUF_HEIGHT_GRID)
+ *     mesh_type == 0 (the plane): h = 0 and height_grid is not read.      known = 1 always.
+ * Source LSIM_FOOT_SCAN_MAP: lsim_elevation_map's lookup, on that map's height / stamp / cell with its size G and res.
+ *     rinv = 1.0f / res, formed ONCE on the host;   (ix, iy) = (floor(w.x * rinv), floor(w.y * rinv))  (a true floor);   the slot as there.
+ *     the slot knows the cell (stamp >= 0 and cell == the packed word):  h = height[e][slot], known = 1
+ *     otherwise -- also when a component of w is not finite or a floor is not inside (-32768, 32768):  h = p.z - unknown_drop, known = 0
+ * Outputs, for i = l * K + j (foot-major, 4 K values per env):
+ *     rows[e * ld + i]         = clamp(((p.z + F_l.z) - z_offset) - h, -1, 1) * scale
+ *                                (one sum, two subtractions in this order, the clamp, one product: nothing a compiler can contract);
+ *                                a difference that is not finite writes 0
+ *     rows[e * ld + 4 K + i]   = known ? 1.0f : 0.0f                                       channels == 2 only
+ *     heights[e * heights_stride + i] = h   and   known[e * known_stride + i] = known      each only when its pointer is given
+ *   Columns >= channels * 4 K of a row are not touched.
+ * Bad env: a non-finite component of pose[e][0:7], a non-finite th_j (any of the twelve), or q.z = q.w = 0.  Its row blocks, heights and known
+ *   are all 0 and state[0] (int64, cumulative) gains 1 per launch.  No NaN is ever written to rows.
+ * NOT BUILT: a confidence at foot points (lsim_map_rows_fused's second block), contact-dependent patterns, the foot's own radius. */
+#define LSIM_FOOT_SCAN_MAX_POINTS 64       /* K: points per foot */
+#define LSIM_FOOT_SCAN_TERRAIN 0           /* source */
+#define LSIM_FOOT_SCAN_MAP 1
+typedef struct lsim_foot_scan {
+    const float* pose;                /* [N,13] root states (the simulator's, or lsim_odometry_step's est); only [e][0:7] is read; 4-byte aligned */
+    const float* dof_state;           /* [N,12,2] simulator buffer, read only; 4-byte aligned */
+    const uint8_t* env_robot;         /* [N] robot index per env, or NULL: robot 0 */
+    const lsim_raycast_robot* robots; /* [num_robots] DEVICE memory: what the launch reads (its `bodies` only) */
+    const lsim_raycast_robot* robots_host;  /* the same bytes in HOST memory: what the argument check reads */
+    const float* pattern;             /* [K,2] offsets around a foot in the base-yaw frame, metres; 4-byte aligned */
+    const int16_t* height_grid;       /* terrain source: [grid_rows,grid_cols] LSIM_BUF_HEIGHT_GRID, 2-byte aligned; may be NULL when mesh_type == 0 */
+    const float* height;              /* map source: lsim_elevation_map_t.height [N,G,G] */
+    const int32_t* stamp;             /* map source: lsim_elevation_map_t.stamp [N,G,G] */
+    const uint32_t* cell;             /* map source: lsim_elevation_map_t.cell [N,G,G] */
+    float* rows;                      /* [N,ld]; 4-byte aligned */
+    float* heights;                   /* [N,heights_stride] or NULL; 4-byte aligned */
+    uint8_t* known;                   /* [N,known_stride] or NULL */
+    void* state;                      /* 1 int64, 8-byte aligned, zeroed by the caller: [0] visits of bad envs */
+    int32_t source;                   /* LSIM_FOOT_SCAN_TERRAIN or LSIM_FOOT_SCAN_MAP */
+    int32_t num_envs, env_stride;     /* N >= 1; every env_stride-th env is visited (>= 1) */
+    int32_t num_robots;               /* 1..LSIM_MAX_ROBOTS; 1 when env_robot == NULL */
+    int32_t num_points;               /* K in 1..LSIM_FOOT_SCAN_MAX_POINTS */
+    int32_t channels;                 /* 1: heights; 2: heights, then known */
+    int32_t ld;                       /* floats between rows of `rows`: >= channels * 4 K */
+    int32_t heights_stride, known_stride;   /* elements between rows: >= 4 K (each ignored when its pointer is NULL) */
+    int32_t mesh_type;                /* terrain source: 0 plane, otherwise the height grid is sampled */
+    int32_t grid_rows, grid_cols;     /* terrain source, mesh_type != 0: >= 2, grid_rows * grid_cols < 2^31 */
+    int32_t size;                     /* map source: G, 16, 32 or 64 */
+    float horizontal_scale, vertical_scale, border_size;   /* terrain source, mesh_type != 0: the config's; the two scales finite and > 0, the border finite */
+    float res;                        /* map source: metres per cell, finite and > 0 */
+    float unknown_drop;               /* map source: finite */
+    float z_offset, scale;            /* finite */
+} lsim_foot_scan_t;
+/* the launch described above.  LSIM_E_INVALID, checked on the host before any launch, nothing written: fs == NULL; pose, dof_state, robots,
+ * robots_host, pattern or rows NULL or not 4-byte aligned; heights given and not 4-byte aligned; state NULL or not 8-byte aligned; source not
+ * one of the two; num_envs < 1; env_stride < 1; num_robots outside 1..LSIM_MAX_ROBOTS, or != 1 with env_robot == NULL; K outside
+ * 1..LSIM_FOOT_SCAN_MAX_POINTS; channels outside 1..2; ld < channels * 4 K; heights given with heights_stride < 4 K; known given with
+ * known_stride < 4 K; z_offset or scale not finite; in robots_host[0..num_robots) a body whose parent / dof is not the tree's
+ * lsim_raycast_bodies accepts or whose joint_pos / joint_axis is not finite (num_prims and prims are not looked at).
+ * Terrain source with mesh_type != 0: height_grid NULL or not 2-byte aligned; grid_rows or grid_cols < 2 or their product >= 2^31;
+ * horizontal_scale or vertical_scale not finite or <= 0; border_size not finite.
+ * Map source: height, stamp or cell NULL or not 4-byte aligned; size not 16, 32 or 64; res not finite or <= 0; unknown_drop not finite. */
+int lsim_foot_scan(const lsim_foot_scan_t* fs, void* stream);
+
 /* ---- depth encoder: a small CNN over a modelled sensor's frame history -> one latent row per env.  FORWARD ONLY (lsim_depth_encode_backward
  * below is its backward pass; isaacgymloco_amd/learn/depth_encoder.py joins the two under autograd).  ONE launch, same rules as lsim_sensor_capture: the caller's stream, no
  * host synchronisation, raw pointers only, so it can be captured in a graph.  It reads `hist` (and episode_length for the due rule), the

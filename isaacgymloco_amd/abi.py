@@ -121,6 +121,7 @@ LsimMapRows = STRUCTS["lsim_map_rows_t"]
 LsimElevationMapFused = STRUCTS["lsim_elevation_map_fused_t"]
 LsimMapRowsFused = STRUCTS["lsim_map_rows_fused_t"]
 LsimElevationMapCleanup = STRUCTS["lsim_elevation_map_cleanup_t"]
+LsimFootScan = STRUCTS["lsim_foot_scan_t"]
 LsimDepthEncoder = STRUCTS["lsim_depth_encoder_t"]
 LsimDepthEncoderBwd = STRUCTS["lsim_depth_encoder_bwd_t"]
 LsimFramesLog = STRUCTS["lsim_frames_log_t"]

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "liblsim.so")
 # three translation units, two flag sets: (source, headers it depends on, extra flags)
 SIM_HEADERS = ["ls_math.h", "ls_shared.h", "ls_physics.h", "ls_post.h", "ls_kernels.h", "ls_api_impl.h", "ls_eval.h", "ls_eval_columns.h", "ls_raycast.h", "ls_raycast_bodies.h",
-               "ls_sensor_model.h", "ls_sensor_mount_jitter.h", "ls_sensor_instrument.h", "ls_sensor_stereo.h", "ls_sensor_shade.h", "ls_elevation_map.h", "ls_odometry.h", "ls_elevation_fuse.h", "ls_elevation_cleanup.h", "ls_depth_encoder.h", "ls_depth_encoder_bwd.h", "ls_depth_memory.h", "ls_frames_log.h"]
+               "ls_sensor_model.h", "ls_sensor_mount_jitter.h", "ls_sensor_instrument.h", "ls_sensor_stereo.h", "ls_sensor_shade.h", "ls_elevation_map.h", "ls_odometry.h", "ls_elevation_fuse.h", "ls_elevation_cleanup.h", "ls_foot_scan.h", "ls_depth_encoder.h", "ls_depth_encoder_bwd.h", "ls_depth_memory.h", "ls_frames_log.h"]
 LEARN_HEADERS = ["ls_math.h", "ls_rollout.h", "ls_learn.h", "ls_gemm.h", "ls_policy.h", "ls_amp.h"]
 DISTILL_HEADERS = ["ls_distill.h"]
 # The simulator kernels' time is their vector instruction count, so ITS flags (SIM_FLAGS) are chosen for that:

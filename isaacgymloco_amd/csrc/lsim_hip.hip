@@ -34,6 +34,7 @@ static void lsbk_prof_free(lsim_sim* s);
 #include "ls_odometry.h"        // the map policy's per-step launches: an estimated pose that drifts (lsim_odometry_step) and the map's scan as actor rows (lsim_map_rows)
 #include "ls_elevation_fuse.h"  // the map with a variance per cell (lsim_elevation_map_fused): a banded mean per capture, a Kalman step over captures; its rows with a confidence (lsim_map_rows_fused)
 #include "ls_elevation_cleanup.h"   // the map's visibility clean-up (lsim_elevation_map_cleanup): cells a capture's rays pass over, well below the held height, are forgotten; between the capture and the map's launch
+#include "ls_foot_scan.h"        // foot scans (lsim_foot_scan): heights at a pattern of points around each foot, feet by forward kinematics, from the terrain or from the map, as actor rows
 #include "ls_depth_encoder.h"    // the depth encoder (lsim_depth_encode): conv - conv - linear over that frame history for the envs that are due, activations in LDS
 #include "ls_depth_encoder_bwd.h"    // its backward pass (lsim_depth_encode_backward): the parameter gradients, activations recomputed per sample in LDS
 #include "ls_depth_memory.h"    // the depth memory (lsim_depth_memory_step, lsim_gru_sequence_forward / _backward): a GRU cell over the latent, one tile of 16 envs per workgroup

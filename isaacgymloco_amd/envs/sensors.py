@@ -518,6 +518,152 @@ def parse_odometry(text):
     return parse_option(OdometryError, text)
 
 
+class FootScan(_Option):
+    """Where lsim_foot_scan samples around each of the four feet (include/lsim.h states every formula): rings of `counts[i]` points at
+    `radii[i]` metres, the first point of every ring on the base-yaw frame's x axis and every other ring turned by half a step, plus the
+    foot's own centre when `centre` -- K = sum(counts) + centre points per foot, at most LSIM_FOOT_SCAN_MAX_POINTS, the same pattern for
+    every foot, turned with the base's yaw only.  `pattern` (a list of [x, y] offsets in metres) takes the place of the rings; radii,
+    counts and centre are then recorded as None.  `z_offset`: subtracted from the foot's height before the terrain's is (a foot's
+    centre stands its own radius above the ground it touches).  The feet are placed by forward kinematics from the pose the source is
+    given and the joint positions, so a map placed by odometry is sampled where the robot believes its feet to be.
+    The defaults are STATED GUESSES, fitted to nothing: three rings of 6, 8 and 10 points at 6, 12 and 20 cm (one, two and three cells of
+    the default 6.25 cm map) and the centre, K = 25.  No training run long enough to show that foot scans help on stairs has been made."""
+    FIELDS = ("radii", "counts", "centre", "z_offset", "pattern")
+    TEXT = {"radii": (float, "/", range(1, 9)), "counts": (int, "/", range(1, 9)), "centre": _flag, "z_offset": float}
+
+    def __init__(self, radii=(0.06, 0.12, 0.20), counts=(6, 8, 10), centre=True, z_offset=0.0, pattern=None):
+        self.z_offset = float(z_offset)
+        if not math.isfinite(self.z_offset):
+            raise ValueError(f"FootScan: z_offset is finite, got {z_offset}")
+        if pattern is not None:
+            self.radii = self.counts = self.centre = None
+            self._pattern = [[float(x), float(y)] for x, y in np.asarray(pattern, dtype=np.float64).reshape(-1, 2)]
+        else:
+            as_tuple = lambda v, conv: tuple(conv(x) for x in (v if isinstance(v, (tuple, list)) else (v,)))
+            self.radii, self.counts, self.centre = as_tuple(radii, float), as_tuple(counts, int), bool(centre)
+            if len(self.radii) != len(self.counts) or any(not (math.isfinite(r) and r > 0.0) for r in self.radii) or any(c < 1 for c in self.counts):
+                raise ValueError(f"FootScan: as many radii (finite, > 0) as counts (>= 1), got {radii}, {counts}")
+            pts = [[0.0, 0.0]] if self.centre else []
+            for i, (r, c) in enumerate(zip(self.radii, self.counts)):
+                pts += [[r * math.cos(2.0 * math.pi * (k + 0.5 * (i % 2)) / c), r * math.sin(2.0 * math.pi * (k + 0.5 * (i % 2)) / c)] for k in range(c)]
+            self._pattern = pts
+        if not 1 <= len(self._pattern) <= abi.DEFINES["LSIM_FOOT_SCAN_MAX_POINTS"] or not np.isfinite(np.asarray(self._pattern)).all():
+            raise ValueError(f"FootScan: 1 to {abi.DEFINES['LSIM_FOOT_SCAN_MAX_POINTS']} finite points per foot, got {len(self._pattern)}")
+
+    def pattern(self):
+        """the [K, 2] table of offsets in the base-yaw frame, metres"""
+        return [list(p) for p in self._pattern]
+
+    @property
+    def num_points(self):
+        return len(self._pattern)
+
+    def record(self):
+        out = super().record()
+        out["pattern"] = self.pattern() if self.radii is None else None
+        return out
+
+    def _shown(self, k):
+        return repr(getattr(self, k)) if k != "pattern" else ("None" if self.radii is not None else f"<{self.num_points} points>")
+
+
+def parse_foot_scan(text):
+    """FootScan of 'radii=0.06/0.12,counts=6/8,centre=1,z_offset=0.02' (any subset; '' or 'default': the defaults), or the same with ':'
+    for '=' and no other ',' -- 'radii:0.06/0.12,counts:6/8' -- the form it takes behind 'foot_scan=' in a tool's option text"""
+    if text in ("1", "", "default"):
+        return FootScan()
+    return parse_option(FootScan, ",".join(item.replace(":", "=", 1) if "=" not in item else item for item in text.split(",")))
+
+
+FOOT_CHANNELS = (("foot_height",), ("foot_height", "foot_known"))
+
+
+def _robot_tables(env):
+    """([lsim_raycast_robot per robot of the instance], body names): given by the env (the test doubles), else built from its config"""
+    from ..robots.model import build_sensor_table
+    tables = getattr(env, "sensor_tables", None)
+    if tables is None:
+        robots = getattr(env, "robots", None)
+        assets = [env.cfg.asset] if robots is None else [config.robot_cfg(env.cfg, k).asset for k in range(len(robots))]
+        built = [build_sensor_table(a) for a in assets]
+        tables = ([t for t, _ in built], built[0][1])
+    return list(tables[0]), list(tables[1])
+
+
+def _foot_scan_struct(env, api, fs_opt, channels, pose, dev, held):
+    """an lsim_foot_scan_t with everything but its source filled -- the robot tables on the device and the host, the pattern, rows [N, C * 4K],
+    heights [N, 4K], known [N, 4K] and state, all kept in `held` -- for the sensor's stage "foot_rows" and for TerrainFootScan"""
+    if not isinstance(fs_opt, FootScan):
+        raise TypeError(f"foot_scan is a FootScan, got {type(fs_opt).__name__}")
+    lib.entry(api, "lsim_foot_scan", "the foot scans")
+    N, K, C = int(env.num_envs), fs_opt.num_points, len(channels)
+    tabs, _ = _robot_tables(env)
+    host = (abi.LsimRaycastRobot * len(tabs))(*tabs)
+    zeros = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+    held.update(robots_host=host, robots=torch.from_numpy(np.frombuffer(host, dtype=np.uint8).copy()).to(dev),
+                pattern=torch.tensor(fs_opt.pattern(), dtype=torch.float32, device=dev).reshape(K, 2).contiguous(),
+                rows=zeros(N, C * 4 * K), heights=zeros(N, 4 * K), known=zeros(N, 4 * K, dtype=torch.uint8), state=zeros(1, dtype=torch.int64))
+    fs = abi.LsimFootScan()
+    fs.pose, fs.dof_state = pose.data_ptr(), env.dof_state.data_ptr()
+    fs.robots, fs.robots_host, fs.num_robots = held["robots"].data_ptr(), ctypes.addressof(host), len(tabs)
+    if len(tabs) > 1:
+        held["env_robot"] = env.robot_ids.to(device=dev, dtype=torch.uint8).contiguous()
+        fs.env_robot = held["env_robot"].data_ptr()
+    fs.pattern, fs.rows, fs.heights, fs.known, fs.state = (held[k].data_ptr() for k in ("pattern", "rows", "heights", "known", "state"))
+    fs.num_envs, fs.env_stride, fs.num_points, fs.channels = N, 1, K, C
+    fs.ld, fs.heights_stride, fs.known_stride = C * 4 * K, 4 * K, 4 * K
+    fs.z_offset, fs.scale = fs_opt.z_offset, float(env.lcfg.obs_scale_height)
+    return fs
+
+
+class TerrainFootScan:
+    """The TRUE foot scan: lsim_foot_scan with the terrain as its source -- the reference's own height sampler at FootScan's pattern around
+    every foot, the feet placed by forward kinematics from env.root_states and env.dof_state.  The input of a privileged teacher
+    (learn/scan_policy.py) and the truth an evaluation measures a map's foot rows against.  `channels`: ("foot_height",) or
+    ("foot_height", "foot_known") -- the terrain knows every point, the second block is all ones and exists so that the rows have the
+    layout of a map's.  Add it with env.add_sensor(name, TerrainFootScan(env, FootScan())): every step then ends with its one launch;
+    it launches once when created, so the rows exist before the first step.  `rows()` is the live [N, channels * 4K] tensor in observation
+    units (clip(foot z - z_offset - h, -1, 1) * obs_scales.height_measurements), `heights()` the live [N, 4, K] terrain heights,
+    `known()` the live uint8 [N, 4, K]."""
+    model = None            # env.add_sensor: nothing to refresh, no noise stream
+
+    def __init__(self, env, foot_scan=None, channels=("foot_height",), api=None):
+        self.env, self._api = env, api if api is not None else env._L
+        self.foot_scan, self.channels = FootScan() if foot_scan is None else foot_scan, tuple(channels)
+        if self.channels not in FOOT_CHANNELS:
+            raise ValueError(f"TerrainFootScan: channels is ('foot_height',) or ('foot_height', 'foot_known'), got {self.channels}")
+        dev = env.root_states.device
+        self._held = {}
+        fs = self.struct = _foot_scan_struct(env, self._api, self.foot_scan, self.channels, env.root_states, dev, self._held)
+        lc = env.lcfg
+        fs.source, fs.mesh_type = abi.DEFINES["LSIM_FOOT_SCAN_TERRAIN"], int(lc.mesh_type)
+        if fs.mesh_type != 0:
+            fs.height_grid, fs.grid_rows, fs.grid_cols = env.height_samples.data_ptr(), int(lc.grid_rows), int(lc.grid_cols)
+            fs.horizontal_scale, fs.vertical_scale, fs.border_size = lc.horizontal_scale, lc.vertical_scale, lc.border_size
+        self._cuda = bool(env.root_states.is_cuda)
+        self.update()
+
+    def update(self, stream=None, tick=None, flags=0):
+        """the one launch, on `stream` (default: the env's); tick and flags are a modelled sensor's and mean nothing here.  Returns rows()"""
+        stream = stream if stream is not None else (self.env._stream() if self._cuda else None)
+        lib.check(self._api.lsim_foot_scan(ctypes.byref(self.struct), stream), what="lsim_foot_scan")
+        return self._held["rows"]
+
+    def rows(self):
+        return self._held["rows"]
+
+    def heights(self):
+        return self._held["heights"].unflatten(1, (4, self.foot_scan.num_points))
+
+    def known(self):
+        return self._held["known"].unflatten(1, (4, self.foot_scan.num_points))
+
+    @property
+    def nonfinite(self):
+        """0-d device tensor: visits of envs whose pose or joints were not finite (their rows are zeros); must stay 0"""
+        return self._held["state"][0]
+
+
 def parse_elevation_map(text):
     """ElevationMap of 'size=32,resolution=0.0625,source=noisy,max_range=3,unknown_drop=0.4' (any subset; '' or 'default': the defaults):
     the text the tools take"""
@@ -528,11 +674,12 @@ _ORDER = ("rays", "odometry", "mount_jitter", "instrument", "capture", "map", "m
 # launched directly behind the stage named, in this order: the stereo artefacts rewrite what the capture wrote before anybody reads it
 # (_ORDER keeps the tuple a test pins); a training buffer's stage is no part of the instrument; the shading reads what the rays just wrote;
 # the map's clean-up tests the capture as the artefacts left it against the map of the earlier captures, ahead of the map's own launch
-_BEHIND = {"shade": "rays", "stereo": "capture", "frames_log": "capture", "map_cleanup": "capture"}
+# the foot rows read the map its launch just wrote
+_BEHIND = {"shade": "rays", "stereo": "capture", "frames_log": "capture", "map_cleanup": "capture", "foot_rows": "map"}
 _LAUNCH_ORDER = tuple(n for o in _ORDER for n in (o,) + tuple(k for k, v in _BEHIND.items() if v == o))
-_DEPENDENTS = {"map": ("odometry", "map_rows", "map_cleanup"), "encoder": ("memory", "frames_log")}                                # who goes with whom
+_DEPENDENTS = {"map": ("odometry", "map_rows", "map_cleanup", "foot_rows"), "encoder": ("memory", "frames_log")}                                # who goes with whom
 _ABSENT = {"instrument": "instrument error (instrument=InstrumentError(...))", "odometry": "odometry (attach_map(m, odometry=OdometryError(...)))",
-           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "shade": "shading (shading=Shading(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)",
+           "stereo": "stereo artefacts (stereo=StereoArtifacts(...))", "shade": "shading (shading=Shading(...))", "map": "elevation map (attach_map)", "map_rows": "map rows (attach_map_rows)", "foot_rows": "foot rows (attach_map_rows(('foot_height',), foot_scan=FootScan()))",
            "map_cleanup": "map clean-up (ElevationMap(cleanup=MapCleanup(...)))", "encoder": "encoder (attach_encoder)",
            "memory": "memory (attach_memory)", "frames_log": "frame log (attach_frames_log)"}
 _FILL_ALL = abi.DEFINES["LSIM_SENSOR_FILL_ALL"]
@@ -605,7 +752,9 @@ class RaySensor:
     outermost that is launched: `ray_struct` and `bodies_struct` (None in the terrain-only form) are views into it.  `out_rows` /
     `label_rows`: the padded tensors `out` / `labels()` are views of; `history()`: the raw frame history."""
 
-    mount_jitter, instrument, map, odometry, map_channels = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "map_rows"))
+    mount_jitter, instrument, map, odometry, foot_scan = (_option(n) for n in ("mount_jitter", "instrument", "map", "odometry", "foot_rows"))
+    map_channels = property(lambda self: self._stages["foot_rows"].channels if "foot_rows" in self._stages else getattr(self._stages.get("map_rows"), "option", None),
+                            doc="the channels of the attached map rows or foot rows (only one of the two is attached at a time); None without either")
     encoder, memory, stereo, shading, map_cleanup = _option("encoder"), _option("memory"), _option("stereo"), _option("shade"), _option("map_cleanup")
 
     def __init__(self, env, dirs, mount_pos=(0.0, 0.0, 0.0), mount_quat=(0.0, 0.0, 0.0, 1.0), near=0.0, far=10.0, scale=None, env_stride=1, api=None,
@@ -942,15 +1091,8 @@ class RaySensor:
 
     def _setup_bodies(self, rb, ignore_bodies, labels, dev):
         """the lsim_raycast_bodies fields around the ray struct: one sensor table per robot of the instance, on the device and (for the argument check) on the host"""
-        from ..robots.model import build_sensor_table
         env = self.env
-        tables = getattr(env, "sensor_tables", None)          # (tables, body names) given by the env (the test doubles), else from its config
-        if tables is None:
-            robots = getattr(env, "robots", None)
-            assets = [env.cfg.asset] if robots is None else [config.robot_cfg(env.cfg, k).asset for k in range(len(robots))]
-            built = [build_sensor_table(a) for a in assets]
-            tables = ([t for t, _ in built], built[0][1])
-        tabs, self.body_names = list(tables[0]), list(tables[1])
+        tabs, self.body_names = _robot_tables(env)
         if not self.see_robot:
             tabs = [abi.LsimRaycastRobot.from_buffer_copy(t) for t in tabs]
             for t in tabs:
@@ -1173,18 +1315,30 @@ class RaySensor:
         """live [N, 12] tensor: row e = {dx, dy, dz, h, scale, yaw_bias, z_bias, 0, prev_x, prev_y, 0, 0} of env e (lsim.h)"""
         return self._need("odometry").buffers["odo"]
 
-    def attach_map_rows(self, channels=("height",), var_ref=None):
+    def attach_map_rows(self, channels=("height",), var_ref=None, foot_scan=None):
         """from now on the map's launch of every update() / refresh() is followed by lsim_map_rows on the same stream: `map_rows()` is the
         live [N, len(channels) * P] tensor of the map's scan as an actor reads it -- ("height",): clip(map_pose z - 0.5 - scan, -1, 1) *
         obs_scales.height_measurements, the privileged height scan's expression; ("height", "known"): then map_known() as 0 / 1.  Needs
         an attached map; builds the rows once now when the sensor has captured before.  None: detach and free.
         ("height", "confidence") (lsim_map_rows_fused; needs a map with a fusion): then var_ref / (var_ref + map_variance()) where the
-        map knows the point and 0 where it does not -- 1/2 at a variance of `var_ref` (None: 16 times the fusion's var_floor)."""
+        map knows the point and 0 where it does not -- 1/2 at a variance of `var_ref` (None: 16 times the fusion's var_floor).
+        ("foot_height",) and ("foot_height", "foot_known") with `foot_scan` (a FootScan; None: its defaults): the stage "foot_rows",
+        lsim_foot_scan directly behind the map's launch -- the map read at FootScan's pattern around each foot, the feet placed by forward
+        kinematics from map_pose() and the joint positions; map_rows() then is the live [N, channels * 4K] tensor of
+        clip(foot z - z_offset - height, -1, 1) * obs_scales.height_measurements, foot-major, then the known block; foot_heights() and
+        foot_known() are [N, 4, K].  Foot rows and scan rows are not both attached: attaching one detaches the other.  A confidence at
+        foot points is not built."""
         if channels is None:
+            self._drop("foot_rows")
             return self._drop("map_rows")
         channels = tuple(channels)
+        if channels in FOOT_CHANNELS:
+            return self._attach_foot_rows(channels, FootScan() if foot_scan is None else foot_scan, var_ref)
+        if foot_scan is not None:
+            raise ValueError(f"attach_map_rows: foot_scan belongs to the channels ('foot_height',) and ('foot_height', 'foot_known'), got {channels}")
         if channels not in (("height",), ("height", "known"), ("height", "confidence")):
-            raise ValueError(f"attach_map_rows: channels is ('height',), ('height', 'known') or ('height', 'confidence'), got {channels}")
+            raise ValueError(f"attach_map_rows: channels is ('height',), ('height', 'known'), ('height', 'confidence'), ('foot_height',) or "
+                             f"('foot_height', 'foot_known'), got {channels}")
         em, mp = self._need("map").struct, self._need("map").buffers
         fused = channels[-1] == "confidence"
         if fused and self.map.fusion is None:
@@ -1205,14 +1359,49 @@ class RaySensor:
         mr.scan, mr.known, mr.pose, mr.rows = mp["scan"].data_ptr(), mp["known"].data_ptr(), self.map_pose().data_ptr(), rows.data_ptr()
         mr.num_points, mr.channels, mr.scan_stride, mr.known_stride, mr.ld = P, C, int(em.scan_stride), int(em.known_stride), C * P
         mr.z_offset, mr.scale = 0.5, float(self.env.lcfg.obs_scale_height)
+        self._drop("foot_rows")             # foot rows and scan rows are not both attached
         stage = self._attach(Stage(self, "map_rows", entry, mr, {"rows": rows}, channels, outer=mf))
         if self.tick >= 0:
             stage.launch(self.tick, _FILL_ALL)
         return rows
 
+    def _attach_foot_rows(self, channels, foot_scan, var_ref):
+        """the stage "foot_rows": lsim_foot_scan with the map as its source, directly behind the map's launch, on the map's arrays and the
+        pose the map is given; the scan rows, if attached, leave"""
+        if var_ref is not None:
+            raise ValueError("attach_map_rows: var_ref belongs to the channel 'confidence'; a confidence at foot points is not built")
+        em, mp = self._need("map").struct, self._need("map").buffers
+        held = {}
+        fs = _foot_scan_struct(self.env, self._api, foot_scan, channels, self.map_pose(), self.out_rows.device, held)
+        fs.source = abi.DEFINES["LSIM_FOOT_SCAN_MAP"]
+        fs.height, fs.stamp, fs.cell = mp["height"].data_ptr(), mp["stamp"].data_ptr(), mp["cell"].data_ptr()
+        fs.size, fs.res, fs.unknown_drop = int(em.size), float(em.res), float(em.unknown_drop)
+        self._drop("map_rows")              # foot rows and scan rows are not both attached
+        stage = self._attach(Stage(self, "foot_rows", "lsim_foot_scan", fs, held, foot_scan))
+        stage.channels = channels
+        if self.tick >= 0:
+            stage.launch(self.tick, _FILL_ALL)
+        return held["rows"]
+
     def map_rows(self):
-        """live [N, channels * P] tensor: the rows lsim_map_rows writes (attach_map_rows)"""
+        """live [N, channels * P] tensor: the rows lsim_map_rows writes (attach_map_rows) -- or, with foot channels, the [N, channels * 4K]
+        rows lsim_foot_scan writes"""
+        if "foot_rows" in self._stages:
+            return self._stages["foot_rows"].buffers["rows"]
         return self._need("map_rows").buffers["rows"]
+
+    def foot_heights(self):
+        """live [N, 4, K] tensor: the map's height at every foot point; where it knows none, the given base height minus unknown_drop"""
+        return self._need("foot_rows").buffers["heights"].unflatten(1, (4, self.foot_scan.num_points))
+
+    def foot_known(self):
+        """live uint8 [N, 4, K] tensor: 1 where foot_heights() is a height the map holds"""
+        return self._need("foot_rows").buffers["known"].unflatten(1, (4, self.foot_scan.num_points))
+
+    @property
+    def foot_nonfinite(self):
+        """0-d device tensor: visits of envs whose given pose or joints were not finite (their foot rows are zeros); must stay 0"""
+        return self._need("foot_rows").buffers["state"][0]
 
     def map_scan(self):
         """live [N, P] tensor: the map's height at every scan point; where it knows none, the base height minus unknown_drop"""
@@ -1399,8 +1588,8 @@ class RaySensor:
         without one) and the mount: {"pos", "quat"} when all envs share it, {robot name: pose} when it is constant per robot, else None.
         With a mount jitter the mount recorded is the nominal one and "mount_jitter" holds the MountJitter's {"pos", "rot_deg"}; without
         one there is no such key.  Likewise "instrument" holds an InstrumentError's record, "map" an attached ElevationMap's,
-        "odometry" the OdometryError the map was attached with, "stereo" a StereoArtifacts' and "shading" a Shading's, each absent
-        without one."""
+        "odometry" the OdometryError the map was attached with, "stereo" a StereoArtifacts', "shading" a Shading's and "foot_scan" the FootScan of attached foot
+        rows, each absent without one."""
         out = dict(self.kind)
         out["dirs"] = self.dirs.cpu().tolist()
         out["scale"] = None if self.scale is None else self.scale.cpu().tolist()
@@ -1419,7 +1608,7 @@ class RaySensor:
         else:
             out["mount"] = None
         for key, option in (("mount_jitter", self.mount_jitter), ("instrument", self.instrument), ("map", self.map), ("odometry", self.odometry), ("stereo", self.stereo),
-                            ("shading", self.shading)):
+                            ("shading", self.shading), ("foot_scan", self.foot_scan)):
             if option is not None:
                 out[key] = option.record()
         return out
@@ -1492,13 +1681,15 @@ _KIND_KEYS = {"rays": (), "camera": ("width", "height"), "lidar": ("channels", "
 
 
 def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter="spec", instrument="spec", elevation_map="spec", odometry="spec", stereo="spec",
-              shading="spec"):
+              shading="spec", foot_scan="spec"):
     """the sensor RaySensor.spec() describes, on `env`: same rays, range, model constants and body mask.  `mount_pos` / `mount_quat` (as
     RaySensor's) override the recorded mount; a recorded mount of None (it varied per env) without the override raises, and so does a
     per-robot mount that lacks one of the env's robots (RaySensor's own check).  `mount_jitter`: "spec" rebuilds the recorded MountJitter
     (none when the record has none); None or a MountJitter takes its place.  `instrument`: the same for the recorded InstrumentError, `elevation_map` for the recorded ElevationMap (attached to the new sensor),
     `odometry` for the OdometryError that map is attached with (without a map it has nothing to act on), `stereo` for the recorded
-    StereoArtifacts, `shading` for the recorded Shading."""
+    StereoArtifacts, `shading` for the recorded Shading, `foot_scan` for the recorded FootScan: with one (and a map) the new sensor gets the
+    one-channel foot rows, attach_map_rows(("foot_height",), foot_scan=...) -- the record holds the pattern, not the channels, which are a
+    policy's; whoever wants the known block attaches again."""
     mount = spec.get("mount")
     if mount is not None and "pos" not in mount:
         pos, quat = {n: p["pos"] for n, p in mount.items()}, {n: p["quat"] for n, p in mount.items()}
@@ -1522,6 +1713,7 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
     mount_jitter, instrument = option("mount_jitter", mount_jitter, MountJitter, "mount_jitter"), option("instrument", instrument, InstrumentError, "instrument")
     elevation_map, odometry = option("elevation_map", elevation_map, ElevationMap, "map"), option("odometry", odometry, OdometryError, "odometry")
     stereo, shading = option("stereo", stereo, StereoArtifacts, "stereo"), option("shading", shading, Shading, "shading")
+    foot_scan = option("foot_scan", foot_scan, FootScan, "foot_scan")
     kind = spec.get("kind", "rays") if spec.get("kind") in _KIND_KEYS else "rays"
     dirs, scale = np.asarray(spec["dirs"], dtype=np.float32), None if spec["scale"] is None else np.asarray(spec["scale"], dtype=np.float32)
     options = dict(env_stride=spec["env_stride"], api=api, see_robot=spec["see_robot"], ignore_bodies=tuple(spec["ignore_bodies"]), labels=spec["labels"],
@@ -1532,5 +1724,7 @@ def from_spec(env, spec, mount_pos=None, mount_quat=None, api=None, mount_jitter
         sensor = RaySensor(env, dirs, pos, quat, spec["near"], spec["far"], scale=scale, kind={"kind": kind, **{k: spec[k] for k in _KIND_KEYS[kind]}}, **options)
     if elevation_map is not None:
         sensor.attach_map(elevation_map, odometry=odometry)
+        if foot_scan is not None:
+            sensor.attach_map_rows(FOOT_CHANNELS[0], foot_scan=foot_scan)
     return sensor
 

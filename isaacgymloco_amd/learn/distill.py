@@ -214,6 +214,9 @@ class DistillRunner(VisionOnPolicyRunner):
         if teacher is None:
             raise ValueError("DistillRunner: teacher= (a ScanOnPolicyRunner, its checkpoint's path or the loaded checkpoint)")
         sd, record = _teacher_checkpoint(teacher, device)
+        if record.get("foot_scan") is not None:
+            raise NotImplementedError("DistillRunner: the teacher reads true foot scans (ScanOnPolicyRunner(foot_scan=...)); distillation from a "
+                                      "foot-scan teacher is not built (the student's warm start and the labels assume the height-scan block)")
         off, width = height_scan_block(env.cfg)
         if (int(record["offset"]), int(record["width"])) != (off, width) or int(record["dim"]) != width:
             raise ValueError(f"DistillRunner: the teacher read the scan block {record}, the env's is offset {off}, width {width}")

@@ -289,8 +289,12 @@ def _policy_sensor(env, parts, device):
             raise ValueError("evaluate: a map policy needs a sensor with an elevation map (sensor=..., env.add_sensor('depth', ...), or a checkpoint "
                              "whose 'map_policy' record names one)")
         channels = tuple(parts.channels or getattr(cam, "map_channels", None) or ("height",))
-        if getattr(cam, "map_channels", None) != channels:
-            cam.attach_map_rows(channels)
+        feet = None
+        if channels in sensors.FOOT_CHANNELS:           # the pattern the policy was trained with: the record's, else what the sensor carries
+            recorded = (parts.sensor_record or {}).get("foot_scan")
+            feet = sensors.FootScan(**recorded) if recorded is not None else getattr(cam, "foot_scan", None) or sensors.FootScan()
+        if getattr(cam, "map_channels", None) != channels or getattr(cam, "foot_scan", None) != feet:
+            cam.attach_map_rows(channels, foot_scan=feet)
         if cam.map_rows().shape[1] != ac.depth_latent_dim:
             raise ValueError(f"evaluate: the map rows have {cam.map_rows().shape[1]} columns, the actor reads {ac.depth_latent_dim}")
         return cam
@@ -349,10 +353,10 @@ def _sensor_options(cam, record, camera_jitter, camera_instrument, odometry, cam
         return apply
 
     def reattached(want):
-        channels = getattr(cam, "map_channels", None)
+        channels, feet = getattr(cam, "map_channels", None), getattr(cam, "foot_scan", None)
         cam.attach_map(cam.map, odometry=want)
         if channels is not None:
-            cam.attach_map_rows(channels)
+            cam.attach_map_rows(channels, foot_scan=feet)
 
     out = {"camera_jitter": _sensor_option(cam, record, camera_jitter, sensors.MountJitter, "mount_jitter", "camera_jitter", redrawn(cam.set_mount_jitter)),
            "camera_instrument": _sensor_option(cam, record, camera_instrument, sensors.InstrumentError, "instrument", "camera_instrument", redrawn(cam.set_instrument))}
@@ -398,6 +402,7 @@ VISION_METRICS = ("depth_influence", "scan_error", "memory_scan_error")
 MAP_METRICS = ("map_scan_error", "map_coverage")        # accepted when named and the sensor carries an elevation map; never a default
 MAP_FUSION_METRICS = ("map_variance", "map_z2")         # likewise, of a map with a fusion (envs.sensors.MapFusion); dropped without one
 MAP_CLEANUP_METRICS = ("map_cleared",)                  # likewise, of a map with a clean-up (envs.sensors.MapCleanup); dropped without one
+FOOT_METRICS = ("foot_scan_error", "foot_scan_coverage")       # likewise, of a sensor with foot rows (envs.sensors.FootScan); dropped without them
 
 
 def _map_fusion_columns(env, cam):
@@ -563,7 +568,7 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
     from .vision import PackedVisionPolicy
     metrics = list(metrics)
     for m in metrics:
-        if m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS:
+        if m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS + FOOT_METRICS:
             raise ValueError(f"unknown vision metric {m!r}: 'depth_influence' or 'scan_error' (with a depth memory also 'memory_scan_error', "
                              f"with an elevation map also 'map_scan_error' and 'map_coverage', with a fused one also 'map_variance' and 'map_z2', with a clean-up also 'map_cleared')")
     has_map = getattr(cam, "map", None) is not None
@@ -581,8 +586,25 @@ def _evaluate_vision(env, ac, ev, steps, cmd, fused, cam, head, blind, metrics, 
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
     columns.update(_map_cleanup_columns(env, cam))
+    columns.update(_foot_columns(env, cam, metrics))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.latent if memory is None else cam.memory_rows, blind,
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
+
+
+def _foot_columns(env, cam, metrics):
+    """the columns of FOOT_METRICS for a sensor with foot rows ({} without them: the metrics are dropped).  "foot_scan_error": the mean
+    square, over the 4K points, of the height block of cam.map_rows() minus the same block of a terrain-source twin (sensors.TerrainFootScan,
+    same pattern, z_offset and scale) placed with the TRUE pose -- observation units, so with odometry the placement error of the feet
+    and of the map is inside it.  The twin is created only when the metric is named and launched once per step from the column itself;
+    it is no sensor of the env.  "foot_scan_coverage": the mean of cam.foot_known()."""
+    feet = getattr(cam, "foot_scan", None)
+    if feet is None:
+        return {}
+    columns = {"foot_scan_coverage": lambda a, a0, live, priv: cam.foot_known().to(torch.float32).mean(dim=(1, 2))}
+    if "foot_scan_error" in metrics:
+        twin, K4 = sensors.TerrainFootScan(env, feet, sensors.FOOT_CHANNELS[0], api=cam._api), 4 * feet.num_points
+        columns["foot_scan_error"] = lambda a, a0, live, priv: (cam.map_rows()[:, :K4] - twin.update()[:, :K4]).square().mean(dim=1)
+    return columns
 
 
 def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics, frames=None):
@@ -591,13 +613,14 @@ def _evaluate_map(env, ac, ev, steps, cmd, fused, cam, blind, metrics, frames=No
     "map_coverage"; the encoder's and the memory's are dropped"""
     from .vision import PackedVisionPolicy
     P, scan = int(cam.map_scan().shape[1]), _scan_block(env)
-    needs = {"map_scan_error": scan is not None and scan[1] == P}
+    needs = {"map_scan_error": scan is not None and scan[1] == P and getattr(cam, "foot_scan", None) is None}        # foot rows are no scan block
     columns = {
         "depth_influence": _influence(blind),
         "map_scan_error": lambda a, a0, live, priv: (live[:, :P] - priv[:, scan[0]:scan[0] + scan[1]]).square().mean(dim=1),
         "map_coverage": lambda a, a0, live, priv: cam.map_known().to(torch.float32).mean(dim=1)}
     columns.update(_map_fusion_columns(env, cam))
     columns.update(_map_cleanup_columns(env, cam))
+    columns.update(_foot_columns(env, cam, metrics))
     return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, cam.map_rows, blind,
                 [(m, columns[m]) for m in metrics if m in columns and needs.get(m, True)], frames=frames)
 
@@ -610,6 +633,16 @@ def _evaluate_scan(env, ac, ev, steps, cmd, fused, record, blind, metrics, expli
     if explicit and metrics:
         raise ValueError(f"evaluate: a scan policy reads the privileged height scan itself -- it has no sensor, encoder or map, so no vision "
                          f"metrics; got {tuple(metrics)} (pass vision_metrics=())")
+    if record.get("foot_scan") is not None:         # the teacher on true foot scans: its rows are a TerrainFootScan's, rebuilt from the record
+        feet, channels = sensors.FootScan(**record["foot_scan"]), tuple(record.get("channels") or sensors.FOOT_CHANNELS[0])
+        have = env.sensors.get("foot_scan")
+        if have is None:
+            have = env.add_sensor("foot_scan", sensors.TerrainFootScan(env, feet, channels))
+        elif not isinstance(have, sensors.TerrainFootScan) or have.foot_scan != feet or have.channels != channels:
+            raise ValueError("evaluate: env.sensors['foot_scan'] is not the TerrainFootScan the scan policy's record names")
+        if have.rows().shape[1] != ac.depth_latent_dim:
+            raise ValueError(f"evaluate: the foot rows have {have.rows().shape[1]} columns, the actor reads {ac.depth_latent_dim}")
+        return _run(env, ac, ev, steps, cmd, fused, PackedVisionPolicy, have.rows, blind, frames=frames)
     off, width = height_scan_block(env.cfg)
     if (int(record.get("offset", off)), int(record.get("width", width))) != (off, width) or width != ac.depth_latent_dim:
         raise ValueError(f"evaluate: the scan policy read the block {record}, the env's is offset {off}, width {width}; the actor reads {ac.depth_latent_dim}")
@@ -648,6 +681,11 @@ def evaluate(env, policy, steps, commands=None, group_by=("robot", "type", "leve
     `odometry` (a sensor with an elevation map only): the dead-reckoning error of the pose the map is placed with
     (envs.sensors.OdometryError) -- "trained", None or an OdometryError, as camera_jitter; written to conventions["odometry"].  With
     odometry map_scan_error uses the ESTIMATED base height, the one the map has.
+    With foot rows on the sensor (cam.attach_map_rows(("foot_height",), foot_scan=FootScan()); a map policy trained on them has them
+    rebuilt from its record) two more metrics are accepted when NAMED: "foot_scan_error" = the mean square of the rows' height block minus
+    the same block sampled from the true terrain at the true pose (_foot_columns), and "foot_scan_coverage" = the mean of cam.foot_known();
+    "map_scan_error" is dropped for such a policy.  A scan policy trained on true foot scans (ScanOnPolicyRunner(foot_scan=...)) reads a
+    sensors.TerrainFootScan rebuilt from its record.
     A scan policy (a ScanOnPolicyRunner or its checkpoint) reads the scan block of the live privileged observation; `blind=True` feeds
     zeros; only the base columns are reported and `vision_metrics` other than the default or an empty tuple are refused: no camera to measure.
     `frames` (None: nothing of this is allocated, launched or written): {"dir": ..., "every": K, "envs": (...), "size": (W, H), "shading":
@@ -757,9 +795,9 @@ def parse_args(argv=None):
             ap.error("--commands takes vx,vy,yaw")
     a.group_by = tuple(g for g in a.group_by.split(",") if g)
     a.vision_metrics = tuple(m for m in a.vision_metrics.split(",") if m)
-    if any(m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS for m in a.vision_metrics):
+    if any(m not in VISION_METRICS + MAP_METRICS + MAP_FUSION_METRICS + MAP_CLEANUP_METRICS + FOOT_METRICS for m in a.vision_metrics):
         ap.error(f"--vision-metrics: 'depth_influence', 'scan_error', 'memory_scan_error', 'map_scan_error' and / or 'map_coverage', got {a.vision_metrics}"
-                 " (a map with a fusion also has 'map_variance' and 'map_z2', one with a clean-up 'map_cleared')")
+                 " (a map with a fusion also has 'map_variance' and 'map_z2', one with a clean-up 'map_cleared', a sensor with foot rows 'foot_scan_error' and 'foot_scan_coverage')")
     try:
         group_mask(a.group_by)
     except ValueError as exc:

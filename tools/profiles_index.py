@@ -80,6 +80,7 @@ STANDALONE = {"pmc_traffic.json": ("the PMC record bench.py matches (task, envs,
               "sensor_stereo_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --stereo default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_stereo` alone (`stereo_us`, `stereo_all_due_us`) next to the capture alone on the same ticks (`capture_us`, `capture_all_due_us`), `update()` without and with the option, the share of a whole capture's pixels the stage rewrites; `counts`: `stereo_counts()` of 64 envs on stairs over 30 steps; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.21'),
               "elevation_map_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_elevation_map` alone over the same ticks (1 env in 5 due) and with every env due, `update()` with both; `bench.py` alternating with the parent's tree", '7.15'),
               "elevation_cleanup_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy[,fusion=default],cleanup=default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_elevation_map_cleanup` alone at period 5 staggered and with every env due next to `lsim_elevation_map` / `lsim_elevation_map_fused` and the capture on the same ticks, `update()` with and without the option; the map, capture and `update()` lines without the option and `bench.py`, alternating with the parent's tree", '7.23'),
+              "foot_scan_time.json": ("`tools/raycast_time.py --foot-scan --iters 50 --warmup 5 --repeats 5`, N = 4096, K = 25, the see-robot 64 × 48 camera at period 5 staggered with a 32 × 32 map on flat ground and stairs, HIP events, five alternating repetitions: `lsim_foot_scan` alone with the map and with the terrain as its source next to `lsim_map_rows`, `lsim_elevation_map` and the capture, `update()` with foot rows and with the parent's scan rows", '7.25'),
               "elevation_fuse_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,fusion=default`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_elevation_map_fused` (`map_us`, `map_all_due_us`) next to `lsim_elevation_map` of the same map on the same ticks (`plain_map_us`, `plain_map_all_due_us`), `update()` with the fused launch; `error_columns`: `evaluate`'s map columns for the plain and the fused map on 64 envs on stairs, same seeds; `bench_pairs`: `bench.py --steps 1000 --warmup 100` alternating with the parent's tree", '7.20'),
               "map_policy_time.json": ("`tools/raycast_time.py --model period=5,stagger=1,latency=1,frames=2,noise=0.01:0.002,dropout=0.02 --map size=32,resolution=0.0625,source=noisy --odometry scale=0.02,yaw_per_m=0.01,z_per_m=0.01,noise=0.005:0.002:0.002 --map-rows 2`, N = 4096, the see-robot 64 × 48 camera on flat ground and stairs, HIP events, five alternating repetitions: `lsim_sensor_capture`, `lsim_odometry_step` alone, `lsim_map_rows` alone and the torch statement of the same rows, `update()` with odometry, capture, map and rows; `bench.py` alternating with the parent's tree", '7.16'),
               "sensor_options_refactor_ab.json": ("parent commit against the commit that gave the sensor options one record, one text grammar and one resolver, `learn/evaluate.py` one step loop and `MapPPO` a base class of its own: `evaluate(...).result()` of a HIM, a vision (with and without memory) and a map policy under every form of `blind`, `camera_jitter`, `camera_instrument` and `odometry`, on the emulated env and on the device (equal), then a 500-step `evaluate()` at N = 4096 and `bench.py --gpus 1 --steps 1000 --warmup 100` in three alternating pairs each, with the parent's run-to-run spread, and the code lines of the four files", "7.16"),

@@ -56,6 +56,13 @@ viewer's case: env 0 alone, 50 times the iterations): `rays_us` = lsim_raycast_b
 `shade_plain_us` = the same launch without LSIM_SHADE_SHADOWS, `update_us` = the pair as update() runs it; `shade_over_rays` their ratio;
 `lit_share` / `shadowed_share` = the share of the drawn pixels that face the sun lit and dark.  `--parent-lib PATH` (a liblsim.so built from
 the parent commit) also times that library's lsim_raycast_bodies on the same struct in the same loops: `rays_parent_us`.
+`--foot-scan` (or `--foot-scan radii:0.06/0.12,counts:6/8`, sensors.parse_foot_scan; a measurement of its own, written to
+profiles/foot_scan_time.json unless --out names another file; --model defaults to period=5,stagger=1 and --map to size=32): the 64 x 48
+camera with a map, per terrain, in one process and alternating `--repeats` times, each with its median and range: `capture_us` and `map_us` =
+the capture and the map's launch alone over whole periods; `map_rows_us` = lsim_map_rows (two channels, 187 points) of a second camera
+that carries the parent's chain; `foot_scan_map_us` = lsim_foot_scan alone with the map as its source (two channels, 4 K points per env);
+`foot_scan_terrain_us` = the same launch with the terrain as its source (sensors.TerrainFootScan); `update_us` / `update_parent_us` =
+update() of the camera with foot rows and of the one with scan rows, as a step runs them.
 The torch restatement of the same walk ("what a user had to do before") was not written: `torch_us` is null.  Prints one JSON line."""
 import argparse
 import ctypes
@@ -365,6 +372,49 @@ def measure_map_policy(n, terrain, iters, warmup, model, emap, odometry, channel
     return out
 
 
+def measure_foot_scan(n, terrain, iters, warmup, model, emap, feet, repeats):
+    """the --foot-scan measurement (module docstring)"""
+    cfg = C.aliengo_cfg()
+    cfg.env.num_envs = n
+    cfg.terrain.terrain_proportions = [1.0, 0.0, 0.0, 0.0, 0.0, 0.0] if terrain == "flat" else [0.0, 0.0, 0.0, 0.0, 0.5, 0.5]
+    env = LeggedRobot(cfg, sim_device="cuda:0", seed=1)
+    env.reset()
+    zero = torch.zeros(n, 12, device="cuda:0")
+    for _ in range(20):
+        env.step_device(zero)
+    env.episode_length_buf[:] = 20               # nobody is fresh inside the timed loops
+    torch.cuda.synchronize()
+    cams = []
+    for channels, kw in ((("foot_height", "foot_known"), {"foot_scan": feet}), (("height", "known"), {})):       # this tree's chain, and the parent's
+        cam = sensors.depth_camera(env, 64, 48, 87.0, mount_pos=(0.3, 0.0, 0.05), pitch_deg=30.0, near=0.05, far=5.0, see_robot=True, labels=True, model=model)
+        cam.refresh(tick=0)
+        cam.attach_map(emap)
+        cam.attach_map_rows(channels, **kw)
+        cams.append(cam)
+    cam, parent = cams
+    truth = sensors.TerrainFootScan(env, feet, ("foot_height", "foot_known"))
+    whole = max(model.period, iters // model.period * model.period)
+    rows = {k: [] for k in ("capture_us", "map_us", "map_rows_us", "foot_scan_map_us", "foot_scan_terrain_us", "update_us", "update_parent_us")}
+    for _ in range(repeats):
+        rows["capture_us"].append(timed_ticks(cam.stage("capture"), whole, warmup))
+        rows["map_us"].append(timed_ticks(cam.stage("map"), whole, warmup))
+        rows["map_rows_us"].append(timed(lambda: parent.stage("map_rows").launch(0, 0), whole, warmup))
+        rows["foot_scan_map_us"].append(timed(lambda: cam.stage("foot_rows").launch(0, 0), whole, warmup))
+        rows["foot_scan_terrain_us"].append(timed(truth.update, whole, warmup))
+        rows["update_parent_us"].append(timed_ticks(parent, whole, warmup))
+        rows["update_us"].append(timed_ticks(cam, whole, warmup))
+    K = feet.num_points
+    out = {"num_envs": n, "terrain": terrain, "rays": cam.num_rays, "points_per_foot": K, "points": 4 * K * n, "columns": int(cam.map_rows().shape[1]),
+           "scan_points": int(parent.stage("map").struct.num_points), "coverage": float(cam.foot_known().float().mean().item()),
+           "error_ms": float((cam.map_rows()[:, :4 * K] - truth.rows()[:, :4 * K]).square().mean().item())}
+    for k, v in rows.items():
+        out[k], out[k + "_range"], out[k + "_all"] = sorted(v)[len(v) // 2], [min(v), max(v)], v
+    out["foot_scan_over_map_rows"] = out["foot_scan_map_us"] / out["map_rows_us"]
+    out["foot_scan_over_map"] = out["foot_scan_map_us"] / out["map_us"]
+    out["nonfinite"] = int(cam.nonfinite_rays.item()) + int(cam.map_nonfinite.item()) + int(cam.foot_nonfinite.item()) + int(truth.nonfinite.item())
+    return out
+
+
 def measure_instrument(n, terrain, iters, warmup, model, instrument, repeats):
     """the --instrument measurement (module docstring)"""
     cfg = C.aliengo_cfg()
@@ -499,6 +549,8 @@ def main():
                     "(any subset; 'default'): time lsim_sensor_stereo next to the capture it follows (needs --model)")
     ap.add_argument("--shade", default=None, nargs="?", const="default", help="sun=AZ:EL,ambient=A,shadows=0|1,checker=M,... (any subset; 'default'): time "
                     "lsim_sensor_shade next to the lsim_raycast_bodies it follows, on the 128 x 96 chase camera")
+    ap.add_argument("--foot-scan", default=None, nargs="?", const="default", help="radii:R/R,counts:C/C,centre:0|1,z_offset:Z (any subset; 'default'): time "
+                    "lsim_foot_scan with the map and with the terrain as its source, next to lsim_map_rows and the map's launch")
     ap.add_argument("--parent-lib", default=None, help="with --shade: a liblsim.so of the parent commit, whose lsim_raycast_bodies is timed in the same loops")
     ap.add_argument("--repeats", type=int, default=5, help="--mount-jitter / --instrument / --map / --stereo / --shade: alternating repetitions of every timed loop")
     ap.add_argument("--build-only", action="store_true", help="build the counters variant of the library and exit (no GPU needed)")
@@ -527,6 +579,17 @@ def main():
                "cases": [measure_shade(a.num_envs, t, a.iters, a.warmup, shading, a.repeats, parent) for t in a.terrains.split(",")]}
         line = json.dumps(res)
         with open(a.out or os.path.join(ROOT, "profiles", "sensor_shade_time.json"), "w") as f:
+            f.write(line + "\n")
+        print(line)
+        return
+    if a.foot_scan is not None:
+        model_text = a.model or "period=5,stagger=1"
+        model, emap, feet = parse_model(model_text), sensors.parse_elevation_map(a.map or "size=32"), sensors.parse_foot_scan(a.foot_scan)
+        res = {"tool": "raycast_time --foot-scan", "iters": a.iters, "warmup": a.warmup, "repeats": a.repeats, "device": torch.cuda.get_device_name(0),
+               "camera": "64x48, hfov 87, pitch 30 down, far 5 m, see_robot, labels", "model": model_text, "map": emap.record(), "foot_scan": feet.record(),
+               "cases": [measure_foot_scan(a.num_envs, t, a.iters, a.warmup, model, emap, feet, a.repeats) for t in a.terrains.split(",")]}
+        line = json.dumps(res)
+        with open(a.out or os.path.join(ROOT, "profiles", "foot_scan_time.json"), "w") as f:
             f.write(line + "\n")
         print(line)
         return
